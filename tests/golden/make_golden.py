@@ -34,14 +34,25 @@ def linear_case(name, M, K, N, store_inputs, row_step=1):
     x = torch.rand(M, K, dtype=torch.float16)
     with torch.no_grad():
         y = lin(x)
+        # oneDNN's native fp16 GEMM runs only on CPUs with AVX512-FP16 / AMX-FP16; every other CPU runs ATen's fp32-accumulating
+        # GEMM, which is what oneDNN switched off gives on any CPU.  Where the two round differently, both are kept.
+        with torch.backends.mkldnn.flags(enabled=False):
+            y_f32acc = lin(x)
     w = lin.weight.detach().numpy()
     out = {"y": y.numpy()[::row_step]}  # every row_step-th token row keeps the fixture small
+    native = bool(torch.ops.mkldnn._is_mkldnn_fp16_supported())
+    if native and not torch.equal(y, y_f32acc):
+        out["y_f32acc"] = y_f32acc.numpy()[::row_step]
     if store_inputs:
         out["w"] = w
         out["x"] = x.numpy()
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
-    return {"file": name + ".npz", "M": M, "K": K, "N": N, "seed": 1, "row_step": row_step, "w_crc32": crc(w), "x_crc32": crc(x.numpy()),
-            "provenance": "torch %s CPU nn.Linear float16 forward" % torch.__version__}
+    doc = {"file": name + ".npz", "M": M, "K": K, "N": N, "seed": 1, "row_step": row_step, "w_crc32": crc(w), "x_crc32": crc(x.numpy()),
+           "provenance": "torch %s CPU nn.Linear float16 forward" % torch.__version__}
+    if "y_f32acc" in out:
+        doc["y_f32acc"] = ("y through ATen's fp32-accumulating GEMM (oneDNN off): what CPUs without AVX512-FP16 / AMX-FP16 compute; "
+                           "y itself is oneDNN's native fp16 GEMM")
+    return doc
 
 
 def quant_edge_inputs():

@@ -141,21 +141,21 @@ def test_bench_two_replicas_on_one_gpu_over_gloo():
     port = str(_free_port())
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "20", "--nbuf", "8",
-           "--no-config5", "--no-cpu-baseline"]
+           "--full", "--no-config5", "--no-cpu-baseline"]
     env = dict(os.environ, EETQ_REPLICA_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]                      # rank 0 prints ONE line
     doc = json.loads(lines[0])
-    assert doc["n_gpus"] == 2 and doc["scaling"] == "weak" and doc["steps"] == 200
+    assert doc["n_gpus"] == 2 and doc["scaling"] == "weak" and doc["steps"] == 200 and doc["timed_steps"] == 200
     assert doc["parity"]["replicas_bit_identical"] is True
     # two replicas time-share one GPU here: the whole-job value is two replicas' bytes over the slower rank's time
     assert doc["value"] > 500 and doc["roofline"]["frac"] > 0
 
 
 def _bench_line(*args):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args, "--no-config5", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args, "--full", "--no-config5", "--no-cpu-baseline"]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -164,23 +164,59 @@ def _bench_line(*args):
 
 
 def test_bench_step_time_does_not_depend_on_steps():
-    """The driver runs `bench.py --gpus 1 --steps 20 --warmup 5`; the builder's default is --steps 2000.  Both capture one graph
-    of >= 1000 dependent launches, so the per-step time of the headline (and of the M = 1024 leg) must not depend on --steps
-    (round 3: 4.97 vs 4.63 us, a 20-launch graph paying the inter-replay gap every 20 steps).  Back to back on one box; the
-    better of two tries each absorbs clock drift between the four processes."""
+    """--steps K is the number of timed steps: exactly K dependent launches, as graphs of at most 2000 (a longer K replays a
+    2000-launch graph and then one graph of the remainder).  Once K fills a graph, the per-step time of the headline must not
+    depend on K (round 3: 4.97 vs 4.63 us, a 20-launch graph paying the inter-replay gap every 20 steps), and the M = 1024 leg
+    (its own graphs) must not either.  Back to back on one box; the better of two tries each absorbs clock drift between the
+    four processes.  A 20-step run times 20 steps."""
     def best(*args):
         docs = [_bench_line(*args) for _ in range(2)]
         return min(docs, key=lambda d: d["ms_per_step"])
-    short = best("--steps", "20", "--warmup", "5")
-    long_ = best("--steps", "2000", "--warmup", "200")
-    assert short["steps"] == 20 and long_["steps"] == 2000
-    assert short["config"]["graph_launches"] >= 1000 and short["config"]["graph_launches"] % 20 == 0
-    assert short["timed_steps"] % short["config"]["graph_launches"] == 0
-    assert abs(short["ms_per_step"] * short["timed_steps"] - short["timed_ms"]) <= 1e-3 * short["timed_ms"] + 1e-3
+    short = best("--steps", "2000", "--warmup", "200")
+    long_ = best("--steps", "10007", "--warmup", "200")
+    tiny = _bench_line("--steps", "20", "--warmup", "5")
+    for doc, k in ((tiny, 20), (short, 2000), (long_, 10007)):
+        assert doc["steps"] == k and doc["timed_steps"] == k and doc["config"]["timed_steps"] == k
+        assert doc["config"]["graph_launches"] == min(k, 2000)
+        assert abs(doc["ms_per_step"] * doc["timed_steps"] - doc["timed_ms"]) <= 1e-3 * doc["timed_ms"] + 1e-3
+    assert "5 x 2000 + 1 x 7" in long_["config"]["launch"]
     a, b = short["ms_per_step"], long_["ms_per_step"]
     assert abs(a - b) <= 0.03 * b, (a, b)
     ga, gb = short["secondary"]["ms_per_step"], long_["secondary"]["ms_per_step"]
     assert abs(ga - gb) <= 0.08 * gb, (ga, gb)      # the GEMM leg is power-bound (clock drifts with the box's temperature): 8 %
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone, timed over exactly --steps launches; --dump-outputs DIR writes the
+    output of the last timed step.  Step i runs on weight set i % nbuf, so with 45 steps over 8 sets the dump is set 4's
+    product, recomputed here from bench.py's own recipe; two runs with the same arguments write the same bits."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "45", "--warmup", "5", "--nbuf", "8"]
+    dumps = []
+    for i in range(2):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(i))], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        doc = json.loads(lines[0])
+        assert doc["steps"] == doc["timed_steps"] == 45 and doc["warmup"] == 5
+        assert doc["unit"] == "GB/s" and doc["higher_is_better"] is True and doc["dtype"] == "f16"
+        assert doc["value"] > 0 and doc["ms_per_step"] > 0
+        assert abs(doc["ms_per_step"] * 45 - doc["timed_ms"]) <= 1e-3 * doc["timed_ms"] + 1e-3
+        assert not {"roofline", "secondary", "parity", "quantizer", "cpu_baseline", "config4", "config5"} & set(doc)
+        y = np.load(tmp_path / str(i) / "gemv_y.npy")
+        assert y.dtype == np.float32 and y.shape == (1, 4096)
+        dumps.append(y)
+    assert np.array_equal(dumps[0], dumps[1])
+    import bench
+    from eetq_amd import ops
+    sets, _, _ = bench.make_weight_sets(ops, 8, 4096, 4096, torch.device(DEV))
+    torch.manual_seed(1)
+    x = torch.rand(1, 4096, dtype=torch.float16).to(DEV)
+    want = torch.empty(1, 4096, dtype=torch.float16, device=DEV)
+    ops.w8_a16_gemm_(x, sets[44 % 8][0], sets[44 % 8][1], want, 1, 4096, 4096)
+    assert np.array_equal(dumps[0], want.float().cpu().numpy())
+    assert np.isfinite(dumps[0]).all() and np.abs(dumps[0]).max() > 0
 
 
 @pytest.mark.parametrize("script", ["test_qlinear.py", "test_w8a16_gemm.py"])

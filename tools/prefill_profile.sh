@@ -5,7 +5,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/pp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o p -- python "$ROOT/bench.py" --no-cpu-baseline --steps 100 --warmup 10 --gemm-steps 20 > /tmp/pp.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o p -- python "$ROOT/bench.py" --full --no-cpu-baseline --steps 100 --warmup 10 --gemm-steps 20 > /tmp/pp.log 2>&1
 f=$(find /tmp/pp -name '*kernel_stats.csv' 2>/dev/null | head -1)
 if [ -n "$f" ]; then
     python - "$f" <<'PY'

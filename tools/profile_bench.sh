@@ -21,11 +21,11 @@ export TMPDIR=/tmp
 PY=${PYTHON:-python}
 
 echo "== 1. un-profiled bench line" >&2
-$PY bench.py "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench.py failed" >&2
+$PY bench.py --full "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench.py failed" >&2
 
 echo "== 2. rocprofv3 --kernel-trace --stats of the same command" >&2
 rm -rf /tmp/prof_bench
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- $PY "$ROOT/bench.py" "$@" --no-cpu-baseline --no-config5 --no-config4 --no-power-check \
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- $PY "$ROOT/bench.py" --full "$@" --no-cpu-baseline --no-config5 --no-config4 --no-power-check \
     > "$OUT/${TAG}_bench_under_rocprof.json" 2> "$OUT/${TAG}_rocprof.err" ) || echo "rocprofv3 stats run failed" >&2
 STATS=$(find /tmp/prof_bench -name '*kernel_stats.csv' | head -1)
 if [ -n "$STATS" ]; then
@@ -59,7 +59,7 @@ def chain(path):
     try:
         line = [l for l in open(path).read().splitlines() if l.startswith("{")][-1]
         d = json.loads(line)
-        return {"gemv": d["ms_per_step"] * 1e3, "gemm_m1024": d["secondary"]["ms_per_step"] * 1e3}
+        return {"gemv": d["roofline"]["kernel_us"], "gemm_m1024": d["secondary"]["ms_per_step"] * 1e3}
     except Exception as e:
         return {}
 prof, plain = chain(sys.argv[3]), chain(sys.argv[4])
@@ -162,6 +162,6 @@ if [ -s "$OUT/bench_rocprof.json" ]; then
     cp "$OUT/bench_rocprof.json" profiles/bench_rocprof.json
     [ -s "$OUT/pmc_traffic.json" ] && cp "$OUT/pmc_traffic.json" profiles/pmc_traffic.json
     [ -s "$OUT/${TAG}_bench_kernel_stats.csv" ] && cp "$OUT/${TAG}_bench_kernel_stats.csv" "profiles/${TAG}_bench_kernel_stats.csv"
-    $PY bench.py "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench.py (second line) failed" >&2
+    $PY bench.py --full "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || echo "bench.py (second line) failed" >&2
 fi
 echo "done: $(ls $OUT | tr '\n' ' ')" >&2
