@@ -30,6 +30,6 @@ try:
 except Exception as _e:  # noqa: BLE001  no compiler / headers: the pure-Python binding of the same C ABI
     _compiled_error = _e
     from eetq_amd.ops_ctypes import (layernorm_forward, preprocess_weights, quant_weights, rotary_embedding_neox,  # noqa: F401
-                                     w8_a16_gemm, w8_a16_gemm_)
-    __all__ = ["w8_a16_gemm", "w8_a16_gemm_", "preprocess_weights", "quant_weights", "rotary_embedding_neox",
+                                     w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t)
+    __all__ = ["w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "preprocess_weights", "quant_weights", "rotary_embedding_neox",
                "layernorm_forward"]

@@ -467,6 +467,14 @@ int eetq_w8a16_gemm(const void* x, const int8_t* w_packed, const void* scales, v
     return gemm_dispatch(x, w_packed, scales, nullptr, nullptr, y, M, N, K, EETQ_PATH_AUTO, stream);
 }
 
+int eetq_w8a16_gemm_t(const void* in, const void* weight, const void* scale, void* out, int M, int N, int K, void* stream)
+{
+    int st = check_gemm_args(in, weight, scale, out, M, N, K);
+    if (st != EETQ_OK) return st;
+    return launch_gemm_t(static_cast<const f16*>(in), static_cast<const uint8_t*>(weight), static_cast<const f16*>(scale),
+                         static_cast<f16*>(out), M, N, K, static_cast<hipStream_t>(stream));
+}
+
 int eetq_w8a16_gemm_bias(const void* x, const int8_t* w_packed, const void* scales, const void* bias, void* y, int M,
                          int N, int K, int path, void* stream)
 {

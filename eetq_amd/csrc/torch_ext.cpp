@@ -440,6 +440,37 @@ Tensor w8_a16_gemm_(const Tensor& input, const Tensor& weight, const Tensor& sca
     return gemm_launch(input, weight, scale, output, m, n, k, EETQ_PATH_AUTO, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
 }
 
+// Extension: the projection's input gradient, out[..., K] = input[..., N] . fp16(q s)^T (eetq_w8a16_gemm_t): what the reference's
+// EetqLinearMMFunction.backward computes as grad @ W_deq^T (python/eetq/modules/qlinear.py:80-94) after dequantising W through
+// an identity GEMM.  Fresh output, current stream, asynchronous; every argument check comes before any GPU work.
+Tensor w8_a16_gemm_t(const Tensor& input, const Tensor& weight, const Tensor& scale)
+{
+    TORCH_CHECK(input.is_cuda() && weight.is_cuda() && scale.is_cuda(), "w8_a16_gemm_t: input, weight and scale must be GPU tensors");
+    TORCH_CHECK(input.scalar_type() == at::kHalf, "w8_a16_gemm_t: input must be float16 (got ", input.scalar_type(), ")");
+    TORCH_CHECK(weight.dim() == 2 && weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf,
+                "w8_a16_gemm_t: weight must be an int8 [K, N] tensor and scale float16");
+    TORCH_CHECK(weight.device() == input.device() && scale.device() == input.device(),
+                "w8_a16_gemm_t: input, weight and scale must be on the same device");
+    const int64_t k = weight.size(0), n = weight.size(1);
+    TORCH_CHECK(n == 0 || scale.numel() != 2 * n, "w8_a16_gemm_t: packed int4 weights are not supported (int8 only)");
+    TORCH_CHECK(scale.numel() == n, "w8_a16_gemm_t: scale must have N = ", n, " elements (got ", scale.numel(), ")");
+    TORCH_CHECK(input.dim() >= 1 && input.size(-1) == n, "w8_a16_gemm_t: weight is [", k, ", ", n, "] but input has N=",
+                input.dim() >= 1 ? input.size(-1) : 0);
+    TORCH_CHECK(weight.is_contiguous() && scale.is_contiguous(), "w8_a16_gemm_t: weight and scale must be contiguous");
+    std::vector<int64_t> shape(input.sizes().begin(), input.sizes().end());
+    shape.back()        = k;
+    Tensor        output = torch::empty(shape, input.options());
+    const int64_t m      = n ? input.numel() / n : 0;
+    if (m == 0 || k == 0) return output;
+    TORCH_CHECK(m <= INT32_MAX, "w8_a16_gemm_t: too many rows");
+    Tensor x = input.contiguous();  // a stride-0 gradient (y.sum().backward()) is materialised here
+    if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+    c10::DeviceGuard guard(input.device());
+    check(eetq_w8a16_gemm_t(x.data_ptr(), weight.data_ptr(), scale.data_ptr(), output.data_ptr(), (int)m, (int)n, (int)k,
+                            stream_of(input)));
+    return output;
+}
+
 // ---- side ops ---------------------------------------------------------------------------------------------------------
 // reference: layernorm_forward_cuda, layernorm.cu:98-113 (returns void; current stream here, default stream there)
 void layernorm_forward(const Tensor& input, const Tensor& gamma, Tensor& out, double eps)
@@ -847,6 +878,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("layernorm_forward", &layernorm_forward, "LayerNorm kernel", py::arg("input"), py::arg("gamma"), py::arg("out"),
           py::arg("eps"));
     // ---- extensions of this library ----------------------------------------------------------------------------------
+    m.def("w8_a16_gemm_t", &w8_a16_gemm_t, "input gradient of the weight-only gemm: input . dequant(weight)^T",
+          py::arg("input"), py::arg("weight"), py::arg("scale"));
     m.def("unprocess_weights", &unprocess_weights, "inverse of preprocess_weights", py::arg("processed_weight"),
           py::arg("layout") = "gfx950", py::arg("is_int4") = false);
     m.def("rotary_embedding_neox_strided", &rotary_embedding_neox_strided, "rotary embedding on strided q/k views",

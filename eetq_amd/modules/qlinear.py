@@ -16,10 +16,10 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import preprocess_weights, quant_weights, w8_a16_gemm
+from ..ops import preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t
 from ..checkpoint import install_layout_hooks
 
-__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "EetqLinearMMFunction", "EetqLinear"]
+__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "EetqLinearMMFunction", "EetqLinear", "input_grad"]
 
 
 def quantize_and_preprocess_weights(weight, scales=None):
@@ -125,23 +125,34 @@ class W4A16Linear(nn.Module):
                                                                         self.bias is not None)
 
 
+def input_grad(grad_output, weight, scales, x_shape, x_dtype=torch.float16):
+    """``grad_output @ dequant(weight, scales).T`` shaped like the forward's input ``x_shape``: the input gradient of the W8A16
+    projection.  An fp16 GPU gradient goes through ``w8_a16_gemm_t`` (the dequantised weight is never materialised); anything
+    else through the reference's identity path (dequantise W by multiplying an identity -- exact: every output element is a
+    single product -- then an fp16 GEMM in torch)."""
+    if grad_output.dtype == torch.float16 and grad_output.is_cuda:
+        return w8_a16_gemm_t(grad_output, weight, scales).reshape(x_shape)
+    eye = torch.eye(weight.shape[0], device=weight.device, dtype=x_dtype)
+    w_deq = w8_a16_gemm(eye, weight, scales)  # fp16 [K, N] == fp16(q * s)
+    return grad_output.matmul(w_deq.transpose(0, 1)).reshape(x_shape)
+
+
 class EetqLinearMMFunction(Function):
-    """Autograd wrapper: forward = fused dequant GEMM; backward dequantises W by multiplying an identity
-    (exact: every output element is a single product) and returns grad_input only."""
+    """Autograd wrapper: forward = fused dequant GEMM; backward returns grad_input only (the int8 weight is frozen), computed
+    by :func:`input_grad`.  ``x`` itself is not saved: no gradient here needs it."""
 
     @staticmethod
     def forward(ctx, x, weight, scales, bias=None):
-        ctx.save_for_backward(x, weight, scales, bias)
+        ctx.save_for_backward(weight, scales)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         return w8_a16_gemm(x, weight, scales, bias=bias)
 
     @staticmethod
     def backward(ctx, grad_output):
-        x, weight, scales, _bias = ctx.saved_tensors
+        weight, scales = ctx.saved_tensors
         grad_input = None
         if ctx.needs_input_grad[0]:
-            eye = torch.eye(weight.shape[0], device=weight.device, dtype=x.dtype)
-            w_deq = w8_a16_gemm(eye, weight, scales)  # fp16 [K, N] == fp16(q * s)
-            grad_input = grad_output.squeeze(0).matmul(w_deq.transpose(0, 1)).unsqueeze(0)
+            grad_input = input_grad(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
         return grad_input, None, None, None
 
 

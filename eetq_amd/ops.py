@@ -32,6 +32,7 @@ if _C is not None:
     unprocess_weights = _C.unprocess_weights
     w8_a16_gemm = _C.w8_a16_gemm
     w8_a16_gemm_ = _C.w8_a16_gemm_
+    w8_a16_gemm_t = _C.w8_a16_gemm_t
     layernorm_forward = _C.layernorm_forward
     rotary_embedding_neox = _C.rotary_embedding_neox
     rotary_embedding_neox_strided = _C.rotary_embedding_neox_strided
@@ -50,12 +51,12 @@ else:
     from .ops_ctypes import (decode_attention, greedy_handover, layernorm_forward, preprocess_weights, quant_weights,  # noqa: F401
                              rope_decode_attention, rotary_embedding_neox, rotary_embedding_neox_kvcache,
                              rotary_embedding_neox_kvcache_prefill, rotary_embedding_neox_strided, silu_mul,
-                             unprocess_weights, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemv_grouped)
+                             unprocess_weights, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t, w8_a16_gemv_grouped)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
 
-__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "layernorm_forward",
+__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
            "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "decode_dropped_steps",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]

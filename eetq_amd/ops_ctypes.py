@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_F32, LAYOUT_GFX950, LAYOUT_ROW_MAJOR,
                    LAYOUT_SM80, PATH_AUTO, PATH_GEMV, PATH_MFMA, check)
 
-__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_",
+__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
@@ -186,6 +186,39 @@ def _gemm_launch(input, weight, scale, output, m, n, k, path, bias=None, residua
         check(_lib.lib().eetq_w8a16_gemm_act(_ptr(x), _ptr(weight), _ptr(scale), _ptr(bias) if bias is not None else None,
                                              _ptr(residual) if residual is not None else None, _ptr(output), m, n, k, path,
                                              act, _stream_ptr()))
+    return output
+
+
+@_eager_only
+def w8_a16_gemm_t(input, weight, scale):
+    """Input gradient of the weight-only GEMM: ``input[..., N] @ dequant(weight, scale).T`` -> ``[..., K]`` for an int8
+    ``[K, N]`` weight, without materialising the dequantised weight (eetq_w8a16_gemm_t).  Current stream, asynchronous."""
+    if not (input.is_cuda and weight.is_cuda and scale.is_cuda):
+        raise RuntimeError("w8_a16_gemm_t: input, weight and scale must be GPU tensors")
+    if input.dtype != torch.float16:
+        raise RuntimeError("w8_a16_gemm_t: input must be float16 (got %s)" % input.dtype)
+    if weight.dim() != 2 or weight.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise RuntimeError("w8_a16_gemm_t: weight must be an int8 [K, N] tensor and scale float16")
+    if weight.device != input.device or scale.device != input.device:
+        raise RuntimeError("w8_a16_gemm_t: input, weight and scale must be on the same device")
+    k, n = weight.shape
+    if n and scale.numel() == 2 * n:
+        raise RuntimeError("w8_a16_gemm_t: packed int4 weights are not supported (int8 only)")
+    if scale.numel() != n:
+        raise RuntimeError("w8_a16_gemm_t: scale must have N = %d elements (got %d)" % (n, scale.numel()))
+    if input.dim() < 1 or input.shape[-1] != n:
+        raise RuntimeError("w8_a16_gemm_t: weight is [%d, %d] but input has N=%d" % (k, n, input.shape[-1] if input.dim() else 0))
+    if not weight.is_contiguous() or not scale.is_contiguous():
+        raise RuntimeError("w8_a16_gemm_t: weight and scale must be contiguous")
+    output = torch.empty(tuple(input.shape[:-1]) + (k,), dtype=input.dtype, device=input.device)
+    m = input.numel() // n if n else 0
+    if m == 0 or k == 0:
+        return output
+    x = input.contiguous()  # a stride-0 gradient (y.sum().backward()) is materialised here
+    if x.data_ptr() % 16:
+        x = x.clone()
+    with torch.cuda.device(input.device):
+        check(_lib.lib().eetq_w8a16_gemm_t(_ptr(x), _ptr(weight), _ptr(scale), _ptr(output), m, n, k, _stream_ptr()))
     return output
 
 

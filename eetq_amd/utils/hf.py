@@ -9,6 +9,12 @@ binaries, needs the ``kernels`` package and a network).  :func:`use_with_transfo
 compiled ``EETQ`` module of this repo instead -- nothing else of transformers is touched, its ``EetqLinear``,
 ``EetqLinearMMFunction`` (forward AND backward) and ``EetqQuantize.convert`` run as shipped.
 
+Fused backward (opt-in, reversible): ``use_with_transformers(fused_backward=True)`` or :func:`set_fused_backward` points
+``transformers.integrations.eetq.EetqLinearMMFunction`` -- the name ``EetqLinear.forward`` looks up at call time -- at
+:class:`FusedBackwardMMFunction`: the same forward, and an input gradient from ``w8_a16_gemm_t`` instead of the shipped
+identity GEMM + dequantised-weight matmul (no ``eye(K)``, no ``[K, N]`` fp16 weight, ``x`` not saved).
+``set_fused_backward(False)`` puts transformers' own class back.
+
 Bytes on disk.  transformers' loader assigns checkpoint tensors straight to the parameters (no ``load_state_dict``), and
 its ``EetqLinear`` knows nothing about layouts; the int8 bytes this library computes on are the ``gfx950`` layout, the
 bytes EETQ checkpoints hold are the reference's ``sm80`` layout (eetq_amd/checkpoint.py).  With ``wire=True`` (default)
@@ -25,20 +31,66 @@ Quantise-on-load (fp16 checkpoint + ``EetqConfig``) produces gfx950 bytes direct
 """
 import functools
 
-__all__ = ["use_with_transformers", "HUB_KERNEL_NAME"]
+import torch
+
+from ..modules.qlinear import input_grad
+
+__all__ = ["use_with_transformers", "set_fused_backward", "FusedBackwardMMFunction", "HUB_KERNEL_NAME"]
 
 HUB_KERNEL_NAME = "kernels-community/quantization-eetq"
 _installed = [False]
 
 
-def use_with_transformers(wire=True):
-    """Idempotent.  Returns the ``EETQ`` module transformers will call."""
+_shipped_mm_function = [None]   # transformers' own EetqLinearMMFunction, kept while the fused one is installed
+
+
+class FusedBackwardMMFunction(torch.autograd.Function):
+    """transformers' ``EetqLinearMMFunction`` with the input gradient from ``w8_a16_gemm_t``: the forward is the shipped one
+    (the hub module's GEMM, then ``+ bias``); the backward returns ``grad_input`` shaped like ``x`` and nothing else."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scales, bias=None):
+        import transformers.integrations.eetq as hf_eetq
+        ctx.save_for_backward(weight, scales)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        output = hf_eetq.eetq_kernels_hub.w8_a16_gemm(x, weight, scales)
+        return output + bias if bias is not None else output
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        weight, scales = ctx.saved_tensors
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            grad_input = input_grad(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
+        return grad_input, None, None, None
+
+
+def set_fused_backward(enabled=True):
+    """Point transformers' ``EetqLinearMMFunction`` at :class:`FusedBackwardMMFunction` (``enabled``) or back at transformers'
+    own class.  Returns the previous setting.  Forward results are the same either way."""
+    import transformers.integrations.eetq as hf_eetq
+    was = hf_eetq.EetqLinearMMFunction is FusedBackwardMMFunction
+    if enabled and not was:
+        _shipped_mm_function[0] = hf_eetq.EetqLinearMMFunction
+        hf_eetq.EetqLinearMMFunction = FusedBackwardMMFunction
+    elif not enabled and was:
+        hf_eetq.EetqLinearMMFunction = _shipped_mm_function[0]
+        _shipped_mm_function[0] = None
+    return was
+
+
+def use_with_transformers(wire=True, fused_backward=None):
+    """Idempotent.  Returns the ``EETQ`` module transformers will call.  ``fused_backward``: True / False switches the fused
+    input gradient on / off (:func:`set_fused_backward`); None (default) leaves the current setting -- transformers' shipped
+    backward unless it was switched on."""
     import EETQ
     import transformers.integrations.eetq as hf_eetq
     import transformers.integrations.hub_kernels as hub
     import transformers.quantizers.quantizer_eetq as hf_quantizer
 
     hf_eetq.eetq_kernels_hub = EETQ   # the handle EetqQuantize / EetqLinearMMFunction read at call time
+    if fused_backward is not None:
+        set_fused_backward(bool(fused_backward))
     if _installed[0]:
         return EETQ
     _installed[0] = True

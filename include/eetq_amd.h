@@ -79,8 +79,8 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported).  Revisions only ADD entry points: a caller built against an older header keeps working. */
-#define EETQ_AMD_ABI_VERSION 6
+ * (+ _supported); 7 = eetq_w8a16_gemm_t.  Revisions only ADD entry points: a caller built against an older header keeps working. */
+#define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
                         int layout, void* scales, float* workspace, size_t workspace_floats, void* stream);
@@ -114,6 +114,14 @@ int eetq_unpack_i8_host(const int8_t* q_packed, size_t K, size_t N, int8_t* q_ra
  * y: fp16 [M][N] row-major.  Device pointers, 16-byte aligned.  Requires K % 64 == 0, N % 16 == 0, M >= 1. */
 int eetq_w8a16_gemm(const void* x, const int8_t* w_packed, const void* scales, void* y, int M, int N, int K,
                     void* stream);
+/* ABI revision 7 (additive): out[M][K] = in[M][N] . fp16(q.s)^T, weight in the gfx950 int8 layout [K][N].
+ * The input gradient of the projection above (the reference's EetqLinearMMFunction.backward computes it as grad @ W_deq^T
+ * after dequantising W through an identity GEMM, python/eetq/modules/qlinear.py:80-94), without materialising W_deq:
+ *   out[m][k] = fp16( sum_n fp32(in[m][n]) * fp32( fp16( q[k][n] * scale[n] ) ) ),  fp32 accumulation, one rounding.
+ * in: fp16 [M][N] row-major; weight / scale: exactly as eetq_w8a16_gemm takes them (int8 only); out: fp16 [M][K] row-major.
+ * Device pointers, 16-byte aligned.  Requires K % 64 == 0, N % 16 == 0, M >= 1.  Deterministic: one pass over N per output
+ * tile, no atomics, so repeated calls give identical bits. */
+int eetq_w8a16_gemm_t(const void* in, const void* weight, const void* scale, void* out, int M, int N, int K, void* stream);
 /* As above with an explicit kernel path (EETQ_PATH_*); returns EETQ_ERR_UNSUPPORTED when the path cannot
  * run the shape (e.g. GEMV with M > 4, STREAM with M > 64). */
 int eetq_w8a16_gemm_ex(const void* x, const int8_t* w_packed, const void* scales, void* y, int M, int N,
