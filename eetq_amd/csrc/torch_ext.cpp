@@ -860,6 +860,77 @@ std::vector<Tensor> w8_a16_gemv_grouped(const std::vector<Tensor>& inputs, const
     return outs;
 }
 
+// Routed W8A16 mixture-of-experts layer (extension): the forward of transformers' experts modules,
+// out[t] = sum_j w[t][j] * down_e( silu(gate_e(x_t)) * up_e(x_t) ), e = top_k_index[t][j], on expert stacks gate_up_weight
+// int8 [E, H, 2I] (gfx950 layout per expert, glu8 column order), gate_up_scale fp16 [E, 2I], down_weight int8 [E, I, H],
+// down_scale fp16 [E, H].  T <= 16: route -> grouped GEMM (gather, silu_glu8) -> grouped GEMM (sorted rows) -> combine, four
+// launches, no host sync (capturable).  T > 16: the expert counts are read back once and every active expert's rows run through
+// the AUTO W8A16 GEMMs, then the same combine (not capturable).  Ids outside [0, E) contribute nothing.
+Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
+                  const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+{
+    TORCH_CHECK(hidden_in.is_cuda() && hidden_in.scalar_type() == at::kHalf && hidden_in.dim() == 2,
+                "w8_a16_moe: hidden must be a float16 GPU tensor [T, H]");
+    const auto dev = hidden_in.device();
+    TORCH_CHECK(gu_w.dim() == 3 && dn_w.dim() == 3 && gu_w.scalar_type() == at::kChar && dn_w.scalar_type() == at::kChar &&
+                    gu_s.scalar_type() == at::kHalf && dn_s.scalar_type() == at::kHalf,
+                "w8_a16_moe: expert weights must be int8 [E, K, N] stacks and scales float16 [E, N]");
+    const int64_t E = gu_w.size(0), H = gu_w.size(1), N1 = gu_w.size(2), I = N1 / 2;
+    TORCH_CHECK(hidden_in.size(1) == H, "w8_a16_moe: hidden is [T, ", hidden_in.size(1), "] but gate_up_weight has H = ", H);
+    TORCH_CHECK(N1 == 2 * I && dn_w.size(0) == E && dn_w.size(1) == I && dn_w.size(2) == H && gu_s.dim() == 2 && gu_s.size(0) == E &&
+                    gu_s.size(1) == N1 && dn_s.dim() == 2 && dn_s.size(0) == E && dn_s.size(1) == H,
+                "w8_a16_moe: expected gate_up_weight [E, H, 2I], gate_up_scale [E, 2I], down_weight [E, I, H], down_scale [E, H]");
+    TORCH_CHECK(H % 64 == 0 && I % 64 == 0, "w8_a16_moe: the gfx950 layout needs H % 64 == 0 and I % 64 == 0");
+    TORCH_CHECK(gu_w.is_contiguous() && gu_s.is_contiguous() && dn_w.is_contiguous() && dn_s.is_contiguous(),
+                "w8_a16_moe: expert weights and scales must be contiguous");
+    TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden_in.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
+                "w8_a16_moe: top_k_index and top_k_weights must both be [T, k]");
+    TORCH_CHECK(top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf,
+                "w8_a16_moe: top_k_weights must be float32 or float16");
+    for (const Tensor* t : {&top_k_index, &top_k_weights, &gu_w, &gu_s, &dn_w, &dn_s})
+        TORCH_CHECK(t->device() == dev, "w8_a16_moe: all tensors must be on the hidden states' device");
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    Tensor        out = torch::empty({T, H}, hidden_in.options());
+    if (T == 0) return out;
+    c10::DeviceGuard guard(dev);
+    void*        st     = stream_of(hidden_in);
+    const Tensor hidden = hidden_in.contiguous();
+    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
+    const Tensor wts    = top_k_weights.contiguous();
+    // counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A]
+    Tensor tables = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
+    int*   counts = tables.data_ptr<int>();
+    int *  offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
+    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
+    Tensor down = torch::empty({S, H}, hidden.options());
+    if (T <= 16) {
+        Tensor inter = torch::empty({S, I}, hidden.options());
+        check(eetq_w8a16_moe_gemm(hidden.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, sorted, active,
+                                  inter.data_ptr(), (int)T, (int)k, (int)E, (int)N1, (int)H, 1, 1, st));
+        check(eetq_w8a16_moe_gemm(inter.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, sorted, active,
+                                  down.data_ptr(), (int)T, (int)k, (int)E, (int)H, (int)I, 0, 0, st));
+    } else {
+        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the prompt path
+        const int*   ch       = counts_h.data_ptr<int>();
+        const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
+        int64_t      off      = 0;
+        for (int64_t e = 0; e < E; ++e) {
+            const int64_t c = ch[e];
+            if (!c) continue;
+            const Tensor tok  = sorted_t.narrow(0, off, c).div(k, "floor");
+            const Tensor gate = w8_a16_gemm(hidden.index_select(0, tok), gu_w[e], gu_s[e], "auto", std::nullopt, std::nullopt,
+                                            std::nullopt, false, std::string("silu_glu8"));
+            Tensor rows = down.narrow(0, off, c);
+            gemm_launch(gate, dn_w[e], dn_s[e], rows, c, H, I, EETQ_PATH_AUTO, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
+            off += c;
+        }
+    }
+    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
+                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
+                               (int)H, st));
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "EETQ operator module on libeetq_amd.so (MI355X / gfx950)";
@@ -917,5 +988,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("w8_a16_gemv_grouped", &w8_a16_gemv_grouped, "independent single-row W8A16 problems in as few dispatches as possible",
           py::arg("inputs"), py::arg("weights"), py::arg("scales"), py::arg("biases") = py::none(),
           py::arg("residuals") = py::none());
+    m.def("w8_a16_moe", &w8_a16_moe, "routed W8A16 mixture-of-experts layer over int8 expert stacks", py::arg("hidden"),
+          py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"));
     m.attr("__eetq_amd_version__") = eetq_version();
 }

@@ -16,10 +16,10 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t
+from ..ops import preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe
 from ..checkpoint import install_layout_hooks
 
-__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "EetqLinearMMFunction", "EetqLinear", "input_grad"]
+__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad"]
 
 
 def quantize_and_preprocess_weights(weight, scales=None):
@@ -123,6 +123,86 @@ class W4A16Linear(nn.Module):
     def extra_repr(self):
         return "in_features={}, out_features={}, bias={}, bits=4".format(self.in_features, self.out_features,
                                                                         self.bias is not None)
+
+
+class W8A16Experts(nn.Module):
+    """int8 stand-in for transformers' 3-D experts modules (``MixtralExperts``, ``Qwen3MoeExperts``, ...): same forward signature
+    ``(hidden_states [T, H], top_k_index [T, k], top_k_weights [T, k]) -> [T, H]``, so the MoE block's ``self.experts(...)`` call
+    is unchanged.  Buffers: ``gate_up_qweight`` int8 [E, H, 2I] (per expert the gfx950 layout, columns in glu8 order: 8 gate + the
+    matching 8 up per 16-column tile), ``gate_up_scales`` fp16 [E, 2I] (same order), ``down_qweight`` int8 [E, I, H],
+    ``down_scales`` fp16 [E, H].  Runs ``ops.w8_a16_moe``.
+
+    State dicts hold the stacks in this library's gfx950 layout, unlike W8A16Linear's: the reference has no experts module, so
+    there is no CUDA-written checkpoint to stay compatible with, and the glu8 column order has no counterpart in its layout."""
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
+        super().__init__()
+        self.num_experts = num_experts
+        self.hidden_dim = hidden_dim
+        self.intermediate_dim = intermediate_dim
+        E, H, I = num_experts, hidden_dim, intermediate_dim
+        self.register_buffer("gate_up_qweight", torch.zeros((E, H, 2 * I), dtype=torch.int8, device=dev))
+        self.register_buffer("gate_up_scales", torch.zeros((E, 2 * I), dtype=torch.float16, device=dev))
+        self.register_buffer("down_qweight", torch.zeros((E, I, H), dtype=torch.int8, device=dev))
+        self.register_buffer("down_scales", torch.zeros((E, H), dtype=torch.float16, device=dev))
+
+    @staticmethod
+    def unsupported_reason(module):
+        """None when :meth:`from_experts` takes ``module``, else why not."""
+        gu, dn = getattr(module, "gate_up_proj", None), getattr(module, "down_proj", None)
+        if not isinstance(gu, torch.Tensor) or not isinstance(dn, torch.Tensor) or gu.dim() != 3 or dn.dim() != 3:
+            return "no 3-D gate_up_proj / down_proj"
+        if not getattr(module, "has_gate", False) or not getattr(module, "is_concatenated", False):
+            return "needs a concatenated [gate; up] projection (has_gate, is_concatenated)"
+        if getattr(module, "is_transposed", False):
+            return "transposed expert weights are not supported"
+        if getattr(module, "has_bias", False):
+            return "expert biases are not supported"
+        act = getattr(module, "act_fn", None)
+        if not isinstance(act, nn.SiLU) and type(act).__name__ != "SiLUActivation":
+            return "the activation must be SiLU (got %s)" % type(act).__name__
+        E, n2, H = gu.shape
+        if n2 % 2 or dn.shape != (E, H, n2 // 2):
+            return "gate_up_proj [E, 2I, H] and down_proj [E, H, I] do not match"
+        if H % 64 or (n2 // 2) % 64:
+            return "the gfx950 layout needs H %% 64 == 0 and I %% 64 == 0 (H = %d, I = %d)" % (H, n2 // 2)
+        return None
+
+    @classmethod
+    def from_experts(cls, module, init_only=False):
+        """Quantise a transformers experts module (see :meth:`unsupported_reason` for what is taken; anything else raises
+        ValueError before any GPU work).  Each expert is quantised per output channel by ``ops.quant_weights``."""
+        why = cls.unsupported_reason(module)
+        if why is not None:
+            raise ValueError("W8A16Experts.from_experts: %s: %s" % (type(module).__name__, why))
+        gu, dn = module.gate_up_proj, module.down_proj
+        E, n2, H = gu.shape
+        I = n2 // 2
+        mod = cls(E, H, I, dev=gu.device)
+        if init_only:
+            return mod
+        if gu.dtype != torch.float16 or dn.dtype != torch.float16:
+            raise ValueError("Unsupported data type: {}".format(gu.dtype))
+        from ..utils.fuse import _glu8_interleave_columns, _glu8_interleave_tiles
+        with torch.no_grad():
+            q, s = quant_weights(gu.detach().transpose(1, 2).contiguous(), torch.int8, False)  # [E, H, 2I] gate | up
+            halves = q.reshape(E, 2, -1)  # per expert: the I/16 gate tile rows, then the I/16 up tile rows
+            mod.gate_up_qweight = _glu8_interleave_tiles(halves[:, 0], halves[:, 1], H).reshape(E, H, n2).to(gu.device)
+            mod.gate_up_scales = _glu8_interleave_columns(s[:, :I], s[:, I:]).half().contiguous().to(gu.device)
+            q, s = quant_weights(dn.detach().transpose(1, 2).contiguous(), torch.int8, False)  # [E, I, H]
+            mod.down_qweight = q.to(gu.device)
+            mod.down_scales = s.half().to(gu.device)
+        return mod
+
+    @torch.no_grad()
+    def forward(self, hidden_states, top_k_index, top_k_weights):
+        """T <= 16 tokens: four launches, no host sync (capturable); more: one read-back of the expert counts (not capturable)."""
+        return w8_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                          self.down_qweight, self.down_scales)
+
+    def extra_repr(self):
+        return "num_experts={}, hidden_dim={}, intermediate_dim={}".format(self.num_experts, self.hidden_dim,
+                                                                           self.intermediate_dim)
 
 
 def input_grad(grad_output, weight, scales, x_shape, x_dtype=torch.float16):

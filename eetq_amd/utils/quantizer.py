@@ -6,11 +6,12 @@ it needs from python/eetq/utils/base.py (``find_layers`` :280-285, ``set_op_by_n
 weight surgery outside the GEMM path and are out of scope.
 """
 import gc
+import warnings
 
 import torch
 import torch.nn as nn
 
-from ..modules.qlinear import W8A16Linear
+from ..modules.qlinear import W8A16Experts, W8A16Linear
 
 __all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears"]
 
@@ -49,13 +50,45 @@ def _progress(items, desc):
         return items
 
 
-def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0"):
+def _experts_modules(model):
+    """name -> module for every transformers-style experts module: 3-D ``gate_up_proj`` / ``down_proj`` parameters (or an
+    ``up_proj`` stack for ungated experts), the layout MoE models keep their experts in since transformers 5."""
+    found = {}
+    for name, sub in model.named_modules():
+        params = dict(sub.named_parameters(recurse=False))
+        stacks = [params.get(n) for n in ("gate_up_proj", "up_proj", "down_proj")]
+        if any(p is not None and p.dim() == 3 for p in stacks):
+            found[name] = sub
+    return found
+
+
+def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
     ``SCB / 127`` scales; other dtypes raise ValueError.  ``device`` is accepted for signature
     compatibility; like the reference, each layer stays on the device its weight is on.
+    ``experts=True`` (extension) also replaces every mixture-of-experts experts module that :class:`W8A16Experts` supports
+    (3-D gated SiLU expert stacks: Mixtral, Qwen2/3-MoE, OLMoE, DeepSeek-V3 ...); unsupported ones stay as they are and are
+    named in one warning.  The default leaves experts modules untouched.
     """
+    if experts:
+        skipped = []
+        found = _experts_modules(model)
+        for name in list(found):
+            mod = found.pop(name)  # the model and this loop hold the only references: the fp16 stacks go as each is replaced
+            if any(tag in name for tag in exclude):
+                continue
+            why = W8A16Experts.unsupported_reason(mod)
+            if why is not None:
+                skipped.append("%s (%s)" % (name, why))
+                continue
+            set_op_by_name(model, name, W8A16Experts.from_experts(mod, init_only=init_only))
+            del mod
+            if not init_only and torch.cuda.is_available():
+                torch.cuda.empty_cache()
+        if skipped:
+            warnings.warn("eet_quantize: %d experts module(s) left in fp16: %s" % (len(skipped), "; ".join(skipped)))
     targets = find_layers(model, include=include, exclude=exclude)
     desc = "[EET][INFO] quantization preprocessing..." + ("(init only)" if init_only else "")
     for name in _progress(list(targets), desc):

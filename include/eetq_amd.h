@@ -256,6 +256,38 @@ int eetq_w8a16_gemm_glu8(const void* x, const int8_t* w_packed, const void* scal
                          int K, void* stream);
 int eetq_silu_mul_glu8_f16(const void* gate_up, void* out, int rows, int intermediate, void* stream);
 
+/* ---- mixture of experts (extension, additive within ABI revision 7) -------------------------------------
+ * The reference has no MoE path: these entries extend its per-weight GEMM (w8_a16_gemm_forward_cuda, fpA_intB_gemm_wrapper.cu:
+ * 130-173) and its [E, K, N] quantiser input (fpA_intB_gemm_wrapper.cu:45-66, which quantises expert 0 only; eetq_quantize_i8
+ * per expert here) to a routed layer.  T tokens each pick k experts of E; "slot" t*k + j is token t's j-th choice.  All three
+ * launch a grid fixed by T, k, E, N, K (never by the routing), synchronise nothing and can be captured in a HIP graph.
+ *
+ * eetq_moe_route: device tables from top_k_index (int64 [T][k], device).  One launch, one workgroup.
+ *   counts [E], offsets [E + 1] (exclusive prefix sum; offsets[E] = slots that take part), sorted_slot [T*k]: the slots ordered
+ *   by expert, then by slot index (stable, deterministic), -1 from offsets[E] on; position [T*k]: the inverse (slot -> its
+ *   sorted position, -1 for a slot that takes part in nothing); active [min(E, T*k)]: the experts with at least one slot, in
+ *   ascending order, padded with -1.  Ids outside [0, E) -- transformers' `expert_idx == num_experts` sentinel, -1 -- take part
+ *   in nothing.  int32 outputs, device pointers.  1 <= E <= 1024, 1 <= k <= E, T >= 1, T*k <= 2^30; else EETQ_ERR_INVALID. */
+int eetq_moe_route(const int64_t* top_k_index, int T, int k, int E, int* counts, int* offsets, int* sorted_slot, int* position,
+                   int* active, void* stream);
+/* eetq_w8a16_moe_gemm: grouped W8A16 GEMM over an expert stack: w_packed [E][K][N] int8, each expert in the GFX950 layout
+ *   (K*N bytes apart), scales fp16 [E][N].  Workgroup (a, column tile): e = active[a] (exits on -1); rows p = offsets[e] ..
+ *   offsets[e+1] - 1 in sorted order, 16 at a time, the expert's weight tile row streamed once per 16 rows.
+ *     gather = 1: row p reads x[sorted_slot[p] / k] (x fp16 [T][K]);  gather = 0: row p reads x[p] (x fp16 [T*k][K], sorted).
+ *     glu8 = 0: y[p][n] = fp16( sum_k fp32(x) * fp32( fp16(q s) ) ), y fp16 [T*k][N] -- the numerics of eetq_w8a16_gemm;
+ *     glu8 = 1: columns in "glu8" order (eetq_w8a16_gemm_glu8), y [T*k][N / 2] = silu_mul of the fp16 column pairs -- bit for bit
+ *               the projection followed by eetq_silu_mul_glu8_f16.
+ *   Rows of y not in any active expert are not written.  offsets / sorted_slot / active as eetq_moe_route wrote them.  Needs
+ *   K % 64 == 0, N % 16 == 0, x / w_packed / y 16-byte aligned, E and k as in eetq_moe_route; else EETQ_ERR_INVALID. */
+int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
+                        const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream);
+/* eetq_moe_combine_f16: out[t][h] = fp16( sum_{j = 0..k-1, in order} fp32(y[position[t*k + j]][h]) * fp32(weights[t][j]) ),
+ *   slots with position -1 adding nothing (a token with none gets 0).  y fp16 [*][H], out fp16 [T][H] (16-byte aligned,
+ *   H % 8 == 0), weights [T][k] of w_dtype EETQ_DTYPE_F32 (transformers' router output) or EETQ_DTYPE_F16.  No atomics:
+ *   deterministic. */
+int eetq_moe_combine_f16(const void* y, const int* position, const void* weights, int w_dtype, void* out, int T, int k, int H,
+                         void* stream);
+
 /* Decode-step rotary + KV-cache write (extension for the EET attention blocks): one new token per batch row b, rotated
  * by cos_sin_cache[positions[b]]; q [batch][q_heads][head_size] is rotated in place, k is rotated and written to
  * k_cache[b][head][slot][:], v is copied to v_cache[b][head][slot][:] (caches [batch][k_heads][max_positions][head_size]).
