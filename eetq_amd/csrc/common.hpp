@@ -265,6 +265,9 @@ int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue
                      hipStream_t stream);
 // input gradient dx[M][K] = dy[M][N] . fp16(q s)^T of the int8 weight in its native [K][N] layout (gemm_t.hip)
 int launch_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, int M, int N, int K, hipStream_t stream);
+// the same per expert over an [E][K][N] stack: rows offsets[e] .. offsets[e + 1] - 1 of dy [S][N] / dx [S][K] (gemm_t.hip)
+int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
+                      int E, int N, int K, hipStream_t stream);
 int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows, int cols, hipStream_t stream);
 int launch_rotary(const int64_t* pos, f16* q, f16* k, const f16* cache, int tokens, int q_heads, int k_heads,
                   int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream);

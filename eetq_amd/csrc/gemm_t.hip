@@ -51,8 +51,20 @@ struct Regs {
     f16   sc;
 };
 
+// One kernel, two row maps.  GROUPED = false: the plain problem dx[M][K] = dy[M][N] . fp16(q s)^T (eetq_w8a16_gemm_t); the
+// trailing arguments are unused.  GROUPED = true (eetq_w8a16_moe_gemm_t): the stack w [E][K][N] (each expert the gfx950 layout,
+// K * N bytes apart), scales [E][N]; expert e's problem is the contiguous sorted rows offsets[e] .. offsets[e + 1] - 1 of
+// dy [S][N] and dx [S][K], M = A = the length of the active list.  The grid is R row-tile slots x ceil(K / 128)
+// column tiles, R = floor(S / 128) + min(E, S) >= sum_e ceil(c_e / 128) whatever the routing; slot r is the r-th row tile in the
+// order of the active list (ascending experts, padded with -1).  Every wave finds its slot's expert on its own: lane l sums the
+// tile counts of active entries l * per .., an inclusive wave scan gives each lane's first tile, and the lane whose range holds
+// r hands (expert, first tile) to the others -- no LDS, no barrier; surplus slots exit before any load of the tile.  The tile
+// body then runs on the expert's rows with dy, dx and the weight and scale bases moved to them: rows past the expert's count
+// read its last row and are never stored.  The GROUPED = false instantiation is the kernel this file had before the grouped map.
+template <bool GROUPED>
 __global__ __launch_bounds__(256, 2) void gemm_t_kernel(const f16* __restrict__ dy, const uint8_t* __restrict__ w,
-                                                        const f16* __restrict__ scales, f16* __restrict__ dx, int M, int N, int K)
+                                                        const f16* __restrict__ scales, f16* __restrict__ dx, int M, int N, int K,
+                                                        const int* __restrict__ offsets, const int* __restrict__ active, int R)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid  = threadIdx.x;
@@ -60,15 +72,69 @@ __global__ __launch_bounds__(256, 2) void gemm_t_kernel(const f16* __restrict__ 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wk = wave >> 1;
 
-    const int tiles_m = (M + BM - 1) / BM;
-    const int T       = tiles_m * ((K + BK - 1) / BK);
-    int       tile;
-    {   // each XCD gets a contiguous run of tiles; row tiles fastest, so an XCD's workgroups share weight columns in its L2
-        const int b = blockIdx.x, q = T >> 3, r = T & 7, xcd = b & 7, idx = b >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    int m0, k0;
+    if constexpr (!GROUPED) {
+        const int tiles_m = (M + BM - 1) / BM;
+        const int T       = tiles_m * ((K + BK - 1) / BK);
+        int       tile;
+        {   // each XCD gets a contiguous run of tiles; row tiles fastest, so an XCD's workgroups share weight columns in its L2
+            const int b = blockIdx.x, q = T >> 3, r = T & 7, xcd = b & 7, idx = b >> 3;
+            tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        }
+        m0 = (tile % tiles_m) * BM;
+        k0 = (tile / tiles_m) * BK;
+    } else {
+        const int A = M;
+        const int T = R * ((K + BK - 1) / BK);
+        int       tile;
+        {   // the same XCD order: one expert's row tiles of a column tile share an L2
+            const int b = blockIdx.x, q = T >> 3, r = T & 7, xcd = b & 7, idx = b >> 3;
+            tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        }
+        const int slot = tile % R;
+        k0             = (tile / R) * BK;
+        const int per  = (A + 63) >> 6;
+        int       mine = 0;
+        for (int i = 0; i < per; ++i) {
+            const int a = lane * per + i;
+            const int e = a < A ? active[a] : -1;
+            if (e >= 0) mine += (offsets[e + 1] - offsets[e] + BM - 1) / BM;
+        }
+        int inc = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        const int first = inc - mine;
+        const unsigned long long hit = __ballot(slot >= first && slot < inc);
+        if (hit == 0) return;  // beyond the routing's row tiles (the same answer in every wave)
+        const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(hit));
+        int       e = -1, t0 = 0;
+        if (lane == src) {  // walk this lane's entries to the one holding the slot
+            int t = first;
+            for (int i = 0; i < per; ++i) {
+                const int a  = lane * per + i;
+                const int ea = a < A ? active[a] : -1;
+                const int n  = ea >= 0 ? (offsets[ea + 1] - offsets[ea] + BM - 1) / BM : 0;
+                if (slot < t + n) {
+                    e  = ea;
+                    t0 = t;
+                    break;
+                }
+                t += n;
+            }
+        }
+        e  = __builtin_amdgcn_readfirstlane(__shfl(e, src, 64));
+        t0 = __builtin_amdgcn_readfirstlane(__shfl(t0, src, 64));
+        const int p0 = offsets[e];
+        M            = offsets[e + 1] - p0;
+        m0           = (slot - t0) * BM;
+        dy += (size_t)p0 * N;
+        dx += (size_t)p0 * K;
+        w += (size_t)e * K * N;
+        scales += (size_t)e * N;
     }
-    const int m0 = (tile % tiles_m) * BM;
-    const int k0 = (tile / tiles_m) * BK;
     const int KT = K >> 6, NT = N >> 4;
     const int NS = (N + BN - 1) / BN;
 
@@ -231,8 +297,20 @@ int launch_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, i
 {
     using namespace gemm_t;
     const int tiles = ((M + BM - 1) / BM) * ((K + BK - 1) / BK);
-    launch_kernel(gemm_t_kernel, dim3(tiles), dim3(256), SMEM_BYTES, stream, dy, w, scales, dx, M, N, K);
+    launch_kernel(gemm_t_kernel<false>, dim3(tiles), dim3(256), SMEM_BYTES, stream, dy, w, scales, dx, M, N, K, (const int*)nullptr,
+                  (const int*)nullptr, 0);
     return check_hip(hipGetLastError(), "gemm_t_kernel launch");
+}
+
+int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
+                      int E, int N, int K, hipStream_t stream)
+{
+    using namespace gemm_t;
+    const int A = S < E ? S : E;
+    const int R = S / BM + A;
+    launch_kernel(gemm_t_kernel<true>, dim3(R * ((K + BK - 1) / BK)), dim3(256), SMEM_BYTES, stream, dy, w, scales, dx, A, N, K,
+                  offsets, active, R);
+    return check_hip(hipGetLastError(), "gemm_t_kernel<grouped> launch");
 }
 
 }  // namespace eetq

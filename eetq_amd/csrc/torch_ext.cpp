@@ -866,29 +866,50 @@ std::vector<Tensor> w8_a16_gemv_grouped(const std::vector<Tensor>& inputs, const
 // down_scale fp16 [E, H].  T <= 16: route -> grouped GEMM (gather, silu_glu8) -> grouped GEMM (sorted rows) -> combine, four
 // launches, no host sync (capturable).  T > 16: the expert counts are read back once and every active expert's rows run through
 // the AUTO W8A16 GEMMs, then the same combine (not capturable).  Ids outside [0, E) contribute nothing.
+// the argument checks the layer's three entries share (`fn` names the caller in the messages): the expert stacks ...
+struct MoeShape {
+    int64_t E, H, N1, I;
+};
+
+MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, c10::Device dev)
+{
+    TORCH_CHECK(gu_w.dim() == 3 && dn_w.dim() == 3 && gu_w.scalar_type() == at::kChar && dn_w.scalar_type() == at::kChar &&
+                    gu_s.scalar_type() == at::kHalf && dn_s.scalar_type() == at::kHalf,
+                fn, ": expert weights must be int8 [E, K, N] stacks and scales float16 [E, N]");
+    const int64_t E = gu_w.size(0), H = gu_w.size(1), N1 = gu_w.size(2), I = N1 / 2;
+    TORCH_CHECK(N1 == 2 * I && dn_w.size(0) == E && dn_w.size(1) == I && dn_w.size(2) == H && gu_s.dim() == 2 && gu_s.size(0) == E &&
+                    gu_s.size(1) == N1 && dn_s.dim() == 2 && dn_s.size(0) == E && dn_s.size(1) == H,
+                fn, ": expected gate_up_weight [E, H, 2I], gate_up_scale [E, 2I], down_weight [E, I, H], down_scale [E, H]");
+    TORCH_CHECK(H % 64 == 0 && I % 64 == 0, fn, ": the gfx950 layout needs H % 64 == 0 and I % 64 == 0");
+    TORCH_CHECK(gu_w.is_contiguous() && gu_s.is_contiguous() && dn_w.is_contiguous() && dn_s.is_contiguous(),
+                fn, ": expert weights and scales must be contiguous");
+    for (const Tensor* t : {&gu_w, &gu_s, &dn_w, &dn_s})
+        TORCH_CHECK(t->device() == dev, fn, ": all tensors must be on the hidden states' device");
+    return {E, H, N1, I};
+}
+
+// ... and, for the forwards, the hidden states and the routing
+MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights,
+                   const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+{
+    TORCH_CHECK(hidden_in.is_cuda() && hidden_in.scalar_type() == at::kHalf && hidden_in.dim() == 2,
+                fn, ": hidden must be a float16 GPU tensor [T, H]");
+    const auto     dev = hidden_in.device();
+    const MoeShape m   = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, dev);
+    TORCH_CHECK(hidden_in.size(1) == m.H, fn, ": hidden is [T, ", hidden_in.size(1), "] but gate_up_weight has H = ", m.H);
+    TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden_in.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
+                fn, ": top_k_index and top_k_weights must both be [T, k]");
+    TORCH_CHECK(top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf,
+                fn, ": top_k_weights must be float32 or float16");
+    TORCH_CHECK(top_k_index.device() == dev && top_k_weights.device() == dev, fn, ": all tensors must be on the hidden states' device");
+    return m;
+}
+
 Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
                   const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
 {
-    TORCH_CHECK(hidden_in.is_cuda() && hidden_in.scalar_type() == at::kHalf && hidden_in.dim() == 2,
-                "w8_a16_moe: hidden must be a float16 GPU tensor [T, H]");
-    const auto dev = hidden_in.device();
-    TORCH_CHECK(gu_w.dim() == 3 && dn_w.dim() == 3 && gu_w.scalar_type() == at::kChar && dn_w.scalar_type() == at::kChar &&
-                    gu_s.scalar_type() == at::kHalf && dn_s.scalar_type() == at::kHalf,
-                "w8_a16_moe: expert weights must be int8 [E, K, N] stacks and scales float16 [E, N]");
-    const int64_t E = gu_w.size(0), H = gu_w.size(1), N1 = gu_w.size(2), I = N1 / 2;
-    TORCH_CHECK(hidden_in.size(1) == H, "w8_a16_moe: hidden is [T, ", hidden_in.size(1), "] but gate_up_weight has H = ", H);
-    TORCH_CHECK(N1 == 2 * I && dn_w.size(0) == E && dn_w.size(1) == I && dn_w.size(2) == H && gu_s.dim() == 2 && gu_s.size(0) == E &&
-                    gu_s.size(1) == N1 && dn_s.dim() == 2 && dn_s.size(0) == E && dn_s.size(1) == H,
-                "w8_a16_moe: expected gate_up_weight [E, H, 2I], gate_up_scale [E, 2I], down_weight [E, I, H], down_scale [E, H]");
-    TORCH_CHECK(H % 64 == 0 && I % 64 == 0, "w8_a16_moe: the gfx950 layout needs H % 64 == 0 and I % 64 == 0");
-    TORCH_CHECK(gu_w.is_contiguous() && gu_s.is_contiguous() && dn_w.is_contiguous() && dn_s.is_contiguous(),
-                "w8_a16_moe: expert weights and scales must be contiguous");
-    TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden_in.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
-                "w8_a16_moe: top_k_index and top_k_weights must both be [T, k]");
-    TORCH_CHECK(top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf,
-                "w8_a16_moe: top_k_weights must be float32 or float16");
-    for (const Tensor* t : {&top_k_index, &top_k_weights, &gu_w, &gu_s, &dn_w, &dn_s})
-        TORCH_CHECK(t->device() == dev, "w8_a16_moe: all tensors must be on the hidden states' device");
+    const auto [E, H, N1, I] = moe_check("w8_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
+    const auto dev           = hidden_in.device();
     const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
     Tensor        out = torch::empty({T, H}, hidden_in.options());
     if (T == 0) return out;
@@ -929,6 +950,142 @@ Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tens
                                wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
                                (int)H, st));
     return out;
+}
+
+// Trainable forward of the layer (extension): the same `out` as w8_a16_moe bit for bit, plus what the backward
+// reads -- the routing tables (int32, eetq_moe_route's counts | offsets | sorted_slot | position | active), gate_up [T*k, 2I] (the
+// gate|up projection of every sorted row, glu8 column order, before the activation) and y [T*k, H] (each sorted row's down
+// projection, before the router weighting).  Rows past offsets[E] of both are unspecified.  T <= 16: route -> grouped GEMM
+// (gather, plain) -> eetq_silu_mul_glu8_f16 -> grouped GEMM -> combine, no host sync; the glu8 epilogue of w8_a16_moe is the
+// projection followed by that launch bit for bit.  T > 16: w8_a16_moe's host path with each expert's gate|up run plain on the
+// kernel its gated write-out uses (the stream kernel for 2 to 16 rows, AUTO otherwise), then one silu_mul over all rows.
+std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden_in, const Tensor& top_k_index,
+                                                            const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
+                                                            const Tensor& dn_w, const Tensor& dn_s)
+{
+    const auto [E, H, N1, I] = moe_check("w8_a16_moe_train", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
+    const auto    dev = hidden_in.device();
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    Tensor        out     = torch::empty({T, H}, hidden_in.options());
+    Tensor        tables  = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor        gate_up = torch::empty({S, N1}, hidden_in.options());
+    Tensor        down    = torch::empty({S, H}, hidden_in.options());
+    if (T == 0) return {out, tables, gate_up, down};
+    c10::DeviceGuard guard(dev);
+    void*        st     = stream_of(hidden_in);
+    const Tensor hidden = hidden_in.contiguous();
+    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
+    const Tensor wts    = top_k_weights.contiguous();
+    int*         counts = tables.data_ptr<int>();
+    int *        offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
+    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
+    if (T <= 16) {
+        Tensor inter = torch::empty({S, I}, hidden.options());
+        check(eetq_w8a16_moe_gemm(hidden.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, sorted, active,
+                                  gate_up.data_ptr(), (int)T, (int)k, (int)E, (int)N1, (int)H, 1, 0, st));
+        check(eetq_silu_mul_glu8_f16(gate_up.data_ptr(), inter.data_ptr(), (int)S, (int)I, st));
+        check(eetq_w8a16_moe_gemm(inter.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, sorted, active,
+                                  down.data_ptr(), (int)T, (int)k, (int)E, (int)H, (int)I, 0, 0, st));
+    } else {
+        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the prompt path
+        const int*   ch       = counts_h.data_ptr<int>();
+        const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
+        int64_t      off      = 0;
+        for (int64_t e = 0; e < E; ++e) {
+            const int64_t c = ch[e];
+            if (!c) continue;
+            const Tensor tok  = sorted_t.narrow(0, off, c).div(k, "floor");
+            Tensor       rows = gate_up.narrow(0, off, c);
+            gemm_launch(hidden.index_select(0, tok), gu_w[e], gu_s[e], rows, c, N1, H,
+                        c >= 2 && c <= 16 ? EETQ_PATH_STREAM : EETQ_PATH_AUTO, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
+            off += c;
+        }
+        if (off) {
+            const Tensor inter = silu_mul(gate_up.narrow(0, 0, off), true);
+            off                = 0;
+            for (int64_t e = 0; e < E; ++e) {
+                const int64_t c = ch[e];
+                if (!c) continue;
+                Tensor rows = down.narrow(0, off, c);
+                gemm_launch(inter.narrow(0, off, c), dn_w[e], dn_s[e], rows, c, H, I, EETQ_PATH_AUTO, std::nullopt, std::nullopt,
+                            EETQ_ACT_IDENTITY);
+                off += c;
+            }
+        }
+    }
+    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
+                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
+                               (int)H, st));
+    return {out, tables, gate_up, down};
+}
+
+// Backward of w8_a16_moe_train with the int8 weights frozen (extension): the gradients of the hidden states
+// (need_input_grad) and of top_k_weights (need_weights_grad, in their dtype), None where not asked for.  Five launches for any T,
+// no host sync (capturable), deterministic:
+//   eetq_moe_combine_bwd_f16 (dy = dout * w per sorted row, dw) -> eetq_w8a16_moe_gemm_t over the down stack (dh) ->
+//   eetq_silu_mul_glu8_bwd_f16 (dgate_up, glu8 order) -> eetq_w8a16_moe_gemm_t over the gate|up stack (per-slot dx) ->
+//   eetq_moe_combine_f16 with unit weights (the sum over each token's slots in j order).
+// The saved tensors are only read, so a retained graph can run it again.
+std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, const Tensor& top_k_weights, const Tensor& tables,
+                                                     const Tensor& gate_up, const Tensor& y, const Tensor& gu_w, const Tensor& gu_s,
+                                                     const Tensor& dn_w, const Tensor& dn_s, bool need_input_grad,
+                                                     bool need_weights_grad)
+{
+    TORCH_CHECK(grad_out.is_cuda() && grad_out.scalar_type() == at::kHalf && grad_out.dim() == 2,
+                "w8_a16_moe_backward: grad_out must be a float16 GPU tensor [T, H]");
+    const auto [E, H, N1, I] = moe_stacks("w8_a16_moe_backward", gu_w, gu_s, dn_w, dn_s, grad_out.device());
+    TORCH_CHECK(grad_out.size(1) == H, "w8_a16_moe_backward: grad_out is [T, ", grad_out.size(1), "] but the experts have H = ", H);
+    TORCH_CHECK(top_k_weights.dim() == 2 && top_k_weights.size(0) == grad_out.size(0) && top_k_weights.device() == grad_out.device() &&
+                    (top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf),
+                "w8_a16_moe_backward: top_k_weights must be float32 or float16 [T, k] on grad_out's device");
+    const int64_t T = grad_out.size(0), k = top_k_weights.size(1), S = T * k, A = std::min(E, S);
+    TORCH_CHECK(tables.is_cuda() && tables.scalar_type() == at::kInt && tables.is_contiguous() && tables.dim() == 1 &&
+                    tables.numel() == E + (E + 1) + 2 * S + A && tables.device() == grad_out.device(),
+                "w8_a16_moe_backward: tables must be w8_a16_moe_train's int32 routing tables for these T, k and E");
+    TORCH_CHECK(gate_up.scalar_type() == at::kHalf && gate_up.is_contiguous() && gate_up.dim() == 2 && gate_up.size(0) == S &&
+                    gate_up.size(1) == N1 && gate_up.device() == grad_out.device(),
+                "w8_a16_moe_backward: gate_up must be w8_a16_moe_train's contiguous float16 [T*k, 2I]");
+    TORCH_CHECK(y.scalar_type() == at::kHalf && y.is_contiguous() && y.dim() == 2 && y.size(0) == S && y.size(1) == H &&
+                    y.device() == grad_out.device(),
+                "w8_a16_moe_backward: y must be w8_a16_moe_train's contiguous float16 [T*k, H]");
+    OptTensor gx, gw;
+    if (!need_input_grad && !need_weights_grad) return {gx, gw};
+    const Tensor wts = top_k_weights.contiguous();
+    if (T == 0) {
+        if (need_input_grad) gx = torch::empty({0, H}, grad_out.options());
+        if (need_weights_grad) gw = torch::empty_like(wts);
+        return {gx, gw};
+    }
+    c10::DeviceGuard guard(grad_out.device());
+    void*      st   = stream_of(grad_out);
+    Tensor     dout = grad_out.contiguous();  // a stride-0 gradient (out.sum().backward()) is materialised here
+    if (reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 != 0) dout = dout.clone();
+    const int* offsets  = tables.data_ptr<int>() + E;
+    const int* position = offsets + (E + 1) + S;
+    const int* active   = position + S;
+    const int  wdt      = wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16;
+    Tensor     dy       = torch::empty({S, H}, grad_out.options());
+    if (need_weights_grad) gw = torch::empty_like(wts);
+    check(eetq_moe_combine_bwd_f16(dout.data_ptr(), y.data_ptr(), position, wts.data_ptr(), wdt, dy.data_ptr(),
+                                   need_weights_grad ? gw->data_ptr() : nullptr, (int)T, (int)k, (int)H, st));
+    if (!need_input_grad) return {gx, gw};
+    // each temporary is released as soon as the next step has consumed it: the peak is dh + dgate_up (+ dy, dx per slot)
+    Tensor dh = torch::empty({S, I}, grad_out.options());
+    check(eetq_w8a16_moe_gemm_t(dy.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, active, dh.data_ptr(), (int)T,
+                                (int)k, (int)E, (int)H, (int)I, st));
+    dy.reset();
+    Tensor dgu = torch::empty({S, N1}, grad_out.options());
+    check(eetq_silu_mul_glu8_bwd_f16(gate_up.data_ptr(), dh.data_ptr(), dgu.data_ptr(), (int)S, (int)I, st));
+    dh.reset();
+    Tensor dxs = torch::empty({S, H}, grad_out.options());
+    check(eetq_w8a16_moe_gemm_t(dgu.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, active, dxs.data_ptr(), (int)T,
+                                (int)k, (int)E, (int)N1, (int)H, st));
+    dgu.reset();
+    const Tensor ones = torch::ones({T, k}, grad_out.options().dtype(at::kFloat));
+    gx                = torch::empty({T, H}, grad_out.options());
+    check(eetq_moe_combine_f16(dxs.data_ptr(), position, ones.data_ptr(), EETQ_DTYPE_F32, gx->data_ptr(), (int)T, (int)k, (int)H,
+                               st));
+    return {gx, gw};
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -991,5 +1148,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("w8_a16_moe", &w8_a16_moe, "routed W8A16 mixture-of-experts layer over int8 expert stacks", py::arg("hidden"),
           py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
           py::arg("down_qweight"), py::arg("down_scales"));
+    m.def("w8_a16_moe_train", &w8_a16_moe_train,
+          "trainable forward of the routed W8A16 experts layer: (out, routing tables, gate_up, y) for w8_a16_moe_backward",
+          py::arg("hidden"), py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"));
+    m.def("w8_a16_moe_backward", &w8_a16_moe_backward,
+          "input and router-weight gradients of the routed W8A16 experts layer (frozen int8 weights)", py::arg("grad_out"),
+          py::arg("top_k_weights"), py::arg("tables"), py::arg("gate_up"), py::arg("y"), py::arg("gate_up_qweight"),
+          py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("need_input_grad") = true,
+          py::arg("need_weights_grad") = true);
     m.attr("__eetq_amd_version__") = eetq_version();
 }

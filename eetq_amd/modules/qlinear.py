@@ -16,10 +16,12 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe
+from ..ops import (preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward,
+                   w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
-__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad"]
+__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
+           "W8A16MoeFunction"]
 
 
 def quantize_and_preprocess_weights(weight, scales=None):
@@ -41,7 +43,12 @@ def quantize_and_preprocess_weights(weight, scales=None):
 
 
 class W8A16Linear(nn.Module):
-    """Inference-only linear layer: int8 weight ``qweight`` [in, out], fp16 ``weight_scales`` [out]."""
+    """Linear layer over an int8 weight ``qweight`` [in, out], fp16 ``weight_scales`` [out].  Inference-only unless ``trainable``
+    is set (``eet_quantize(..., trainable=True)`` or ``utils.set_trainable``): then a call in grad mode whose input requires grad
+    and that passes no extension argument runs through :class:`EetqLinearMMFunction` -- the same output bits, and an input
+    gradient from ``w8_a16_gemm_t`` (the int8 weight stays frozen)."""
+
+    trainable = False   # a plain attribute, not a buffer: state dicts do not change
 
     def __init__(self, in_features, out_features, bias=True, dev="cuda:0"):
         super().__init__()
@@ -70,8 +77,14 @@ class W8A16Linear(nn.Module):
         mod.weight_scales = scales.half().to(dev)
         return mod
 
-    @torch.no_grad()
     def forward(self, input, residual=None, norm=None, gated=False, activation=""):
+        if (self.trainable and torch.is_grad_enabled() and input.requires_grad and residual is None and norm is None
+                and not gated and not activation):
+            return EetqLinearMMFunction.apply(input, self.qweight, self.weight_scales, self.bias)
+        with torch.no_grad():
+            return self._forward(input, residual, norm, gated, activation)
+
+    def _forward(self, input, residual, norm, gated, activation):
         # bias is fused into the kernel epilogue: same bits as the reference's `output + self.bias` (qlinear.py:61);
         # `residual` (extension) is added after it in the same epilogue: the decoder block's `residual + proj(x)`
         # `norm=(gamma, eps)` (extension): RMS-norm of the input, fused into the launch for single-row inputs
@@ -132,8 +145,14 @@ class W8A16Experts(nn.Module):
     matching 8 up per 16-column tile), ``gate_up_scales`` fp16 [E, 2I] (same order), ``down_qweight`` int8 [E, I, H],
     ``down_scales`` fp16 [E, H].  Runs ``ops.w8_a16_moe``.
 
+    Inference-only unless ``trainable`` is set (``eet_quantize(..., trainable=True)`` or ``utils.set_trainable``): then a call in
+    grad mode with ``hidden_states`` or ``top_k_weights`` requiring grad runs through :class:`W8A16MoeFunction` -- the same
+    output bits, and gradients for both (the int8 stacks stay frozen).
+
     State dicts hold the stacks in this library's gfx950 layout, unlike W8A16Linear's: the reference has no experts module, so
     there is no CUDA-written checkpoint to stay compatible with, and the glu8 column order has no counterpart in its layout."""
+
+    trainable = False   # a plain attribute, not a buffer: state dicts do not change
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
         super().__init__()
@@ -194,11 +213,15 @@ class W8A16Experts(nn.Module):
             mod.down_scales = s.half().to(gu.device)
         return mod
 
-    @torch.no_grad()
     def forward(self, hidden_states, top_k_index, top_k_weights):
         """T <= 16 tokens: four launches, no host sync (capturable); more: one read-back of the expert counts (not capturable)."""
-        return w8_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
-                          self.down_qweight, self.down_scales)
+        if (self.trainable and torch.is_grad_enabled()
+                and (hidden_states.requires_grad or top_k_weights.requires_grad)):
+            return W8A16MoeFunction.apply(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                                          self.down_qweight, self.down_scales)
+        with torch.no_grad():
+            return w8_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                              self.down_qweight, self.down_scales)
 
     def extra_repr(self):
         return "num_experts={}, hidden_dim={}, intermediate_dim={}".format(self.num_experts, self.hidden_dim,
@@ -234,6 +257,26 @@ class EetqLinearMMFunction(Function):
         if ctx.needs_input_grad[0]:
             grad_input = input_grad(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
         return grad_input, None, None, None
+
+
+class W8A16MoeFunction(Function):
+    """Autograd wrapper of the routed experts layer: forward = ``w8_a16_moe_train`` (the output bits of
+    ``w8_a16_moe``), which also returns the routing tables, the gate|up projection and the per-slot down projection the backward
+    reads; backward = ``w8_a16_moe_backward``: gradients of ``hidden_states`` and ``top_k_weights`` (the int8 stacks are frozen,
+    the expert ids are integers).  The hidden states themselves are not saved."""
+
+    @staticmethod
+    def forward(ctx, hidden_states, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s):
+        out, tables, gate_up, y = w8_a16_moe_train(hidden_states, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s)
+        ctx.save_for_backward(top_k_weights, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        wts, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        grad_x, grad_w = w8_a16_moe_backward(grad_output, wts, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s, need_x, need_w)
+        return grad_x, None, grad_w, None, None, None, None
 
 
 class EetqLinear(nn.Module):

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ..modules.qlinear import W8A16Experts, W8A16Linear
 
-__all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears"]
+__all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable"]
 
 
 def find_layers(module, include=(nn.Linear,), exclude=("lm_head",)):
@@ -62,7 +62,21 @@ def _experts_modules(model):
     return found
 
 
-def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False):
+def set_trainable(model, flag=True):
+    """Set the ``trainable`` flag of every :class:`W8A16Linear` and :class:`W8A16Experts` in ``model`` (itself included) and
+    return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to the router weights)
+    in grad mode; their int8 weights stay frozen and their output bits do not change.  Off by default: untrainable modules
+    return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, (W8A16Linear, W8A16Experts)):
+            m.trainable = bool(flag)
+            n += 1
+    return n
+
+
+def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False,
+                 trainable=False):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
@@ -71,6 +85,8 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     ``experts=True`` (extension) also replaces every mixture-of-experts experts module that :class:`W8A16Experts` supports
     (3-D gated SiLU expert stacks: Mixtral, Qwen2/3-MoE, OLMoE, DeepSeek-V3 ...); unsupported ones stay as they are and are
     named in one warning.  The default leaves experts modules untouched.
+    ``trainable=True`` (extension) then sets the flag of :func:`set_trainable` on every quantised module of the model, so that
+    gradients cross them (fine-tuning adapters or prompts on a frozen int8 model).
     """
     if experts:
         skipped = []
@@ -108,4 +124,6 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
         if not init_only and torch.cuda.is_available():
             torch.cuda.empty_cache()
     gc.collect()
+    if trainable:
+        set_trainable(model, True)
     return model

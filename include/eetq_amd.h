@@ -288,6 +288,30 @@ int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scale
 int eetq_moe_combine_f16(const void* y, const int* position, const void* weights, int w_dtype, void* out, int T, int k, int H,
                          void* stream);
 
+/* ---- mixture-of-experts backward (extension, additive within ABI revision 7) --------------------------------
+ * The input and router-weight gradients of the layer above with its int8 weights frozen (no weight gradients), on the tables
+ * eetq_moe_route wrote and the sorted rows the forward kept.  Grids fixed by the shapes, no host sync, no atomics: deterministic
+ * and capturable.
+ *
+ * eetq_w8a16_moe_gemm_t: grouped eetq_w8a16_gemm_t over an expert stack w_packed [E][K][N] (each expert the GFX950 layout, K*N bytes
+ *   apart), scales fp16 [E][N]: for every expert e, rows p = offsets[e] .. offsets[e+1] - 1 of dy fp16 [T*k][N] give the same
+ *   rows of dx fp16 [T*k][K] = dy . fp16(q_e s_e)^T, bit for bit eetq_w8a16_gemm_t on those rows and expert e's weight.  Rows of dx
+ *   not in any active expert are not written.  offsets / active as eetq_moe_route wrote them.  Needs K % 64 == 0, N % 16 == 0,
+ *   dy / w_packed / dx 16-byte aligned, E and k as in eetq_moe_route; else EETQ_ERR_INVALID. */
+int eetq_w8a16_moe_gemm_t(const void* dy, const int8_t* w_packed, const void* scales, const int* offsets, const int* active, void* dx,
+                          int T, int k, int E, int N, int K, void* stream);
+/* eetq_moe_combine_bwd_f16: for every slot t*k + j with p = position[t*k + j] >= 0:
+ *   dy[p][h] = fp16( fp32(dout[t][h]) * fp32(weights[t][j]) ),   dw[t][j] = sum_h fp32(dout[t][h]) * fp32(y[p][h]) (fixed order),
+ *   and dw[t][j] = 0 for slots with p = -1.  dout fp16 [T][H], y / dy fp16 [*][H] (sorted rows), weights / dw [T][k] of w_dtype
+ *   EETQ_DTYPE_F32 or EETQ_DTYPE_F16; dw = NULL skips the router gradient.  H % 8 == 0, dout / y / dy 16-byte aligned. */
+int eetq_moe_combine_bwd_f16(const void* dout, const void* y, const int* position, const void* weights, int w_dtype, void* dy,
+                             void* dw, int T, int k, int H, void* stream);
+/* eetq_silu_mul_glu8_bwd_f16: backward of eetq_silu_mul_glu8_f16.  gate_up [rows][2 * intermediate] in glu8 order (the forward's
+ *   input), dh [rows][intermediate] (the gradient of its output), dgate_up [rows][2 * intermediate] in the same glu8 order:
+ *   du = fp16(dh * s) with s the forward's fp16 silu(g); dg = fp16( fp32(dh) * fp32(u) * sig * (1 + g (1 - sig)) ), sig = sigmoid(g).
+ *   intermediate % 8 == 0, 16-byte aligned pointers. */
+int eetq_silu_mul_glu8_bwd_f16(const void* gate_up, const void* dh, void* dgate_up, int rows, int intermediate, void* stream);
+
 /* Decode-step rotary + KV-cache write (extension for the EET attention blocks): one new token per batch row b, rotated
  * by cos_sin_cache[positions[b]]; q [batch][q_heads][head_size] is rotated in place, k is rotated and written to
  * k_cache[b][head][slot][:], v is copied to v_cache[b][head][slot][:] (caches [batch][k_heads][max_positions][head_size]).

@@ -5,6 +5,14 @@ experts forward (MixtralExperts) on the same routing, and a Python loop of per-e
 silu_glu8, down, weighted index_add).  Weights are random (int8 stacks, small fp16 scales): the time depends on shapes only.
 
     python tools/moe_bench.py --out profiles/r07_moe_bench.jsonl
+
+--backward times the training path instead, at --tokens (default 16,64,512,4096), uniform routing: the no-grad
+forward (w8_a16_moe), the trainable forward (w8_a16_moe_train), the backward (w8_a16_moe_backward, both gradients) and each of
+its five launches on its own, the two grouped input-gradient GEMMs against a Python loop of per-expert w8_a16_gemm_t calls after
+a host read-back of the expert counts, and transformers' eager fp16 experts forward + backward (frozen fp16 stacks).  Memory:
+the trainable forward's saved tensors and the backward's peak above what was allocated before it.
+
+    python tools/moe_bench.py --backward --out profiles/r08_moe_backward_bench.jsonl
 """
 import argparse
 import json
@@ -43,14 +51,130 @@ def _routing(T, k, E, kind, g):
     return torch.cat([torch.zeros(T, 1, dtype=torch.long), rest], 1).to(DEV)
 
 
+def _ptr(t):
+    import ctypes
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def backward(args, out):
+    import ctypes
+
+    from transformers import MixtralConfig
+    from transformers.models.mixtral.modeling_mixtral import MixtralExperts
+
+    from eetq_amd import _lib
+    from eetq_amd.ops import w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train
+    L = _lib.lib()
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        gu_w = torch.randint(-127, 128, (E, H, 2 * I), dtype=torch.int8, device=DEV)
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-3).half()
+        dn_w = torch.randint(-127, 128, (E, I, H), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-3).half()
+        stacks = (gu_w, gu_s, dn_w, dn_s)
+        cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=k)
+        cfg._experts_implementation = "eager"
+        eager = MixtralExperts(cfg).half().to(DEV)
+        with torch.no_grad():
+            eager.gate_up_proj.normal_(0, 0.02)
+            eager.down_proj.normal_(0, 0.02)
+        eager.requires_grad_(False)
+        g = torch.Generator().manual_seed(1)
+        for T in (int(t) for t in args.tokens.split(",")):
+            S = T * k
+            x = (torch.rand(T, H, device=DEV) - 0.5).half()
+            idx = _routing(T, k, E, "uniform", g)
+            wts = torch.rand(T, k, device=DEV).softmax(-1)
+            dout = (torch.rand(T, H, device=DEV) - 0.5).half()
+            active = torch.unique(idx).tolist()
+            us_fwd = _time(lambda: w8_a16_moe(x, idx, wts, *stacks), args.warmup, args.iters)
+            us_train = _time(lambda: w8_a16_moe_train(x, idx, wts, *stacks), args.warmup, args.iters)
+            torch.cuda.synchronize()
+            m0 = torch.cuda.memory_allocated()
+            o, tables, gate_up, y = w8_a16_moe_train(x, idx, wts, *stacks)
+            torch.cuda.synchronize()
+            saved = torch.cuda.memory_allocated() - m0 - o.numel() * 2
+            us_bwd = _time(lambda: w8_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks, True, True), args.warmup, args.iters)
+            torch.cuda.synchronize()
+            m1 = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            w8_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks, True, True)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - m1
+            # the five launches one at a time, on the tensors the backward makes
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            offsets, position = tables[E:], tables[2 * E + 1 + S:]
+            active_t = tables[2 * E + 1 + 2 * S:]
+            dy = torch.empty(S, H, dtype=torch.float16, device=DEV)
+            dw = torch.empty_like(wts)
+            dh = torch.empty(S, I, dtype=torch.float16, device=DEV)
+            dgu = torch.empty(S, 2 * I, dtype=torch.float16, device=DEV)
+            dxs = torch.empty(S, H, dtype=torch.float16, device=DEV)
+            dx = torch.empty(T, H, dtype=torch.float16, device=DEV)
+            ones = torch.ones(T, k, device=DEV)
+            steps = {
+                "combine_bwd": lambda: L.eetq_moe_combine_bwd_f16(_ptr(dout), _ptr(y), _ptr(position), _ptr(wts), 1, _ptr(dy),
+                                                                  _ptr(dw), T, k, H, st),
+                "gemm_t_down": lambda: L.eetq_w8a16_moe_gemm_t(_ptr(dy), _ptr(dn_w), _ptr(dn_s), _ptr(offsets), _ptr(active_t),
+                                                               _ptr(dh), T, k, E, H, I, st),
+                "silu_bwd": lambda: L.eetq_silu_mul_glu8_bwd_f16(_ptr(gate_up), _ptr(dh), _ptr(dgu), S, I, st),
+                "gemm_t_gate_up": lambda: L.eetq_w8a16_moe_gemm_t(_ptr(dgu), _ptr(gu_w), _ptr(gu_s), _ptr(offsets),
+                                                                  _ptr(active_t), _ptr(dxs), T, k, E, 2 * I, H, st),
+                "combine": lambda: L.eetq_moe_combine_f16(_ptr(dxs), _ptr(position), _ptr(ones), 1, _ptr(dx), T, k, H, st),
+            }
+            split = {n: round(_time(f, args.warmup, args.iters), 2) for n, f in steps.items()}
+
+            def loop():   # the workaround: host read-back, then per-expert w8_a16_gemm_t for both projections
+                counts = tables[:E].cpu().tolist()
+                off = 0
+                for e in range(E):
+                    c = counts[e]
+                    if c:
+                        w8_a16_gemm_t(dy[off:off + c], dn_w[e], dn_s[e])
+                        w8_a16_gemm_t(dgu[off:off + c], gu_w[e], gu_s[e])
+                        off += c
+            us_loop = _time(loop, args.warmup, args.iters)
+            xe = x.clone().requires_grad_()
+            we = wts.clone().requires_grad_()
+
+            def eager_fb():
+                out_e = eager(xe, idx, we)
+                out_e.backward(dout)
+            us_eager = _time(eager_fb, max(1, args.warmup // 2), max(3, args.iters // 4))
+            grouped = split["gemm_t_down"] + split["gemm_t_gate_up"]
+            rec = {"shape": name, "H": H, "I": I, "E": E, "k": k, "T": T, "routing": "uniform", "active_experts": len(active),
+                   "us_fwd_nograd": round(us_fwd, 2), "us_fwd_trainable": round(us_train, 2), "us_backward": round(us_bwd, 2),
+                   "us_backward_split": split, "us_grouped_gemm_t": round(grouped, 2),
+                   "us_per_expert_gemm_t_loop": round(us_loop, 2), "loop_over_grouped": round(us_loop / grouped, 2),
+                   "bwd_over_trainable_fwd": round(us_bwd / us_train, 3),
+                   "us_fp16_eager_fwd_bwd": round(us_eager, 2),
+                   "saved_bytes": saved, "backward_peak_bytes": peak}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            del o, tables, gate_up, y, dy, dh, dgu, dxs, dx
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--tokens", default="1,2,4,8,16,64,512")
+    ap.add_argument("--tokens", default=None)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--backward", action="store_true", help="time the training path (DESIGN.md 4.11)")
     args = ap.parse_args()
+    if args.backward:
+        args.tokens = args.tokens or "16,64,512,4096"
+        out = open(args.out, "w") if args.out else None
+        backward(args, out)
+        if out:
+            out.close()
+        return
+    args.tokens = args.tokens or "1,2,4,8,16,64,512"
 
     from transformers import MixtralConfig
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts
