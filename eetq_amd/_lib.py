@@ -104,6 +104,8 @@ def _declare(L):
         "eetq_diag_splitk_plan": [i32, i32, i32, vp, vp, vp, vp],
         "eetq_moe_route": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp],
         "eetq_w8a16_moe_gemm": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+        "eetq_w8a16_moe_gemm_tiled": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+        "eetq_diag_moe_host_path": [],
         "eetq_moe_combine_f16": [vp, vp, vp, i32, vp, i32, i32, i32, vp],
         "eetq_w8a16_moe_gemm_t": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
         "eetq_moe_combine_bwd_f16": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp],
@@ -133,6 +135,7 @@ EXPORTED_SYMBOLS = (
     "eetq_quantize_workspace_floats", "eetq_release_workspace", "eetq_release_stream_workspace", "eetq_rotary_neox", "eetq_w8a16_gemv_grouped", "eetq_decode_dropped_steps",
     "eetq_moe_route", "eetq_w8a16_moe_gemm", "eetq_moe_combine_f16",
     "eetq_w8a16_moe_gemm_t", "eetq_moe_combine_bwd_f16", "eetq_silu_mul_glu8_bwd_f16",
+    "eetq_w8a16_moe_gemm_tiled", "eetq_diag_moe_host_path",
 )
 
 

@@ -268,6 +268,11 @@ int launch_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, i
 // the same per expert over an [E][K][N] stack: rows offsets[e] .. offsets[e + 1] - 1 of dy [S][N] / dx [S][K] (gemm_t.hip)
 int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
                       int E, int N, int K, hipStream_t stream);
+// grouped LDS-tiled forward over an [E][K][N] stack on eetq_moe_route's tables (moe_gemm_tiled.hip): the prompt path of the routed
+// experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs moe_gemm_kernel
+bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather);
+int  launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
+                           const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream);
 int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows, int cols, hipStream_t stream);
 int launch_rotary(const int64_t* pos, f16* q, f16* k, const f16* cache, int tokens, int q_heads, int k_heads,
                   int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream);

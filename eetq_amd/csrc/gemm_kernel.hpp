@@ -51,6 +51,17 @@ struct TileCfg {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
+// row map of the grouped form (gemm_tile_body, GROUPED): eetq_moe_route's device tables and the launch's shape-only bounds
+struct GroupMap {
+    const int* offsets     = nullptr;  // [E + 1]
+    const int* sorted_slot = nullptr;  // [S]; read when topk > 0
+    const int* active      = nullptr;  // [A], ascending experts, padded with -1
+    int        topk        = 0;        // > 0: gather token rows sorted_slot[p] / topk; 0: activation rows are the sorted rows
+    int        A           = 0;        // min(E, S)
+    int        R           = 0;        // row-tile slots: floor(S / 128) + A
+    int        x_rows      = 0;        // rows of x (T when gathering, S otherwise)
+};
+
 // LDS-DMA: 16 B per lane from a buffer (base in the descriptor, per-lane byte offset in voff, wave-uniform byte
 // offset in soff) straight into LDS at wave-uniform base + lane*16, no VGPR round trip.  The MUBUF form
 // (buffer_load_dwordx4 ... lds) is used rather than global_load_lds: hipcc treats the latter as a FLAT access
@@ -107,12 +118,22 @@ __device__ __forceinline__ f16x8 make_frag(f16x2 a, f16x2 b, f16x2 c, f16x2 d)
 // GLU (its own instantiation, identity rounding): the weight is in "glu8" column order (groups of 16 = 8 gate + the 8 matching up
 // columns); the fp16 image of the tile is written out as silu_mul(gate, up) -- y is [M][N / 2] with row stride ldc, what
 // eetq_silu_mul_glu8_f16 makes of the plain projection's output, without the [M][N] round trip through HBM.
-template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, int RH = 1, int RB = 1>
+// GROUPED (moe_gemm_tiled.hip): the same tile over an expert stack w [E][K][N] (each expert the gfx950 layout,
+// K * N bytes apart), scales [E][N].  Expert e's problem is the sorted rows offsets[e] .. offsets[e + 1] - 1 of y; the "row
+// tiles" of the tile order are map.R row-tile SLOTS, slot r = the r-th 128-row tile in the order of the active list.  Every
+// wave finds its slot's (expert, tile) on its own, as gemm_t_kernel<true> does: lane l sums the tile counts of active entries
+// l * per .., an inclusive wave scan gives each lane's first tile, the lane whose range holds the slot hands (expert, first
+// tile) to the others -- no LDS, no barrier; a surplus slot leaves before its first DMA request.  Then M, m0, y, w and scales
+// are the expert's, and only the activation pieces' source rows differ from the ungrouped tile: sorted row p0 + m of x [S][K],
+// or (map.topk > 0) the token row sorted_slot[p0 + m] / topk of x [T][K]; the descriptor spans map.x_rows rows.
+template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, int RH = 1, int RB = 1, bool GROUPED = false>
 __device__ __forceinline__ void gemm_tile_body(
     const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales,
     f16* __restrict__ y, int M, int N, int K, int ldc, Epilogue ep, int S, float* __restrict__ slabs,
-    unsigned* __restrict__ counters)
+    unsigned* __restrict__ counters, GroupMap map = GroupMap{})
 {
+    static_assert(!GROUPED || (!SPLIT && !ACT && RH == 1 && RB == 1 && CW == 2 && ABLATE == 0),
+                  "the grouped form exists for the unsplit 4-wave identity tile (plain and GLU)");
     // N = columns of THIS launch (w, scales, y, ep.* already point at its first column); ldc = row stride of y / residual
     EETQ_GEMM_STAMP(0);
     using Cfg = TileCfg<J, CW, RH, RB>;
@@ -135,7 +156,7 @@ __device__ __forceinline__ void gemm_tile_body(
     const int wn   = wave % CW;               // which 32*J-column part of the tile
     const int KT   = K >> 6;
 
-    const int tiles_m = (M + BMT - 1) / BMT;
+    const int tiles_m = GROUPED ? map.R : (M + BMT - 1) / BMT;
     const int tiles_n = (N + BN - 1) / BN;
     const int T       = tiles_m * tiles_n;
     int       tile, slice = 0, k0 = 0, ksteps = KT;  // this workgroup's K steps: [k0, k0 + ksteps)
@@ -161,14 +182,59 @@ __device__ __forceinline__ void gemm_tile_body(
     const int chunk   = tile / (kGroupM * tiles_n);
     const int in_ch   = tile - chunk * (kGroupM * tiles_n);
     const int ch_rows = tiles_m - chunk * kGroupM < kGroupM ? tiles_m - chunk * kGroupM : kGroupM;
-    const int m0 = (chunk * kGroupM + in_ch % ch_rows) * BMT;
+    int       m0 = (chunk * kGroupM + in_ch % ch_rows) * BMT;
     const int n0 = (in_ch / ch_rows) * BN;
+    int       p0 = 0;  // grouped: the expert's first sorted row
+    if constexpr (GROUPED) {
+        const int slot = chunk * kGroupM + in_ch % ch_rows;
+        const int A    = map.A;
+        const int per  = (A + 63) >> 6;
+        int       mine = 0;
+        for (int i = 0; i < per; ++i) {
+            const int a = lane * per + i;
+            const int e = a < A ? map.active[a] : -1;
+            if (e >= 0) mine += (map.offsets[e + 1] - map.offsets[e] + BM - 1) / BM;
+        }
+        int inc = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        const int                first = inc - mine;
+        const unsigned long long hit   = __ballot(slot >= first && slot < inc);
+        if (hit == 0) return;  // beyond the routing's row tiles (the same answer in every wave): nothing requested, nothing stored
+        const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(hit));
+        int       e = -1, t0 = 0;
+        if (lane == src) {  // walk this lane's entries to the one holding the slot
+            int t = first;
+            for (int i = 0; i < per; ++i) {
+                const int a  = lane * per + i;
+                const int ea = a < A ? map.active[a] : -1;
+                const int n  = ea >= 0 ? (map.offsets[ea + 1] - map.offsets[ea] + BM - 1) / BM : 0;
+                if (slot < t + n) {
+                    e  = ea;
+                    t0 = t;
+                    break;
+                }
+                t += n;
+            }
+        }
+        e  = __builtin_amdgcn_readfirstlane(__shfl(e, src, 64));
+        t0 = __builtin_amdgcn_readfirstlane(__shfl(t0, src, 64));
+        p0 = __builtin_amdgcn_readfirstlane(map.offsets[e]);
+        M  = __builtin_amdgcn_readfirstlane(map.offsets[e + 1]) - p0;
+        m0 = (slot - t0) * BM;
+        y += (size_t)p0 * ldc;
+        w += (size_t)e * K * N;
+        scales += (size_t)e * N;
+    }
 
     // descriptors start kShift bytes below the operands: a piece's voff is pre-compensated by -(its instruction
     // offset), and must stay non-negative for the hardware's range check
     constexpr int kShift = 4096;
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<uint8_t*>(const_cast<f16*>(x)) - kShift, 0, (int)((size_t)M * K * 2) + kShift, 0x00020000);
+        reinterpret_cast<uint8_t*>(const_cast<f16*>(x)) - kShift, 0, (int)((size_t)(GROUPED ? map.x_rows : M) * K * 2) + kShift, 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t*>(w) - kShift, 0, (int)((size_t)N * K) + kShift, 0x00020000);
     // DMA pieces of this wave: i < APW: activation piece APW*wave + i (rows 8p..8p+7, 128 B each); i >= APW: weight tile
@@ -182,6 +248,10 @@ __device__ __forceinline__ void gemm_tile_body(
         const int slot = (lane & 7) ^ ((row >> 1) & 7);
         int       gm   = m0 + row;
         gm             = gm < M ? gm : M - 1;
+        if constexpr (GROUPED) {  // the expert's row -> sorted row -> (gather) the token's row
+            gm += p0;
+            if (map.topk > 0) gm = (int)((unsigned)map.sorted_slot[gm] / (unsigned)map.topk);
+        }
         dma_voff[i]    = (gm * K + slot * 8) * 2 + kShift - (i & 3) * 1024;  // the instruction offset: at most 3 KiB
     }
 #pragma unroll

@@ -354,6 +354,23 @@ __global__ __launch_bounds__(256) void silu_mul_glu8_bwd_kernel(const f16* __res
 
 bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
+// the argument checks eetq_w8a16_moe_gemm and eetq_w8a16_moe_gemm_tiled share (`fn` names the entry in the messages)
+int moe_gemm_check(const char* fn, const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
+                   const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8)
+{
+    const std::string f(fn);
+    EETQ_REQUIRE(x && w_packed && scales && offsets && active && y && (sorted_slot || !gather), f + ": null pointer");
+    EETQ_REQUIRE(E >= 1 && E <= kMoeMaxExperts, f + ": E must be in [1, 1024]");
+    EETQ_REQUIRE(k >= 1 && k <= E, f + ": k must be in [1, E]");
+    EETQ_REQUIRE(T >= 1 && (long long)T * k <= (1ll << 30), f + ": T must be >= 1 and T * k <= 2^30");
+    EETQ_REQUIRE(N >= kTileN && N % kTileN == 0 && K >= kTileK && K % kTileK == 0,
+                 f + ": the gfx950 layout needs K % 64 == 0 and N % 16 == 0");
+    EETQ_REQUIRE((gather == 0 || gather == 1) && (glu8 == 0 || glu8 == 1), f + ": gather and glu8 are 0 or 1");
+    EETQ_REQUIRE((long long)T * k * K < (1ll << 40) && (long long)E * K * N < (1ll << 40), f + ": activation or weight stack too large");
+    EETQ_REQUIRE(aligned16(x) && aligned16(w_packed) && aligned16(y), "x, weight and y must be 16-byte aligned");
+    return EETQ_OK;
+}
+
 }  // namespace
 
 }  // namespace eetq
@@ -385,16 +402,8 @@ int eetq_moe_route(const int64_t* top_k_index, int T, int k, int E, int* counts,
 int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
                         const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream)
 {
-    EETQ_REQUIRE(x && w_packed && scales && offsets && active && y && (sorted_slot || !gather), "eetq_w8a16_moe_gemm: null pointer");
-    EETQ_REQUIRE(E >= 1 && E <= kMoeMaxExperts, "eetq_w8a16_moe_gemm: E must be in [1, 1024]");
-    EETQ_REQUIRE(k >= 1 && k <= E, "eetq_w8a16_moe_gemm: k must be in [1, E]");
-    EETQ_REQUIRE(T >= 1 && (long long)T * k <= (1ll << 30), "eetq_w8a16_moe_gemm: T must be >= 1 and T * k <= 2^30");
-    EETQ_REQUIRE(N >= kTileN && N % kTileN == 0 && K >= kTileK && K % kTileK == 0,
-                 "eetq_w8a16_moe_gemm: the gfx950 layout needs K % 64 == 0 and N % 16 == 0");
-    EETQ_REQUIRE((gather == 0 || gather == 1) && (glu8 == 0 || glu8 == 1), "eetq_w8a16_moe_gemm: gather and glu8 are 0 or 1");
-    EETQ_REQUIRE((long long)T * k * K < (1ll << 40) && (long long)E * K * N < (1ll << 40),
-                 "eetq_w8a16_moe_gemm: activation or weight stack too large");
-    EETQ_REQUIRE(aligned16(x) && aligned16(w_packed) && aligned16(y), "x, weight and y must be 16-byte aligned");
+    const int st = moe_gemm_check("eetq_w8a16_moe_gemm", x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8);
+    if (st != EETQ_OK) return st;
     const int   S  = T * k;
     const int   A  = S < E ? S : E;
     const int   KT = K / kTileK;
@@ -408,6 +417,25 @@ int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scale
     if (KT >= 16) return launch_moe_gemm_inst<8, 2>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
     if (KT >= 8) return launch_moe_gemm_inst<4, 2>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
     return launch_moe_gemm_inst<1, 1>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
+}
+
+int eetq_w8a16_moe_gemm_tiled(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
+                              const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream)
+{
+    const int st = moe_gemm_check("eetq_w8a16_moe_gemm_tiled", x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8);
+    if (st != EETQ_OK) return st;
+    return launch_moe_gemm_tiled(static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed), static_cast<const f16*>(scales),
+                                 offsets, sorted_slot, active, static_cast<f16*>(y), T, k, E, N, K, gather != 0, glu8 != 0,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int eetq_diag_moe_host_path(void)
+{
+    static const bool on = [] {
+        const char* e = tuning_env("EETQ_AMD_MOE_HOST");
+        return e && e[0] == '1';
+    }();
+    return on ? 1 : 0;
 }
 
 int eetq_moe_combine_f16(const void* y, const int* position, const void* weights, int w_dtype, void* out, int T, int k, int H,

@@ -1,0 +1,92 @@
+// Grouped form of the LDS-tiled MFMA dequant-GEMM over an [E][K][N] int8 expert stack: the prompt path of the
+// routed-experts layer.  The kernel is gemm_tile_body (gemm_kernel.hpp) with its GROUPED row map -- the K loop, the ring, the gap
+// placement and the epilogues are the ungrouped tile's, so an expert's rows come out as eetq_w8a16_gemm_ex(EETQ_PATH_MFMA) makes
+// them from the gathered rows, bit for bit at the same tile shape.
+//
+//   * grid = R row-tile slots x column tiles, R = floor(S / 128) + min(E, S), S = T k: sum_e ceil(c_e / 128) <= R for any counts
+//     (every expert with rows has at most one ragged tile, and the full tiles cannot exceed floor(S / 128)), so the grid depends
+//     on the shapes only and the launch can be captured;
+//   * slot r is the r-th row tile in the order of the active list; a workgroup finds (expert, tile) from `offsets` / `active`
+//     with a wave scan and a ballot (no LDS, no barrier) and leaves before its first DMA request when the slot is surplus;
+//   * tile order: the ungrouped kernel's (XCD-contiguous runs, chunks of four row-tile slots, column tiles inside a chunk): the
+//     workgroups resident on an XCD cover 4 consecutive slots x 8 column tiles -- one expert's weight tiles shared by its row
+//     tiles wherever an expert has several (>= 512 rows), four experts' worth of distinct tiles otherwise, which is what any
+//     order must fetch there;
+//   * gather = 1: row p reads x[sorted_slot[p] / k] of x [T][K]; gather = 0: x[p] of x [S][K].  Rows past the expert's count
+//     read its last row and are never stored; rows at or past offsets[E] and rows of inactive experts are never written.
+#include "gemm_kernel.hpp"
+
+namespace eetq {
+
+using namespace gemm;
+
+namespace {
+
+template <int J, bool GLU>
+__global__ __launch_bounds__(256, 1) void moe_gemm_tile_kernel(const f16* __restrict__ x, const uint8_t* __restrict__ w,
+                                                               const f16* __restrict__ scales, f16* __restrict__ y, int N, int K,
+                                                               int ldc, GroupMap map)
+{
+    gemm_tile_body<0, J, false, 2, false, GLU, 1, 1, true>(x, w, scales, y, 0, N, K, ldc, Epilogue{}, 1, nullptr, nullptr, map);
+}
+
+}  // namespace
+
+// Which tile shape: the wide tile (128 x 128) is the efficient one when it fills the chip, the narrow one (128 x 64) doubles the
+// workgroups (launch_gemm_mfma's rule and its measured 0.70 cost ratio).  The counts live on the device, so the row tiles are
+// estimated from the shapes: min(E, S) experts with the mean S / min(E, S) rows each.
+static bool moe_tiled_narrow(int S, int E, int N)
+{
+    const int    A     = S < E ? S : E;
+    const int    mean  = (S + A - 1) / A;
+    const long   rows  = (long)A * ((mean + BM - 1) / BM);
+    const long   ncu   = device_cu_count();
+    const long   t2    = rows * ((N + TileCfg<2>::BN - 1) / TileCfg<2>::BN);
+    const long   t1    = rows * ((N + TileCfg<1>::BN - 1) / TileCfg<1>::BN);
+    const double cost2 = (double)((t2 + ncu - 1) / ncu);
+    const double cost1 = 0.70 * (double)((t1 + ncu - 1) / ncu);
+    return cost1 < cost2;
+}
+
+bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather)
+{
+    const long long S = (long long)T * k;
+    const long long x_bytes = (gather ? (long long)T : S) * K * 2;
+    const long long R = S / BM + (S < E ? S : E);
+    return K % BK == 0 && K / BK >= kMinKSteps && N % kTileN == 0 && (long long)N * K < (1ll << 31) &&
+           x_bytes + 4096 < (1ll << 31) && R * ((N + TileCfg<1>::BN - 1) / TileCfg<1>::BN) < (1ll << 31);
+}
+
+int launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
+                          const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream)
+{
+    if (!moe_gemm_tiled_supports(T, k, E, N, K, gather)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs moe_gemm_kernel
+    const int S = T * k, A = S < E ? S : E, R = S / BM + A;
+    GroupMap  map;
+    map.offsets     = offsets;
+    map.sorted_slot = sorted_slot;
+    map.active      = active;
+    map.topk        = gather ? k : 0;
+    map.A           = A;
+    map.R           = R;
+    map.x_rows      = gather ? T : S;
+    static const int force_j = [] {  // EETQ_AMD_MOE_TILE_J = 1 / 2 (behind EETQ_AMD_TUNING): A/B runs of the two tile shapes
+        const char* e = tuning_env("EETQ_AMD_MOE_TILE_J");
+        return e ? atoi(e) : 0;
+    }();
+    const bool narrow = force_j == 1 || (force_j != 2 && moe_tiled_narrow(S, E, N));
+    const int  ldc    = glu8 ? N / 2 : N;
+    auto go = [&](auto kern, std::atomic<unsigned long long>& opted, int bn, size_t smem) -> int {
+        int st = opt_in_large_lds(kern, opted);  // > 64 KiB of dynamic LDS: once per kernel and device
+        if (st != EETQ_OK) return st;
+        launch_kernel(kern, dim3((unsigned)(R * ((N + bn - 1) / bn))), dim3(256), smem, stream, x, w, scales, y, N, K, ldc, map);
+        return check_hip(hipGetLastError(), "moe_gemm_tile_kernel launch");
+    };
+    static std::atomic<unsigned long long> o1{0}, o2{0}, o1g{0}, o2g{0};
+    if (glu8 && narrow) return go(moe_gemm_tile_kernel<1, true>, o1g, TileCfg<1>::BN, TileCfg<1>::SMEM_BYTES);
+    if (glu8) return go(moe_gemm_tile_kernel<2, true>, o2g, TileCfg<2>::BN, TileCfg<2>::SMEM_BYTES);
+    if (narrow) return go(moe_gemm_tile_kernel<1, false>, o1, TileCfg<1>::BN, TileCfg<1>::SMEM_BYTES);
+    return go(moe_gemm_tile_kernel<2, false>, o2, TileCfg<2>::BN, TileCfg<2>::SMEM_BYTES);
+}
+
+}  // namespace eetq

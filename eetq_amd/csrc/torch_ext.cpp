@@ -863,9 +863,9 @@ std::vector<Tensor> w8_a16_gemv_grouped(const std::vector<Tensor>& inputs, const
 // Routed W8A16 mixture-of-experts layer (extension): the forward of transformers' experts modules,
 // out[t] = sum_j w[t][j] * down_e( silu(gate_e(x_t)) * up_e(x_t) ), e = top_k_index[t][j], on expert stacks gate_up_weight
 // int8 [E, H, 2I] (gfx950 layout per expert, glu8 column order), gate_up_scale fp16 [E, 2I], down_weight int8 [E, I, H],
-// down_scale fp16 [E, H].  T <= 16: route -> grouped GEMM (gather, silu_glu8) -> grouped GEMM (sorted rows) -> combine, four
-// launches, no host sync (capturable).  T > 16: the expert counts are read back once and every active expert's rows run through
-// the AUTO W8A16 GEMMs, then the same combine (not capturable).  Ids outside [0, E) contribute nothing.
+// down_scale fp16 [E, H].  Any T: route -> grouped GEMM (gather, silu_glu8) -> grouped GEMM (sorted rows) -> combine, four
+// launches, no host sync (capturable); the grouped GEMMs are the decode kernel or the tiled prompt kernel (moe_grouped_gemm below).
+// Ids outside [0, E) contribute nothing.
 // the argument checks the layer's three entries share (`fn` names the caller in the messages): the expert stacks ...
 struct MoeShape {
     int64_t E, H, N1, I;
@@ -905,6 +905,47 @@ MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_
     return m;
 }
 
+// One grouped projection of the layer.  Which of the two grouped kernels serves it is decided from the SHAPES alone -- the counts live
+// on the device -- so every call with the same (T, k, E, N, K) runs the same kernel whatever the routing (a skewed routing costs
+// time, never correctness), and the trainable and the inference forward always agree on it:
+//   * T <= 16, or mean rows per expert S / E < kMoeTiledMinMeanRows: eetq_w8a16_moe_gemm (16-row MFMA tiles, the expert's weight
+//     tile row streamed once per 16 rows);
+//   * above: eetq_w8a16_moe_gemm_tiled (128-row LDS tiles, the weight read once per 128 rows); a shape outside the tile body's
+//     limits (EETQ_ERR_UNSUPPORTED, quiet) takes the decode kernel, which is correct at any row count.
+// The seam is measured (tools/moe_bench.py --seam, profiles/r09_moe_seam.jsonl), one MI355X, us per
+// gate|up + down pair of launches, decode kernel / tiled kernel, uniform routing (skewed routing moves no entry across 1.0):
+//   mean rows S / E      1        2        4        8        16       32       64
+//   qwen3-30b-a3b        87/203   116/211  140/226  161/231  226/229  385/262  662/303
+//   mixtral-8x7b         -        -        256/343  301/344  469/406  886/434  1552/519     (4: T = 17, 4.25 rows)
+// Below 16 rows per expert the decode kernel wins at both shapes (one 16-row pass streams the weights once; the tiled kernel pays
+// 128-row MFMA work and its ring's ramp per tile), at 16 the two meet (Qwen 0.99, Mixtral 1.16 in the tiled kernel's favour),
+// above it the decode kernel re-streams the weights once per 16 rows and loses by S / E / 16.
+constexpr int64_t kMoeTiledMinMeanRows = 16;
+
+void moe_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const int* offsets, const int* sorted, const int* active, void* y,
+                      int64_t T, int64_t k, int64_t E, int64_t N, int64_t K, int gather, int glu8, void* st)
+{
+    if (T > 16 && T * k >= kMoeTiledMinMeanRows * E) {
+        const int rc = eetq_w8a16_moe_gemm_tiled(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k,
+                                                 (int)E, (int)N, (int)K, gather, glu8, st);
+        if (rc != EETQ_ERR_UNSUPPORTED) {
+            check(rc);
+            return;
+        }
+    }
+    check(eetq_w8a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E, (int)N, (int)K,
+                              gather, glu8, st));
+}
+
+// EETQ_AMD_MOE_HOST=1 behind EETQ_AMD_TUNING=1 (an A/B hook like every other: the library reads it through tuning_env, once per
+// process): T > 16 takes the former host path -- the expert counts read back once, every active expert's rows through the AUTO
+// W8A16 GEMMs.  For A/B timing only: it synchronises the stream and cannot be captured.
+bool moe_host_path()
+{
+    static const bool on = eetq_diag_moe_host_path() == 1;
+    return on;
+}
+
 Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
                   const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
 {
@@ -924,14 +965,12 @@ Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tens
     int *  offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
     check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
     Tensor down = torch::empty({S, H}, hidden.options());
-    if (T <= 16) {
+    if (T <= 16 || !moe_host_path()) {
         Tensor inter = torch::empty({S, I}, hidden.options());
-        check(eetq_w8a16_moe_gemm(hidden.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, sorted, active,
-                                  inter.data_ptr(), (int)T, (int)k, (int)E, (int)N1, (int)H, 1, 1, st));
-        check(eetq_w8a16_moe_gemm(inter.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, sorted, active,
-                                  down.data_ptr(), (int)T, (int)k, (int)E, (int)H, (int)I, 0, 0, st));
+        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, inter.data_ptr(), T, k, E, N1, H, 1, 1, st);
+        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, st);
     } else {
-        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the prompt path
+        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
         const int*   ch       = counts_h.data_ptr<int>();
         const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
         int64_t      off      = 0;
@@ -955,10 +994,11 @@ Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tens
 // Trainable forward of the layer (extension): the same `out` as w8_a16_moe bit for bit, plus what the backward
 // reads -- the routing tables (int32, eetq_moe_route's counts | offsets | sorted_slot | position | active), gate_up [T*k, 2I] (the
 // gate|up projection of every sorted row, glu8 column order, before the activation) and y [T*k, H] (each sorted row's down
-// projection, before the router weighting).  Rows past offsets[E] of both are unspecified.  T <= 16: route -> grouped GEMM
-// (gather, plain) -> eetq_silu_mul_glu8_f16 -> grouped GEMM -> combine, no host sync; the glu8 epilogue of w8_a16_moe is the
-// projection followed by that launch bit for bit.  T > 16: w8_a16_moe's host path with each expert's gate|up run plain on the
-// kernel its gated write-out uses (the stream kernel for 2 to 16 rows, AUTO otherwise), then one silu_mul over all rows.
+// projection, before the router weighting).  Rows past offsets[E] of both are unspecified.  Any T: route -> grouped GEMM
+// (gather, plain) -> eetq_silu_mul_glu8_f16 -> grouped GEMM -> combine, five launches, no host sync (capturable); the glu8 write-out
+// of either grouped kernel is the plain projection followed by that launch bit for bit, and moe_grouped_gemm picks the same kernel
+// for both forwards.  (Under the A/B host switch: w8_a16_moe's host path with each expert's gate|up run plain on the kernel its
+// gated write-out uses, then one silu_mul over all rows.)
 std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden_in, const Tensor& top_k_index,
                                                             const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
                                                             const Tensor& dn_w, const Tensor& dn_s)
@@ -979,15 +1019,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden
     int*         counts = tables.data_ptr<int>();
     int *        offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
     check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
-    if (T <= 16) {
+    if (T <= 16 || !moe_host_path()) {
         Tensor inter = torch::empty({S, I}, hidden.options());
-        check(eetq_w8a16_moe_gemm(hidden.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, sorted, active,
-                                  gate_up.data_ptr(), (int)T, (int)k, (int)E, (int)N1, (int)H, 1, 0, st));
+        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, gate_up.data_ptr(), T, k, E, N1, H, 1, 0, st);
         check(eetq_silu_mul_glu8_f16(gate_up.data_ptr(), inter.data_ptr(), (int)S, (int)I, st));
-        check(eetq_w8a16_moe_gemm(inter.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, sorted, active,
-                                  down.data_ptr(), (int)T, (int)k, (int)E, (int)H, (int)I, 0, 0, st));
+        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, st);
     } else {
-        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the prompt path
+        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
         const int*   ch       = counts_h.data_ptr<int>();
         const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
         int64_t      off      = 0;

@@ -214,7 +214,9 @@ class W8A16Experts(nn.Module):
         return mod
 
     def forward(self, hidden_states, top_k_index, top_k_weights):
-        """T <= 16 tokens: four launches, no host sync (capturable); more: one read-back of the expert counts (not capturable)."""
+        """Any number of tokens: four launches (five when trainable), no host sync, capturable in a graph.  The two grouped GEMMs run
+        the decode kernel at T <= 16 or fewer than 16 rows per expert on average, the grouped tiled kernel above -- chosen from the
+        shapes, never from the routing."""
         if (self.trainable and torch.is_grad_enabled()
                 and (hidden_states.requires_grad or top_k_weights.requires_grad)):
             return W8A16MoeFunction.apply(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,

@@ -281,6 +281,22 @@ int eetq_moe_route(const int64_t* top_k_index, int T, int k, int E, int* counts,
  *   K % 64 == 0, N % 16 == 0, x / w_packed / y 16-byte aligned, E and k as in eetq_moe_route; else EETQ_ERR_INVALID. */
 int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
                         const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream);
+/* eetq_w8a16_moe_gemm_tiled: the same grouped GEMM on the LDS-tiled MFMA kernel (128 x 128 / 128 x 64 tiles, the kernel of
+ *   EETQ_PATH_MFMA), for prompts: the signature, argument checks, error codes and y of eetq_w8a16_moe_gemm.  Grid = (floor(T*k /
+ *   128) + min(E, T*k)) row-tile slots x column tiles -- an upper bound on sum_e ceil(count_e / 128) for any routing; a workgroup
+ *   maps its slot to (expert, 128-row tile) from offsets / active and leaves at once when the slot is surplus.  No host sync, no
+ *   atomics, capturable.  Numerics: per live row y[p][n] = fp16( sum_k fp32(x) * fp32( fp16(q s) ) ), fp32 accumulation in the
+ *   tile kernel's K order, one rounding; glu8 = 1 rounds both operands to fp16, then silu_mul (= the plain call followed by
+ *   eetq_silu_mul_glu8_f16, bit for bit).  An expert's rows equal eetq_w8a16_gemm_ex(..., EETQ_PATH_MFMA) on its gathered rows bit
+ *   for bit wherever that call runs the unsplit tile; a row's bits do not depend on T, on the other tokens' routing or on where
+ *   the row lands in its tile.  Rows at or past offsets[E] and rows of inactive experts are never written.
+ *   Returns EETQ_ERR_UNSUPPORTED, launching nothing and setting no message, for a shape outside the tile kernel's limits (K < 320,
+ *   K*N >= 2^31 per expert, rows(x)*K*2 + 4096 >= 2^31): the caller runs eetq_w8a16_moe_gemm, which is correct at any row count. */
+int eetq_w8a16_moe_gemm_tiled(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
+                              const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream);
+/* 1 when the process asked for the layer's former host path at T > 16 (EETQ_AMD_TUNING=1 and EETQ_AMD_MOE_HOST=1, read once): an
+ *   A/B switch for timing the per-expert AUTO launches against the grouped kernels; 0 in every production process. */
+int eetq_diag_moe_host_path(void);
 /* eetq_moe_combine_f16: out[t][h] = fp16( sum_{j = 0..k-1, in order} fp32(y[position[t*k + j]][h]) * fp32(weights[t][j]) ),
  *   slots with position -1 adding nothing (a token with none gets 0).  y fp16 [*][H], out fp16 [T][H] (16-byte aligned,
  *   H % 8 == 0), weights [T][k] of w_dtype EETQ_DTYPE_F32 (transformers' router output) or EETQ_DTYPE_F16.  No atomics:

@@ -13,10 +13,24 @@ a host read-back of the expert counts, and transformers' eager fp16 experts forw
 the trainable forward's saved tensors and the backward's peak above what was allocated before it.
 
     python tools/moe_bench.py --backward --out profiles/r08_moe_backward_bench.jsonl
+
+Prompts: --tokens 64,512,4096 times the device-side prompt path; --host-path adds the column `us_host_path`, the
+same layer on the former host path (one read-back of the expert counts, per-expert AUTO GEMMs), measured in a child process of its
+own that sets EETQ_AMD_TUNING=1 EETQ_AMD_MOE_HOST=1 (the switch is read once per process); --no-baselines skips the fp16 eager
+forward and the Python loop.
+
+    python tools/moe_bench.py --tokens 64,512,4096 --host-path --out profiles/r09_moe_prompt_bench.jsonl
+
+--seam sweeps the seam between the two grouped kernels: at mean rows per expert S / E = 1 .. 64 (T = rows * E / k, uniform and
+skewed routing) the layer's two projections (gate|up with the gated write-out, gathered; down on the sorted rows) on
+eetq_w8a16_moe_gemm and on eetq_w8a16_moe_gemm_tiled, us per pair of launches.
+
+    python tools/moe_bench.py --seam --out profiles/r09_moe_seam.jsonl
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import torch
@@ -28,6 +42,11 @@ DEV = "cuda:0"
 
 
 def _time(fn, warmup, iters):
+    return _time_stats(fn, warmup, iters)[0]
+
+
+def _time_stats(fn, warmup, iters):
+    """(median, min, max) us over `iters` launches"""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -40,7 +59,7 @@ def _time(fn, warmup, iters):
         b.synchronize()
         times.append(a.elapsed_time(b) * 1000.0)
     times.sort()
-    return times[len(times) // 2]
+    return times[len(times) // 2], times[0], times[-1]
 
 
 def _routing(T, k, E, kind, g):
@@ -158,6 +177,68 @@ def backward(args, out):
             del o, tables, gate_up, y, dy, dh, dgu, dxs, dx
 
 
+def seam(args, out):
+    import ctypes
+
+    from eetq_amd import _lib
+    L = _lib.lib()
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        gu_w = torch.randint(-127, 128, (E, H, 2 * I), dtype=torch.int8, device=DEV)
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-3).half()
+        dn_w = torch.randint(-127, 128, (E, I, H), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-3).half()
+        g = torch.Generator().manual_seed(1)
+        done = set()
+        for rows in (int(r) for r in args.seam_rows.split(",")):
+            T = max(17, rows * E // k)   # the prompt path starts at T = 17
+            if T in done:
+                continue
+            done.add(T)
+            S, A = T * k, min(E, T * k)
+            for kind in ("uniform", "skewed"):
+                x = (torch.rand(T, H, device=DEV) - 0.5).half()
+                idx = _routing(T, k, E, kind, g)
+                tabs = [torch.empty(n, dtype=torch.int32, device=DEV) for n in (E, E + 1, S, S, A)]
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                assert L.eetq_moe_route(_ptr(idx), T, k, E, *[_ptr(t) for t in tabs], st) == 0
+                _, offsets, sorted_slot, _, active = tabs
+                inter = torch.empty(S, I, dtype=torch.float16, device=DEV)
+                down = torch.empty(S, H, dtype=torch.float16, device=DEV)
+                tab = (_ptr(offsets), _ptr(sorted_slot), _ptr(active))
+
+                def pair(fn):
+                    a = fn(_ptr(x), _ptr(gu_w), _ptr(gu_s), *tab, _ptr(inter), T, k, E, 2 * I, H, 1, 1, st)
+                    b = fn(_ptr(inter), _ptr(dn_w), _ptr(dn_s), *tab, _ptr(down), T, k, E, H, I, 0, 0, st)
+                    assert a == 0 and b == 0, (a, b)
+                us_dec = _time(lambda: pair(L.eetq_w8a16_moe_gemm), args.warmup, args.iters)
+                us_tile = _time(lambda: pair(L.eetq_w8a16_moe_gemm_tiled), args.warmup, args.iters)
+                rec = {"shape": name, "H": H, "I": I, "E": E, "k": k, "T": T, "mean_rows": round(S / E, 2), "routing": kind,
+                       "max_rows": int(tabs[0].max()), "us_decode_kernel": round(us_dec, 2), "us_tiled_kernel": round(us_tile, 2),
+                       "decode_over_tiled": round(us_dec / us_tile, 3)}
+                line = json.dumps(rec)
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
+
+
+def _host_path_times(args):
+    """{(shape, T, routing): us} of the layer on the host path, from a child process that sets the A/B switch"""
+    env = dict(os.environ, EETQ_AMD_TUNING="1", EETQ_AMD_MOE_HOST="1")
+    cmd = [sys.executable, os.path.abspath(__file__), "--shapes", args.shapes, "--tokens", args.tokens, "--warmup", str(args.warmup),
+           "--iters", str(args.iters), "--no-baselines"]
+    res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, check=True)
+    times = {}
+    for line in res.stdout.splitlines():
+        if line.startswith("{"):
+            r = json.loads(line)
+            assert r["path"] == "host" or r["T"] <= 16, r
+            times[(r["shape"], r["T"], r["routing"])] = (r["us"], r["us_min"], r["us_max"])
+    return times
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -166,7 +247,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--backward", action="store_true", help="time the training path (DESIGN.md 4.11)")
+    ap.add_argument("--host-path", action="store_true", help="add us_host_path: the T > 16 host path, timed in a child process")
+    ap.add_argument("--no-baselines", action="store_true", help="skip the fp16 eager forward and the per-expert Python loop")
+    ap.add_argument("--seam", action="store_true", help="sweep the seam between the two grouped kernels (DESIGN.md 4.10)")
+    ap.add_argument("--seam-rows", default="1,2,4,8,16,32,64", help="mean rows per expert of the seam sweep")
     args = ap.parse_args()
+    if args.seam:
+        out = open(args.out, "w") if args.out else None
+        seam(args, out)
+        if out:
+            out.close()
+        return
     if args.backward:
         args.tokens = args.tokens or "16,64,512,4096"
         out = open(args.out, "w") if args.out else None
@@ -174,12 +265,15 @@ def main():
         if out:
             out.close()
         return
-    args.tokens = args.tokens or "1,2,4,8,16,64,512"
+    args.tokens = args.tokens or "1,2,4,8,16,64,512,4096"
+    host_us = _host_path_times(args) if args.host_path else {}   # before this process opens the GPU
 
     from transformers import MixtralConfig
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts
 
+    from eetq_amd import _lib
     from eetq_amd.ops import w8_a16_gemm, w8_a16_moe
+    host = _lib.lib().eetq_diag_moe_host_path() == 1
     out = open(args.out, "w") if args.out else None
     for name in args.shapes.split(","):
         H, I, E, k = SHAPES[name]
@@ -188,12 +282,13 @@ def main():
         gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-3).half()
         dn_w = torch.randint(-127, 128, (E, I, H), dtype=torch.int8, device=DEV)
         dn_s = (torch.rand(E, H, device=DEV) * 1e-3).half()
-        cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=k)
-        cfg._experts_implementation = "eager"
-        eager = MixtralExperts(cfg).half().to(DEV)
-        with torch.no_grad():
-            eager.gate_up_proj.normal_(0, 0.02)
-            eager.down_proj.normal_(0, 0.02)
+        if not args.no_baselines:
+            cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=k)
+            cfg._experts_implementation = "eager"
+            eager = MixtralExperts(cfg).half().to(DEV)
+            with torch.no_grad():
+                eager.gate_up_proj.normal_(0, 0.02)
+                eager.down_proj.normal_(0, 0.02)
         g = torch.Generator().manual_seed(1)
         for T in (int(t) for t in args.tokens.split(",")):
             for kind in ("uniform", "skewed"):
@@ -211,15 +306,21 @@ def main():
                         y.index_add_(0, tok, d * wts[tok, j, None].half())
                     return y
 
-                us = _time(lambda: w8_a16_moe(x, idx, wts, gu_w, gu_s, dn_w, dn_s), args.warmup, args.iters)
-                with torch.no_grad():
-                    us_eager = _time(lambda: eager(x, idx, wts), args.warmup, args.iters)
-                us_loop = _time(loop, args.warmup, args.iters)
+                us, us_lo, us_hi = _time_stats(lambda: w8_a16_moe(x, idx, wts, gu_w, gu_s, dn_w, dn_s), args.warmup, args.iters)
                 nbytes = len(active) * 3 * H * I
                 rec = {"shape": name, "H": H, "I": I, "E": E, "k": k, "T": T, "routing": kind, "active_experts": len(active),
-                       "path": "device" if T <= 16 else "host", "us": round(us, 2), "int8_bytes": nbytes,
-                       "TBps": round(nbytes / us / 1e6, 3), "us_fp16_eager": round(us_eager, 2),
-                       "us_per_expert_loop": round(us_loop, 2), "speedup_vs_eager": round(us_eager / us, 2)}
+                       "path": "host" if host and T > 16 else "device", "us": round(us, 2), "us_min": round(us_lo, 2),
+                       "us_max": round(us_hi, 2), "int8_bytes": nbytes,
+                       "TBps": round(nbytes / us / 1e6, 3), "TFLOPs": round(6.0 * T * k * H * I / us / 1e6, 1)}
+                if (name, T, kind) in host_us:
+                    rec["us_host_path"], rec["us_host_path_min"], rec["us_host_path_max"] = host_us[(name, T, kind)]
+                    rec["host_over_device"] = round(rec["us_host_path"] / us, 2)
+                if not args.no_baselines:
+                    with torch.no_grad():
+                        us_eager = _time(lambda: eager(x, idx, wts), args.warmup, args.iters)
+                    us_loop = _time(loop, args.warmup, args.iters)
+                    rec.update({"us_fp16_eager": round(us_eager, 2), "us_per_expert_loop": round(us_loop, 2),
+                                "speedup_vs_eager": round(us_eager / us, 2)})
                 line = json.dumps(rec)
                 print(line, flush=True)
                 if out:
