@@ -404,3 +404,26 @@ int launch_w4a16(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep,
 }
 
 }  // namespace eetq
+
+using namespace eetq;
+
+extern "C" {
+
+// The expansion kernel above on caller-owned memory.  int4 tile t becomes int8 tiles 2t and 2t + 1 whatever the
+// matrix it belongs to (ntile * 2 ktiles + 2 kt = 2 t), so any whole number of tiles -- one weight, or an [E] stack of them -- is
+// one contiguous run of 16-byte lane chunks: the kernel runs with one k tile per tile row.
+int eetq_expand_i4_to_i8(const int8_t* src, int8_t* dst, size_t bytes_src, void* stream)
+{
+    EETQ_REQUIRE(src && dst, "eetq_expand_i4_to_i8: null pointer");
+    EETQ_REQUIRE(bytes_src >= (size_t)kTileBytes && bytes_src % kTileBytes == 0 && bytes_src < (1ull << 40),
+                 "eetq_expand_i4_to_i8: bytes_src must be a whole number of 1 KiB int4 tiles, below 2^40");
+    EETQ_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, "eetq_expand_i4_to_i8: src and dst must be 16-byte aligned");
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    EETQ_REQUIRE(s0 + bytes_src <= d0 || d0 + 2 * bytes_src <= s0, "eetq_expand_i4_to_i8: src and dst must not overlap");
+    const size_t chunks = bytes_src / 16;
+    launch_kernel(expand_i4_to_i8_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                  reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), chunks, (size_t)1);
+    return check_hip(hipGetLastError(), "expand_i4_to_i8_kernel launch");
+}
+
+}  // extern "C"

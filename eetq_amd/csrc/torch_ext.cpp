@@ -871,16 +871,27 @@ struct MoeShape {
     int64_t E, H, N1, I;
 };
 
-MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, c10::Device dev)
+// bits = 4: packed int4 stacks, two values per byte along N -- gate_up [E, H, I], down [E, I, H / 2] -- and 128-deep
+// tiles; the checks, their order and (for bits = 8) their messages are the same
+MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, c10::Device dev,
+                    int bits = 8)
 {
+    const bool i4 = bits == 4;
     TORCH_CHECK(gu_w.dim() == 3 && dn_w.dim() == 3 && gu_w.scalar_type() == at::kChar && dn_w.scalar_type() == at::kChar &&
                     gu_s.scalar_type() == at::kHalf && dn_s.scalar_type() == at::kHalf,
-                fn, ": expert weights must be int8 [E, K, N] stacks and scales float16 [E, N]");
-    const int64_t E = gu_w.size(0), H = gu_w.size(1), N1 = gu_w.size(2), I = N1 / 2;
-    TORCH_CHECK(N1 == 2 * I && dn_w.size(0) == E && dn_w.size(1) == I && dn_w.size(2) == H && gu_s.dim() == 2 && gu_s.size(0) == E &&
+                fn, i4 ? ": expert weights must be packed int4 stacks (int8 [E, K, N / 2]) and scales float16 [E, N]"
+                       : ": expert weights must be int8 [E, K, N] stacks and scales float16 [E, N]");
+    const int64_t pack = i4 ? 2 : 1;   // values per byte
+    const int64_t E = gu_w.size(0), H = gu_w.size(1), N1 = gu_w.size(2) * pack, I = N1 / 2;
+    TORCH_CHECK(N1 == 2 * I && dn_w.size(0) == E && dn_w.size(1) == I && dn_w.size(2) * pack == H && gu_s.dim() == 2 && gu_s.size(0) == E &&
                     gu_s.size(1) == N1 && dn_s.dim() == 2 && dn_s.size(0) == E && dn_s.size(1) == H,
-                fn, ": expected gate_up_weight [E, H, 2I], gate_up_scale [E, 2I], down_weight [E, I, H], down_scale [E, H]");
-    TORCH_CHECK(H % 64 == 0 && I % 64 == 0, fn, ": the gfx950 layout needs H % 64 == 0 and I % 64 == 0");
+                fn, i4 ? ": expected gate_up_qweight [E, H, I], gate_up_scales [E, 2I], down_qweight [E, I, H / 2], down_scales [E, H]"
+                       : ": expected gate_up_weight [E, H, 2I], gate_up_scale [E, 2I], down_weight [E, I, H], down_scale [E, H]");
+    if (i4) {
+        TORCH_CHECK(H % 128 == 0 && I % 128 == 0, fn, ": the gfx950 int4 layout needs H % 128 == 0 and I % 128 == 0");
+    } else {
+        TORCH_CHECK(H % 64 == 0 && I % 64 == 0, fn, ": the gfx950 layout needs H % 64 == 0 and I % 64 == 0");
+    }
     TORCH_CHECK(gu_w.is_contiguous() && gu_s.is_contiguous() && dn_w.is_contiguous() && dn_s.is_contiguous(),
                 fn, ": expert weights and scales must be contiguous");
     for (const Tensor* t : {&gu_w, &gu_s, &dn_w, &dn_s})
@@ -890,12 +901,12 @@ MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, cons
 
 // ... and, for the forwards, the hidden states and the routing
 MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights,
-                   const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+                   const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, int bits = 8)
 {
     TORCH_CHECK(hidden_in.is_cuda() && hidden_in.scalar_type() == at::kHalf && hidden_in.dim() == 2,
                 fn, ": hidden must be a float16 GPU tensor [T, H]");
     const auto     dev = hidden_in.device();
-    const MoeShape m   = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, dev);
+    const MoeShape m   = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, dev, bits);
     TORCH_CHECK(hidden_in.size(1) == m.H, fn, ": hidden is [T, ", hidden_in.size(1), "] but gate_up_weight has H = ", m.H);
     TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden_in.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
                 fn, ": top_k_index and top_k_weights must both be [T, k]");
@@ -1126,6 +1137,99 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
     return {gx, gw};
 }
 
+// Routed W4A16 mixture-of-experts layer (extension): w8_a16_moe on int4 expert stacks -- gate_up_qweight int8
+// [E, H, I] (= [E, K = H, N / 2], N = 2I: two values per byte; per expert the gfx950 int4 layout, glu8 column order), gate_up_scales
+// fp16 [E, 2I], down_qweight int8 [E, I, H / 2], down_scales fp16 [E, H].  Inference only.  route -> grouped GEMM (gather, glu8) ->
+// grouped GEMM (sorted rows) -> combine; eetq_moe_route and eetq_moe_combine_f16 are the int8 layer's, unchanged.  No host sync,
+// capturable.
+// Which grouped kernel serves the layer's two projections, from the SHAPES alone (like moe_grouped_gemm: the counts live on the
+// device, and every call with the same T, k, E, H, I runs the same kernels whatever the routing):
+//   * "decode": eetq_w4a16_moe_gemm on the int4 tiles (16-row MFMA tiles, the expert's tile row streamed once per 16 rows);
+//   * "expand": eetq_expand_i4_to_i8 of the whole stack into a torch::empty [E, K, N] int8 buffer (freed after the projection: at
+//     most one expansion is alive), then eetq_w8a16_moe_gemm_tiled on it with the unchanged scales.
+// The expansion moves 1.5 E K N bytes per projection whatever T is (E K N / 2 read, E K N written) and the tiled kernel then reads
+// E_active K N, against ceil(rows / 16) E_active K N / 2 for the decode kernel: by bytes alone the two meet near 5 x 16 rows per
+// expert, far above the int8 layer's seam of 16.
+// Measured (tools/moe_bench.py --seam --bits 4, profiles/r10_moe_int4_seam.jsonl), one MI355X, us per gate|up + down
+// pair, decode kernel / expansions + tiled kernel (of which the two expansions alone: 355 us Mixtral, 157 us Qwen3, whatever T),
+// uniform routing (skewed routing moves no entry across 1.0):
+//   mean rows S / E      16        32        64         128         256
+//   qwen3-30b-a3b        177/369   328/400   583/443    1124/582    2220/787
+//   mixtral-8x7b         400/752   708/771   1353/859   2650/1060   5231/1404
+// At 32 rows per expert the decode kernel still wins at both shapes (0.82, 0.92), at 64 the expanded path does (1.31, 1.58): the
+// seam sits 2-4 x higher than the int8 layer's 16, where the bytes put it.  In rows per expert it is the same at both shapes:
+// both sides of the comparison scale with E K N, so E K N drops out of the rule.  (The lines cross near 40 rows by interpolation;
+// nothing between 32 and 64 was measured, so the rule starts at the first measured point where the expansion wins.)
+constexpr int64_t kMoeI4ExpandMinMeanRows = 64;
+
+// ... and only where eetq_w8a16_moe_gemm_tiled takes BOTH projections (its own limits, asked of the library: K >= 320, N K < 2^31
+// per expert, the activation block below 2 GiB): nothing is allocated or expanded for a shape that would then run the decode
+// kernel, and w4_a16_moe_path reports what runs.
+bool moe_i4_tiled_takes(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    if (T < 1 || T * k > (int64_t(1) << 30)) return false;
+    return eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)(2 * I), (int)H, 1) == 1 &&
+           eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)H, (int)I, 0) == 1;
+}
+
+bool moe_i4_expands(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    return T > 16 && T * k >= kMoeI4ExpandMinMeanRows * E && moe_i4_tiled_takes(T, k, E, H, I);
+}
+
+std::string w4_a16_moe_path(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    TORCH_CHECK(T >= 0 && k >= 1 && E >= 1 && k <= E && H >= 1 && I >= 1, "w4_a16_moe_path: T >= 0, 1 <= k <= E, H >= 1, I >= 1");
+    return moe_i4_expands(T, k, E, H, I) ? "expand" : "decode";
+}
+
+// One grouped projection over an int4 stack w [E, K, N / 2].  `expand` is set only where the tiled kernel takes the shape.
+void moe_i4_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const int* offsets, const int* sorted, const int* active,
+                         void* y, int64_t T, int64_t k, int64_t E, int64_t N, int64_t K, int gather, int glu8, bool expand, void* st)
+{
+    if (expand) {
+        Tensor w8 = torch::empty({E, K, N}, w.options());
+        check(eetq_expand_i4_to_i8(w.data_ptr<int8_t>(), w8.data_ptr<int8_t>(), (size_t)w.numel(), st));
+        check(eetq_w8a16_moe_gemm_tiled(x, w8.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E,
+                                        (int)N, (int)K, gather, glu8, st));
+        return;
+    }
+    check(eetq_w4a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E, (int)N, (int)K,
+                              gather, glu8, st));
+}
+
+Tensor w4_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
+                  const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
+{
+    const auto [E, H, N1, I] = moe_check("w4_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s, 4);
+    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", "w4_a16_moe: path must be 'auto', 'decode' or 'expand'");
+    const auto dev           = hidden_in.device();
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    Tensor        out = torch::empty({T, H}, hidden_in.options());
+    if (T == 0) return out;
+    c10::DeviceGuard guard(dev);
+    void*        st     = stream_of(hidden_in);
+    const Tensor hidden = hidden_in.contiguous();
+    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
+    const Tensor wts    = top_k_weights.contiguous();
+    TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
+                "w4_a16_moe: path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
+    const bool   expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
+    // counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A]
+    Tensor tables = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
+    int*   counts = tables.data_ptr<int>();
+    int *  offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
+    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
+    Tensor inter = torch::empty({S, I}, hidden.options());
+    Tensor down  = torch::empty({S, H}, hidden.options());
+    moe_i4_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, st);
+    moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, expand, st);
+    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
+                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
+                               (int)H, st));
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "EETQ operator module on libeetq_amd.so (MI355X / gfx950)";
@@ -1195,5 +1299,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("top_k_weights"), py::arg("tables"), py::arg("gate_up"), py::arg("y"), py::arg("gate_up_qweight"),
           py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("need_input_grad") = true,
           py::arg("need_weights_grad") = true);
+    m.def("w4_a16_moe", &w4_a16_moe, "routed W4A16 mixture-of-experts layer over int4 expert stacks (inference only)",
+          py::arg("hidden"), py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
+    m.def("w4_a16_moe_path", &w4_a16_moe_path,
+          "'decode' or 'expand': the grouped kernels w4_a16_moe(path='auto') runs for T tokens, k choices, E experts, H, I",
+          py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
     m.attr("__eetq_amd_version__") = eetq_version();
 }

@@ -16,11 +16,11 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import (preprocess_weights, quant_weights, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward,
+from ..ops import (preprocess_weights, quant_weights, w4_a16_moe, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward,
                    w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
-__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
+__all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
            "W8A16MoeFunction"]
 
 
@@ -228,6 +228,79 @@ class W8A16Experts(nn.Module):
     def extra_repr(self):
         return "num_experts={}, hidden_dim={}, intermediate_dim={}".format(self.num_experts, self.hidden_dim,
                                                                            self.intermediate_dim)
+
+
+class W4A16Experts(nn.Module):
+    """int4 stand-in for transformers' 3-D experts modules: :class:`W8A16Experts` at half the expert bytes, same
+    forward signature.  Buffers: ``gate_up_qweight`` int8 [E, H, I] (= [E, K = H, N / 2] with N = 2I: two values per byte; per expert
+    the gfx950 int4 layout of its [H, 2I] weight, columns in glu8 order: 8 gate + the matching 8 up per 16-column tile),
+    ``gate_up_scales`` fp16 [E, 2I] (same order), ``down_qweight`` int8 [E, I, H / 2], ``down_scales`` fp16 [E, H].  Needs
+    H % 128 == 0 and I % 128 == 0 (int4 tiles are 128 deep).  Runs ``ops.w4_a16_moe``.
+
+    Inference only: there is no int4 backward, the module has no ``trainable`` flag and ``utils.set_trainable`` passes it by;
+    its output is always detached.  State dicts hold the four buffers as they are, like :class:`W8A16Experts`."""
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
+        super().__init__()
+        self.num_experts = num_experts
+        self.hidden_dim = hidden_dim
+        self.intermediate_dim = intermediate_dim
+        E, H, I = num_experts, hidden_dim, intermediate_dim
+        self.register_buffer("gate_up_qweight", torch.zeros((E, H, I), dtype=torch.int8, device=dev))
+        self.register_buffer("gate_up_scales", torch.zeros((E, 2 * I), dtype=torch.float16, device=dev))
+        self.register_buffer("down_qweight", torch.zeros((E, I, H // 2), dtype=torch.int8, device=dev))
+        self.register_buffer("down_scales", torch.zeros((E, H), dtype=torch.float16, device=dev))
+
+    @staticmethod
+    def unsupported_reason(module):
+        """None when :meth:`from_experts` takes ``module``, else why not: :meth:`W8A16Experts.unsupported_reason`'s rules, and
+        H and I multiples of 128."""
+        why = W8A16Experts.unsupported_reason(module)
+        if why is not None:
+            return why
+        _, n2, H = module.gate_up_proj.shape
+        if H % 128 or (n2 // 2) % 128:
+            return "the gfx950 int4 layout needs H %% 128 == 0 and I %% 128 == 0 (H = %d, I = %d)" % (H, n2 // 2)
+        return None
+
+    @classmethod
+    def from_experts(cls, module, init_only=False):
+        """Quantise a transformers experts module (see :meth:`unsupported_reason`; anything else raises ValueError before any GPU
+        work).  Per-channel quantisation commutes with a permutation of the output channels, so the gate|up columns are put
+        in glu8 order in fp16 and each expert is then quantised and packed by ``ops.quant_weights(w, torch.quint4x2)``."""
+        why = cls.unsupported_reason(module)
+        if why is not None:
+            raise ValueError("W4A16Experts.from_experts: %s: %s" % (type(module).__name__, why))
+        gu, dn = module.gate_up_proj, module.down_proj
+        E, n2, H = gu.shape
+        I = n2 // 2
+        mod = cls(E, H, I, dev=gu.device)
+        if init_only:
+            return mod
+        if gu.dtype != torch.float16 or dn.dtype != torch.float16:
+            raise ValueError("Unsupported data type: {}".format(gu.dtype))
+        from ..utils.fuse import _glu8_interleave_columns
+        with torch.no_grad():
+            w = gu.detach().transpose(1, 2)  # [E, H, 2I] gate | up
+            q, s = quant_weights(_glu8_interleave_columns(w[..., :I], w[..., I:]).contiguous(), torch.quint4x2, False)
+            mod.gate_up_qweight = q.to(gu.device)
+            mod.gate_up_scales = s.half().to(gu.device)
+            q, s = quant_weights(dn.detach().transpose(1, 2).contiguous(), torch.quint4x2, False)  # [E, I, H / 2]
+            mod.down_qweight = q.to(gu.device)
+            mod.down_scales = s.half().to(gu.device)
+        return mod
+
+    @torch.no_grad()
+    def forward(self, hidden_states, top_k_index, top_k_weights):
+        """Any number of tokens, no host sync, capturable in a graph.  Four launches on the int4 decode kernel; on the prompt path
+        (``ops.w4_a16_moe_path``: chosen from the shapes, never from the routing) each projection's stack is first expanded to
+        int8 tiles and runs the grouped tiled W8A16 kernel."""
+        return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                          self.down_qweight, self.down_scales)
+
+    def extra_repr(self):
+        return "num_experts={}, hidden_dim={}, intermediate_dim={}, bits=4".format(self.num_experts, self.hidden_dim,
+                                                                                   self.intermediate_dim)
 
 
 def input_grad(grad_output, weight, scales, x_shape, x_dtype=torch.float16):

@@ -49,20 +49,22 @@ if _C is not None:
     w8_a16_moe = _C.w8_a16_moe                   # compiled boundary only (the ctypes twin refuses it)
     w8_a16_moe_train = _C.w8_a16_moe_train       # compiled boundary only, as w8_a16_moe
     w8_a16_moe_backward = _C.w8_a16_moe_backward
+    w4_a16_moe = _C.w4_a16_moe                   # compiled boundary only, as w8_a16_moe
+    w4_a16_moe_path = _C.w4_a16_moe_path
 else:
     BOUNDARY = "ctypes"
     from .ops_ctypes import (decode_attention, greedy_handover, layernorm_forward, preprocess_weights, quant_weights,  # noqa: F401
                              rope_decode_attention, rotary_embedding_neox, rotary_embedding_neox_kvcache,
                              rotary_embedding_neox_kvcache_prefill, rotary_embedding_neox_strided, silu_mul,
-                             unprocess_weights, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t, w8_a16_gemv_grouped, w8_a16_moe,
-                             w8_a16_moe_backward, w8_a16_moe_train)
+                             unprocess_weights, w4_a16_moe, w4_a16_moe_path, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t,
+                             w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
-           "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "decode_dropped_steps",
+           "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "decode_dropped_steps",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]
 
 

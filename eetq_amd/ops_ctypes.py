@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
-           "w8_a16_moe_train", "w8_a16_moe_backward"]
+           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
             LAYOUT_GFX950: LAYOUT_GFX950, LAYOUT_SM80: LAYOUT_SM80, LAYOUT_ROW_MAJOR: LAYOUT_ROW_MAJOR}
@@ -404,6 +404,18 @@ def w8_a16_moe(hidden, top_k_index, top_k_weights, gate_up_qweight, gate_up_scal
     """The routed MoE layer lives in the compiled module only (its device path is four launches with no host sync; a Python
     twin of the prompt path's per-expert loop would add nothing the tests need)."""
     raise RuntimeError("eetq_amd: w8_a16_moe needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not implement it")
+
+
+def w4_a16_moe(hidden, top_k_index, top_k_weights, gate_up_qweight, gate_up_scales, down_qweight, down_scales, path="auto"):
+    """The routed W4A16 MoE layer: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w4_a16_moe needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not implement it")
+
+
+def w4_a16_moe_path(T, k, E, H, I):
+    """The shape rule of :func:`w4_a16_moe`: compiled module only."""
+    raise RuntimeError("eetq_amd: w4_a16_moe_path needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
                        "the ctypes binding does not implement it")
 
 

@@ -11,7 +11,7 @@ import warnings
 import torch
 import torch.nn as nn
 
-from ..modules.qlinear import W8A16Experts, W8A16Linear
+from ..modules.qlinear import W4A16Experts, W8A16Experts, W8A16Linear
 
 __all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable"]
 
@@ -66,7 +66,8 @@ def set_trainable(model, flag=True):
     """Set the ``trainable`` flag of every :class:`W8A16Linear` and :class:`W8A16Experts` in ``model`` (itself included) and
     return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to the router weights)
     in grad mode; their int8 weights stay frozen and their output bits do not change.  Off by default: untrainable modules
-    return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``."""
+    return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``.  :class:`W4A16Experts` is
+    inference only and is passed by."""
     n = 0
     for m in model.modules():
         if isinstance(m, (W8A16Linear, W8A16Experts)):
@@ -76,7 +77,7 @@ def set_trainable(model, flag=True):
 
 
 def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False,
-                 trainable=False):
+                 trainable=False, expert_bits=8):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
@@ -87,7 +88,18 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     named in one warning.  The default leaves experts modules untouched.
     ``trainable=True`` (extension) then sets the flag of :func:`set_trainable` on every quantised module of the model, so that
     gradients cross them (fine-tuning adapters or prompts on a frozen int8 model).
+    ``expert_bits=4`` (extension; with ``experts=True``) builds :class:`W4A16Experts` -- int4 expert stacks, half the bytes,
+    H and I multiples of 128, inference only -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
+    but 8 or 4, ``expert_bits=4`` without ``experts=True`` (it would quantise no expert and say nothing) and ``expert_bits=4``
+    together with ``trainable=True`` (there is no int4 backward) raise ValueError before the model is touched.
     """
+    if expert_bits not in (8, 4):
+        raise ValueError("eet_quantize: expert_bits must be 8 or 4 (got %r)" % (expert_bits,))
+    if expert_bits == 4 and not experts:
+        raise ValueError("eet_quantize: expert_bits=4 needs experts=True (without it no experts module is quantised)")
+    if expert_bits == 4 and trainable:
+        raise ValueError("eet_quantize: expert_bits=4 cannot be trainable (W4A16Experts has no backward)")
+    experts_cls = W4A16Experts if expert_bits == 4 else W8A16Experts
     if experts:
         skipped = []
         found = _experts_modules(model)
@@ -95,11 +107,11 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
             mod = found.pop(name)  # the model and this loop hold the only references: the fp16 stacks go as each is replaced
             if any(tag in name for tag in exclude):
                 continue
-            why = W8A16Experts.unsupported_reason(mod)
+            why = experts_cls.unsupported_reason(mod)
             if why is not None:
                 skipped.append("%s (%s)" % (name, why))
                 continue
-            set_op_by_name(model, name, W8A16Experts.from_experts(mod, init_only=init_only))
+            set_op_by_name(model, name, experts_cls.from_experts(mod, init_only=init_only))
             del mod
             if not init_only and torch.cuda.is_available():
                 torch.cuda.empty_cache()

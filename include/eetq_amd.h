@@ -304,6 +304,30 @@ int eetq_diag_moe_host_path(void);
 int eetq_moe_combine_f16(const void* y, const int* position, const void* weights, int w_dtype, void* out, int T, int k, int H,
                          void* stream);
 
+/* ---- int4 expert stacks (extension, additive within ABI revision 7) -----------------------------------------
+ * eetq_w4a16_moe_gemm: eetq_w8a16_moe_gemm over an int4 expert stack: w_packed [E][K][N / 2] bytes, each expert the GFX950 int4
+ *   layout of its [K][N] weight (1 KiB tiles of 16 columns x 128 k, as eetq_quantize_i4 writes it; K*N/2 bytes apart), scales fp16
+ *   [E][N].  The same tables, grid (N / 16 column tiles x min(E, T*k) active slots), row loop (16 rows at a time, any number of
+ *   rows per expert), gather / glu8 flags, y and untouched rows as eetq_w8a16_moe_gemm; numerics y[p][n] = fp16( sum_k fp32(x) *
+ *   fp32( fp16(q s) ) ) with q in -8 .. 7, fp32 accumulation, one rounding; glu8 = 1 is the plain call followed by
+ *   eetq_silu_mul_glu8_f16, bit for bit.  A row's bits do not depend on T, on the other tokens' routing or on its place among the
+ *   expert's rows.  Needs K % 128 == 0, N % 16 == 0, x / w_packed / y 16-byte aligned, E and k as in eetq_moe_route; else
+ *   EETQ_ERR_INVALID.  Inference only: there is no int4 backward. */
+int eetq_w4a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
+                        const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream);
+/* eetq_expand_i4_to_i8: GFX950 int4 tiles -> GFX950 int8 tiles holding the same integers (-8 .. 7), on caller-owned memory: src
+ *   bytes_src bytes (a whole number of 1 KiB int4 tiles: one weight [K][N / 2] or a stack of them), dst 2 * bytes_src bytes.  int4
+ *   tile t becomes int8 tiles 2t and 2t + 1 of the [n / 16][k / 64] order; columns, and with them the scales and a glu8 column
+ *   order, are untouched, so eetq_w8a16_gemm / eetq_w8a16_moe_gemm_tiled on dst with the int4 weight's scales compute what the
+ *   W4A16 entries define.  One launch, no scratch of the library's, capturable.  16-byte aligned, non-overlapping device pointers;
+ *   else EETQ_ERR_INVALID. */
+int eetq_expand_i4_to_i8(const int8_t* src, int8_t* dst, size_t bytes_src, void* stream);
+
+/* eetq_w8a16_moe_gemm_tiled_supported: 1 when eetq_w8a16_moe_gemm_tiled takes a projection of these sizes (its shape limits: the
+ *   cases for which it would return EETQ_ERR_UNSUPPORTED), else 0.  Host arithmetic only, no device needed.  Lets a caller that has
+ *   to prepare something for the tiled kernel first -- the int4 layer's expansion -- decide before it does. */
+int eetq_w8a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather);
+
 /* ---- mixture-of-experts backward (extension, additive within ABI revision 7) --------------------------------
  * The input and router-weight gradients of the layer above with its int8 weights frozen (no weight gradients), on the tables
  * eetq_moe_route wrote and the sorted rows the forward kept.  Grids fixed by the shapes, no host sync, no atomics: deterministic

@@ -26,6 +26,17 @@ skewed routing) the layer's two projections (gate|up with the gated write-out, g
 eetq_w8a16_moe_gemm and on eetq_w8a16_moe_gemm_tiled, us per pair of launches.
 
     python tools/moe_bench.py --seam --out profiles/r09_moe_seam.jsonl
+
+--bits 4 times the W4A16 layer (ops.w4_a16_moe on int4 stacks; no fp16 / loop baselines) and, with --seam, its
+two routes per pair of projections: eetq_w4a16_moe_gemm on the int4 tiles against eetq_expand_i4_to_i8 + eetq_w8a16_moe_gemm_tiled.
+--plan-sweep times eetq_w4a16_moe_gemm's instantiations (waves x stages in flight) on every projection at T = 1, 4, 16, one
+child process per plan (EETQ_AMD_TUNING=1 EETQ_AMD_MOE_I4_PLAN=<waves>x<depth>, read once per process).
+
+    python tools/moe_bench.py --bits 4 --no-baselines --tokens 1,4,16,64,512,4096 --out profiles/r10_moe_int4_bench.jsonl
+    python tools/moe_bench.py --bits 4 --seam --out profiles/r10_moe_int4_seam.jsonl      (--seam-rows: 16,32,64,128,256 by default)
+    python tools/moe_bench.py --plan-sweep --out profiles/r10_moe_int4_plans.jsonl
+(profiles/r10_moe_int4_plans.jsonl also holds 8x1, 4x2, 6x1 and 3x2: instantiations that lost or tied in that sweep and were
+deleted after it; the sweep now covers the ones that are left.)
 """
 import argparse
 import json
@@ -224,6 +235,124 @@ def seam(args, out):
                     out.flush()
 
 
+def seam_i4(args, out):
+    """the int4 layer's two routes per pair of projections: the decode kernel on the int4 tiles vs expansion + the tiled kernel"""
+    import ctypes
+
+    from eetq_amd import _lib
+    L = _lib.lib()
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        gu_w = torch.randint(-128, 128, (E, H, I), dtype=torch.int8, device=DEV)
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-2).half()
+        dn_w = torch.randint(-128, 128, (E, I, H // 2), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-2).half()
+        w8 = torch.empty(E * H * 2 * I, dtype=torch.int8, device=DEV)   # one projection's expansion at a time, like the layer
+        g = torch.Generator().manual_seed(1)
+        done = set()
+        for rows in (int(r) for r in args.seam_rows.split(",")):
+            T = max(17, rows * E // k)
+            if T in done:
+                continue
+            done.add(T)
+            S, A = T * k, min(E, T * k)
+            for kind in ("uniform", "skewed"):
+                x = (torch.rand(T, H, device=DEV) - 0.5).half()
+                idx = _routing(T, k, E, kind, g)
+                tabs = [torch.empty(n, dtype=torch.int32, device=DEV) for n in (E, E + 1, S, S, A)]
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                assert L.eetq_moe_route(_ptr(idx), T, k, E, *[_ptr(t) for t in tabs], st) == 0
+                _, offsets, sorted_slot, _, active = tabs
+                inter = torch.empty(S, I, dtype=torch.float16, device=DEV)
+                down = torch.empty(S, H, dtype=torch.float16, device=DEV)
+                tab = (_ptr(offsets), _ptr(sorted_slot), _ptr(active))
+
+                def decode():
+                    a = L.eetq_w4a16_moe_gemm(_ptr(x), _ptr(gu_w), _ptr(gu_s), *tab, _ptr(inter), T, k, E, 2 * I, H, 1, 1, st)
+                    b = L.eetq_w4a16_moe_gemm(_ptr(inter), _ptr(dn_w), _ptr(dn_s), *tab, _ptr(down), T, k, E, H, I, 0, 0, st)
+                    assert a == 0 and b == 0, (a, b)
+
+                def expand_only():
+                    a = L.eetq_expand_i4_to_i8(_ptr(gu_w), _ptr(w8), gu_w.numel(), st)
+                    b = L.eetq_expand_i4_to_i8(_ptr(dn_w), _ptr(w8), dn_w.numel(), st)
+                    assert a == 0 and b == 0, (a, b)
+
+                def expanded():
+                    a = L.eetq_expand_i4_to_i8(_ptr(gu_w), _ptr(w8), gu_w.numel(), st)
+                    b = L.eetq_w8a16_moe_gemm_tiled(_ptr(x), _ptr(w8), _ptr(gu_s), *tab, _ptr(inter), T, k, E, 2 * I, H, 1, 1, st)
+                    c = L.eetq_expand_i4_to_i8(_ptr(dn_w), _ptr(w8), dn_w.numel(), st)
+                    d = L.eetq_w8a16_moe_gemm_tiled(_ptr(inter), _ptr(w8), _ptr(dn_s), *tab, _ptr(down), T, k, E, H, I, 0, 0, st)
+                    assert a == 0 and b == 0 and c == 0 and d == 0, (a, b, c, d)
+                us_dec = _time(decode, args.warmup, args.iters)
+                us_exp = _time(expanded, args.warmup, args.iters)
+                us_only = _time(expand_only, args.warmup, args.iters)
+                rec = {"shape": name, "bits": 4, "H": H, "I": I, "E": E, "k": k, "T": T, "mean_rows": round(S / E, 2), "routing": kind,
+                       "max_rows": int(tabs[0].max()), "us_decode_kernel": round(us_dec, 2), "us_expand_plus_tiled": round(us_exp, 2),
+                       "us_expansions_alone": round(us_only, 2), "decode_over_expanded": round(us_dec / us_exp, 3)}
+                line = json.dumps(rec)
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
+
+
+PLANS = ("8x2", "4x1", "2x1")
+
+
+def plan_child(args):
+    """one process = one forced plan (or none): us of eetq_w4a16_moe_gemm per projection at T = 1, 4, 16, uniform routing"""
+    import ctypes
+
+    from eetq_amd import _lib
+    L = _lib.lib()
+    plan = os.environ.get("EETQ_AMD_MOE_I4_PLAN", "default")
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        gu_w = torch.randint(-128, 128, (E, H, I), dtype=torch.int8, device=DEV)
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-2).half()
+        dn_w = torch.randint(-128, 128, (E, I, H // 2), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-2).half()
+        g = torch.Generator().manual_seed(1)
+        for T in (1, 4, 16):
+            S, A = T * k, min(E, T * k)
+            x = (torch.rand(T, H, device=DEV) - 0.5).half()
+            idx = _routing(T, k, E, "uniform", g)
+            tabs = [torch.empty(n, dtype=torch.int32, device=DEV) for n in (E, E + 1, S, S, A)]
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            assert L.eetq_moe_route(_ptr(idx), T, k, E, *[_ptr(t) for t in tabs], st) == 0
+            _, offsets, sorted_slot, _, active = tabs
+            inter = torch.zeros(S, I, dtype=torch.float16, device=DEV)
+            down = torch.empty(S, H, dtype=torch.float16, device=DEV)
+            tab = (_ptr(offsets), _ptr(sorted_slot), _ptr(active))
+            for proj, fn, K in (("gate_up", lambda: L.eetq_w4a16_moe_gemm(_ptr(x), _ptr(gu_w), _ptr(gu_s), *tab, _ptr(inter), T, k, E,
+                                                                          2 * I, H, 1, 1, st), H),
+                                ("down", lambda: L.eetq_w4a16_moe_gemm(_ptr(inter), _ptr(dn_w), _ptr(dn_s), *tab, _ptr(down), T, k, E,
+                                                                       H, I, 0, 0, st), I)):
+                wv, d = (int(v) for v in plan.split("x")) if plan != "default" else (0, 0)
+                us, lo, hi = _time_stats(fn, args.warmup, args.iters)
+                print(json.dumps({"shape": name, "proj": proj, "K": K, "k_tiles": K // 128, "T": T, "plan": plan,
+                                  "plan_applied": plan == "default" or K // 128 >= wv * d, "us": round(us, 2), "us_min": round(lo, 2),
+                                  "us_max": round(hi, 2)}), flush=True)
+
+
+def plan_sweep(args, out):
+    for plan in ("default",) + PLANS:
+        env = dict(os.environ)
+        if plan != "default":
+            env.update(EETQ_AMD_TUNING="1", EETQ_AMD_MOE_I4_PLAN=plan)
+        cmd = [sys.executable, os.path.abspath(__file__), "--plan-child", "--shapes", args.shapes, "--warmup", str(args.warmup),
+               "--iters", str(args.iters)]
+        res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, check=True)
+        for line in res.stdout.splitlines():
+            if line.startswith("{"):
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
+
+
 def _host_path_times(args):
     """{(shape, T, routing): us} of the layer on the host path, from a child process that sets the A/B switch"""
     env = dict(os.environ, EETQ_AMD_TUNING="1", EETQ_AMD_MOE_HOST="1")
@@ -250,11 +379,25 @@ def main():
     ap.add_argument("--host-path", action="store_true", help="add us_host_path: the T > 16 host path, timed in a child process")
     ap.add_argument("--no-baselines", action="store_true", help="skip the fp16 eager forward and the per-expert Python loop")
     ap.add_argument("--seam", action="store_true", help="sweep the seam between the two grouped kernels (DESIGN.md 4.10)")
-    ap.add_argument("--seam-rows", default="1,2,4,8,16,32,64", help="mean rows per expert of the seam sweep")
+    ap.add_argument("--seam-rows", default=None,
+                    help="mean rows per expert of the seam sweep (default 1,2,4,8,16,32,64; 16,32,64,128,256 with --bits 4)")
+    ap.add_argument("--bits", type=int, choices=(8, 4), default=8, help="the layer table / --seam on int8 or int4 expert stacks")
+    ap.add_argument("--plan-sweep", action="store_true", help="sweep eetq_w4a16_moe_gemm's instantiations (DESIGN.md 4.12)")
+    ap.add_argument("--plan-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.seam:
+    if args.plan_child:
+        plan_child(args)
+        return
+    if args.plan_sweep:
         out = open(args.out, "w") if args.out else None
-        seam(args, out)
+        plan_sweep(args, out)
+        if out:
+            out.close()
+        return
+    if args.seam:
+        args.seam_rows = args.seam_rows or ("16,32,64,128,256" if args.bits == 4 else "1,2,4,8,16,32,64")
+        out = open(args.out, "w") if args.out else None
+        (seam_i4 if args.bits == 4 else seam)(args, out)
         if out:
             out.close()
         return
@@ -272,7 +415,9 @@ def main():
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts
 
     from eetq_amd import _lib
-    from eetq_amd.ops import w8_a16_gemm, w8_a16_moe
+    from eetq_amd.ops import w4_a16_moe, w4_a16_moe_path, w8_a16_gemm, w8_a16_moe
+    if args.bits == 4:
+        args.no_baselines = True
     host = _lib.lib().eetq_diag_moe_host_path() == 1
     out = open(args.out, "w") if args.out else None
     for name in args.shapes.split(","):
@@ -282,6 +427,10 @@ def main():
         gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-3).half()
         dn_w = torch.randint(-127, 128, (E, I, H), dtype=torch.int8, device=DEV)
         dn_s = (torch.rand(E, H, device=DEV) * 1e-3).half()
+        if args.bits == 4:   # any bytes are valid int4 stacks: [E, H, I] and [E, I, H / 2]
+            gu_w = torch.randint(-128, 128, (E, H, I), dtype=torch.int8, device=DEV)
+            dn_w = torch.randint(-128, 128, (E, I, H // 2), dtype=torch.int8, device=DEV)
+        layer = w4_a16_moe if args.bits == 4 else w8_a16_moe
         if not args.no_baselines:
             cfg = MixtralConfig(hidden_size=H, intermediate_size=I, num_local_experts=E, num_experts_per_tok=k)
             cfg._experts_implementation = "eager"
@@ -306,12 +455,14 @@ def main():
                         y.index_add_(0, tok, d * wts[tok, j, None].half())
                     return y
 
-                us, us_lo, us_hi = _time_stats(lambda: w8_a16_moe(x, idx, wts, gu_w, gu_s, dn_w, dn_s), args.warmup, args.iters)
-                nbytes = len(active) * 3 * H * I
+                us, us_lo, us_hi = _time_stats(lambda: layer(x, idx, wts, gu_w, gu_s, dn_w, dn_s), args.warmup, args.iters)
+                nbytes = len(active) * 3 * H * I * args.bits // 8
                 rec = {"shape": name, "H": H, "I": I, "E": E, "k": k, "T": T, "routing": kind, "active_experts": len(active),
                        "path": "host" if host and T > 16 else "device", "us": round(us, 2), "us_min": round(us_lo, 2),
-                       "us_max": round(us_hi, 2), "int8_bytes": nbytes,
+                       "us_max": round(us_hi, 2), "bits": args.bits, "int8_bytes" if args.bits == 8 else "int4_bytes": nbytes,
                        "TBps": round(nbytes / us / 1e6, 3), "TFLOPs": round(6.0 * T * k * H * I / us / 1e6, 1)}
+                if args.bits == 4:
+                    rec["path"] = w4_a16_moe_path(T, k, E, H, I)
                 if (name, T, kind) in host_us:
                     rec["us_host_path"], rec["us_host_path_min"], rec["us_host_path_max"] = host_us[(name, T, kind)]
                     rec["host_over_device"] = round(rec["us_host_path"] / us, 2)
