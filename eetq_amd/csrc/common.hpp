@@ -269,7 +269,8 @@ int launch_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, i
 int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
                       int E, int N, int K, hipStream_t stream);
 // grouped LDS-tiled forward over an [E][K][N] stack on eetq_moe_route's tables (moe_gemm_tiled.hip): the prompt path of the routed
-// experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs moe_gemm_kernel
+// experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs the
+// decode kernel (moe_gemm_kernel.hpp)
 bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather);
 int  launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
                            const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream);

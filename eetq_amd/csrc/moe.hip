@@ -1,10 +1,9 @@
 // Routed mixture-of-experts kernels: device-side routing tables, the grouped W8A16 GEMM over an [E][K][N] int8
-// expert stack that reads them, and the weighted combine; and the backward's combine and gated-activation steps (DESIGN.md 4.11,
-// whose grouped input-gradient GEMM lives in gemm_t.hip).  No launch needs a host sync, so a decode step's MoE layer
-// (route -> gate|up GEMM with the gated activation -> down GEMM -> combine) can be captured in a graph; the grid of every launch
-// depends on T, k, E, N and K only, never on the routing.
-#include "common.hpp"
-#include "gemv_kernel.hpp"
+// expert stack that reads them (the BITS = 8 instantiations of moe_gemm_kernel.hpp), and the weighted combine; and the backward's
+// combine and gated-activation steps (whose grouped input-gradient GEMM lives in gemm_t.hip).  No launch needs a
+// host sync, so a decode step's MoE layer (route -> gate|up GEMM with the gated activation -> down GEMM -> combine) can be
+// captured in a graph; the grid of every launch depends on T, k, E, N and K only, never on the routing.
+#include "moe_gemm_kernel.hpp"
 
 namespace eetq {
 
@@ -12,7 +11,6 @@ namespace {
 
 constexpr int kRouteThreads = 1024;  // 16 waves; wave w owns the w-th contiguous segment of the T*k slots
 constexpr int kRouteWaves   = kRouteThreads / 64;
-constexpr int kMoeMaxExperts = 1024;
 
 // exclusive block-wide prefix sum of v (every thread of the kRouteThreads calls it); *total = the sum over the block.
 // wsum: kRouteWaves ints of LDS.  Deterministic: a fixed tree of integer adds.
@@ -122,130 +120,6 @@ __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const int64_t*
     }
 }
 
-// Grouped GEMM over the expert stack: the small-batch stream kernel's body (streamk_kernel.hpp, one row tile, activations straight
-// from global memory: XM = 0, int8) with a row map.  blockIdx.y = active slot a (exit on -1), blockIdx.x = 16-column tile row.
-// Rows of expert e: sorted positions offsets[e] .. offsets[e + 1] - 1, taken 16 at a time (one MFMA row tile; T <= 16 needs one).
-// Row p reads x[sorted_slot[p] / k] (GATHER) or x[p], and writes y[p].  The expert's weight tile row is streamed once per 16 rows.
-// GLU8: columns in glu8 order (8 gate + the matching 8 up per 16-column tile), y[p][8 tile + c] = silu_mul(gate, up) -- the
-// streamk kernel's glu8 epilogue, i.e. the projection followed by eetq_silu_mul_glu8_f16, bit for bit.
-template <int WAVES, int D, bool GATHER, bool GLU8>
-__global__ __launch_bounds__(WAVES * 64) void moe_gemm_kernel(const f16* __restrict__ x, const uint8_t* __restrict__ w_all,
-                                                               const f16* __restrict__ scales_all, const int* __restrict__ offsets,
-                                                               const int* __restrict__ sorted_slot, const int* __restrict__ active,
-                                                               f16* __restrict__ y, int topk, int N, int K)
-{
-    const int e = active[blockIdx.y];
-    if (e < 0) return;
-    const int p0 = offsets[e], rows = offsets[e + 1] - p0;
-
-    __shared__ float red[WAVES * 256];
-    const int tid  = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int KT    = K / kTileK;
-    const int ntile = blockIdx.x;
-
-    const uint8_t* w      = w_all + (size_t)e * K * N;
-    const f16*     scales = scales_all + (size_t)e * N;
-    const u32      sraw   = reinterpret_cast<const uint16_t*>(scales)[ntile * 16 + c];
-    const u32x4*   wp     = reinterpret_cast<const u32x4*>(w + (size_t)ntile * KT * kTileBytes) + lane;  // + 64 per k tile
-
-    for (int r0 = 0; r0 < rows; r0 += 16) {
-        // lane (g, c) feeds row r0 + c (clamped: rows beyond the expert's compute garbage that is never stored)
-        const int rc = r0 + c < rows ? r0 + c : rows - 1;
-        const int xr = GATHER ? sorted_slot[p0 + rc] / topk : p0 + rc;
-        const u32x4* xrow = reinterpret_cast<const u32x4*>(x + (size_t)xr * K + 16 * g);  // + 8 u32x4 per k tile
-
-        struct Stage {
-            u32x4 wq, xa[2];
-        };
-        auto load_stage = [&](int kt, Stage& s) {
-            s.wq    = gemv::load_w<true>(wp + (size_t)kt * 64);
-            s.xa[0] = xrow[(size_t)kt * 8];
-            s.xa[1] = xrow[(size_t)kt * 8 + 1];
-        };
-        f32x4       acc    = {0.f, 0.f, 0.f, 0.f};
-        const f16x2 scale2 = as_f16x2(sraw | (sraw << 16));
-        auto consume = [&](const Stage& s) {
-            f16x2 wq[8];
-            dequant_16(s.wq, scale2, wq);
-            const f16x8 b0 = {wq[0].x, wq[0].y, wq[1].x, wq[1].y, wq[2].x, wq[2].y, wq[3].x, wq[3].y};
-            const f16x8 b1 = {wq[4].x, wq[4].y, wq[5].x, wq[5].y, wq[6].x, wq[6].y, wq[7].x, wq[7].y};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, s.xa[0]), b0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, s.xa[1]), b1, acc, 0, 0, 0);
-        };
-
-        // software-pipelined K loop over this wave's tiles (k tiles wave, wave + WAVES, ...; >= D of them by launch contract)
-        const int n = (KT - wave + WAVES - 1) / WAVES;
-        Stage     st[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) load_stage(wave + d * WAVES, st[d]);
-        int i = 0;
-        for (; i + 2 * D <= n; i += D) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                consume(st[d]);
-                load_stage(wave + (i + d + D) * WAVES, st[d]);
-            }
-        }
-        const int r = n - (i + D);
-        Stage     tail[D > 1 ? D - 1 : 1];
-#pragma unroll
-        for (int d = 0; d < D - 1; ++d) {
-            const int t = i + D + d;
-            load_stage(wave + (t < n ? t : n - 1) * WAVES, tail[d]);
-        }
-#pragma unroll
-        for (int d = 0; d < D; ++d) consume(st[d]);
-#pragma unroll
-        for (int d = 0; d < D - 1; ++d)
-            if (d < r) consume(tail[d]);
-
-        // cross-wave reduction: acc[j] = partial y[row 4g + j][column c]
-#pragma unroll
-        for (int j = 0; j < 4; ++j) red[wave * 256 + (4 * g + j) * 16 + c] = acc[j];
-        __syncthreads();
-        for (int o = tid; o < 256; o += WAVES * 64) {
-            const int cc = o & 15, rr = o >> 4;
-            if (r0 + rr < rows) {
-                const size_t p = (size_t)p0 + r0 + rr;
-                if constexpr (GLU8) {
-                    if (cc < 8) {
-                        float sg = 0.f, su = 0.f;
-#pragma unroll
-                        for (int wv = 0; wv < WAVES; ++wv) {
-                            sg += red[wv * 256 + o];
-                            su += red[wv * 256 + o + 8];
-                        }
-                        y[p * (N >> 1) + ntile * 8 + cc] = silu_mul_f16((f16)sg, (f16)su);
-                    }
-                } else {
-                    float s = 0.f;
-#pragma unroll
-                    for (int wv = 0; wv < WAVES; ++wv) s += red[wv * 256 + o];
-                    y[p * N + ntile * 16 + cc] = (f16)s;
-                }
-            }
-        }
-        __syncthreads();  // red is rewritten by the next 16 rows
-    }
-}
-
-template <int WAVES, int D>
-int launch_moe_gemm_inst(const f16* x, const uint8_t* w, const f16* s, const int* offsets, const int* sorted_slot,
-                         const int* active, f16* y, int topk, int A, int N, int K, bool gather, bool glu8, hipStream_t stream)
-{
-    const dim3 grid(N / kTileN, A), block(WAVES * 64);
-    if (gather)
-        glu8 ? launch_kernel(moe_gemm_kernel<WAVES, D, true, true>, grid, block, 0, stream, x, w, s, offsets, sorted_slot, active, y, topk, N, K)
-             : launch_kernel(moe_gemm_kernel<WAVES, D, true, false>, grid, block, 0, stream, x, w, s, offsets, sorted_slot, active, y, topk, N, K);
-    else
-        glu8 ? launch_kernel(moe_gemm_kernel<WAVES, D, false, true>, grid, block, 0, stream, x, w, s, offsets, sorted_slot, active, y, topk, N, K)
-             : launch_kernel(moe_gemm_kernel<WAVES, D, false, false>, grid, block, 0, stream, x, w, s, offsets, sorted_slot, active, y, topk, N, K);
-    return check_hip(hipGetLastError(), "moe_gemm_kernel launch");
-}
-
 // out[t][h] = fp16( sum_{j < k, in order} fp32(y[position[t k + j]][h]) * fp32(w[t][j]) ), slots with position -1 skipped.
 // grid (ceil(H / 2048), T), 256 threads x 8 columns (16-byte loads; H % 8 == 0).
 template <typename WT>
@@ -352,26 +226,25 @@ __global__ __launch_bounds__(256) void silu_mul_glu8_bwd_kernel(const f16* __res
     *reinterpret_cast<f16x8*>(dgu + 2 * idx + 8) = du;
 }
 
-bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+}  // namespace
 
-// the argument checks eetq_w8a16_moe_gemm and eetq_w8a16_moe_gemm_tiled share (`fn` names the entry in the messages)
-int moe_gemm_check(const char* fn, const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
-                   const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8)
+int moe_gemm_check(const char* fn, int bits, const void* x, const int8_t* w_packed, const void* scales, const int* offsets,
+                   const int* sorted_slot, const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8)
 {
     const std::string f(fn);
+    const int         tk = bits == 4 ? gemv::Codec<4>::kTileK : kTileK;
     EETQ_REQUIRE(x && w_packed && scales && offsets && active && y && (sorted_slot || !gather), f + ": null pointer");
     EETQ_REQUIRE(E >= 1 && E <= kMoeMaxExperts, f + ": E must be in [1, 1024]");
     EETQ_REQUIRE(k >= 1 && k <= E, f + ": k must be in [1, E]");
     EETQ_REQUIRE(T >= 1 && (long long)T * k <= (1ll << 30), f + ": T must be >= 1 and T * k <= 2^30");
-    EETQ_REQUIRE(N >= kTileN && N % kTileN == 0 && K >= kTileK && K % kTileK == 0,
-                 f + ": the gfx950 layout needs K % 64 == 0 and N % 16 == 0");
+    EETQ_REQUIRE(N >= kTileN && N % kTileN == 0 && K >= tk && K % tk == 0,
+                 f + (bits == 4 ? ": the gfx950 int4 layout needs K % 128 == 0 and N % 16 == 0"
+                                : ": the gfx950 layout needs K % 64 == 0 and N % 16 == 0"));
     EETQ_REQUIRE((gather == 0 || gather == 1) && (glu8 == 0 || glu8 == 1), f + ": gather and glu8 are 0 or 1");
     EETQ_REQUIRE((long long)T * k * K < (1ll << 40) && (long long)E * K * N < (1ll << 40), f + ": activation or weight stack too large");
     EETQ_REQUIRE(aligned16(x) && aligned16(w_packed) && aligned16(y), "x, weight and y must be 16-byte aligned");
     return EETQ_OK;
 }
-
-}  // namespace
 
 }  // namespace eetq
 
@@ -402,31 +275,32 @@ int eetq_moe_route(const int64_t* top_k_index, int T, int k, int E, int* counts,
 int eetq_w8a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
                         const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream)
 {
-    const int st = moe_gemm_check("eetq_w8a16_moe_gemm", x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8);
+    const int st = moe_gemm_check("eetq_w8a16_moe_gemm", 8, x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather,
+                                  glu8);
     if (st != EETQ_OK) return st;
-    const int   S  = T * k;
-    const int   A  = S < E ? S : E;
-    const int   KT = K / kTileK;
-    const auto  xp = static_cast<const f16*>(x);
-    const auto  wp = reinterpret_cast<const uint8_t*>(w_packed);
-    const auto  sp = static_cast<const f16*>(scales);
-    const auto  yp = static_cast<f16*>(y);
-    hipStream_t s  = static_cast<hipStream_t>(stream);
-    const bool  g = gather != 0, a = glu8 != 0;
+    const MoeGemmArgs a = moe_gemm_args(x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8, stream);
+    const int         KT = K / kTileK;
     // every wave must own >= D k tiles: 8 waves from K = 1024, 4 from K = 512
-    if (KT >= 16) return launch_moe_gemm_inst<8, 2>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
-    if (KT >= 8) return launch_moe_gemm_inst<4, 2>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
-    return launch_moe_gemm_inst<1, 1>(xp, wp, sp, offsets, sorted_slot, active, yp, k, A, N, K, g, a, s);
+    if (KT >= 16) return launch_moe_gemm_inst<8, 8, 2>(a);
+    if (KT >= 8) return launch_moe_gemm_inst<8, 4, 2>(a);
+    return launch_moe_gemm_inst<8, 1, 1>(a);
 }
 
 int eetq_w8a16_moe_gemm_tiled(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
                               const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream)
 {
-    const int st = moe_gemm_check("eetq_w8a16_moe_gemm_tiled", x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8);
+    const int st = moe_gemm_check("eetq_w8a16_moe_gemm_tiled", 8, x, w_packed, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather,
+                                  glu8);
     if (st != EETQ_OK) return st;
     return launch_moe_gemm_tiled(static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed), static_cast<const f16*>(scales),
                                  offsets, sorted_slot, active, static_cast<f16*>(y), T, k, E, N, K, gather != 0, glu8 != 0,
                                  static_cast<hipStream_t>(stream));
+}
+
+int eetq_w8a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather)
+{
+    if (T < 1 || k < 1 || E < 1 || N < 1 || K < 1) return 0;
+    return moe_gemm_tiled_supports(T, k, E, N, K, gather != 0) ? 1 : 0;
 }
 
 int eetq_diag_moe_host_path(void)

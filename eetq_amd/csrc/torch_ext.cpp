@@ -916,6 +916,44 @@ MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_
     return m;
 }
 
+// eetq_moe_route's tables in one int32 buffer: counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A], S = T k
+// slots, A = min(E, S)
+struct MoeTables {
+    int *counts, *offsets, *sorted, *position, *active;
+    MoeTables(int* p, int64_t E, int64_t S)
+        : counts(p), offsets(p + E), sorted(offsets + E + 1), position(sorted + S), active(position + S)
+    {
+    }
+    static int64_t numel(int64_t E, int64_t S) { return E + (E + 1) + 2 * S + std::min(E, S); }
+    static Tensor  alloc(int64_t E, int64_t S, c10::Device dev)
+    {
+        return torch::empty({numel(E, S)}, at::device(dev).dtype(at::kInt));
+    }
+};
+
+// What the three forwards start with (T >= 1): the device guard, the contiguous hidden states, ids as int64 and router weights, the
+// current stream, and eetq_moe_route into `tables`.  Everything the layer's launches read lives as long as this.
+struct MoeRouted {
+    c10::DeviceGuard guard;
+    Tensor           hidden, idx, wts, tables;
+    MoeTables        t;
+    void*            st;
+    MoeRouted(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, int64_t E, const Tensor& tables_in)
+        : guard(hidden_in.device()), hidden(hidden_in.contiguous()), idx(top_k_index.to(at::kLong).contiguous()),
+          wts(top_k_weights.contiguous()), tables(tables_in), t(tables.data_ptr<int>(), E, idx.numel()), st(stream_of(hidden_in))
+    {
+        check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)idx.size(0), (int)idx.size(1), (int)E, t.counts, t.offsets, t.sorted,
+                             t.position, t.active, st));
+    }
+};
+
+// out [T, H] = the router-weighted sum of each token's k rows of y [T k, H] (wts [T, k], float32 or float16)
+void moe_combine(const Tensor& y, const int* position, const Tensor& wts, Tensor& out, void* st)
+{
+    check(eetq_moe_combine_f16(y.data_ptr(), position, wts.data_ptr(), wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16,
+                               out.data_ptr(), (int)out.size(0), (int)wts.size(1), (int)out.size(1), st));
+}
+
 // One grouped projection of the layer.  Which of the two grouped kernels serves it is decided from the SHAPES alone -- the counts live
 // on the device -- so every call with the same (T, k, E, N, K) runs the same kernel whatever the routing (a skewed routing costs
 // time, never correctness), and the trainable and the inference forward always agree on it:
@@ -933,19 +971,19 @@ MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_
 // above it the decode kernel re-streams the weights once per 16 rows and loses by S / E / 16.
 constexpr int64_t kMoeTiledMinMeanRows = 16;
 
-void moe_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const int* offsets, const int* sorted, const int* active, void* y,
-                      int64_t T, int64_t k, int64_t E, int64_t N, int64_t K, int gather, int glu8, void* st)
+void moe_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k, int64_t E,
+                      int64_t N, int64_t K, int gather, int glu8, void* st)
 {
     if (T > 16 && T * k >= kMoeTiledMinMeanRows * E) {
-        const int rc = eetq_w8a16_moe_gemm_tiled(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k,
+        const int rc = eetq_w8a16_moe_gemm_tiled(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k,
                                                  (int)E, (int)N, (int)K, gather, glu8, st);
         if (rc != EETQ_ERR_UNSUPPORTED) {
             check(rc);
             return;
         }
     }
-    check(eetq_w8a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E, (int)N, (int)K,
-                              gather, glu8, st));
+    check(eetq_w8a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E, (int)N,
+                              (int)K, gather, glu8, st));
 }
 
 // EETQ_AMD_MOE_HOST=1 behind EETQ_AMD_TUNING=1 (an A/B hook like every other: the library reads it through tuning_env, once per
@@ -957,48 +995,59 @@ bool moe_host_path()
     return on;
 }
 
+// The host path: the expert counts read back once, then every active expert's rows [off, off + c) of the sorted order through the
+// dense W8A16 GEMMs into `down`.  Inference (gate_up null): per expert, gate|up with the fused silu_glu8 write-out on the AUTO path,
+// then down.  Trainable forward: every expert's gate|up plain into gate_up on the kernel the gated write-out uses (EETQ_PATH_STREAM
+// for 2 to 16 rows, AUTO otherwise), one silu_mul over all rows, then every expert's down.
+void moe_host_experts(const MoeRouted& r, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, Tensor& down,
+                      Tensor* gate_up)
+{
+    const int64_t E = gu_w.size(0), k = r.idx.size(1);
+    const Tensor  counts_h = r.tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
+    const Tensor  sorted_t = r.tables.narrow(0, r.t.sorted - r.t.counts, r.idx.numel());
+    std::vector<std::tuple<int64_t, int64_t, int64_t>> experts;  // e, off, c
+    int64_t                                            n = 0;
+    for (int64_t e = 0; e < E; ++e)
+        if (const int64_t c = counts_h.data_ptr<int>()[e]) {
+            experts.emplace_back(e, n, c);
+            n += c;
+        }
+    auto gathered = [&](int64_t off, int64_t c) { return r.hidden.index_select(0, sorted_t.narrow(0, off, c).div(k, "floor")); };
+    auto project  = [](const Tensor& in, const Tensor& w, const Tensor& s, Tensor& y, int64_t off, int64_t c, int path) {
+        Tensor rows = y.narrow(0, off, c);
+        gemm_launch(in, w, s, rows, c, s.numel(), in.size(1), path, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
+    };
+    for (const auto& [e, off, c] : experts) {
+        if (gate_up) {
+            project(gathered(off, c), gu_w[e], gu_s[e], *gate_up, off, c, c >= 2 && c <= 16 ? EETQ_PATH_STREAM : EETQ_PATH_AUTO);
+            continue;
+        }
+        const Tensor gate = w8_a16_gemm(gathered(off, c), gu_w[e], gu_s[e], "auto", std::nullopt, std::nullopt, std::nullopt, false,
+                                        std::string("silu_glu8"));
+        project(gate, dn_w[e], dn_s[e], down, off, c, EETQ_PATH_AUTO);
+    }
+    if (!gate_up || !n) return;
+    const Tensor inter = silu_mul(gate_up->narrow(0, 0, n), true);
+    for (const auto& [e, off, c] : experts) project(inter.narrow(0, off, c), dn_w[e], dn_s[e], down, off, c, EETQ_PATH_AUTO);
+}
+
 Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
                   const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
 {
     const auto [E, H, N1, I] = moe_check("w8_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
-    const auto dev           = hidden_in.device();
-    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
     Tensor        out = torch::empty({T, H}, hidden_in.options());
     if (T == 0) return out;
-    c10::DeviceGuard guard(dev);
-    void*        st     = stream_of(hidden_in);
-    const Tensor hidden = hidden_in.contiguous();
-    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
-    const Tensor wts    = top_k_weights.contiguous();
-    // counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A]
-    Tensor tables = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
-    int*   counts = tables.data_ptr<int>();
-    int *  offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
-    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
-    Tensor down = torch::empty({S, H}, hidden.options());
+    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, MoeTables::alloc(E, S, hidden_in.device()));
+    Tensor          down = torch::empty({S, H}, r.hidden.options());
     if (T <= 16 || !moe_host_path()) {
-        Tensor inter = torch::empty({S, I}, hidden.options());
-        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, inter.data_ptr(), T, k, E, N1, H, 1, 1, st);
-        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, st);
+        Tensor inter = torch::empty({S, I}, r.hidden.options());
+        moe_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, inter.data_ptr(), T, k, E, N1, H, 1, 1, r.st);
+        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, r.st);
     } else {
-        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
-        const int*   ch       = counts_h.data_ptr<int>();
-        const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
-        int64_t      off      = 0;
-        for (int64_t e = 0; e < E; ++e) {
-            const int64_t c = ch[e];
-            if (!c) continue;
-            const Tensor tok  = sorted_t.narrow(0, off, c).div(k, "floor");
-            const Tensor gate = w8_a16_gemm(hidden.index_select(0, tok), gu_w[e], gu_s[e], "auto", std::nullopt, std::nullopt,
-                                            std::nullopt, false, std::string("silu_glu8"));
-            Tensor rows = down.narrow(0, off, c);
-            gemm_launch(gate, dn_w[e], dn_s[e], rows, c, H, I, EETQ_PATH_AUTO, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
-            off += c;
-        }
+        moe_host_experts(r, gu_w, gu_s, dn_w, dn_s, down, nullptr);
     }
-    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
-                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
-                               (int)H, st));
+    moe_combine(down, r.t.position, r.wts, out, r.st);
     return out;
 }
 
@@ -1015,56 +1064,22 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden
                                                             const Tensor& dn_w, const Tensor& dn_s)
 {
     const auto [E, H, N1, I] = moe_check("w8_a16_moe_train", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
-    const auto    dev = hidden_in.device();
-    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
     Tensor        out     = torch::empty({T, H}, hidden_in.options());
-    Tensor        tables  = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor        tables  = MoeTables::alloc(E, S, hidden_in.device());
     Tensor        gate_up = torch::empty({S, N1}, hidden_in.options());
     Tensor        down    = torch::empty({S, H}, hidden_in.options());
     if (T == 0) return {out, tables, gate_up, down};
-    c10::DeviceGuard guard(dev);
-    void*        st     = stream_of(hidden_in);
-    const Tensor hidden = hidden_in.contiguous();
-    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
-    const Tensor wts    = top_k_weights.contiguous();
-    int*         counts = tables.data_ptr<int>();
-    int *        offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
-    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
+    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, tables);
     if (T <= 16 || !moe_host_path()) {
-        Tensor inter = torch::empty({S, I}, hidden.options());
-        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, gate_up.data_ptr(), T, k, E, N1, H, 1, 0, st);
-        check(eetq_silu_mul_glu8_f16(gate_up.data_ptr(), inter.data_ptr(), (int)S, (int)I, st));
-        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, st);
+        Tensor inter = torch::empty({S, I}, r.hidden.options());
+        moe_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, gate_up.data_ptr(), T, k, E, N1, H, 1, 0, r.st);
+        check(eetq_silu_mul_glu8_f16(gate_up.data_ptr(), inter.data_ptr(), (int)S, (int)I, r.st));
+        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, r.st);
     } else {
-        const Tensor counts_h = tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
-        const int*   ch       = counts_h.data_ptr<int>();
-        const Tensor sorted_t = tables.narrow(0, 2 * E + 1, S);
-        int64_t      off      = 0;
-        for (int64_t e = 0; e < E; ++e) {
-            const int64_t c = ch[e];
-            if (!c) continue;
-            const Tensor tok  = sorted_t.narrow(0, off, c).div(k, "floor");
-            Tensor       rows = gate_up.narrow(0, off, c);
-            gemm_launch(hidden.index_select(0, tok), gu_w[e], gu_s[e], rows, c, N1, H,
-                        c >= 2 && c <= 16 ? EETQ_PATH_STREAM : EETQ_PATH_AUTO, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
-            off += c;
-        }
-        if (off) {
-            const Tensor inter = silu_mul(gate_up.narrow(0, 0, off), true);
-            off                = 0;
-            for (int64_t e = 0; e < E; ++e) {
-                const int64_t c = ch[e];
-                if (!c) continue;
-                Tensor rows = down.narrow(0, off, c);
-                gemm_launch(inter.narrow(0, off, c), dn_w[e], dn_s[e], rows, c, H, I, EETQ_PATH_AUTO, std::nullopt, std::nullopt,
-                            EETQ_ACT_IDENTITY);
-                off += c;
-            }
-        }
+        moe_host_experts(r, gu_w, gu_s, dn_w, dn_s, down, &gate_up);
     }
-    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
-                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
-                               (int)H, st));
+    moe_combine(down, r.t.position, r.wts, out, r.st);
     return {out, tables, gate_up, down};
 }
 
@@ -1087,9 +1102,9 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
     TORCH_CHECK(top_k_weights.dim() == 2 && top_k_weights.size(0) == grad_out.size(0) && top_k_weights.device() == grad_out.device() &&
                     (top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf),
                 "w8_a16_moe_backward: top_k_weights must be float32 or float16 [T, k] on grad_out's device");
-    const int64_t T = grad_out.size(0), k = top_k_weights.size(1), S = T * k, A = std::min(E, S);
+    const int64_t T = grad_out.size(0), k = top_k_weights.size(1), S = T * k;
     TORCH_CHECK(tables.is_cuda() && tables.scalar_type() == at::kInt && tables.is_contiguous() && tables.dim() == 1 &&
-                    tables.numel() == E + (E + 1) + 2 * S + A && tables.device() == grad_out.device(),
+                    tables.numel() == MoeTables::numel(E, S) && tables.device() == grad_out.device(),
                 "w8_a16_moe_backward: tables must be w8_a16_moe_train's int32 routing tables for these T, k and E");
     TORCH_CHECK(gate_up.scalar_type() == at::kHalf && gate_up.is_contiguous() && gate_up.dim() == 2 && gate_up.size(0) == S &&
                     gate_up.size(1) == N1 && gate_up.device() == grad_out.device(),
@@ -1109,31 +1124,28 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
     void*      st   = stream_of(grad_out);
     Tensor     dout = grad_out.contiguous();  // a stride-0 gradient (out.sum().backward()) is materialised here
     if (reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 != 0) dout = dout.clone();
-    const int* offsets  = tables.data_ptr<int>() + E;
-    const int* position = offsets + (E + 1) + S;
-    const int* active   = position + S;
-    const int  wdt      = wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16;
-    Tensor     dy       = torch::empty({S, H}, grad_out.options());
+    const MoeTables t(tables.data_ptr<int>(), E, S);
+    const int       wdt = wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16;
+    Tensor          dy  = torch::empty({S, H}, grad_out.options());
     if (need_weights_grad) gw = torch::empty_like(wts);
-    check(eetq_moe_combine_bwd_f16(dout.data_ptr(), y.data_ptr(), position, wts.data_ptr(), wdt, dy.data_ptr(),
+    check(eetq_moe_combine_bwd_f16(dout.data_ptr(), y.data_ptr(), t.position, wts.data_ptr(), wdt, dy.data_ptr(),
                                    need_weights_grad ? gw->data_ptr() : nullptr, (int)T, (int)k, (int)H, st));
     if (!need_input_grad) return {gx, gw};
     // each temporary is released as soon as the next step has consumed it: the peak is dh + dgate_up (+ dy, dx per slot)
     Tensor dh = torch::empty({S, I}, grad_out.options());
-    check(eetq_w8a16_moe_gemm_t(dy.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), offsets, active, dh.data_ptr(), (int)T,
+    check(eetq_w8a16_moe_gemm_t(dy.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), t.offsets, t.active, dh.data_ptr(), (int)T,
                                 (int)k, (int)E, (int)H, (int)I, st));
     dy.reset();
     Tensor dgu = torch::empty({S, N1}, grad_out.options());
     check(eetq_silu_mul_glu8_bwd_f16(gate_up.data_ptr(), dh.data_ptr(), dgu.data_ptr(), (int)S, (int)I, st));
     dh.reset();
     Tensor dxs = torch::empty({S, H}, grad_out.options());
-    check(eetq_w8a16_moe_gemm_t(dgu.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), offsets, active, dxs.data_ptr(), (int)T,
+    check(eetq_w8a16_moe_gemm_t(dgu.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), t.offsets, t.active, dxs.data_ptr(), (int)T,
                                 (int)k, (int)E, (int)N1, (int)H, st));
     dgu.reset();
     const Tensor ones = torch::ones({T, k}, grad_out.options().dtype(at::kFloat));
     gx                = torch::empty({T, H}, grad_out.options());
-    check(eetq_moe_combine_f16(dxs.data_ptr(), position, ones.data_ptr(), EETQ_DTYPE_F32, gx->data_ptr(), (int)T, (int)k, (int)H,
-                               st));
+    moe_combine(dxs, t.position, ones, *gx, st);
     return {gx, gw};
 }
 
@@ -1184,18 +1196,18 @@ std::string w4_a16_moe_path(int64_t T, int64_t k, int64_t E, int64_t H, int64_t 
 }
 
 // One grouped projection over an int4 stack w [E, K, N / 2].  `expand` is set only where the tiled kernel takes the shape.
-void moe_i4_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const int* offsets, const int* sorted, const int* active,
-                         void* y, int64_t T, int64_t k, int64_t E, int64_t N, int64_t K, int gather, int glu8, bool expand, void* st)
+void moe_i4_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k, int64_t E,
+                         int64_t N, int64_t K, int gather, int glu8, bool expand, void* st)
 {
     if (expand) {
         Tensor w8 = torch::empty({E, K, N}, w.options());
         check(eetq_expand_i4_to_i8(w.data_ptr<int8_t>(), w8.data_ptr<int8_t>(), (size_t)w.numel(), st));
-        check(eetq_w8a16_moe_gemm_tiled(x, w8.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E,
+        check(eetq_w8a16_moe_gemm_tiled(x, w8.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E,
                                         (int)N, (int)K, gather, glu8, st));
         return;
     }
-    check(eetq_w4a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), offsets, sorted, active, y, (int)T, (int)k, (int)E, (int)N, (int)K,
-                              gather, glu8, st));
+    check(eetq_w4a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E, (int)N,
+                              (int)K, gather, glu8, st));
 }
 
 Tensor w4_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
@@ -1203,30 +1215,18 @@ Tensor w4_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tens
 {
     const auto [E, H, N1, I] = moe_check("w4_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s, 4);
     TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", "w4_a16_moe: path must be 'auto', 'decode' or 'expand'");
-    const auto dev           = hidden_in.device();
-    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k, A = std::min(E, S);
+    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
     Tensor        out = torch::empty({T, H}, hidden_in.options());
     if (T == 0) return out;
-    c10::DeviceGuard guard(dev);
-    void*        st     = stream_of(hidden_in);
-    const Tensor hidden = hidden_in.contiguous();
-    const Tensor idx    = top_k_index.to(at::kLong).contiguous();
-    const Tensor wts    = top_k_weights.contiguous();
     TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
                 "w4_a16_moe: path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
-    const bool   expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
-    // counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A]
-    Tensor tables = torch::empty({E + (E + 1) + 2 * S + A}, torch::TensorOptions().dtype(at::kInt).device(dev));
-    int*   counts = tables.data_ptr<int>();
-    int *  offsets = counts + E, *sorted = offsets + E + 1, *position = sorted + S, *active = position + S;
-    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, counts, offsets, sorted, position, active, st));
-    Tensor inter = torch::empty({S, I}, hidden.options());
-    Tensor down  = torch::empty({S, H}, hidden.options());
-    moe_i4_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, offsets, sorted, active, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, st);
-    moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, offsets, sorted, active, down.data_ptr(), T, k, E, H, I, 0, 0, expand, st);
-    check(eetq_moe_combine_f16(down.data_ptr(), position, wts.data_ptr(),
-                               wts.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16, out.data_ptr(), (int)T, (int)k,
-                               (int)H, st));
+    const bool      expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
+    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, MoeTables::alloc(E, S, hidden_in.device()));
+    Tensor          inter = torch::empty({S, I}, r.hidden.options());
+    Tensor          down  = torch::empty({S, H}, r.hidden.options());
+    moe_i4_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, r.st);
+    moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, expand, r.st);
+    moe_combine(down, r.t.position, r.wts, out, r.st);
     return out;
 }
 

@@ -138,7 +138,53 @@ class W4A16Linear(nn.Module):
                                                                         self.bias is not None)
 
 
-class W8A16Experts(nn.Module):
+class _QuantExperts(nn.Module):
+    """What :class:`W8A16Experts` and :class:`W4A16Experts` share: the four buffers (``bits`` per weight, 8 / bits values per byte
+    along the last dimension), the scaffolding of :meth:`from_experts` and ``extra_repr``.  A subclass sets ``bits`` and gives
+    ``unsupported_reason``, ``_quantize_gate_up`` and ``forward``."""
+
+    bits = None
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
+        super().__init__()
+        self.num_experts = num_experts
+        self.hidden_dim = hidden_dim
+        self.intermediate_dim = intermediate_dim
+        E, H, I, pack = num_experts, hidden_dim, intermediate_dim, 8 // self.bits
+        self.register_buffer("gate_up_qweight", torch.zeros((E, H, 2 * I // pack), dtype=torch.int8, device=dev))
+        self.register_buffer("gate_up_scales", torch.zeros((E, 2 * I), dtype=torch.float16, device=dev))
+        self.register_buffer("down_qweight", torch.zeros((E, I, H // pack), dtype=torch.int8, device=dev))
+        self.register_buffer("down_scales", torch.zeros((E, H), dtype=torch.float16, device=dev))
+
+    @classmethod
+    def from_experts(cls, module, init_only=False):
+        """Quantise a transformers experts module (see :meth:`unsupported_reason` for what is taken; anything else raises
+        ValueError before any GPU work).  Each expert is quantised per output channel by ``ops.quant_weights``."""
+        why = cls.unsupported_reason(module)
+        if why is not None:
+            raise ValueError("%s.from_experts: %s: %s" % (cls.__name__, type(module).__name__, why))
+        gu, dn = module.gate_up_proj, module.down_proj
+        E, n2, H = gu.shape
+        mod = cls(E, H, n2 // 2, dev=gu.device)
+        if init_only:
+            return mod
+        if gu.dtype != torch.float16 or dn.dtype != torch.float16:
+            raise ValueError("Unsupported data type: {}".format(gu.dtype))
+        with torch.no_grad():
+            q, s = cls._quantize_gate_up(gu.detach().transpose(1, 2))  # from [E, H, 2I] gate | up
+            mod.gate_up_qweight = q.to(gu.device)
+            mod.gate_up_scales = s.to(gu.device)
+            q, s = quant_weights(dn.detach().transpose(1, 2).contiguous(), torch.int8 if cls.bits == 8 else torch.quint4x2, False)
+            mod.down_qweight = q.to(gu.device)  # [E, I, H * bits / 8]
+            mod.down_scales = s.half().to(gu.device)
+        return mod
+
+    def extra_repr(self):
+        return "num_experts={}, hidden_dim={}, intermediate_dim={}{}".format(self.num_experts, self.hidden_dim, self.intermediate_dim,
+                                                                             "" if self.bits == 8 else ", bits=%d" % self.bits)
+
+
+class W8A16Experts(_QuantExperts):
     """int8 stand-in for transformers' 3-D experts modules (``MixtralExperts``, ``Qwen3MoeExperts``, ...): same forward signature
     ``(hidden_states [T, H], top_k_index [T, k], top_k_weights [T, k]) -> [T, H]``, so the MoE block's ``self.experts(...)`` call
     is unchanged.  Buffers: ``gate_up_qweight`` int8 [E, H, 2I] (per expert the gfx950 layout, columns in glu8 order: 8 gate + the
@@ -154,16 +200,7 @@ class W8A16Experts(nn.Module):
 
     trainable = False   # a plain attribute, not a buffer: state dicts do not change
 
-    def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
-        super().__init__()
-        self.num_experts = num_experts
-        self.hidden_dim = hidden_dim
-        self.intermediate_dim = intermediate_dim
-        E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.register_buffer("gate_up_qweight", torch.zeros((E, H, 2 * I), dtype=torch.int8, device=dev))
-        self.register_buffer("gate_up_scales", torch.zeros((E, 2 * I), dtype=torch.float16, device=dev))
-        self.register_buffer("down_qweight", torch.zeros((E, I, H), dtype=torch.int8, device=dev))
-        self.register_buffer("down_scales", torch.zeros((E, H), dtype=torch.float16, device=dev))
+    bits = 8
 
     @staticmethod
     def unsupported_reason(module):
@@ -187,31 +224,15 @@ class W8A16Experts(nn.Module):
             return "the gfx950 layout needs H %% 64 == 0 and I %% 64 == 0 (H = %d, I = %d)" % (H, n2 // 2)
         return None
 
-    @classmethod
-    def from_experts(cls, module, init_only=False):
-        """Quantise a transformers experts module (see :meth:`unsupported_reason` for what is taken; anything else raises
-        ValueError before any GPU work).  Each expert is quantised per output channel by ``ops.quant_weights``."""
-        why = cls.unsupported_reason(module)
-        if why is not None:
-            raise ValueError("W8A16Experts.from_experts: %s: %s" % (type(module).__name__, why))
-        gu, dn = module.gate_up_proj, module.down_proj
-        E, n2, H = gu.shape
-        I = n2 // 2
-        mod = cls(E, H, I, dev=gu.device)
-        if init_only:
-            return mod
-        if gu.dtype != torch.float16 or dn.dtype != torch.float16:
-            raise ValueError("Unsupported data type: {}".format(gu.dtype))
+    @staticmethod
+    def _quantize_gate_up(w):
+        """int8 tiles and scales of the [E, H, 2I] gate | up weights: quantised in that order, then put in glu8 order"""
         from ..utils.fuse import _glu8_interleave_columns, _glu8_interleave_tiles
-        with torch.no_grad():
-            q, s = quant_weights(gu.detach().transpose(1, 2).contiguous(), torch.int8, False)  # [E, H, 2I] gate | up
-            halves = q.reshape(E, 2, -1)  # per expert: the I/16 gate tile rows, then the I/16 up tile rows
-            mod.gate_up_qweight = _glu8_interleave_tiles(halves[:, 0], halves[:, 1], H).reshape(E, H, n2).to(gu.device)
-            mod.gate_up_scales = _glu8_interleave_columns(s[:, :I], s[:, I:]).half().contiguous().to(gu.device)
-            q, s = quant_weights(dn.detach().transpose(1, 2).contiguous(), torch.int8, False)  # [E, I, H]
-            mod.down_qweight = q.to(gu.device)
-            mod.down_scales = s.half().to(gu.device)
-        return mod
+        E, H, n2 = w.shape
+        q, s = quant_weights(w.contiguous(), torch.int8, False)
+        halves = q.reshape(E, 2, -1)  # per expert: the I/16 gate tile rows, then the I/16 up tile rows
+        return (_glu8_interleave_tiles(halves[:, 0], halves[:, 1], H).reshape(E, H, n2),
+                _glu8_interleave_columns(s[:, :n2 // 2], s[:, n2 // 2:]).half().contiguous())
 
     def forward(self, hidden_states, top_k_index, top_k_weights):
         """Any number of tokens: four launches (five when trainable), no host sync, capturable in a graph.  The two grouped GEMMs run
@@ -225,12 +246,8 @@ class W8A16Experts(nn.Module):
             return w8_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
                               self.down_qweight, self.down_scales)
 
-    def extra_repr(self):
-        return "num_experts={}, hidden_dim={}, intermediate_dim={}".format(self.num_experts, self.hidden_dim,
-                                                                           self.intermediate_dim)
 
-
-class W4A16Experts(nn.Module):
+class W4A16Experts(_QuantExperts):
     """int4 stand-in for transformers' 3-D experts modules: :class:`W8A16Experts` at half the expert bytes, same
     forward signature.  Buffers: ``gate_up_qweight`` int8 [E, H, I] (= [E, K = H, N / 2] with N = 2I: two values per byte; per expert
     the gfx950 int4 layout of its [H, 2I] weight, columns in glu8 order: 8 gate + the matching 8 up per 16-column tile),
@@ -240,16 +257,7 @@ class W4A16Experts(nn.Module):
     Inference only: there is no int4 backward, the module has no ``trainable`` flag and ``utils.set_trainable`` passes it by;
     its output is always detached.  State dicts hold the four buffers as they are, like :class:`W8A16Experts`."""
 
-    def __init__(self, num_experts, hidden_dim, intermediate_dim, dev="cuda:0"):
-        super().__init__()
-        self.num_experts = num_experts
-        self.hidden_dim = hidden_dim
-        self.intermediate_dim = intermediate_dim
-        E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.register_buffer("gate_up_qweight", torch.zeros((E, H, I), dtype=torch.int8, device=dev))
-        self.register_buffer("gate_up_scales", torch.zeros((E, 2 * I), dtype=torch.float16, device=dev))
-        self.register_buffer("down_qweight", torch.zeros((E, I, H // 2), dtype=torch.int8, device=dev))
-        self.register_buffer("down_scales", torch.zeros((E, H), dtype=torch.float16, device=dev))
+    bits = 4
 
     @staticmethod
     def unsupported_reason(module):
@@ -263,32 +271,14 @@ class W4A16Experts(nn.Module):
             return "the gfx950 int4 layout needs H %% 128 == 0 and I %% 128 == 0 (H = %d, I = %d)" % (H, n2 // 2)
         return None
 
-    @classmethod
-    def from_experts(cls, module, init_only=False):
-        """Quantise a transformers experts module (see :meth:`unsupported_reason`; anything else raises ValueError before any GPU
-        work).  Per-channel quantisation commutes with a permutation of the output channels, so the gate|up columns are put
-        in glu8 order in fp16 and each expert is then quantised and packed by ``ops.quant_weights(w, torch.quint4x2)``."""
-        why = cls.unsupported_reason(module)
-        if why is not None:
-            raise ValueError("W4A16Experts.from_experts: %s: %s" % (type(module).__name__, why))
-        gu, dn = module.gate_up_proj, module.down_proj
-        E, n2, H = gu.shape
-        I = n2 // 2
-        mod = cls(E, H, I, dev=gu.device)
-        if init_only:
-            return mod
-        if gu.dtype != torch.float16 or dn.dtype != torch.float16:
-            raise ValueError("Unsupported data type: {}".format(gu.dtype))
+    @staticmethod
+    def _quantize_gate_up(w):
+        """Per-channel quantisation commutes with a permutation of the output channels, so the gate|up columns are put in glu8
+        order in fp16 and each expert is then quantised and packed by ``ops.quant_weights(w, torch.quint4x2)``."""
         from ..utils.fuse import _glu8_interleave_columns
-        with torch.no_grad():
-            w = gu.detach().transpose(1, 2)  # [E, H, 2I] gate | up
-            q, s = quant_weights(_glu8_interleave_columns(w[..., :I], w[..., I:]).contiguous(), torch.quint4x2, False)
-            mod.gate_up_qweight = q.to(gu.device)
-            mod.gate_up_scales = s.half().to(gu.device)
-            q, s = quant_weights(dn.detach().transpose(1, 2).contiguous(), torch.quint4x2, False)  # [E, I, H / 2]
-            mod.down_qweight = q.to(gu.device)
-            mod.down_scales = s.half().to(gu.device)
-        return mod
+        I = w.shape[2] // 2
+        q, s = quant_weights(_glu8_interleave_columns(w[..., :I], w[..., I:]).contiguous(), torch.quint4x2, False)
+        return q, s.half()
 
     @torch.no_grad()
     def forward(self, hidden_states, top_k_index, top_k_weights):
@@ -297,10 +287,6 @@ class W4A16Experts(nn.Module):
         int8 tiles and runs the grouped tiled W8A16 kernel."""
         return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
                           self.down_qweight, self.down_scales)
-
-    def extra_repr(self):
-        return "num_experts={}, hidden_dim={}, intermediate_dim={}, bits=4".format(self.num_experts, self.hidden_dim,
-                                                                                   self.intermediate_dim)
 
 
 def input_grad(grad_output, weight, scales, x_shape, x_dtype=torch.float16):
