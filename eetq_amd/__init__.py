@@ -21,7 +21,8 @@ def __getattr__(name):
                 "rotary_embedding_neox"):
         from . import ops
         return getattr(ops, name)
-    if name in ("W8A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinear", "EetqLinearMMFunction", "quantize_and_preprocess_weights"):
+    if name in ("W8A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinear", "EetqLinearMMFunction", "quantize_and_preprocess_weights",
+                "EetqTopKRouter", "EetqSparseMoeBlock"):
         from .modules import qlinear
         return getattr(qlinear, name)
     if name in ("eet_quantize", "find_layers", "set_op_by_name"):

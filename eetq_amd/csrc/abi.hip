@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "gemv_kernel.hpp"
+#include "moe_route_tables.hpp"
 
 namespace eetq {
 
@@ -222,6 +223,8 @@ int eetq_release_workspace(size_t* bytes_freed)
     int    st    = release_splitk_workspace(&freed);
     if (st != EETQ_OK) return st;
     st = release_w4a16_workspace(&freed);
+    if (st != EETQ_OK) return st;
+    st = release_moe_router_workspace(&freed);
     if (st != EETQ_OK) return st;
     {
         std::lock_guard<std::mutex> lock(g_scratch_mutex);

@@ -4,6 +4,7 @@
 // host sync, so a decode step's MoE layer (route -> gate|up GEMM with the gated activation -> down GEMM -> combine) can be
 // captured in a graph; the grid of every launch depends on T, k, E, N and K only, never on the routing.
 #include "moe_gemm_kernel.hpp"
+#include "moe_route_tables.hpp"
 
 namespace eetq {
 
@@ -12,112 +13,15 @@ namespace {
 constexpr int kRouteThreads = 1024;  // 16 waves; wave w owns the w-th contiguous segment of the T*k slots
 constexpr int kRouteWaves   = kRouteThreads / 64;
 
-// exclusive block-wide prefix sum of v (every thread of the kRouteThreads calls it); *total = the sum over the block.
-// wsum: kRouteWaves ints of LDS.  Deterministic: a fixed tree of integer adds.
-__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int       inc  = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kRouteWaves; ++w) {
-        const int s = wsum[w];
-        base += w < wave ? s : 0;
-        all += s;
-    }
-    __syncthreads();  // wsum is reused by the next call
-    *total = all;
-    return base + inc - v;
-}
-
-// the lanes of this wave whose expert id equals mine (ids < 2^nbits; invalid lanes pass id = -1 and get an empty mask)
-__device__ __forceinline__ unsigned long long same_id_lanes(int id, int nbits)
-{
-    unsigned long long m = __ballot(id >= 0);
-    for (int b = 0; b < nbits; ++b) {
-        const unsigned long long set = __ballot(id >= 0 && ((id >> b) & 1));
-        m &= ((id >> b) & 1) ? set : ~set;
-    }
-    return id >= 0 ? m : 0ull;
-}
-
-// One workgroup.  Dynamic LDS: kRouteWaves * E ints (per-wave, per-expert counters) + kRouteWaves ints (scan).
-// Pass 1: wave w counts the ids of its slot segment (the lowest lane of every group of equal ids adds the group's size).
-// Scan:   counts, offsets, the active list; every per-wave counter becomes that wave's first position for the expert.
-// Pass 2: wave w walks its segment again in the same order: position = its counter + the rank among equal ids of lower lanes.
-// Segments are in slot order and so are lanes within a chunk: sorted_slot is ordered by expert, then by slot, whatever the timing.
+// One workgroup.  Dynamic LDS: kRouteWaves * E ints (per-wave, per-expert counters) + kRouteWaves ints (scan).  The two passes
+// are route_tables() (moe_route_tables.hpp), which the fused router kernel (moe_router.hip) runs on its own indices as well.
 __global__ __launch_bounds__(kRouteThreads) void moe_route_kernel(const int64_t* __restrict__ idx, int S, int E, int A,
                                                                    int* __restrict__ counts, int* __restrict__ offsets,
                                                                    int* __restrict__ sorted_slot, int* __restrict__ position,
                                                                    int* __restrict__ active)
 {
     extern __shared__ int lds[];
-    int*      cnt  = lds;                     // [kRouteWaves][E]
-    int*      wsum = lds + kRouteWaves * E;   // [kRouteWaves]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nbits = 32 - __clz(E - 1 > 0 ? E - 1 : 1);
-    for (int i = tid; i < kRouteWaves * E; i += kRouteThreads) cnt[i] = 0;
-    __syncthreads();
-
-    const int seg = (S + kRouteWaves - 1) / kRouteWaves;
-    const int s0 = wave * seg, s1 = min(S, s0 + seg);
-    int*      mine = cnt + wave * E;
-    for (int c = s0; c < s1; c += 64) {
-        const int     s  = c + lane;
-        const int64_t v  = s < s1 ? idx[s] : -1;
-        const int     id = (v >= 0 && v < E) ? (int)v : -1;
-        const unsigned long long m = same_id_lanes(id, nbits);
-        if (id >= 0 && (m & ((1ull << lane) - 1)) == 0) mine[id] += __popcll(m);
-    }
-    __syncthreads();
-
-    int carry = 0, carry_active = 0;
-    for (int e0 = 0; e0 < E; e0 += kRouteThreads) {
-        const int e = e0 + tid;
-        int       n = 0;
-        if (e < E)
-            for (int w = 0; w < kRouteWaves; ++w) n += cnt[w * E + e];
-        int       tot_n, tot_a;
-        const int off = carry + block_excl_scan(n, wsum, &tot_n);
-        const int act = carry_active + block_excl_scan(n > 0 ? 1 : 0, wsum, &tot_a);
-        if (e < E) {
-            counts[e]  = n;
-            offsets[e] = off;
-            if (n > 0) active[act] = e;
-            int base = off;
-            for (int w = 0; w < kRouteWaves; ++w) {
-                const int c = cnt[w * E + e];
-                cnt[w * E + e] = base;
-                base += c;
-            }
-        }
-        carry += tot_n;
-        carry_active += tot_a;
-    }
-    if (tid == 0) offsets[E] = carry;
-    for (int a = carry_active + tid; a < A; a += kRouteThreads) active[a] = -1;
-    for (int s = carry + tid; s < S; s += kRouteThreads) sorted_slot[s] = -1;
-    __syncthreads();
-
-    for (int c = s0; c < s1; c += 64) {
-        const int     s  = c + lane;
-        const int64_t v  = s < s1 ? idx[s] : -1;
-        const int     id = (v >= 0 && v < E) ? (int)v : -1;
-        const unsigned long long m = same_id_lanes(id, nbits);
-        const unsigned long long below = m & ((1ull << lane) - 1);
-        int pos = -1;
-        if (id >= 0) pos = mine[id] + __popcll(below);  // every lane reads before the group's lowest lane moves the counter on
-        if (id >= 0) sorted_slot[pos] = s;
-        if (s < s1) position[s] = pos;
-        if (id >= 0 && below == 0) mine[id] += __popcll(m);
-    }
+    route_tables<kRouteThreads>([idx](int s) { return idx[s]; }, S, E, A, lds, counts, offsets, sorted_slot, position, active);
 }
 
 // out[t][h] = fp16( sum_{j < k, in order} fp32(y[position[t k + j]][h]) * fp32(w[t][j]) ), slots with position -1 skipped.

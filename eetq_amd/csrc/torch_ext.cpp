@@ -1230,6 +1230,128 @@ Tensor w4_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tens
     return out;
 }
 
+// ---- the MoE router on the device (extension) ----------------------------------------------------------------
+// What transformers' *TopKRouter forwards return -- (router_logits fp16 [T, E], router_scores [T, k], router_indices int64 [T, k])
+// -- from hidden [T, H] and the router weight [E, H].  T <= 16: eetq_moe_router_f16, ONE launch, which also fills `t` (when given)
+// with eetq_moe_route's tables for its indices.  T > 16: the logits are a real GEMM and stay at::linear's; eetq_moe_topk_f16 and
+// (with `t`) eetq_moe_route follow: three launches.  No host sync either way.
+struct RouterOut {
+    Tensor logits, scores, idx;
+};
+
+at::ScalarType router_scores_dtype(const char* fn, const py::object& scores_dtype)
+{
+    const at::ScalarType dt = scores_dtype.is_none() ? at::kFloat : torch::python::detail::py_object_to_dtype(scores_dtype);
+    TORCH_CHECK(dt == at::kFloat || dt == at::kHalf, fn, ": scores_dtype must be torch.float32 or torch.float16");
+    return dt;
+}
+
+void router_check(const char* fn, const Tensor& hidden, const Tensor& weight, int64_t top_k)
+{
+    TORCH_CHECK(hidden.is_cuda() && hidden.scalar_type() == at::kHalf && hidden.dim() == 2, fn, ": hidden must be a float16 GPU tensor [T, H]");
+    TORCH_CHECK(weight.scalar_type() == at::kHalf && weight.dim() == 2 && weight.device() == hidden.device(),
+                fn, ": the router weight must be a float16 tensor [E, H] on the hidden states' device");
+    TORCH_CHECK(weight.size(1) == hidden.size(1), fn, ": hidden is [T, ", hidden.size(1), "] but the router weight has H = ", weight.size(1));
+    TORCH_CHECK(top_k >= 1 && top_k <= weight.size(0), fn, ": top_k must be in [1, E]");
+    TORCH_CHECK(hidden.size(0) * weight.size(0) < (1ll << 31) && hidden.size(0) * top_k <= (1ll << 30), fn, ": too many tokens");
+}
+
+// hidden and weight contiguous, T >= 1, the device guard set by the caller
+RouterOut router_launch(const Tensor& hidden, const Tensor& weight, int64_t k, bool renorm, at::ScalarType sdt, const MoeTables* t, void* st)
+{
+    const int64_t T = hidden.size(0), H = hidden.size(1), E = weight.size(0);
+    const int     wdt = sdt == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16;
+    RouterOut     r;
+    r.scores = torch::empty({T, k}, hidden.options().dtype(sdt));
+    r.idx    = torch::empty({T, k}, hidden.options().dtype(at::kLong));
+    if (T <= 16) {
+        r.logits = torch::empty({T, E}, hidden.options());
+        check(eetq_moe_router_f16(hidden.data_ptr(), weight.data_ptr(), (int)T, (int)H, (int)E, (int)k, renorm ? 1 : 0, wdt,
+                                  r.logits.data_ptr(), r.idx.data_ptr<int64_t>(), r.scores.data_ptr(), t ? t->counts : nullptr,
+                                  t ? t->offsets : nullptr, t ? t->sorted : nullptr, t ? t->position : nullptr,
+                                  t ? t->active : nullptr, st));
+        return r;
+    }
+    {
+        at::NoGradGuard no_grad;
+        r.logits = at::linear(hidden, weight).contiguous();
+    }
+    check(eetq_moe_topk_f16(r.logits.data_ptr(), (int)T, (int)E, (int)k, renorm ? 1 : 0, wdt, r.idx.data_ptr<int64_t>(),
+                            r.scores.data_ptr(), st));
+    if (t)
+        check(eetq_moe_route(r.idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, t->counts, t->offsets, t->sorted, t->position, t->active,
+                             st));
+    return r;
+}
+
+std::tuple<Tensor, Tensor, Tensor> moe_router(const Tensor& hidden_in, const Tensor& weight_in, int64_t top_k, bool norm_topk_prob,
+                                              const py::object& scores_dtype)
+{
+    const at::ScalarType sdt = router_scores_dtype("moe_router", scores_dtype);
+    router_check("moe_router", hidden_in, weight_in, top_k);
+    const int64_t T = hidden_in.size(0), E = weight_in.size(0);
+    if (T == 0)
+        return {torch::empty({0, E}, hidden_in.options()), torch::empty({0, top_k}, hidden_in.options().dtype(sdt)),
+                torch::empty({0, top_k}, hidden_in.options().dtype(at::kLong))};
+    c10::DeviceGuard guard(hidden_in.device());
+    const Tensor     hidden = hidden_in.detach().contiguous(), weight = weight_in.detach().contiguous();
+    RouterOut        r = router_launch(hidden, weight, top_k, norm_topk_prob, sdt, nullptr, stream_of(hidden_in));
+    return {r.logits, r.scores, r.idx};
+}
+
+// The whole sparse MoE block (extension): router -> grouped GEMM (gather, silu_glu8) -> grouped GEMM -> combine on the
+// stacks of w8_a16_moe (bits = 8) or w4_a16_moe (bits = 4).  The same launches as those layers on the router's output, bit for bit;
+// only the tables come from the router launch (T <= 16: four launches in all) instead of a launch of their own.
+Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor& router_w, int64_t top_k, bool norm_topk_prob,
+                 const py::object& scores_dtype, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s,
+                 const std::string& path)
+{
+    const at::ScalarType sdt = router_scores_dtype(fn, scores_dtype);
+    router_check(fn, hidden_in, router_w, top_k);
+    const auto [E, H, N1, I] = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, hidden_in.device(), bits);
+    TORCH_CHECK(hidden_in.size(1) == H, fn, ": hidden is [T, ", hidden_in.size(1), "] but the experts have H = ", H);
+    TORCH_CHECK(router_w.size(0) == E, fn, ": the router weight has ", router_w.size(0), " experts but the stacks have E = ", E);
+    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", fn, ": path must be 'auto', 'decode' or 'expand'");
+    const int64_t T = hidden_in.size(0), k = top_k, S = T * k;
+    Tensor        out = torch::empty({T, H}, hidden_in.options());
+    if (T == 0) return out;
+    bool expand = false;
+    if (bits == 4) {
+        TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
+                    fn, ": path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
+        expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
+    }
+    c10::DeviceGuard guard(hidden_in.device());
+    const Tensor     hidden = hidden_in.detach().contiguous(), weight = router_w.detach().contiguous();
+    void*            st     = stream_of(hidden_in);
+    Tensor           tables = MoeTables::alloc(E, S, hidden.device());
+    const MoeTables  t(tables.data_ptr<int>(), E, S);
+    const RouterOut  r = router_launch(hidden, weight, k, norm_topk_prob, sdt, &t, st);
+    Tensor           inter = torch::empty({S, I}, hidden.options());
+    Tensor           down  = torch::empty({S, H}, hidden.options());
+    if (bits == 4) {
+        moe_i4_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, t, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, st);
+        moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, t, down.data_ptr(), T, k, E, H, I, 0, 0, expand, st);
+    } else {
+        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, t, inter.data_ptr(), T, k, E, N1, H, 1, 1, st);
+        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, t, down.data_ptr(), T, k, E, H, I, 0, 0, st);
+    }
+    moe_combine(down, t.position, r.scores, out, st);
+    return out;
+}
+
+Tensor w8_a16_moe_block(const Tensor& hidden, const Tensor& router_weight, int64_t top_k, bool norm_topk_prob, const py::object& scores_dtype,
+                        const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+{
+    return moe_block("w8_a16_moe_block", 8, hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s, dn_w, dn_s, "auto");
+}
+
+Tensor w4_a16_moe_block(const Tensor& hidden, const Tensor& router_weight, int64_t top_k, bool norm_topk_prob, const py::object& scores_dtype,
+                        const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
+{
+    return moe_block("w4_a16_moe_block", 4, hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s, dn_w, dn_s, path);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "EETQ operator module on libeetq_amd.so (MI355X / gfx950)";
@@ -1305,5 +1427,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("w4_a16_moe_path", &w4_a16_moe_path,
           "'decode' or 'expand': the grouped kernels w4_a16_moe(path='auto') runs for T tokens, k choices, E experts, H, I",
           py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
+    const py::object f32 = py::module_::import("torch").attr("float32");
+    m.def("moe_router", &moe_router,
+          "transformers' TopKRouter forward on the device: (router_logits fp16 [T, E], router_scores [T, k], router_indices int64 [T, k])",
+          py::arg("hidden"), py::arg("weight"), py::arg("top_k"), py::arg("norm_topk_prob") = true, py::arg("scores_dtype") = f32);
+    m.def("w8_a16_moe_block", &w8_a16_moe_block, "router + routed W8A16 experts: the whole sparse MoE block (four launches at T <= 16)",
+          py::arg("hidden"), py::arg("router_weight"), py::arg("top_k"), py::arg("norm_topk_prob"), py::arg("scores_dtype"),
+          py::arg("gate_up_qweight"), py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"));
+    m.def("w4_a16_moe_block", &w4_a16_moe_block, "router + routed W4A16 experts: the whole sparse MoE block (inference only)",
+          py::arg("hidden"), py::arg("router_weight"), py::arg("top_k"), py::arg("norm_topk_prob"), py::arg("scores_dtype"),
+          py::arg("gate_up_qweight"), py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
     m.attr("__eetq_amd_version__") = eetq_version();
 }

@@ -16,12 +16,12 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import (preprocess_weights, quant_weights, w4_a16_moe, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward,
-                   w8_a16_moe_train)
+from ..ops import (moe_router, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block, w8_a16_gemm, w8_a16_gemm_t,
+                   w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
 __all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
-           "W8A16MoeFunction"]
+           "W8A16MoeFunction", "EetqTopKRouter", "EetqSparseMoeBlock"]
 
 
 def quantize_and_preprocess_weights(weight, scales=None):
@@ -287,6 +287,176 @@ class W4A16Experts(_QuantExperts):
         int8 tiles and runs the grouped tiled W8A16 kernel."""
         return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
                           self.down_qweight, self.down_scales)
+
+
+def _adopt(module, mixin):
+    """Give ``module`` the class ``mixin`` in place: a subclass of (mixin, type(module)) named after the mixin, made once per
+    original class.  The module keeps its parameters, buffers, attributes and hooks, stays an instance of its original class (what
+    transformers' output recorders match on) and finds the original forward as ``_eetq_base.forward``.  The subclass exists only
+    in the process that made it: ``state_dict()`` / ``load_state_dict()`` are unaffected, but pickling a whole converted model
+    (``torch.save(model)``) is not supported -- save the state dict and run ``eet_quantize(..., router=True)`` on the loading side."""
+    base = type(module)
+    if isinstance(module, mixin):
+        return module
+    sub = mixin._adopted.get(base)
+    if sub is None:
+        sub = type(mixin.__name__, (mixin, base), {"__module__": mixin.__module__, "_eetq_base": base})
+        mixin._adopted[base] = sub
+    module.__class__ = sub
+    return module
+
+
+def _observed(module):
+    """True when forward hooks (the module's own or global ones) would see a call of ``module``"""
+    from torch.nn.modules import module as _m
+    return bool(module._forward_hooks or module._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks)
+
+
+class EetqTopKRouter(nn.Module):
+    """Drop-in for transformers' softmax top-k routers -- ``MixtralTopKRouter``, ``Qwen2MoeTopKRouter``, ``Qwen3MoeTopKRouter``,
+    ``OlmoeTopKRouter`` (by class name) -- on ``ops.moe_router``: one launch at T <= 16 instead of
+    ``F.linear -> softmax -> topk -> sum -> div (-> .to)``.  Same parameter (``weight`` [E, H]: state-dict keys do not change), same
+    return triple ``(router_logits [T, E], router_scores [T, k], router_indices int64 [T, k])`` and score dtype: Mixtral float32 and
+    always renormalised, the others ``norm_topk_prob`` and the logits' dtype.
+
+    :meth:`from_router` converts a router in place and keeps it an instance of its original class.  When grad mode is on and
+    ``hidden_states`` or ``weight`` requires grad, the call runs the original torch forward, so router training and the auxiliary
+    loss keep their autograd path; everything else needs fp16 GPU tensors, E <= 256, top_k <= 16 and H % 64 == 0."""
+
+    CLASS_NAMES = ("MixtralTopKRouter", "Qwen2MoeTopKRouter", "Qwen3MoeTopKRouter", "OlmoeTopKRouter")
+    _adopted = {}
+    _eetq_base = None
+
+    def __init__(self, num_experts, hidden_dim, top_k, norm_topk_prob=True, scores_dtype=None, dev=None):
+        """A stand-alone router (``scores_dtype`` None: the logits' dtype, like the Qwen / OLMoE routers)"""
+        super().__init__()
+        self.num_experts, self.hidden_dim, self.top_k = num_experts, hidden_dim, top_k
+        self.norm_topk_prob = norm_topk_prob
+        self._scores_dtype = scores_dtype
+        self.weight = nn.Parameter(torch.zeros(num_experts, hidden_dim, dtype=torch.float16, device=dev))
+
+    @classmethod
+    def unsupported_reason(cls, module):
+        """None when :meth:`from_router` takes ``module``, else why not."""
+        if isinstance(module, cls):
+            return None
+        if type(module).__name__ not in cls.CLASS_NAMES:
+            return "%s is not one of %s" % (type(module).__name__, ", ".join(cls.CLASS_NAMES))
+        w = getattr(module, "weight", None)
+        if not isinstance(w, torch.Tensor) or w.dim() != 2:
+            return "no 2-D weight"
+        if w.dtype != torch.float16:
+            return "the router kernel needs a float16 weight (got %s)" % str(w.dtype).replace("torch.", "")
+        E, H = w.shape
+        k = getattr(module, "top_k", None)
+        if not isinstance(k, int) or not 1 <= k <= min(E, 16) or E > 256:
+            return "the router kernel serves E <= 256 and top_k <= 16 (E = %d, top_k = %r)" % (E, k)
+        if H % 64:
+            return "the router kernel needs H %% 64 == 0 (H = %d)" % H
+        return None
+
+    @classmethod
+    def from_router(cls, module):
+        why = cls.unsupported_reason(module)
+        if why is not None:
+            raise ValueError("EetqTopKRouter.from_router: %s" % why)
+        return _adopt(module, cls)
+
+    @property
+    def renormalises(self):
+        base = self._eetq_base
+        return True if base is not None and base.__name__.startswith("Mixtral") else bool(self.norm_topk_prob)
+
+    def scores_dtype(self, logits_dtype=torch.float16):
+        base = self._eetq_base
+        if base is not None:
+            return torch.float32 if base.__name__.startswith("Mixtral") else logits_dtype
+        return self._scores_dtype if self._scores_dtype is not None else logits_dtype
+
+    def falls_back(self, hidden_states):
+        """True when this call takes the torch forward: grad mode with a gradient to deliver"""
+        return torch.is_grad_enabled() and (hidden_states.requires_grad or self.weight.requires_grad)
+
+    def _torch_forward(self, hidden_states):
+        if self._eetq_base is not None:
+            return self._eetq_base.forward(self, hidden_states)
+        logits = nn.functional.linear(hidden_states, self.weight)
+        top, idx = torch.topk(nn.functional.softmax(logits, dtype=torch.float, dim=-1), self.top_k, dim=-1)
+        if self.norm_topk_prob:
+            top = top / top.sum(dim=-1, keepdim=True)
+        return logits, top.to(self.scores_dtype(logits.dtype)), idx
+
+    def forward(self, hidden_states):
+        hidden_states = hidden_states.reshape(-1, self.hidden_dim)
+        if self.falls_back(hidden_states):
+            return self._torch_forward(hidden_states)
+        with torch.no_grad():
+            return moe_router(hidden_states, self.weight, self.top_k, self.renormalises, self.scores_dtype())
+
+    def extra_repr(self):
+        return "num_experts={}, hidden_dim={}, top_k={}".format(self.weight.shape[0], self.weight.shape[1], self.top_k)
+
+
+class EetqSparseMoeBlock(nn.Module):
+    """Drop-in for the sparse MoE blocks whose forward is exactly ``gate -> experts -> reshape`` -- ``MixtralSparseMoeBlock``,
+    ``Qwen3MoeSparseMoeBlock``, ``OlmoeSparseMoeBlock`` (by class name) -- once their ``gate`` is an :class:`EetqTopKRouter` and their
+    ``experts`` a :class:`W8A16Experts` / :class:`W4A16Experts`: the submodules keep their names, and in inference the block is
+    ``ops.w8_a16_moe_block`` / ``ops.w4_a16_moe_block`` on their buffers (four launches at T <= 16), the bits of
+    ``experts(hidden, *gate(hidden)[2:0:-1])``.
+
+    The original forward (``gate`` then ``experts``, each through its ``__call__``) runs instead whenever the router would fall
+    back (grad mode with a gradient to deliver), the experts are ``trainable`` in grad mode, a Mixtral block is in training mode
+    with jitter noise > 0, or forward hooks observe ``gate`` or ``experts``.  The last rule is how ``output_router_logits=True``
+    keeps working: transformers records the router's output with a forward hook on the gate.  It installs ALL of a model's
+    recording hooks, the gates' included, the first time ANY ``output_*`` flag (``output_router_logits``, ``output_hidden_states``,
+    ``output_attentions``) is asked for, and never removes them: from that call on every block of that model stays on the unfused
+    path for the model's lifetime (the router swap still applies; :meth:`fused` tells)."""
+
+    CLASS_NAMES = ("MixtralSparseMoeBlock", "Qwen3MoeSparseMoeBlock", "OlmoeSparseMoeBlock")
+    _adopted = {}
+    _eetq_base = None
+
+    @classmethod
+    def unsupported_reason(cls, module):
+        """None when :meth:`from_block` takes ``module``, else why not."""
+        if isinstance(module, cls):
+            return None
+        if type(module).__name__ not in cls.CLASS_NAMES:
+            return "%s is not one of %s" % (type(module).__name__, ", ".join(cls.CLASS_NAMES))
+        if not isinstance(getattr(module, "gate", None), EetqTopKRouter):
+            return "its gate is not an EetqTopKRouter"
+        if not isinstance(getattr(module, "experts", None), (W8A16Experts, W4A16Experts)):
+            return "its experts are not quantised"
+        return None
+
+    @classmethod
+    def from_block(cls, module):
+        why = cls.unsupported_reason(module)
+        if why is not None:
+            raise ValueError("EetqSparseMoeBlock.from_block: %s" % why)
+        return _adopt(module, cls)
+
+    def fused(self, hidden_states):
+        """True when this call runs the block op"""
+        gate, experts = self.gate, self.experts
+        if gate.falls_back(hidden_states):
+            return False
+        if getattr(experts, "trainable", False) and torch.is_grad_enabled():
+            return False
+        if self.training and getattr(self, "jitter_noise", 0) > 0:
+            return False
+        return not (_observed(gate) or _observed(experts))
+
+    def forward(self, hidden_states):
+        if not self.fused(hidden_states):
+            return self._eetq_base.forward(self, hidden_states)
+        gate, experts = self.gate, self.experts
+        flat = hidden_states.reshape(-1, hidden_states.shape[-1])
+        args = (flat, gate.weight, gate.top_k, gate.renormalises, gate.scores_dtype(), experts.gate_up_qweight, experts.gate_up_scales,
+                experts.down_qweight, experts.down_scales)
+        with torch.no_grad():
+            out = w4_a16_moe_block(*args) if experts.bits == 4 else w8_a16_moe_block(*args)
+        return out.reshape(hidden_states.shape)
 
 
 def input_grad(grad_output, weight, scales, x_shape, x_dtype=torch.float16):

@@ -51,20 +51,24 @@ if _C is not None:
     w8_a16_moe_backward = _C.w8_a16_moe_backward
     w4_a16_moe = _C.w4_a16_moe                   # compiled boundary only, as w8_a16_moe
     w4_a16_moe_path = _C.w4_a16_moe_path
+    moe_router = _C.moe_router                   # compiled boundary only, as w8_a16_moe
+    w8_a16_moe_block = _C.w8_a16_moe_block
+    w4_a16_moe_block = _C.w4_a16_moe_block
 else:
     BOUNDARY = "ctypes"
     from .ops_ctypes import (decode_attention, greedy_handover, layernorm_forward, preprocess_weights, quant_weights,  # noqa: F401
                              rope_decode_attention, rotary_embedding_neox, rotary_embedding_neox_kvcache,
                              rotary_embedding_neox_kvcache_prefill, rotary_embedding_neox_strided, silu_mul,
                              unprocess_weights, w4_a16_moe, w4_a16_moe_path, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t,
-                             w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train)
+                             w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, moe_router,
+                             w8_a16_moe_block, w4_a16_moe_block)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
-           "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "decode_dropped_steps",
+           "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]
 
 
@@ -98,9 +102,9 @@ def release_stream_workspace(stream=None):
 
 
 def release_workspace():
-    """Free ALL library-owned scratch on every device (split-K regions, W4A16 expansion buffers, the quantiser's NULL-workspace
-    buffer); returns the bytes freed.  Not while a HIP graph that captured a split-K / W4A16 launch is still going to be
-    replayed.  eetq_release_workspace."""
+    """Free ALL library-owned scratch on every device (split-K regions, W4A16 expansion buffers, the MoE router's hand-over slots, the
+    quantiser's NULL-workspace buffer); returns the bytes freed.  Not while a HIP graph that captured a split-K / W4A16 / MoE router (T <= 16) launch is still going
+    to be replayed: the replay would write freed memory.  eetq_release_workspace."""
     import ctypes
 
     from . import _lib

@@ -26,7 +26,8 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
-           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path"]
+           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block",
+           "w4_a16_moe_block"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
             LAYOUT_GFX950: LAYOUT_GFX950, LAYOUT_SM80: LAYOUT_SM80, LAYOUT_ROW_MAJOR: LAYOUT_ROW_MAJOR}
@@ -417,6 +418,26 @@ def w4_a16_moe_path(T, k, E, H, I):
     """The shape rule of :func:`w4_a16_moe`: compiled module only."""
     raise RuntimeError("eetq_amd: w4_a16_moe_path needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
                        "the ctypes binding does not implement it")
+
+
+def moe_router(hidden, weight, top_k, norm_topk_prob=True, scores_dtype=None):
+    """The device router: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: moe_router needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
+
+
+def w8_a16_moe_block(hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gate_up_qweight, gate_up_scales, down_qweight,
+                     down_scales):
+    """The whole sparse MoE block on int8 experts: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w8_a16_moe_block needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
+
+
+def w4_a16_moe_block(hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gate_up_qweight, gate_up_scales, down_qweight,
+                     down_scales, path="auto"):
+    """The whole sparse MoE block on int4 experts: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w4_a16_moe_block needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
 
 
 def w8_a16_moe_train(hidden, top_k_index, top_k_weights, gate_up_qweight, gate_up_scales, down_qweight, down_scales):

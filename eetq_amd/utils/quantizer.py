@@ -11,7 +11,7 @@ import warnings
 import torch
 import torch.nn as nn
 
-from ..modules.qlinear import W4A16Experts, W8A16Experts, W8A16Linear
+from ..modules.qlinear import EetqSparseMoeBlock, EetqTopKRouter, W4A16Experts, W8A16Experts, W8A16Linear
 
 __all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable"]
 
@@ -62,6 +62,28 @@ def _experts_modules(model):
     return found
 
 
+def _swap_routers(model, quantised, exclude):
+    """``router=True``: every allow-listed router becomes an :class:`EetqTopKRouter`, then every allow-listed block around quantised
+    experts (``quantised``: their names) an :class:`EetqSparseMoeBlock`, both in place.  Returns one line per block of quantised
+    experts whose router stays on torch."""
+    for name, sub in list(model.named_modules()):
+        if any(tag in name for tag in exclude):
+            continue
+        if type(sub).__name__ in EetqTopKRouter.CLASS_NAMES and EetqTopKRouter.unsupported_reason(sub) is None:
+            EetqTopKRouter.from_router(sub)
+    left = []
+    for name in quantised:
+        parent = name.rpartition(".")[0]
+        block = model.get_submodule(parent) if parent else model
+        gate = getattr(block, "gate", None)
+        if not isinstance(gate, EetqTopKRouter):
+            why = EetqTopKRouter.unsupported_reason(gate) if isinstance(gate, nn.Module) else "no gate module"
+            left.append("%s (%s)" % (parent + ".gate" if parent else "gate", why))
+        elif EetqSparseMoeBlock.unsupported_reason(block) is None:
+            EetqSparseMoeBlock.from_block(block)
+    return left
+
+
 def set_trainable(model, flag=True):
     """Set the ``trainable`` flag of every :class:`W8A16Linear` and :class:`W8A16Experts` in ``model`` (itself included) and
     return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to the router weights)
@@ -77,7 +99,7 @@ def set_trainable(model, flag=True):
 
 
 def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False,
-                 trainable=False, expert_bits=8):
+                 trainable=False, expert_bits=8, router=False):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
@@ -92,6 +114,13 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     H and I multiples of 128, inference only -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
     but 8 or 4, ``expert_bits=4`` without ``experts=True`` (it would quantise no expert and say nothing) and ``expert_bits=4``
     together with ``trainable=True`` (there is no int4 backward) raise ValueError before the model is touched.
+    ``router=True`` (extension; needs ``experts=True``, else ValueError before the model is touched) also moves the router onto
+    the device kernel: every ``MixtralTopKRouter`` / ``Qwen2MoeTopKRouter`` / ``Qwen3MoeTopKRouter`` /
+    ``OlmoeTopKRouter`` becomes an :class:`EetqTopKRouter`, and every ``MixtralSparseMoeBlock`` / ``Qwen3MoeSparseMoeBlock`` /
+    ``OlmoeSparseMoeBlock`` whose experts were quantised an :class:`EetqSparseMoeBlock` (the whole block in four launches at
+    T <= 16).  Both are converted in place: parameters, state-dict keys and submodule names stay.  Other blocks (a shared expert,
+    sigmoid or group-limited routing, anything unknown) keep their block and get the router swap if their router is on the list;
+    a quantised block whose router is not is named in the same warning as the experts left in fp16.
     """
     if expert_bits not in (8, 4):
         raise ValueError("eet_quantize: expert_bits must be 8 or 4 (got %r)" % (expert_bits,))
@@ -99,10 +128,13 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
         raise ValueError("eet_quantize: expert_bits=4 needs experts=True (without it no experts module is quantised)")
     if expert_bits == 4 and trainable:
         raise ValueError("eet_quantize: expert_bits=4 cannot be trainable (W4A16Experts has no backward)")
+    if router and not experts:
+        raise ValueError("eet_quantize: router=True needs experts=True (the device router feeds the quantised experts)")
     experts_cls = W4A16Experts if expert_bits == 4 else W8A16Experts
     if experts:
         skipped = []
         found = _experts_modules(model)
+        quantised = []
         for name in list(found):
             mod = found.pop(name)  # the model and this loop hold the only references: the fp16 stacks go as each is replaced
             if any(tag in name for tag in exclude):
@@ -112,11 +144,18 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
                 skipped.append("%s (%s)" % (name, why))
                 continue
             set_op_by_name(model, name, experts_cls.from_experts(mod, init_only=init_only))
+            quantised.append(name)
             del mod
             if not init_only and torch.cuda.is_available():
                 torch.cuda.empty_cache()
-        if skipped:
-            warnings.warn("eet_quantize: %d experts module(s) left in fp16: %s" % (len(skipped), "; ".join(skipped)))
+        no_router = _swap_routers(model, quantised, exclude) if router else []
+        if skipped or no_router:
+            parts = []
+            if skipped:
+                parts.append("%d experts module(s) left in fp16: %s" % (len(skipped), "; ".join(skipped)))
+            if no_router:
+                parts.append("%d router(s) left on torch: %s" % (len(no_router), "; ".join(no_router)))
+            warnings.warn("eet_quantize: " + ". ".join(parts))
     targets = find_layers(model, include=include, exclude=exclude)
     desc = "[EET][INFO] quantization preprocessing..." + ("(init only)" if init_only else "")
     for name in _progress(list(targets), desc):

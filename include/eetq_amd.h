@@ -328,6 +328,33 @@ int eetq_expand_i4_to_i8(const int8_t* src, int8_t* dst, size_t bytes_src, void*
  *   to prepare something for the tiled kernel first -- the int4 layer's expansion -- decide before it does. */
 int eetq_w8a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather);
 
+/* ---- mixture-of-experts router (extension, additive within ABI revision 7) -----------------------------------
+ * The reference has no MoE path.  These entries replace the forward of transformers' *TopKRouter modules (MixtralTopKRouter,
+ * Qwen2MoeTopKRouter, Qwen3MoeTopKRouter, OlmoeTopKRouter: F.linear -> softmax(float) -> topk -> sum -> div (-> .to)), five or six
+ * torch launches, and the eetq_moe_route launch behind them.  Numerics (what those modules compute on an fp16 model):
+ *   logit[t][e] = fp16( sum_h fp32(x[t][h]) * fp32(w[e][h]) ): fp32 accumulation in a fixed order, one rounding;
+ *   selection: the k largest fp16 logits of the row, ties to the lower expert id, in descending order;
+ *   scores: p = softmax over all E fp16 logits in fp32, max-subtracted; renorm = 1 divides the k selected p by their sum (added
+ *     in selection order); written as w_dtype EETQ_DTYPE_F32, or EETQ_DTYPE_F16 = the rounding of the fp32 result.
+ *
+ * eetq_moe_router_f16: x fp16 [T][H], w fp16 [E][H] (both 16-byte aligned) -> logits_out fp16 [T][E], top_k_index int64 [T][k],
+ *   top_k_weights [T][k] of w_dtype and, unless the five table pointers are all NULL (they are all NULL or all set), the tables
+ *   eetq_moe_route builds from top_k_index, bit for bit.  T <= 16: ONE launch -- ceil(E / (4 / wpe)) workgroups (wpe = 4, 2, 1 waves
+ *   per expert row for H >= 2048, >= 1024, below) stream the weight and hand their sums to the workgroup that finishes last,
+ *   through library-owned scratch (one slot per launch stream and device, created by the first call -- not during a graph capture:
+ *   EETQ_ERR_UNSUPPORTED then -- and freed by eetq_release_workspace); deterministic, capturable, no host sync.  T > 16: the logits
+ *   kernel per 16 tokens, eetq_moe_topk_f16 and (with tables) eetq_moe_route: three launches, for callers without a GEMM of their own.
+ *   1 <= E <= 256, 1 <= k <= min(E, 16), H % 64 == 0, 1 <= T <= 16 * 65535, T*k <= 2^30; E > 256 or k > 16: EETQ_ERR_UNSUPPORTED; anything else
+ *   out of range, a null pointer, tables half set, renorm not 0 / 1 or a w_dtype other than the two: EETQ_ERR_INVALID.  Every check
+ *   runs before any device work.
+ * eetq_moe_topk_f16: the selection and the scores alone, from logits fp16 [T][E]: one wave per token, ceil(T / 4) workgroups, the
+ *   device code of the fused launch (the same bits from the same logits).  Limits and errors as above. */
+int eetq_moe_router_f16(const void* x, const void* w, int T, int H, int E, int k, int renorm, int w_dtype, void* logits_out,
+                        int64_t* top_k_index, void* top_k_weights, int* counts, int* offsets, int* sorted_slot, int* position,
+                        int* active, void* stream);
+int eetq_moe_topk_f16(const void* logits, int T, int E, int k, int renorm, int w_dtype, int64_t* top_k_index, void* top_k_weights,
+                      void* stream);
+
 /* ---- mixture-of-experts backward (extension, additive within ABI revision 7) --------------------------------
  * The input and router-weight gradients of the layer above with its int8 weights frozen (no weight gradients), on the tables
  * eetq_moe_route wrote and the sorted rows the forward kept.  Grids fixed by the shapes, no host sync, no atomics: deterministic

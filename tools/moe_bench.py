@@ -37,6 +37,16 @@ child process per plan (EETQ_AMD_TUNING=1 EETQ_AMD_MOE_I4_PLAN=<waves>x<depth>, 
     python tools/moe_bench.py --plan-sweep --out profiles/r10_moe_int4_plans.jsonl
 (profiles/r10_moe_int4_plans.jsonl also holds 8x1, 4x2, 6x1 and 3x2: instantiations that lost or tied in that sweep and were
 deleted after it; the sweep now covers the ones that are left.)
+
+--block times the whole sparse block at --tokens (default 1,4,16,64,512), int8 or int4 experts (--bits): (a) the
+sequence before the device router -- the transformers router formula in torch (F.linear, softmax(float), topk, sum, div, .to) followed
+by w8_a16_moe / w4_a16_moe -- against (b) ops.w8_a16_moe_block / w4_a16_moe_block; the router formula alone against ops.moe_router;
+and, at T <= 16, the fused router launch with tables (eetq_moe_router_f16) next to eetq_moe_route alone.  Both sides eager and both
+captured as a HIP graph (one replay per timing); median of --iters with min and max.
+
+    python tools/moe_bench.py --block --out <file>.jsonl
+    python tools/moe_bench.py --block --bits 4 --out <file>.jsonl
+(no output of this mode is committed under profiles/ yet: DESIGN.md 4.13)
 """
 import argparse
 import json
@@ -300,6 +310,85 @@ def seam_i4(args, out):
 PLANS = ("8x2", "4x1", "2x1")
 
 
+def _graphed(fn):
+    """fn captured once (after a warm-up call) -> a callable that replays the graph"""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        keep = fn()
+    g.keep = keep
+    return g.replay
+
+
+def block(args, out):
+    """the whole sparse block: torch router + layer op (the sequence before DESIGN.md 4.13) against the block op"""
+    import ctypes
+
+    import torch.nn.functional as F
+
+    from eetq_amd import _lib, ops
+    lib = _lib.lib()
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        pack = 2 if args.bits == 4 else 1
+        gu_w = torch.randint(-127, 128, (E, H, 2 * I // pack), dtype=torch.int8, device=DEV)
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-3).half()
+        dn_w = torch.randint(-127, 128, (E, I, H // pack), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-3).half()
+        stacks = (gu_w, gu_s, dn_w, dn_s)
+        layer = ops.w4_a16_moe if args.bits == 4 else ops.w8_a16_moe
+        block_op = ops.w4_a16_moe_block if args.bits == 4 else ops.w8_a16_moe_block
+        mixtral = name.startswith("mixtral")   # fp32 scores, always renormalised; the others: fp16 scores
+        sdt = torch.float32 if mixtral else torch.float16
+        wr = (torch.randn(E, H, device=DEV) / H ** 0.5).half()
+
+        def torch_router(x):
+            logits = F.linear(x, wr)
+            top, idx = torch.topk(F.softmax(logits, dtype=torch.float, dim=-1), k, dim=-1)
+            top /= top.sum(dim=-1, keepdim=True)
+            return logits, top.to(sdt), idx
+
+        for T in (int(t) for t in args.tokens.split(",")):
+            x = torch.randn(T, H, device=DEV).half()
+
+            def before():
+                _, sc, idx = torch_router(x)
+                return layer(x, idx, sc, *stacks)
+
+            def after():
+                return block_op(x, wr, k, True, sdt, *stacks)
+
+            cases = {"before": before, "after": after, "router_torch": lambda: torch_router(x),
+                     "router_op": lambda: ops.moe_router(x, wr, k, True, sdt)}
+            if T <= 16:
+                S, A = T * k, min(E, T * k)
+                lg = torch.empty(T, E, dtype=torch.float16, device=DEV)
+                ix = torch.zeros(T, k, dtype=torch.int64, device=DEV)
+                sc = torch.empty(T, k, dtype=sdt, device=DEV)
+                tb = [torch.empty(n, dtype=torch.int32, device=DEV) for n in (E, E + 1, S, S, A)]
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                dt = 1 if sdt == torch.float32 else 0
+                cases["router_launch_with_tables"] = lambda: lib.eetq_moe_router_f16(
+                    _ptr(x), _ptr(wr), T, H, E, k, 1, dt, _ptr(lg), _ptr(ix), _ptr(sc), *[_ptr(t) for t in tb], st)
+                cases["route_launch"] = lambda: lib.eetq_moe_route(_ptr(ix), T, k, E, *[_ptr(t) for t in tb], st)
+            with torch.no_grad():
+                assert torch.equal(after(), layer(x, *ops.moe_router(x, wr, k, True, sdt)[2:0:-1], *stacks))
+                rec = {"shape": name, "bits": args.bits, "T": T, "H": H, "I": I, "E": E, "k": k, "iters": args.iters}
+                for tag, fn in cases.items():
+                    for mode, f in (("eager", fn), ("graph", _graphed(fn) if "launch" not in tag else None)):
+                        if f is None:
+                            continue
+                        med, lo, hi = _time_stats(f, args.warmup, args.iters)
+                        rec["us_%s_%s" % (tag, mode)] = [round(med, 2), round(lo, 2), round(hi, 2)]
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+
+
 def plan_child(args):
     """one process = one forced plan (or none): us of eetq_w4a16_moe_gemm per projection at T = 1, 4, 16, uniform routing"""
     import ctypes
@@ -384,7 +473,15 @@ def main():
     ap.add_argument("--bits", type=int, choices=(8, 4), default=8, help="the layer table / --seam on int8 or int4 expert stacks")
     ap.add_argument("--plan-sweep", action="store_true", help="sweep eetq_w4a16_moe_gemm's instantiations (DESIGN.md 4.12)")
     ap.add_argument("--plan-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--block", action="store_true", help="time the whole sparse block with and without the device router (DESIGN.md 4.13)")
     args = ap.parse_args()
+    if args.block:
+        args.tokens = args.tokens or "1,4,16,64,512"
+        out = open(args.out, "w") if args.out else None
+        block(args, out)
+        if out:
+            out.close()
+        return
     if args.plan_child:
         plan_child(args)
         return
