@@ -860,21 +860,26 @@ std::vector<Tensor> w8_a16_gemv_grouped(const std::vector<Tensor>& inputs, const
     return outs;
 }
 
-// Routed W8A16 mixture-of-experts layer (extension): the forward of transformers' experts modules,
-// out[t] = sum_j w[t][j] * down_e( silu(gate_e(x_t)) * up_e(x_t) ), e = top_k_index[t][j], on expert stacks gate_up_weight
-// int8 [E, H, 2I] (gfx950 layout per expert, glu8 column order), gate_up_scale fp16 [E, 2I], down_weight int8 [E, I, H],
-// down_scale fp16 [E, H].  Any T: route -> grouped GEMM (gather, silu_glu8) -> grouped GEMM (sorted rows) -> combine, four
-// launches, no host sync (capturable); the grouped GEMMs are the decode kernel or the tiled prompt kernel (moe_grouped_gemm below).
-// Ids outside [0, E) contribute nothing.
-// the argument checks the layer's three entries share (`fn` names the caller in the messages): the expert stacks ...
+// ---- routed mixture-of-experts layers (extensions) ---------------------------------------------------------
+// One layer behind every forward below: out[t] = sum_j w[t][j] * down_e( silu(gate_e(x_t)) * up_e(x_t) ), e = top_k_index[t][j], on
+// expert stacks gate_up_weight int8 [E, H, 2I] (gfx950 layout per expert, glu8 column order), gate_up_scale fp16 [E, 2I], down_weight
+// int8 [E, I, H], down_scale fp16 [E, H].  Ids outside [0, E) contribute nothing.  An entry point is its checks, the source of its
+// routing tables (eetq_moe_route on the caller's ids, or the device router) and moe_experts under the plan moe_plan made from the
+// shapes; w8_a16_moe_backward is a computation of its own on the same checks.
+// The argument checks, each condition stated once (`fn` names the op in the messages, `what` its [T, H] argument) ...
+void moe_rows_check(const char* fn, const char* what, const Tensor& x)
+{
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kHalf && x.dim() == 2, fn, ": ", what, " must be a float16 GPU tensor [T, H]");
+}
+
 struct MoeShape {
     int64_t E, H, N1, I;
 };
 
-// bits = 4: packed int4 stacks, two values per byte along N -- gate_up [E, H, I], down [E, I, H / 2] -- and 128-deep
-// tiles; the checks, their order and (for bits = 8) their messages are the same
-MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, c10::Device dev,
-                    int bits = 8)
+// ... the expert stacks, on x's device and of x's H.  bits = 4: packed int4 stacks, two values per byte along N --
+// gate_up [E, H, I], down [E, I, H / 2] -- and 128-deep tiles; the checks, their order and (for bits = 8) their messages are the same
+MoeShape moe_stacks(const char* fn, const char* what, const Tensor& x, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w,
+                    const Tensor& dn_s, int bits = 8)
 {
     const bool i4 = bits == 4;
     TORCH_CHECK(gu_w.dim() == 3 && dn_w.dim() == 3 && gu_w.scalar_type() == at::kChar && dn_w.scalar_type() == at::kChar &&
@@ -895,25 +900,106 @@ MoeShape moe_stacks(const char* fn, const Tensor& gu_w, const Tensor& gu_s, cons
     TORCH_CHECK(gu_w.is_contiguous() && gu_s.is_contiguous() && dn_w.is_contiguous() && dn_s.is_contiguous(),
                 fn, ": expert weights and scales must be contiguous");
     for (const Tensor* t : {&gu_w, &gu_s, &dn_w, &dn_s})
-        TORCH_CHECK(t->device() == dev, fn, ": all tensors must be on the hidden states' device");
+        TORCH_CHECK(t->device() == x.device(), fn, ": all tensors must be on the hidden states' device");
+    TORCH_CHECK(x.size(1) == H, fn, ": ", what, " is [T, ", x.size(1), "] but the experts have H = ", H);
     return {E, H, N1, I};
 }
 
-// ... and, for the forwards, the hidden states and the routing
-MoeShape moe_check(const char* fn, const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights,
-                   const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, int bits = 8)
+// ... and the caller's routing
+void moe_routing_check(const char* fn, const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights)
 {
-    TORCH_CHECK(hidden_in.is_cuda() && hidden_in.scalar_type() == at::kHalf && hidden_in.dim() == 2,
-                fn, ": hidden must be a float16 GPU tensor [T, H]");
-    const auto     dev = hidden_in.device();
-    const MoeShape m   = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, dev, bits);
-    TORCH_CHECK(hidden_in.size(1) == m.H, fn, ": hidden is [T, ", hidden_in.size(1), "] but gate_up_weight has H = ", m.H);
-    TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden_in.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
+    TORCH_CHECK(top_k_index.dim() == 2 && top_k_index.size(0) == hidden.size(0) && top_k_weights.sizes() == top_k_index.sizes(),
                 fn, ": top_k_index and top_k_weights must both be [T, k]");
     TORCH_CHECK(top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf,
                 fn, ": top_k_weights must be float32 or float16");
-    TORCH_CHECK(top_k_index.device() == dev && top_k_weights.device() == dev, fn, ": all tensors must be on the hidden states' device");
-    return m;
+    TORCH_CHECK(top_k_index.device() == hidden.device() && top_k_weights.device() == hidden.device(),
+                fn, ": all tensors must be on the hidden states' device");
+}
+
+// EETQ_AMD_MOE_HOST=1 behind EETQ_AMD_TUNING=1 (an A/B hook like every other: the library reads it through tuning_env, once per
+// process): T > 16 takes the former host path -- the expert counts read back once, every active expert's rows through the AUTO
+// W8A16 GEMMs.  For A/B timing only: it synchronises the stream and cannot be captured.
+bool moe_host_path()
+{
+    static const bool on = eetq_diag_moe_host_path() == 1;
+    return on;
+}
+
+// Where eetq_w8a16_moe_gemm_tiled takes BOTH projections (its own limits, asked of the library: K >= 320, N K < 2^31 per expert, the
+// activation block below 2 GiB): nothing is allocated or expanded for a shape that would then run the decode kernel.
+bool moe_i4_tiled_takes(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    if (T < 1 || T * k > (int64_t(1) << 30)) return false;
+    return eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)(2 * I), (int)H, 1) == 1 &&
+           eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)H, (int)I, 0) == 1;
+}
+
+// What serves one call of the layer: the stacks' format, and for BOTH projections the kernel.
+struct MoePlan {
+    int  bits;    // 8 or 4
+    bool tiled;   // eetq_w8a16_moe_gemm_tiled (128-row LDS tiles, the weight read once per 128 rows); else the decode kernel of `bits`
+                  // (16-row MFMA tiles, the expert's weight tile row streamed once per 16 rows)
+    bool expand;  // bits = 4 and tiled: eetq_expand_i4_to_i8 of the whole stack in front of each projection
+    bool host;    // the A/B host path instead of the grouped kernels
+};
+
+// The plan is decided from the SHAPES alone -- the counts live on the device -- so every call with the same (T, k, E, H, I) runs
+// the same kernels whatever the routing (a skewed routing costs time, never correctness), and the trainable and the inference
+// forward always agree on it.  T <= 16 always takes the decode kernel.
+//
+// bits = 8: tiled from kMoeTiledMinMeanRows mean rows per expert S / E (a shape outside the tile body's limits still takes the decode
+// kernel: moe_project).  The seam is measured (tools/moe_bench.py --seam, profiles/r09_moe_seam.jsonl), one MI355X,
+// us per gate|up + down pair of launches, decode kernel / tiled kernel, uniform routing (skewed routing moves no entry across 1.0):
+//   mean rows S / E      1        2        4        8        16       32       64
+//   qwen3-30b-a3b        87/203   116/211  140/226  161/231  226/229  385/262  662/303
+//   mixtral-8x7b         -        -        256/343  301/344  469/406  886/434  1552/519     (4: T = 17, 4.25 rows)
+// Below 16 rows per expert the decode kernel wins at both shapes (one 16-row pass streams the weights once; the tiled kernel pays
+// 128-row MFMA work and its ring's ramp per tile), at 16 the two meet (Qwen 0.99, Mixtral 1.16 in the tiled kernel's favour),
+// above it the decode kernel re-streams the weights once per 16 rows and loses by S / E / 16.
+constexpr int64_t kMoeTiledMinMeanRows = 16;
+
+// bits = 4: "decode" is eetq_w4a16_moe_gemm on the int4 tiles, "expand" the expansion of each stack into a torch::empty [E, K, N] int8
+// buffer and the tiled kernel on it with the unchanged scales.  The expansion moves 1.5 E K N bytes per projection whatever T is
+// (E K N / 2 read, E K N written) and the tiled kernel then reads E_active K N, against ceil(rows / 16) E_active K N / 2 for the
+// decode kernel: by bytes alone the two meet near 5 x 16 rows per expert, far above the int8 layer's seam of 16.
+// Measured (tools/moe_bench.py --seam --bits 4, profiles/r10_moe_int4_seam.jsonl, DESIGN.md 4.12), one MI355X, us per gate|up + down
+// pair, decode kernel / expansions + tiled kernel (of which the two expansions alone: 355 us Mixtral, 157 us Qwen3, whatever T),
+// uniform routing (skewed routing moves no entry across 1.0):
+//   mean rows S / E      16        32        64         128         256
+//   qwen3-30b-a3b        177/369   328/400   583/443    1124/582    2220/787
+//   mixtral-8x7b         400/752   708/771   1353/859   2650/1060   5231/1404
+// At 32 rows per expert the decode kernel still wins at both shapes (0.82, 0.92), at 64 the expanded path does (1.31, 1.58): the
+// seam sits 2-4 x higher than the int8 layer's 16, where the bytes put it.  In rows per expert it is the same at both shapes:
+// both sides of the comparison scale with E K N, so E K N drops out of the rule.  (The lines cross near 40 rows by interpolation;
+// nothing between 32 and 64 was measured, so the rule starts at the first measured point where the expansion wins.)
+constexpr int64_t kMoeI4ExpandMinMeanRows = 64;
+
+// `path` is the int4 ops' argument ("auto" everywhere else): "decode" and "expand" force one side of the int4 rule, "expand" only
+// where the tiled kernel takes both projections.  `caller_routed`: the routing is the caller's (w8_a16_moe, w8_a16_moe_train), which
+// is where the A/B host switch applies -- never to the block ops, whose tables come from the device router, and never to int4.
+MoePlan moe_plan(const char* fn, int bits, const std::string& path, int64_t T, int64_t k, int64_t E, int64_t H, int64_t I,
+                 bool caller_routed)
+{
+    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", fn, ": path must be 'auto', 'decode' or 'expand'");
+    MoePlan p{bits, false, false, false};
+    if (T == 0) return p;  // nothing runs
+    if (bits == 8) {
+        p.host  = caller_routed && T > 16 && moe_host_path();
+        p.tiled = !p.host && T > 16 && T * k >= kMoeTiledMinMeanRows * E;
+        return p;
+    }
+    TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
+                fn, ": path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
+    p.expand = path == "expand" ||
+               (path == "auto" && T > 16 && T * k >= kMoeI4ExpandMinMeanRows * E && moe_i4_tiled_takes(T, k, E, H, I));
+    p.tiled = p.expand;
+    return p;
+}
+
+std::string w4_a16_moe_path(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    TORCH_CHECK(T >= 0 && k >= 1 && E >= 1 && k <= E && H >= 1 && I >= 1, "w4_a16_moe_path: T >= 0, 1 <= k <= E, H >= 1, I >= 1");
+    return moe_plan("w4_a16_moe_path", 4, "auto", T, k, E, H, I, true).expand ? "expand" : "decode";
 }
 
 // eetq_moe_route's tables in one int32 buffer: counts [E] | offsets [E + 1] | sorted_slot [S] | position [S] | active [A], S = T k
@@ -931,21 +1017,26 @@ struct MoeTables {
     }
 };
 
-// What the three forwards start with (T >= 1): the device guard, the contiguous hidden states, ids as int64 and router weights, the
-// current stream, and eetq_moe_route into `tables`.  Everything the layer's launches read lives as long as this.
-struct MoeRouted {
+// What a forward sets up before its first launch (T >= 1): the device guard, the contiguous hidden states, the tables and the view
+// of them, the current stream.  It launches nothing.
+struct MoeSetup {
     c10::DeviceGuard guard;
-    Tensor           hidden, idx, wts, tables;
+    Tensor           hidden, tables;
     MoeTables        t;
     void*            st;
-    MoeRouted(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, int64_t E, const Tensor& tables_in)
-        : guard(hidden_in.device()), hidden(hidden_in.contiguous()), idx(top_k_index.to(at::kLong).contiguous()),
-          wts(top_k_weights.contiguous()), tables(tables_in), t(tables.data_ptr<int>(), E, idx.numel()), st(stream_of(hidden_in))
+    MoeSetup(const Tensor& hidden_in, const Tensor& tables_in, int64_t E, int64_t S)
+        : guard(hidden_in.device()), hidden(hidden_in.contiguous()), tables(tables_in), t(tables.data_ptr<int>(), E, S),
+          st(stream_of(hidden_in))
     {
-        check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)idx.size(0), (int)idx.size(1), (int)E, t.counts, t.offsets, t.sorted,
-                             t.position, t.active, st));
     }
 };
+
+// the tables of ids idx [T, k] (int64, contiguous)
+void moe_route(const Tensor& idx, int64_t E, const MoeTables& t, void* st)
+{
+    check(eetq_moe_route(idx.data_ptr<int64_t>(), (int)idx.size(0), (int)idx.size(1), (int)E, t.counts, t.offsets, t.sorted, t.position,
+                         t.active, st));
+}
 
 // out [T, H] = the router-weighted sum of each token's k rows of y [T k, H] (wts [T, k], float32 or float16)
 void moe_combine(const Tensor& y, const int* position, const Tensor& wts, Tensor& out, void* st)
@@ -954,133 +1045,141 @@ void moe_combine(const Tensor& y, const int* position, const Tensor& wts, Tensor
                                out.data_ptr(), (int)out.size(0), (int)wts.size(1), (int)out.size(1), st));
 }
 
-// One grouped projection of the layer.  Which of the two grouped kernels serves it is decided from the SHAPES alone -- the counts live
-// on the device -- so every call with the same (T, k, E, N, K) runs the same kernel whatever the routing (a skewed routing costs
-// time, never correctness), and the trainable and the inference forward always agree on it:
-//   * T <= 16, or mean rows per expert S / E < kMoeTiledMinMeanRows: eetq_w8a16_moe_gemm (16-row MFMA tiles, the expert's weight
-//     tile row streamed once per 16 rows);
-//   * above: eetq_w8a16_moe_gemm_tiled (128-row LDS tiles, the weight read once per 128 rows); a shape outside the tile body's
-//     limits (EETQ_ERR_UNSUPPORTED, quiet) takes the decode kernel, which is correct at any row count.
-// The seam is measured (tools/moe_bench.py --seam, profiles/r09_moe_seam.jsonl), one MI355X, us per
-// gate|up + down pair of launches, decode kernel / tiled kernel, uniform routing (skewed routing moves no entry across 1.0):
-//   mean rows S / E      1        2        4        8        16       32       64
-//   qwen3-30b-a3b        87/203   116/211  140/226  161/231  226/229  385/262  662/303
-//   mixtral-8x7b         -        -        256/343  301/344  469/406  886/434  1552/519     (4: T = 17, 4.25 rows)
-// Below 16 rows per expert the decode kernel wins at both shapes (one 16-row pass streams the weights once; the tiled kernel pays
-// 128-row MFMA work and its ring's ramp per tile), at 16 the two meet (Qwen 0.99, Mixtral 1.16 in the tiled kernel's favour),
-// above it the decode kernel re-streams the weights once per 16 rows and loses by S / E / 16.
-constexpr int64_t kMoeTiledMinMeanRows = 16;
-
-void moe_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k, int64_t E,
-                      int64_t N, int64_t K, int gather, int glu8, void* st)
+// One grouped projection of the layer, y = rows(x) . w [E, K, N] per expert, on the plan's kernel.  An int8 shape outside the tiled
+// body's limits (EETQ_ERR_UNSUPPORTED, quiet) takes the decode kernel, which is correct at any row count.  The int4 expansion lives
+// for this projection only: at most one expanded stack is alive.
+void moe_project(const MoePlan& p, const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k,
+                 int64_t E, int64_t N, int64_t K, int gather, int glu8, void* st)
 {
-    if (T > 16 && T * k >= kMoeTiledMinMeanRows * E) {
-        const int rc = eetq_w8a16_moe_gemm_tiled(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k,
-                                                 (int)E, (int)N, (int)K, gather, glu8, st);
-        if (rc != EETQ_ERR_UNSUPPORTED) {
+    if (p.tiled) {
+        Tensor w8;
+        if (p.expand) {
+            w8 = torch::empty({E, K, N}, w.options());
+            check(eetq_expand_i4_to_i8(w.data_ptr<int8_t>(), w8.data_ptr<int8_t>(), (size_t)w.numel(), st));
+        }
+        const int rc = eetq_w8a16_moe_gemm_tiled(x, (p.expand ? w8 : w).data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y,
+                                                 (int)T, (int)k, (int)E, (int)N, (int)K, gather, glu8, st);
+        if (p.expand || rc != EETQ_ERR_UNSUPPORTED) {
             check(rc);
             return;
         }
     }
-    check(eetq_w8a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E, (int)N,
-                              (int)K, gather, glu8, st));
-}
-
-// EETQ_AMD_MOE_HOST=1 behind EETQ_AMD_TUNING=1 (an A/B hook like every other: the library reads it through tuning_env, once per
-// process): T > 16 takes the former host path -- the expert counts read back once, every active expert's rows through the AUTO
-// W8A16 GEMMs.  For A/B timing only: it synchronises the stream and cannot be captured.
-bool moe_host_path()
-{
-    static const bool on = eetq_diag_moe_host_path() == 1;
-    return on;
+    check((p.bits == 4 ? eetq_w4a16_moe_gemm : eetq_w8a16_moe_gemm)(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active,
+                                                                    y, (int)T, (int)k, (int)E, (int)N, (int)K, gather, glu8, st));
 }
 
 // The host path: the expert counts read back once, then every active expert's rows [off, off + c) of the sorted order through the
 // dense W8A16 GEMMs into `down`.  Inference (gate_up null): per expert, gate|up with the fused silu_glu8 write-out on the AUTO path,
 // then down.  Trainable forward: every expert's gate|up plain into gate_up on the kernel the gated write-out uses (EETQ_PATH_STREAM
 // for 2 to 16 rows, AUTO otherwise), one silu_mul over all rows, then every expert's down.
-void moe_host_experts(const MoeRouted& r, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, Tensor& down,
-                      Tensor* gate_up)
+void moe_host_experts(const MoeSetup& c, int64_t k, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s,
+                      Tensor& down, Tensor* gate_up)
 {
-    const int64_t E = gu_w.size(0), k = r.idx.size(1);
-    const Tensor  counts_h = r.tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
-    const Tensor  sorted_t = r.tables.narrow(0, r.t.sorted - r.t.counts, r.idx.numel());
+    const int64_t E = gu_w.size(0);
+    const Tensor  counts_h = c.tables.narrow(0, 0, E).cpu();  // the one host sync of the A/B host path
+    const Tensor  sorted_t = c.tables.narrow(0, c.t.sorted - c.t.counts, c.hidden.size(0) * k);
     std::vector<std::tuple<int64_t, int64_t, int64_t>> experts;  // e, off, c
     int64_t                                            n = 0;
     for (int64_t e = 0; e < E; ++e)
-        if (const int64_t c = counts_h.data_ptr<int>()[e]) {
-            experts.emplace_back(e, n, c);
-            n += c;
+        if (const int64_t cnt = counts_h.data_ptr<int>()[e]) {
+            experts.emplace_back(e, n, cnt);
+            n += cnt;
         }
-    auto gathered = [&](int64_t off, int64_t c) { return r.hidden.index_select(0, sorted_t.narrow(0, off, c).div(k, "floor")); };
-    auto project  = [](const Tensor& in, const Tensor& w, const Tensor& s, Tensor& y, int64_t off, int64_t c, int path) {
-        Tensor rows = y.narrow(0, off, c);
-        gemm_launch(in, w, s, rows, c, s.numel(), in.size(1), path, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
+    auto gathered = [&](int64_t off, int64_t cnt) { return c.hidden.index_select(0, sorted_t.narrow(0, off, cnt).div(k, "floor")); };
+    auto project  = [](const Tensor& in, const Tensor& w, const Tensor& s, Tensor& y, int64_t off, int64_t cnt, int path) {
+        Tensor rows = y.narrow(0, off, cnt);
+        gemm_launch(in, w, s, rows, cnt, s.numel(), in.size(1), path, std::nullopt, std::nullopt, EETQ_ACT_IDENTITY);
     };
-    for (const auto& [e, off, c] : experts) {
+    for (const auto& [e, off, cnt] : experts) {
         if (gate_up) {
-            project(gathered(off, c), gu_w[e], gu_s[e], *gate_up, off, c, c >= 2 && c <= 16 ? EETQ_PATH_STREAM : EETQ_PATH_AUTO);
+            project(gathered(off, cnt), gu_w[e], gu_s[e], *gate_up, off, cnt, cnt >= 2 && cnt <= 16 ? EETQ_PATH_STREAM : EETQ_PATH_AUTO);
             continue;
         }
-        const Tensor gate = w8_a16_gemm(gathered(off, c), gu_w[e], gu_s[e], "auto", std::nullopt, std::nullopt, std::nullopt, false,
+        const Tensor gate = w8_a16_gemm(gathered(off, cnt), gu_w[e], gu_s[e], "auto", std::nullopt, std::nullopt, std::nullopt, false,
                                         std::string("silu_glu8"));
-        project(gate, dn_w[e], dn_s[e], down, off, c, EETQ_PATH_AUTO);
+        project(gate, dn_w[e], dn_s[e], down, off, cnt, EETQ_PATH_AUTO);
     }
     if (!gate_up || !n) return;
     const Tensor inter = silu_mul(gate_up->narrow(0, 0, n), true);
-    for (const auto& [e, off, c] : experts) project(inter.narrow(0, off, c), dn_w[e], dn_s[e], down, off, c, EETQ_PATH_AUTO);
+    for (const auto& [e, off, cnt] : experts) project(inter.narrow(0, off, cnt), dn_w[e], dn_s[e], down, off, cnt, EETQ_PATH_AUTO);
 }
 
-Tensor w8_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
-                  const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+// The experts on routed rows (the tables of c are filled, or their launch is queued on c.st): grouped GEMM (gather) -> grouped GEMM
+// (sorted rows) -> combine with wts [T, k] into out [T, H]; no host sync, capturable.  Inference (gate_up null): the first GEMM writes
+// silu(gate) * up itself (glu8 = 1), three launches.  Trainable forward: it writes the plain gate|up projection into gate_up [T k, 2I]
+// and eetq_silu_mul_glu8_f16 follows, four launches -- the glu8 write-out of either grouped kernel is the plain projection followed
+// by that launch bit for bit.  y [T k, H], when given, receives each sorted row's down projection.
+void moe_experts(const MoePlan& p, const MoeSetup& c, const Tensor& wts, const MoeShape& m, const Tensor& gu_w, const Tensor& gu_s,
+                 const Tensor& dn_w, const Tensor& dn_s, Tensor& out, Tensor* gate_up = nullptr, Tensor* y = nullptr)
 {
-    const auto [E, H, N1, I] = moe_check("w8_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
-    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
-    Tensor        out = torch::empty({T, H}, hidden_in.options());
-    if (T == 0) return out;
-    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, MoeTables::alloc(E, S, hidden_in.device()));
-    Tensor          down = torch::empty({S, H}, r.hidden.options());
-    if (T <= 16 || !moe_host_path()) {
-        Tensor inter = torch::empty({S, I}, r.hidden.options());
-        moe_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, inter.data_ptr(), T, k, E, N1, H, 1, 1, r.st);
-        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, r.st);
+    const int64_t T = c.hidden.size(0), k = wts.size(1), S = T * k;
+    Tensor        down = y ? *y : torch::empty({S, m.H}, c.hidden.options());
+    if (p.host) {
+        moe_host_experts(c, k, gu_w, gu_s, dn_w, dn_s, down, gate_up);
     } else {
-        moe_host_experts(r, gu_w, gu_s, dn_w, dn_s, down, nullptr);
+        Tensor inter = torch::empty({S, m.I}, c.hidden.options());
+        moe_project(p, c.hidden.data_ptr(), gu_w, gu_s, c.t, gate_up ? gate_up->data_ptr() : inter.data_ptr(), T, k, m.E, m.N1, m.H, 1,
+                    gate_up ? 0 : 1, c.st);
+        if (gate_up) check(eetq_silu_mul_glu8_f16(gate_up->data_ptr(), inter.data_ptr(), (int)S, (int)m.I, c.st));
+        moe_project(p, inter.data_ptr(), dn_w, dn_s, c.t, down.data_ptr(), T, k, m.E, m.H, m.I, 0, 0, c.st);
     }
-    moe_combine(down, r.t.position, r.wts, out, r.st);
-    return out;
+    moe_combine(down, c.t.position, wts, out, c.st);
 }
 
-// Trainable forward of the layer (extension): the same `out` as w8_a16_moe bit for bit, plus what the backward
-// reads -- the routing tables (int32, eetq_moe_route's counts | offsets | sorted_slot | position | active), gate_up [T*k, 2I] (the
-// gate|up projection of every sorted row, glu8 column order, before the activation) and y [T*k, H] (each sorted row's down
-// projection, before the router weighting).  Rows past offsets[E] of both are unspecified.  Any T: route -> grouped GEMM
-// (gather, plain) -> eetq_silu_mul_glu8_f16 -> grouped GEMM -> combine, five launches, no host sync (capturable); the glu8 write-out
-// of either grouped kernel is the plain projection followed by that launch bit for bit, and moe_grouped_gemm picks the same kernel
-// for both forwards.  (Under the A/B host switch: w8_a16_moe's host path with each expert's gate|up run plain on the kernel its
-// gated write-out uses, then one silu_mul over all rows.)
-std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden_in, const Tensor& top_k_index,
-                                                            const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
-                                                            const Tensor& dn_w, const Tensor& dn_s)
+// The three layer ops: the caller's routing, eetq_moe_route in front of the experts (four launches at inference, five for the
+// trainable forward, any T).  `keep`: the trainable forward's outputs next to `out` -- the routing tables (int32, counts | offsets |
+// sorted_slot | position | active), gate_up [T*k, 2I] (the gate|up projection of every sorted row, glu8 column order, before the
+// activation) and y [T*k, H] (each sorted row's down projection, before the router weighting); rows past offsets[E] of both are
+// unspecified.
+using MoeLayerOut = std::tuple<Tensor, Tensor, Tensor, Tensor>;  // out, tables, gate_up, y
+
+MoeLayerOut moe_layer(const char* fn, int bits, const std::string& path, bool keep, const Tensor& hidden_in, const Tensor& top_k_index,
+                      const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
 {
-    const auto [E, H, N1, I] = moe_check("w8_a16_moe_train", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
+    moe_rows_check(fn, "hidden", hidden_in);
+    const MoeShape m = moe_stacks(fn, "hidden", hidden_in, gu_w, gu_s, dn_w, dn_s, bits);
+    moe_routing_check(fn, hidden_in, top_k_index, top_k_weights);
     const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
-    Tensor        out     = torch::empty({T, H}, hidden_in.options());
-    Tensor        tables  = MoeTables::alloc(E, S, hidden_in.device());
-    Tensor        gate_up = torch::empty({S, N1}, hidden_in.options());
-    Tensor        down    = torch::empty({S, H}, hidden_in.options());
-    if (T == 0) return {out, tables, gate_up, down};
-    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, tables);
-    if (T <= 16 || !moe_host_path()) {
-        Tensor inter = torch::empty({S, I}, r.hidden.options());
-        moe_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, gate_up.data_ptr(), T, k, E, N1, H, 1, 0, r.st);
-        check(eetq_silu_mul_glu8_f16(gate_up.data_ptr(), inter.data_ptr(), (int)S, (int)I, r.st));
-        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, r.st);
-    } else {
-        moe_host_experts(r, gu_w, gu_s, dn_w, dn_s, down, &gate_up);
+    const MoePlan p = moe_plan(fn, bits, path, T, k, m.E, m.H, m.I, true);
+    Tensor        out    = torch::empty({T, m.H}, hidden_in.options());
+    Tensor        tables = MoeTables::alloc(m.E, S, hidden_in.device());
+    Tensor        gate_up, y;
+    if (keep) {
+        gate_up = torch::empty({S, m.N1}, hidden_in.options());
+        y       = torch::empty({S, m.H}, hidden_in.options());
     }
-    moe_combine(down, r.t.position, r.wts, out, r.st);
-    return {out, tables, gate_up, down};
+    if (T == 0) return {out, tables, gate_up, y};
+    const MoeSetup c(hidden_in, tables, m.E, S);
+    const Tensor   idx = top_k_index.to(at::kLong).contiguous(), wts = top_k_weights.contiguous();
+    moe_route(idx, m.E, c.t, c.st);
+    moe_experts(p, c, wts, m, gu_w, gu_s, dn_w, dn_s, out, keep ? &gate_up : nullptr, keep ? &y : nullptr);
+    return {out, tables, gate_up, y};
+}
+
+// Routed W8A16 mixture-of-experts layer: the forward of transformers' experts modules.
+Tensor w8_a16_moe(const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
+                  const Tensor& dn_w, const Tensor& dn_s)
+{
+    return std::get<0>(moe_layer("w8_a16_moe", 8, "auto", false, hidden, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s));
+}
+
+// Trainable forward of the layer: the same `out` as w8_a16_moe bit for bit -- the plan is the same -- plus what the
+// backward reads.  (Under the A/B host switch: w8_a16_moe's host path with each expert's gate|up run plain on the kernel its gated
+// write-out uses, then one silu_mul over all rows.)
+std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights,
+                                                            const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+{
+    return moe_layer("w8_a16_moe_train", 8, "auto", true, hidden, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
+}
+
+// Routed W4A16 mixture-of-experts layer: w8_a16_moe on int4 expert stacks -- gate_up_qweight int8 [E, H, I]
+// (= [E, K = H, N / 2], N = 2I: two values per byte; per expert the gfx950 int4 layout, glu8 column order), gate_up_scales fp16
+// [E, 2I], down_qweight int8 [E, I, H / 2], down_scales fp16 [E, H].  Inference only; eetq_moe_route and eetq_moe_combine_f16 are the
+// int8 layer's, unchanged.  w4_a16_moe_path reports what path = "auto" runs.
+Tensor w4_a16_moe(const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
+                  const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
+{
+    return std::get<0>(moe_layer("w4_a16_moe", 4, path, false, hidden, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s));
 }
 
 // Backward of w8_a16_moe_train with the int8 weights frozen (extension): the gradients of the hidden states
@@ -1095,10 +1194,8 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
                                                      const Tensor& dn_w, const Tensor& dn_s, bool need_input_grad,
                                                      bool need_weights_grad)
 {
-    TORCH_CHECK(grad_out.is_cuda() && grad_out.scalar_type() == at::kHalf && grad_out.dim() == 2,
-                "w8_a16_moe_backward: grad_out must be a float16 GPU tensor [T, H]");
-    const auto [E, H, N1, I] = moe_stacks("w8_a16_moe_backward", gu_w, gu_s, dn_w, dn_s, grad_out.device());
-    TORCH_CHECK(grad_out.size(1) == H, "w8_a16_moe_backward: grad_out is [T, ", grad_out.size(1), "] but the experts have H = ", H);
+    moe_rows_check("w8_a16_moe_backward", "grad_out", grad_out);
+    const auto [E, H, N1, I] = moe_stacks("w8_a16_moe_backward", "grad_out", grad_out, gu_w, gu_s, dn_w, dn_s);
     TORCH_CHECK(top_k_weights.dim() == 2 && top_k_weights.size(0) == grad_out.size(0) && top_k_weights.device() == grad_out.device() &&
                     (top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf),
                 "w8_a16_moe_backward: top_k_weights must be float32 or float16 [T, k] on grad_out's device");
@@ -1149,87 +1246,6 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
     return {gx, gw};
 }
 
-// Routed W4A16 mixture-of-experts layer (extension): w8_a16_moe on int4 expert stacks -- gate_up_qweight int8
-// [E, H, I] (= [E, K = H, N / 2], N = 2I: two values per byte; per expert the gfx950 int4 layout, glu8 column order), gate_up_scales
-// fp16 [E, 2I], down_qweight int8 [E, I, H / 2], down_scales fp16 [E, H].  Inference only.  route -> grouped GEMM (gather, glu8) ->
-// grouped GEMM (sorted rows) -> combine; eetq_moe_route and eetq_moe_combine_f16 are the int8 layer's, unchanged.  No host sync,
-// capturable.
-// Which grouped kernel serves the layer's two projections, from the SHAPES alone (like moe_grouped_gemm: the counts live on the
-// device, and every call with the same T, k, E, H, I runs the same kernels whatever the routing):
-//   * "decode": eetq_w4a16_moe_gemm on the int4 tiles (16-row MFMA tiles, the expert's tile row streamed once per 16 rows);
-//   * "expand": eetq_expand_i4_to_i8 of the whole stack into a torch::empty [E, K, N] int8 buffer (freed after the projection: at
-//     most one expansion is alive), then eetq_w8a16_moe_gemm_tiled on it with the unchanged scales.
-// The expansion moves 1.5 E K N bytes per projection whatever T is (E K N / 2 read, E K N written) and the tiled kernel then reads
-// E_active K N, against ceil(rows / 16) E_active K N / 2 for the decode kernel: by bytes alone the two meet near 5 x 16 rows per
-// expert, far above the int8 layer's seam of 16.
-// Measured (tools/moe_bench.py --seam --bits 4, profiles/r10_moe_int4_seam.jsonl, DESIGN.md 4.12), one MI355X, us per gate|up + down
-// pair, decode kernel / expansions + tiled kernel (of which the two expansions alone: 355 us Mixtral, 157 us Qwen3, whatever T),
-// uniform routing (skewed routing moves no entry across 1.0):
-//   mean rows S / E      16        32        64         128         256
-//   qwen3-30b-a3b        177/369   328/400   583/443    1124/582    2220/787
-//   mixtral-8x7b         400/752   708/771   1353/859   2650/1060   5231/1404
-// At 32 rows per expert the decode kernel still wins at both shapes (0.82, 0.92), at 64 the expanded path does (1.31, 1.58): the
-// seam sits 2-4 x higher than the int8 layer's 16, where the bytes put it.  In rows per expert it is the same at both shapes:
-// both sides of the comparison scale with E K N, so E K N drops out of the rule.  (The lines cross near 40 rows by interpolation;
-// nothing between 32 and 64 was measured, so the rule starts at the first measured point where the expansion wins.)
-constexpr int64_t kMoeI4ExpandMinMeanRows = 64;
-
-// ... and only where eetq_w8a16_moe_gemm_tiled takes BOTH projections (its own limits, asked of the library: K >= 320, N K < 2^31
-// per expert, the activation block below 2 GiB): nothing is allocated or expanded for a shape that would then run the decode
-// kernel, and w4_a16_moe_path reports what runs.
-bool moe_i4_tiled_takes(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
-{
-    if (T < 1 || T * k > (int64_t(1) << 30)) return false;
-    return eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)(2 * I), (int)H, 1) == 1 &&
-           eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)H, (int)I, 0) == 1;
-}
-
-bool moe_i4_expands(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
-{
-    return T > 16 && T * k >= kMoeI4ExpandMinMeanRows * E && moe_i4_tiled_takes(T, k, E, H, I);
-}
-
-std::string w4_a16_moe_path(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
-{
-    TORCH_CHECK(T >= 0 && k >= 1 && E >= 1 && k <= E && H >= 1 && I >= 1, "w4_a16_moe_path: T >= 0, 1 <= k <= E, H >= 1, I >= 1");
-    return moe_i4_expands(T, k, E, H, I) ? "expand" : "decode";
-}
-
-// One grouped projection over an int4 stack w [E, K, N / 2].  `expand` is set only where the tiled kernel takes the shape.
-void moe_i4_grouped_gemm(const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k, int64_t E,
-                         int64_t N, int64_t K, int gather, int glu8, bool expand, void* st)
-{
-    if (expand) {
-        Tensor w8 = torch::empty({E, K, N}, w.options());
-        check(eetq_expand_i4_to_i8(w.data_ptr<int8_t>(), w8.data_ptr<int8_t>(), (size_t)w.numel(), st));
-        check(eetq_w8a16_moe_gemm_tiled(x, w8.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E,
-                                        (int)N, (int)K, gather, glu8, st));
-        return;
-    }
-    check(eetq_w4a16_moe_gemm(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E, (int)N,
-                              (int)K, gather, glu8, st));
-}
-
-Tensor w4_a16_moe(const Tensor& hidden_in, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
-                  const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
-{
-    const auto [E, H, N1, I] = moe_check("w4_a16_moe", hidden_in, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s, 4);
-    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", "w4_a16_moe: path must be 'auto', 'decode' or 'expand'");
-    const int64_t T = hidden_in.size(0), k = top_k_index.size(1), S = T * k;
-    Tensor        out = torch::empty({T, H}, hidden_in.options());
-    if (T == 0) return out;
-    TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
-                "w4_a16_moe: path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
-    const bool      expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
-    const MoeRouted r(hidden_in, top_k_index, top_k_weights, E, MoeTables::alloc(E, S, hidden_in.device()));
-    Tensor          inter = torch::empty({S, I}, r.hidden.options());
-    Tensor          down  = torch::empty({S, H}, r.hidden.options());
-    moe_i4_grouped_gemm(r.hidden.data_ptr(), gu_w, gu_s, r.t, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, r.st);
-    moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, r.t, down.data_ptr(), T, k, E, H, I, 0, 0, expand, r.st);
-    moe_combine(down, r.t.position, r.wts, out, r.st);
-    return out;
-}
-
 // ---- the MoE router on the device (extension) ----------------------------------------------------------------
 // What transformers' *TopKRouter forwards return -- (router_logits fp16 [T, E], router_scores [T, k], router_indices int64 [T, k])
 // -- from hidden [T, H] and the router weight [E, H].  T <= 16: eetq_moe_router_f16, ONE launch, which also fills `t` (when given)
@@ -1248,7 +1264,7 @@ at::ScalarType router_scores_dtype(const char* fn, const py::object& scores_dtyp
 
 void router_check(const char* fn, const Tensor& hidden, const Tensor& weight, int64_t top_k)
 {
-    TORCH_CHECK(hidden.is_cuda() && hidden.scalar_type() == at::kHalf && hidden.dim() == 2, fn, ": hidden must be a float16 GPU tensor [T, H]");
+    moe_rows_check(fn, "hidden", hidden);
     TORCH_CHECK(weight.scalar_type() == at::kHalf && weight.dim() == 2 && weight.device() == hidden.device(),
                 fn, ": the router weight must be a float16 tensor [E, H] on the hidden states' device");
     TORCH_CHECK(weight.size(1) == hidden.size(1), fn, ": hidden is [T, ", hidden.size(1), "] but the router weight has H = ", weight.size(1));
@@ -1278,9 +1294,7 @@ RouterOut router_launch(const Tensor& hidden, const Tensor& weight, int64_t k, b
     }
     check(eetq_moe_topk_f16(r.logits.data_ptr(), (int)T, (int)E, (int)k, renorm ? 1 : 0, wdt, r.idx.data_ptr<int64_t>(),
                             r.scores.data_ptr(), st));
-    if (t)
-        check(eetq_moe_route(r.idx.data_ptr<int64_t>(), (int)T, (int)k, (int)E, t->counts, t->offsets, t->sorted, t->position, t->active,
-                             st));
+    if (t) moe_route(r.idx, E, *t, st);
     return r;
 }
 
@@ -1299,44 +1313,25 @@ std::tuple<Tensor, Tensor, Tensor> moe_router(const Tensor& hidden_in, const Ten
     return {r.logits, r.scores, r.idx};
 }
 
-// The whole sparse MoE block (extension): router -> grouped GEMM (gather, silu_glu8) -> grouped GEMM -> combine on the
-// stacks of w8_a16_moe (bits = 8) or w4_a16_moe (bits = 4).  The same launches as those layers on the router's output, bit for bit;
-// only the tables come from the router launch (T <= 16: four launches in all) instead of a launch of their own.
+// The whole sparse MoE block (extension): router -> moe_experts on the stacks of w8_a16_moe (bits = 8) or w4_a16_moe
+// (bits = 4).  The same launches as those layers on the router's output, bit for bit; only the tables come from the router launch
+// (T <= 16: four launches in all) instead of a launch of their own.
 Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor& router_w, int64_t top_k, bool norm_topk_prob,
                  const py::object& scores_dtype, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s,
                  const std::string& path)
 {
     const at::ScalarType sdt = router_scores_dtype(fn, scores_dtype);
     router_check(fn, hidden_in, router_w, top_k);
-    const auto [E, H, N1, I] = moe_stacks(fn, gu_w, gu_s, dn_w, dn_s, hidden_in.device(), bits);
-    TORCH_CHECK(hidden_in.size(1) == H, fn, ": hidden is [T, ", hidden_in.size(1), "] but the experts have H = ", H);
-    TORCH_CHECK(router_w.size(0) == E, fn, ": the router weight has ", router_w.size(0), " experts but the stacks have E = ", E);
-    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", fn, ": path must be 'auto', 'decode' or 'expand'");
-    const int64_t T = hidden_in.size(0), k = top_k, S = T * k;
-    Tensor        out = torch::empty({T, H}, hidden_in.options());
+    const MoeShape m = moe_stacks(fn, "hidden", hidden_in, gu_w, gu_s, dn_w, dn_s, bits);
+    TORCH_CHECK(router_w.size(0) == m.E, fn, ": the router weight has ", router_w.size(0), " experts but the stacks have E = ", m.E);
+    const int64_t T = hidden_in.size(0), S = T * top_k;
+    const MoePlan p = moe_plan(fn, bits, path, T, top_k, m.E, m.H, m.I, false);
+    Tensor        out = torch::empty({T, m.H}, hidden_in.options());
     if (T == 0) return out;
-    bool expand = false;
-    if (bits == 4) {
-        TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
-                    fn, ": path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
-        expand = path == "expand" || (path == "auto" && moe_i4_expands(T, k, E, H, I));
-    }
-    c10::DeviceGuard guard(hidden_in.device());
-    const Tensor     hidden = hidden_in.detach().contiguous(), weight = router_w.detach().contiguous();
-    void*            st     = stream_of(hidden_in);
-    Tensor           tables = MoeTables::alloc(E, S, hidden.device());
-    const MoeTables  t(tables.data_ptr<int>(), E, S);
-    const RouterOut  r = router_launch(hidden, weight, k, norm_topk_prob, sdt, &t, st);
-    Tensor           inter = torch::empty({S, I}, hidden.options());
-    Tensor           down  = torch::empty({S, H}, hidden.options());
-    if (bits == 4) {
-        moe_i4_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, t, inter.data_ptr(), T, k, E, N1, H, 1, 1, expand, st);
-        moe_i4_grouped_gemm(inter.data_ptr(), dn_w, dn_s, t, down.data_ptr(), T, k, E, H, I, 0, 0, expand, st);
-    } else {
-        moe_grouped_gemm(hidden.data_ptr(), gu_w, gu_s, t, inter.data_ptr(), T, k, E, N1, H, 1, 1, st);
-        moe_grouped_gemm(inter.data_ptr(), dn_w, dn_s, t, down.data_ptr(), T, k, E, H, I, 0, 0, st);
-    }
-    moe_combine(down, t.position, r.scores, out, st);
+    const MoeSetup  c(hidden_in.detach(), MoeTables::alloc(m.E, S, hidden_in.device()), m.E, S);
+    const Tensor    weight = router_w.detach().contiguous();
+    const RouterOut r = router_launch(c.hidden, weight, top_k, norm_topk_prob, sdt, &c.t, c.st);
+    moe_experts(p, c, r.scores, m, gu_w, gu_s, dn_w, dn_s, out);
     return out;
 }
 
