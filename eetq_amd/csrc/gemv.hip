@@ -14,13 +14,15 @@ namespace {
 
 using gemv::gemv_kernel;
 
-template <int M, int WAVES, int D, bool EXACT, bool XREG, int XV, int OCC, int NORM = 0>
+// One launcher per kernel form for both tile widths (BITS = 8 / 4: 64 / 128 k per tile).  int8 only: the PLAIN instantiation and the
+// activation prologues (NORM = 1 RMS-norm, 2 gated) -- the int4 launchers pass no Prologue.
+template <int M, int WAVES, int D, bool EXACT, bool XREG, int XV, int OCC, int BITS = 8, int NORM = 0>
 int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K,
                 hipStream_t stream, Prologue pro = Prologue{})
 {
-    if constexpr (!NORM && !XREG && M == 1) {
-        if (pro.gamma) return launch_inst<M, WAVES, D, EXACT, XREG, XV, OCC, 1>(x, w, scales, ep, y, N, K, stream, pro);
-        if (pro.up) return launch_inst<M, WAVES, D, EXACT, XREG, XV, OCC, 2>(x, w, scales, ep, y, N, K, stream, pro);
+    if constexpr (BITS == 8 && !NORM && !XREG && M == 1) {
+        if (pro.gamma) return launch_inst<M, WAVES, D, EXACT, XREG, XV, OCC, BITS, 1>(x, w, scales, ep, y, N, K, stream, pro);
+        if (pro.up) return launch_inst<M, WAVES, D, EXACT, XREG, XV, OCC, BITS, 2>(x, w, scales, ep, y, N, K, stream, pro);
     }
     const size_t smem = gemv::gemv_smem_bytes(M, K, WAVES, XREG);
     auto go = [&](auto kern, std::atomic<unsigned long long>& opted) {
@@ -30,9 +32,9 @@ int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
         }
         launch_kernel(kern, dim3(N / kTileN), dim3(WAVES * 64), smem, stream, x, w, scales, y, N, K, pro.gamma ? pro.gamma : pro.up, ep.bias,
                       ep.residual, ep.act, pro.eps);
-        return check_hip(hipGetLastError(), "gemv_kernel launch");
+        return check_hip(hipGetLastError(), BITS == 4 ? "gemv_kernel (int4) launch" : "gemv_kernel launch");
     };
-    if constexpr (M == 1 && !NORM) {
+    if constexpr (BITS == 8 && M == 1 && !NORM) {
         // the plain projection (no bias, residual or activation) has its own instantiation of every M = 1 kernel form: same
         // arithmetic, same bits, no run-time epilogue (gemv_kernel.hpp: PLAIN)
         if (!ep.bias && !ep.residual && ep.act == 0) {
@@ -41,48 +43,68 @@ int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
         }
     }
     static std::atomic<unsigned long long> opted{0};
-    return go(gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, NORM>, opted);
+    return go(gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, NORM, BITS>, opted);
 }
 
 // LDS-staged activations: pick the number of 16-byte x loads per thread at compile time (no conditional loads)
-template <int M, int WAVES, int D, bool EXACT, int OCC>
+template <int M, int WAVES, int D, bool EXACT, int OCC, int BITS = 8>
 int launch_lds(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K,
                 hipStream_t stream, Prologue pro = Prologue{})
 {
     const int xvecs = M * K / 8, threads = WAVES * 64;
     const int need  = (xvecs + threads - 1) / threads;
     if (gemv::gemv_smem_bytes(M, K, WAVES, false) > 160 * 1024 || need > 8)
-        return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] GEMV: M*K too large for LDS staging");
-    if (need <= 1) return launch_inst<M, WAVES, D, EXACT, false, 1, OCC>(x, w, scales, ep, y, N, K, stream, pro);
-    if (need <= 2) return launch_inst<M, WAVES, D, EXACT, false, 2, OCC>(x, w, scales, ep, y, N, K, stream, pro);
-    if (need <= 4) return launch_inst<M, WAVES, D, EXACT, false, 4, OCC>(x, w, scales, ep, y, N, K, stream, pro);
-    return launch_inst<M, WAVES, D, EXACT, false, 8, OCC>(x, w, scales, ep, y, N, K, stream, pro);
+        return fail(EETQ_ERR_UNSUPPORTED, BITS == 4 ? "[eetq_amd] W4A16 GEMV: M*K too large for LDS staging"
+                                                    : "[eetq_amd] GEMV: M*K too large for LDS staging");
+    if (need <= 1) return launch_inst<M, WAVES, D, EXACT, false, 1, OCC, BITS>(x, w, scales, ep, y, N, K, stream, pro);
+    if (need <= 2) return launch_inst<M, WAVES, D, EXACT, false, 2, OCC, BITS>(x, w, scales, ep, y, N, K, stream, pro);
+    if (need <= 4) return launch_inst<M, WAVES, D, EXACT, false, 4, OCC, BITS>(x, w, scales, ep, y, N, K, stream, pro);
+    return launch_inst<M, WAVES, D, EXACT, false, 8, OCC, BITS>(x, w, scales, ep, y, N, K, stream, pro);
 }
 
-// 8-column units (gemv_half_kernel), M = 1: when they put fewer bytes on the busiest CU than whole tile rows do
-template <int XV, int NORM = 0>
-int launch_half_xv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream,
-                   Prologue pro)
+// Column units, M = 1, 8-wave workgroups: one body for both unit kernels (KERN carries every template argument, so the opt-in flag
+// is one per kernel)
+template <auto KERN>
+int launch_units(int grid, const char* what, const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K,
+                 hipStream_t stream, Prologue pro)
 {
-    if constexpr (!NORM) {
-        if (pro.gamma) return launch_half_xv<XV, 1>(x, w, scales, ep, y, N, K, stream, pro);
-        if (pro.up) return launch_half_xv<XV, 2>(x, w, scales, ep, y, N, K, stream, pro);
-    }
-    auto         kern = gemv::gemv_half_kernel<8, 2, XV, 8, NORM>;
     const size_t smem = gemv::gemv_half_smem_bytes(K, 8);
     if (smem > 64 * 1024) {
         static std::atomic<unsigned long long> opted{0};
-        int st = opt_in_large_lds(kern, opted);
+        int st = opt_in_large_lds(KERN, opted);
         if (st != EETQ_OK) return st;
     }
-    launch_kernel(kern, dim3(N / 8), dim3(8 * 64), smem, stream, x, w, scales, y, N, K, pro.gamma ? pro.gamma : pro.up, ep.bias, ep.residual,
+    launch_kernel(KERN, dim3(grid), dim3(8 * 64), smem, stream, x, w, scales, y, N, K, pro.gamma ? pro.gamma : pro.up, ep.bias, ep.residual,
                   ep.act, pro.eps);
-    return check_hip(hipGetLastError(), "gemv_half_kernel launch");
+    return check_hip(hipGetLastError(), what);
 }
 
-// 8 + 8 + 4 (gemv_mixed_kernel): N splits into exactly N / CUs = 8a + 4 columns per CU -- N = 5120 on 256 CUs: two 8-column
-// units and one 4-column unit each, 768 workgroups resident at once, instead of 640 eight-column units of which a quarter of
-// the CUs get three.  EETQ_AMD_GEMV_MIXED=0 keeps the 8-column units (A/B runs).
+// 8-column units (gemv_half_kernel): when they put fewer bytes on the busiest CU than whole tile rows do.  On int4 tiles
+// (BITS = 4) the same rule -- whole tile rows would leave CUs idle or put a second workgroup on only a few (N = 5120 on 256 CUs) --
+// with pairs of 128-deep k tiles.
+// MIXED, 8 + 8 + 4 (gemv_mixed_kernel, int8): N splits into exactly N / CUs = 8a + 4 columns per CU -- N = 5120 on 256 CUs: two
+// 8-column units and one 4-column unit each, 768 workgroups resident at once, instead of 640 eight-column units of which a quarter
+// of the CUs get three.  EETQ_AMD_GEMV_MIXED=0 keeps the 8-column units (A/B runs).
+template <int XV, int BITS = 8, bool MIXED = false, int NORM = 0>
+int launch_units_xv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream,
+                    Prologue pro = Prologue{})
+{
+    static_assert(BITS == 8 || !MIXED, "the 8 + 8 + 4 split exists on int8 tiles");
+    if constexpr (BITS == 8 && !NORM) {
+        if (pro.gamma) return launch_units_xv<XV, BITS, MIXED, 1>(x, w, scales, ep, y, N, K, stream, pro);
+        if (pro.up) return launch_units_xv<XV, BITS, MIXED, 2>(x, w, scales, ep, y, N, K, stream, pro);
+    }
+    if constexpr (MIXED) {
+        const int ncu = device_cu_count(), per = N / ncu;
+        const int n8 = ncu * (per / 8), n4 = (N - 8 * n8) / 4;  // (the kernel derives n8 from N and the grid)
+        return launch_units<gemv::gemv_mixed_kernel<8, 2, XV, 8, NORM>>(n8 + n4, "gemv_mixed_kernel launch", x, w, scales, ep, y, N, K,
+                                                                        stream, pro);
+    } else {
+        return launch_units<gemv::gemv_half_kernel<8, 2, XV, (BITS == 8 ? 8 : 4), NORM, BITS>>(
+            N / 8, BITS == 4 ? "gemv_half_kernel (int4) launch" : "gemv_half_kernel launch", x, w, scales, ep, y, N, K, stream, pro);
+    }
+}
+
 bool mixed_units_pay(int N, int K)
 {
     static const bool allowed = [] {
@@ -93,28 +115,6 @@ bool mixed_units_pay(int N, int K)
     if (!allowed || KT % 4 || KT / 4 < 16 || K > 32768 || N % (4 * ncu)) return false;  // groups of 4 k tiles, >= 2 per wave
     const int per = N / ncu;
     return per % 8 == 4 && per >= 12 && per <= 28;
-}
-
-template <int XV, int NORM = 0>
-int launch_mixed_xv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream,
-                    Prologue pro)
-{
-    if constexpr (!NORM) {
-        if (pro.gamma) return launch_mixed_xv<XV, 1>(x, w, scales, ep, y, N, K, stream, pro);
-        if (pro.up) return launch_mixed_xv<XV, 2>(x, w, scales, ep, y, N, K, stream, pro);
-    }
-    auto         kern = gemv::gemv_mixed_kernel<8, 2, XV, 8, NORM>;
-    const size_t smem = gemv::gemv_half_smem_bytes(K, 8);
-    if (smem > 64 * 1024) {
-        static std::atomic<unsigned long long> opted{0};
-        int st = opt_in_large_lds(kern, opted);
-        if (st != EETQ_OK) return st;
-    }
-    const int ncu = device_cu_count(), per = N / ncu;
-    const int n8 = ncu * (per / 8), n4 = (N - 8 * n8) / 4;
-    launch_kernel(kern, dim3(n8 + n4), dim3(8 * 64), smem, stream, x, w, scales, y, N, K, pro.gamma ? pro.gamma : pro.up, ep.bias, ep.residual,
-                  ep.act, pro.eps);  // (the kernel derives n8 from N and the grid)
-    return check_hip(hipGetLastError(), "gemv_mixed_kernel launch");
 }
 
 bool half_units_pay(int N, int K)
@@ -138,13 +138,13 @@ int launch_half(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
 {
     const int need = (K / 8 + 511) / 512;  // 16-byte activation loads per thread
     if (mixed_units_pay(N, K)) {
-        if (need <= 2) return launch_mixed_xv<2>(x, w, scales, ep, y, N, K, stream, pro);
-        if (need <= 4) return launch_mixed_xv<4>(x, w, scales, ep, y, N, K, stream, pro);
-        return launch_mixed_xv<8>(x, w, scales, ep, y, N, K, stream, pro);
+        if (need <= 2) return launch_units_xv<2, 8, true>(x, w, scales, ep, y, N, K, stream, pro);
+        if (need <= 4) return launch_units_xv<4, 8, true>(x, w, scales, ep, y, N, K, stream, pro);
+        return launch_units_xv<8, 8, true>(x, w, scales, ep, y, N, K, stream, pro);
     }
-    if (need <= 2) return launch_half_xv<2>(x, w, scales, ep, y, N, K, stream, pro);
-    if (need <= 4) return launch_half_xv<4>(x, w, scales, ep, y, N, K, stream, pro);
-    return launch_half_xv<8>(x, w, scales, ep, y, N, K, stream, pro);
+    if (need <= 2) return launch_units_xv<2>(x, w, scales, ep, y, N, K, stream, pro);
+    if (need <= 4) return launch_units_xv<4>(x, w, scales, ep, y, N, K, stream, pro);
+    return launch_units_xv<8>(x, w, scales, ep, y, N, K, stream, pro);
 }
 
 template <int M>
@@ -204,50 +204,8 @@ int launch_m(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16
     return launch_lds<M, 1, 1, false, 1>(x, w, scales, ep, y, N, K, stream, pro);
 }
 
-// ---- int4 tiles (W4A16): the same kernel template with BITS = 4 (128 k per tile, 32 k per lane) ----
-template <int M, int WAVES, int D, bool EXACT, bool XREG, int XV, int OCC>
-int launch_inst_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream)
-{
-    auto         kern = gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, 0, 4>;
-    const size_t smem = gemv::gemv_smem_bytes(M, K, WAVES, XREG);
-    if (smem > 64 * 1024) {
-        static std::atomic<unsigned long long> opted{0};
-        int st = opt_in_large_lds(kern, opted);
-        if (st != EETQ_OK) return st;
-    }
-    launch_kernel(kern, dim3(N / kTileN), dim3(WAVES * 64), smem, stream, x, w, scales, y, N, K, (const f16*)nullptr, ep.bias, ep.residual, ep.act, 0.f);
-    return check_hip(hipGetLastError(), "gemv_kernel (int4) launch");
-}
 
-template <int M, int WAVES, int D, int OCC>
-int launch_lds_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream)
-{
-    const int xvecs = M * K / 8, threads = WAVES * 64;
-    const int need  = (xvecs + threads - 1) / threads;
-    if (gemv::gemv_smem_bytes(M, K, WAVES, false) > 160 * 1024 || need > 8)
-        return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] W4A16 GEMV: M*K too large for LDS staging");
-    if (need <= 1) return launch_inst_i4<M, WAVES, D, false, false, 1, OCC>(x, w, scales, ep, y, N, K, stream);
-    if (need <= 2) return launch_inst_i4<M, WAVES, D, false, false, 2, OCC>(x, w, scales, ep, y, N, K, stream);
-    if (need <= 4) return launch_inst_i4<M, WAVES, D, false, false, 4, OCC>(x, w, scales, ep, y, N, K, stream);
-    return launch_inst_i4<M, WAVES, D, false, false, 8, OCC>(x, w, scales, ep, y, N, K, stream);
-}
-
-// 8-column units on int4 tiles (gemv_half_kernel<..., BITS = 4>): the same rule as for int8 tiles -- whole tile rows would leave CUs
-// idle or put a second workgroup on only a few (N = 5120 on 256 CUs) -- with pairs of 128-deep k tiles
-template <int XV>
-int launch_half_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K, hipStream_t stream)
-{
-    auto         kern = gemv::gemv_half_kernel<8, 2, XV, 4, 0, 4>;
-    const size_t smem = gemv::gemv_half_smem_bytes(K, 8);
-    if (smem > 64 * 1024) {
-        static std::atomic<unsigned long long> opted{0};
-        int st = opt_in_large_lds(kern, opted);
-        if (st != EETQ_OK) return st;
-    }
-    launch_kernel(kern, dim3(N / 8), dim3(8 * 64), smem, stream, x, w, scales, y, N, K, (const f16*)nullptr, ep.bias, ep.residual, ep.act, 0.f);
-    return check_hip(hipGetLastError(), "gemv_half_kernel (int4) launch");
-}
-
+// ---- int4 tiles (W4A16): the same launchers with BITS = 4 (128 k per tile, 32 k per lane) ----
 bool half_units_pay_i4(int N, int K)
 {
     const int KT = K / 128;
@@ -273,9 +231,9 @@ int launch_m_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
     if constexpr (M == 1) {
         if (ep.act == 0 && half_units_pay_i4(N, K)) {
             const int need = (K / 8 + 511) / 512;  // 16-byte activation loads per thread
-            if (need <= 2) return launch_half_i4<2>(x, w, scales, ep, y, N, K, stream);
-            if (need <= 4) return launch_half_i4<4>(x, w, scales, ep, y, N, K, stream);
-            return launch_half_i4<8>(x, w, scales, ep, y, N, K, stream);
+            if (need <= 2) return launch_units_xv<2, 4>(x, w, scales, ep, y, N, K, stream);
+            if (need <= 4) return launch_units_xv<4, 4>(x, w, scales, ep, y, N, K, stream);
+            return launch_units_xv<8, 4>(x, w, scales, ep, y, N, K, stream);
         }
     }
     if constexpr (M == 1) {
@@ -286,23 +244,23 @@ int launch_m_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
             const char* e = tuning_env("EETQ_AMD_I4_GEMV_K4096");
             return e ? atoi(e) : 0;
         }();
-        if (KT == 32 && forced32 == 84) return launch_lds_i4<M, 8, 4, 2>(x, w, scales, ep, y, N, K, stream);
+        if (KT == 32 && forced32 == 84) return launch_lds<M, 8, 4, false, 2, 4>(x, w, scales, ep, y, N, K, stream);
         if (KT == 32 && (forced32 == 82 || (forced32 == 0 && N / kTileN > 2 * device_cu_count())))
-            return launch_lds_i4<M, 8, 2, 2>(x, w, scales, ep, y, N, K, stream);
+            return launch_lds<M, 8, 2, false, 2, 4>(x, w, scales, ep, y, N, K, stream);
     }
     if constexpr (M <= 2) {
         // whole tile row in flight, activations straight to registers (the K = 4096 / 8192 decode shapes)
-        if (KT == 32) return launch_inst_i4<M, 16, 2, true, true, 1, 4>(x, w, scales, ep, y, N, K, stream);
-        if (KT == 64) return launch_inst_i4<M, 16, 4, true, true, 1, 2>(x, w, scales, ep, y, N, K, stream);
+        if (KT == 32) return launch_inst<M, 16, 2, true, true, 1, 4, 4>(x, w, scales, ep, y, N, K, stream);
+        if (KT == 64) return launch_inst<M, 16, 4, true, true, 1, 2, 4>(x, w, scales, ep, y, N, K, stream);
     }
     // (round 4: straight-line instantiations for the 13B widths -- K = 5120 as 8 waves x 5 tiles, K = 13824 as 12 x 9 -- were
     // measured and dropped: 5120 x 13824 11.9 vs 11.4 us with the generic loop.  The int4 GEMV is not bound by the shape of its
     // load stream but by ~2.1 VALU operations per weight that overlap poorly with it: profiles/r04_int4_m1.jsonl)
-    if (KT >= 64) return launch_lds_i4<M, 16, 4, 4>(x, w, scales, ep, y, N, K, stream);  // every wave owns >= 4 tiles
-    if (KT >= 32) return launch_lds_i4<M, 16, 2, 4>(x, w, scales, ep, y, N, K, stream);
-    if (KT >= 16) return launch_lds_i4<M, 8, 2, 2>(x, w, scales, ep, y, N, K, stream);
-    if (KT >= 4) return launch_lds_i4<M, 4, 1, 1>(x, w, scales, ep, y, N, K, stream);
-    return launch_lds_i4<M, 1, 1, 1>(x, w, scales, ep, y, N, K, stream);
+    if (KT >= 64) return launch_lds<M, 16, 4, false, 4, 4>(x, w, scales, ep, y, N, K, stream);  // every wave owns >= 4 tiles
+    if (KT >= 32) return launch_lds<M, 16, 2, false, 4, 4>(x, w, scales, ep, y, N, K, stream);
+    if (KT >= 16) return launch_lds<M, 8, 2, false, 2, 4>(x, w, scales, ep, y, N, K, stream);
+    if (KT >= 4) return launch_lds<M, 4, 1, false, 1, 4>(x, w, scales, ep, y, N, K, stream);
+    return launch_lds<M, 1, 1, false, 1, 4>(x, w, scales, ep, y, N, K, stream);
 }
 
 }  // namespace

@@ -1,9 +1,15 @@
 // Small-batch (AUTO: 2 <= M <= 16; by explicit path up to 64 rows) W8A16 / W4A16 stream GEMM launcher; kernel in streamk_kernel.hpp.
 // Covers the reference's batched-GEMV range (m <= 4, weightOnlyBatchedGemv/kernelLauncher.cu:165-192) and the
 // small-M end of its CUTLASS range, where the weight stream -- not the matrix cores -- bounds the time.
+//
+// One launch = one StreamRecipe.  resolve() is the only place that decides it (the measured rules below, the overrides, every
+// clamp); launch_streamk, launch_streamk_i4 and stream_plan_query all call it.  StreamInsts<MT, BITS> lists the kernels that exist,
+// one row each; dispatch() walks that list and refuses a recipe that has no row.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
+#include <utility>
 
 #include "streamk_kernel.hpp"
 
@@ -11,50 +17,51 @@ namespace eetq {
 
 namespace {
 
-template <int MT, int NT, int WAVES, int D, int OCC, int BITS = 8, int XM = 0>
-int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
-                hipStream_t stream)
-{
-    auto         kern = streamk::streamk_kernel<MT, NT, WAVES, D, OCC, BITS, XM>;
-    const size_t smem = streamk::streamk_smem_bytes(MT, NT, WAVES) +
-                        (XM == 1 ? (((size_t)M * K * 2 + 1023) & ~(size_t)1023)
-                                 : XM >= 2 ? (size_t)WAVES * (2 * D - 1) * (XM == 5 ? 4096 : XM == 4 ? (BITS == 4 ? 4096 : 2048) : (BITS == 4 && XM == 2) ? 2048 : 1024) : 0);
-    if (smem > 64 * 1024) {
-        static std::atomic<unsigned long long> opted{0};
-        int st = opt_in_large_lds(kern, opted);
-        if (st != EETQ_OK) return st;
-    }
-    launch_kernel(kern, dim3(N / (kTileN * NT)), dim3(WAVES * 64), smem, stream, x, w, scales, y, M, N, K, ep);
-    return check_hip(hipGetLastError(), "streamk_kernel launch");
-}
-
 // How a small-batch launch gets its activation fragments: form 0 = registers, 1 = block copy in LDS, 2 = per-wave ring in LDS
+// (all three feed the same fragments to the same MFMAs in the same order -- bit-identical results at equal wave count,
+// tests/test_gpu_stream_xlds.py):
+//   regs  : straight from L2 into registers, 16 (clamped) rows x 128 B per weight tile: two vector loads of activations per vector
+//           load of weights (four on int4 tiles), whatever M is
+//   block : the M rows copied ONCE per workgroup into LDS (LDS-DMA); needs K % 128 == 0; the per-tile cost is the weight load alone,
+//           so one tile row per workgroup is affordable where two load the CUs unevenly
+//   ring  : one or more LDS-DMA instructions per k tile and wave into the wave's own ring; any K, no copy up front
 struct StreamPlan {
     int form, nt, waves;
 };
 
-// The block copy keeps M x K fp16 (rounded up to 1 KiB) in dynamic LDS NEXT TO the cross-wave reduction area (WAVES x NT KiB for one
-// row tile): the launch fits only while the SUM stays within the CU's 160 KiB -- for the NT and WAVES the plan actually uses.  The
-// launchers and stream_plan_query share this check; a plan that does not fit falls back to the register form (same bits).
-inline bool block_copy_fits(int M, int K, int nt, int waves)
+// The complete launch recipe: the plan, and what follows from it -- the kernel's ring form XM (0 registers, 1 block copy, 2 / 3 / 4 /
+// 5 rings of 8 / 4 / 16 / 32 rows), D tiles in flight per wave, OCC = MIN_WAVES_PER_SIMD of its launch bounds.
+struct StreamRecipe {
+    int form, nt, waves;
+    int xm, d, occ;
+};
+
+// EETQ_AMD_I{8,4}_STREAM_PLAN=form,nt,waves (rule|regs|block|ring, 1|2, 8|16; "rule" / 0 = as the rule says) overrides single fields
+// for A/B runs and tests; _STREAM_WAVES=8 / 16 forces the workgroup size of the register form the rule starts from as well;
+// _STREAM_XLDS=0 switches both LDS forms off (the register form with its own tile rows per workgroup and workgroup size: the kernel
+// of rounds 1-3).  All empty: the rule alone.
+struct StreamOverrides {
+    StreamPlan plan{-1, 0, 0};
+    int        waves   = 0;
+    bool       lds_off = false;
+};
+
+// The activation bytes a launch keeps in dynamic LDS NEXT TO the cross-wave reduction area (streamk_smem_bytes): the block copy
+// holds M x K fp16, rounded up to 1 KiB; a ring holds 2 D - 1 slots per wave, a slot its rows x one k tile of activations (128 B
+// per row on int8 tiles, 256 B on int4 tiles: 1 / 2 / 4 KiB).
+constexpr size_t stream_x_lds_bytes(int bits, int xm, int waves, int d, int M, int K)
 {
-    const size_t xs = ((size_t)M * K * 2 + 1023) & ~(size_t)1023;
-    return xs + streamk::streamk_smem_bytes(1, nt, waves) <= (size_t)kMaxDynamicLds;
+    if (xm == 0) return 0;
+    if (xm == 1) return ((size_t)M * K * 2 + 1023) & ~(size_t)1023;
+    const int rows = xm == 3 ? 4 : xm == 4 ? 16 : xm == 5 ? 32 : 8;
+    return (size_t)waves * (2 * d - 1) * rows * (bits == 8 ? 128 : 256);
 }
 
-inline StreamPlan plan_from_env(const char* name)
+// The block copy fits only while the SUM of copy and reduction area (WAVES x NT KiB for one row tile) stays within the CU's 160 KiB
+// -- for the NT and WAVES the plan actually uses; a plan that does not fit falls back to the register form (same bits).
+inline bool block_copy_fits(int bits, int M, int K, int nt, int waves)
 {
-    StreamPlan  p{-1, 0, 0};
-    const char* e = tuning_env(name);
-    if (!e) return p;
-    char form[16] = {0};
-    int  nt = 0, waves = 0;
-    if (sscanf(e, "%15[^,],%d,%d", form, &nt, &waves) >= 1) {
-        p.form  = !strcmp(form, "regs") ? 0 : !strcmp(form, "block") ? 1 : !strcmp(form, "ring") ? 2 : -1;
-        p.nt    = nt == 1 || nt == 2 ? nt : 0;
-        p.waves = waves == 8 || waves == 16 ? waves : 0;
-    }
-    return p;
+    return stream_x_lds_bytes(bits, 1, waves, 2, M, K) + streamk::streamk_smem_bytes(1, nt, waves) <= (size_t)kMaxDynamicLds;
 }
 
 // The register form's plan.  int8: every workgroup re-reads the activations (M x K fp16 from L2) for its columns; with two tile
@@ -111,12 +118,8 @@ inline StreamPlan regs_plan_i4(int N, int ncu)
 //   rpc > 2           ring, 2 rows, 8 waves    4096 x 11008 M = 12 12.33 -> 11.74, M = 16 13.45 -> 12.39; 5120 x 13824 M = 16 18.5 -> 16.5;
 //                                              8192 x 28672 M = 16 51.5 -> 44.9
 // All forms are bit-identical at equal wave count, so a wrong pick costs time only.
-inline StreamPlan pick_plan(int M, int N, int K, int ncu, int nt0, bool eight0)
+inline StreamPlan pick_plan(int M, int N, int K, int ncu, int nt0, bool eight0, bool lds_off)
 {
-    static const bool lds_off = [] {
-        const char* e = tuning_env("EETQ_AMD_I8_STREAM_XLDS");
-        return e && atoi(e) == 0;
-    }();
     StreamPlan p{0, nt0, eight0 ? 8 : 16};
     if (lds_off || M > 16) return p;
     const int  rows   = N / kTileN;
@@ -158,12 +161,8 @@ inline StreamPlan pick_plan(int M, int N, int K, int ncu, int nt0, bool eight0)
 //   rpc > 4              ring, 1 row, 8 waves at M <= 4 from K = 5120 (5120 x 27648 M = 4 18.28 -> 16.57; 8192 x 28672 25.9 -> 24.5);
 //                        ring, 2 rows, 8 waves at M >= 5 from K = 8192 (8192 x 28672 M = 8 27.9 -> 26.9)
 // and registers everywhere else (5120^2, 5120 x 13824 / 15360, 4096 x 14336 / 22016, 6144^2 ...: nothing beats them by more than 2-3 %).
-inline StreamPlan pick_plan_i4(int M, int N, int K, int ncu, int nt0, bool eight0)
+inline StreamPlan pick_plan_i4(int M, int N, int K, int ncu, int nt0, bool eight0, bool lds_off)
 {
-    static const bool lds_off = [] {
-        const char* e = tuning_env("EETQ_AMD_I4_STREAM_XLDS");
-        return e && atoi(e) == 0;
-    }();
     StreamPlan p{0, nt0, eight0 ? 8 : 16};
     if (lds_off) return p;
     const int  rows   = N / kTileN;
@@ -195,201 +194,192 @@ inline StreamPlan ring32_plan(int M, int N, int K, int ncu)
     return StreamPlan{2, N / kTileN <= ncu ? 1 : 2, 8};
 }
 
-template <int MT>
-int launch_mt(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
-                hipStream_t stream)
+// The one decision: which kernel a launch of M rows on bits-wide tiles takes.  Pure host arithmetic -- no environment, no device.
+inline StreamRecipe resolve(int bits, int M, int N, int K, int ncu, const StreamOverrides& ov)
 {
-    const int KT = K / kTileK;  // every wave must own >= D k tiles
-    if (KT >= 32) {
-        static const int forced_waves = [] {  // EETQ_AMD_I8_STREAM_WAVES=8 / 16: force the workgroup size (A/B runs)
-            const char* e = tuning_env("EETQ_AMD_I8_STREAM_WAVES");
-            return e ? atoi(e) : 0;
-        }();
-        if constexpr (MT == 1) {
-            const int ncu = device_cu_count();
-            // the register form's own plan (regs_plan_i8): two tile rows per workgroup where that puts fewer loads on the busiest
-            // CU; 8-wave workgroups (round 4, profiles/r04_int8_stream_waves_ab.txt) wherever there are two tile rows per workgroup
-            // or more workgroups than CUs, and at M > 4
-            const StreamPlan regs  = regs_plan_i8(M, N, ncu);
-            const int        nt    = regs.nt;
-            const bool       eight = forced_waves ? forced_waves == 8 : regs.waves == 8;
-            // Where the activation fragments come from (round 4; all three forms feed the same fragments to the same MFMAs in the
-            // same order -- bit-identical results, tests/test_gpu_stream_xlds.py):
-            //   regs  : straight from L2 into registers, 16 (clamped) rows x 128 B per weight tile: two vector loads of activations
-            //           per vector load of weights, whatever M is
-            //   block : the M rows copied ONCE per workgroup into LDS (LDS-DMA); needs K % 128 == 0 and M*K*2 <= 64 KiB; the per-tile
-            //           cost is the weight load alone, so one tile row per workgroup is affordable where two load the CUs unevenly
-            //   ring  : M <= 8: one LDS-DMA instruction per k tile and wave into the wave's own ring; any K, no copy up front
-            // The rule: pick_plan above.  EETQ_AMD_I8_STREAM_PLAN=form,nt,waves (rule|regs|block|ring, 1|2, 8|16; "rule" / 0 = as
-            // the rule says) overrides single fields for A/B runs and tests; EETQ_AMD_I8_STREAM_XLDS=0 switches both LDS forms off
-            // (the register form with its own tile rows per workgroup and workgroup size: the kernel of rounds 1-3).
-            StreamPlan plan = pick_plan(M, N, K, ncu, nt, eight);
-            static const StreamPlan forced = plan_from_env("EETQ_AMD_I8_STREAM_PLAN");
-            if (forced.form >= 0) plan.form = forced.form;
-            if (forced.nt) plan.nt = forced.nt;
-            if (forced.waves) plan.waves = forced.waves;
-            if (forced_waves) plan.waves = forced_waves;
-            if (plan.nt == 2 && N % (2 * kTileN) != 0) plan.nt = 1;
-            if (plan.form == 1 && (K % 128 != 0 || (long)M * K * 2 > 128 * 1024 || !block_copy_fits(M, K, plan.nt, plan.waves))) plan.form = 0;
-            if (plan.form == 2 && M > 16) plan.form = 0;
-            const bool e8 = plan.waves == 8;
-            if (plan.form == 2 && M > 8) {  // 16-row ring: two DMAs per tile
-                if (plan.nt == 2)
-                    return e8 ? launch_inst<MT, 2, 8, 2, 4, 8, 4>(x, w, scales, ep, y, M, N, K, stream)
-                              : launch_inst<MT, 2, 16, 2, 4, 8, 4>(x, w, scales, ep, y, M, N, K, stream);
-                return e8 ? launch_inst<MT, 1, 8, 2, 4, 8, 4>(x, w, scales, ep, y, M, N, K, stream)
-                          : launch_inst<MT, 1, 16, 2, 4, 8, 4>(x, w, scales, ep, y, M, N, K, stream);
-            }
-            // (two tiles in flight per wave is the optimum of the ring forms too: one +4.8 %, three +6 %, four +9 % in geometric
-            // mean over the sweep's shapes -- profiles/r04_stream_depth_ab.txt, r04_stream_depth1_ab.txt)
-            if (plan.form == 2) {
-                if (plan.nt == 2)
-                    return e8 ? launch_inst<MT, 2, 8, 2, 4, 8, 2>(x, w, scales, ep, y, M, N, K, stream)
-                              : launch_inst<MT, 2, 16, 2, 4, 8, 2>(x, w, scales, ep, y, M, N, K, stream);
-                return e8 ? launch_inst<MT, 1, 8, 2, 4, 8, 2>(x, w, scales, ep, y, M, N, K, stream)
-                          : launch_inst<MT, 1, 16, 2, 4, 8, 2>(x, w, scales, ep, y, M, N, K, stream);
-            }
-            if (plan.form == 1) {
-                if (plan.nt == 2)
-                    return e8 ? launch_inst<MT, 2, 8, 2, 4, 8, 1>(x, w, scales, ep, y, M, N, K, stream)
-                              : launch_inst<MT, 2, 16, 2, 4, 8, 1>(x, w, scales, ep, y, M, N, K, stream);
-                return e8 ? launch_inst<MT, 1, 8, 2, 4, 8, 1>(x, w, scales, ep, y, M, N, K, stream)
-                          : launch_inst<MT, 1, 16, 2, 4, 8, 1>(x, w, scales, ep, y, M, N, K, stream);
-            }
-            if (plan.nt == 2)
-                return e8 ? launch_inst<MT, 2, 8, 2, 4>(x, w, scales, ep, y, M, N, K, stream)
-                          : launch_inst<MT, 2, 16, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
-            return e8 ? launch_inst<MT, 1, 8, 2, 4>(x, w, scales, ep, y, M, N, K, stream)
-                      : launch_inst<MT, 1, 16, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
-        }
-        if constexpr (MT == 2) {
-            // 17 <= M <= 32 (round 6): the 32-row per-wave ring -- four LDS-DMAs per k tile and wave, two MFMA row tiles per weight
-            // register tile, 8-wave workgroups (4 KiB slots: 16 waves would need 192 KiB of LDS) -- next to the register form
-            // (16 clamped rows x 128 B of activations from L2 per row tile and weight tile).  Same fragments into the same MFMAs at
-            // equal wave count.  EETQ_AMD_I8_STREAM_PLAN=ring|regs,nt,waves picks for A/B runs; the default: see the ring32 rule.
-            static const StreamPlan forced = plan_from_env("EETQ_AMD_I8_STREAM_PLAN");
-            const int ncu = device_cu_count();
-            StreamPlan plan = ring32_plan(M, N, K, ncu);
-            if (forced.form >= 0) plan.form = forced.form;
-            if (forced.nt) plan.nt = forced.nt;
-            if (forced.waves) plan.waves = forced.waves;
-            if (plan.nt == 2 && N % (2 * kTileN) != 0) plan.nt = 1;
-            if (plan.form == 2) {
-                if (plan.nt == 2) return launch_inst<MT, 2, 8, 2, 2, 8, 5>(x, w, scales, ep, y, M, N, K, stream);
-                return launch_inst<MT, 1, 8, 2, 2, 8, 5>(x, w, scales, ep, y, M, N, K, stream);
-            }
-            if (plan.waves == 8) {
-                if (plan.nt == 2) return launch_inst<MT, 2, 8, 2, 2>(x, w, scales, ep, y, M, N, K, stream);
-                return launch_inst<MT, 1, 8, 2, 2>(x, w, scales, ep, y, M, N, K, stream);
-            }
-        }
-        return launch_inst<MT, 1, 16, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
+    const int mt = (M + 15) / 16;                     // 16-row MFMA tiles
+    const int KT = K / (bits == 4 ? 128 : kTileK);    // every wave must own >= D k tiles
+    if (KT < 32) {                                    // shallow K: fixed register forms
+        if (KT >= 16) return StreamRecipe{0, 1, 8, 0, 2, 2};
+        if (KT >= 4) return StreamRecipe{0, 1, 4, 0, 1, 1};
+        return StreamRecipe{0, 1, 1, 0, 1, 1};
     }
-    if (KT >= 16) return launch_inst<MT, 1, 8, 2, 2>(x, w, scales, ep, y, M, N, K, stream);
-    if (KT >= 4) return launch_inst<MT, 1, 4, 1, 1>(x, w, scales, ep, y, M, N, K, stream);
-    return launch_inst<MT, 1, 1, 1, 1>(x, w, scales, ep, y, M, N, K, stream);
+    // (two tiles in flight per wave is the optimum of the ring forms too: one +4.8 %, three +6 %, four +9 % in geometric mean over
+    // the sweep's shapes -- profiles/r04_stream_depth_ab.txt, r04_stream_depth1_ab.txt)
+    if (mt > 2) return StreamRecipe{0, 1, 16, 0, 2, 4};  // deliberate parity with the parent: 33 <= M <= 64 has this one deep-K form, no override applies
+    StreamPlan p;
+    if (mt == 2) {
+        // 17 <= M <= 32 (round 6): the 32-row per-wave ring -- four LDS-DMAs per k tile and wave, two MFMA row tiles per weight
+        // register tile, 8-wave workgroups (4 KiB slots: 16 waves would need 192 KiB of LDS) -- next to the register form.
+        p = ring32_plan(M, N, K, ncu);
+    } else if (bits == 8) {
+        // the register form's own plan (regs_plan_i8): two tile rows per workgroup where that puts fewer loads on the busiest CU;
+        // 8-wave workgroups (round 4, profiles/r04_int8_stream_waves_ab.txt) wherever there are two tile rows per workgroup or more
+        // workgroups than CUs, and at M > 4
+        const StreamPlan regs = regs_plan_i8(M, N, ncu);
+        p = pick_plan(M, N, K, ncu, regs.nt, ov.waves ? ov.waves == 8 : regs.waves == 8, ov.lds_off);
+    } else {
+        // regs_plan_i4: 8-wave workgroups when there are enough of them to give every CU one (round 4,
+        // profiles/r04_int4_stream_waves_ab.txt), 16 waves when two tile rows per workgroup leave fewer workgroups than CUs
+        const StreamPlan regs = regs_plan_i4(N, ncu);
+        p = pick_plan_i4(M, N, K, ncu, regs.nt, ov.waves ? ov.waves == 8 : regs.waves == 8, ov.lds_off);
+    }
+    if (ov.plan.form >= 0) p.form = ov.plan.form;
+    if (ov.plan.nt) p.nt = ov.plan.nt;
+    if (ov.plan.waves) p.waves = ov.plan.waves;
+    // deliberate parity with the parent: at 17 <= M <= 32 neither _STREAM_WAVES nor _STREAM_XLDS is applied
+    if (ov.waves && mt == 1) p.waves = ov.waves;
+    if (p.nt == 2 && N % (2 * kTileN) != 0) p.nt = 1;
+    if (mt == 2) {
+        // deliberate parity with the parent, all three: the ring runs with 8 waves whatever the plan says; a forced block copy is
+        // treated as registers; the register form with 16 waves ignores nt
+        if (p.form == 2) return StreamRecipe{2, p.nt, 8, 5, 2, 2};
+        if (p.waves == 8) return StreamRecipe{0, p.nt, 8, 0, 2, 2};
+        return StreamRecipe{0, 1, 16, 0, 2, 4};
+    }
+    // one row tile.  int4, 9 <= M <= 16: the 16-row ring has 4 KiB slots, 8-wave workgroups only (16 waves would need 192 KiB of LDS)
+    if (bits == 4 && p.form == 2 && M > 8) p.waves = 8;
+    // the block copy: 128 KiB of rows at most next to int8 tiles, 144 KiB next to int4 tiles
+    if (p.form == 1 && (K % 128 != 0 || (long)M * K * 2 > (bits == 4 ? 144 : 128) * 1024 || !block_copy_fits(bits, M, K, p.nt, p.waves)))
+        p.form = 0;
+    // ring rows: 8 (one DMA per int8 tile, two per int4 tile), 16 from M = 9 (two / four DMAs), 4 up to M = 4 on int4 tiles (one DMA)
+    const int xm = p.form != 2 ? p.form : M > 8 ? 4 : (bits == 4 && M <= 4) ? 3 : 2;
+    return StreamRecipe{p.form, p.nt, p.waves, xm, 2, bits == 4 ? 2 : 4};
 }
 
-// W4A16, 2 <= M <= 16 (one row tile): int4 tiles carry 128 k, so a wave needs K / 128 >= WAVES * D tiles.  Two tile rows per
-// workgroup when that puts fewer loads on the busiest CU (per k tile: NT weight loads + 4 activation loads).
-int launch_mt_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K, hipStream_t stream)
+// Read once per process, through tuning_env(): without EETQ_AMD_TUNING=1 every field stays empty.
+inline const StreamOverrides& stream_overrides(int bits)
 {
-    const int KT = K / 128;
-    static const int forced_waves = [] {  // EETQ_AMD_I4_STREAM_WAVES=8 / 16: force the workgroup size (A/B runs)
-        const char* e = tuning_env("EETQ_AMD_I4_STREAM_WAVES");
-        return e ? atoi(e) : 0;
-    }();
-    if (KT >= 32) {
-        const int ncu = device_cu_count();
-        // the register form's own plan (regs_plan_i4): 8-wave workgroups when there are enough of them to give every CU one (round 4,
-        // profiles/r04_int4_stream_waves_ab.txt), 16 waves when two tile rows per workgroup leave fewer workgroups than CUs
-        const StreamPlan regs  = regs_plan_i4(N, ncu);
-        const int        nt    = regs.nt;
-        const bool       eight = forced_waves ? forced_waves == 8 : regs.waves == 8;
-        // Where the activation fragments come from (see launch_mt / pick_plan): four activation loads per weight load in the
-        // register form.  EETQ_AMD_I4_STREAM_PLAN=form,nt,waves overrides (A/B runs), EETQ_AMD_I4_STREAM_XLDS=0: registers only.
-        StreamPlan plan = pick_plan_i4(M, N, K, ncu, nt, eight);
-        static const StreamPlan forced = plan_from_env("EETQ_AMD_I4_STREAM_PLAN");
-        if (forced.form >= 0) plan.form = forced.form;
-        if (forced.nt) plan.nt = forced.nt;
-        if (forced.waves) plan.waves = forced.waves;
-        if (forced_waves) plan.waves = forced_waves;
-        if (plan.nt == 2 && N % (2 * kTileN) != 0) plan.nt = 1;
-        if (plan.form == 2 && M > 8) plan.waves = 8;
-        if (plan.form == 1 && ((long)M * K * 2 > 144 * 1024 || !block_copy_fits(M, K, plan.nt, plan.waves))) plan.form = 0;
-        const bool e8 = plan.waves == 8;
-        if (plan.form == 2 && M > 8) {  // 16-row ring: 4 KiB slots, 8-wave workgroups only (16 waves would need 192 KiB of LDS)
-            if (plan.nt == 2) return launch_inst<1, 2, 8, 2, 2, 4, 4>(x, w, scales, ep, y, M, N, K, stream);
-            return launch_inst<1, 1, 8, 2, 2, 4, 4>(x, w, scales, ep, y, M, N, K, stream);
+    static const auto parse = [](const char* plan, const char* waves, const char* xlds) {
+        StreamOverrides ov;
+        char            form[16] = {0};
+        int             nt = 0, wv = 0;
+        if (plan && sscanf(plan, "%15[^,],%d,%d", form, &nt, &wv) >= 1) {
+            ov.plan.form  = !strcmp(form, "regs") ? 0 : !strcmp(form, "block") ? 1 : !strcmp(form, "ring") ? 2 : -1;
+            ov.plan.nt    = nt == 1 || nt == 2 ? nt : 0;
+            ov.plan.waves = wv == 8 || wv == 16 ? wv : 0;
         }
-        if (plan.form == 2 && M <= 4) {
-            if (plan.nt == 2) return e8 ? launch_inst<1, 2, 8, 2, 2, 4, 3>(x, w, scales, ep, y, M, N, K, stream)
-                                        : launch_inst<1, 2, 16, 2, 2, 4, 3>(x, w, scales, ep, y, M, N, K, stream);
-            return e8 ? launch_inst<1, 1, 8, 2, 2, 4, 3>(x, w, scales, ep, y, M, N, K, stream)
-                      : launch_inst<1, 1, 16, 2, 2, 4, 3>(x, w, scales, ep, y, M, N, K, stream);
-        }
-        if (plan.form == 2) {
-            if (plan.nt == 2) return e8 ? launch_inst<1, 2, 8, 2, 2, 4, 2>(x, w, scales, ep, y, M, N, K, stream)
-                                        : launch_inst<1, 2, 16, 2, 2, 4, 2>(x, w, scales, ep, y, M, N, K, stream);
-            return e8 ? launch_inst<1, 1, 8, 2, 2, 4, 2>(x, w, scales, ep, y, M, N, K, stream)
-                      : launch_inst<1, 1, 16, 2, 2, 4, 2>(x, w, scales, ep, y, M, N, K, stream);
-        }
-        if (plan.form == 1) {
-            if (plan.nt == 2) return e8 ? launch_inst<1, 2, 8, 2, 2, 4, 1>(x, w, scales, ep, y, M, N, K, stream)
-                                        : launch_inst<1, 2, 16, 2, 2, 4, 1>(x, w, scales, ep, y, M, N, K, stream);
-            return e8 ? launch_inst<1, 1, 8, 2, 2, 4, 1>(x, w, scales, ep, y, M, N, K, stream)
-                      : launch_inst<1, 1, 16, 2, 2, 4, 1>(x, w, scales, ep, y, M, N, K, stream);
-        }
-        if (plan.nt == 2) return e8 ? launch_inst<1, 2, 8, 2, 2, 4>(x, w, scales, ep, y, M, N, K, stream)
-                                    : launch_inst<1, 2, 16, 2, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
-        return e8 ? launch_inst<1, 1, 8, 2, 2, 4>(x, w, scales, ep, y, M, N, K, stream)
-                  : launch_inst<1, 1, 16, 2, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
+        wv         = waves ? atoi(waves) : 0;
+        ov.waves   = wv == 0 ? 0 : wv == 8 ? 8 : 16;  // any value but 8 has always meant 16
+        ov.lds_off = xlds && atoi(xlds) == 0;
+        return ov;
+    };
+    static const StreamOverrides i8 = parse(tuning_env("EETQ_AMD_I8_STREAM_PLAN"), tuning_env("EETQ_AMD_I8_STREAM_WAVES"),
+                                            tuning_env("EETQ_AMD_I8_STREAM_XLDS"));
+    static const StreamOverrides i4 = parse(tuning_env("EETQ_AMD_I4_STREAM_PLAN"), tuning_env("EETQ_AMD_I4_STREAM_WAVES"),
+                                            tuning_env("EETQ_AMD_I4_STREAM_XLDS"));
+    return bits == 4 ? i4 : i8;
+}
+
+struct StreamArgs {
+    const f16*     x;
+    const uint8_t* w;
+    const f16*     scales;
+    Epilogue       ep;
+    f16*           y;
+    int            M, N, K;
+    hipStream_t    stream;
+};
+
+template <int MT, int NT, int WAVES, int D, int OCC, int BITS, int XM>
+int launch_inst(const StreamArgs& a)
+{
+    auto         kern = streamk::streamk_kernel<MT, NT, WAVES, D, OCC, BITS, XM>;
+    const size_t smem = streamk::streamk_smem_bytes(MT, NT, WAVES) + stream_x_lds_bytes(BITS, XM, WAVES, D, a.M, a.K);
+    if (smem > 64 * 1024) {
+        static std::atomic<unsigned long long> opted{0};
+        int st = opt_in_large_lds(kern, opted);
+        if (st != EETQ_OK) return st;
     }
-    if (KT >= 16) return launch_inst<1, 1, 8, 2, 2, 4>(x, w, scales, ep, y, M, N, K, stream);
-    if (KT >= 4) return launch_inst<1, 1, 4, 1, 1, 4>(x, w, scales, ep, y, M, N, K, stream);
-    return launch_inst<1, 1, 1, 1, 1, 4>(x, w, scales, ep, y, M, N, K, stream);
+    launch_kernel(kern, dim3(a.N / (kTileN * NT)), dim3(WAVES * 64), smem, a.stream, a.x, a.w, a.scales, a.y, a.M, a.N, a.K, a.ep);
+    return check_hip(hipGetLastError(), "streamk_kernel launch");
+}
+
+// The kernels that exist: one row per instantiation of streamk_kernel<MT, NT, WAVES, D, OCC, BITS, XM>.
+struct StreamInst {
+    int nt, waves, d, occ, xm;
+};
+template <int MT, int BITS>
+struct StreamInsts;
+template <>
+struct StreamInsts<1, 8> {
+    static constexpr StreamInst rows[] = {
+        // NT WAVES D OCC XM
+        {1, 16, 2, 4, 0}, {1, 8, 2, 4, 0}, {2, 16, 2, 4, 0}, {2, 8, 2, 4, 0},  // registers
+        {1, 16, 2, 4, 1}, {1, 8, 2, 4, 1}, {2, 16, 2, 4, 1}, {2, 8, 2, 4, 1},  // block copy
+        {1, 16, 2, 4, 2}, {1, 8, 2, 4, 2}, {2, 16, 2, 4, 2}, {2, 8, 2, 4, 2},  // 8-row ring
+        {1, 16, 2, 4, 4}, {1, 8, 2, 4, 4}, {2, 16, 2, 4, 4}, {2, 8, 2, 4, 4},  // 16-row ring: two DMAs per tile
+        {1, 8, 2, 2, 0},  {1, 4, 1, 1, 0}, {1, 1, 1, 1, 0},                    // K / 64 < 32
+    };
+};
+template <>
+struct StreamInsts<2, 8> {
+    static constexpr StreamInst rows[] = {
+        {1, 8, 2, 2, 5},  {2, 8, 2, 2, 5},                                     // 32-row ring
+        {1, 8, 2, 2, 0},  {2, 8, 2, 2, 0},  {1, 16, 2, 4, 0},                  // registers (the first also at K / 64 < 32)
+        {1, 4, 1, 1, 0},  {1, 1, 1, 1, 0},                                     // K / 64 < 32
+    };
+};
+template <int MT>
+struct StreamInsts<MT, 8> {  // three and four row tiles
+    static constexpr StreamInst rows[] = {{1, 16, 2, 4, 0}, {1, 8, 2, 2, 0}, {1, 4, 1, 1, 0}, {1, 1, 1, 1, 0}};
+};
+template <>
+struct StreamInsts<1, 4> {
+    static constexpr StreamInst rows[] = {
+        {1, 16, 2, 2, 0}, {1, 8, 2, 2, 0}, {2, 16, 2, 2, 0}, {2, 8, 2, 2, 0},  // registers (the second also at K / 128 < 32)
+        {1, 16, 2, 2, 1}, {1, 8, 2, 2, 1}, {2, 16, 2, 2, 1}, {2, 8, 2, 2, 1},  // block copy
+        {1, 16, 2, 2, 2}, {1, 8, 2, 2, 2}, {2, 16, 2, 2, 2}, {2, 8, 2, 2, 2},  // 8-row ring: two DMAs per tile
+        {1, 16, 2, 2, 3}, {1, 8, 2, 2, 3}, {2, 16, 2, 2, 3}, {2, 8, 2, 2, 3},  // 4-row ring: one DMA per tile
+        {1, 8, 2, 2, 4},  {2, 8, 2, 2, 4},                                     // 16-row ring: four DMAs per tile
+        {1, 4, 1, 1, 0},  {1, 1, 1, 1, 0},                                     // K / 128 < 32
+    };
+};
+
+template <int MT, int BITS, size_t... I>
+int dispatch(const StreamRecipe& r, const StreamArgs& a, std::index_sequence<I...>)
+{
+    constexpr auto& rows = StreamInsts<MT, BITS>::rows;
+    int             st   = EETQ_OK;
+    const bool      hit  = ((r.nt == rows[I].nt && r.waves == rows[I].waves && r.d == rows[I].d && r.occ == rows[I].occ && r.xm == rows[I].xm &&
+                       ((st = launch_inst<MT, rows[I].nt, rows[I].waves, rows[I].d, rows[I].occ, BITS, rows[I].xm>(a)), true)) || ...);
+    if (hit) return st;
+    char msg[160];
+    snprintf(msg, sizeof msg, "[eetq_amd] stream-MFMA path: no kernel for W%dA16 M = %d: form %d, nt %d, waves %d, D %d, OCC %d, XM %d", BITS,
+             a.M, r.form, r.nt, r.waves, r.d, r.occ, r.xm);
+    return fail(EETQ_ERR_UNSUPPORTED, msg);
+}
+
+template <int MT, int BITS>
+int launch_mt(const StreamArgs& a)
+{
+    const StreamRecipe r = resolve(BITS, a.M, a.N, a.K, device_cu_count(), stream_overrides(BITS));
+    return dispatch<MT, BITS>(r, a, std::make_index_sequence<std::size(StreamInsts<MT, BITS>::rows)>{});
 }
 
 }  // namespace
 
-// Which plan a small-batch launch takes (eetq_diag_stream_plan): pure host arithmetic, the same functions the launchers call.
+// Which plan a small-batch launch takes (eetq_diag_stream_plan): resolve() with empty overrides, i.e. what a production launch runs.
 // Returns 0 and fills form (0 registers, 1 block copy, 2 ring), tile rows per workgroup, waves per workgroup, or -1 when the shape is
-// outside the kernel (M > 16 rows of one tile, K not a multiple of the tile depth).  Environment overrides are NOT applied.
+// outside the kernel (M > 16 rows of one tile, K not a multiple of the tile depth).
 int stream_plan_query(int bits, int M, int N, int K, int ncu, int* form, int* nt, int* waves)
 {
     const int tile_k = bits == 4 ? 128 : 64;
     if ((bits != 4 && bits != 8) || M < 1 || M > 16 || N < kTileN || N % kTileN || K < tile_k || K % tile_k || ncu < 1) return -1;
-    const int  KT = K / tile_k;
-    StreamPlan p{0, 1, 16};
-    if (KT >= 32) {
-        if (bits == 8) {
-            const StreamPlan r = regs_plan_i8(M, N, ncu);
-            p                  = pick_plan(M, N, K, ncu, r.nt, r.waves == 8);
-            if (p.nt == 2 && N % (2 * kTileN) != 0) p.nt = 1;
-            if (p.form == 1 && (K % 128 != 0 || (long)M * K * 2 > 128 * 1024 || !block_copy_fits(M, K, p.nt, p.waves))) p.form = 0;
-        } else {
-            const StreamPlan r = regs_plan_i4(N, ncu);
-            p                  = pick_plan_i4(M, N, K, ncu, r.nt, r.waves == 8);
-            if (p.form == 2 && M > 8) p.waves = 8;
-            if (p.nt == 2 && N % (2 * kTileN) != 0) p.nt = 1;
-            if (p.form == 1 && ((long)M * K * 2 > 144 * 1024 || !block_copy_fits(M, K, p.nt, p.waves))) p.form = 0;
-        }
-        if (p.nt == 2 && N % (2 * kTileN) != 0) p.nt = 1;
-    } else {
-        p.waves = KT >= 16 ? 8 : KT >= 4 ? 4 : 1;
-    }
-    *form  = p.form;
-    *nt    = p.nt;
-    *waves = p.waves;
+    const StreamRecipe r = resolve(bits, M, N, K, ncu, StreamOverrides{});
+    *form  = r.form;
+    *nt    = r.nt;
+    *waves = r.waves;
     return 0;
 }
 
+// W4A16, 1 <= M <= 16 (one row tile): int4 tiles carry 128 k
 int launch_streamk_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                       hipStream_t stream)
 {
     if (M < 1 || M > 16 || K % 128)
         return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] W4A16 stream-MFMA path supports 1 <= M <= 16, K % 128 == 0");
-    return launch_mt_i4(x, w, scales, ep, y, M, N, K, stream);
+    return launch_mt<1, 4>(StreamArgs{x, w, scales, ep, y, M, N, K, stream});
 }
 
 int launch_streamk(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
@@ -397,11 +387,12 @@ int launch_streamk(const f16* x, const uint8_t* w, const f16* scales, Epilogue e
 {
     if (M < 1 || M > kStreamMaxM)
         return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] stream-MFMA path supports 1 <= M <= 64");
+    const StreamArgs a{x, w, scales, ep, y, M, N, K, stream};
     switch ((M + 15) / 16) {
-        case 1: return launch_mt<1>(x, w, scales, ep, y, M, N, K, stream);
-        case 2: return launch_mt<2>(x, w, scales, ep, y, M, N, K, stream);
-        case 3: return launch_mt<3>(x, w, scales, ep, y, M, N, K, stream);
-        default: return launch_mt<4>(x, w, scales, ep, y, M, N, K, stream);
+        case 1: return launch_mt<1, 8>(a);
+        case 2: return launch_mt<2, 8>(a);
+        case 3: return launch_mt<3, 8>(a);
+        default: return launch_mt<4, 8>(a);
     }
 }
 
