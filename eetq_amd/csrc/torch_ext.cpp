@@ -10,6 +10,7 @@
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -1255,6 +1256,17 @@ struct RouterOut {
     Tensor logits, scores, idx;
 };
 
+// The routing rule.  bias undefined: the softmax rule above (fp16 logits).  bias defined: the sigmoid, bias-corrected, group-limited
+// rule of DeepseekV3TopkRouter -- fp32 logits, fp32 weights = sigmoid (renormalised) * scale -- on
+// eetq_moe_router_sigmoid_f16 (T <= 16, one launch) or at::linear in fp32, eetq_moe_topk_sigmoid_f32 and eetq_moe_route above it.
+struct RouterRule {
+    Tensor  bias;  // e_score_correction_bias [E], fp16 or fp32
+    int64_t n_group = 1, topk_group = 1;
+    double  scale = 1.0;
+    bool    sigmoid() const { return bias.defined(); }
+    int     bias_dtype() const { return bias.scalar_type() == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16; }
+};
+
 at::ScalarType router_scores_dtype(const char* fn, const py::object& scores_dtype)
 {
     const at::ScalarType dt = scores_dtype.is_none() ? at::kFloat : torch::python::detail::py_object_to_dtype(scores_dtype);
@@ -1272,30 +1284,78 @@ void router_check(const char* fn, const Tensor& hidden, const Tensor& weight, in
     TORCH_CHECK(hidden.size(0) * weight.size(0) < (1ll << 31) && hidden.size(0) * top_k <= (1ll << 30), fn, ": too many tokens");
 }
 
+// the sigmoid rule's arguments against the router weight [E, H] (the C entries check the same limits; here before any launch)
+RouterRule router_rule(const char* fn, const Tensor& weight, const Tensor& bias, int64_t top_k, int64_t n_group, int64_t topk_group,
+                       double scale)
+{
+    const int64_t E = weight.size(0);
+    TORCH_CHECK(bias.defined() && bias.dim() == 1 && bias.size(0) == E && bias.device() == weight.device() &&
+                    (bias.scalar_type() == at::kHalf || bias.scalar_type() == at::kFloat),
+                fn, ": the correction bias must be a float16 or float32 tensor [E] on the router weight's device");
+    TORCH_CHECK(n_group >= 1 && n_group <= 64 && E % n_group == 0 && (n_group == 1 || E / n_group >= 2), fn,
+                ": n_group must be in [1, 64] and divide E into groups of at least two experts (E = ", E, ", n_group = ", n_group, ")");
+    TORCH_CHECK(topk_group >= 1 && topk_group <= n_group, fn, ": topk_group must be in [1, n_group]");
+    TORCH_CHECK(top_k <= topk_group * (E / n_group), fn, ": top_k exceeds the experts of the topk_group kept groups");
+    TORCH_CHECK(std::isfinite(scale), fn, ": routed_scaling_factor must be finite");
+    RouterRule r;
+    r.bias       = bias.detach().contiguous();
+    r.n_group    = n_group;
+    r.topk_group = topk_group;
+    r.scale      = scale;
+    return r;
+}
+
 // hidden and weight contiguous, T >= 1, the device guard set by the caller
-RouterOut router_launch(const Tensor& hidden, const Tensor& weight, int64_t k, bool renorm, at::ScalarType sdt, const MoeTables* t, void* st)
+RouterOut router_launch(const Tensor& hidden, const Tensor& weight, const RouterRule& rule, int64_t k, bool renorm, at::ScalarType sdt,
+                        const MoeTables* t, void* st)
 {
     const int64_t T = hidden.size(0), H = hidden.size(1), E = weight.size(0);
     const int     wdt = sdt == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F16;
+    const bool    sig = rule.sigmoid();
     RouterOut     r;
     r.scores = torch::empty({T, k}, hidden.options().dtype(sdt));
     r.idx    = torch::empty({T, k}, hidden.options().dtype(at::kLong));
     if (T <= 16) {
-        r.logits = torch::empty({T, E}, hidden.options());
-        check(eetq_moe_router_f16(hidden.data_ptr(), weight.data_ptr(), (int)T, (int)H, (int)E, (int)k, renorm ? 1 : 0, wdt,
-                                  r.logits.data_ptr(), r.idx.data_ptr<int64_t>(), r.scores.data_ptr(), t ? t->counts : nullptr,
-                                  t ? t->offsets : nullptr, t ? t->sorted : nullptr, t ? t->position : nullptr,
-                                  t ? t->active : nullptr, st));
+        r.logits = torch::empty({T, E}, hidden.options().dtype(sig ? at::kFloat : at::kHalf));
+        int* const tb[5] = {t ? t->counts : nullptr, t ? t->offsets : nullptr, t ? t->sorted : nullptr, t ? t->position : nullptr,
+                            t ? t->active : nullptr};
+        if (sig)
+            check(eetq_moe_router_sigmoid_f16(hidden.data_ptr(), weight.data_ptr(), rule.bias.data_ptr(), rule.bias_dtype(), (int)T, (int)H,
+                                              (int)E, (int)k, (int)rule.n_group, (int)rule.topk_group, renorm ? 1 : 0, (float)rule.scale,
+                                              wdt, r.logits.data_ptr(), r.idx.data_ptr<int64_t>(), r.scores.data_ptr(), tb[0], tb[1],
+                                              tb[2], tb[3], tb[4], st));
+        else
+            check(eetq_moe_router_f16(hidden.data_ptr(), weight.data_ptr(), (int)T, (int)H, (int)E, (int)k, renorm ? 1 : 0, wdt,
+                                      r.logits.data_ptr(), r.idx.data_ptr<int64_t>(), r.scores.data_ptr(), tb[0], tb[1], tb[2], tb[3],
+                                      tb[4], st));
         return r;
     }
     {
         at::NoGradGuard no_grad;
-        r.logits = at::linear(hidden, weight).contiguous();
+        r.logits = (sig ? at::linear(hidden.to(at::kFloat), weight.to(at::kFloat)) : at::linear(hidden, weight)).contiguous();
     }
-    check(eetq_moe_topk_f16(r.logits.data_ptr(), (int)T, (int)E, (int)k, renorm ? 1 : 0, wdt, r.idx.data_ptr<int64_t>(),
-                            r.scores.data_ptr(), st));
+    if (sig)
+        check(eetq_moe_topk_sigmoid_f32(r.logits.data_ptr(), rule.bias.data_ptr(), rule.bias_dtype(), (int)T, (int)E, (int)k,
+                                        (int)rule.n_group, (int)rule.topk_group, renorm ? 1 : 0, (float)rule.scale, wdt,
+                                        r.idx.data_ptr<int64_t>(), r.scores.data_ptr(), st));
+    else
+        check(eetq_moe_topk_f16(r.logits.data_ptr(), (int)T, (int)E, (int)k, renorm ? 1 : 0, wdt, r.idx.data_ptr<int64_t>(),
+                                r.scores.data_ptr(), st));
     if (t) moe_route(r.idx, E, *t, st);
     return r;
+}
+
+// the router op of either rule: (logits, scores, idx)
+RouterOut router_op(const Tensor& hidden_in, const Tensor& weight_in, const RouterRule& rule, int64_t top_k, bool renorm,
+                    at::ScalarType sdt)
+{
+    const int64_t T = hidden_in.size(0), E = weight_in.size(0);
+    if (T == 0)
+        return {torch::empty({0, E}, hidden_in.options().dtype(rule.sigmoid() ? at::kFloat : at::kHalf)),
+                torch::empty({0, top_k}, hidden_in.options().dtype(sdt)), torch::empty({0, top_k}, hidden_in.options().dtype(at::kLong))};
+    c10::DeviceGuard guard(hidden_in.device());
+    const Tensor     hidden = hidden_in.detach().contiguous(), weight = weight_in.detach().contiguous();
+    return router_launch(hidden, weight, rule, top_k, renorm, sdt, nullptr, stream_of(hidden_in));
 }
 
 std::tuple<Tensor, Tensor, Tensor> moe_router(const Tensor& hidden_in, const Tensor& weight_in, int64_t top_k, bool norm_topk_prob,
@@ -1303,25 +1363,33 @@ std::tuple<Tensor, Tensor, Tensor> moe_router(const Tensor& hidden_in, const Ten
 {
     const at::ScalarType sdt = router_scores_dtype("moe_router", scores_dtype);
     router_check("moe_router", hidden_in, weight_in, top_k);
-    const int64_t T = hidden_in.size(0), E = weight_in.size(0);
-    if (T == 0)
-        return {torch::empty({0, E}, hidden_in.options()), torch::empty({0, top_k}, hidden_in.options().dtype(sdt)),
-                torch::empty({0, top_k}, hidden_in.options().dtype(at::kLong))};
-    c10::DeviceGuard guard(hidden_in.device());
-    const Tensor     hidden = hidden_in.detach().contiguous(), weight = weight_in.detach().contiguous();
-    RouterOut        r = router_launch(hidden, weight, top_k, norm_topk_prob, sdt, nullptr, stream_of(hidden_in));
+    const RouterOut r = router_op(hidden_in, weight_in, RouterRule{}, top_k, norm_topk_prob, sdt);
+    return {r.logits, r.scores, r.idx};
+}
+
+// DeepseekV3TopkRouter.forward on the device (extension): the reference's triple in the reference's order --
+// (router_logits fp32 [T, E], top_k_weights fp32 [T, k], top_k_index int64 [T, k]).
+std::tuple<Tensor, Tensor, Tensor> moe_router_sigmoid(const Tensor& hidden_in, const Tensor& weight_in, const Tensor& bias, int64_t top_k,
+                                                      int64_t n_group, int64_t topk_group, bool norm_topk_prob,
+                                                      double routed_scaling_factor)
+{
+    router_check("moe_router_sigmoid", hidden_in, weight_in, top_k);
+    const RouterRule rule = router_rule("moe_router_sigmoid", weight_in, bias, top_k, n_group, topk_group, routed_scaling_factor);
+    const RouterOut  r    = router_op(hidden_in, weight_in, rule, top_k, norm_topk_prob, at::kFloat);
     return {r.logits, r.scores, r.idx};
 }
 
 // The whole sparse MoE block (extension): router -> moe_experts on the stacks of w8_a16_moe (bits = 8) or w4_a16_moe
 // (bits = 4).  The same launches as those layers on the router's output, bit for bit; only the tables come from the router launch
 // (T <= 16: four launches in all) instead of a launch of their own.
-Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor& router_w, int64_t top_k, bool norm_topk_prob,
-                 const py::object& scores_dtype, const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s,
-                 const std::string& path)
+// `bias` defined: the sigmoid rule (fp32 weights; scores_dtype is not read), else the softmax rule.
+Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor& router_w, const Tensor& bias, int64_t n_group,
+                 int64_t topk_group, double scale, int64_t top_k, bool norm_topk_prob, const py::object& scores_dtype, const Tensor& gu_w,
+                 const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
 {
-    const at::ScalarType sdt = router_scores_dtype(fn, scores_dtype);
+    const at::ScalarType sdt = bias.defined() ? at::kFloat : router_scores_dtype(fn, scores_dtype);
     router_check(fn, hidden_in, router_w, top_k);
+    const RouterRule rule = bias.defined() ? router_rule(fn, router_w, bias, top_k, n_group, topk_group, scale) : RouterRule{};
     const MoeShape m = moe_stacks(fn, "hidden", hidden_in, gu_w, gu_s, dn_w, dn_s, bits);
     TORCH_CHECK(router_w.size(0) == m.E, fn, ": the router weight has ", router_w.size(0), " experts but the stacks have E = ", m.E);
     const int64_t T = hidden_in.size(0), S = T * top_k;
@@ -1330,7 +1398,7 @@ Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor
     if (T == 0) return out;
     const MoeSetup  c(hidden_in.detach(), MoeTables::alloc(m.E, S, hidden_in.device()), m.E, S);
     const Tensor    weight = router_w.detach().contiguous();
-    const RouterOut r = router_launch(c.hidden, weight, top_k, norm_topk_prob, sdt, &c.t, c.st);
+    const RouterOut r = router_launch(c.hidden, weight, rule, top_k, norm_topk_prob, sdt, &c.t, c.st);
     moe_experts(p, c, r.scores, m, gu_w, gu_s, dn_w, dn_s, out);
     return out;
 }
@@ -1338,13 +1406,35 @@ Tensor moe_block(const char* fn, int bits, const Tensor& hidden_in, const Tensor
 Tensor w8_a16_moe_block(const Tensor& hidden, const Tensor& router_weight, int64_t top_k, bool norm_topk_prob, const py::object& scores_dtype,
                         const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
 {
-    return moe_block("w8_a16_moe_block", 8, hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s, dn_w, dn_s, "auto");
+    return moe_block("w8_a16_moe_block", 8, hidden, router_weight, Tensor(), 1, 1, 1.0, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s,
+                     dn_w, dn_s, "auto");
 }
 
 Tensor w4_a16_moe_block(const Tensor& hidden, const Tensor& router_weight, int64_t top_k, bool norm_topk_prob, const py::object& scores_dtype,
                         const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
 {
-    return moe_block("w4_a16_moe_block", 4, hidden, router_weight, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s, dn_w, dn_s, path);
+    return moe_block("w4_a16_moe_block", 4, hidden, router_weight, Tensor(), 1, 1, 1.0, top_k, norm_topk_prob, scores_dtype, gu_w, gu_s,
+                     dn_w, dn_s, path);
+}
+
+// The DeepSeek-V3 family's routed half of the block: the sigmoid router in front of the same experts; the shared
+// expert stays the caller's.
+Tensor w8_a16_moe_block_sigmoid(const Tensor& hidden, const Tensor& router_weight, const Tensor& bias, int64_t top_k, int64_t n_group,
+                                int64_t topk_group, bool norm_topk_prob, double routed_scaling_factor, const Tensor& gu_w,
+                                const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s)
+{
+    TORCH_CHECK(bias.defined(), "w8_a16_moe_block_sigmoid: the correction bias is required");
+    return moe_block("w8_a16_moe_block_sigmoid", 8, hidden, router_weight, bias, n_group, topk_group, routed_scaling_factor, top_k,
+                     norm_topk_prob, py::none(), gu_w, gu_s, dn_w, dn_s, "auto");
+}
+
+Tensor w4_a16_moe_block_sigmoid(const Tensor& hidden, const Tensor& router_weight, const Tensor& bias, int64_t top_k, int64_t n_group,
+                                int64_t topk_group, bool norm_topk_prob, double routed_scaling_factor, const Tensor& gu_w,
+                                const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
+{
+    TORCH_CHECK(bias.defined(), "w4_a16_moe_block_sigmoid: the correction bias is required");
+    return moe_block("w4_a16_moe_block_sigmoid", 4, hidden, router_weight, bias, n_group, topk_group, routed_scaling_factor, top_k,
+                     norm_topk_prob, py::none(), gu_w, gu_s, dn_w, dn_s, path);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -1432,5 +1522,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("w4_a16_moe_block", &w4_a16_moe_block, "router + routed W4A16 experts: the whole sparse MoE block (inference only)",
           py::arg("hidden"), py::arg("router_weight"), py::arg("top_k"), py::arg("norm_topk_prob"), py::arg("scores_dtype"),
           py::arg("gate_up_qweight"), py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
+    m.def("moe_router_sigmoid", &moe_router_sigmoid,
+          "transformers' DeepseekV3TopkRouter forward on the device: (router_logits fp32 [T, E], top_k_weights fp32 [T, k], top_k_index "
+          "int64 [T, k])",
+          py::arg("hidden"), py::arg("weight"), py::arg("bias"), py::arg("top_k"), py::arg("n_group"), py::arg("topk_group"),
+          py::arg("norm_topk_prob"), py::arg("routed_scaling_factor"));
+    m.def("w8_a16_moe_block_sigmoid", &w8_a16_moe_block_sigmoid,
+          "sigmoid group-limited router + routed W8A16 experts (four launches at T <= 16; the shared expert is the caller's)",
+          py::arg("hidden"), py::arg("router_weight"), py::arg("bias"), py::arg("top_k"), py::arg("n_group"), py::arg("topk_group"),
+          py::arg("norm_topk_prob"), py::arg("routed_scaling_factor"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"));
+    m.def("w4_a16_moe_block_sigmoid", &w4_a16_moe_block_sigmoid,
+          "sigmoid group-limited router + routed W4A16 experts (inference only; the shared expert is the caller's)", py::arg("hidden"),
+          py::arg("router_weight"), py::arg("bias"), py::arg("top_k"), py::arg("n_group"), py::arg("topk_group"),
+          py::arg("norm_topk_prob"), py::arg("routed_scaling_factor"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
     m.attr("__eetq_amd_version__") = eetq_version();
 }

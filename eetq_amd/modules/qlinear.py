@@ -16,8 +16,9 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ..ops import (moe_router, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block, w8_a16_gemm, w8_a16_gemm_t,
-                   w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block, w8_a16_moe_train)
+from ..ops import (moe_router, moe_router_sigmoid, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block,
+                   w4_a16_moe_block_sigmoid, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
+                   w8_a16_moe_block_sigmoid, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
 __all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
@@ -321,9 +322,15 @@ class EetqTopKRouter(nn.Module):
 
     :meth:`from_router` converts a router in place and keeps it an instance of its original class.  When grad mode is on and
     ``hidden_states`` or ``weight`` requires grad, the call runs the original torch forward, so router training and the auxiliary
-    loss keep their autograd path; everything else needs fp16 GPU tensors, E <= 256, top_k <= 16 and H % 64 == 0."""
+    loss keep their autograd path; everything else needs fp16 GPU tensors, E <= 256, top_k <= 16 and H % 64 == 0.
 
-    CLASS_NAMES = ("MixtralTopKRouter", "Qwen2MoeTopKRouter", "Qwen3MoeTopKRouter", "OlmoeTopKRouter")
+    The sigmoid, bias-corrected, group-limited routers whose forward is DeepSeek-V3's program text -- ``SIGMOID_CLASS_NAMES`` -- are
+    adopted the same way, on ``ops.moe_router_sigmoid``: the return triple is theirs, ``(router_logits fp32 [T, E],
+    topk_weights fp32 [T, k], topk_indices int64 [T, k])``, and the ``e_score_correction_bias`` buffer stays where it is."""
+
+    SIGMOID_CLASS_NAMES = ("DeepseekV3TopkRouter", "DeepseekV32TopkRouter", "Glm4MoeTopkRouter", "Glm4MoeLiteTopkRouter",
+                           "Dots1TopkRouter", "SolarOpenTopkRouter")
+    CLASS_NAMES = ("MixtralTopKRouter", "Qwen2MoeTopKRouter", "Qwen3MoeTopKRouter", "OlmoeTopKRouter") + SIGMOID_CLASS_NAMES
     _adopted = {}
     _eetq_base = None
 
@@ -353,7 +360,34 @@ class EetqTopKRouter(nn.Module):
             return "the router kernel serves E <= 256 and top_k <= 16 (E = %d, top_k = %r)" % (E, k)
         if H % 64:
             return "the router kernel needs H %% 64 == 0 (H = %d)" % H
+        if type(module).__name__ in cls.SIGMOID_CLASS_NAMES:
+            return cls._sigmoid_unsupported_reason(module, E, k)
         return None
+
+    @staticmethod
+    def _sigmoid_unsupported_reason(module, E, k):
+        """the sigmoid routers are matched by name, so everything their forward reads is required here"""
+        missing = [a for a in ("num_group", "topk_group", "norm_topk_prob", "routed_scaling_factor", "e_score_correction_bias")
+                   if getattr(module, a, None) is None]
+        if missing:
+            return "no %s" % ", ".join(missing)
+        bias, G, KG = module.e_score_correction_bias, module.num_group, module.topk_group
+        if not isinstance(bias, torch.Tensor) or bias.shape != (E,) or bias.dtype not in (torch.float16, torch.float32):
+            return "e_score_correction_bias is not a float16 or float32 tensor [E]"
+        if not isinstance(G, int) or not isinstance(KG, int) or not 1 <= G <= 64 or E % G or (G > 1 and E // G < 2):
+            return ("the router kernel needs 1 <= n_group <= 64 dividing E into groups of at least two experts (E = %d, n_group = %r)"
+                    % (E, G))
+        if not 1 <= KG <= G or k > KG * (E // G):
+            return "the router kernel needs 1 <= topk_group <= n_group and top_k <= topk_group * E / n_group (topk_group = %r)" % (KG,)
+        scale = module.routed_scaling_factor
+        if not isinstance(scale, (int, float)) or scale != scale or scale in (float("inf"), float("-inf")):
+            return "routed_scaling_factor is not a finite number (%r)" % (scale,)
+        return None
+
+    @property
+    def is_sigmoid(self):
+        base = self._eetq_base
+        return base is not None and base.__name__ in self.SIGMOID_CLASS_NAMES
 
     @classmethod
     def from_router(cls, module):
@@ -370,7 +404,7 @@ class EetqTopKRouter(nn.Module):
     def scores_dtype(self, logits_dtype=torch.float16):
         base = self._eetq_base
         if base is not None:
-            return torch.float32 if base.__name__.startswith("Mixtral") else logits_dtype
+            return torch.float32 if base.__name__.startswith("Mixtral") or self.is_sigmoid else logits_dtype
         return self._scores_dtype if self._scores_dtype is not None else logits_dtype
 
     def falls_back(self, hidden_states):
@@ -391,7 +425,14 @@ class EetqTopKRouter(nn.Module):
         if self.falls_back(hidden_states):
             return self._torch_forward(hidden_states)
         with torch.no_grad():
+            if self.is_sigmoid:
+                return moe_router_sigmoid(hidden_states, self.weight, *self.sigmoid_args())
             return moe_router(hidden_states, self.weight, self.top_k, self.renormalises, self.scores_dtype())
+
+    def sigmoid_args(self):
+        """what ``ops.moe_router_sigmoid`` and the ``*_moe_block_sigmoid`` ops take after the router weight"""
+        return (self.e_score_correction_bias, self.top_k, self.num_group, self.topk_group, bool(self.norm_topk_prob),
+                float(self.routed_scaling_factor))
 
     def extra_repr(self):
         return "num_experts={}, hidden_dim={}, top_k={}".format(self.weight.shape[0], self.weight.shape[1], self.top_k)
@@ -410,9 +451,15 @@ class EetqSparseMoeBlock(nn.Module):
     keeps working: transformers records the router's output with a forward hook on the gate.  It installs ALL of a model's
     recording hooks, the gates' included, the first time ANY ``output_*`` flag (``output_router_logits``, ``output_hidden_states``,
     ``output_attentions``) is asked for, and never removes them: from that call on every block of that model stays on the unfused
-    path for the model's lifetime (the router swap still applies; :meth:`fused` tells)."""
+    path for the model's lifetime (the router swap still applies; :meth:`fused` tells).
 
-    CLASS_NAMES = ("MixtralSparseMoeBlock", "Qwen3MoeSparseMoeBlock", "OlmoeSparseMoeBlock")
+    ``SHARED_CLASS_NAMES`` are the blocks around the sigmoid routers, whose forward is
+    ``experts(x, *gate(x)[2:0:-1]) + shared_experts(x)``: fused, the routed half is ``ops.w8_a16_moe_block_sigmoid`` /
+    ``ops.w4_a16_moe_block_sigmoid`` and the shared expert (quantised linears already) is added in the original's operand order, so
+    the result is the bits of the unfused path.  Hooks observing ``shared_experts`` keep such a block unfused as well."""
+
+    SHARED_CLASS_NAMES = ("DeepseekV3MoE", "DeepseekV32MoE", "Glm4MoeMoE", "Glm4MoeLiteMoE", "Dots1MoE", "SolarOpenMoE")
+    CLASS_NAMES = ("MixtralSparseMoeBlock", "Qwen3MoeSparseMoeBlock", "OlmoeSparseMoeBlock") + SHARED_CLASS_NAMES
     _adopted = {}
     _eetq_base = None
 
@@ -427,6 +474,11 @@ class EetqSparseMoeBlock(nn.Module):
             return "its gate is not an EetqTopKRouter"
         if not isinstance(getattr(module, "experts", None), (W8A16Experts, W4A16Experts)):
             return "its experts are not quantised"
+        shared = type(module).__name__ in cls.SHARED_CLASS_NAMES
+        if shared != module.gate.is_sigmoid:
+            return "its gate's routing rule is not the one its forward expects"
+        if shared and not isinstance(getattr(module, "shared_experts", None), nn.Module):
+            return "no shared_experts module"
         return None
 
     @classmethod
@@ -445,6 +497,8 @@ class EetqSparseMoeBlock(nn.Module):
             return False
         if self.training and getattr(self, "jitter_noise", 0) > 0:
             return False
+        if gate.is_sigmoid and _observed(self.shared_experts):
+            return False
         return not (_observed(gate) or _observed(experts))
 
     def forward(self, hidden_states):
@@ -452,6 +506,12 @@ class EetqSparseMoeBlock(nn.Module):
             return self._eetq_base.forward(self, hidden_states)
         gate, experts = self.gate, self.experts
         flat = hidden_states.reshape(-1, hidden_states.shape[-1])
+        if gate.is_sigmoid:
+            args = (flat, gate.weight, *gate.sigmoid_args(), experts.gate_up_qweight, experts.gate_up_scales, experts.down_qweight,
+                    experts.down_scales)
+            with torch.no_grad():
+                out = w4_a16_moe_block_sigmoid(*args) if experts.bits == 4 else w8_a16_moe_block_sigmoid(*args)
+            return out.reshape(hidden_states.shape) + self.shared_experts(hidden_states)
         args = (flat, gate.weight, gate.top_k, gate.renormalises, gate.scores_dtype(), experts.gate_up_qweight, experts.gate_up_scales,
                 experts.down_qweight, experts.down_scales)
         with torch.no_grad():

@@ -27,7 +27,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block",
-           "w4_a16_moe_block"]
+           "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
             LAYOUT_GFX950: LAYOUT_GFX950, LAYOUT_SM80: LAYOUT_SM80, LAYOUT_ROW_MAJOR: LAYOUT_ROW_MAJOR}
@@ -437,6 +437,26 @@ def w4_a16_moe_block(hidden, router_weight, top_k, norm_topk_prob, scores_dtype,
                      down_scales, path="auto"):
     """The whole sparse MoE block on int4 experts: compiled module only, like :func:`w8_a16_moe`."""
     raise RuntimeError("eetq_amd: w4_a16_moe_block needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
+
+
+def moe_router_sigmoid(hidden, weight, bias, top_k, n_group, topk_group, norm_topk_prob, routed_scaling_factor):
+    """The sigmoid, group-limited device router: compiled module only, like :func:`moe_router`."""
+    raise RuntimeError("eetq_amd: moe_router_sigmoid needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
+
+
+def w8_a16_moe_block_sigmoid(hidden, router_weight, bias, top_k, n_group, topk_group, norm_topk_prob, routed_scaling_factor,
+                             gate_up_qweight, gate_up_scales, down_qweight, down_scales):
+    """The sigmoid router in front of int8 experts: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w8_a16_moe_block_sigmoid needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not provide it")
+
+
+def w4_a16_moe_block_sigmoid(hidden, router_weight, bias, top_k, n_group, topk_group, norm_topk_prob, routed_scaling_factor,
+                             gate_up_qweight, gate_up_scales, down_qweight, down_scales, path="auto"):
+    """The sigmoid router in front of int4 experts: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w4_a16_moe_block_sigmoid needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
                        "the ctypes binding does not provide it")
 
 

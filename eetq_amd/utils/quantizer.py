@@ -118,9 +118,14 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     the device kernel: every ``MixtralTopKRouter`` / ``Qwen2MoeTopKRouter`` / ``Qwen3MoeTopKRouter`` /
     ``OlmoeTopKRouter`` becomes an :class:`EetqTopKRouter`, and every ``MixtralSparseMoeBlock`` / ``Qwen3MoeSparseMoeBlock`` /
     ``OlmoeSparseMoeBlock`` whose experts were quantised an :class:`EetqSparseMoeBlock` (the whole block in four launches at
-    T <= 16).  Both are converted in place: parameters, state-dict keys and submodule names stay.  Other blocks (a shared expert,
-    sigmoid or group-limited routing, anything unknown) keep their block and get the router swap if their router is on the list;
-    a quantised block whose router is not is named in the same warning as the experts left in fp16.
+    T <= 16).  So do the sigmoid, bias-corrected, group-limited routers with DeepSeek-V3's forward --
+    ``DeepseekV3TopkRouter`` / ``DeepseekV32TopkRouter`` / ``Glm4MoeTopkRouter`` / ``Glm4MoeLiteTopkRouter`` / ``Dots1TopkRouter`` /
+    ``SolarOpenTopkRouter`` -- and the blocks around them, ``DeepseekV3MoE`` / ``DeepseekV32MoE`` / ``Glm4MoeMoE`` /
+    ``Glm4MoeLiteMoE`` / ``Dots1MoE`` / ``SolarOpenMoE`` (the routed half in four launches, then the shared expert).  All are
+    converted in place: parameters, buffers, state-dict keys and submodule names stay.  Other blocks (Qwen2-MoE's gated shared
+    expert, other variants of bias-corrected routing, anything unknown) keep their block and get the router swap if their router is on
+    the list; a quantised block whose router is not, or whose router's configuration the kernel does not serve, is named in the
+    same warning as the experts left in fp16.
     """
     if expert_bits not in (8, 4):
         raise ValueError("eet_quantize: expert_bits must be 8 or 4 (got %r)" % (expert_bits,))

@@ -355,6 +355,32 @@ int eetq_moe_router_f16(const void* x, const void* w, int T, int H, int E, int k
 int eetq_moe_topk_f16(const void* logits, int T, int E, int k, int renorm, int w_dtype, int64_t* top_k_index, void* top_k_weights,
                       void* stream);
 
+/* ---- the sigmoid, bias-corrected, group-limited router (extension, additive within ABI revision 7) --------------
+ * The forward of transformers' DeepseekV3TopkRouter (source-identical in DeepseekV32, Glm4Moe, Glm4MoeLite, Dots1 and SolarOpen): two
+ * fp32 casts, F.linear, sigmoid, bias add, per-group top-2 sums, group top-k, mask, expert top-k, gather, sum, div, mul.  Numerics:
+ *   logit[t][e] = sum_h fp32(x[t][h]) * fp32(w[e][h]): fp32 accumulation in eetq_moe_router_f16's fixed order, NOT rounded to fp16;
+ *   s = 1 / (1 + exp(-logit)), c = s + fp32(bias[e]) in fp32; bias (e_score_correction_bias [E]) is bias_dtype EETQ_DTYPE_F16 or _F32;
+ *   n_group contiguous groups of E / n_group experts score the sum of their two largest c; the topk_group best stay, ties to the lower
+ *     group id (n_group = 1: no group limiting);
+ *   selection: the k largest c among the experts of the kept groups, ties to the lower expert id, in descending order of c;
+ *   weights: s[id_j] (without the bias); renorm = 1 divides by (their sum, added in selection order, + 1e-20); then * scale (the
+ *     routed_scaling_factor); written as w_dtype EETQ_DTYPE_F32, or EETQ_DTYPE_F16 = the rounding of the fp32 result.
+ *
+ * eetq_moe_router_sigmoid_f16: x fp16 [T][H], w fp16 [E][H] (16-byte aligned) -> logits_out_f32 float [T][E], top_k_index, top_k_weights
+ *   and the tables, as eetq_moe_router_f16: ONE launch at T <= 16 (the same hand-over scratch and slot), above it the logits kernel
+ *   per 16 tokens, eetq_moe_topk_sigmoid_f32 and (with tables) eetq_moe_route.  Limits of eetq_moe_router_f16, and 1 <= n_group <= 64,
+ *   E % n_group == 0, E / n_group >= 2 when n_group > 1, 1 <= topk_group <= n_group, k <= topk_group * E / n_group, scale finite.
+ *   E > 256, k > 16 or n_group > 64: EETQ_ERR_UNSUPPORTED; anything else out of range, a null pointer, a bias_dtype other than the two:
+ *   EETQ_ERR_INVALID.  Every check runs before any device work.
+ * eetq_moe_topk_sigmoid_f32: the selection and the weights alone, from logits float [T][E]: one wave per token, the device code of the
+ *   fused launch (the same bits from the same logits). */
+int eetq_moe_router_sigmoid_f16(const void* x, const void* w, const void* bias, int bias_dtype, int T, int H, int E, int k, int n_group,
+                                int topk_group, int renorm, float scale, int w_dtype, void* logits_out_f32, int64_t* top_k_index,
+                                void* top_k_weights, int* counts, int* offsets, int* sorted_slot, int* position, int* active,
+                                void* stream);
+int eetq_moe_topk_sigmoid_f32(const void* logits, const void* bias, int bias_dtype, int T, int E, int k, int n_group, int topk_group,
+                              int renorm, float scale, int w_dtype, int64_t* top_k_index, void* top_k_weights, void* stream);
+
 /* ---- mixture-of-experts backward (extension, additive within ABI revision 7) --------------------------------
  * The input and router-weight gradients of the layer above with its int8 weights frozen (no weight gradients), on the tables
  * eetq_moe_route wrote and the sorted rows the forward kept.  Grids fixed by the shapes, no host sync, no atomics: deterministic

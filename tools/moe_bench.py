@@ -38,6 +38,10 @@ child process per plan (EETQ_AMD_TUNING=1 EETQ_AMD_MOE_I4_PLAN=<waves>x<depth>, 
 (profiles/r10_moe_int4_plans.jsonl also holds 8x1, 4x2, 6x1 and 3x2: instantiations that lost or tied in that sweep and were
 deleted after it; the sweep now covers the ones that are left.)
 
+--block --shapes deepseek-v3 --tokens 1,4,16,64 is the same comparison under the sigmoid, bias-corrected, group-limited
+rule at DeepSeek-V3's sizes (H 7168, I 2048, E 256, k 8, 8 groups, 4 kept): DeepseekV3TopkRouter's forward op for op followed by
+w8_a16_moe / w4_a16_moe against ops.w8_a16_moe_block_sigmoid / w4_a16_moe_block_sigmoid, and the formula against ops.moe_router_sigmoid.
+
 --block times the whole sparse block at --tokens (default 1,4,16,64,512), int8 or int4 experts (--bits): (a) the
 sequence before the device router -- the transformers router formula in torch (F.linear, softmax(float), topk, sum, div, .to) followed
 by w8_a16_moe / w4_a16_moe -- against (b) ops.w8_a16_moe_block / w4_a16_moe_block; the router formula alone against ops.moe_router;
@@ -59,6 +63,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = {"mixtral-8x7b": (4096, 14336, 8, 2), "qwen3-30b-a3b": (2048, 768, 128, 8)}
+# --block only (asked for by name): the sigmoid, group-limited rule; name -> (H, I, E, k), (n_group, topk_group, scale)
+SIGMOID_SHAPES = {"deepseek-v3": ((7168, 2048, 256, 8), (8, 4, 2.5))}
 DEV = "cuda:0"
 
 
@@ -330,7 +336,8 @@ def block(args, out):
     from eetq_amd import _lib, ops
     lib = _lib.lib()
     for name in args.shapes.split(","):
-        H, I, E, k = SHAPES[name]
+        sigmoid = SIGMOID_SHAPES.get(name)
+        H, I, E, k = sigmoid[0] if sigmoid else SHAPES[name]
         torch.manual_seed(0)
         pack = 2 if args.bits == 4 else 1
         gu_w = torch.randint(-127, 128, (E, H, 2 * I // pack), dtype=torch.int8, device=DEV)
@@ -350,6 +357,28 @@ def block(args, out):
             top /= top.sum(dim=-1, keepdim=True)
             return logits, top.to(sdt), idx
 
+        if sigmoid:
+            G, KG, scale = sigmoid[1]
+            sdt = torch.float32
+            bias = (torch.rand(E, device=DEV) * 0.5 - 0.25).half()
+            rule = (bias, k, G, KG, True, scale)
+            block_op = ops.w4_a16_moe_block_sigmoid if args.bits == 4 else ops.w8_a16_moe_block_sigmoid
+
+            def torch_router(x):  # noqa: F811 -- DeepseekV3TopkRouter.forward, op for op
+                logits = F.linear(x.type(torch.float32), wr.type(torch.float32))
+                scores = logits.sigmoid()
+                choice = scores + bias
+                group_scores = choice.view(-1, G, E // G).topk(2, dim=-1)[0].sum(dim=-1)
+                group_idx = torch.topk(group_scores, k=KG, dim=-1, sorted=False)[1]
+                group_mask = torch.zeros_like(group_scores)
+                group_mask.scatter_(1, group_idx, 1)
+                score_mask = group_mask.unsqueeze(-1).expand(-1, G, E // G).reshape(-1, E)
+                choice = choice.masked_fill(~score_mask.bool(), float("-inf"))
+                idx = torch.topk(choice, k=k, dim=-1, sorted=False)[1]
+                top = scores.gather(1, idx)
+                top /= top.sum(dim=-1, keepdim=True) + 1e-20
+                return logits, top * scale, idx
+
         for T in (int(t) for t in args.tokens.split(",")):
             x = torch.randn(T, H, device=DEV).half()
 
@@ -358,11 +387,13 @@ def block(args, out):
                 return layer(x, idx, sc, *stacks)
 
             def after():
-                return block_op(x, wr, k, True, sdt, *stacks)
+                return block_op(x, wr, *rule, *stacks) if sigmoid else block_op(x, wr, k, True, sdt, *stacks)
 
-            cases = {"before": before, "after": after, "router_torch": lambda: torch_router(x),
-                     "router_op": lambda: ops.moe_router(x, wr, k, True, sdt)}
-            if T <= 16:
+            def router_op():
+                return ops.moe_router_sigmoid(x, wr, *rule) if sigmoid else ops.moe_router(x, wr, k, True, sdt)
+
+            cases = {"before": before, "after": after, "router_torch": lambda: torch_router(x), "router_op": router_op}
+            if T <= 16 and not sigmoid:
                 S, A = T * k, min(E, T * k)
                 lg = torch.empty(T, E, dtype=torch.float16, device=DEV)
                 ix = torch.zeros(T, k, dtype=torch.int64, device=DEV)
@@ -374,7 +405,7 @@ def block(args, out):
                     _ptr(x), _ptr(wr), T, H, E, k, 1, dt, _ptr(lg), _ptr(ix), _ptr(sc), *[_ptr(t) for t in tb], st)
                 cases["route_launch"] = lambda: lib.eetq_moe_route(_ptr(ix), T, k, E, *[_ptr(t) for t in tb], st)
             with torch.no_grad():
-                assert torch.equal(after(), layer(x, *ops.moe_router(x, wr, k, True, sdt)[2:0:-1], *stacks))
+                assert torch.equal(after(), layer(x, *router_op()[2:0:-1], *stacks))
                 rec = {"shape": name, "bits": args.bits, "T": T, "H": H, "I": I, "E": E, "k": k, "iters": args.iters}
                 for tag, fn in cases.items():
                     for mode, f in (("eager", fn), ("graph", _graphed(fn) if "launch" not in tag else None)):

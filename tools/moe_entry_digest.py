@@ -5,7 +5,7 @@
 Every op is called twice -- a warm-up call, then the call whose outputs are hashed.  Two builds of eetq_amd/csrc/torch_ext.cpp that
 print the same lines compute the same bits on every path the module can take: decode and tiled grouped kernels, the int4 expansion,
 the quiet fall-back of a shape the tiled kernel refuses, the trainable forward and its backward, the device router below and above
-T = 16 and both block ops.  Under `rocprofv3 --kernel-trace --stats -- python tools/moe_entry_digest.py` the same run gives the
+T = 16, both block ops and, last, the sigmoid rule's router and block ops.  Under `rocprofv3 --kernel-trace --stats -- python tools/moe_entry_digest.py` the same run gives the
 kernels each call launches.  Needs an MI355X.
 
     python tools/moe_entry_digest.py > digest.txt
@@ -91,6 +91,17 @@ def main():
             assert ops.w4_a16_moe_path(127, K_TOP, E, H, I) == "decode"
             x, idx, wts, _ = _inputs(128, H, g)
             _emit("w4_a16_moe", 4, 128, "auto", lambda: ops.w4_a16_moe(x, idx, wts, *s4), ["out"])
+        # the sigmoid, group-limited rule, drawn after everything above: 2 groups of 2 experts, 1 kept
+        H = I = 384
+        s8, s4 = _stacks(8, H, I, g), _stacks(4, H, I, g)
+        wr = (torch.randn(E, H, generator=g) / H ** 0.5).half().to(DEV)
+        bias = (torch.rand(E, generator=g) * 0.5 - 0.25).half().to(DEV)
+        rule = (bias, K_TOP, 2, 1, True, 2.5)
+        for T in (3, 40):
+            x = _inputs(T, H, g)[0]
+            _emit("moe_router_sigmoid", "-", T, "auto", lambda: ops.moe_router_sigmoid(x, wr, *rule), ["logits", "weights", "idx"])
+            _emit("w8_a16_moe_block_sigmoid", 8, T, "auto", lambda: ops.w8_a16_moe_block_sigmoid(x, wr, *rule, *s8), ["out"])
+            _emit("w4_a16_moe_block_sigmoid", 4, T, "auto", lambda: ops.w4_a16_moe_block_sigmoid(x, wr, *rule, *s4), ["out"])
 
 
 if __name__ == "__main__":
