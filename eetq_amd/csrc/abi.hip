@@ -122,6 +122,9 @@ int eetq::device_cu_count()
 namespace eetq {
 int launch_greedy_handover(const f16* logits, long row_stride, int vocab, int batch, int64_t* out_buf, long out_stride, int out_cols,
                            int64_t* s_idx, int64_t* s_tok, int64_t* s_pos, hipStream_t stream);  // norm_rope.hip
+int launch_sample_handover(const f16* logits, long row_stride, int vocab, int batch, int64_t* out_buf, long out_stride, int out_cols,
+                           int64_t* s_idx, int64_t* s_tok, int64_t* s_pos, const void* params, int* done, const float* uniforms,
+                           hipStream_t stream);  // sample.hip
 }
 
 extern "C" {
@@ -744,6 +747,14 @@ int eetq_greedy_handover_f16(const void* logits, long row_stride, int vocab, int
 {
     return eetq::launch_greedy_handover(static_cast<const f16*>(logits), row_stride, vocab, batch, out_tokens, out_stride, out_cols,
                                         column, next_token, position, static_cast<hipStream_t>(stream));
+}
+
+int eetq_sample_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
+                             int out_cols, int64_t* column, int64_t* next_token, int64_t* position, const void* params,
+                             int32_t* done, const float* uniforms, void* stream)
+{
+    return eetq::launch_sample_handover(static_cast<const f16*>(logits), row_stride, vocab, batch, out_tokens, out_stride, out_cols,
+                                        column, next_token, position, params, done, uniforms, static_cast<hipStream_t>(stream));
 }
 
 int eetq_rope_decode_attention_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,

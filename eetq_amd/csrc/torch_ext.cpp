@@ -644,6 +644,38 @@ void greedy_handover(const Tensor& logits, Tensor& out_tokens, Tensor& column, T
                                    next_token.data_ptr<int64_t>(), position.data_ptr<int64_t>(), stream_of(logits)));
 }
 
+// Sampling decode hand-over (extension): greedy_handover's bookkeeping with the token drawn by temperature / top-k / top-p sampling
+// from a 32-byte device parameter block (int32[8]: eetq_amd.sampling.sampling_params), EOS flags `done` (int32 [B]) and, for
+// tests, explicit random numbers `uniforms` (float32 [B]) instead of the kernel's Philox stream (eetq_sample_handover_f16)
+void sample_handover(const Tensor& logits, Tensor& out_tokens, Tensor& column, Tensor& next_token, Tensor& position,
+                     const Tensor& params, const OptTensor& done, const OptTensor& uniforms)
+{
+    const char* name = "sample_handover: ";
+    TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kHalf && logits.dim() == 2 && logits.stride(1) == 1, name,
+                "logits must be a float16 CUDA tensor [B, V] with dense rows");
+    const int64_t B = logits.size(0), V = logits.size(1);
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&out_tokens, &column, &next_token, &position})
+        TORCH_CHECK(t->scalar_type() == at::kLong && t->device() == logits.device(), name, "int64 tensors on the logits' device expected");
+    TORCH_CHECK(out_tokens.dim() == 2 && out_tokens.size(0) == B && out_tokens.stride(1) == 1 && next_token.numel() == B &&
+                    next_token.is_contiguous() && column.numel() == 1 && position.numel() == 1 && V > 0,
+                name, "shape mismatch");
+    TORCH_CHECK(params.scalar_type() == at::kInt && params.numel() == 8 && params.is_contiguous() && params.device() == logits.device(),
+                name, "params must be a contiguous int32[8] tensor on the logits' device (sampling_params)");
+    if (done)
+        TORCH_CHECK(done->scalar_type() == at::kInt && done->numel() == B && done->is_contiguous() && done->device() == logits.device(),
+                    name, "done must be a contiguous int32 [B] tensor on the logits' device");
+    if (uniforms)
+        TORCH_CHECK(uniforms->scalar_type() == at::kFloat && uniforms->numel() == B && uniforms->is_contiguous() &&
+                        uniforms->device() == logits.device(),
+                    name, "uniforms must be a contiguous float32 [B] tensor on the logits' device");
+    c10::DeviceGuard guard(logits.device());
+    check(eetq_sample_handover_f16(logits.data_ptr(), (long)logits.stride(0), (int)V, (int)B, out_tokens.data_ptr<int64_t>(),
+                                   (long)out_tokens.stride(0), (int)out_tokens.size(1), column.data_ptr<int64_t>(),
+                                   next_token.data_ptr<int64_t>(), position.data_ptr<int64_t>(), params.data_ptr(),
+                                   done ? done->data_ptr<int32_t>() : nullptr, uniforms ? uniforms->data_ptr<float>() : nullptr,
+                                   stream_of(logits)));
+}
+
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
                         int64_t kv_len_bias, const OptTensor& advance)
@@ -1470,6 +1502,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("first_row_dev") = py::none());
     m.def("greedy_handover", &greedy_handover, "argmax + token hand-over of a greedy decode step", py::arg("logits"),
           py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"));
+    m.def("sample_handover", &sample_handover, "temperature / top-k / top-p sampling + token hand-over of a decode step",
+          py::arg("logits"), py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"), py::arg("params"),
+          py::arg("done") = py::none(), py::arg("uniforms") = py::none());
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,

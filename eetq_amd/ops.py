@@ -39,6 +39,7 @@ if _C is not None:
     rotary_embedding_neox_kvcache = _C.rotary_embedding_neox_kvcache
     rotary_embedding_neox_kvcache_prefill = _C.rotary_embedding_neox_kvcache_prefill
     greedy_handover = _C.greedy_handover
+    sample_handover = _C.sample_handover
     decode_attention = _C.decode_attention
     rope_decode_attention = _C.rope_decode_attention
     silu_mul = _C.silu_mul
@@ -65,16 +66,18 @@ else:
                              unprocess_weights, w4_a16_moe, w4_a16_moe_path, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t,
                              w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, moe_router,
                              w8_a16_moe_block, w4_a16_moe_block, moe_router_sigmoid, w8_a16_moe_block_sigmoid,
-                             w4_a16_moe_block_sigmoid)
+                             w4_a16_moe_block_sigmoid, sample_handover)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
-           "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
+           "greedy_handover", "sample_handover", "sampling_params", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]
+
+from .sampling import sampling_params  # noqa: E402  (plain Python, shared by both bindings)
 
 
 def decode_dropped_steps(reset=True, device=None):

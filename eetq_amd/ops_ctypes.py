@@ -25,7 +25,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
                    LAYOUT_SM80, PATH_AUTO, PATH_GEMV, PATH_MFMA, check)
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
-           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
+           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
@@ -802,6 +802,39 @@ def greedy_handover(logits, out_tokens, column, next_token, position):
         check(_lib.lib().eetq_greedy_handover_f16(_ptr(logits), logits.stride(0), V, B, _ptr(out_tokens), out_tokens.stride(0),
                                                   out_tokens.shape[1], _ptr(column), _ptr(next_token), _ptr(position),
                                                   _stream_ptr()))
+    return None
+
+
+@_eager_only
+def sample_handover(logits, out_tokens, column, next_token, position, params, done=None, uniforms=None):
+    """Sampling decode hand-over in one launch: ``greedy_handover``'s bookkeeping with the token of each row of ``logits`` [B, V]
+    (fp16) drawn by temperature / top-k / top-p sampling.  ``params``: the int32[8] device block of
+    ``eetq_amd.sampling.sampling_params``; ``done``: int32 [B] EOS flags (a finished row hands on the pad token; a row that draws
+    the EOS token is flagged); ``uniforms``: float32 [B] random numbers in [0, 1) instead of the kernel's Philox stream.
+    (eetq_sample_handover_f16)"""
+    name = "sample_handover: "
+    if not logits.is_cuda or logits.dtype != torch.float16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError(name + "logits must be a float16 CUDA tensor [B, V] with dense rows")
+    B, V = logits.shape
+    for t in (out_tokens, column, next_token, position):
+        if t.dtype != torch.int64 or t.device != logits.device:
+            raise RuntimeError(name + "int64 tensors on the logits' device expected")
+    if (out_tokens.dim() != 2 or out_tokens.shape[0] != B or out_tokens.stride(1) != 1 or next_token.numel() != B
+            or not next_token.is_contiguous() or column.numel() != 1 or position.numel() != 1 or V <= 0):
+        raise RuntimeError(name + "shape mismatch")
+    if params.dtype != torch.int32 or params.numel() != 8 or not params.is_contiguous() or params.device != logits.device:
+        raise RuntimeError(name + "params must be a contiguous int32[8] tensor on the logits' device (sampling_params)")
+    if done is not None and (done.dtype != torch.int32 or done.numel() != B or not done.is_contiguous()
+                             or done.device != logits.device):
+        raise RuntimeError(name + "done must be a contiguous int32 [B] tensor on the logits' device")
+    if uniforms is not None and (uniforms.dtype != torch.float32 or uniforms.numel() != B or not uniforms.is_contiguous()
+                                 or uniforms.device != logits.device):
+        raise RuntimeError(name + "uniforms must be a contiguous float32 [B] tensor on the logits' device")
+    with torch.cuda.device(logits.device):
+        check(_lib.lib().eetq_sample_handover_f16(_ptr(logits), logits.stride(0), V, B, _ptr(out_tokens), out_tokens.stride(0),
+                                                  out_tokens.shape[1], _ptr(column), _ptr(next_token), _ptr(position),
+                                                  _ptr(params), _ptr(done) if done is not None else None,
+                                                  _ptr(uniforms) if uniforms is not None else None, _stream_ptr()))
     return None
 
 

@@ -16,7 +16,7 @@ __all__ = ["GraphDecoder"]
 
 
 class GraphDecoder:
-    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7):
+    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -24,8 +24,13 @@ class GraphDecoder:
         hand-over between steps (next input id, position, the output row) is done by launches INSIDE the graphs, so a
         generated token costs the host one ``replay`` per ``steps_per_graph`` tokens and nothing else -- with one graph
         per token plus three eager bookkeeping launches the host side was 0.125 ms of every 2.96 ms token at 13B shapes
-        (``profiles/r06_bench_*.json``: decode_budget.step_us vs the end-to-end time)."""
+        (``profiles/r06_bench_*.json``: decode_budget.step_us vs the end-to-end time).
+        ``sampling``: the hand-over inside the graphs is ``ops.sample_handover`` on a static parameter block and static EOS
+        flags instead of the argmax: ``generate`` then takes ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` /
+        ``eos_token_id`` / ``pad_token_id`` per call, without recapture (needs fp16 logits on the GPU).  The default leaves
+        launches and tokens as they were."""
         self.lean = bool(lean)
+        self.sampling = bool(sampling)
         from transformers import StaticCache
         self.model = model
         self.batch = int(batch)
@@ -42,6 +47,11 @@ class GraphDecoder:
         # generated tokens: step i of a generate() writes column s_idx (a device counter the graphs advance themselves)
         self.s_idx = torch.zeros(1, 1, dtype=torch.long, device=dev)
         self.out_buf = torch.zeros(self.batch, self.max_len + 1, dtype=torch.long, device=dev)
+        self.params = self.done = None
+        if self.sampling:
+            from ..sampling import sampling_params
+            self.params = sampling_params(temperature=0.0, device=dev)
+            self.done = torch.zeros(self.batch, dtype=torch.int32, device=dev)   # per row: EOS drawn (readable after generate)
         self.graph = None
         self.graph_n = None
         # the prompt pass needs the LAST position's logits only (the stock forward projects all of them onto the vocabulary)
@@ -50,7 +60,10 @@ class GraphDecoder:
         self.steps_per_graph = max(1, int(steps_per_graph))
         with torch.no_grad():
             # the cache tensors are allocated lazily by the first forward: run one tiny prefill before capturing
-            model(self.s_tok, past_key_values=self.cache, cache_position=self.s_pos, use_cache=True)
+            first = model(self.s_tok, past_key_values=self.cache, cache_position=self.s_pos, use_cache=True)
+            if self.sampling and not (first.logits.is_cuda and first.logits.dtype == torch.float16):
+                raise ValueError("GraphDecoder: sampling=True needs float16 logits on the GPU (got %s on %s)"
+                                 % (first.logits.dtype, first.logits.device))
             if capture:
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
@@ -112,6 +125,11 @@ class GraphDecoder:
         input id; position and output column move on -- one library launch (``ops.greedy_handover``: torch.argmax's answer)
         where the logits are fp16 on the GPU, otherwise argmax + scatter_ + copy_ + two add_."""
         lg = self._logits()
+        if self.sampling:
+            from .. import ops
+            ops.sample_handover(lg if lg.stride(-1) == 1 else lg.contiguous(), self.out_buf, self.s_idx, self.s_tok, self.s_pos,
+                                self.params, self.done)
+            return
         if lg.is_cuda and lg.dtype == torch.float16 and lg.stride(-1) == 1:
             from .. import ops
             ops.greedy_handover(lg, self.out_buf, self.s_idx, self.s_tok, self.s_pos)
@@ -123,17 +141,38 @@ class GraphDecoder:
         self.s_idx.add_(1)
 
     @torch.no_grad()
-    def generate(self, prompt, new_tokens, return_prefill_logits=False):
-        """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens]."""
+    def generate(self, prompt, new_tokens, return_prefill_logits=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
+                 seed=0, eos_token_id=None, pad_token_id=None):
+        """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens].  On a decoder built with ``sampling=True``:
+        ``do_sample`` draws every token by temperature / top-k / top-p sampling (``seed``: the 64-bit Philox key; token i of
+        row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
+        finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on."""
         B, P = prompt.shape
         if B != self.batch or P + new_tokens > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))
-        out = self.prefill(prompt)
-        tok = out.logits[:, -1].argmax(-1, keepdim=True)
-        self.out_buf[:, :1].copy_(tok)
-        self.s_tok.copy_(tok)
-        self.s_pos.fill_(P)
-        self.s_idx.fill_(1)
+        if not self.sampling:
+            if (do_sample or temperature != 1.0 or top_k != 0 or top_p != 1.0 or seed != 0 or eos_token_id is not None
+                    or pad_token_id is not None):
+                raise ValueError("GraphDecoder: sampling and EOS arguments need a decoder built with sampling=True")
+            out = self.prefill(prompt)
+            tok = out.logits[:, -1].argmax(-1, keepdim=True)
+            self.out_buf[:, :1].copy_(tok)
+            self.s_tok.copy_(tok)
+            self.s_pos.fill_(P)
+            self.s_idx.fill_(1)
+        else:
+            from .. import ops
+            from ..sampling import sampling_params
+            sampling_params(temperature=float(temperature) if do_sample else 0.0, top_k=top_k, top_p=top_p, seed=seed,
+                            eos_token_id=eos_token_id, pad_token_id=0 if pad_token_id is None else pad_token_id, out=self.params)
+            self.done.zero_()
+            out = self.prefill(prompt)
+            # the first token: the same op on the prompt's logits at column 0 (it leaves position = P, column = 1)
+            self.s_pos.fill_(P - 1)
+            self.s_idx.fill_(0)
+            last = out.logits[:, -1]
+            ops.sample_handover(last if last.stride(-1) == 1 else last.contiguous(), self.out_buf, self.s_idx, self.s_tok, self.s_pos, self.params,
+                                self.done)
         left = new_tokens - 1
         while left > 0:
             if self.graph_n is not None and left >= self.steps_per_graph:

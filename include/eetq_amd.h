@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t.  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -440,6 +440,36 @@ int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, 
  * what a HIP-graph decode loop does between two model steps. */
 int eetq_greedy_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
                              int out_cols, int64_t* column, int64_t* next_token, int64_t* position, void* stream);
+
+/* Sampling decode hand-over (extension, added within ABI 7; what transformers' generate does with do_sample=True and an EOS
+ * token): the bookkeeping of eetq_greedy_handover_f16 -- token to out_tokens[b][*column] (skipped outside [0, out_cols), still
+ * handed on) and next_token[b], then *position += 1 and *column += 1; one launch, capturable, no host sync, no allocation -- with
+ * the token of a row chosen by temperature / top-k / top-p sampling.
+ *   params : DEVICE block of 32 bytes, 8-byte aligned, read by the kernel (a captured graph serves any setting):
+ *            float temperature (0 selects greedy; negative or NaN too), float top_p (>= 1, <= 0 or NaN: off), int32 top_k
+ *            (<= 0 or >= vocab: off), int32 eos_token (< 0: none), int32 pad_token, int32 reserved (0), uint64 seed.
+ *   done   : DEVICE int32[batch] or NULL.  A row with done[b] != 0 is not sampled: it writes and hands on pad_token.  A row whose
+ *            token equals eos_token writes that token and sets done[b] = 1.  NULL: no EOS handling.
+ *   uniforms: DEVICE float[batch] in [0, 1) or NULL: the row's random number u.  NULL: u = (x0 >> 8) * 2^-24 with
+ *            (x0, x1, x2, x3) = Philox4x32-10(counter = (col_lo, col_hi, b, 0), key = (seed_lo, seed_hi)), col = *column at entry:
+ *            no state is kept, and every replay of a captured graph draws afresh because the graph advances the column.
+ * The token of a row, deterministic given u:
+ *   temperature == 0: the token of eetq_greedy_handover_f16 (first index of the maximum, NaN = maximum).
+ *   otherwise: NaN counts as -inf; a maximum of +inf gives the first index holding +inf; nothing above -inf gives index 0;
+ *   z_i = float(logit_i) / temperature (order and ties: those of the fp16 logits); top-k (0 < k < vocab) keeps z_i >= the k-th
+ *   largest value, ties at the threshold included; top-p (0 < p < 1) walks the distinct values of the survivors in descending
+ *   order and keeps a value class iff the softmax mass of the strictly larger classes is < p (a tie is never cut: the whole
+ *   class stays); the survivors, ordered by value descending then index ascending and renormalised, are walked until the
+ *   cumulative probability exceeds u (none: the last survivor).  fp32 exponentials, integer (fixed-point) sums: every cumulative
+ *   sum compared against p or u is within 2^-14 absolute of exact arithmetic.  The token index is always < vocab.
+ * EETQ_ERR_INVALID (nothing launched): a null logits / out_tokens / column / next_token / position / params, vocab <= 0,
+ * batch < 0 or >= 2^24, row_stride < vocab, out_cols <= 0, out_stride < out_cols, params not 8-byte aligned.  batch == 0: OK, no
+ * launch.  One workgroup per row; the row that finishes last does the advance, counted in bits 40.. of *position for the length
+ * of the launch: -2^39 <= *position < 2^39 (outside it the counters do not advance), and nothing else may touch *position while
+ * the launch runs.  Rows of more than 2^23 entries are summed in 2^-32 instead of 2^-40 steps. */
+int eetq_sample_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
+                             int out_cols, int64_t* column, int64_t* next_token, int64_t* position, const void* params,
+                             int32_t* done, const float* uniforms, void* stream);
 
 /* Single-query (decode) attention over a KV cache; extension used by the EET attention blocks' decode step (the
  * reference delegates the attention product to flash-attn, python/eetq/modules/llama_modules.py:131-143).
