@@ -114,6 +114,8 @@ def _declare(L):
         "eetq_w4a16_moe_gemm": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
         "eetq_expand_i4_to_i8": [vp, vp, sz, vp],
         "eetq_w8a16_moe_gemm_tiled_supported": [i32, i32, i32, i32, i32, i32],
+        "eetq_w4a16_moe_gemm_tiled": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+        "eetq_w4a16_moe_gemm_tiled_supported": [i32, i32, i32, i32, i32, i32],
         "eetq_moe_router_f16": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "eetq_moe_topk_f16": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
         "eetq_moe_router_sigmoid_f16": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -146,6 +148,7 @@ EXPORTED_SYMBOLS = (
     "eetq_w8a16_moe_gemm_t", "eetq_moe_combine_bwd_f16", "eetq_silu_mul_glu8_bwd_f16",
     "eetq_w8a16_moe_gemm_tiled", "eetq_diag_moe_host_path",
     "eetq_w4a16_moe_gemm", "eetq_expand_i4_to_i8", "eetq_w8a16_moe_gemm_tiled_supported",
+    "eetq_w4a16_moe_gemm_tiled", "eetq_w4a16_moe_gemm_tiled_supported",
     "eetq_moe_router_f16", "eetq_moe_topk_f16", "eetq_moe_router_sigmoid_f16", "eetq_moe_topk_sigmoid_f32",
 )
 

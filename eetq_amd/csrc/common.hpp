@@ -272,6 +272,7 @@ int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const 
 // experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs the
 // decode kernel (moe_gemm_kernel.hpp)
 bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather);
+bool moe_tiled_narrow(int S, int E, int N);  // the launcher's tile rule: true = the 128 x 64 tile (shared with moe_int4_tiled.hip)
 int  launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
                            const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream);
 int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows, int cols, hipStream_t stream);

@@ -37,14 +37,15 @@ constexpr int kMinKSteps    = STAGES - 1;   // the statically unrolled drain nee
 // RB = 32-row-block multiplier per wave: RB = 2 is the DEEP tile, 256 x 128 on FOUR waves -- a wave owns 256 rows x 64 columns of
 // one K half (256 accumulators per lane, one wave per SIMD): every dequantised weight fragment feeds 8 MFMAs instead of 4, so the
 // dequant work and the weight reads per MFMA halve as well as the weight DMA.  Same stages, ring and epilogue phases as the tall tile.
-template <int J, int CW = 2, int RH = 1, int RB = 1>
+// BITS = 4 (grouped tile on an int4 expert stack, moe_int4_tiled.hip): a K step needs half an int4 tile per column tile, 512 bytes
+template <int J, int CW = 2, int RH = 1, int RB = 1, int BITS = 8>
 struct TileCfg {
     static constexpr int BN            = 32 * J * CW;
     static constexpr int WAVES         = 2 * CW * RH;
     static constexpr int ROWS          = BM * RH * RB;
     static constexpr int RING          = RH * RB == 2 ? 4 : STAGES;
     static constexpr int A_BYTES       = A_STAGE_BYTES * RH * RB;
-    static constexpr int B_STAGE_BYTES = BN * BK;  // BN/16 native 1 KiB tiles per K step
+    static constexpr int B_STAGE_BYTES = BN * BK * BITS / 8;  // BN/16 native 1 KiB tiles per K step (int4: BN/16 half tiles)
     static constexpr int STAGE_BYTES   = A_BYTES + B_STAGE_BYTES;
     static constexpr int SMEM_BYTES    = RING * STAGE_BYTES;  // 144 / 120 / 160 KiB (also covers the end-of-kernel reduction)
 };
@@ -83,6 +84,21 @@ __device__ __forceinline__ void dma16_imm(__amdgpu_buffer_rsrc_t rsrc, int voff,
 // 16-byte LDS read at an integer LDS address (the dynamic-LDS base is folded into the per-lane constants once)
 typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
 __device__ __forceinline__ u32x4 lds_read16(int addr) { return *(lds_cu32x4*)(uintptr_t)(uint32_t)addr; }
+// 8-byte form (the BITS = 4 weight fragment: two dwords = 16 k of one column)
+typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
+__device__ __forceinline__ u32x2 lds_read8(int addr) { return *(lds_cu32x2*)(uintptr_t)(uint32_t)addr; }
+
+// BITS = 4: two dwords of one column (k-locals 0..15: dword d = k 8 d .. 8 d + 7 at nibble positions [0, 4, 1, 5, 2, 6, 3, 7]) -> 8 fp16
+// pairs, fp16(q) * scale with one rounding: the value dequant_16 gives for the expanded int8 tile
+__device__ __forceinline__ void dequant_16_i4(const u32x2& w, f16x2 scale2, f16x2 (&out)[8])
+{
+    const f16x2 bias1032 = {(f16)1032.0f, (f16)1032.0f};
+#pragma unroll
+    for (int h = 0; h < 8; ++h) {
+        const u32 wdw = h < 4 ? w.x : w.y;
+        out[h]        = (as_f16x2(((wdw >> (4 * (h & 3))) & 0x000f000fu) | 0x64006400u) - bias1032) * scale2;
+    }
+}
 
 __device__ __forceinline__ f16x8 make_frag(f16x2 a, f16x2 b, f16x2 c, f16x2 d)
 {
@@ -126,7 +142,19 @@ __device__ __forceinline__ f16x8 make_frag(f16x2 a, f16x2 b, f16x2 c, f16x2 d)
 // tile) to the others -- no LDS, no barrier; a surplus slot leaves before its first DMA request.  Then M, m0, y, w and scales
 // are the expert's, and only the activation pieces' source rows differ from the ungrouped tile: sorted row p0 + m of x [S][K],
 // or (map.topk > 0) the token row sorted_slot[p0 + m] / topk of x [T][K]; the descriptor spans map.x_rows rows.
-template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, int RH = 1, int RB = 1, bool GROUPED = false>
+// BITS = 4 (moe_int4_tiled.hip): the grouped tile over an int4 expert stack w [E][K][N / 2].  Only the weight side
+// differs.  An int4 tile is 1 KiB = 16 columns x 128 k, lane g * 16 + c = k 32 g .. 32 g + 31 of column c, so K step kt needs chunks
+// g = 2 (kt & 1), 2 (kt & 1) + 1: the contiguous 512 bytes at kt * 512 of the column tile's row of tiles.  A stage holds BN / 16 such
+// half tiles; one wave DMA carries two of them (lanes 0..31 column tile 2 p, lanes 32..63 column tile 2 p + 1, each clamped to the
+// launch's last column tile).  J = 2: one piece per wave.  J = 1: the stage has two pieces; waves 2, 3 request the pieces of waves
+// 0, 1 again (same bytes to the same LDS addresses), which keeps the piece count -- and with it every counted vmcnt -- wave-uniform.
+// Wave (grp, wn), lane (fn, fh) reads the 8 bytes at tile * 512 + grp * 256 + (fn & 15) * 16 + fh * 8 = k 32 grp + 16 fh + [0, 16)
+// of its column; dword d holds k 8 d .. 8 d + 7 at nibble positions [0, 4, 1, 5, 2, 6, 3, 7], the operands of MFMA e = d -- the k
+// split of the int8 fragment.  ((w >> 4 i) & 0x000f000f) | 0x64006400 is the fp16 pair (k 2 i, 2 i + 1) + 1024; - 1032 and * scale are
+// separate packed ops (the int8 path's fp16(q) * s, one rounding: the same bits as expansion + the int8 tile).  The dequant fills
+// the int8 schedule's gaps: gap (jj, dword, kind) with kind = extract (three shifts, four and-or) / - 1032 / * scale.
+// K % 128 == 0 makes the K-step count even: only the tail == 6 drain exists.
+template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, int RH = 1, int RB = 1, bool GROUPED = false, int BITS = 8>
 __device__ __forceinline__ void gemm_tile_body(
     const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales,
     f16* __restrict__ y, int M, int N, int K, int ldc, Epilogue ep, int S, float* __restrict__ slabs,
@@ -134,13 +162,16 @@ __device__ __forceinline__ void gemm_tile_body(
 {
     static_assert(!GROUPED || (!SPLIT && !ACT && RH == 1 && RB == 1 && CW == 2 && ABLATE == 0),
                   "the grouped form exists for the unsplit 4-wave identity tile (plain and GLU)");
+    static_assert(BITS == 8 || (BITS == 4 && GROUPED), "int4 tiles: the grouped, unsplit, four-wave identity tile only");
     // N = columns of THIS launch (w, scales, y, ep.* already point at its first column); ldc = row stride of y / residual
     EETQ_GEMM_STAMP(0);
-    using Cfg = TileCfg<J, CW, RH, RB>;
+    using Cfg = TileCfg<J, CW, RH, RB, BITS>;
     constexpr int BN = Cfg::BN, STAGE_BYTES = Cfg::STAGE_BYTES, SMEM_BYTES = Cfg::SMEM_BYTES, NW = Cfg::WAVES;
     constexpr int ST = Cfg::RING, BMT = Cfg::ROWS, A_BYTES = Cfg::A_BYTES;
     constexpr int APW = 16 * RH * RB / NW;    // activation DMA pieces (8 rows each) per wave and stage: 4 or 2; 8 in the deep tile
-    constexpr int BPW = (BN / 16) / NW;       // weight tiles per wave and stage: J, or 1 in the tall tile
+    // weight tiles per wave and stage: J, or 1 in the tall tile; int4: one piece (two half tiles) per wave
+    constexpr int BPW = BITS == 4 ? 1 : (BN / 16) / NW;
+    constexpr int kStepBytesB = BITS == 4 ? kTileBytes / 2 : kTileBytes;  // weight source bytes per K step and column tile
     constexpr int WN_COLS = 32 * J, PIECES = APW + BPW, NMFMA = 8 * J * RB;
     constexpr int MT = 4 * RB;                // 32-row blocks per wave
     static_assert(J == 1 || J == 2, "slot tables exist for J = 1 and J = 2");
@@ -226,7 +257,8 @@ __device__ __forceinline__ void gemm_tile_body(
         M  = __builtin_amdgcn_readfirstlane(map.offsets[e + 1]) - p0;
         m0 = (slot - t0) * BM;
         y += (size_t)p0 * ldc;
-        w += (size_t)e * K * N;
+        if constexpr (BITS == 4) w += (size_t)e * K * N / 2;
+        else w += (size_t)e * K * N;
         scales += (size_t)e * N;
     }
 
@@ -236,7 +268,7 @@ __device__ __forceinline__ void gemm_tile_body(
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<uint8_t*>(const_cast<f16*>(x)) - kShift, 0, (int)((size_t)(GROUPED ? map.x_rows : M) * K * 2) + kShift, 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(w) - kShift, 0, (int)((size_t)N * K) + kShift, 0x00020000);
+        const_cast<uint8_t*>(w) - kShift, 0, (int)(BITS == 4 ? (size_t)N * K / 2 : (size_t)N * K) + kShift, 0x00020000);
     // DMA pieces of this wave: i < APW: activation piece APW*wave + i (rows 8p..8p+7, 128 B each); i >= APW: weight tile
     // J*wave + i - APW of the stage's BN/16
     int       dma_voff[PIECES];
@@ -256,12 +288,19 @@ __device__ __forceinline__ void gemm_tile_body(
     }
 #pragma unroll
     for (int i = APW; i < PIECES; ++i) {
+        if constexpr (BITS == 4) {  // piece bp: lanes 0..31 the half tile of column tile 2 bp, lanes 32..63 of column tile 2 bp + 1
+            const int bp = J == 2 ? wave : (wave & 1);
+            int       nt = (n0 >> 4) + 2 * bp + (lane >> 5);
+            nt           = nt < n_tiles_total ? nt : n_tiles_total - 1;
+            dma_voff[i]  = nt * (KT >> 1) * kTileBytes + (lane & 31) * 16 + kShift;
+        } else {
         int nt      = (n0 >> 4) + wave * BPW + (i - APW);
         nt          = nt < n_tiles_total ? nt : n_tiles_total - 1;
         dma_voff[i] = nt * KT * kTileBytes + lane * 16 + kShift - (i - APW) * 1024;
+        }
     }
     const int dma_lds_a = wave * APW * 1024;                  // + i * 1024
-    const int dma_lds_b = A_BYTES + wave * BPW * 1024;        // + (i - APW) * 1024
+    const int dma_lds_b = A_BYTES + (BITS == 4 ? (J == 2 ? wave : (wave & 1)) : wave * BPW) * 1024;  // + (i - APW) * 1024
 
     const int fn = lane & 31, fh = lane >> 5;
     const int a_key = (fn >> 1) & 7;
@@ -269,8 +308,9 @@ __device__ __forceinline__ void gemm_tile_body(
     const int lds0 = (int)(uint32_t)(uintptr_t)(lds_void*)smem;
     const int c_a0 = lds0 + rh * A_STAGE_BYTES + fn * 128 + (((4 * grp + 2 * fh + 0) ^ a_key) << 4);
     const int c_a1 = lds0 + rh * A_STAGE_BYTES + fn * 128 + (((4 * grp + 2 * fh + 1) ^ a_key) << 4);
-    const int c_b0 = lds0 + A_BYTES + ((wn * WN_COLS + fn) >> 4) * 1024 + (fn & 15) * 16 + fh * 256 + grp * 512;
-    const int c_b1 = c_b0 + 2048;
+    const int c_b0 = BITS == 4 ? lds0 + A_BYTES + ((wn * WN_COLS + fn) >> 4) * 512 + grp * 256 + (fn & 15) * 16 + fh * 8
+                               : lds0 + A_BYTES + ((wn * WN_COLS + fn) >> 4) * 1024 + (fn & 15) * 16 + fh * 256 + grp * 512;
+    const int c_b1 = c_b0 + (BITS == 4 ? 1024 : 2048);
 
     f16x2 scale2[J];
 #pragma unroll
@@ -288,17 +328,27 @@ __device__ __forceinline__ void gemm_tile_body(
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[mt][j][i] = 0.f;
 
+    using WQ = std::conditional_t<BITS == 4, u32x2, u32x4>;  // raw weight fragment of one column block: 16 k
+    auto wq_read = [](int addr) {
+        if constexpr (BITS == 4) return lds_read8(addr);
+        else return lds_read16(addr);
+    };
     struct Frags {
-        u32x4 wq[J];
+        WQ    wq[J];
         f16x8 xa[2][4];
     };
     struct WFrag {
         f16x8 f[J][2];
     };
 
+    // BITS = 4: the extraction's two constants in registers (an SGPR and a VGPR: one v_and_or_b32 per pair instead of an and and
+    // an or that each carry a 32-bit literal)
+    u32 nib_mask = 0x000f000fu, nib_exp = 0x64006400u;
+    if constexpr (BITS == 4) asm volatile("" : "+s"(nib_mask), "+v"(nib_exp));
+
     // ring state of the step about to run (wave-uniform): rd = LDS offset of the stage whose fragments it reads
     // (stage kt+1), wr = LDS offset its DMA fills (stage kt+5), ka / kb = source offsets of that stage
-    int rd = STAGE_BYTES, wr = (ST - 1) * STAGE_BYTES, ka = (k0 + ST - 1) * BK * 2, kb = (k0 + ST - 1) * kTileBytes;
+    int rd = STAGE_BYTES, wr = (ST - 1) * STAGE_BYTES, ka = (k0 + ST - 1) * BK * 2, kb = (k0 + ST - 1) * kStepBytesB;
     int ra0 = rd + c_a0, ra1 = rd + c_a1, rb0 = rd + c_b0, rb1 = rd + c_b1;
 
     auto dma_piece = [&](auto itag) {
@@ -322,8 +372,8 @@ __device__ __forceinline__ void gemm_tile_body(
             __builtin_amdgcn_sched_barrier(0);  // the MFMA opens its gap: dependent VALU ops of adjacent gaps never abut
             if constexpr (READ && !(ABLATE & 4)) {
                 if (i == 0) {
-                    fnext.wq[0] = lds_read16(rb0);
-                    if constexpr (J == 2) fnext.wq[1] = lds_read16(rb1);
+                    fnext.wq[0] = wq_read(rb0);
+                    if constexpr (J == 2) fnext.wq[1] = wq_read(rb1);
                 }
                 // activation fragments q = 4e + mt.  J = 2: gap 1: q0; 2: q1,q2; 3: q3; 4: q4; 6: q5; 7: q6; 9: q7.
                 // J = 1: two per gap in gaps 1..4.
@@ -350,6 +400,21 @@ __device__ __forceinline__ void gemm_tile_body(
                     // applies ONE kind of op (perm / -1152 / *scale) to its four half-dwords: four independent VALU
                     // ops per gap, dependent ops a gap apart (no hazard nops)
                     const int jj = (i - kDq0) / 6, dp = ((i - kDq0) / 3) & 1, kind = (i - kDq0) % 3;
+                    if constexpr (BITS == 4) {  // dword dp of the fragment = k 8 dp .. 8 dp + 7 -> half-dwords 4 dp .. 4 dp + 3
+                        const f16x2 bias1032 = {(f16)1032.0f, (f16)1032.0f};
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int h = 4 * dp + u;
+                            if (kind == 0) {
+                                const u32 wdw = dp == 0 ? fnext.wq[jj].x : fnext.wq[jj].y;
+                                wd[jj][h]     = ((wdw >> (4 * u)) & nib_mask) | nib_exp;
+                            } else if (kind == 1) {
+                                wd[jj][h] = as_u32(as_f16x2(wd[jj][h]) - bias1032);
+                            } else {
+                                wd[jj][h] = as_u32(as_f16x2(wd[jj][h]) * scale2[jj]);
+                            }
+                        }
+                    } else {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int h = 4 * dp + u, d = h >> 1;
@@ -364,6 +429,7 @@ __device__ __forceinline__ void gemm_tile_body(
                         } else {
                             wd[jj][h] = as_u32(as_f16x2(wd[jj][h]) * scale2[jj]);
                         }
+                    }
                     }
                     // pin the pure VALU ops to this gap (instruction selection would sink them to their uses); input-only
                     // operands: an asm with VGPR outputs costs a hazard pad (s_nop) before the next instruction
@@ -402,7 +468,7 @@ __device__ __forceinline__ void gemm_tile_body(
                 if (i == (J == 2 ? 13 : 6)) {
                     wr = wr + STAGE_BYTES == SMEM_BYTES ? 0 : wr + STAGE_BYTES;
                     ka += BK * 2;
-                    kb += kTileBytes;
+                    kb += kStepBytesB;
                     asm volatile("" : "+s"(wr), "+s"(ka), "+s"(kb));
                 }
                 if (i == (J == 2 ? 14 : 6)) {
@@ -443,6 +509,7 @@ __device__ __forceinline__ void gemm_tile_body(
     f16x8 xw[WIN];
     int   ca0 = c_a0, ca1 = c_a1;  // fragment addresses of the CURRENT stage (ra0 / ra1: the next one's)
     auto  step_tall = [&](const WFrag& wcur, auto read_tag, Frags& fnext, WFrag& wnext, auto dma_tag) {
+        if constexpr (RH * RB == 2) {  // (the body names int8 fragment members: not instantiated for any other tile)
         constexpr bool READ = decltype(read_tag)::value;
         constexpr bool DMA  = decltype(dma_tag)::value;
         u32            wd[J][8];
@@ -536,12 +603,13 @@ __device__ __forceinline__ void gemm_tile_body(
             }
             __builtin_amdgcn_s_waitcnt(0xC07F);
         }
+        }
     };
 
     // ---- prologue: STAGES-1 stages in flight; stage 0 -> fragments ----
     asm volatile("" ::"v"(scale2[0]));
     {
-        int pwr = 0, pka = k0 * BK * 2, pkb = k0 * kTileBytes;
+        int pwr = 0, pka = k0 * BK * 2, pkb = k0 * kStepBytesB;
 #pragma unroll
         for (int s = 0; s < ST - 1; ++s) {  // KT >= STAGES - 1 by launch contract
 #pragma unroll
@@ -553,7 +621,7 @@ __device__ __forceinline__ void gemm_tile_body(
             }
             pwr += STAGE_BYTES;
             pka += BK * 2;
-            pkb += kTileBytes;
+            pkb += kStepBytesB;
         }
     }
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * PIECES) : "memory");  // stage 0 landed
@@ -562,8 +630,8 @@ __device__ __forceinline__ void gemm_tile_body(
     Frags f0, f1;
     WFrag w0, w1;
     {
-        f0.wq[0] = lds_read16(c_b0);
-        if constexpr (J == 2) f0.wq[1] = lds_read16(c_b1);
+        f0.wq[0] = wq_read(c_b0);
+        if constexpr (J == 2) f0.wq[1] = wq_read(c_b1);
         if constexpr (RH * RB == 2) {  // the window's first pairs
 #pragma unroll
             for (int q = 0; q < DIST; ++q) xw[q] = __builtin_bit_cast(f16x8, lds_read16(c_a0 + q * 32 * 128));
@@ -577,7 +645,8 @@ __device__ __forceinline__ void gemm_tile_body(
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             f16x2 wdq[8];
-            dequant_16(f0.wq[j], scale2[j], wdq);
+            if constexpr (BITS == 4) dequant_16_i4(f0.wq[j], scale2[j], wdq);
+            else dequant_16(f0.wq[j], scale2[j], wdq);
             w0.f[j][0] = make_frag(wdq[0], wdq[1], wdq[2], wdq[3]);
             w0.f[j][1] = make_frag(wdq[4], wdq[5], wdq[6], wdq[7]);
         }
@@ -599,7 +668,7 @@ __device__ __forceinline__ void gemm_tile_body(
         }
     };
     using Steady = std::integral_constant<int, ST - 1>;
-    const int tail = (ksteps & 1) ? 5 : 6;
+    const int tail = BITS == 4 ? 6 : (ksteps & 1) ? 5 : 6;  // int4: K % 128 == 0, the K-step count is even
     int       kt   = 0;
     for (; kt < ksteps - tail; kt += 2) {
         k_step(Steady{}, w0, f0, w1, f1);

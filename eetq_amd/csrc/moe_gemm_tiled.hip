@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256, 1) void moe_gemm_tile_kernel(const f16* __rest
 // Which tile shape: the wide tile (128 x 128) is the efficient one when it fills the chip, the narrow one (128 x 64) doubles the
 // workgroups (launch_gemm_mfma's rule and its measured 0.70 cost ratio).  The counts live on the device, so the row tiles are
 // estimated from the shapes: min(E, S) experts with the mean S / min(E, S) rows each.
-static bool moe_tiled_narrow(int S, int E, int N)
+bool moe_tiled_narrow(int S, int E, int N)
 {
     const int    A     = S < E ? S : E;
     const int    mean  = (S + A - 1) / A;

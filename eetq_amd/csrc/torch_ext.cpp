@@ -967,12 +967,22 @@ bool moe_i4_tiled_takes(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
            eetq_w8a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)H, (int)I, 0) == 1;
 }
 
+// Where eetq_w4a16_moe_gemm_tiled takes BOTH projections on the int4 stacks themselves (the limits above with K % 128 == 0 and
+// K >= 384 for K = H and K = I)
+bool moe_i4_direct_takes(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    if (T < 1 || T * k > (int64_t(1) << 30)) return false;
+    return eetq_w4a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)(2 * I), (int)H, 1) == 1 &&
+           eetq_w4a16_moe_gemm_tiled_supported((int)T, (int)k, (int)E, (int)H, (int)I, 0) == 1;
+}
+
 // What serves one call of the layer: the stacks' format, and for BOTH projections the kernel.
 struct MoePlan {
     int  bits;    // 8 or 4
     bool tiled;   // eetq_w8a16_moe_gemm_tiled (128-row LDS tiles, the weight read once per 128 rows); else the decode kernel of `bits`
                   // (16-row MFMA tiles, the expert's weight tile row streamed once per 16 rows)
     bool expand;  // bits = 4 and tiled: eetq_expand_i4_to_i8 of the whole stack in front of each projection
+    bool direct;  // bits = 4 and tiled: eetq_w4a16_moe_gemm_tiled on the int4 stack itself -- no expansion, no [E, K, N] buffer
     bool host;    // the A/B host path instead of the grouped kernels
 };
 
@@ -1008,13 +1018,17 @@ constexpr int64_t kMoeTiledMinMeanRows = 16;
 constexpr int64_t kMoeI4ExpandMinMeanRows = 64;
 
 // `path` is the int4 ops' argument ("auto" everywhere else): "decode" and "expand" force one side of the int4 rule, "expand" only
-// where the tiled kernel takes both projections.  `caller_routed`: the routing is the caller's (w8_a16_moe, w8_a16_moe_train), which
+// where the tiled kernel takes both projections.  "direct" is the third int4 path: the tiled kernel on the int4 tiles
+// (eetq_w4a16_moe_gemm_tiled), bit for bit what "expand" computes without its 1.5 E K N bytes of traffic and its transient stack;
+// it raises where that kernel does not take both projections.  "auto" never picks it: its rule stays the measured one above until
+// the direct kernel's seam against the decode kernel is measured.  `caller_routed`: the routing is the caller's (w8_a16_moe, w8_a16_moe_train), which
 // is where the A/B host switch applies -- never to the block ops, whose tables come from the device router, and never to int4.
 MoePlan moe_plan(const char* fn, int bits, const std::string& path, int64_t T, int64_t k, int64_t E, int64_t H, int64_t I,
                  bool caller_routed)
 {
-    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand", fn, ": path must be 'auto', 'decode' or 'expand'");
-    MoePlan p{bits, false, false, false};
+    TORCH_CHECK(path == "auto" || path == "decode" || path == "expand" || (bits == 4 && path == "direct"), fn,
+                ": path must be 'auto', 'decode' or 'expand', or 'direct'");
+    MoePlan p{bits, false, false, false, false};
     if (T == 0) return p;  // nothing runs
     if (bits == 8) {
         p.host  = caller_routed && T > 16 && moe_host_path();
@@ -1023,10 +1037,21 @@ MoePlan moe_plan(const char* fn, int bits, const std::string& path, int64_t T, i
     }
     TORCH_CHECK(path != "expand" || moe_i4_tiled_takes(T, k, E, H, I),
                 fn, ": path='expand' needs a shape the grouped tiled kernel takes (H >= 320 and I >= 320)");
+    TORCH_CHECK(path != "direct" || moe_i4_direct_takes(T, k, E, H, I), fn,
+                ": path='direct' needs a shape the grouped int4 tiled kernel takes (H and I multiples of 128, both >= 384)");
+    p.direct = path == "direct";
     p.expand = path == "expand" ||
                (path == "auto" && T > 16 && T * k >= kMoeI4ExpandMinMeanRows * E && moe_i4_tiled_takes(T, k, E, H, I));
-    p.tiled = p.expand;
+    p.tiled = p.expand || p.direct;
     return p;
+}
+
+// 1 where w4_a16_moe(path="direct") runs for these sizes (both projections inside eetq_w4a16_moe_gemm_tiled_supported)
+bool w4_a16_moe_direct_supported(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
+{
+    TORCH_CHECK(T >= 0 && k >= 1 && E >= 1 && k <= E && H >= 1 && I >= 1,
+                "w4_a16_moe_direct_supported: T >= 0, 1 <= k <= E, H >= 1, I >= 1");
+    return E <= (int64_t(1) << 20) && H < (int64_t(1) << 31) && 2 * I < (int64_t(1) << 31) && moe_i4_direct_takes(T, k, E, H, I);
 }
 
 std::string w4_a16_moe_path(int64_t T, int64_t k, int64_t E, int64_t H, int64_t I)
@@ -1084,6 +1109,11 @@ void moe_combine(const Tensor& y, const int* position, const Tensor& wts, Tensor
 void moe_project(const MoePlan& p, const void* x, const Tensor& w, const Tensor& s, const MoeTables& t, void* y, int64_t T, int64_t k,
                  int64_t E, int64_t N, int64_t K, int gather, int glu8, void* st)
 {
+    if (p.direct) {  // moe_plan asked eetq_w4a16_moe_gemm_tiled_supported: UNSUPPORTED cannot come back
+        check(eetq_w4a16_moe_gemm_tiled(x, w.data_ptr<int8_t>(), s.data_ptr(), t.offsets, t.sorted, t.active, y, (int)T, (int)k, (int)E,
+                                        (int)N, (int)K, gather, glu8, /*tile_j*/ 0, st));
+        return;
+    }
     if (p.tiled) {
         Tensor w8;
         if (p.expand) {
@@ -1541,11 +1571,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("top_k_weights"), py::arg("tables"), py::arg("gate_up"), py::arg("y"), py::arg("gate_up_qweight"),
           py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("need_input_grad") = true,
           py::arg("need_weights_grad") = true);
-    m.def("w4_a16_moe", &w4_a16_moe, "routed W4A16 mixture-of-experts layer over int4 expert stacks (inference only)",
+    m.def("w4_a16_moe", &w4_a16_moe,
+          "routed W4A16 mixture-of-experts layer over int4 expert stacks (inference only); path: 'auto', 'decode', 'expand' or 'direct'",
           py::arg("hidden"), py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
           py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
     m.def("w4_a16_moe_path", &w4_a16_moe_path,
           "'decode' or 'expand': the grouped kernels w4_a16_moe(path='auto') runs for T tokens, k choices, E experts, H, I",
+          py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
+    m.def("w4_a16_moe_direct_supported", &w4_a16_moe_direct_supported,
+          "True where w4_a16_moe(path='direct') takes T tokens, k choices, E experts, H, I (the grouped int4 tiled kernel's limits)",
           py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));
     const py::object f32 = py::module_::import("torch").attr("float32");
     m.def("moe_router", &moe_router,
@@ -1554,7 +1588,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("w8_a16_moe_block", &w8_a16_moe_block, "router + routed W8A16 experts: the whole sparse MoE block (four launches at T <= 16)",
           py::arg("hidden"), py::arg("router_weight"), py::arg("top_k"), py::arg("norm_topk_prob"), py::arg("scores_dtype"),
           py::arg("gate_up_qweight"), py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"));
-    m.def("w4_a16_moe_block", &w4_a16_moe_block, "router + routed W4A16 experts: the whole sparse MoE block (inference only)",
+    m.def("w4_a16_moe_block", &w4_a16_moe_block,
+          "router + routed W4A16 experts: the whole sparse MoE block (inference only); path: 'auto', 'decode', 'expand' or 'direct'",
           py::arg("hidden"), py::arg("router_weight"), py::arg("top_k"), py::arg("norm_topk_prob"), py::arg("scores_dtype"),
           py::arg("gate_up_qweight"), py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
     m.def("moe_router_sigmoid", &moe_router_sigmoid,
@@ -1568,7 +1603,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("norm_topk_prob"), py::arg("routed_scaling_factor"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
           py::arg("down_qweight"), py::arg("down_scales"));
     m.def("w4_a16_moe_block_sigmoid", &w4_a16_moe_block_sigmoid,
-          "sigmoid group-limited router + routed W4A16 experts (inference only; the shared expert is the caller's)", py::arg("hidden"),
+          "sigmoid group-limited router + routed W4A16 experts (inference only; the shared expert is the caller's); path: 'auto', "
+          "'decode', 'expand' or 'direct'",
+          py::arg("hidden"),
           py::arg("router_weight"), py::arg("bias"), py::arg("top_k"), py::arg("n_group"), py::arg("topk_group"),
           py::arg("norm_topk_prob"), py::arg("routed_scaling_factor"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
           py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");

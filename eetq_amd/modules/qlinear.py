@@ -17,6 +17,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from ..ops import (moe_router, moe_router_sigmoid, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block,
+                   w4_a16_moe_direct_supported,
                    w4_a16_moe_block_sigmoid, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
                    w8_a16_moe_block_sigmoid, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
@@ -255,10 +256,29 @@ class W4A16Experts(_QuantExperts):
     ``gate_up_scales`` fp16 [E, 2I] (same order), ``down_qweight`` int8 [E, I, H / 2], ``down_scales`` fp16 [E, H].  Needs
     H % 128 == 0 and I % 128 == 0 (int4 tiles are 128 deep).  Runs ``ops.w4_a16_moe``.
 
+    ``prompt_path`` (a plain attribute, not a buffer: state dicts do not change; ``eet_quantize(..., expert_prompt_path=...)`` sets
+    it) chooses what serves prompts: ``"auto"``, the default, is the op's own rule (the decode kernel, or from 64 rows per expert
+    the expansion to int8 tiles); ``"direct"`` sends a call with T > 16, T k >= 16 E (the int8 layer's seam) and both projections
+    inside ``ops.w4_a16_moe_direct_supported`` to the grouped tiled kernel on the int4 tiles themselves -- the bits of the expanded
+    path, no [E, K, N] buffer -- and every other call to the decode kernel; the expansion is never used in this mode.
+
     Inference only: there is no int4 backward, the module has no ``trainable`` flag and ``utils.set_trainable`` passes it by;
     its output is always detached.  State dicts hold the four buffers as they are, like :class:`W8A16Experts`."""
 
     bits = 4
+
+    prompt_path = "auto"
+    PROMPT_PATHS = ("auto", "direct")
+
+    def op_path(self, T, k):
+        """The ``path`` argument of the int4 ops for a call with T tokens and k choices per token (shapes only, never the routing)."""
+        if self.prompt_path == "auto":
+            return "auto"
+        if self.prompt_path != "direct":
+            raise ValueError("W4A16Experts.prompt_path must be one of %r (got %r)" % (self.PROMPT_PATHS, self.prompt_path))
+        E, H, I = self.num_experts, self.hidden_dim, self.intermediate_dim
+        direct = T > 16 and T * k >= 16 * E and w4_a16_moe_direct_supported(T, k, E, H, I)
+        return "direct" if direct else "decode"
 
     @staticmethod
     def unsupported_reason(module):
@@ -285,9 +305,10 @@ class W4A16Experts(_QuantExperts):
     def forward(self, hidden_states, top_k_index, top_k_weights):
         """Any number of tokens, no host sync, capturable in a graph.  Four launches on the int4 decode kernel; on the prompt path
         (``ops.w4_a16_moe_path``: chosen from the shapes, never from the routing) each projection's stack is first expanded to
-        int8 tiles and runs the grouped tiled W8A16 kernel."""
+        int8 tiles and runs the grouped tiled W8A16 kernel.  With ``prompt_path = "direct"`` prompts run the grouped tiled kernel
+        on the int4 tiles instead (see the class)."""
         return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
-                          self.down_qweight, self.down_scales)
+                          self.down_qweight, self.down_scales, self.op_path(hidden_states.shape[0], top_k_index.shape[1]))
 
 
 def _adopt(module, mixin):
@@ -510,12 +531,13 @@ class EetqSparseMoeBlock(nn.Module):
             args = (flat, gate.weight, *gate.sigmoid_args(), experts.gate_up_qweight, experts.gate_up_scales, experts.down_qweight,
                     experts.down_scales)
             with torch.no_grad():
-                out = w4_a16_moe_block_sigmoid(*args) if experts.bits == 4 else w8_a16_moe_block_sigmoid(*args)
+                out = (w4_a16_moe_block_sigmoid(*args, experts.op_path(flat.shape[0], gate.top_k)) if experts.bits == 4
+                       else w8_a16_moe_block_sigmoid(*args))
             return out.reshape(hidden_states.shape) + self.shared_experts(hidden_states)
         args = (flat, gate.weight, gate.top_k, gate.renormalises, gate.scores_dtype(), experts.gate_up_qweight, experts.gate_up_scales,
                 experts.down_qweight, experts.down_scales)
         with torch.no_grad():
-            out = w4_a16_moe_block(*args) if experts.bits == 4 else w8_a16_moe_block(*args)
+            out = w4_a16_moe_block(*args, experts.op_path(flat.shape[0], gate.top_k)) if experts.bits == 4 else w8_a16_moe_block(*args)
         return out.reshape(hidden_states.shape)
 
 

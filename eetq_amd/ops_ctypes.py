@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
-           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "moe_router", "w8_a16_moe_block",
+           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
@@ -418,6 +418,16 @@ def w4_a16_moe_path(T, k, E, H, I):
     """The shape rule of :func:`w4_a16_moe`: compiled module only."""
     raise RuntimeError("eetq_amd: w4_a16_moe_path needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
                        "the ctypes binding does not implement it")
+
+
+def w4_a16_moe_direct_supported(T, k, E, H, I):
+    """Where ``w4_a16_moe(path="direct")`` runs: both projections inside ``eetq_w4a16_moe_gemm_tiled_supported`` (host arithmetic)."""
+    if not (T >= 0 and 1 <= k <= E and H >= 1 and I >= 1):
+        raise RuntimeError("w4_a16_moe_direct_supported: T >= 0, 1 <= k <= E, H >= 1, I >= 1")
+    if T < 1 or T * k > 1 << 30 or E > 1 << 20 or H >= 1 << 31 or 2 * I >= 1 << 31:
+        return False
+    f = _lib.lib().eetq_w4a16_moe_gemm_tiled_supported
+    return f(T, k, E, 2 * I, H, 1) == 1 and f(T, k, E, H, I, 0) == 1
 
 
 def moe_router(hidden, weight, top_k, norm_topk_prob=True, scores_dtype=None):

@@ -99,7 +99,7 @@ def set_trainable(model, flag=True):
 
 
 def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False,
-                 trainable=False, expert_bits=8, router=False):
+                 trainable=False, expert_bits=8, expert_prompt_path="auto", router=False):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
@@ -114,6 +114,10 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     H and I multiples of 128, inference only -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
     but 8 or 4, ``expert_bits=4`` without ``experts=True`` (it would quantise no expert and say nothing) and ``expert_bits=4``
     together with ``trainable=True`` (there is no int4 backward) raise ValueError before the model is touched.
+    ``expert_prompt_path="direct"`` (extension; with ``expert_bits=4``) sets :attr:`W4A16Experts.prompt_path` on every int4 experts
+    module it builds: prompts then run the grouped tiled kernel on the int4 tiles instead of the decode kernel or the expansion
+    (DESIGN.md 4.12).  The default ``"auto"`` changes nothing; any other value, or ``"direct"`` without ``expert_bits=4``, raises
+    ValueError before the model is touched.
     ``router=True`` (extension; needs ``experts=True``, else ValueError before the model is touched) also moves the router onto
     the device kernel: every ``MixtralTopKRouter`` / ``Qwen2MoeTopKRouter`` / ``Qwen3MoeTopKRouter`` /
     ``OlmoeTopKRouter`` becomes an :class:`EetqTopKRouter`, and every ``MixtralSparseMoeBlock`` / ``Qwen3MoeSparseMoeBlock`` /
@@ -133,6 +137,10 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
         raise ValueError("eet_quantize: expert_bits=4 needs experts=True (without it no experts module is quantised)")
     if expert_bits == 4 and trainable:
         raise ValueError("eet_quantize: expert_bits=4 cannot be trainable (W4A16Experts has no backward)")
+    if expert_prompt_path not in W4A16Experts.PROMPT_PATHS:
+        raise ValueError("eet_quantize: expert_prompt_path must be one of %r (got %r)" % (W4A16Experts.PROMPT_PATHS, expert_prompt_path))
+    if expert_prompt_path != "auto" and expert_bits != 4:
+        raise ValueError("eet_quantize: expert_prompt_path=%r needs expert_bits=4 (it is the int4 experts' switch)" % (expert_prompt_path,))
     if router and not experts:
         raise ValueError("eet_quantize: router=True needs experts=True (the device router feeds the quantised experts)")
     experts_cls = W4A16Experts if expert_bits == 4 else W8A16Experts
@@ -148,7 +156,10 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
             if why is not None:
                 skipped.append("%s (%s)" % (name, why))
                 continue
-            set_op_by_name(model, name, experts_cls.from_experts(mod, init_only=init_only))
+            qmod = experts_cls.from_experts(mod, init_only=init_only)
+            if expert_prompt_path != "auto":
+                qmod.prompt_path = expert_prompt_path
+            set_op_by_name(model, name, qmod)
             quantised.append(name)
             del mod
             if not init_only and torch.cuda.is_available():

@@ -327,6 +327,22 @@ int eetq_expand_i4_to_i8(const int8_t* src, int8_t* dst, size_t bytes_src, void*
  *   cases for which it would return EETQ_ERR_UNSUPPORTED), else 0.  Host arithmetic only, no device needed.  Lets a caller that has
  *   to prepare something for the tiled kernel first -- the int4 layer's expansion -- decide before it does. */
 int eetq_w8a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather);
+/* eetq_w4a16_moe_gemm_tiled: eetq_w8a16_moe_gemm_tiled on an int4 expert stack (w_packed_i4 [E][K][N / 2] bytes, as
+ *   eetq_w4a16_moe_gemm takes it), read by the tile kernel directly: no expansion, no scratch.  The contract is
+ *   eetq_w8a16_moe_gemm_tiled's -- tables, gather, glu8, untouched rows, a grid that depends on the shapes only, capturable, no
+ *   allocation, no host sync -- and a live row's bits are those of eetq_expand_i4_to_i8 followed by eetq_w8a16_moe_gemm_tiled
+ *   (fp16(q s) with one rounding, the same K order), at either tile shape.
+ *   tile_j: 0 = the tile shape eetq_w8a16_moe_gemm_tiled would pick for these sizes, 1 = the 128 x 64 tile, 2 = the 128 x 128
+ *   tile; anything else EETQ_ERR_INVALID.  Argument checks as eetq_w4a16_moe_gemm (K % 128 == 0, N % 16 == 0, 16-byte aligned
+ *   pointers, ...): EETQ_ERR_INVALID, nothing launched.  A valid shape outside eetq_w4a16_moe_gemm_tiled_supported returns
+ *   EETQ_ERR_UNSUPPORTED, launching nothing and setting no message: the caller runs eetq_w4a16_moe_gemm. */
+int eetq_w4a16_moe_gemm_tiled(const void* x, const int8_t* w_packed_i4, const void* scales, const int* offsets,
+                              const int* sorted_slot, const int* active, void* y, int T, int k, int E, int N, int K, int gather,
+                              int glu8, int tile_j, void* stream);
+/* eetq_w4a16_moe_gemm_tiled_supported: 1 where eetq_w4a16_moe_gemm_tiled takes a projection of these sizes: the limits of
+ *   eetq_w8a16_moe_gemm_tiled_supported with K % 128 == 0 and K >= 384 (an even number of 64-deep K steps, at least six).  Host
+ *   arithmetic only, no device needed. */
+int eetq_w4a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather);
 
 /* ---- mixture-of-experts router (extension, additive within ABI revision 7) -----------------------------------
  * The reference has no MoE path.  These entries replace the forward of transformers' *TopKRouter modules (MixtralTopKRouter,

@@ -38,6 +38,13 @@ child process per plan (EETQ_AMD_TUNING=1 EETQ_AMD_MOE_I4_PLAN=<waves>x<depth>, 
 (profiles/r10_moe_int4_plans.jsonl also holds 8x1, 4x2, 6x1 and 3x2: instantiations that lost or tied in that sweep and were
 deleted after it; the sweep now covers the ones that are left.)
 
+--path direct (with --bits 4) runs the layer table on ops.w4_a16_moe(path="direct") -- the grouped tiled kernel on the
+int4 tiles -- where both projections take it (T > 16; the record's `path` says what ran), and adds to --seam a third route per pair
+of projections, eetq_w4a16_moe_gemm_tiled at the launcher's tile shape (us_direct, with min and max), next to the other two.
+
+    python tools/moe_bench.py --bits 4 --seam --path direct --out <file>.jsonl
+    python tools/moe_bench.py --bits 4 --path direct --tokens 64,512,4096 --out <file>.jsonl
+
 --block --shapes deepseek-v3 --tokens 1,4,16,64 is the same comparison under the sigmoid, bias-corrected, group-limited
 rule at DeepSeek-V3's sizes (H 7168, I 2048, E 256, k 8, 8 groups, 4 kept): DeepseekV3TopkRouter's forward op for op followed by
 w8_a16_moe / w4_a16_moe against ops.w8_a16_moe_block_sigmoid / w4_a16_moe_block_sigmoid, and the formula against ops.moe_router_sigmoid.
@@ -300,12 +307,23 @@ def seam_i4(args, out):
                     c = L.eetq_expand_i4_to_i8(_ptr(dn_w), _ptr(w8), dn_w.numel(), st)
                     d = L.eetq_w8a16_moe_gemm_tiled(_ptr(inter), _ptr(w8), _ptr(dn_s), *tab, _ptr(down), T, k, E, H, I, 0, 0, st)
                     assert a == 0 and b == 0 and c == 0 and d == 0, (a, b, c, d)
-                us_dec = _time(decode, args.warmup, args.iters)
-                us_exp = _time(expanded, args.warmup, args.iters)
+
+                def direct():
+                    a = L.eetq_w4a16_moe_gemm_tiled(_ptr(x), _ptr(gu_w), _ptr(gu_s), *tab, _ptr(inter), T, k, E, 2 * I, H, 1, 1, 0, st)
+                    b = L.eetq_w4a16_moe_gemm_tiled(_ptr(inter), _ptr(dn_w), _ptr(dn_s), *tab, _ptr(down), T, k, E, H, I, 0, 0, 0, st)
+                    assert a == 0 and b == 0, (a, b)
+                us_dec, dec_lo, dec_hi = _time_stats(decode, args.warmup, args.iters)
+                us_exp, exp_lo, exp_hi = _time_stats(expanded, args.warmup, args.iters)
                 us_only = _time(expand_only, args.warmup, args.iters)
                 rec = {"shape": name, "bits": 4, "H": H, "I": I, "E": E, "k": k, "T": T, "mean_rows": round(S / E, 2), "routing": kind,
                        "max_rows": int(tabs[0].max()), "us_decode_kernel": round(us_dec, 2), "us_expand_plus_tiled": round(us_exp, 2),
                        "us_expansions_alone": round(us_only, 2), "decode_over_expanded": round(us_dec / us_exp, 3)}
+                if args.path == "direct":
+                    us_dir, lo, hi = _time_stats(direct, args.warmup, args.iters)
+                    rec.update({"us_direct": round(us_dir, 2), "us_direct_min": round(lo, 2), "us_direct_max": round(hi, 2),
+                                "us_decode_min_max": [round(dec_lo, 2), round(dec_hi, 2)],
+                                "us_expand_min_max": [round(exp_lo, 2), round(exp_hi, 2)],
+                                "decode_over_direct": round(us_dec / us_dir, 3), "expanded_over_direct": round(us_exp / us_dir, 3)})
                 line = json.dumps(rec)
                 print(line, flush=True)
                 if out:
@@ -502,10 +520,14 @@ def main():
     ap.add_argument("--seam-rows", default=None,
                     help="mean rows per expert of the seam sweep (default 1,2,4,8,16,32,64; 16,32,64,128,256 with --bits 4)")
     ap.add_argument("--bits", type=int, choices=(8, 4), default=8, help="the layer table / --seam on int8 or int4 expert stacks")
+    ap.add_argument("--path", choices=("auto", "direct"), default="auto",
+                    help="--bits 4: 'direct' = the grouped tiled kernel on the int4 tiles (DESIGN.md 4.12), in the layer table and --seam")
     ap.add_argument("--plan-sweep", action="store_true", help="sweep eetq_w4a16_moe_gemm's instantiations (DESIGN.md 4.12)")
     ap.add_argument("--plan-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--block", action="store_true", help="time the whole sparse block with and without the device router (DESIGN.md 4.13)")
     args = ap.parse_args()
+    if args.path != "auto" and args.bits != 4:
+        ap.error("--path direct needs --bits 4")
     if args.block:
         args.tokens = args.tokens or "1,4,16,64,512"
         out = open(args.out, "w") if args.out else None
@@ -543,7 +565,7 @@ def main():
     from transformers.models.mixtral.modeling_mixtral import MixtralExperts
 
     from eetq_amd import _lib
-    from eetq_amd.ops import w4_a16_moe, w4_a16_moe_path, w8_a16_gemm, w8_a16_moe
+    from eetq_amd.ops import w4_a16_moe, w4_a16_moe_direct_supported, w4_a16_moe_path, w8_a16_gemm, w8_a16_moe
     if args.bits == 4:
         args.no_baselines = True
     host = _lib.lib().eetq_diag_moe_host_path() == 1
@@ -583,14 +605,17 @@ def main():
                         y.index_add_(0, tok, d * wts[tok, j, None].half())
                     return y
 
-                us, us_lo, us_hi = _time_stats(lambda: layer(x, idx, wts, gu_w, gu_s, dn_w, dn_s), args.warmup, args.iters)
+                # --path direct: the module's opt-in rule (T > 16, T k >= 16 E, both projections supported), else the decode kernel
+                direct = (args.path == "direct" and T > 16 and T * k >= 16 * E and w4_a16_moe_direct_supported(T, k, E, H, I))
+                extra = () if args.path == "auto" else ("direct" if direct else "decode",)
+                us, us_lo, us_hi = _time_stats(lambda: layer(x, idx, wts, gu_w, gu_s, dn_w, dn_s, *extra), args.warmup, args.iters)
                 nbytes = len(active) * 3 * H * I * args.bits // 8
                 rec = {"shape": name, "H": H, "I": I, "E": E, "k": k, "T": T, "routing": kind, "active_experts": len(active),
                        "path": "host" if host and T > 16 else "device", "us": round(us, 2), "us_min": round(us_lo, 2),
                        "us_max": round(us_hi, 2), "bits": args.bits, "int8_bytes" if args.bits == 8 else "int4_bytes": nbytes,
                        "TBps": round(nbytes / us / 1e6, 3), "TFLOPs": round(6.0 * T * k * H * I / us / 1e6, 1)}
                 if args.bits == 4:
-                    rec["path"] = w4_a16_moe_path(T, k, E, H, I)
+                    rec["path"] = extra[0] if extra else w4_a16_moe_path(T, k, E, H, I)
                 if (name, T, kind) in host_us:
                     rec["us_host_path"], rec["us_host_path_min"], rec["us_host_path_max"] = host_us[(name, T, kind)]
                     rec["host_over_device"] = round(rec["us_host_path"] / us, 2)
