@@ -30,6 +30,13 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kPfThreads = 256, kPfBM = 128, kPfBN = 64;
+// The probabilities are carried as 2^12 p: the running maximum is kept kPfPShift below the true one (the shift rides in the fma that
+// scales the block maximum; one constant register, no instruction in the loop), so the row maximum maps to 4 096 and the row sum to
+// 4 096 l, and the factor leaves with the division at the end.  As fp16 B operands of the second product the probabilities then keep
+// 11 significant bits down to p = 2^-26.  Unshifted, every p below 2^-14 is an fp16 subnormal with an ABSOLUTE error of up to 2^-25,
+// and a handful of such keys move an output that is itself tiny (a peaked row whose winning value is near zero) by more than its
+// own fp16 spacing (tests/test_gpu_attn_prefill_edges.py).  4 096 (1 + rounding) is far below fp16's 65 504.
+constexpr float kPfPShift = 12.f;
 
 struct PrefillArgs {
     const f16* q;
@@ -177,7 +184,7 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[kb][r]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64)) * a.c;              // (c > 0)
+            mloc = fmaf(fmaxf(mloc, __shfl_xor(mloc, 32, 64)), a.c, -kPfPShift);   // (c > 0); the maxima are kept 12 below: p as 2^12 p
             const float m_new = fmaxf(m_run, mloc);
             const float m_use = m_new > -INFINITY ? m_new : 0.f;             // a row with nothing to attend yet: every p = 0
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);       // exp2(-inf) = 0 for the first block
