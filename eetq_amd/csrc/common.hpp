@@ -220,6 +220,24 @@ inline int opt_in_large_lds(Kern kern, std::atomic<unsigned long long>& done)
     return EETQ_OK;
 }
 
+// A kernel that needs the opt-in and its mask of devices: launch sites keep one static row per instantiation they may launch.
+template <typename Kern>
+struct LargeLdsKernel {
+    Kern                            kern;
+    std::atomic<unsigned long long> opted{0};
+};
+
+// opt-in (for this kernel and no other), launch, launch check
+template <typename Kern, typename... Args>
+inline int launch_large_lds(LargeLdsKernel<Kern>& k, const char* what, dim3 grid, dim3 block, size_t smem, hipStream_t stream,
+                            Args... args)
+{
+    const int st = opt_in_large_lds(k.kern, k.opted);
+    if (st != EETQ_OK) return st;
+    launch_kernel(k.kern, grid, block, smem, stream, args...);
+    return check_hip(hipGetLastError(), what);
+}
+
 // ---- A/B hooks ----------------------------------------------------------------------------------------
 // Every EETQ_AMD_* variable that steers kernel SELECTION (stream plans, workgroup sizes, column units, quantiser forms ...) is
 // an A/B hook for tools/ and tests/: it is read through tuning_env(), which answers only when the process also sets

@@ -51,16 +51,13 @@ int launch_tile_splitk_cols(const f16* x, const uint8_t* w, const f16* scales, E
     if (st == EETQ_ERR_UNSUPPORTED || (st == EETQ_OK && ((size_t)tiles > max_tiles || (size_t)tiles * S * BM * BN * 4 > slab_bytes)))
         return EETQ_ERR_UNSUPPORTED;  // no scratch of its own for this stream right now
     if (st != EETQ_OK) return st;
-    static std::atomic<unsigned long long> opted{0};
-    st = opt_in_large_lds(gemm_tile_splitk_kernel<1>, opted);
-    if (st != EETQ_OK) return st;
     Epilogue e = ep;
     if (e.bias) e.bias += c0;
     if (e.residual) e.residual += c0;
     const uint8_t* wc = w + (size_t)(c0 / kTileN) * (K / kTileK) * kTileBytes;
-    launch_kernel(gemm_tile_splitk_kernel<1>, dim3(tiles * S), dim3(256), TileCfg<1>::SMEM_BYTES, stream, x, wc, scales + c0, y + c0, rows,
-                  cols, K, ldc, e, S, slabs, S == 2 ? t2 : t4);
-    return check_hip(hipGetLastError(), "gemm_tile_splitk_kernel launch");
+    static LargeLdsKernel<decltype(&gemm_tile_splitk_kernel<1>)> kernel{gemm_tile_splitk_kernel<1>};
+    return launch_large_lds(kernel, "gemm_tile_splitk_kernel launch", dim3(tiles * S), dim3(256), TileCfg<1>::SMEM_BYTES, stream, x, wc,
+                            scales + c0, y + c0, rows, cols, K, ldc, e, S, slabs, S == 2 ? t2 : t4);
 }
 }  // namespace
 
@@ -81,24 +78,6 @@ int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue
             if (st != EETQ_OK) return st;
         }
         return EETQ_OK;
-    }
-    {   // > 64 KiB of dynamic LDS: one opt-in per kernel and device (common.hpp)
-        static std::atomic<unsigned long long> opted2{0}, opted1{0}, opted2a{0}, opted1a{0}, opted2g{0}, opted1g{0}, opted_tall{0};
-        static std::atomic<unsigned long long> opted_deep{0};
-        int st = opt_in_large_lds(gemm_tile_kernel<0, 2, false, 2, false, 2>, opted_tall);
-        if (st == EETQ_OK) st = opt_in_large_lds(gemm_tile_kernel<0, 2, false, 2, false, 1, 2>, opted_deep);
-        if (st != EETQ_OK) return st;
-        if (glu) {
-            st = opt_in_large_lds(gemm_tile_kernel<0, 2, false, 2, true>, opted2g);
-            if (st == EETQ_OK) st = opt_in_large_lds(gemm_tile_kernel<0, 1, false, 2, true>, opted1g);
-        } else if (ep.act == 0) {
-            st = opt_in_large_lds(gemm_tile_kernel<0, 2>, opted2);
-            if (st == EETQ_OK) st = opt_in_large_lds(gemm_tile_kernel<0, 1>, opted1);
-        } else {  // the activation epilogues are their own instantiation (gemm_kernel.hpp)
-            st = opt_in_large_lds(gemm_tile_kernel<0, 2, true>, opted2a);
-            if (st == EETQ_OK) st = opt_in_large_lds(gemm_tile_kernel<0, 1, true>, opted1a);
-        }
-        if (st != EETQ_OK) return st;
     }
     // the LDS-DMA path addresses its operands with 32-bit buffer offsets
     EETQ_REQUIRE((size_t)N * K < (1ull << 31), "weight larger than 2 GiB is not supported by the buffer-addressed DMA path");
@@ -123,35 +102,15 @@ int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue
         if (e.residual) e.residual += (size_t)m * N + c0;
         const uint8_t* wc = w + (size_t)(c0 / kTileN) * (K / kTileK) * kTileBytes;
         const bool     narrow = force_j == 1 || (force_j == 0 && cost1 < cost2);
-        auto go = [&](auto kern, int tiles, size_t smem, int threads = 256) {
-            const int ldc = glu ? N / 2 : N;
-            launch_kernel(kern, dim3(tiles), dim3(threads), smem, stream, x + (size_t)m * K, wc, scales + c0,
-                          y + (size_t)m * ldc + (glu ? c0 / 2 : c0), rows, cols, K, ldc, e);
-        };
-        // the tall tile (256 x 128 on eight waves, gemm_kernel.hpp): EETQ_AMD_TILE_TALL=1 (behind EETQ_AMD_TUNING) for A/B runs
-        static const int tall_env = [] {
-            const char* t = tuning_env("EETQ_AMD_TILE_TALL");
-            return t ? atoi(t) : 0;
-        }();
-        if (tall_env == 2 && !glu && e.act == 0 && rows >= 256) {  // the deep tile: 256 x 128 on four waves
-            using Deep = TileCfg<2, 2, 1, 2>;
-            const int tiles_d = ((rows + Deep::ROWS - 1) / Deep::ROWS) * ((cols + Deep::BN - 1) / Deep::BN);
-            go(gemm_tile_kernel<0, 2, false, 2, false, 1, 2>, tiles_d, Deep::SMEM_BYTES, 256);
-            return check_hip(hipGetLastError(), "gemm_tile_kernel (deep) launch");
-        }
-        if (tall_env == 1 && !glu && e.act == 0 && rows >= 256) {
-            using Tall = TileCfg<2, 2, 2>;
-            const int tiles_t = ((rows + Tall::ROWS - 1) / Tall::ROWS) * ((cols + Tall::BN - 1) / Tall::BN);
-            go(gemm_tile_kernel<0, 2, false, 2, false, 2>, tiles_t, Tall::SMEM_BYTES, 512);
-            return check_hip(hipGetLastError(), "gemm_tile_kernel (tall) launch");
-        }
-        if (glu && narrow) go(gemm_tile_kernel<0, 1, false, 2, true>, tiles1, TileCfg<1>::SMEM_BYTES);
-        else if (glu) go(gemm_tile_kernel<0, 2, false, 2, true>, tiles2, TileCfg<2>::SMEM_BYTES);
-        else if (narrow && e.act == 0) go(gemm_tile_kernel<0, 1>, tiles1, TileCfg<1>::SMEM_BYTES);
-        else if (narrow) go(gemm_tile_kernel<0, 1, true>, tiles1, TileCfg<1>::SMEM_BYTES);
-        else if (e.act == 0) go(gemm_tile_kernel<0, 2>, tiles2, TileCfg<2>::SMEM_BYTES);
-        else go(gemm_tile_kernel<0, 2, true>, tiles2, TileCfg<2>::SMEM_BYTES);
-        return check_hip(hipGetLastError(), "gemm_tile_kernel launch");
+        // [narrow][identity / activation epilogue / GLU write-out], each its own instantiation (gemm_kernel.hpp).  > 64 KiB of
+        // dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
+        static LargeLdsKernel<decltype(&gemm_tile_kernel<0, 2>)> kernels[2][3] = {
+            {{gemm_tile_kernel<0, 2>}, {gemm_tile_kernel<0, 2, true>}, {gemm_tile_kernel<0, 2, false, 2, true>}},
+            {{gemm_tile_kernel<0, 1>}, {gemm_tile_kernel<0, 1, true>}, {gemm_tile_kernel<0, 1, false, 2, true>}}};
+        const int ldc = glu ? N / 2 : N;
+        return launch_large_lds(kernels[narrow][glu ? 2 : e.act != 0], "gemm_tile_kernel launch", dim3(narrow ? tiles1 : tiles2), dim3(256),
+                                narrow ? TileCfg<1>::SMEM_BYTES : TileCfg<2>::SMEM_BYTES, stream, x + (size_t)m * K, wc, scales + c0,
+                                y + (size_t)m * ldc + (glu ? c0 / 2 : c0), rows, cols, K, ldc, e);
     };
     for (int m = 0; m < M; m += max_rows) {
         const int rows    = M - m < max_rows ? M - m : max_rows;
@@ -257,16 +216,10 @@ int launch_gemm_tile_splitk(const f16* x, const uint8_t* w, const f16* scales, E
     if (st == EETQ_ERR_UNSUPPORTED || (st == EETQ_OK && ((size_t)tiles > max_tiles || (size_t)tiles * S * BM * BN * 4 > slab_bytes)))
         return launch_gemm_mfma(x, w, scales, ep, y, M, N, K, stream);  // no scratch of its own for this stream: unsplit
     if (st != EETQ_OK) return st;
-    static std::atomic<unsigned long long> opted{0}, opted_wide{0};
-    st = wide ? opt_in_large_lds(gemm_tile_splitk_kernel<2>, opted_wide) : opt_in_large_lds(gemm_tile_splitk_kernel<1>, opted);
-    if (st != EETQ_OK) return st;
-    if (wide)
-        launch_kernel(gemm_tile_splitk_kernel<2>, dim3(tiles * S), dim3(256), TileCfg<2>::SMEM_BYTES, stream, x, w, scales, y, M, N, K, N,
-                      ep, S, slabs, t2);
-    else
-        launch_kernel(gemm_tile_splitk_kernel<1>, dim3(tiles * S), dim3(256), TileCfg<1>::SMEM_BYTES, stream, x, w, scales, y, M, N, K, N,
-                      ep, S, slabs, S == 2 ? t2 : t4);
-    st = check_hip(hipGetLastError(), "gemm_tile_splitk_kernel launch");
+    static LargeLdsKernel<decltype(&gemm_tile_splitk_kernel<1>)> kernels[2] = {{gemm_tile_splitk_kernel<1>}, {gemm_tile_splitk_kernel<2>}};
+    st = launch_large_lds(kernels[wide], "gemm_tile_splitk_kernel launch", dim3(tiles * S), dim3(256),
+                          wide ? TileCfg<2>::SMEM_BYTES : TileCfg<1>::SMEM_BYTES, stream, x, w, scales, y, M, N, K, N, ep, S, slabs,
+                          S == 2 ? t2 : t4);
     if (st == EETQ_OK && used_s) *used_s = S;
     return st;
 }

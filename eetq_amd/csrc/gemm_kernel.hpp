@@ -31,23 +31,14 @@ constexpr int kMinKSteps    = STAGES - 1;   // the statically unrolled drain nee
 // CW = waves across the tile's columns (each owns 32*J of them); 2*CW waves per workgroup.  CW = 2: the round-1 geometry,
 // one wave per SIMD.  (J, CW) = (1, 4): the 128 x 128 tile on EIGHT waves, two per SIMD -- half the accumulators and half the
 // DMA pieces per wave, and a second wave on every SIMD to issue MFMAs while the first sits in an LDS-DMA issue or a barrier.
-// RH = row halves: RH = 2 is the TALL tile, 256 x 128 on eight waves (round 6) -- waves 0..3 own rows 0..127 exactly as the four
-// waves of the 128 x 128 tile do, waves 4..7 rows 128..255, both halves read the SAME weight stage (one weight DMA and 8 KiB of LDS
-// per K step and 256 rows instead of two), 40 KiB stages in a 4-slot ring (all 160 KiB of LDS), the epilogue in two phases.
-// RB = 32-row-block multiplier per wave: RB = 2 is the DEEP tile, 256 x 128 on FOUR waves -- a wave owns 256 rows x 64 columns of
-// one K half (256 accumulators per lane, one wave per SIMD): every dequantised weight fragment feeds 8 MFMAs instead of 4, so the
-// dequant work and the weight reads per MFMA halve as well as the weight DMA.  Same stages, ring and epilogue phases as the tall tile.
 // BITS = 4 (grouped tile on an int4 expert stack, moe_int4_tiled.hip): a K step needs half an int4 tile per column tile, 512 bytes
-template <int J, int CW = 2, int RH = 1, int RB = 1, int BITS = 8>
+template <int J, int CW = 2, int BITS = 8>
 struct TileCfg {
     static constexpr int BN            = 32 * J * CW;
-    static constexpr int WAVES         = 2 * CW * RH;
-    static constexpr int ROWS          = BM * RH * RB;
-    static constexpr int RING          = RH * RB == 2 ? 4 : STAGES;
-    static constexpr int A_BYTES       = A_STAGE_BYTES * RH * RB;
+    static constexpr int WAVES         = 2 * CW;
     static constexpr int B_STAGE_BYTES = BN * BK * BITS / 8;  // BN/16 native 1 KiB tiles per K step (int4: BN/16 half tiles)
-    static constexpr int STAGE_BYTES   = A_BYTES + B_STAGE_BYTES;
-    static constexpr int SMEM_BYTES    = RING * STAGE_BYTES;  // 144 / 120 / 160 KiB (also covers the end-of-kernel reduction)
+    static constexpr int STAGE_BYTES   = A_STAGE_BYTES + B_STAGE_BYTES;
+    static constexpr int SMEM_BYTES    = STAGES * STAGE_BYTES;  // 144 / 120 KiB (also covers the end-of-kernel reduction)
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -62,6 +53,13 @@ struct GroupMap {
     int        R           = 0;        // row-tile slots: floor(S / 128) + A
     int        x_rows      = 0;        // rows of x (T when gathering, S otherwise)
 };
+
+// the map of a launch over T tokens x k choices among E experts (S = T k sorted rows)
+inline GroupMap make_group_map(const int* offsets, const int* sorted_slot, const int* active, int T, int k, int E, bool gather)
+{
+    const int S = T * k, A = S < E ? S : E;
+    return GroupMap{offsets, sorted_slot, active, gather ? k : 0, A, S / BM + A, gather ? T : S};
+}
 
 // LDS-DMA: 16 B per lane from a buffer (base in the descriptor, per-lane byte offset in voff, wave-uniform byte
 // offset in soff) straight into LDS at wave-uniform base + lane*16, no VGPR round trip.  The MUBUF form
@@ -154,40 +152,35 @@ __device__ __forceinline__ f16x8 make_frag(f16x2 a, f16x2 b, f16x2 c, f16x2 d)
 // separate packed ops (the int8 path's fp16(q) * s, one rounding: the same bits as expansion + the int8 tile).  The dequant fills
 // the int8 schedule's gaps: gap (jj, dword, kind) with kind = extract (three shifts, four and-or) / - 1032 / * scale.
 // K % 128 == 0 makes the K-step count even: only the tail == 6 drain exists.
-template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, int RH = 1, int RB = 1, bool GROUPED = false, int BITS = 8>
+template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, bool GROUPED = false, int BITS = 8>
 __device__ __forceinline__ void gemm_tile_body(
     const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales,
     f16* __restrict__ y, int M, int N, int K, int ldc, Epilogue ep, int S, float* __restrict__ slabs,
     unsigned* __restrict__ counters, GroupMap map = GroupMap{})
 {
-    static_assert(!GROUPED || (!SPLIT && !ACT && RH == 1 && RB == 1 && CW == 2 && ABLATE == 0),
+    static_assert(!GROUPED || (!SPLIT && !ACT && CW == 2 && ABLATE == 0),
                   "the grouped form exists for the unsplit 4-wave identity tile (plain and GLU)");
     static_assert(BITS == 8 || (BITS == 4 && GROUPED), "int4 tiles: the grouped, unsplit, four-wave identity tile only");
     // N = columns of THIS launch (w, scales, y, ep.* already point at its first column); ldc = row stride of y / residual
     EETQ_GEMM_STAMP(0);
-    using Cfg = TileCfg<J, CW, RH, RB, BITS>;
+    using Cfg = TileCfg<J, CW, BITS>;
     constexpr int BN = Cfg::BN, STAGE_BYTES = Cfg::STAGE_BYTES, SMEM_BYTES = Cfg::SMEM_BYTES, NW = Cfg::WAVES;
-    constexpr int ST = Cfg::RING, BMT = Cfg::ROWS, A_BYTES = Cfg::A_BYTES;
-    constexpr int APW = 16 * RH * RB / NW;    // activation DMA pieces (8 rows each) per wave and stage: 4 or 2; 8 in the deep tile
-    // weight tiles per wave and stage: J, or 1 in the tall tile; int4: one piece (two half tiles) per wave
+    constexpr int APW = 16 / NW;              // activation DMA pieces (8 rows each) per wave and stage: 4 or 2
+    // weight tiles per wave and stage: J; int4: one piece (two half tiles) per wave
     constexpr int BPW = BITS == 4 ? 1 : (BN / 16) / NW;
     constexpr int kStepBytesB = BITS == 4 ? kTileBytes / 2 : kTileBytes;  // weight source bytes per K step and column tile
-    constexpr int WN_COLS = 32 * J, PIECES = APW + BPW, NMFMA = 8 * J * RB;
-    constexpr int MT = 4 * RB;                // 32-row blocks per wave
+    constexpr int WN_COLS = 32 * J, PIECES = APW + BPW, NMFMA = 8 * J;
     static_assert(J == 1 || J == 2, "slot tables exist for J = 1 and J = 2");
     static_assert(CW == 2 || (CW == 4 && J == 1), "geometries with slot tables: 4 waves (J = 1, 2) and 8 waves (J = 1)");
-    static_assert(RH == 1 || (RH == 2 && J == 2 && CW == 2 && !SPLIT), "the tall tile is 256 x 128, unsplit");
-    static_assert(RB == 1 || (RB == 2 && RH == 1 && J == 2 && CW == 2 && !SPLIT && ABLATE == 0), "the deep tile is 256 x 128 on four waves, unsplit");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid  = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const int rh   = wave / (2 * CW);         // which 128-row half of the tile (0 unless RH = 2)
     const int grp  = (wave % (2 * CW)) / CW;  // which 32-deep half of each K step
     const int wn   = wave % CW;               // which 32*J-column part of the tile
     const int KT   = K >> 6;
 
-    const int tiles_m = GROUPED ? map.R : (M + BMT - 1) / BMT;
+    const int tiles_m = GROUPED ? map.R : (M + BM - 1) / BM;
     const int tiles_n = (N + BN - 1) / BN;
     const int T       = tiles_m * tiles_n;
     int       tile, slice = 0, k0 = 0, ksteps = KT;  // this workgroup's K steps: [k0, k0 + ksteps)
@@ -213,7 +206,7 @@ __device__ __forceinline__ void gemm_tile_body(
     const int chunk   = tile / (kGroupM * tiles_n);
     const int in_ch   = tile - chunk * (kGroupM * tiles_n);
     const int ch_rows = tiles_m - chunk * kGroupM < kGroupM ? tiles_m - chunk * kGroupM : kGroupM;
-    int       m0 = (chunk * kGroupM + in_ch % ch_rows) * BMT;
+    int       m0 = (chunk * kGroupM + in_ch % ch_rows) * BM;
     const int n0 = (in_ch / ch_rows) * BN;
     int       p0 = 0;  // grouped: the expert's first sorted row
     if constexpr (GROUPED) {
@@ -300,16 +293,17 @@ __device__ __forceinline__ void gemm_tile_body(
         }
     }
     const int dma_lds_a = wave * APW * 1024;                  // + i * 1024
-    const int dma_lds_b = A_BYTES + (BITS == 4 ? (J == 2 ? wave : (wave & 1)) : wave * BPW) * 1024;  // + (i - APW) * 1024
+    const int dma_lds_b = A_STAGE_BYTES + (BITS == 4 ? (J == 2 ? wave : (wave & 1)) : wave * BPW) * 1024;  // + (i - APW) * 1024
 
     const int fn = lane & 31, fh = lane >> 5;
     const int a_key = (fn >> 1) & 7;
     // per-lane constants of the LDS fragment reads (added to the stage offset)
     const int lds0 = (int)(uint32_t)(uintptr_t)(lds_void*)smem;
-    const int c_a0 = lds0 + rh * A_STAGE_BYTES + fn * 128 + (((4 * grp + 2 * fh + 0) ^ a_key) << 4);
-    const int c_a1 = lds0 + rh * A_STAGE_BYTES + fn * 128 + (((4 * grp + 2 * fh + 1) ^ a_key) << 4);
-    const int c_b0 = BITS == 4 ? lds0 + A_BYTES + ((wn * WN_COLS + fn) >> 4) * 512 + grp * 256 + (fn & 15) * 16 + fh * 8
-                               : lds0 + A_BYTES + ((wn * WN_COLS + fn) >> 4) * 1024 + (fn & 15) * 16 + fh * 256 + grp * 512;
+    const int a_hi = wave / (2 * CW) * A_STAGE_BYTES;  // always 0 (the epilogue's comment says why it stays)
+    const int c_a0 = lds0 + a_hi + fn * 128 + (((4 * grp + 2 * fh + 0) ^ a_key) << 4);
+    const int c_a1 = lds0 + a_hi + fn * 128 + (((4 * grp + 2 * fh + 1) ^ a_key) << 4);
+    const int c_b0 = BITS == 4 ? lds0 + A_STAGE_BYTES + ((wn * WN_COLS + fn) >> 4) * 512 + grp * 256 + (fn & 15) * 16 + fh * 8
+                               : lds0 + A_STAGE_BYTES + ((wn * WN_COLS + fn) >> 4) * 1024 + (fn & 15) * 16 + fh * 256 + grp * 512;
     const int c_b1 = c_b0 + (BITS == 4 ? 1024 : 2048);
 
     f16x2 scale2[J];
@@ -320,9 +314,9 @@ __device__ __forceinline__ void gemm_tile_body(
         scale2[j]      = f16x2{sc, sc};
     }
 
-    f32x16 acc[MT][J];
+    f32x16 acc[4][J];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
         for (int j = 0; j < J; ++j)
 #pragma unroll
@@ -348,7 +342,7 @@ __device__ __forceinline__ void gemm_tile_body(
 
     // ring state of the step about to run (wave-uniform): rd = LDS offset of the stage whose fragments it reads
     // (stage kt+1), wr = LDS offset its DMA fills (stage kt+5), ka / kb = source offsets of that stage
-    int rd = STAGE_BYTES, wr = (ST - 1) * STAGE_BYTES, ka = (k0 + ST - 1) * BK * 2, kb = (k0 + ST - 1) * kStepBytesB;
+    int rd = STAGE_BYTES, wr = (STAGES - 1) * STAGE_BYTES, ka = (k0 + STAGES - 1) * BK * 2, kb = (k0 + STAGES - 1) * kStepBytesB;
     int ra0 = rd + c_a0, ra1 = rd + c_a1, rb0 = rd + c_b0, rb1 = rd + c_b1;
 
     auto dma_piece = [&](auto itag) {
@@ -496,122 +490,12 @@ __device__ __forceinline__ void gemm_tile_body(
         }
     };
 
-    // ---- the tall tile's K step (RH = 2).  Two waves per SIMD leave 256 registers each: the schedule above keeps two full fragment
-    // sets next to 128 accumulators (1 373 spilled registers when compiled for eight waves: 1.2 - 1.3 x the 128 x 128 tile's time,
-    // tools/experiments/tall_tile_ab.py).  Here only the WEIGHTS are double-buffered (raw + dequantised, as above); an activation
-    // fragment is requested two MFMA pairs ahead of its use into a four-deep window -- pair p = (K half e = p / 4, row block mt = p % 4)
-    // feeds the two column blocks back to back -- and the window carries the next step's first two pairs across the barrier.  Every
-    // accumulator still adds its K halves in the order e = 0, 1: the same bits as the 128 x 128 tile.
-    // The deep tile (RB = 2) runs the same K step on ONE wave per SIMD with 16 pairs, an eight-deep window and requests four pairs
-    // ahead (128+ cycles of MFMA between request and use), 32 MFMA gaps: fragment requests in the even gaps, the dequant micro-ops in
-    // the odd gaps 5..27, the wave's ten DMA pieces in gaps 1, 3, 4, 8, ..., 28, ring bookkeeping in gaps 29..31.
-    constexpr int NP = 8 * RB, WIN = 4 * RB, DIST = 2 * RB;  // pairs per step, window depth, request distance
-    f16x8 xw[WIN];
-    int   ca0 = c_a0, ca1 = c_a1;  // fragment addresses of the CURRENT stage (ra0 / ra1: the next one's)
-    auto  step_tall = [&](const WFrag& wcur, auto read_tag, Frags& fnext, WFrag& wnext, auto dma_tag) {
-        if constexpr (RH * RB == 2) {  // (the body names int8 fragment members: not instantiated for any other tile)
-        constexpr bool READ = decltype(read_tag)::value;
-        constexpr bool DMA  = decltype(dma_tag)::value;
-        u32            wd[J][8];
-        const f16x2    bias1152 = {(f16)1152.0f, (f16)1152.0f};
-#pragma unroll
-        for (int i = 0; i < NMFMA; ++i) {
-            const int p = i >> 1, j = i & 1, e = p / (NP / 2), mt = p % (NP / 2);
-            acc[mt][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wcur.f[j][e], xw[p % WIN], acc[mt][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if ((i & 1) == 0) {  // the pair's first MFMA is issued: request pair p + DIST (its slot of the window was pair p + DIST - WIN's)
-                const int q = p + DIST;
-                if (q < NP) {
-                    xw[q % WIN] = __builtin_bit_cast(f16x8, lds_read16((q >= NP / 2 ? ca1 : ca0) + (q % (NP / 2)) * 32 * 128));
-                } else if constexpr (READ) {
-                    xw[q % WIN] = __builtin_bit_cast(f16x8, lds_read16(ra0 + (q - NP) * 32 * 128));
-                }
-            }
-            if constexpr (READ) {
-                if (i == 0) {
-                    fnext.wq[0] = lds_read16(rb0);
-                    fnext.wq[1] = lds_read16(rb1);
-                }
-                // dequant micro-ops, as in the 128 x 128 schedule: one kind of op on four half-dwords per gap, dependent ops a gap
-                // (deep tile: two gaps) apart; g = which of the 12 groups this gap carries, -1 = none
-                const int g = RB == 2 ? ((i >= 5 && i <= 27 && (i & 1)) ? (i - 5) / 2 : -1) : (i >= 4 ? i - 4 : -1);
-                if (g >= 0) {
-                    const int jj = g / 6, dp = (g / 3) & 1, kind = g % 3;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int h = 4 * dp + u, d = h >> 1;
-                        if (kind == 0) {
-                            const u32 wdw = d == 0 ? fnext.wq[jj].x : d == 1 ? fnext.wq[jj].y : d == 2 ? fnext.wq[jj].z : fnext.wq[jj].w;
-                            wd[jj][h] = __builtin_amdgcn_perm(wdw, 0x64646464u, (h & 1) ? 0x00070005u : 0x00060004u);
-                        } else if (kind == 1) {
-                            wd[jj][h] = as_u32(as_f16x2(wd[jj][h]) - bias1152);
-                        } else {
-                            wd[jj][h] = as_u32(as_f16x2(wd[jj][h]) * scale2[jj]);
-                        }
-                    }
-                    asm volatile("" ::"v"(wd[jj][4 * dp]), "v"(wd[jj][4 * dp + 1]), "v"(wd[jj][4 * dp + 2]), "v"(wd[jj][4 * dp + 3]));
-                }
-            }
-            if constexpr (DMA) {
-                if constexpr (RB == 2) {
-                    if (i == 1) dma_piece(std::integral_constant<int, 0>{});
-                    if (i == 3) dma_piece(std::integral_constant<int, 1>{});
-                    if (i == 4) dma_piece(std::integral_constant<int, 2>{});
-                    if (i == 8) dma_piece(std::integral_constant<int, 3>{});
-                    if (i == 12) dma_piece(std::integral_constant<int, 4>{});
-                    if (i == 16) dma_piece(std::integral_constant<int, 5>{});
-                    if (i == 20) dma_piece(std::integral_constant<int, 6>{});
-                    if (i == 24) dma_piece(std::integral_constant<int, 7>{});
-                    if (i == 26) dma_piece(std::integral_constant<int, 8>{});
-                    if (i == 28) dma_piece(std::integral_constant<int, 9>{});
-                } else {
-                    if (i == 0) dma_piece(std::integral_constant<int, 0>{});
-                    if (i == 1) dma_piece(std::integral_constant<int, 1>{});
-                    if (i == 3) dma_piece(std::integral_constant<int, 2>{});
-                    if (i == 5) dma_piece(std::integral_constant<int, 3>{});
-                    if (i == 8) dma_piece(std::integral_constant<int, 4>{});
-                }
-            }
-            if constexpr (READ) {
-                if (i == NMFMA - 4 + (RB == 2 ? 1 : 0)) {  // gap 12 / 29
-                    rd = rd + STAGE_BYTES == SMEM_BYTES ? 0 : rd + STAGE_BYTES;
-                    asm volatile("" : "+s"(rd));
-                }
-                if (i == NMFMA - 3 + (RB == 2 ? 1 : 0)) {  // gap 13 / 30: behind the step's last DMA piece
-                    wr = wr + STAGE_BYTES == SMEM_BYTES ? 0 : wr + STAGE_BYTES;
-                    ka += BK * 2;
-                    kb += kTileBytes;
-                    asm volatile("" : "+s"(wr), "+s"(ka), "+s"(kb));
-                }
-                if (i == NMFMA - 1) {  // behind the step's last fragment request
-                    ca0 = ra0;
-                    ca1 = ra1;
-                    ra0 = rd + c_a0;
-                    ra1 = rd + c_a1;
-                    rb0 = rd + c_b0;
-                    rb1 = rd + c_b1;
-                    asm volatile("" : "+v"(ca0), "+v"(ca1), "+v"(ra0), "+v"(ra1), "+v"(rb0), "+v"(rb1));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (READ) {
-#pragma unroll
-            for (int jj = 0; jj < J; ++jj) {
-                wnext.f[jj][0] = make_frag(as_f16x2(wd[jj][0]), as_f16x2(wd[jj][1]), as_f16x2(wd[jj][2]), as_f16x2(wd[jj][3]));
-                wnext.f[jj][1] = make_frag(as_f16x2(wd[jj][4]), as_f16x2(wd[jj][5]), as_f16x2(wd[jj][6]), as_f16x2(wd[jj][7]));
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-        }
-        }
-    };
-
     // ---- prologue: STAGES-1 stages in flight; stage 0 -> fragments ----
     asm volatile("" ::"v"(scale2[0]));
     {
         int pwr = 0, pka = k0 * BK * 2, pkb = k0 * kStepBytesB;
 #pragma unroll
-        for (int s = 0; s < ST - 1; ++s) {  // KT >= STAGES - 1 by launch contract
+        for (int s = 0; s < STAGES - 1; ++s) {  // KT >= STAGES - 1 by launch contract
 #pragma unroll
             for (int i = 0; i < PIECES; ++i) {  // plain form: voff carries -IMM, so the LDS address gets it back here
                 if (i < APW)
@@ -624,7 +508,7 @@ __device__ __forceinline__ void gemm_tile_body(
             pkb += kStepBytesB;
         }
     }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * PIECES) : "memory");  // stage 0 landed
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PIECES) : "memory");  // stage 0 landed
     __builtin_amdgcn_s_barrier();
     EETQ_GEMM_STAMP(1);
     Frags f0, f1;
@@ -632,15 +516,10 @@ __device__ __forceinline__ void gemm_tile_body(
     {
         f0.wq[0] = wq_read(c_b0);
         if constexpr (J == 2) f0.wq[1] = wq_read(c_b1);
-        if constexpr (RH * RB == 2) {  // the window's first pairs
 #pragma unroll
-            for (int q = 0; q < DIST; ++q) xw[q] = __builtin_bit_cast(f16x8, lds_read16(c_a0 + q * 32 * 128));
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                f0.xa[0][mt] = __builtin_bit_cast(f16x8, lds_read16(c_a0 + mt * 32 * 128));
-                f0.xa[1][mt] = __builtin_bit_cast(f16x8, lds_read16(c_a1 + mt * 32 * 128));
-            }
+        for (int mt = 0; mt < 4; ++mt) {
+            f0.xa[0][mt] = __builtin_bit_cast(f16x8, lds_read16(c_a0 + mt * 32 * 128));
+            f0.xa[1][mt] = __builtin_bit_cast(f16x8, lds_read16(c_a1 + mt * 32 * 128));
         }
 #pragma unroll
         for (int j = 0; j < J; ++j) {
@@ -657,17 +536,15 @@ __device__ __forceinline__ void gemm_tile_body(
     auto k_step = [&](auto rem_tag, const WFrag& wcur, const Frags& fcur, WFrag& wnext, Frags& fnext) {
         constexpr int REM = decltype(rem_tag)::value;
         if constexpr (REM >= 1) {
-            constexpr int younger = (REM - 1) < (ST - 3) ? (REM - 1) : (ST - 3);
+            constexpr int younger = (REM - 1) < (STAGES - 3) ? (REM - 1) : (STAGES - 3);
             if constexpr (!(ABLATE & 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(younger * PIECES) : "memory");
             if constexpr (!(ABLATE & 16)) __builtin_amdgcn_s_barrier();
-            if constexpr (RH * RB == 2) step_tall(wcur, std::true_type{}, fnext, wnext, std::integral_constant<bool, (REM >= ST - 1)>{});
-            else step(wcur, fcur, std::true_type{}, fnext, wnext, std::integral_constant<bool, (REM >= ST - 1)>{});
+            step(wcur, fcur, std::true_type{}, fnext, wnext, std::integral_constant<bool, (REM >= STAGES - 1)>{});
         } else {
-            if constexpr (RH * RB == 2) step_tall(wcur, std::false_type{}, fnext, wnext, std::false_type{});
-            else step(wcur, fcur, std::false_type{}, fnext, wnext, std::false_type{});
+            step(wcur, fcur, std::false_type{}, fnext, wnext, std::false_type{});
         }
     };
-    using Steady = std::integral_constant<int, ST - 1>;
+    using Steady = std::integral_constant<int, STAGES - 1>;
     const int tail = BITS == 4 ? 6 : (ksteps & 1) ? 5 : 6;  // int4: K % 128 == 0, the K-step count is even
     int       kt   = 0;
     for (; kt < ksteps - tail; kt += 2) {
@@ -695,199 +572,201 @@ __device__ __forceinline__ void gemm_tile_body(
     // writes scattered over 32 rows per instruction: 3.1 us of a 36.5 us kernel (tools/kbench_stamps gemmstamps).  Instead
     // group 0 rounds to fp16 (+ bias / activation) into a row-major LDS image of the tile, and all four waves write it out 16
     // bytes per lane, whole 256-byte rows (4 rows per wave instruction), adding the residual on the way. ----
+    // Two leftovers of the shelved 256-row tiles' two-phase epilogue (tools/experiments/tile_tall_deep.patch) stay for the code
+    // generator alone: the body sits in a loop of ONE trip, and a_hi above is always 0.  hipcc hoists the body's invariants above
+    // the barrier only out of a loop, and does not see wave < 2 CW behind the readfirstlane; without either, every kernel built
+    // from this body gets other register assignments and another instruction order, the K loop included
+    // (profiles/r14_tile_tall_deep_moved_out.txt).  With them, moving the two tiles out changed no instruction of a kernel
+    // that ships.  They go with the next change that measures this kernel again.
     EETQ_GEMM_STAMP(3);
-    // (tall tile: one 128-row half after the other -- the parked K half (64 KiB) and the fp16 image (34 KiB) of both do not fit)
 #pragma unroll
-    for (int ph = 0; ph < RH * RB; ++ph) {
-    const bool mine = RH == 1 || rh == ph;  // this wave's rows are the phase's
-    const int  ab   = RB == 2 ? 4 * ph : 0; // deep tile: the phase's four row blocks of this wave's eight
-    __builtin_amdgcn_s_barrier();
-    f32x4* red4 = reinterpret_cast<f32x4*>(smem) + (size_t)wn * (16 * J) * 64;  // [block][quad][lane]
-    if (grp == 1 && mine) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int j = 0; j < J; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    red4[((mt * J + j) * 4 + q) * 64 + lane] =
-                        f32x4{acc[ab + mt][j][4 * q], acc[ab + mt][j][4 * q + 1], acc[ab + mt][j][4 * q + 2], acc[ab + mt][j][4 * q + 3]};
-    }
-    __syncthreads();
-    EETQ_GEMM_STAMP(4);
-    if constexpr (SPLIT) {
-        // ---- this slice's partial tile -> slab; the last of the tile's S slices adds all of them in slice order ----
-        static_assert(!SPLIT || (CW == 2 && !ACT), "the split form exists for the 4-wave tile with the identity epilogue");
-        constexpr int kSlabFloats = BM * BN;
-        const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            slabs + (size_t)tile * S * kSlabFloats, 0, S * kSlabFloats * 4, 0x00020000);
-        // float4 index inside a slab: (((wn*4 + mt)*J + j)*4 + q)*64 + lane  (only the K-half-0 waves hold sums)
-        const int lane_off = (wn * 16 * J * 64 + lane) * 16;
-        if (grp == 0) {
+    for (int once = 0; once < 1; ++once) {  // (one trip: see above)
+        __builtin_amdgcn_s_barrier();
+        f32x4* red4 = reinterpret_cast<f32x4*>(smem) + (size_t)wn * (16 * J) * 64;  // [block][quad][lane]
+        if (grp == 1) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int j = 0; j < J; ++j)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 o = red4[((mt * J + j) * 4 + q) * 64 + lane];
-                        acc[mt][j][4 * q + 0] += o.x;
-                        acc[mt][j][4 * q + 1] += o.y;
-                        acc[mt][j][4 * q + 2] += o.z;
-                        acc[mt][j][4 * q + 3] += o.w;
-                    }
-            if (S > 1) {
+                    for (int q = 0; q < 4; ++q)
+                        red4[((mt * J + j) * 4 + q) * 64 + lane] =
+                            f32x4{acc[mt][j][4 * q], acc[mt][j][4 * q + 1], acc[mt][j][4 * q + 2], acc[mt][j][4 * q + 3]};
+        }
+        __syncthreads();
+        EETQ_GEMM_STAMP(4);
+        if constexpr (SPLIT) {
+            // ---- this slice's partial tile -> slab; the last of the tile's S slices adds all of them in slice order ----
+            static_assert(!SPLIT || (CW == 2 && !ACT), "the split form exists for the 4-wave tile with the identity epilogue");
+            constexpr int kSlabFloats = BM * BN;
+            const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                slabs + (size_t)tile * S * kSlabFloats, 0, S * kSlabFloats * 4, 0x00020000);
+            // float4 index inside a slab: (((wn*4 + mt)*J + j)*4 + q)*64 + lane  (only the K-half-0 waves hold sums)
+            const int lane_off = (wn * 16 * J * 64 + lane) * 16;
+            if (grp == 0) {
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                     for (int j = 0; j < J; ++j)
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            // (through named floats: __builtin_bit_cast applied directly to an element of the 16-wide
-                            // accumulator vector read element 0 for every index with this hipcc)
-                            const float f0 = acc[mt][j][4 * q + 0], f1 = acc[mt][j][4 * q + 1], f2 = acc[mt][j][4 * q + 2],
-                                        f3 = acc[mt][j][4 * q + 3];
-                            const u32x4 v = {__builtin_bit_cast(u32, f0), __builtin_bit_cast(u32, f1), __builtin_bit_cast(u32, f2),
-                                             __builtin_bit_cast(u32, f3)};
-                            // everything in the per-lane offset, soffset 0: hipcc then guards the store's data registers
-                            // itself (gemm_splitk_kernel.hpp has the story of the form it does not guard); the build
-                            // disassembles this object and fails if a store's data register is rewritten too early or
-                            // the uniform part ever moves into an SGPR soffset (tools/check_store_hazard.py, Makefile)
-                            __builtin_amdgcn_raw_buffer_store_b128(v, s_rsrc, slice * kSlabFloats * 4 + ((mt * J + j) * 4 + q) * 1024 + lane_off,
-                                                                   0, /*sc1*/ 16);
+                            const f32x4 o = red4[((mt * J + j) * 4 + q) * 64 + lane];
+                            acc[mt][j][4 * q + 0] += o.x;
+                            acc[mt][j][4 * q + 1] += o.y;
+                            acc[mt][j][4 * q + 2] += o.z;
+                            acc[mt][j][4 * q + 3] += o.w;
                         }
-            }
-        }
-        if (S > 1) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave drains its write-through stores
-            __syncthreads();
-            unsigned* flag = reinterpret_cast<unsigned*>(smem + SMEM_BYTES - 16);
-            if (tid == 0) *flag = __hip_atomic_fetch_add(counters + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            const unsigned ticket = *flag;
-            if ((ticket & (unsigned)(S - 1)) != (unsigned)(S - 1)) return;  // not the last slice of this tile
-            // All four waves read back: wave (grp, wn) takes row blocks 2*grp, 2*grp + 1 of its column half, every slice's
-            // float4s requested before the first is used (S * 8 * J loads in flight per lane), summed in slice order -- the
-            // last arriver's own slab like the others, so the result does not depend on who arrived last.
-            constexpr int kMaxS = J == 1 ? 4 : 2;  // slices a launch may use: the read-back keeps kMaxS * 8 * J float4 per lane
-            u32x4 part[kMaxS][2][J][4];
+                if (S > 1) {
 #pragma unroll
-            for (int sl = 0; sl < kMaxS; ++sl)
+                    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                        for (int j = 0; j < J; ++j)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                // (through named floats: __builtin_bit_cast applied directly to an element of the 16-wide
+                                // accumulator vector read element 0 for every index with this hipcc)
+                                const float f0 = acc[mt][j][4 * q + 0], f1 = acc[mt][j][4 * q + 1], f2 = acc[mt][j][4 * q + 2],
+                                            f3 = acc[mt][j][4 * q + 3];
+                                const u32x4 v = {__builtin_bit_cast(u32, f0), __builtin_bit_cast(u32, f1), __builtin_bit_cast(u32, f2),
+                                                 __builtin_bit_cast(u32, f3)};
+                                // everything in the per-lane offset, soffset 0: hipcc then guards the store's data registers
+                                // itself (gemm_splitk_kernel.hpp has the story of the form it does not guard); the build
+                                // disassembles this object and fails if a store's data register is rewritten too early or
+                                // the uniform part ever moves into an SGPR soffset (tools/check_store_hazard.py, Makefile)
+                                __builtin_amdgcn_raw_buffer_store_b128(v, s_rsrc, slice * kSlabFloats * 4 + ((mt * J + j) * 4 + q) * 1024 + lane_off,
+                                                                       0, /*sc1*/ 16);
+                            }
+                }
+            }
+            if (S > 1) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave drains its write-through stores
+                __syncthreads();
+                unsigned* flag = reinterpret_cast<unsigned*>(smem + SMEM_BYTES - 16);
+                if (tid == 0) *flag = __hip_atomic_fetch_add(counters + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __syncthreads();
+                const unsigned ticket = *flag;
+                if ((ticket & (unsigned)(S - 1)) != (unsigned)(S - 1)) return;  // not the last slice of this tile
+                // All four waves read back: wave (grp, wn) takes row blocks 2*grp, 2*grp + 1 of its column half, every slice's
+                // float4s requested before the first is used (S * 8 * J loads in flight per lane), summed in slice order -- the
+                // last arriver's own slab like the others, so the result does not depend on who arrived last.
+                constexpr int kMaxS = J == 1 ? 4 : 2;  // slices a launch may use: the read-back keeps kMaxS * 8 * J float4 per lane
+                u32x4 part[kMaxS][2][J][4];
+#pragma unroll
+                for (int sl = 0; sl < kMaxS; ++sl)
+#pragma unroll
+                    for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+                        for (int j = 0; j < J; ++j)
+#pragma unroll
+                            for (int q = 0; q < 4; ++q)  // slices beyond S: clamped address, value unused (no load behind a branch)
+                                part[sl][mm][j][q] = __builtin_amdgcn_raw_buffer_load_b128(
+                                    s_rsrc, (sl < S ? sl : S - 1) * kSlabFloats * 4 + (((2 * grp + mm) * J + j) * 4 + q) * 1024 + lane_off, 0, /*sc1*/ 16);
 #pragma unroll
                 for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
                     for (int j = 0; j < J; ++j)
 #pragma unroll
-                        for (int q = 0; q < 4; ++q)  // slices beyond S: clamped address, value unused (no load behind a branch)
-                            part[sl][mm][j][q] = __builtin_amdgcn_raw_buffer_load_b128(
-                                s_rsrc, (sl < S ? sl : S - 1) * kSlabFloats * 4 + (((2 * grp + mm) * J + j) * 4 + q) * 1024 + lane_off, 0, /*sc1*/ 16);
+                        for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int mm = 0; mm < 2; ++mm)
+                            for (int i = 0; i < 4; ++i) {
+                                float t = __builtin_bit_cast(float, (u32)part[0][mm][j][q][i]);
 #pragma unroll
-                for (int j = 0; j < J; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float t = __builtin_bit_cast(float, (u32)part[0][mm][j][q][i]);
-#pragma unroll
-                            for (int sl = 1; sl < kMaxS; ++sl) {
-                                const float v = __builtin_bit_cast(float, (u32)part[sl][mm][j][q][i]);
-                                t             = sl < S ? t + v : t;
+                                for (int sl = 1; sl < kMaxS; ++sl) {
+                                    const float v = __builtin_bit_cast(float, (u32)part[sl][mm][j][q][i]);
+                                    t             = sl < S ? t + v : t;
+                                }
+                                // both row blocks of this wave end up in acc[mm] .. the epilogue below maps them back to 2*grp + mm
+                                if (mm == 0) acc[0][j][4 * q + i] = t; else acc[1][j][4 * q + i] = t;
                             }
-                            // both row blocks of this wave end up in acc[mm] .. the epilogue below maps them back to 2*grp + mm
-                            if (mm == 0) acc[0][j][4 * q + i] = t; else acc[1][j][4 * q + i] = t;
-                        }
+            }
         }
-    }
-    constexpr int kRowHalfs = BN + 8;                       // row stride of the image: 272 / 144 bytes (bank shift per row)
-    f16* image = reinterpret_cast<f16*>(smem + CW * (16 * J) * 64 * 16);  // behind every column part's parked accumulators
-    static_assert(CW * (16 * J) * 64 * 16 + BM * kRowHalfs * 2 <= SMEM_BYTES, "the output image must fit behind the parked halves");
-    // who rounds which row blocks into the image: the K-half-0 waves all four -- or, after a split read-back, every wave the two
-    // it summed (held in acc[0], acc[1])
-    const bool summed = SPLIT && S > 1;
-    if ((grp == 0 && mine) || summed) {
+        constexpr int kRowHalfs = BN + 8;                       // row stride of the image: 272 / 144 bytes (bank shift per row)
+        f16* image = reinterpret_cast<f16*>(smem + CW * (16 * J) * 64 * 16);  // behind every column part's parked accumulators
+        static_assert(CW * (16 * J) * 64 * 16 + BM * kRowHalfs * 2 <= SMEM_BYTES, "the output image must fit behind the parked halves");
+        // who rounds which row blocks into the image: the K-half-0 waves all four -- or, after a split read-back, every wave the two
+        // it summed (held in acc[0], acc[1])
+        const bool summed = SPLIT && S > 1;
+        if (grp == 0 || summed) {
 #pragma unroll
-        for (int mt_ = 0; mt_ < 4; ++mt_) {
-            if (summed && mt_ >= 2) break;
-            const int mt = summed ? 2 * grp + mt_ : mt_;  // row block of the tile; its sums sit in acc[mt_]
+            for (int mt_ = 0; mt_ < 4; ++mt_) {
+                if (summed && mt_ >= 2) break;
+                const int mt = summed ? 2 * grp + mt_ : mt_;  // row block of the tile; its sums sit in acc[mt_]
 #pragma unroll
-            for (int j = 0; j < J; ++j) {
-                const int ncol = wn * WN_COLS + 32 * j + 4 * fh;  // tile-local column of quad 0
+                for (int j = 0; j < J; ++j) {
+                    const int ncol = wn * WN_COLS + 32 * j + 4 * fh;  // tile-local column of quad 0
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    // (SPLIT: the other K half -- and the other slices -- were added above)
-                    const f32x4 o  = SPLIT ? f32x4{0.f, 0.f, 0.f, 0.f} : red4[((mt * J + j) * 4 + q) * 64 + lane];
-                    const float a4[4] = {acc[ab + mt_][j][4 * q + 0] + o.x, acc[ab + mt_][j][4 * q + 1] + o.y, acc[ab + mt_][j][4 * q + 2] + o.z,
-                                         acc[ab + mt_][j][4 * q + 3] + o.w};
-                    f16x2      lo = {}, hi = {};
-                    const bool in_n = n0 + ncol + 8 * q < N;  // columns beyond a ragged launch edge: nothing to read or keep
-                    if constexpr (ACT) {
-                        if (in_n) finish_quad(a4, ep, n0 + ncol + 8 * q, lo, hi);
-                    } else {  // identity: round to fp16, then the fp16 bias add (the reference's `output + bias`)
-                        lo = f16x2{(f16)a4[0], (f16)a4[1]};
-                        hi = f16x2{(f16)a4[2], (f16)a4[3]};
-                        if (ep.bias && in_n) {
-                            const u32x2 b = *reinterpret_cast<const u32x2*>(ep.bias + n0 + ncol + 8 * q);
-                            lo            = lo + as_f16x2(b.x);
-                            hi            = hi + as_f16x2(b.y);
+                    for (int q = 0; q < 4; ++q) {
+                        // (SPLIT: the other K half -- and the other slices -- were added above)
+                        const f32x4 o  = SPLIT ? f32x4{0.f, 0.f, 0.f, 0.f} : red4[((mt * J + j) * 4 + q) * 64 + lane];
+                        const float a4[4] = {acc[mt_][j][4 * q + 0] + o.x, acc[mt_][j][4 * q + 1] + o.y, acc[mt_][j][4 * q + 2] + o.z,
+                                             acc[mt_][j][4 * q + 3] + o.w};
+                        f16x2      lo = {}, hi = {};
+                        const bool in_n = n0 + ncol + 8 * q < N;  // columns beyond a ragged launch edge: nothing to read or keep
+                        if constexpr (ACT) {
+                            if (in_n) finish_quad(a4, ep, n0 + ncol + 8 * q, lo, hi);
+                        } else {  // identity: round to fp16, then the fp16 bias add (the reference's `output + bias`)
+                            lo = f16x2{(f16)a4[0], (f16)a4[1]};
+                            hi = f16x2{(f16)a4[2], (f16)a4[3]};
+                            if (ep.bias && in_n) {
+                                const u32x2 b = *reinterpret_cast<const u32x2*>(ep.bias + n0 + ncol + 8 * q);
+                                lo            = lo + as_f16x2(b.x);
+                                hi            = hi + as_f16x2(b.y);
+                            }
                         }
+                        *reinterpret_cast<u32x2*>(image + (mt * 32 + fn) * kRowHalfs + ncol + 8 * q) = u32x2{as_u32(lo), as_u32(hi)};
                     }
-                    *reinterpret_cast<u32x2*>(image + (mt * 32 + fn) * kRowHalfs + ncol + 8 * q) = u32x2{as_u32(lo), as_u32(hi)};
                 }
             }
         }
-    }
-    __syncthreads();
-    if constexpr (GLU) {
-        static_assert(!GLU || (!ACT && !SPLIT), "the gated write-out exists for the unsplit identity tile");
-        constexpr int kLanesPerRow = BN / 16, kRowsPerWave = 64 / kLanesPerRow, kRowsPerRound = NW * kRowsPerWave;
-        const int     c            = (lane % kLanesPerRow) * 16;  // one group per lane: 8 gate + 8 up halfs -> 8 outputs
+        __syncthreads();
+        if constexpr (GLU) {
+            static_assert(!GLU || (!ACT && !SPLIT), "the gated write-out exists for the unsplit identity tile");
+            constexpr int kLanesPerRow = BN / 16, kRowsPerWave = 64 / kLanesPerRow, kRowsPerRound = NW * kRowsPerWave;
+            const int     c            = (lane % kLanesPerRow) * 16;  // one group per lane: 8 gate + 8 up halfs -> 8 outputs
 #pragma unroll
-        for (int r0 = 0; r0 < BM; r0 += kRowsPerRound) {
-            const int r = r0 + wave * kRowsPerWave + lane / kLanesPerRow;
-            const int m = m0 + ph * BM + r;
-            if (m < M && n0 + c < N) {
-                const f16x8 g = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c));
-                const f16x8 u = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c + 8));
-                f16x8       o;
+            for (int r0 = 0; r0 < BM; r0 += kRowsPerRound) {
+                const int r = r0 + wave * kRowsPerWave + lane / kLanesPerRow;
+                const int m = m0 + r;
+                if (m < M && n0 + c < N) {
+                    const f16x8 g = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c));
+                    const f16x8 u = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c + 8));
+                    f16x8       o;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = silu_mul_f16(g[j], u[j]);
-                *reinterpret_cast<f16x8*>(y + (size_t)m * ldc + ((n0 + c) >> 1)) = o;
-            }
-        }
-    } else {
-        constexpr int kLanesPerRow = BN / 8, kRowsPerWave = 64 / kLanesPerRow, kRowsPerRound = NW * kRowsPerWave;
-        const int     c            = (lane % kLanesPerRow) * 8;
-#pragma unroll
-        for (int r0 = 0; r0 < BM; r0 += kRowsPerRound) {
-            const int r = r0 + wave * kRowsPerWave + lane / kLanesPerRow;
-            const int m = m0 + ph * BM + r;
-            if (m < M && n0 + c < N) {
-                u32x4 v = *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c);
-                if (ep.residual) {
-                    const u32x4 rr = *reinterpret_cast<const u32x4*>(ep.residual + (size_t)m * ldc + n0 + c);
-                    v.x = as_u32(as_f16x2(v.x) + as_f16x2(rr.x));
-                    v.y = as_u32(as_f16x2(v.y) + as_f16x2(rr.y));
-                    v.z = as_u32(as_f16x2(v.z) + as_f16x2(rr.z));
-                    v.w = as_u32(as_f16x2(v.w) + as_f16x2(rr.w));
+                    for (int j = 0; j < 8; ++j) o[j] = silu_mul_f16(g[j], u[j]);
+                    *reinterpret_cast<f16x8*>(y + (size_t)m * ldc + ((n0 + c) >> 1)) = o;
                 }
-                *reinterpret_cast<u32x4*>(y + (size_t)m * ldc + n0 + c) = v;
+            }
+        } else {
+            constexpr int kLanesPerRow = BN / 8, kRowsPerWave = 64 / kLanesPerRow, kRowsPerRound = NW * kRowsPerWave;
+            const int     c            = (lane % kLanesPerRow) * 8;
+#pragma unroll
+            for (int r0 = 0; r0 < BM; r0 += kRowsPerRound) {
+                const int r = r0 + wave * kRowsPerWave + lane / kLanesPerRow;
+                const int m = m0 + r;
+                if (m < M && n0 + c < N) {
+                    u32x4 v = *reinterpret_cast<const u32x4*>(image + r * kRowHalfs + c);
+                    if (ep.residual) {
+                        const u32x4 rr = *reinterpret_cast<const u32x4*>(ep.residual + (size_t)m * ldc + n0 + c);
+                        v.x = as_u32(as_f16x2(v.x) + as_f16x2(rr.x));
+                        v.y = as_u32(as_f16x2(v.y) + as_f16x2(rr.y));
+                        v.z = as_u32(as_f16x2(v.z) + as_f16x2(rr.z));
+                        v.w = as_u32(as_f16x2(v.w) + as_f16x2(rr.w));
+                    }
+                    *reinterpret_cast<u32x4*>(y + (size_t)m * ldc + n0 + c) = v;
+                }
             }
         }
-    }
-    if constexpr (RH * RB > 1) __syncthreads();  // the next phase reuses the parked area and the image
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     EETQ_GEMM_STAMP(5);
 }
 
-template <int ABLATE, int J, bool ACT = false, int CW = 2, bool GLU = false, int RH = 1, int RB = 1>
-__global__ __launch_bounds__(128 * CW * RH, 1) void gemm_tile_kernel(
+template <int ABLATE, int J, bool ACT = false, int CW = 2, bool GLU = false>
+__global__ __launch_bounds__(128 * CW, 1) void gemm_tile_kernel(
     const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales,
     f16* __restrict__ y, int M, int N, int K, int ldc, Epilogue ep)
 {
-    gemm_tile_body<ABLATE, J, ACT, CW, false, GLU, RH, RB>(x, w, scales, y, M, N, K, ldc, ep, 1, nullptr, nullptr);
+    gemm_tile_body<ABLATE, J, ACT, CW, false, GLU>(x, w, scales, y, M, N, K, ldc, ep, 1, nullptr, nullptr);
 }
 
 // Round 5, measured and shelved with their patch (tools/experiments/tile_ring_depth_and_persistent.patch): the

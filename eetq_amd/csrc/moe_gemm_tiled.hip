@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256, 1) void moe_gemm_tile_kernel(const f16* __rest
                                                                const f16* __restrict__ scales, f16* __restrict__ y, int N, int K,
                                                                int ldc, GroupMap map)
 {
-    gemm_tile_body<0, J, false, 2, false, GLU, 1, 1, true>(x, w, scales, y, 0, N, K, ldc, Epilogue{}, 1, nullptr, nullptr, map);
+    gemm_tile_body<0, J, false, 2, false, GLU, true>(x, w, scales, y, 0, N, K, ldc, Epilogue{}, 1, nullptr, nullptr, map);
 }
 
 }  // namespace
@@ -61,32 +61,20 @@ int launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, con
                           const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream)
 {
     if (!moe_gemm_tiled_supports(T, k, E, N, K, gather)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs moe_gemm_kernel
-    const int S = T * k, A = S < E ? S : E, R = S / BM + A;
-    GroupMap  map;
-    map.offsets     = offsets;
-    map.sorted_slot = sorted_slot;
-    map.active      = active;
-    map.topk        = gather ? k : 0;
-    map.A           = A;
-    map.R           = R;
-    map.x_rows      = gather ? T : S;
+    const int      S   = T * k;
+    const GroupMap map = make_group_map(offsets, sorted_slot, active, T, k, E, gather);
     static const int force_j = [] {  // EETQ_AMD_MOE_TILE_J = 1 / 2 (behind EETQ_AMD_TUNING): A/B runs of the two tile shapes
         const char* e = tuning_env("EETQ_AMD_MOE_TILE_J");
         return e ? atoi(e) : 0;
     }();
     const bool narrow = force_j == 1 || (force_j != 2 && moe_tiled_narrow(S, E, N));
     const int  ldc    = glu8 ? N / 2 : N;
-    auto go = [&](auto kern, std::atomic<unsigned long long>& opted, int bn, size_t smem) -> int {
-        int st = opt_in_large_lds(kern, opted);  // > 64 KiB of dynamic LDS: once per kernel and device
-        if (st != EETQ_OK) return st;
-        launch_kernel(kern, dim3((unsigned)(R * ((N + bn - 1) / bn))), dim3(256), smem, stream, x, w, scales, y, N, K, ldc, map);
-        return check_hip(hipGetLastError(), "moe_gemm_tile_kernel launch");
-    };
-    static std::atomic<unsigned long long> o1{0}, o2{0}, o1g{0}, o2g{0};
-    if (glu8 && narrow) return go(moe_gemm_tile_kernel<1, true>, o1g, TileCfg<1>::BN, TileCfg<1>::SMEM_BYTES);
-    if (glu8) return go(moe_gemm_tile_kernel<2, true>, o2g, TileCfg<2>::BN, TileCfg<2>::SMEM_BYTES);
-    if (narrow) return go(moe_gemm_tile_kernel<1, false>, o1, TileCfg<1>::BN, TileCfg<1>::SMEM_BYTES);
-    return go(moe_gemm_tile_kernel<2, false>, o2, TileCfg<2>::BN, TileCfg<2>::SMEM_BYTES);
+    const int  bn     = narrow ? TileCfg<1>::BN : TileCfg<2>::BN;
+    // [narrow][GLU]; > 64 KiB of dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
+    static LargeLdsKernel<decltype(&moe_gemm_tile_kernel<2, false>)> kernels[2][2] = {
+        {{moe_gemm_tile_kernel<2, false>}, {moe_gemm_tile_kernel<2, true>}}, {{moe_gemm_tile_kernel<1, false>}, {moe_gemm_tile_kernel<1, true>}}};
+    return launch_large_lds(kernels[narrow][glu8], "moe_gemm_tile_kernel launch", dim3((unsigned)(map.R * ((N + bn - 1) / bn))), dim3(256),
+                            narrow ? TileCfg<1>::SMEM_BYTES : TileCfg<2>::SMEM_BYTES, stream, x, w, scales, y, N, K, ldc, map);
 }
 
 }  // namespace eetq

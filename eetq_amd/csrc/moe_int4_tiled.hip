@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256, 1) void moe_gemm_tile_i4_kernel(const f16* __r
                                                                   const f16* __restrict__ scales, f16* __restrict__ y, int N, int K,
                                                                   int ldc, GroupMap map)
 {
-    gemm_tile_body<0, J, false, 2, false, GLU, 1, 1, true, 4>(x, w, scales, y, 0, N, K, ldc, Epilogue{}, 1, nullptr, nullptr, map);
+    gemm_tile_body<0, J, false, 2, false, GLU, true, 4>(x, w, scales, y, 0, N, K, ldc, Epilogue{}, 1, nullptr, nullptr, map);
 }
 
 // the int8 tile's limits (moe_gemm_tiled_supports) and the int4 layout's: whole 128-deep tiles, and at least kMinKSteps + 1 K steps
@@ -44,32 +44,20 @@ int eetq_w4a16_moe_gemm_tiled(const void* x, const int8_t* w_packed_i4, const vo
     if (st != EETQ_OK) return st;
     EETQ_REQUIRE(tile_j >= 0 && tile_j <= 2, "eetq_w4a16_moe_gemm_tiled: tile_j is 0 (the launcher's rule), 1 (128 x 64) or 2 (128 x 128)");
     if (!supports(T, k, E, N, K, gather != 0)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs eetq_w4a16_moe_gemm
-    const int S = T * k, A = S < E ? S : E, R = S / BM + A;
-    GroupMap  map;
-    map.offsets     = offsets;
-    map.sorted_slot = sorted_slot;
-    map.active      = active;
-    map.topk        = gather ? k : 0;
-    map.A           = A;
-    map.R           = R;
-    map.x_rows      = gather ? T : S;
-    const bool narrow = tile_j == 1 || (tile_j == 0 && moe_tiled_narrow(S, E, N));
+    const GroupMap map    = make_group_map(offsets, sorted_slot, active, T, k, E, gather != 0);
+    const bool     narrow = tile_j == 1 || (tile_j == 0 && moe_tiled_narrow(T * k, E, N));
     const int  ldc    = glu8 ? N / 2 : N;
-    auto go = [&](auto kern, std::atomic<unsigned long long>& opted, int bn, size_t smem) -> int {
-        int rc = opt_in_large_lds(kern, opted);  // > 64 KiB of dynamic LDS: once per kernel and device
-        if (rc != EETQ_OK) return rc;
-        launch_kernel(kern, dim3((unsigned)(R * ((N + bn - 1) / bn))), dim3(256), smem, static_cast<hipStream_t>(stream),
-                      static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed_i4), static_cast<const f16*>(scales),
-                      static_cast<f16*>(y), N, K, ldc, map);
-        return check_hip(hipGetLastError(), "moe_gemm_tile_i4_kernel launch");
-    };
-    using C1 = TileCfg<1, 2, 1, 1, 4>;
-    using C2 = TileCfg<2, 2, 1, 1, 4>;
-    static std::atomic<unsigned long long> o1{0}, o2{0}, o1g{0}, o2g{0};
-    if (glu8 && narrow) return go(moe_gemm_tile_i4_kernel<1, true>, o1g, C1::BN, C1::SMEM_BYTES);
-    if (glu8) return go(moe_gemm_tile_i4_kernel<2, true>, o2g, C2::BN, C2::SMEM_BYTES);
-    if (narrow) return go(moe_gemm_tile_i4_kernel<1, false>, o1, C1::BN, C1::SMEM_BYTES);
-    return go(moe_gemm_tile_i4_kernel<2, false>, o2, C2::BN, C2::SMEM_BYTES);
+    using C1 = TileCfg<1, 2, 4>;
+    using C2 = TileCfg<2, 2, 4>;
+    const int bn = narrow ? C1::BN : C2::BN;
+    // [narrow][GLU]; > 64 KiB of dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
+    static LargeLdsKernel<decltype(&moe_gemm_tile_i4_kernel<2, false>)> kernels[2][2] = {
+        {{moe_gemm_tile_i4_kernel<2, false>}, {moe_gemm_tile_i4_kernel<2, true>}},
+        {{moe_gemm_tile_i4_kernel<1, false>}, {moe_gemm_tile_i4_kernel<1, true>}}};
+    return launch_large_lds(kernels[narrow][glu8 != 0], "moe_gemm_tile_i4_kernel launch", dim3((unsigned)(map.R * ((N + bn - 1) / bn))),
+                            dim3(256), narrow ? C1::SMEM_BYTES : C2::SMEM_BYTES, static_cast<hipStream_t>(stream),
+                            static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed_i4), static_cast<const f16*>(scales),
+                            static_cast<f16*>(y), N, K, ldc, map);
 }
 
 int eetq_w4a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather)

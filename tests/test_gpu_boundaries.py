@@ -140,41 +140,33 @@ print("AUTO_IS_MID", int(torch.equal(auto, mid)), "AUTO_IS_SPLIT", int(torch.equ
     assert outs["1"][3] == "1", outs                                # default: AUTO == split-K
 
 
-_TALL_CHILD = r"""
-import sys, numpy as np, torch
-sys.path.insert(0, {root!r})
-import eetq_amd.ops as ops
-out = {{}}
-for K, N, M in {cases!r}:
-    g = torch.Generator(device="cuda:0").manual_seed(K + N + M)
-    w = torch.randint(-128, 127, (K, N), dtype=torch.int8, device="cuda:0", generator=g)
-    s = torch.rand(N, dtype=torch.float16, device="cuda:0", generator=g) * 0.01
-    x = torch.randn(M, K, dtype=torch.float16, device="cuda:0", generator=g)
-    b = torch.randn(N, dtype=torch.float16, device="cuda:0", generator=g)
-    r = torch.randn(M, N, dtype=torch.float16, device="cuda:0", generator=g)
-    out["%d_%d_%d" % (K, N, M)] = ops.w8_a16_gemm(x, w, s, path="mfma", bias=b, residual=r).cpu().numpy()
-np.savez({dst!r}, **out)
-"""
+def _tier_a(y, ref):  # the suite's GEMM bar against the oracle contract (test_gpu_parity.py)
+    y, ref = y.astype(np.float32), ref.astype(np.float32)
+    return np.abs(y - ref) <= 1e-3 * np.abs(ref).max() + 2e-3 * np.abs(ref)
 
 
-def test_tall_tile_equals_the_128_row_tile(tmp_path):
-    """(and the deep tile, RB = 2: 256 x 128 on FOUR waves with 256 accumulators per lane, hook value 2)  The 256 x 128 tile on eight waves (gemm_tile_kernel<..., RH = 2>: both row halves read one weight stage, activation fragments
-    through a four-deep window, two-phase epilogue; measured 5 - 23 % behind the 128 x 128 tile and therefore only reachable through
-    the A/B hook EETQ_AMD_TILE_TALL) must give the 128-row tile's BITS: whole and ragged row tiles, ragged column edge, bias and
-    residual, an odd and an even number of K steps."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cases = [(4096, 4096, 2048), (1024, 640, 300), (704, 4096, 1000), (2048, 1008, 513)]
-    got = {}
-    for name, hook in (("tile128", None), ("tall256", "1"), ("deep256", "2")):
-        dst = str(tmp_path / (name + ".npz"))
-        env = dict(os.environ)
-        if hook:
-            env.update(EETQ_AMD_TUNING="1", EETQ_AMD_TILE_TALL=hook)
-        r = subprocess.run([sys.executable, "-c", _TALL_CHILD.format(root=root, cases=cases, dst=dst)], env=env, capture_output=True,
-                           text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-3000:]
-        got[name] = np.load(dst)
-    for key in got["tile128"].files:
-        assert np.array_equal(got["tile128"][key], got["tall256"][key]), key
-        assert np.array_equal(got["tile128"][key], got["deep256"][key]), key
+def test_mfma_tile_whole_and_ragged_tiles_odd_and_even_k_steps(oracle):
+    """Written to compare the 128-row tile with the 256-row tiles that were shelved (tools/experiments/tile_tall_deep.patch, whose
+    A/B script checks bit identity on these shapes); kept as coverage of the tiled kernel on them: whole and ragged row tiles, a
+    ragged column edge, an odd and an even number of K steps.  Per case: two launches give the same bits; the fused bias and
+    residual are the separate fp16 adds, bit for bit; tier A against the oracle on the first and last 128 rows x the first and
+    last 64 columns (the ragged corner included)."""
+    import eetq_amd.ops as ops
+    for K, N, M in [(4096, 4096, 2048), (1024, 640, 300), (704, 4096, 1000), (2048, 1008, 513)]:
+        g = torch.Generator(device=DEV).manual_seed(K + N + M)
+        q = torch.randint(-128, 127, (K, N), dtype=torch.int8, device=DEV, generator=g)
+        s = torch.rand(N, dtype=torch.float16, device=DEV, generator=g) * 0.01
+        x = torch.randn(M, K, dtype=torch.float16, device=DEV, generator=g)
+        b = torch.randn(N, dtype=torch.float16, device=DEV, generator=g)
+        r = torch.randn(M, N, dtype=torch.float16, device=DEV, generator=g)
+        qn, sn, xn = q.cpu().numpy(), s.cpu().numpy(), x.cpu().numpy()
+        w = torch.from_numpy(oracle.gfx950_pack(qn)).to(DEV)
+        y = ops.w8_a16_gemm(x, w, s, path="mfma")
+        assert torch.equal(y, ops.w8_a16_gemm(x, w, s, path="mfma")), (K, N, M)
+        assert torch.equal(ops.w8_a16_gemm(x, w, s, path="mfma", bias=b, residual=r), (y + b) + r), (K, N, M)
+        got = y.cpu().numpy()
+        for rows in (slice(0, 128), slice(M - 128, M)):
+            for cols in (slice(0, 64), slice(N - 64, N)):
+                ref = oracle.w8a16_gemm(xn[rows], np.ascontiguousarray(qn[:, cols]), np.ascontiguousarray(sn[cols]))
+                err = np.abs(got[rows, cols].astype(np.float32) - ref.astype(np.float32)).max()
+                assert _tier_a(got[rows, cols], ref).all(), (K, N, M, rows, cols, err)
