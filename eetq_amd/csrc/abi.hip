@@ -481,6 +481,18 @@ int eetq_w8a16_gemm_t(const void* in, const void* weight, const void* scale, voi
                          static_cast<f16*>(out), M, N, K, static_cast<hipStream_t>(stream));
 }
 
+int eetq_w4a16_gemm_t(const void* in, const void* weight_i4, const void* scale, void* out, int M, int N, int K, void* stream)
+{
+    EETQ_REQUIRE(in && weight_i4 && scale && out, "eetq_w4a16_gemm_t: null pointer");
+    EETQ_REQUIRE(M >= 1 && N >= 1 && K >= 1, "eetq_w4a16_gemm_t: invalid GEMM shape");
+    EETQ_REQUIRE(K % 128 == 0, "eetq_w4a16_gemm_t: int4: k must be a multiple of 128");
+    EETQ_REQUIRE(N % 16 == 0, "eetq_w4a16_gemm_t: n must be a multiple of 16");
+    EETQ_REQUIRE(((uintptr_t)in | (uintptr_t)weight_i4 | (uintptr_t)out) % 16 == 0 && (uintptr_t)scale % 2 == 0,
+                 "eetq_w4a16_gemm_t: in, weight and out must be 16-byte aligned");
+    return launch_gemm_t_i4(static_cast<const f16*>(in), static_cast<const uint8_t*>(weight_i4), static_cast<const f16*>(scale),
+                            static_cast<f16*>(out), M, N, K, static_cast<hipStream_t>(stream));
+}
+
 int eetq_w8a16_gemm_bias(const void* x, const int8_t* w_packed, const void* scales, const void* bias, void* y, int M,
                          int N, int K, int path, void* stream)
 {

@@ -283,6 +283,8 @@ int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue
                      hipStream_t stream);
 // input gradient dx[M][K] = dy[M][N] . fp16(q s)^T of the int8 weight in its native [K][N] layout (gemm_t.hip)
 int launch_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, int M, int N, int K, hipStream_t stream);
+// the same from the gfx950 int4 tiles of a [K][N/2] weight, K % 128 == 0 (gemm_t_int4.hip); same bits as launch_gemm_t on the same integers
+int launch_gemm_t_i4(const f16* dy, const uint8_t* w, const f16* scales, f16* dx, int M, int N, int K, hipStream_t stream);
 // the same per expert over an [E][K][N] stack: rows offsets[e] .. offsets[e + 1] - 1 of dy [S][N] / dx [S][K] (gemm_t.hip)
 int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
                       int E, int N, int K, hipStream_t stream);

@@ -472,6 +472,39 @@ Tensor w8_a16_gemm_t(const Tensor& input, const Tensor& weight, const Tensor& sc
     return output;
 }
 
+// The same from a packed int4 [K, N/2] weight in the gfx950 int4 layout (eetq_w4a16_gemm_t): the input gradient of W4A16Linear,
+// the bits of w8_a16_gemm_t on the same integers held as int8.  Checks as above, all before any GPU work.
+Tensor w4_a16_gemm_t(const Tensor& input, const Tensor& weight, const Tensor& scale)
+{
+    TORCH_CHECK(input.is_cuda() && weight.is_cuda() && scale.is_cuda(), "w4_a16_gemm_t: input, weight and scale must be GPU tensors");
+    TORCH_CHECK(input.scalar_type() == at::kHalf, "w4_a16_gemm_t: input must be float16 (got ", input.scalar_type(), ")");
+    TORCH_CHECK(weight.dim() == 2 && weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf,
+                "w4_a16_gemm_t: weight must be an int8 [K, N/2] tensor (packed int4) and scale float16");
+    TORCH_CHECK(weight.device() == input.device() && scale.device() == input.device(),
+                "w4_a16_gemm_t: input, weight and scale must be on the same device");
+    const int64_t k = weight.size(0), half = weight.size(1), n = 2 * half;
+    TORCH_CHECK(half == 0 || scale.numel() != half,
+                "w4_a16_gemm_t: weight must be packed int4 [K, N/2] (got an int8 [K, N] weight with N scales: that is w8_a16_gemm_t's)");
+    TORCH_CHECK(scale.numel() == n, "w4_a16_gemm_t: scale must have N = ", n, " elements (got ", scale.numel(), ")");
+    TORCH_CHECK(input.dim() >= 1 && input.size(-1) == n, "w4_a16_gemm_t: weight is [", k, ", ", n, " / 2] but input has N=",
+                input.dim() >= 1 ? input.size(-1) : 0);
+    TORCH_CHECK(k % 128 == 0 && n % 16 == 0, "w4_a16_gemm_t: the int4 layout needs K % 128 == 0 and N % 16 == 0 (got K=", k, ", N=", n,
+                ")");
+    TORCH_CHECK(weight.is_contiguous() && scale.is_contiguous(), "w4_a16_gemm_t: weight and scale must be contiguous");
+    std::vector<int64_t> shape(input.sizes().begin(), input.sizes().end());
+    shape.back()        = k;
+    Tensor        output = torch::empty(shape, input.options());
+    const int64_t m      = n ? input.numel() / n : 0;
+    if (m == 0 || k == 0) return output;
+    TORCH_CHECK(m <= INT32_MAX, "w4_a16_gemm_t: too many rows");
+    Tensor x = input.contiguous();  // a stride-0 gradient (y.sum().backward()) is materialised here
+    if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+    c10::DeviceGuard guard(input.device());
+    check(eetq_w4a16_gemm_t(x.data_ptr(), weight.data_ptr(), scale.data_ptr(), output.data_ptr(), (int)m, (int)n, (int)k,
+                            stream_of(input)));
+    return output;
+}
+
 // ---- side ops ---------------------------------------------------------------------------------------------------------
 // reference: layernorm_forward_cuda, layernorm.cu:98-113 (returns void; current stream here, default stream there)
 void layernorm_forward(const Tensor& input, const Tensor& gamma, Tensor& out, double eps)
@@ -1518,6 +1551,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("eps"));
     // ---- extensions of this library ----------------------------------------------------------------------------------
     m.def("w8_a16_gemm_t", &w8_a16_gemm_t, "input gradient of the weight-only gemm: input . dequant(weight)^T",
+          py::arg("input"), py::arg("weight"), py::arg("scale"));
+    m.def("w4_a16_gemm_t", &w4_a16_gemm_t, "the same from a packed int4 [K, N/2] weight in the gfx950 int4 layout",
           py::arg("input"), py::arg("weight"), py::arg("scale"));
     m.def("unprocess_weights", &unprocess_weights, "inverse of preprocess_weights", py::arg("processed_weight"),
           py::arg("layout") = "gfx950", py::arg("is_int4") = false);

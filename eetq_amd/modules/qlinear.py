@@ -17,12 +17,13 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from ..ops import (moe_router, moe_router_sigmoid, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block,
-                   w4_a16_moe_direct_supported,
+                   w4_a16_gemm_t, w4_a16_moe_direct_supported,
                    w4_a16_moe_block_sigmoid, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
                    w8_a16_moe_block_sigmoid, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
 __all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
+           "W4A16LinearMMFunction", "input_grad_i4",
            "W8A16MoeFunction", "EetqTopKRouter", "EetqSparseMoeBlock"]
 
 
@@ -103,7 +104,12 @@ class W8A16Linear(nn.Module):
 class W4A16Linear(nn.Module):
     """int4 weight-only linear layer (extension; the reference binds int4 quantisation -- ``quant_weights(w, torch.quint4x2)``
     -- but no int4 GEMM): packed ``qweight`` int8 [in, out / 2] (two values per byte) in the gfx950 int4 layout, fp16
-    ``weight_scales`` [out].  Needs in_features % 128 == 0 and out_features % 16 == 0."""
+    ``weight_scales`` [out].  Needs in_features % 128 == 0 and out_features % 16 == 0.  Inference-only unless ``trainable`` is
+    set (``eet_quantize(..., bits=4, trainable=True)`` or ``utils.set_trainable``): then a call in grad mode whose input requires
+    grad and that passes no ``residual`` runs through :class:`W4A16LinearMMFunction` -- the same output bits, and an input
+    gradient from ``w4_a16_gemm_t`` (the int4 weight stays frozen)."""
+
+    trainable = False   # a plain attribute, not a buffer: state dicts do not change
 
     def __init__(self, in_features, out_features, bias=True, dev="cuda:0"):
         super().__init__()
@@ -131,9 +137,11 @@ class W4A16Linear(nn.Module):
         mod.weight_scales = scales.half().to(dev)
         return mod
 
-    @torch.no_grad()
     def forward(self, input, residual=None):
-        return w8_a16_gemm(input, self.qweight, self.weight_scales, bias=self.bias, residual=residual)
+        if self.trainable and torch.is_grad_enabled() and input.requires_grad and residual is None:
+            return W4A16LinearMMFunction.apply(input, self.qweight, self.weight_scales, self.bias)
+        with torch.no_grad():
+            return w8_a16_gemm(input, self.qweight, self.weight_scales, bias=self.bias, residual=residual)
 
     def extra_repr(self):
         return "in_features={}, out_features={}, bias={}, bits=4".format(self.in_features, self.out_features,
@@ -569,6 +577,36 @@ class EetqLinearMMFunction(Function):
         grad_input = None
         if ctx.needs_input_grad[0]:
             grad_input = input_grad(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
+        return grad_input, None, None, None
+
+
+def input_grad_i4(grad_output, weight, scales, x_shape, x_dtype=torch.float16):
+    """:func:`input_grad` for a packed int4 ``[K, N/2]`` weight: an fp16 GPU gradient goes through ``w4_a16_gemm_t`` (neither
+    int8 tiles nor the dequantised weight are materialised); anything else through the identity path, which the forward operator
+    accepts for int4 as it is."""
+    if grad_output.dtype == torch.float16 and grad_output.is_cuda:
+        return w4_a16_gemm_t(grad_output, weight, scales).reshape(x_shape)
+    eye = torch.eye(weight.shape[0], device=weight.device, dtype=x_dtype)
+    w_deq = w8_a16_gemm(eye, weight, scales)  # fp16 [K, N] == fp16(q * s)
+    return grad_output.matmul(w_deq.transpose(0, 1)).reshape(x_shape)
+
+
+class W4A16LinearMMFunction(Function):
+    """:class:`EetqLinearMMFunction` over a packed int4 weight: forward = the fused int4 dequant GEMM (the bits of the module's
+    inference call); backward returns grad_input only, computed by :func:`input_grad_i4`.  ``x`` is not saved."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scales, bias=None):
+        ctx.save_for_backward(weight, scales)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        return w8_a16_gemm(x, weight, scales, bias=bias)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        weight, scales = ctx.saved_tensors
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            grad_input = input_grad_i4(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
         return grad_input, None, None, None
 
 

@@ -24,7 +24,7 @@ from . import _lib
 from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_F32, LAYOUT_GFX950, LAYOUT_ROW_MAJOR,
                    LAYOUT_SM80, PATH_AUTO, PATH_GEMV, PATH_MFMA, check)
 
-__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t",
+__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
@@ -221,6 +221,44 @@ def w8_a16_gemm_t(input, weight, scale):
         x = x.clone()
     with torch.cuda.device(input.device):
         check(_lib.lib().eetq_w8a16_gemm_t(_ptr(x), _ptr(weight), _ptr(scale), _ptr(output), m, n, k, _stream_ptr()))
+    return output
+
+
+@_eager_only
+def w4_a16_gemm_t(input, weight, scale):
+    """Input gradient of the int4 weight-only GEMM: ``input[..., N] @ dequant(weight, scale).T`` -> ``[..., K]`` for a packed
+    int4 ``[K, N/2]`` weight in the gfx950 layout (K % 128 == 0, N % 16 == 0), straight from the int4 tiles: the same bits as
+    ``w8_a16_gemm_t`` on the same integers held as int8 (eetq_w4a16_gemm_t).  Current stream, asynchronous."""
+    if not (input.is_cuda and weight.is_cuda and scale.is_cuda):
+        raise RuntimeError("w4_a16_gemm_t: input, weight and scale must be GPU tensors")
+    if input.dtype != torch.float16:
+        raise RuntimeError("w4_a16_gemm_t: input must be float16 (got %s)" % input.dtype)
+    if weight.dim() != 2 or weight.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise RuntimeError("w4_a16_gemm_t: weight must be an int8 [K, N/2] tensor (packed int4) and scale float16")
+    if weight.device != input.device or scale.device != input.device:
+        raise RuntimeError("w4_a16_gemm_t: input, weight and scale must be on the same device")
+    k, half = weight.shape
+    n = 2 * half
+    if half and scale.numel() == half:
+        raise RuntimeError("w4_a16_gemm_t: weight must be packed int4 [K, N/2] (got an int8 [K, N] weight with N scales: "
+                           "that is w8_a16_gemm_t's)")
+    if scale.numel() != n:
+        raise RuntimeError("w4_a16_gemm_t: scale must have N = %d elements (got %d)" % (n, scale.numel()))
+    if input.dim() < 1 or input.shape[-1] != n:
+        raise RuntimeError("w4_a16_gemm_t: weight is [%d, %d / 2] but input has N=%d" % (k, n, input.shape[-1] if input.dim() else 0))
+    if k % 128 or n % 16:
+        raise RuntimeError("w4_a16_gemm_t: the int4 layout needs K %% 128 == 0 and N %% 16 == 0 (got K=%d, N=%d)" % (k, n))
+    if not weight.is_contiguous() or not scale.is_contiguous():
+        raise RuntimeError("w4_a16_gemm_t: weight and scale must be contiguous")
+    output = torch.empty(tuple(input.shape[:-1]) + (k,), dtype=input.dtype, device=input.device)
+    m = input.numel() // n if n else 0
+    if m == 0 or k == 0:
+        return output
+    x = input.contiguous()  # a stride-0 gradient (y.sum().backward()) is materialised here
+    if x.data_ptr() % 16:
+        x = x.clone()
+    with torch.cuda.device(input.device):
+        check(_lib.lib().eetq_w4a16_gemm_t(_ptr(x), _ptr(weight), _ptr(scale), _ptr(output), m, n, k, _stream_ptr()))
     return output
 
 

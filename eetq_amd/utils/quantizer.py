@@ -11,7 +11,7 @@ import warnings
 import torch
 import torch.nn as nn
 
-from ..modules.qlinear import EetqSparseMoeBlock, EetqTopKRouter, W4A16Experts, W8A16Experts, W8A16Linear
+from ..modules.qlinear import EetqSparseMoeBlock, EetqTopKRouter, W4A16Experts, W4A16Linear, W8A16Experts, W8A16Linear
 
 __all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable"]
 
@@ -85,21 +85,21 @@ def _swap_routers(model, quantised, exclude):
 
 
 def set_trainable(model, flag=True):
-    """Set the ``trainable`` flag of every :class:`W8A16Linear` and :class:`W8A16Experts` in ``model`` (itself included) and
-    return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to the router weights)
-    in grad mode; their int8 weights stay frozen and their output bits do not change.  Off by default: untrainable modules
+    """Set the ``trainable`` flag of every :class:`W8A16Linear`, :class:`W4A16Linear` and :class:`W8A16Experts` in ``model``
+    (itself included) and return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to
+    the router weights) in grad mode; their quantised weights stay frozen and their output bits do not change.  Off by default: untrainable modules
     return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``.  :class:`W4A16Experts` is
     inference only and is passed by."""
     n = 0
     for m in model.modules():
-        if isinstance(m, (W8A16Linear, W8A16Experts)):
+        if isinstance(m, (W8A16Linear, W4A16Linear, W8A16Experts)):
             m.trainable = bool(flag)
             n += 1
     return n
 
 
 def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"], device="cuda:0", experts=False,
-                 trainable=False, expert_bits=8, expert_prompt_path="auto", router=False):
+                 trainable=False, expert_bits=8, expert_prompt_path="auto", bits=8, router=False):
     """Swap every matching ``nn.Linear`` of ``model`` for a :class:`W8A16Linear` (in place).
 
     fp16 weights are quantised by the HIP quantiser; int8 weights (bitsandbytes ``Linear8bitLt``) reuse their
@@ -110,10 +110,16 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     named in one warning.  The default leaves experts modules untouched.
     ``trainable=True`` (extension) then sets the flag of :func:`set_trainable` on every quantised module of the model, so that
     gradients cross them (fine-tuning adapters or prompts on a frozen int8 model).
+    ``bits=4`` (extension) turns every fp16 target with ``in_features % 128 == 0`` and ``out_features % 16 == 0`` into a
+    :class:`W4A16Linear` (int4 weights in the gfx950 int4 layout, half the bytes) instead; every other target -- a shape the int4
+    layout does not hold, an int8 / bitsandbytes weight -- takes the int8 branch exactly as with ``bits=8``, and the fp16 targets
+    left on int8 for their shape are named in one warning.  ``bits=4, trainable=True`` is allowed: :class:`W4A16Linear` has an
+    input gradient (``w4_a16_gemm_t``).  Any value but 8 or 4 raises ValueError before the model is touched; the default changes
+    nothing.
     ``expert_bits=4`` (extension; with ``experts=True``) builds :class:`W4A16Experts` -- int4 expert stacks, half the bytes,
     H and I multiples of 128, inference only -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
     but 8 or 4, ``expert_bits=4`` without ``experts=True`` (it would quantise no expert and say nothing) and ``expert_bits=4``
-    together with ``trainable=True`` (there is no int4 backward) raise ValueError before the model is touched.
+    together with ``trainable=True`` (the int4 experts have no backward) raise ValueError before the model is touched.
     ``expert_prompt_path="direct"`` (extension; with ``expert_bits=4``) sets :attr:`W4A16Experts.prompt_path` on every int4 experts
     module it builds: prompts then run the grouped tiled kernel on the int4 tiles instead of the decode kernel or the expansion
     (DESIGN.md 4.12).  The default ``"auto"`` changes nothing; any other value, or ``"direct"`` without ``expert_bits=4``, raises
@@ -131,6 +137,8 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     the list; a quantised block whose router is not, or whose router's configuration the kernel does not serve, is named in the
     same warning as the experts left in fp16.
     """
+    if isinstance(bits, bool) or not isinstance(bits, int) or bits not in (8, 4):
+        raise ValueError("eet_quantize: bits must be 8 or 4 (got %r)" % (bits,))
     if expert_bits not in (8, 4):
         raise ValueError("eet_quantize: expert_bits must be 8 or 4 (got %r)" % (expert_bits,))
     if expert_bits == 4 and not experts:
@@ -173,11 +181,16 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
                 parts.append("%d router(s) left on torch: %s" % (len(no_router), "; ".join(no_router)))
             warnings.warn("eet_quantize: " + ". ".join(parts))
     targets = find_layers(model, include=include, exclude=exclude)
+    left_int8 = []
     desc = "[EET][INFO] quantization preprocessing..." + ("(init only)" if init_only else "")
     for name in _progress(list(targets), desc):
         linear = targets.pop(name)  # the model and this loop hold the only references
         wdtype = linear.weight.dtype
-        if wdtype == torch.float16:
+        if wdtype == torch.float16 and bits == 4 and linear.in_features % 128 == 0 and linear.out_features % 16 == 0:
+            qlinear = W4A16Linear.from_torch(linear, init_only=init_only)
+        elif wdtype == torch.float16:
+            if bits == 4:
+                left_int8.append("%s (%d -> %d)" % (name, linear.in_features, linear.out_features))
             qlinear = W8A16Linear.from_torch(linear, scales=None, init_only=init_only)
         elif wdtype == torch.int8:
             scales = torch.div(linear.state_dict()["SCB"], 127.0)
@@ -190,6 +203,9 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
         del linear
         if not init_only and torch.cuda.is_available():
             torch.cuda.empty_cache()
+    if left_int8:
+        warnings.warn("eet_quantize: bits=4 needs in_features %% 128 == 0 and out_features %% 16 == 0; %d layer(s) quantised to "
+                      "int8 instead: %s" % (len(left_int8), "; ".join(left_int8)))
     gc.collect()
     if trainable:
         set_trainable(model, True)

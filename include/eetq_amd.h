@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -122,6 +122,15 @@ int eetq_w8a16_gemm(const void* x, const int8_t* w_packed, const void* scales, v
  * Device pointers, 16-byte aligned.  Requires K % 64 == 0, N % 16 == 0, M >= 1.  Deterministic: one pass over N per output
  * tile, no atomics, so repeated calls give identical bits. */
 int eetq_w8a16_gemm_t(const void* in, const void* weight, const void* scale, void* out, int M, int N, int K, void* stream);
+/* ABI revision 7 (additive): the same input gradient from an int4 weight, out[M][K] = in[M][N] . fp16(q.s)^T with q in -8..7:
+ *   out[m][k] = fp16( sum_n fp32(in[m][n]) * fp32( fp16( q[k][n] * scale[n] ) ) ),  fp32 accumulation, one rounding.
+ * in: fp16 [M][N] row-major; weight_i4: the gfx950 int4 layout of the [K][N/2] packed weight, exactly as eetq_w4a16_gemm takes
+ * it (1 KiB tiles of 16 columns x 128 k ordered [n/16][k/128], K * N / 2 bytes); scale: fp16 [N]; out: fp16 [M][K] row-major.
+ * Device pointers; in, weight_i4 and out 16-byte aligned.  Requires K % 128 == 0, N % 16 == 0, M >= 1; a violation returns
+ * EETQ_ERR_INVALID with a message before any launch.  Rows >= M of a larger out are left untouched.  The tile and the order of
+ * accumulation are eetq_w8a16_gemm_t's: the result bits equal eetq_w8a16_gemm_t on the same integers held as int8 tiles.
+ * Deterministic (one pass over N per output tile, no atomics), no scratch, no allocation, capturable in a graph. */
+int eetq_w4a16_gemm_t(const void* in, const void* weight_i4, const void* scale, void* out, int M, int N, int K, void* stream);
 /* As above with an explicit kernel path (EETQ_PATH_*); returns EETQ_ERR_UNSUPPORTED when the path cannot
  * run the shape (e.g. GEMV with M > 4, STREAM with M > 64). */
 int eetq_w8a16_gemm_ex(const void* x, const int8_t* w_packed, const void* scales, void* y, int M, int N,
