@@ -288,6 +288,9 @@ int launch_gemm_t_i4(const f16* dy, const uint8_t* w, const f16* scales, f16* dx
 // the same per expert over an [E][K][N] stack: rows offsets[e] .. offsets[e + 1] - 1 of dy [S][N] / dx [S][K] (gemm_t.hip)
 int launch_moe_gemm_t(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
                       int E, int N, int K, hipStream_t stream);
+// the same over an int4 stack [E][K][N / 2], K % 128 == 0 (moe_gemm_t_int4.hip); same bits as launch_moe_gemm_t on the same integers
+int launch_moe_gemm_t_i4(const f16* dy, const uint8_t* w, const f16* scales, const int* offsets, const int* active, f16* dx, int S,
+                         int E, int N, int K, hipStream_t stream);
 // grouped LDS-tiled forward over an [E][K][N] stack on eetq_moe_route's tables (moe_gemm_tiled.hip): the prompt path of the routed
 // experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs the
 // decode kernel (moe_gemm_kernel.hpp)

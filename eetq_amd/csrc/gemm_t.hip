@@ -18,7 +18,8 @@
 //   * tails: k columns beyond K (K % 128 == 64) are computed from a clamped tile and never stored; 16-column groups beyond
 //     N write zeros into the weight image and dy chunks beyond N are zero, so ragged N adds exact zeros; rows beyond M read
 //     row M - 1 and are not stored.  One pass over N per tile, no atomics: the result bits do not depend on the launch.
-// The kernel itself is the BITS = 8 instantiation of gemm_t_kernel.hpp (shared with gemm_t_int4.hip, whose producer reads int4 tiles).
+// The kernel itself is the BITS = 8 instantiation of gemm_t_kernel.hpp (shared with gemm_t_int4.hip and
+// moe_gemm_t_int4.hip, whose producer reads int4 tiles).
 #include "gemm_t_kernel.hpp"
 
 namespace eetq {

@@ -1,5 +1,5 @@
 // Kernel template of the projection's input gradient dx[M][K] = fp16( sum_n dy[M][n] * fp16(q[k][n] * s[n]) ) (included by
-// gemm_t.hip, BITS = 8, and gemm_t_int4.hip, BITS = 4).  The tile, the LDS images, the pipeline and the epilogue are described
+// gemm_t.hip, BITS = 8 plain and grouped, gemm_t_int4.hip, BITS = 4 plain, and moe_gemm_t_int4.hip, BITS = 4 grouped).  The tile, the LDS images, the pipeline and the epilogue are described
 // in gemm_t.hip's header; the two BITS differ only in the weight PRODUCER (global load -> dequant -> fp16 image rows), see `store`.
 #pragma once
 #include "common.hpp"
@@ -59,8 +59,8 @@ struct Regs {
 };
 
 // One kernel, two row maps.  GROUPED = false: the plain problem dx[M][K] = dy[M][N] . fp16(q s)^T (eetq_w8a16_gemm_t); the
-// trailing arguments are unused.  GROUPED = true (eetq_w8a16_moe_gemm_t): the stack w [E][K][N] (each expert the gfx950 layout,
-// K * N bytes apart), scales [E][N]; expert e's problem is the contiguous sorted rows offsets[e] .. offsets[e + 1] - 1 of
+// trailing arguments are unused.  GROUPED = true (eetq_w8a16_moe_gemm_t, eetq_w4a16_moe_gemm_t): the stack w [E][K][N] (each expert
+// the gfx950 layout of its BITS, K * N bytes apart for int8 and K * N / 2 for int4), scales [E][N]; expert e's problem is the contiguous sorted rows offsets[e] .. offsets[e + 1] - 1 of
 // dy [S][N] and dx [S][K], M = A = the length of the active list.  The grid is R row-tile slots x ceil(K / 128)
 // column tiles, R = floor(S / 128) + min(E, S) >= sum_e ceil(c_e / 128) whatever the routing; slot r is the r-th row tile in the
 // order of the active list (ascending experts, padded with -1).  Every wave finds its slot's expert on its own: lane l sums the
@@ -69,7 +69,7 @@ struct Regs {
 // body then runs on the expert's rows with dy, dx and the weight and scale bases moved to them: rows past the expert's count
 // read its last row and are never stored.  The GROUPED = false instantiation is the kernel this file had before the grouped map.
 //
-// BITS = 4 (eetq_w4a16_gemm_t, plain map only): w is the gfx950 int4 layout -- 1 KiB tiles of 16 columns x 128 k ordered
+// BITS = 4 (eetq_w4a16_gemm_t on the plain map, eetq_w4a16_moe_gemm_t on the grouped one): w is the gfx950 int4 layout -- 1 KiB tiles of 16 columns x 128 k ordered
 // [n / 16][k / 128], lane ((k >> 5) & 3) * 16 + (n & 15) holds 32 k of one column -- and K % 128 == 0, so a tile's 128 k are ONE
 // int4 tile per 16-column group: one 16-byte load per lane and step, no clamped second k tile.
 template <bool GROUPED, int BITS>
@@ -78,7 +78,6 @@ __global__ __launch_bounds__(256, 2) void gemm_t_kernel(const f16* __restrict__ 
                                                         const int* __restrict__ offsets, const int* __restrict__ active, int R)
 {
     static_assert(BITS == 8 || BITS == 4, "int8 or int4 tiles");
-    static_assert(BITS == 8 || !GROUPED, "the grouped map strides the stack by K * N bytes: int8 only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
@@ -145,7 +144,10 @@ __global__ __launch_bounds__(256, 2) void gemm_t_kernel(const f16* __restrict__ 
         m0           = (slot - t0) * BM;
         dy += (size_t)p0 * N;
         dx += (size_t)p0 * K;
-        w += (size_t)e * K * N;
+        if constexpr (BITS == 4)  // a compile-time branch: the int8 stride stays the expression it was
+            w += (size_t)e * K * N / 2;
+        else
+            w += (size_t)e * K * N;
         scales += (size_t)e * N;
     }
     constexpr int kTileShift = BITS == 8 ? 6 : 7;  // k per 1 KiB tile: 64 (int8), 128 (int4)

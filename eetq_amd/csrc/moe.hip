@@ -1,6 +1,7 @@
 // Routed mixture-of-experts kernels: device-side routing tables, the grouped W8A16 GEMM over an [E][K][N] int8
 // expert stack that reads them (the BITS = 8 instantiations of moe_gemm_kernel.hpp), and the weighted combine; and the backward's
-// combine and gated-activation steps (whose grouped input-gradient GEMM lives in gemm_t.hip).  No launch needs a
+// combine and gated-activation steps (whose grouped input-gradient GEMM lives in gemm_t.hip and, for int4 stacks,
+// in moe_gemm_t_int4.hip).  No launch needs a
 // host sync, so a decode step's MoE layer (route -> gate|up GEMM with the gated activation -> down GEMM -> combine) can be
 // captured in a graph; the grid of every launch depends on T, k, E, N and K only, never on the routing.
 #include "moe_gemm_kernel.hpp"

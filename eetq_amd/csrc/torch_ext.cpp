@@ -1270,8 +1270,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> w8_a16_moe_train(const Tensor& hidden
 
 // Routed W4A16 mixture-of-experts layer: w8_a16_moe on int4 expert stacks -- gate_up_qweight int8 [E, H, I]
 // (= [E, K = H, N / 2], N = 2I: two values per byte; per expert the gfx950 int4 layout, glu8 column order), gate_up_scales fp16
-// [E, 2I], down_qweight int8 [E, I, H / 2], down_scales fp16 [E, H].  Inference only; eetq_moe_route and eetq_moe_combine_f16 are the
-// int8 layer's, unchanged.  w4_a16_moe_path reports what path = "auto" runs.
+// [E, 2I], down_qweight int8 [E, I, H / 2], down_scales fp16 [E, H].  This op is the inference forward (w4_a16_moe_train /
+// w4_a16_moe_backward below train through the layer); eetq_moe_route and eetq_moe_combine_f16 are the int8 layer's, unchanged.
+// w4_a16_moe_path reports what path = "auto" runs.
 Tensor w4_a16_moe(const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w, const Tensor& gu_s,
                   const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
 {
@@ -1285,26 +1286,30 @@ Tensor w4_a16_moe(const Tensor& hidden, const Tensor& top_k_index, const Tensor&
 //   eetq_silu_mul_glu8_bwd_f16 (dgate_up, glu8 order) -> eetq_w8a16_moe_gemm_t over the gate|up stack (per-slot dx) ->
 //   eetq_moe_combine_f16 with unit weights (the sum over each token's slots in j order).
 // The saved tensors are only read, so a retained graph can run it again.
-std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, const Tensor& top_k_weights, const Tensor& tables,
-                                                     const Tensor& gate_up, const Tensor& y, const Tensor& gu_w, const Tensor& gu_s,
-                                                     const Tensor& dn_w, const Tensor& dn_s, bool need_input_grad,
-                                                     bool need_weights_grad)
+// bits = 4 (w4_a16_moe_backward): the same five launches on int4 stacks, eetq_w4a16_moe_gemm_t reading the int4 tiles
+// for the two transposed GEMMs -- no stack is expanded, the extra memory is the same activations.  `fn` names the op and `train` its
+// forward in the messages.
+std::tuple<OptTensor, OptTensor> moe_backward(const char* fn, const char* train, int bits, const Tensor& grad_out,
+                                              const Tensor& top_k_weights, const Tensor& tables, const Tensor& gate_up, const Tensor& y,
+                                              const Tensor& gu_w, const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s,
+                                              bool need_input_grad, bool need_weights_grad)
 {
-    moe_rows_check("w8_a16_moe_backward", "grad_out", grad_out);
-    const auto [E, H, N1, I] = moe_stacks("w8_a16_moe_backward", "grad_out", grad_out, gu_w, gu_s, dn_w, dn_s);
+    moe_rows_check(fn, "grad_out", grad_out);
+    const auto [E, H, N1, I] = moe_stacks(fn, "grad_out", grad_out, gu_w, gu_s, dn_w, dn_s, bits);
+    const auto gemm_t        = bits == 4 ? eetq_w4a16_moe_gemm_t : eetq_w8a16_moe_gemm_t;
     TORCH_CHECK(top_k_weights.dim() == 2 && top_k_weights.size(0) == grad_out.size(0) && top_k_weights.device() == grad_out.device() &&
                     (top_k_weights.scalar_type() == at::kFloat || top_k_weights.scalar_type() == at::kHalf),
-                "w8_a16_moe_backward: top_k_weights must be float32 or float16 [T, k] on grad_out's device");
+                fn, ": top_k_weights must be float32 or float16 [T, k] on grad_out's device");
     const int64_t T = grad_out.size(0), k = top_k_weights.size(1), S = T * k;
     TORCH_CHECK(tables.is_cuda() && tables.scalar_type() == at::kInt && tables.is_contiguous() && tables.dim() == 1 &&
                     tables.numel() == MoeTables::numel(E, S) && tables.device() == grad_out.device(),
-                "w8_a16_moe_backward: tables must be w8_a16_moe_train's int32 routing tables for these T, k and E");
+                fn, ": tables must be ", train, "'s int32 routing tables for these T, k and E");
     TORCH_CHECK(gate_up.scalar_type() == at::kHalf && gate_up.is_contiguous() && gate_up.dim() == 2 && gate_up.size(0) == S &&
                     gate_up.size(1) == N1 && gate_up.device() == grad_out.device(),
-                "w8_a16_moe_backward: gate_up must be w8_a16_moe_train's contiguous float16 [T*k, 2I]");
+                fn, ": gate_up must be ", train, "'s contiguous float16 [T*k, 2I]");
     TORCH_CHECK(y.scalar_type() == at::kHalf && y.is_contiguous() && y.dim() == 2 && y.size(0) == S && y.size(1) == H &&
                     y.device() == grad_out.device(),
-                "w8_a16_moe_backward: y must be w8_a16_moe_train's contiguous float16 [T*k, H]");
+                fn, ": y must be ", train, "'s contiguous float16 [T*k, H]");
     OptTensor gx, gw;
     if (!need_input_grad && !need_weights_grad) return {gx, gw};
     const Tensor wts = top_k_weights.contiguous();
@@ -1326,20 +1331,46 @@ std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, con
     if (!need_input_grad) return {gx, gw};
     // each temporary is released as soon as the next step has consumed it: the peak is dh + dgate_up (+ dy, dx per slot)
     Tensor dh = torch::empty({S, I}, grad_out.options());
-    check(eetq_w8a16_moe_gemm_t(dy.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), t.offsets, t.active, dh.data_ptr(), (int)T,
-                                (int)k, (int)E, (int)H, (int)I, st));
+    check(gemm_t(dy.data_ptr(), dn_w.data_ptr<int8_t>(), dn_s.data_ptr(), t.offsets, t.active, dh.data_ptr(), (int)T, (int)k, (int)E,
+                 (int)H, (int)I, st));
     dy.reset();
     Tensor dgu = torch::empty({S, N1}, grad_out.options());
     check(eetq_silu_mul_glu8_bwd_f16(gate_up.data_ptr(), dh.data_ptr(), dgu.data_ptr(), (int)S, (int)I, st));
     dh.reset();
     Tensor dxs = torch::empty({S, H}, grad_out.options());
-    check(eetq_w8a16_moe_gemm_t(dgu.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), t.offsets, t.active, dxs.data_ptr(), (int)T,
-                                (int)k, (int)E, (int)N1, (int)H, st));
+    check(gemm_t(dgu.data_ptr(), gu_w.data_ptr<int8_t>(), gu_s.data_ptr(), t.offsets, t.active, dxs.data_ptr(), (int)T, (int)k, (int)E,
+                 (int)N1, (int)H, st));
     dgu.reset();
     const Tensor ones = torch::ones({T, k}, grad_out.options().dtype(at::kFloat));
     gx                = torch::empty({T, H}, grad_out.options());
     moe_combine(dxs, t.position, ones, *gx, st);
     return {gx, gw};
+}
+
+std::tuple<OptTensor, OptTensor> w8_a16_moe_backward(const Tensor& grad_out, const Tensor& top_k_weights, const Tensor& tables,
+                                                     const Tensor& gate_up, const Tensor& y, const Tensor& gu_w, const Tensor& gu_s,
+                                                     const Tensor& dn_w, const Tensor& dn_s, bool need_input_grad,
+                                                     bool need_weights_grad)
+{
+    return moe_backward("w8_a16_moe_backward", "w8_a16_moe_train", 8, grad_out, top_k_weights, tables, gate_up, y, gu_w, gu_s, dn_w,
+                        dn_s, need_input_grad, need_weights_grad);
+}
+
+// Trainable forward and backward of the W4A16 layer: w8_a16_moe_train / w8_a16_moe_backward on int4 stacks.  The
+// forward runs w4_a16_moe's plan for the same `path`, so `out` is w4_a16_moe's bit for bit on every path.
+MoeLayerOut w4_a16_moe_train(const Tensor& hidden, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gu_w,
+                             const Tensor& gu_s, const Tensor& dn_w, const Tensor& dn_s, const std::string& path)
+{
+    return moe_layer("w4_a16_moe_train", 4, path, true, hidden, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s);
+}
+
+std::tuple<OptTensor, OptTensor> w4_a16_moe_backward(const Tensor& grad_out, const Tensor& top_k_weights, const Tensor& tables,
+                                                     const Tensor& gate_up, const Tensor& y, const Tensor& gu_w, const Tensor& gu_s,
+                                                     const Tensor& dn_w, const Tensor& dn_s, bool need_input_grad,
+                                                     bool need_weights_grad)
+{
+    return moe_backward("w4_a16_moe_backward", "w4_a16_moe_train", 4, grad_out, top_k_weights, tables, gate_up, y, gu_w, gu_s, dn_w,
+                        dn_s, need_input_grad, need_weights_grad);
 }
 
 // ---- the MoE router on the device (extension) ----------------------------------------------------------------
@@ -1607,9 +1638,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("need_input_grad") = true,
           py::arg("need_weights_grad") = true);
     m.def("w4_a16_moe", &w4_a16_moe,
-          "routed W4A16 mixture-of-experts layer over int4 expert stacks (inference only); path: 'auto', 'decode', 'expand' or 'direct'",
+          "routed W4A16 mixture-of-experts layer over int4 expert stacks (the inference forward); path: 'auto', 'decode', 'expand' or "
+          "'direct'",
           py::arg("hidden"), py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
           py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
+    m.def("w4_a16_moe_train", &w4_a16_moe_train,
+          "trainable forward of the routed W4A16 experts layer: (out, routing tables, gate_up, y) for w4_a16_moe_backward; path as "
+          "w4_a16_moe",
+          py::arg("hidden"), py::arg("top_k_index"), py::arg("top_k_weights"), py::arg("gate_up_qweight"), py::arg("gate_up_scales"),
+          py::arg("down_qweight"), py::arg("down_scales"), py::arg("path") = "auto");
+    m.def("w4_a16_moe_backward", &w4_a16_moe_backward,
+          "input and router-weight gradients of the routed W4A16 experts layer (frozen int4 weights, read as int4 tiles)",
+          py::arg("grad_out"), py::arg("top_k_weights"), py::arg("tables"), py::arg("gate_up"), py::arg("y"), py::arg("gate_up_qweight"),
+          py::arg("gate_up_scales"), py::arg("down_qweight"), py::arg("down_scales"), py::arg("need_input_grad") = true,
+          py::arg("need_weights_grad") = true);
     m.def("w4_a16_moe_path", &w4_a16_moe_path,
           "'decode' or 'expand': the grouped kernels w4_a16_moe(path='auto') runs for T tokens, k choices, E experts, H, I",
           py::arg("T"), py::arg("k"), py::arg("E"), py::arg("H"), py::arg("I"));

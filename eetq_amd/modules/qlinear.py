@@ -18,13 +18,13 @@ from torch.autograd import Function
 
 from ..ops import (moe_router, moe_router_sigmoid, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block,
                    w4_a16_gemm_t, w4_a16_moe_direct_supported,
-                   w4_a16_moe_block_sigmoid, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
+                   w4_a16_moe_backward, w4_a16_moe_block_sigmoid, w4_a16_moe_train, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
                    w8_a16_moe_block_sigmoid, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
 
 __all__ = ["quantize_and_preprocess_weights", "W8A16Linear", "W4A16Linear", "W8A16Experts", "W4A16Experts", "EetqLinearMMFunction", "EetqLinear", "input_grad",
            "W4A16LinearMMFunction", "input_grad_i4",
-           "W8A16MoeFunction", "EetqTopKRouter", "EetqSparseMoeBlock"]
+           "W8A16MoeFunction", "W4A16MoeFunction", "EetqTopKRouter", "EetqSparseMoeBlock"]
 
 
 def quantize_and_preprocess_weights(weight, scales=None):
@@ -270,8 +270,13 @@ class W4A16Experts(_QuantExperts):
     inside ``ops.w4_a16_moe_direct_supported`` to the grouped tiled kernel on the int4 tiles themselves -- the bits of the expanded
     path, no [E, K, N] buffer -- and every other call to the decode kernel; the expansion is never used in this mode.
 
-    Inference only: there is no int4 backward, the module has no ``trainable`` flag and ``utils.set_trainable`` passes it by;
-    its output is always detached.  State dicts hold the four buffers as they are, like :class:`W8A16Experts`."""
+    Inference-only unless ``trainable`` is set (``utils.set_trainable(model, True, int4_experts=True)``; the two-argument call
+    passes int4 experts by): then a call in grad mode with ``hidden_states`` or ``top_k_weights`` requiring grad runs through
+    :class:`W4A16MoeFunction` -- the same output bits on the same path, and gradients for both (the int4 stacks stay frozen and
+    are read as int4 tiles, never expanded, by the backward).  Every other call returns a detached output.
+    State dicts hold the four buffers as they are, like :class:`W8A16Experts`."""
+
+    trainable = False   # a plain attribute, not a buffer: state dicts do not change
 
     bits = 4
 
@@ -309,14 +314,19 @@ class W4A16Experts(_QuantExperts):
         q, s = quant_weights(_glu8_interleave_columns(w[..., :I], w[..., I:]).contiguous(), torch.quint4x2, False)
         return q, s.half()
 
-    @torch.no_grad()
     def forward(self, hidden_states, top_k_index, top_k_weights):
-        """Any number of tokens, no host sync, capturable in a graph.  Four launches on the int4 decode kernel; on the prompt path
-        (``ops.w4_a16_moe_path``: chosen from the shapes, never from the routing) each projection's stack is first expanded to
-        int8 tiles and runs the grouped tiled W8A16 kernel.  With ``prompt_path = "direct"`` prompts run the grouped tiled kernel
-        on the int4 tiles instead (see the class)."""
-        return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
-                          self.down_qweight, self.down_scales, self.op_path(hidden_states.shape[0], top_k_index.shape[1]))
+        """Any number of tokens, no host sync, capturable in a graph.  Four launches on the int4 decode kernel (five when
+        trainable); on the prompt path (``ops.w4_a16_moe_path``: chosen from the shapes, never from the routing) each projection's
+        stack is first expanded to int8 tiles and runs the grouped tiled W8A16 kernel.  With ``prompt_path = "direct"`` prompts
+        run the grouped tiled kernel on the int4 tiles instead (see the class)."""
+        path = self.op_path(hidden_states.shape[0], top_k_index.shape[1])
+        if (self.trainable and torch.is_grad_enabled()
+                and (hidden_states.requires_grad or top_k_weights.requires_grad)):
+            return W4A16MoeFunction.apply(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                                          self.down_qweight, self.down_scales, path)
+        with torch.no_grad():
+            return w4_a16_moe(hidden_states, top_k_index, top_k_weights, self.gate_up_qweight, self.gate_up_scales,
+                              self.down_qweight, self.down_scales, path)
 
 
 def _adopt(module, mixin):
@@ -628,6 +638,25 @@ class W8A16MoeFunction(Function):
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
         grad_x, grad_w = w8_a16_moe_backward(grad_output, wts, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s, need_x, need_w)
         return grad_x, None, grad_w, None, None, None, None
+
+
+class W4A16MoeFunction(Function):
+    """:class:`W8A16MoeFunction` over int4 expert stacks: forward = ``w4_a16_moe_train`` on the module's ``path``
+    (the output bits of ``w4_a16_moe`` on that path), backward = ``w4_a16_moe_backward``, whose two transposed grouped GEMMs read
+    the int4 tiles themselves.  Gradients of ``hidden_states`` and ``top_k_weights`` only; the hidden states are not saved."""
+
+    @staticmethod
+    def forward(ctx, hidden_states, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s, path="auto"):
+        out, tables, gate_up, y = w4_a16_moe_train(hidden_states, top_k_index, top_k_weights, gu_w, gu_s, dn_w, dn_s, path)
+        ctx.save_for_backward(top_k_weights, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        wts, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        grad_x, grad_w = w4_a16_moe_backward(grad_output, wts, tables, gate_up, y, gu_w, gu_s, dn_w, dn_s, need_x, need_w)
+        return grad_x, None, grad_w, None, None, None, None, None
 
 
 class EetqLinear(nn.Module):

@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
-           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
+           "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
 _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM80, "row_major": LAYOUT_ROW_MAJOR,
@@ -518,6 +518,19 @@ def w8_a16_moe_backward(grad_out, top_k_weights, tables, gate_up, y, gate_up_qwe
                         need_input_grad=True, need_weights_grad=True):
     """The backward of the routed MoE layer: compiled module only, like :func:`w8_a16_moe`."""
     raise RuntimeError("eetq_amd: w8_a16_moe_backward needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not implement it")
+
+
+def w4_a16_moe_train(hidden, top_k_index, top_k_weights, gate_up_qweight, gate_up_scales, down_qweight, down_scales, path="auto"):
+    """The trainable forward of the routed int4 MoE layer: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w4_a16_moe_train needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
+                       "the ctypes binding does not implement it")
+
+
+def w4_a16_moe_backward(grad_out, top_k_weights, tables, gate_up, y, gate_up_qweight, gate_up_scales, down_qweight, down_scales,
+                        need_input_grad=True, need_weights_grad=True):
+    """The backward of the routed int4 MoE layer: compiled module only, like :func:`w8_a16_moe`."""
+    raise RuntimeError("eetq_amd: w4_a16_moe_backward needs the compiled EETQ module (EETQ_AMD_BOUNDARY=ext); "
                        "the ctypes binding does not implement it")
 
 

@@ -84,15 +84,16 @@ def _swap_routers(model, quantised, exclude):
     return left
 
 
-def set_trainable(model, flag=True):
+def set_trainable(model, flag=True, int4_experts=False):
     """Set the ``trainable`` flag of every :class:`W8A16Linear`, :class:`W4A16Linear` and :class:`W8A16Experts` in ``model``
-    (itself included) and return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to
+    (itself included) -- with ``int4_experts=True`` of every :class:`W4A16Experts` as well -- and return how many modules it set.  Trainable modules pass gradients to their inputs (and, for experts, to
     the router weights) in grad mode; their quantised weights stay frozen and their output bits do not change.  Off by default: untrainable modules
-    return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``.  :class:`W4A16Experts` is
-    inference only and is passed by."""
+    return detached outputs, as they always have.  Reversible: ``set_trainable(model, False)``.  Without ``int4_experts`` every
+    :class:`W4A16Experts` is passed by and not counted, as before the int4 experts had a backward."""
+    classes = (W8A16Linear, W4A16Linear, W8A16Experts) + ((W4A16Experts,) if int4_experts else ())
     n = 0
     for m in model.modules():
-        if isinstance(m, (W8A16Linear, W4A16Linear, W8A16Experts)):
+        if isinstance(m, classes):
             m.trainable = bool(flag)
             n += 1
     return n
@@ -117,9 +118,10 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     input gradient (``w4_a16_gemm_t``).  Any value but 8 or 4 raises ValueError before the model is touched; the default changes
     nothing.
     ``expert_bits=4`` (extension; with ``experts=True``) builds :class:`W4A16Experts` -- int4 expert stacks, half the bytes,
-    H and I multiples of 128, inference only -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
+    H and I multiples of 128 -- instead of :class:`W8A16Experts`; the ``nn.Linear`` pass stays int8.  Any value
     but 8 or 4, ``expert_bits=4`` without ``experts=True`` (it would quantise no expert and say nothing) and ``expert_bits=4``
-    together with ``trainable=True`` (the int4 experts have no backward) raise ValueError before the model is touched.
+    together with ``trainable=True`` raise ValueError before the model is touched: the int4 experts are made trainable afterwards,
+    with ``set_trainable(model, True, int4_experts=True)``.
     ``expert_prompt_path="direct"`` (extension; with ``expert_bits=4``) sets :attr:`W4A16Experts.prompt_path` on every int4 experts
     module it builds: prompts then run the grouped tiled kernel on the int4 tiles instead of the decode kernel or the expansion
     (DESIGN.md 4.12).  The default ``"auto"`` changes nothing; any other value, or ``"direct"`` without ``expert_bits=4``, raises
@@ -144,7 +146,8 @@ def eet_quantize(model, init_only=False, include=[nn.Linear], exclude=["lm_head"
     if expert_bits == 4 and not experts:
         raise ValueError("eet_quantize: expert_bits=4 needs experts=True (without it no experts module is quantised)")
     if expert_bits == 4 and trainable:
-        raise ValueError("eet_quantize: expert_bits=4 cannot be trainable (W4A16Experts has no backward)")
+        raise ValueError("eet_quantize: expert_bits=4 does not take trainable=True; quantise first, then make the int4 experts "
+                         "trainable with set_trainable(model, True, int4_experts=True)")
     if expert_prompt_path not in W4A16Experts.PROMPT_PATHS:
         raise ValueError("eet_quantize: expert_prompt_path must be one of %r (got %r)" % (W4A16Experts.PROMPT_PATHS, expert_prompt_path))
     if expert_prompt_path != "auto" and expert_bits != 4:

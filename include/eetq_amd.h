@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -321,7 +321,7 @@ int eetq_moe_combine_f16(const void* y, const int* position, const void* weights
  *   fp32( fp16(q s) ) ) with q in -8 .. 7, fp32 accumulation, one rounding; glu8 = 1 is the plain call followed by
  *   eetq_silu_mul_glu8_f16, bit for bit.  A row's bits do not depend on T, on the other tokens' routing or on its place among the
  *   expert's rows.  Needs K % 128 == 0, N % 16 == 0, x / w_packed / y 16-byte aligned, E and k as in eetq_moe_route; else
- *   EETQ_ERR_INVALID.  Inference only: there is no int4 backward. */
+ *   EETQ_ERR_INVALID.  The forward only: the backward of the int4 experts is eetq_w4a16_moe_gemm_t (below). */
 int eetq_w4a16_moe_gemm(const void* x, const int8_t* w_packed, const void* scales, const int* offsets, const int* sorted_slot,
                         const int* active, void* y, int T, int k, int E, int N, int K, int gather, int glu8, void* stream);
 /* eetq_expand_i4_to_i8: GFX950 int4 tiles -> GFX950 int8 tiles holding the same integers (-8 .. 7), on caller-owned memory: src
@@ -418,6 +418,13 @@ int eetq_moe_topk_sigmoid_f32(const void* logits, const void* bias, int bias_dty
  *   dy / w_packed / dx 16-byte aligned, E and k as in eetq_moe_route; else EETQ_ERR_INVALID. */
 int eetq_w8a16_moe_gemm_t(const void* dy, const int8_t* w_packed, const void* scales, const int* offsets, const int* active, void* dx,
                           int T, int k, int E, int N, int K, void* stream);
+/* eetq_w4a16_moe_gemm_t: eetq_w8a16_moe_gemm_t on an int4 expert stack (w_packed_i4 [E][K][N / 2] bytes, each expert the GFX950 int4
+ *   layout, K*N/2 bytes apart), read straight from the int4 tiles: it replaces eetq_expand_i4_to_i8 of the whole stack followed by
+ *   eetq_w8a16_moe_gemm_t, whose result bits it equals on the same integers; per expert it is eetq_w4a16_gemm_t on that expert's rows
+ *   and weight, bit for bit.  Same tables, untouched rows, grid rule and argument order.  Needs K % 128 == 0, N % 16 == 0, dy /
+ *   w_packed_i4 / dx 16-byte aligned, E and k as in eetq_moe_route; else EETQ_ERR_INVALID, before any launch. */
+int eetq_w4a16_moe_gemm_t(const void* dy, const int8_t* w_packed_i4, const void* scales, const int* offsets, const int* active,
+                          void* dx, int T, int k, int E, int N, int K, void* stream);
 /* eetq_moe_combine_bwd_f16: for every slot t*k + j with p = position[t*k + j] >= 0:
  *   dy[p][h] = fp16( fp32(dout[t][h]) * fp32(weights[t][j]) ),   dw[t][j] = sum_h fp32(dout[t][h]) * fp32(y[p][h]) (fixed order),
  *   and dw[t][j] = 0 for slots with p = -1.  dout fp16 [T][H], y / dy fp16 [*][H] (sorted rows), weights / dw [T][k] of w_dtype

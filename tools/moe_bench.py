@@ -14,6 +14,14 @@ the trainable forward's saved tensors and the backward's peak above what was all
 
     python tools/moe_bench.py --backward --out profiles/r08_moe_backward_bench.jsonl
 
+--backward --bits 4 times the int4 training path at the same shapes and token counts: the no-grad forward
+(w4_a16_moe), the trainable forward (w4_a16_moe_train), the backward (w4_a16_moe_backward, both gradients) with its five launches
+one at a time and its saved / peak bytes -- and, in the same process and interleaved call by call, w8_a16_moe_backward and
+eetq_w8a16_moe_gemm_t on the same integers held as int8 stacks (eetq_expand_i4_to_i8, done once outside the timing), given the
+same saved tensors.  Every timing is [median, min, max] us.
+
+    python tools/moe_bench.py --backward --bits 4 --out profiles/r16_moe_int4_backward_bench.jsonl
+
 Prompts: --tokens 64,512,4096 times the device-side prompt path; --host-path adds the column `us_host_path`, the
 same layer on the former host path (one read-back of the expert counts, per-expert AUTO GEMMs), measured in a child process of its
 own that sets EETQ_AMD_TUNING=1 EETQ_AMD_MOE_HOST=1 (the switch is read once per process); --no-baselines skips the fp16 eager
@@ -202,6 +210,122 @@ def backward(args, out):
                    "us_per_expert_gemm_t_loop": round(us_loop, 2), "loop_over_grouped": round(us_loop / grouped, 2),
                    "bwd_over_trainable_fwd": round(us_bwd / us_train, 3),
                    "us_fp16_eager_fwd_bwd": round(us_eager, 2),
+                   "saved_bytes": saved, "backward_peak_bytes": peak}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            del o, tables, gate_up, y, dy, dh, dgu, dxs, dx
+
+
+def _interleaved(fns, warmup, iters):
+    """{name: (median, min, max) us}: the callables timed in turn, one call each per round, so that they share the device's state"""
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    times = {n: [] for n in fns}
+    for _ in range(iters):
+        for n, f in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            times[n].append(a.elapsed_time(b) * 1000.0)
+    return {n: (sorted(t)[len(t) // 2], min(t), max(t)) for n, t in times.items()}
+
+
+def backward_i4(args, out):
+    """the int4 training path next to the int8 backward on the same integers (expanded once, outside every timing)"""
+    import ctypes
+
+    from eetq_amd import _lib
+    from eetq_amd.ops import w4_a16_moe, w4_a16_moe_backward, w4_a16_moe_path, w4_a16_moe_train, w8_a16_moe_backward
+    L = _lib.lib()
+
+    def r3(t):
+        return [round(v, 2) for v in t]
+    for name in args.shapes.split(","):
+        H, I, E, k = SHAPES[name]
+        torch.manual_seed(0)
+        gu_w = torch.randint(-128, 128, (E, H, I), dtype=torch.int8, device=DEV)       # any bytes are valid int4 stacks
+        gu_s = (torch.rand(E, 2 * I, device=DEV) * 1e-2).half()
+        dn_w = torch.randint(-128, 128, (E, I, H // 2), dtype=torch.int8, device=DEV)
+        dn_s = (torch.rand(E, H, device=DEV) * 1e-2).half()
+        stacks = (gu_w, gu_s, dn_w, dn_s)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        gu_w8 = torch.empty(E, H, 2 * I, dtype=torch.int8, device=DEV)
+        dn_w8 = torch.empty(E, I, H, dtype=torch.int8, device=DEV)
+        assert L.eetq_expand_i4_to_i8(_ptr(gu_w), _ptr(gu_w8), gu_w.numel(), st) == 0
+        assert L.eetq_expand_i4_to_i8(_ptr(dn_w), _ptr(dn_w8), dn_w.numel(), st) == 0
+        stacks8 = (gu_w8, gu_s, dn_w8, dn_s)
+        g = torch.Generator().manual_seed(1)
+        for T in (int(t) for t in args.tokens.split(",")):
+            S = T * k
+            x = (torch.rand(T, H, device=DEV) - 0.5).half()
+            idx = _routing(T, k, E, "uniform", g)
+            wts = torch.rand(T, k, device=DEV).softmax(-1)
+            dout = (torch.rand(T, H, device=DEV) - 0.5).half()
+            active = torch.unique(idx).tolist()
+            fwd = _time_stats(lambda: w4_a16_moe(x, idx, wts, *stacks), args.warmup, args.iters)
+            train = _time_stats(lambda: w4_a16_moe_train(x, idx, wts, *stacks), args.warmup, args.iters)
+            torch.cuda.synchronize()
+            m0 = torch.cuda.memory_allocated()
+            o, tables, gate_up, y = w4_a16_moe_train(x, idx, wts, *stacks)
+            torch.cuda.synchronize()
+            saved = torch.cuda.memory_allocated() - m0 - o.numel() * 2
+            a4 = w4_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks, True, True)
+            a8 = w8_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks8, True, True)
+            assert torch.equal(a4[0], a8[0]) and torch.equal(a4[1], a8[1]), "int4 and int8 backward differ on the same integers"
+            del a4, a8
+            bwd = _interleaved({"int4": lambda: w4_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks, True, True),
+                                "int8": lambda: w8_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks8, True, True)},
+                               args.warmup, args.iters)
+            torch.cuda.synchronize()
+            m1 = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            w4_a16_moe_backward(dout, wts, tables, gate_up, y, *stacks, True, True)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - m1
+            offsets, position = tables[E:], tables[2 * E + 1 + S:]
+            active_t = tables[2 * E + 1 + 2 * S:]
+            dy = torch.empty(S, H, dtype=torch.float16, device=DEV)
+            dw = torch.empty_like(wts)
+            dh = torch.empty(S, I, dtype=torch.float16, device=DEV)
+            dgu = torch.empty(S, 2 * I, dtype=torch.float16, device=DEV)
+            dxs = torch.empty(S, H, dtype=torch.float16, device=DEV)
+            dx = torch.empty(T, H, dtype=torch.float16, device=DEV)
+            ones = torch.ones(T, k, device=DEV)
+
+            def gemm_t(fn, w, which):
+                if which == "down":
+                    return lambda: fn(_ptr(dy), _ptr(w), _ptr(dn_s), _ptr(offsets), _ptr(active_t), _ptr(dh), T, k, E, H, I, st)
+                return lambda: fn(_ptr(dgu), _ptr(w), _ptr(gu_s), _ptr(offsets), _ptr(active_t), _ptr(dxs), T, k, E, 2 * I, H, st)
+            split = {"combine_bwd": _time_stats(lambda: L.eetq_moe_combine_bwd_f16(_ptr(dout), _ptr(y), _ptr(position), _ptr(wts), 1,
+                                                                                  _ptr(dy), _ptr(dw), T, k, H, st), args.warmup, args.iters)}
+            down = _interleaved({"int4": gemm_t(L.eetq_w4a16_moe_gemm_t, dn_w, "down"),
+                                 "int8": gemm_t(L.eetq_w8a16_moe_gemm_t, dn_w8, "down")}, args.warmup, args.iters)
+            split["gemm_t_down"] = down["int4"]
+            split["silu_bwd"] = _time_stats(lambda: L.eetq_silu_mul_glu8_bwd_f16(_ptr(gate_up), _ptr(dh), _ptr(dgu), S, I, st),
+                                            args.warmup, args.iters)
+            gate = _interleaved({"int4": gemm_t(L.eetq_w4a16_moe_gemm_t, gu_w, "gate_up"),
+                                 "int8": gemm_t(L.eetq_w8a16_moe_gemm_t, gu_w8, "gate_up")}, args.warmup, args.iters)
+            split["gemm_t_gate_up"] = gate["int4"]
+            split["combine"] = _time_stats(lambda: L.eetq_moe_combine_f16(_ptr(dxs), _ptr(position), _ptr(ones), 1, _ptr(dx), T, k, H, st),
+                                           args.warmup, args.iters)
+            g4, g8 = down["int4"][0] + gate["int4"][0], down["int8"][0] + gate["int8"][0]
+            rec = {"shape": name, "bits": 4, "H": H, "I": I, "E": E, "k": k, "T": T, "routing": "uniform", "active_experts": len(active),
+                   "iters": args.iters, "fwd_path": w4_a16_moe_path(T, k, E, H, I), "us_fwd_nograd": r3(fwd), "us_fwd_trainable": r3(train),
+                   "us_backward": r3(bwd["int4"]), "us_backward_int8_same_integers": r3(bwd["int8"]),
+                   "backward_int4_over_int8": round(bwd["int4"][0] / bwd["int8"][0], 3),
+                   "us_backward_split": {n: r3(t) for n, t in split.items()},
+                   "us_gemm_t_down_int8": r3(down["int8"]), "us_gemm_t_gate_up_int8": r3(gate["int8"]),
+                   "gemm_t_down_int4_over_int8": round(down["int4"][0] / down["int8"][0], 3),
+                   "gemm_t_gate_up_int4_over_int8": round(gate["int4"][0] / gate["int8"][0], 3),
+                   "gemm_t_pair_int4_over_int8": round(g4 / g8, 3),
+                   "bwd_over_trainable_fwd": round(bwd["int4"][0] / train[0], 3),
                    "saved_bytes": saved, "backward_peak_bytes": peak}
             line = json.dumps(rec)
             print(line, flush=True)
@@ -554,7 +678,7 @@ def main():
     if args.backward:
         args.tokens = args.tokens or "16,64,512,4096"
         out = open(args.out, "w") if args.out else None
-        backward(args, out)
+        (backward_i4 if args.bits == 4 else backward)(args, out)
         if out:
             out.close()
         return
