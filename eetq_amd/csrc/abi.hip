@@ -324,7 +324,10 @@ static AutoChoice auto_path_i8(int M, int N, int K, int act)
     // Llama-3-8B's fused q|k|v, 4096 x 6144: 6.8 -> 6.4 us, the one M = 1 point above 5 % in tools/auto_regret.py -- and took it
     // back: the GEMV entry points with fused prologues / epilogues (norm, glu8, the compiled decode layer) promise the bits of the
     // plain M = 1 projection, which therefore has to stay on the GEMV kernel too: tests/test_gpu_glu.py.)
-    if (M == 1) return {EETQ_PATH_GEMV, 0};
+    // A row no GEMV form can stage in LDS (K > 65536) goes to the small-batch kernel run with one row, which streams its activations
+    // and has no limit in K.  The fused-prologue entry points (norm, gated, glu8) still refuse such a row; the operator wrappers run
+    // the unfused sequence there, whose projection lands here.
+    if (M == 1) return {gemv_stages_row(1, K) ? EETQ_PATH_GEMV : EETQ_PATH_STREAM, 0};
     // One row tile (2 <= M <= 16): the MFMA stream kernel (same weight stream as the GEMV, activation rows through a per-wave
     // LDS ring or a per-workgroup copy: streamk.hip::pick_plan) on every shape (us stream / split-K at M = 16: 4096 x 11008
     // 12.60 / 12.74, 11008 x 4096 12.48 / 13.15, 8192^2 13.9 / 18.5, 28672 x 8192 41.8 / 46.9; the other way only 5120 x 27648

@@ -274,6 +274,7 @@ int launch_w4a16(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep,
                  hipStream_t stream, int path = EETQ_PATH_AUTO);
 int launch_gemv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                 hipStream_t stream, Prologue pro = Prologue{});
+bool gemv_stages_row(int M, int K);  // some GEMV form stages M rows of K activations in LDS (M * K <= 65536): gemv.hip
 namespace gemv {
 struct GroupedArgs;
 }

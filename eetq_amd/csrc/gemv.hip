@@ -46,6 +46,15 @@ int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
     return go(gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, NORM, BITS>, opted);
 }
 
+// What a WAVES-wave workgroup can stage: at most eight 16-byte x loads per thread (the widest XV instantiated) and 160 KiB of LDS.
+// 8 waves: M * K <= 32768, 16 waves: M * K <= 65536.  The launchers below ask before they pick a workgroup size, and AUTO asks
+// (gemv_stages_row) before it picks the GEMV at all.
+inline bool lds_stages(int M, int K, int waves)
+{
+    const int xvecs = M * K / 8, threads = waves * 64;
+    return gemv::gemv_smem_bytes(M, K, waves, false) <= 160 * 1024 && (xvecs + threads - 1) / threads <= 8;
+}
+
 // LDS-staged activations: pick the number of 16-byte x loads per thread at compile time (no conditional loads)
 template <int M, int WAVES, int D, bool EXACT, int OCC, int BITS = 8>
 int launch_lds(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int N, int K,
@@ -53,7 +62,7 @@ int launch_lds(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f
 {
     const int xvecs = M * K / 8, threads = WAVES * 64;
     const int need  = (xvecs + threads - 1) / threads;
-    if (gemv::gemv_smem_bytes(M, K, WAVES, false) > 160 * 1024 || need > 8)
+    if (!lds_stages(M, K, WAVES))
         return fail(EETQ_ERR_UNSUPPORTED, BITS == 4 ? "[eetq_amd] W4A16 GEMV: M*K too large for LDS staging"
                                                     : "[eetq_amd] GEMV: M*K too large for LDS staging");
     if (need <= 1) return launch_inst<M, WAVES, D, EXACT, false, 1, OCC, BITS>(x, w, scales, ep, y, N, K, stream, pro);
@@ -194,8 +203,11 @@ int launch_m(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16
             const char* e = tuning_env("EETQ_AMD_I8_GEMV_WAVES");
             return e ? atoi(e) : 0;
         }();
-        if (KT >= 32 && forced == 84) return launch_lds<M, 8, 4, false, 8>(x, w, scales, ep, y, N, K, stream, pro);
-        if (KT >= 32 && (forced == 82 || (forced == 0 && N / kTileN > 2 * device_cu_count())))
+        // (8 waves stage K <= 32768; a deeper row takes the 16-wave form below, which stages K <= 65536 -- Llama-3.1-405B's down
+        // projection, 53248 x 16384, has 1024 tile rows and would otherwise be refused here)
+        const bool fits8 = lds_stages(M, K, 8);
+        if (KT >= 32 && fits8 && forced == 84) return launch_lds<M, 8, 4, false, 8>(x, w, scales, ep, y, N, K, stream, pro);
+        if (KT >= 32 && fits8 && (forced == 82 || (forced == 0 && N / kTileN > 2 * device_cu_count())))
             return launch_lds<M, 8, 2, false, 8>(x, w, scales, ep, y, N, K, stream, pro);
     }
     if (KT >= 32) return launch_lds<M, 16, 2, false, (M == 1 ? 8 : 4)>(x, w, scales, ep, y, N, K, stream, pro);
@@ -264,6 +276,9 @@ int launch_m_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
 }
 
 }  // namespace
+
+// Whether any GEMV form (int8 or int4 tiles) stages M rows of K activations: the 16-wave forms' limit, M * K <= 65536
+bool gemv_stages_row(int M, int K) { return lds_stages(M, K, 16); }
 
 int launch_gemv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                 hipStream_t stream, Prologue pro)

@@ -310,6 +310,11 @@ std::vector<int64_t> out_shape(const Tensor& input, int64_t n)
     return s;
 }
 
+// The M = 1 GEMV stages its activation row in LDS: 65536 values at most (gemv.hip::lds_stages).  The entry points that fuse a norm, a
+// gated activation or the glu8 write-out into that launch refuse a deeper row; w8_a16_gemm then runs the unfused sequence, whose
+// projection AUTO puts on the small-batch kernel.
+constexpr int64_t kGemvMaxStaged = 65536;
+
 // reference: w8_a16_gemm_forward_cuda, fpA_intB_gemm_wrapper.cu:130-173 (fresh output, current stream, asynchronous)
 Tensor w8_a16_gemm(const Tensor& input_in, const Tensor& weight, const Tensor& scale, const std::string& path,
                    const OptTensor& bias, const OptTensor& residual, const std::optional<std::tuple<Tensor, double>>& norm,
@@ -328,8 +333,8 @@ Tensor w8_a16_gemm(const Tensor& input_in, const Tensor& weight, const Tensor& s
         const bool    fusable_norm = !norm || (std::get<0>(*norm).scalar_type() == at::kHalf &&
                                             std::get<0>(*norm).is_contiguous() && std::get<0>(*norm).numel() == kw &&
                                             std::get<0>(*norm).device() == input.device());
-        if (rows == 1 && path == "auto" && input.size(-1) == kw && input.is_cuda() && input.scalar_type() == at::kHalf &&
-            fusable_norm) {
+        if (rows == 1 && path == "auto" && kw <= kGemvMaxStaged && input.size(-1) == kw && input.is_cuda() &&
+            input.scalar_type() == at::kHalf && fusable_norm) {
             TORCH_CHECK(weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf && weight.is_contiguous() &&
                             weight.device() == input.device() && scale.device() == input.device(),
                         "w8_a16_gemm: weight must be contiguous int8 and scale float16, on the input's device");
@@ -387,7 +392,7 @@ Tensor w8_a16_gemm(const Tensor& input_in, const Tensor& weight, const Tensor& s
     if (gated) {
         TORCH_CHECK(input.size(-1) == 2 * kw, "w8_a16_gemm: gated input must be [..., 2K] for a [K, N] weight");
         const int64_t rows = input.numel() / input.size(-1);
-        if (rows == 1 && path == "auto" && !norm && input.is_cuda() && input.scalar_type() == at::kHalf &&
+        if (rows == 1 && path == "auto" && kw <= kGemvMaxStaged && !norm && input.is_cuda() && input.scalar_type() == at::kHalf &&
             input.is_contiguous() && kw % 8 == 0 && weight.size(1) == n && activation.empty()) {
             TORCH_CHECK(weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf && weight.is_contiguous(),
                         "w8_a16_gemm: weight must be contiguous int8 and scale float16");
@@ -409,8 +414,8 @@ Tensor w8_a16_gemm(const Tensor& input_in, const Tensor& weight, const Tensor& s
     if (norm) {
         const Tensor& gamma = std::get<0>(*norm);
         const double  eps   = std::get<1>(*norm);
-        if (m == 1 && path == "auto" && gamma.scalar_type() == at::kHalf && gamma.is_contiguous() && gamma.numel() == k &&
-            weight.size(1) == n && activation.empty()) {
+        if (m == 1 && path == "auto" && k <= kGemvMaxStaged && gamma.scalar_type() == at::kHalf && gamma.is_contiguous() &&
+            gamma.numel() == k && weight.size(1) == n && activation.empty()) {
             TORCH_CHECK(input.scalar_type() == at::kHalf && input.is_cuda(), "w8_a16_gemm: input must be a float16 CUDA tensor");
             TORCH_CHECK(weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf && weight.is_contiguous(),
                         "w8_a16_gemm: weight must be contiguous int8 and scale float16");

@@ -33,6 +33,10 @@ _LAYOUTS = {"gfx950": LAYOUT_GFX950, "native": LAYOUT_GFX950, "sm80": LAYOUT_SM8
             LAYOUT_GFX950: LAYOUT_GFX950, LAYOUT_SM80: LAYOUT_SM80, LAYOUT_ROW_MAJOR: LAYOUT_ROW_MAJOR}
 _PATHS = {"auto": PATH_AUTO, "gemv": PATH_GEMV, "mfma": PATH_MFMA, "stream": _lib.PATH_STREAM, "mid": _lib.PATH_MID,
           "splitk": _lib.PATH_SPLITK, "tilesplit": _lib.PATH_TILESPLIT}
+# The M = 1 GEMV stages its activation row in LDS: 65536 values at most (gemv.hip::lds_stages).  The entry points that fuse a norm, a gated
+# activation or the glu8 write-out into that launch refuse a deeper row; the operators below then run the unfused sequence, whose
+# projection AUTO puts on the small-batch kernel.
+GEMV_MAX_STAGED = 65536
 _ACTS = {"": ACT_IDENTITY, "identity": ACT_IDENTITY, "none": ACT_IDENTITY, "relu": ACT_RELU, "gelu": ACT_GELU,
          "silu": ACT_SILU}
 
@@ -283,7 +287,8 @@ def w8_a16_gemm(input, weight, scale, path="auto", bias=None, residual=None, nor
             raise RuntimeError("w8_a16_gemm: silu_glu8 takes an int8 [K, N] weight with N % 16 == 0, no residual")
         rows = input.numel() // k if k else 0
         gamma = norm[0] if norm is not None else None
-        if (rows == 1 and path == "auto" and input.shape[-1] == k and input.is_cuda and input.dtype == torch.float16
+        if (rows == 1 and path == "auto" and k <= GEMV_MAX_STAGED and input.shape[-1] == k and input.is_cuda
+                and input.dtype == torch.float16
                 and (gamma is None or (gamma.dtype == torch.float16 and gamma.is_contiguous() and gamma.numel() == k
                                        and gamma.device == input.device))):
             return _gemv_glu8_launch(input, gamma, norm[1] if norm is not None else 0.0, weight, scale, bias, n, k)
@@ -303,8 +308,8 @@ def w8_a16_gemm(input, weight, scale, path="auto", bias=None, residual=None, nor
         if k2 != 2 * k:
             raise RuntimeError("w8_a16_gemm: gated input must be [..., 2K] for a [K, N] weight")
         rows = input.numel() // k2 if k2 else 0
-        if (rows == 1 and path == "auto" and norm is None and input.is_cuda and input.dtype == torch.float16
-                and input.is_contiguous() and k % 8 == 0 and not act):
+        if (rows == 1 and path == "auto" and k <= GEMV_MAX_STAGED and norm is None and input.is_cuda
+                and input.dtype == torch.float16 and input.is_contiguous() and k % 8 == 0 and not act):
             n = weight.shape[-1]
             output = torch.empty(tuple(input.shape[:-1]) + (n,), dtype=input.dtype, device=input.device)
             return _gemv_gated_launch(input, weight, scale, output, n, k, bias, residual)
@@ -319,8 +324,8 @@ def w8_a16_gemm(input, weight, scale, path="auto", bias=None, residual=None, nor
         return output
     if norm is not None:
         gamma, eps = norm
-        if (m == 1 and path == "auto" and gamma.dtype == torch.float16 and gamma.is_contiguous() and gamma.numel() == k
-                and not act):
+        if (m == 1 and path == "auto" and k <= GEMV_MAX_STAGED and gamma.dtype == torch.float16 and gamma.is_contiguous()
+                and gamma.numel() == k and not act):
             return _gemv_rmsnorm_launch(input, gamma, eps, weight, scale, output, n, k, bias, residual)
         normed = torch.empty_like(input if input.is_contiguous() else input.contiguous())
         layernorm_forward(input if input.is_contiguous() else input.contiguous(), gamma, normed, eps)

@@ -28,6 +28,11 @@ M_GEMV = (1, 2, 3, 4)
 SHAPES = [(N, K) for K in (4096, 8192) for N in (4096, 4112, 5120, 8192, 11008, 14336, 22016)] + \
          [(4096, 64), (4096, 256), (4096, 1024), (4096, 2048), (1024, 8192), (5120, 13824)]
 MAX_N, MAX_K, MAX_M = 22016, 13824, 64
+# (N, K), 16384 <= K <= 32768, for the GEMV launchers alone (M * K <= 65536: what they stage in LDS): the column units with eight
+# activation loads per thread (64 x 28672, 64 x 32768; 5120 x 28672: 8 + 8 + 4), the 16-wave generic form with four (64 x 28736, K / 64
+# odd) and the 8-wave one with four and eight (8208 x 16384 / 28672 / 32768: 513 tile rows), M = 4 at its deepest K (64 x 16384)
+DEEP_SHAPES = [(64, 16384), (8208, 16384), (64, 28672), (5120, 28672), (8208, 28672), (64, 28736), (64, 32768), (8208, 32768)]
+DEEP_N, DEEP_K = 8208, 32768
 
 
 def _sha(t):
@@ -46,10 +51,13 @@ def main():
     bpool = torch.randn(MAX_N, generator=g).half().to(DEV)
     rpool = torch.randn(MAX_M * MAX_N, generator=g).half().to(DEV)
     gamma = (torch.rand(MAX_K, generator=g) + 0.5).half().to(DEV)
+    # (drawn after everything above, so the lines of SHAPES do not depend on the deep pools)
+    wdeep = torch.randint(-128, 128, (DEEP_K * DEEP_N,), dtype=torch.int8, generator=g).to(DEV)
+    gamma_deep = (torch.rand(DEEP_K, generator=g) + 0.5).half().to(DEV)
 
     def emit(bits, path, M, N, K, variant, **kw):
         nb = N // 2 if bits == 4 else N
-        w = wpool[:K * nb].view(K, nb)
+        w = (wdeep if K > MAX_K else wpool)[:K * nb].view(K, nb)
         x = xpool[:M * K * (2 if kw.get("gated") else 1)].view(M, -1)
         y = ops.w8_a16_gemm(x, w, spool[bits][:N], path, **kw)
         assert bool(torch.isfinite(y.float()).all()), (bits, path, M, N, K, variant)
@@ -68,6 +76,19 @@ def main():
                             emit(bits, path, M, N, K, "silu_glu8", activation="silu_glu8")
                         if bits == 8 and path == "auto" and M == 1:   # the GEMV's prologue instantiations
                             emit(bits, path, M, N, K, "norm", norm=(gamma[:K], 1e-5))
+                            emit(bits, path, M, N, K, "gated", gated=True)
+            for path in ("gemv", "auto"):
+                for N, K in DEEP_SHAPES:
+                    if bits == 4 and K % 128:
+                        continue
+                    for M in M_GEMV:
+                        if M * K > 65536:
+                            continue
+                        emit(bits, path, M, N, K, "plain")
+                        emit(bits, path, M, N, K, "bias+residual", bias=bpool[:N], residual=rpool[:M * N].view(M, N))
+                        if bits == 8 and path == "auto" and M == 1:
+                            emit(bits, path, M, N, K, "silu_glu8", activation="silu_glu8")
+                            emit(bits, path, M, N, K, "norm", norm=(gamma_deep[:K], 1e-5))
                             emit(bits, path, M, N, K, "gated", gated=True)
 
 
