@@ -75,6 +75,13 @@ def _declare(L):
         "eetq_rmsnorm_f16": [vp, vp, vp, f32, i32, i32, vp],
         "eetq_rotary_neox_f16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "eetq_rotary_neox": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+        "eetq_rotary_neox_bounded": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "eetq_rotary_neox_strided_bounded_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+        "eetq_rotary_neox_kvcache_bounded_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp],
+        "eetq_rotary_neox_kvcache_prefill_bounded_f16": [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp,
+                                                         i32, vp],
+        "eetq_rope_decode_attention_bounded_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                                   i32, ctypes.c_float, vp, vp, i32, vp, vp],
         "eetq_w8a16_gemv_grouped": [vp, i32, vp],
         "eetq_decode_dropped_steps": [vp, i32],
         "eetq_rotary_neox_strided_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
@@ -152,6 +159,8 @@ EXPORTED_SYMBOLS = (
     "eetq_w4a16_moe_gemm", "eetq_expand_i4_to_i8", "eetq_w8a16_moe_gemm_tiled_supported",
     "eetq_w4a16_moe_gemm_tiled", "eetq_w4a16_moe_gemm_tiled_supported",
     "eetq_moe_router_f16", "eetq_moe_topk_f16", "eetq_moe_router_sigmoid_f16", "eetq_moe_topk_sigmoid_f32",
+    "eetq_rotary_neox_bounded", "eetq_rotary_neox_strided_bounded_f16", "eetq_rotary_neox_kvcache_bounded_f16",
+    "eetq_rotary_neox_kvcache_prefill_bounded_f16", "eetq_rope_decode_attention_bounded_f16",
 )
 
 

@@ -567,7 +567,7 @@ int eetq_rotary_neox_f16(const int64_t* positions, void* query, void* key, const
 {
     return launch_rotary(positions, static_cast<f16*>(query), static_cast<f16*>(key),
                          static_cast<const f16*>(cos_sin_cache), tokens, heads, heads, head_size, rot_dim,
-                         heads * head_size, heads * head_size, static_cast<hipStream_t>(stream));
+                         heads * head_size, heads * head_size, kTableRowsUnknown, static_cast<hipStream_t>(stream));
 }
 
 int eetq_w8a16_gemv_grouped(const eetq_gemv_problem* problems, int count, void* stream)
@@ -627,7 +627,15 @@ int eetq_rotary_neox(const int64_t* positions, void* query, void* key, const voi
                      int heads, int head_size, int rot_dim, void* stream)
 {
     return launch_rotary_any(positions, query, key, cos_sin_cache, dtype, tokens, heads, heads, head_size, rot_dim,
-                             heads * head_size, heads * head_size, static_cast<hipStream_t>(stream));
+                             heads * head_size, heads * head_size, kTableRowsUnknown, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rotary_neox_bounded(const int64_t* positions, void* query, void* key, const void* cos_sin_cache, int table_rows,
+                             int dtype, int tokens, int heads, int head_size, int rot_dim, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return launch_rotary_any(positions, query, key, cos_sin_cache, dtype, tokens, heads, heads, head_size, rot_dim,
+                             heads * head_size, heads * head_size, table_rows, static_cast<hipStream_t>(stream));
 }
 
 int eetq_rotary_neox_strided_f16(const int64_t* positions, void* query, void* key, const void* cos_sin_cache,
@@ -636,7 +644,17 @@ int eetq_rotary_neox_strided_f16(const int64_t* positions, void* query, void* ke
 {
     return launch_rotary(positions, static_cast<f16*>(query), static_cast<f16*>(key),
                          static_cast<const f16*>(cos_sin_cache), tokens, q_heads, k_heads, head_size, rot_dim, q_stride,
-                         k_stride, static_cast<hipStream_t>(stream));
+                         k_stride, kTableRowsUnknown, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rotary_neox_strided_bounded_f16(const int64_t* positions, void* query, void* key, const void* cos_sin_cache,
+                                         int table_rows, int tokens, int q_heads, int k_heads, int head_size, int rot_dim,
+                                         int q_stride, int k_stride, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return launch_rotary(positions, static_cast<f16*>(query), static_cast<f16*>(key),
+                         static_cast<const f16*>(cos_sin_cache), tokens, q_heads, k_heads, head_size, rot_dim, q_stride,
+                         k_stride, table_rows, static_cast<hipStream_t>(stream));
 }
 
 int eetq_w8a16_gemv_rmsnorm(const void* x, const void* gamma, float eps, const int8_t* w_packed, const void* scales,
@@ -727,10 +745,10 @@ int eetq_silu_mul_f16(const void* gate_up, void* out, int rows, int intermediate
                            static_cast<hipStream_t>(stream));
 }
 
-int eetq_rotary_neox_kvcache_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query,
-                                 const void* key, const void* value, const void* cos_sin_cache, void* k_cache,
-                                 void* v_cache, int batch, int q_heads, int k_heads, int head_size, int rot_dim,
-                                 const long* strides, int max_positions, void* stream)
+static int rotary_kvcache_entry(const int64_t* positions, const int64_t* slots, int slot_stride, void* query, const void* key,
+                                const void* value, const void* cos_sin_cache, long table_rows, void* k_cache, void* v_cache,
+                                int batch, int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                int max_positions, void* stream)
 {
     EETQ_REQUIRE(strides, "null pointer");
     EETQ_REQUIRE(slot_stride == 0 || slot_stride == 1, "slot_stride must be 0 (one slot for the batch) or 1");
@@ -738,13 +756,32 @@ int eetq_rotary_neox_kvcache_f16(const int64_t* positions, const int64_t* slots,
                                  static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
                                  static_cast<f16*>(k_cache), static_cast<f16*>(v_cache), batch, q_heads, k_heads, head_size,
                                  rot_dim, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
-                                 max_positions, static_cast<hipStream_t>(stream));
+                                 max_positions, table_rows, static_cast<hipStream_t>(stream));
 }
 
-int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, const void* key, const void* value,
-                                         const void* cos_sin_cache, void* k_cache, void* v_cache, int batch, int tokens,
-                                         const int64_t* first_row_dev, int first_row, int q_heads, int k_heads, int head_size,
+int eetq_rotary_neox_kvcache_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query,
+                                 const void* key, const void* value, const void* cos_sin_cache, void* k_cache,
+                                 void* v_cache, int batch, int q_heads, int k_heads, int head_size, int rot_dim,
+                                 const long* strides, int max_positions, void* stream)
+{
+    return rotary_kvcache_entry(positions, slots, slot_stride, query, key, value, cos_sin_cache, kTableRowsUnknown, k_cache,
+                                v_cache, batch, q_heads, k_heads, head_size, rot_dim, strides, max_positions, stream);
+}
+
+int eetq_rotary_neox_kvcache_bounded_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query,
+                                         const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                         void* k_cache, void* v_cache, int batch, int q_heads, int k_heads, int head_size,
                                          int rot_dim, const long* strides, int max_positions, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return rotary_kvcache_entry(positions, slots, slot_stride, query, key, value, cos_sin_cache, table_rows, k_cache, v_cache,
+                                batch, q_heads, k_heads, head_size, rot_dim, strides, max_positions, stream);
+}
+
+static int rotary_kvcache_prefill_entry(const int64_t* positions, void* query, const void* key, const void* value,
+                                        const void* cos_sin_cache, long table_rows, void* k_cache, void* v_cache, int batch,
+                                        int tokens, const int64_t* first_row_dev, int first_row, int q_heads, int k_heads,
+                                        int head_size, int rot_dim, const long* strides, int max_positions, void* stream)
 {
     EETQ_REQUIRE(strides, "null pointer");
     EETQ_REQUIRE(batch >= 0 && tokens >= 0, "invalid shape");
@@ -754,7 +791,29 @@ int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, 
                                  static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
                                  static_cast<f16*>(k_cache), static_cast<f16*>(v_cache), batch, q_heads, k_heads, head_size,
                                  rot_dim, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
-                                 max_positions, static_cast<hipStream_t>(stream), tokens, first_row);
+                                 max_positions, table_rows, static_cast<hipStream_t>(stream), tokens, first_row);
+}
+
+int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, const void* key, const void* value,
+                                         const void* cos_sin_cache, void* k_cache, void* v_cache, int batch, int tokens,
+                                         const int64_t* first_row_dev, int first_row, int q_heads, int k_heads, int head_size,
+                                         int rot_dim, const long* strides, int max_positions, void* stream)
+{
+    return rotary_kvcache_prefill_entry(positions, query, key, value, cos_sin_cache, kTableRowsUnknown, k_cache, v_cache, batch,
+                                        tokens, first_row_dev, first_row, q_heads, k_heads, head_size, rot_dim, strides,
+                                        max_positions, stream);
+}
+
+int eetq_rotary_neox_kvcache_prefill_bounded_f16(const int64_t* positions, void* query, const void* key, const void* value,
+                                                 const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache,
+                                                 int batch, int tokens, const int64_t* first_row_dev, int first_row,
+                                                 int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                                 int max_positions, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return rotary_kvcache_prefill_entry(positions, query, key, value, cos_sin_cache, table_rows, k_cache, v_cache, batch, tokens,
+                                        first_row_dev, first_row, q_heads, k_heads, head_size, rot_dim, strides, max_positions,
+                                        stream);
 }
 
 int eetq_greedy_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
@@ -784,7 +843,23 @@ int eetq_rope_decode_attention_f16(const int64_t* positions, const int64_t* slot
                                    static_cast<const f16*>(cos_sin_cache), static_cast<f16*>(k_cache),
                                    static_cast<f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
                                    workspace, tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling,
-                                   strides, kv_len, kv_len_bias, advance, static_cast<hipStream_t>(stream));
+                                   strides, kv_len, kv_len_bias, advance, kTableRowsUnknown, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rope_decode_attention_bounded_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                           const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                           void* k_cache, void* v_cache, const void* mask, void* out, float* workspace,
+                                           unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                           int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                           int kv_len_bias, int64_t* advance, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return launch_rope_attn_decode(positions, slots, slot_stride, static_cast<const f16*>(query),
+                                   static_cast<const f16*>(key), static_cast<const f16*>(value),
+                                   static_cast<const f16*>(cos_sin_cache), static_cast<f16*>(k_cache),
+                                   static_cast<f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
+                                   workspace, tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling,
+                                   strides, kv_len, kv_len_bias, advance, table_rows, static_cast<hipStream_t>(stream));
 }
 
 int eetq_prefill_attention_f16(const void* q, const void* k, const void* v, void* out, int batch, int heads, int kv_heads, int q_tokens,

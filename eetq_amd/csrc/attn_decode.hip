@@ -617,6 +617,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
                  : "memory");
     ATTN_STAMP(1);
     // a slot outside the cache is neither written nor attended, and (like the two-launch form) nothing is rotated then
+    // (no upper bound on rpos here, unlike the two-launch form: launch_rope_attn_decode's table_rows)
     const bool have_new = slot64 >= 0 && slot64 < a.S && rpos >= 0;
     const int  slot = have_new ? (int)slot64 : -1;
     // a full cache (or a bad position) used to be silent: count the dropped steps (eetq_decode_dropped_steps)
@@ -743,11 +744,15 @@ void set_attn_stamps(unsigned long long* buf) { g_attn_stamps = buf; }
 int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
                             const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
                             unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
-                            const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, hipStream_t stream)
+                            const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
+                            hipStream_t stream)
 {
     EETQ_REQUIRE(positions && q && k && v && cos_sin && kc && vc && out && ws && tickets && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S && splits <= 4096,
                  "invalid attention shape");
+    // validated, not yet enforced on the device: with the compare in have_new the attention term of the decode budget measured
+    // above the parent's run-to-run spread, so the kernel is as it was
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
     for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v / cache strides must be multiples of 8 elements (16-byte accesses)");
     EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)cos_sin) % 16 == 0,
                  "q, k, v, the caches and the cos|sin table must be 16-byte aligned");

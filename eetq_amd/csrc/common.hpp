@@ -300,17 +300,21 @@ bool moe_tiled_narrow(int S, int E, int N);  // the launcher's tile rule: true =
 int  launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
                            const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream);
 int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows, int cols, hipStream_t stream);
+// table_rows of the rotary launchers: rows of the cos|sin table (a position outside [0, table_rows) is not rotated: nothing is
+// read for it, the token is left / dropped and counted), or kTableRowsUnknown from the entry points that do not carry it
+// (no upper bound)
+constexpr long kTableRowsUnknown = 0x7fffffffffffffffL;
 int launch_rotary(const int64_t* pos, f16* q, f16* k, const f16* cache, int tokens, int q_heads, int k_heads,
-                  int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream);
+                  int head_size, int rot_dim, int q_stride, int k_stride, long table_rows, hipStream_t stream);
 
 int launch_rotary_any(const int64_t* pos, void* q, void* k, const void* cache, int dtype, int tokens, int q_heads,
-                      int k_heads, int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream);
+                      int k_heads, int head_size, int rot_dim, int q_stride, int k_stride, long table_rows, hipStream_t stream);
 
 void set_attn_stamps(unsigned long long* buf);
 int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
                             const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
                             unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
-                            const long* strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance,
+                            const long* strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
                             hipStream_t stream);
 // causal attention over a prompt on MFMA (attn_prefill.hip); st: {q_b, q_token, q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b,
 // out_token, out_head} in elements
@@ -323,7 +327,7 @@ int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask
 
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,
                           const f16* cache, f16* kcache, f16* vcache, int batch, int q_heads, int k_heads, int head_size, int rot_dim, long q_stride,
-                          long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, hipStream_t stream, int tokens = 0,
+                          long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream, int tokens = 0,
                           int first_row = 0);  // tokens > 0: the prefill form (batch * tokens blocks, rows first_row + t)
 
 int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t stream, bool glu8 = false);

@@ -8,7 +8,9 @@
 #include "common.hpp"
 
 namespace eetq {
-__device__ unsigned g_rope_dropped = 0;  // decode steps dropped by rotary_neox_kvcache_kernel (cache row outside the cache)
+// tokens dropped by rotary_neox_kvcache_kernel (cache row outside the cache, position outside the cos|sin table) and tokens
+// left unrotated by rotary_neox_kernel (position outside the table)
+__device__ unsigned g_rope_dropped = 0;
 }  // namespace eetq
 
 namespace eetq {
@@ -36,7 +38,7 @@ __device__ __forceinline__ float block_sum(float v, float* red)
     return s;
 }
 
-// one workgroup per row; 8 fp16 (16 B) per lane per step when cols % 8 == 0
+// one workgroup per row; 8 fp16 (16 B) per lane per step when cols % 8 == 0 and x, gamma and out are 16-byte aligned
 template <int THREADS, bool VEC>
 __global__ __launch_bounds__(THREADS) void rmsnorm_kernel(const f16* __restrict__ x, const f16* __restrict__ gamma,
                                                           f16* __restrict__ out, float eps, int cols)
@@ -77,14 +79,20 @@ __global__ __launch_bounds__(THREADS) void rmsnorm_kernel(const f16* __restrict_
 // T = f16 (every product and sum an fp16 operation, like the reference's half operators), float or double (plain IEEE
 // operations of that type, no contraction): the reference dispatches float / double / half / bfloat16
 // (pos_encoding_kernels.cu:73-86); bf16 is outside this library's scope.
+// A token whose position is outside [0, table_rows) has no row in the table: it is left unrotated and counted
+// (eetq_decode_dropped_steps); the reference reads whatever lies there.
 template <typename T>
 __global__ void rotary_neox_kernel(const int64_t* __restrict__ positions, T* __restrict__ query,
                                    T* __restrict__ key, const T* __restrict__ cache, int rot_dim, int q_stride,
-                                   int k_stride, int q_heads, int k_heads, int head_size)
+                                   int k_stride, int q_heads, int k_heads, int head_size, int64_t table_rows)
 {
 #pragma clang fp contract(off)
     const int     token = blockIdx.x;
     const int64_t pos   = positions[token];
+    if (pos < 0 || pos >= table_rows) {
+        if (threadIdx.x == 0) atomicAdd(&g_rope_dropped, 1u);
+        return;
+    }
     const T*      cp    = cache + pos * rot_dim;
     const int     embed = rot_dim / 2;
     const int     nq = q_heads * embed, n = nq + k_heads * embed;
@@ -147,7 +155,7 @@ __global__ void rotary_neox_kvcache_kernel(const int64_t* __restrict__ positions
                                            const f16* __restrict__ cache, f16* __restrict__ kcache,
                                            f16* __restrict__ vcache, int rot_dim, long q_stride, long k_stride,
                                            long v_stride, long c_sb, long c_sh, long c_ss, int q_heads, int k_heads,
-                                           int head_size, int max_pos, int tokens, int first_row)
+                                           int head_size, int max_pos, int tokens, int first_row, int64_t table_rows)
 {
 #pragma clang fp contract(off)
     const int     b    = blockIdx.x;
@@ -155,7 +163,8 @@ __global__ void rotary_neox_kvcache_kernel(const int64_t* __restrict__ positions
     const int64_t rpos = positions[b];                               // index into the cos|sin table
     const int64_t pos  = tokens > 0 ? (slots ? slots[0] : (int64_t)first_row) + (b - cb * tokens)
                                     : slots ? slots[(long)b * slot_stride] : rpos;  // cache row the new token is written to
-    if (pos < 0 || pos >= max_pos || rpos < 0) {  // never write outside the cache; counted (eetq_decode_dropped_steps)
+    // never write outside the cache, never read outside the table; counted (eetq_decode_dropped_steps)
+    if (pos < 0 || pos >= max_pos || rpos < 0 || rpos >= table_rows) {
         if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&g_rope_dropped, 1u);
         return;
     }
@@ -301,14 +310,15 @@ int launch_greedy_handover(const f16* logits, long row_stride, int vocab, int ba
 
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,
                           const f16* cache, f16* kcache, f16* vcache, int batch, int q_heads, int k_heads, int head_size, int rot_dim, long q_stride,
-                          long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, hipStream_t stream, int tokens,
-                          int first_row)
+                          long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream,
+                          int tokens, int first_row)
 {
     EETQ_REQUIRE(pos && q && k && v && cache && kcache && vcache, "null pointer");
     EETQ_REQUIRE(tokens >= 0 && first_row >= 0 && (slots || (long)first_row + tokens <= max_pos), "the prefill rows must lie inside the cache");
     EETQ_REQUIRE(batch >= 0 && q_heads > 0 && k_heads > 0 && head_size > 0 && rot_dim > 0 && rot_dim % 2 == 0 &&
                      rot_dim <= head_size && max_pos > 0,
                  "invalid rotary shape");
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
     if (batch == 0) return EETQ_OK;
     const int  blocks = tokens > 0 ? batch * tokens : batch;
     const bool vec    = rot_dim == head_size && head_size % 16 == 0 &&
@@ -317,11 +327,11 @@ int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_str
     if (vec)
         rotary_neox_kvcache_kernel<true><<<dim3(blocks, 3), 256, 0, stream>>>(pos, slots, slot_stride, q, k, v, cache, kcache, vcache,
                                                                                rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss,
-                                                                               q_heads, k_heads, head_size, max_pos, tokens, first_row);
+                                                                               q_heads, k_heads, head_size, max_pos, tokens, first_row, (int64_t)table_rows);
     else
         rotary_neox_kvcache_kernel<false><<<dim3(blocks, 3), 512, 0, stream>>>(pos, slots, slot_stride, q, k, v, cache, kcache, vcache,
                                                                                 rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss,
-                                                                                q_heads, k_heads, head_size, max_pos, tokens, first_row);
+                                                                                q_heads, k_heads, head_size, max_pos, tokens, first_row, (int64_t)table_rows);
     return check_hip(hipGetLastError(), "rotary_neox_kvcache_kernel launch");
 }
 
@@ -329,6 +339,7 @@ int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t st
 {
     EETQ_REQUIRE(gu && out, "null pointer");
     EETQ_REQUIRE(rows >= 0 && inter > 0 && inter % 8 == 0, "silu_mul: the intermediate size must be a multiple of 8");
+    EETQ_REQUIRE((((uintptr_t)gu | (uintptr_t)out) & 15) == 0, "silu_mul: gate_up and out must be 16-byte aligned");
     if (rows == 0) return EETQ_OK;
     const long n = (long)rows * inter;
     if (glu8)
@@ -343,7 +354,8 @@ int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows
     EETQ_REQUIRE(x && gamma && out, "null pointer");
     EETQ_REQUIRE(rows >= 0 && cols > 0, "invalid shape");
     if (rows == 0) return EETQ_OK;
-    if (cols % 8 == 0)
+    // the 16-byte form needs whole vectors per row and aligned rows: anything else takes the scalar form
+    if (cols % 8 == 0 && (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)out) & 15) == 0)
         rmsnorm_kernel<256, true><<<rows, 256, 0, stream>>>(x, gamma, out, eps, cols);
     else
         rmsnorm_kernel<256, false><<<rows, 256, 0, stream>>>(x, gamma, out, eps, cols);
@@ -352,43 +364,45 @@ int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows
 
 template <typename T>
 static int launch_rotary_t(const int64_t* pos, T* q, T* k, const T* cache, int tokens, int q_heads, int k_heads,
-                           int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream)
+                           int head_size, int rot_dim, int q_stride, int k_stride, long table_rows, hipStream_t stream)
 {
     EETQ_REQUIRE(pos && q && k && cache, "null pointer");
     EETQ_REQUIRE(tokens >= 0 && q_heads > 0 && k_heads > 0 && head_size > 0 && rot_dim > 0 && rot_dim % 2 == 0 &&
                      rot_dim <= head_size,
                  "invalid rotary shape");
     EETQ_REQUIRE(q_stride >= q_heads * head_size && k_stride >= k_heads * head_size, "invalid rotary token stride");
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
     if (tokens == 0) return EETQ_OK;
     int threads = (q_heads + k_heads) * rot_dim / 2;
     threads     = threads < 512 ? threads : 512;
     threads     = (threads + 63) / 64 * 64;
     rotary_neox_kernel<T><<<tokens, threads, 0, stream>>>(pos, q, k, cache, rot_dim, q_stride, k_stride, q_heads, k_heads,
-                                                          head_size);
+                                                          head_size, (int64_t)table_rows);
     return check_hip(hipGetLastError(), "rotary_neox_kernel launch");
 }
 
 int launch_rotary(const int64_t* pos, f16* q, f16* k, const f16* cache, int tokens, int q_heads, int k_heads,
-                  int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream)
+                  int head_size, int rot_dim, int q_stride, int k_stride, long table_rows, hipStream_t stream)
 {
-    return launch_rotary_t<f16>(pos, q, k, cache, tokens, q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, stream);
+    return launch_rotary_t<f16>(pos, q, k, cache, tokens, q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, table_rows,
+                                stream);
 }
 
 // dtype: EETQ_DTYPE_F16 / F32 / F64 (query, key and cache share it)
 int launch_rotary_any(const int64_t* pos, void* q, void* k, const void* cache, int dtype, int tokens, int q_heads,
-                      int k_heads, int head_size, int rot_dim, int q_stride, int k_stride, hipStream_t stream)
+                      int k_heads, int head_size, int rot_dim, int q_stride, int k_stride, long table_rows, hipStream_t stream)
 {
     switch (dtype) {
         case EETQ_DTYPE_F16:
             return launch_rotary_t<f16>(pos, static_cast<f16*>(q), static_cast<f16*>(k), static_cast<const f16*>(cache), tokens,
-                                        q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, stream);
+                                        q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, table_rows, stream);
         case EETQ_DTYPE_F32:
             return launch_rotary_t<float>(pos, static_cast<float*>(q), static_cast<float*>(k), static_cast<const float*>(cache),
-                                          tokens, q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, stream);
+                                          tokens, q_heads, k_heads, head_size, rot_dim, q_stride, k_stride, table_rows, stream);
         case EETQ_DTYPE_F64:
             return launch_rotary_t<double>(pos, static_cast<double*>(q), static_cast<double*>(k),
                                            static_cast<const double*>(cache), tokens, q_heads, k_heads, head_size, rot_dim,
-                                           q_stride, k_stride, stream);
+                                           q_stride, k_stride, table_rows, stream);
         default: return fail(EETQ_ERR_INVALID, "[eetq_amd] rotary_embedding_neox: dtype must be float16, float32 or float64");
     }
 }

@@ -212,9 +212,10 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
                                 (long)value_cache.stride(0), (long)value_cache.stride(1), (long)value_cache.stride(2),
                                 (long)m_sb,                  (long)out.stride(0),         (long)out.stride(1)};
     c10::DeviceGuard guard(query.device());
-    check(eetq_rope_decode_attention_f16(
+    check(eetq_rope_decode_attention_bounded_f16(
         positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(),
-        key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
+        key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(),
+        value_cache.data_ptr(),
         mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
         reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits,
         (float)sc, strides, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
@@ -528,6 +529,10 @@ void layernorm_forward(const Tensor& input, const Tensor& gamma, Tensor& out, do
 }
 
 // reference: rotary_embedding_neox, pos_encoding_kernels.cu:55-87 (float / double / half; bf16 is out of scope)
+// Every rotary operator here hands the table's row count on: a token whose position is outside [0, cos_sin_cache.size(0)) is left
+// unrotated (the cache-writing forms drop it: nothing rotated, nothing cached) and counted (decode_dropped_steps) -- the
+// reference reads past its table there.  (rope_decode_attention hands it on too, but its kernel checks no upper bound yet:
+// INTEGRATION.md.)
 void rotary_embedding_neox(const Tensor& positions, Tensor& query, Tensor& key, int64_t head_size, const Tensor& cos_sin_cache)
 {
     const auto st = query.scalar_type();
@@ -543,8 +548,9 @@ void rotary_embedding_neox(const Tensor& positions, Tensor& query, Tensor& key, 
     const int64_t heads  = query.size(-2);
     c10::DeviceGuard guard(query.device());
     const int dt = st == at::kHalf ? EETQ_DTYPE_F16 : (st == at::kFloat ? EETQ_DTYPE_F32 : EETQ_DTYPE_F64);
-    check(eetq_rotary_neox(positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), cos_sin_cache.data_ptr(), dt,
-                           (int)tokens, (int)heads, (int)head_size, (int)cos_sin_cache.size(1), stream_of(query)));
+    check(eetq_rotary_neox_bounded(positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), cos_sin_cache.data_ptr(),
+                                   (int)cos_sin_cache.size(0), dt, (int)tokens, (int)heads, (int)head_size,
+                                   (int)cos_sin_cache.size(1), stream_of(query)));
 }
 
 // tokens / heads / token stride of a [..., heads, head_size] view whose leading dimensions collapse to one stride
@@ -581,9 +587,9 @@ void rotary_embedding_neox_strided(const Tensor& positions, Tensor& query, Tenso
     TORCH_CHECK(tq == tk && positions.numel() == tq,
                 "rotary_embedding_neox_strided: query, key and positions disagree on the token count");
     c10::DeviceGuard guard(query.device());
-    check(eetq_rotary_neox_strided_f16(positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(),
-                                       cos_sin_cache.data_ptr(), (int)tq, (int)hq, (int)hk, (int)head_size,
-                                       (int)cos_sin_cache.size(1), (int)sq, (int)sk, stream_of(query)));
+    check(eetq_rotary_neox_strided_bounded_f16(positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(),
+                                               cos_sin_cache.data_ptr(), (int)cos_sin_cache.size(0), (int)tq, (int)hq, (int)hk,
+                                               (int)head_size, (int)cos_sin_cache.size(1), (int)sq, (int)sk, stream_of(query)));
 }
 
 void rotary_embedding_neox_kvcache(const Tensor& positions, Tensor& query, const Tensor& key, const Tensor& value,
@@ -616,11 +622,11 @@ void rotary_embedding_neox_kvcache(const Tensor& positions, Tensor& query, const
     const long strides[6] = {(long)query.stride(0), (long)key.stride(0), (long)value.stride(0), (long)key_cache.stride(0),
                              (long)key_cache.stride(1), (long)key_cache.stride(2)};
     c10::DeviceGuard guard(query.device());
-    check(eetq_rotary_neox_kvcache_f16(positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr,
-                                       slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
-                                       cos_sin_cache.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), (int)B, (int)H,
-                                       (int)Hkv, (int)head_size, (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2),
-                                       stream_of(query)));
+    check(eetq_rotary_neox_kvcache_bounded_f16(positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr,
+                                               slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+                                               cos_sin_cache.data_ptr(), (int)cos_sin_cache.size(0), key_cache.data_ptr(),
+                                               value_cache.data_ptr(), (int)B, (int)H, (int)Hkv, (int)head_size,
+                                               (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2), stream_of(query)));
 }
 
 // Prefill on a pre-allocated KV cache (extension): query [B, T, H, D] rotated in place, key [B, T, Hkv, D] rotated into
@@ -656,11 +662,11 @@ void rotary_embedding_neox_kvcache_prefill(const Tensor& positions, Tensor& quer
     const long strides[6] = {(long)query.stride(tdim), (long)key.stride(tdim), (long)value.stride(tdim), (long)key_cache.stride(0),
                              (long)key_cache.stride(1), (long)key_cache.stride(2)};
     c10::DeviceGuard guard(query.device());
-    check(eetq_rotary_neox_kvcache_prefill_f16(positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(),
-                                               cos_sin_cache.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), (int)B,
-                                               (int)T, first_row_dev ? first_row_dev->data_ptr<int64_t>() : nullptr,
-                                               (int)first_row, (int)H, (int)Hkv, (int)head_size,
-                                               (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2), stream_of(query)));
+    check(eetq_rotary_neox_kvcache_prefill_bounded_f16(
+        positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
+        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)B, (int)T,
+        first_row_dev ? first_row_dev->data_ptr<int64_t>() : nullptr, (int)first_row, (int)H, (int)Hkv, (int)head_size,
+        (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2), stream_of(query)));
 }
 
 // Greedy decode hand-over (extension): argmax of logits [B, V] (fp16, dense rows) -> out_tokens[:, column] and next_token, then
@@ -851,11 +857,12 @@ Tensor llama_decode_layer(const Tensor& hidden, const NormArg& input_norm, const
         check(eetq_w8a16_gemv_rmsnorm(hidden.data_ptr(), g1.data_ptr(), (float)std::get<1>(input_norm), qkv_w.data_ptr<int8_t>(),
                                       qkv_s.data_ptr(), optp(qkv_b), nullptr, qkv, (int)NQ, (int)C, stream));
         const char* q = static_cast<const char*>(qkv);
-        check(eetq_rope_decode_attention_f16(positions.data_ptr<int64_t>(), cnt, 0, q, q + heads * D * 2,
-                                             q + (heads + kv_heads) * D * 2, cos_sin_cache.data_ptr(), key_cache.data_ptr(),
-                                             value_cache.data_ptr(), mrow, att, ws,
-                                             reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), 1, (int)heads,
-                                             (int)kv_heads, (int)S, (int)D, (int)splits, (float)scaling, st, cnt, 1, cnt, stream));
+        check(eetq_rope_decode_attention_bounded_f16(positions.data_ptr<int64_t>(), cnt, 0, q, q + heads * D * 2,
+                                                     q + (heads + kv_heads) * D * 2, cos_sin_cache.data_ptr(),
+                                                     (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(),
+                                                     mrow, att, ws, reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), 1,
+                                                     (int)heads, (int)kv_heads, (int)S, (int)D, (int)splits, (float)scaling, st, cnt,
+                                                     1, cnt, stream));
         check(eetq_w8a16_gemm_act(att, o_w.data_ptr<int8_t>(), o_s.data_ptr(), optp(o_b), hidden.data_ptr(), h.data_ptr(), 1,
                                   (int)C, (int)(heads * D), EETQ_PATH_AUTO, EETQ_ACT_IDENTITY, stream));
         if (glu8) {  // gate|up in "glu8" column order: the activation rides in the projection's epilogue

@@ -86,7 +86,10 @@ from .sampling import sampling_params  # noqa: E402  (plain Python, shared by bo
 
 def decode_dropped_steps(reset=True, device=None):
     """Decode steps the KV-cache kernels skipped because the cache row lay outside the cache (a full static cache): 0 unless
-    generation overran ``max_cache_len`` -- then every token after that point is wrong.  Synchronises the device."""
+    generation overran ``max_cache_len`` -- then every token after that point is wrong.  Tokens whose position lies outside the
+    cos|sin table (``position >= cos_sin_cache.shape[0]`` or negative) are counted here as well: the cache-writing rotary ops
+    drop them, the plain rotary ops leave them unrotated (``rope_decode_attention`` checks no upper bound: INTEGRATION.md).
+    Synchronises the device."""
     import ctypes
 
     import torch

@@ -590,7 +590,10 @@ def w8_a16_gemv_grouped(inputs, weights, scales, biases=None, residuals=None):
 
 @_eager_only
 def rotary_embedding_neox(positions, query, key, head_size, cos_sin_cache):
-    """In-place NeoX rotary embedding of query/key (reference: pos_encoding_kernels.cu:55-87): float16, float32, float64."""
+    """In-place NeoX rotary embedding of query/key (reference: pos_encoding_kernels.cu:55-87): float16, float32, float64.
+    A token whose position is outside ``[0, cos_sin_cache.shape[0])`` is left unrotated and counted
+    (``decode_dropped_steps``); so it is in the rotary operators below, and the cache-writing ones cache nothing for it --
+    except ``rope_decode_attention``, whose kernel checks no upper bound on the position."""
     dts = {torch.float16: 0, torch.float32: 1, torch.float64: 2}
     if query.dtype not in dts:
         raise RuntimeError("eetq_amd: rotary_embedding_neox is implemented for float16, float32 and float64")
@@ -605,8 +608,9 @@ def rotary_embedding_neox(positions, query, key, head_size, cos_sin_cache):
     rot_dim = cos_sin_cache.shape[1]
     heads = query.shape[-2]
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_rotary_neox(_ptr(positions), _ptr(query), _ptr(key), _ptr(cos_sin_cache), dts[query.dtype],
-                                          tokens, heads, int(head_size), rot_dim, _stream_ptr()))
+        check(_lib.lib().eetq_rotary_neox_bounded(_ptr(positions), _ptr(query), _ptr(key), _ptr(cos_sin_cache),
+                                                  cos_sin_cache.shape[0], dts[query.dtype], tokens, heads, int(head_size),
+                                                  rot_dim, _stream_ptr()))
     return None
 
 
@@ -645,9 +649,9 @@ def rotary_embedding_neox_strided(positions, query, key, head_size, cos_sin_cach
     if tq != tk or positions.numel() != tq:
         raise RuntimeError("rotary_embedding_neox_strided: query, key and positions disagree on the token count")
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_rotary_neox_strided_f16(_ptr(positions), _ptr(query), _ptr(key), _ptr(cos_sin_cache), tq,
-                                                      hq, hk, int(head_size), cos_sin_cache.shape[1], sq, sk,
-                                                      _stream_ptr()))
+        check(_lib.lib().eetq_rotary_neox_strided_bounded_f16(_ptr(positions), _ptr(query), _ptr(key), _ptr(cos_sin_cache),
+                                                              cos_sin_cache.shape[0], tq, hq, hk, int(head_size),
+                                                              cos_sin_cache.shape[1], sq, sk, _stream_ptr()))
     return None
 
 
@@ -755,9 +759,10 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
                                    key_cache.stride(1), key_cache.stride(2), value_cache.stride(0), value_cache.stride(1),
                                    value_cache.stride(2), m_sb, out.stride(0), out.stride(1))
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_rope_decode_attention_f16(
+        check(_lib.lib().eetq_rope_decode_attention_bounded_f16(
             _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
-            _ptr(cos_sin_cache), _ptr(key_cache), _ptr(value_cache), _ptr(mrow) if mrow is not None else None, _ptr(out),
+            _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache),
+            _ptr(mrow) if mrow is not None else None, _ptr(out),
             _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits), float(scaling), strides,
             _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
             _ptr(advance) if advance is not None else None, _stream_ptr()))
@@ -797,11 +802,12 @@ def rotary_embedding_neox_kvcache(positions, query, key, value, head_size, cos_s
     strides = (ctypes.c_long * 6)(query.stride(0), key.stride(0), value.stride(0), key_cache.stride(0),
                                   key_cache.stride(1), key_cache.stride(2))
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_rotary_neox_kvcache_f16(_ptr(positions), _ptr(slots) if slots is not None else None,
-                                                      slot_stride, _ptr(query), _ptr(key), _ptr(value),
-                                                      _ptr(cos_sin_cache), _ptr(key_cache), _ptr(value_cache), B, H, Hkv,
-                                                      int(head_size), cos_sin_cache.shape[1], strides,
-                                                      key_cache.shape[2], _stream_ptr()))
+        check(_lib.lib().eetq_rotary_neox_kvcache_bounded_f16(_ptr(positions), _ptr(slots) if slots is not None else None,
+                                                              slot_stride, _ptr(query), _ptr(key), _ptr(value),
+                                                              _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
+                                                              _ptr(value_cache), B, H, Hkv, int(head_size),
+                                                              cos_sin_cache.shape[1], strides, key_cache.shape[2],
+                                                              _stream_ptr()))
     return None
 
 
@@ -841,11 +847,10 @@ def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_siz
     strides = (ctypes.c_long * 6)(query.stride(tdim), key.stride(tdim), value.stride(tdim), key_cache.stride(0),
                                   key_cache.stride(1), key_cache.stride(2))
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_rotary_neox_kvcache_prefill_f16(_ptr(positions), _ptr(query), _ptr(key), _ptr(value),
-                                                              _ptr(cos_sin_cache), _ptr(key_cache), _ptr(value_cache), B, T,
-                                                              _ptr(first_row_dev) if first_row_dev is not None else None,
-                                                              int(first_row), H, Hkv, int(head_size), cos_sin_cache.shape[1],
-                                                              strides, key_cache.shape[2], _stream_ptr()))
+        check(_lib.lib().eetq_rotary_neox_kvcache_prefill_bounded_f16(
+            _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
+            _ptr(value_cache), B, T, _ptr(first_row_dev) if first_row_dev is not None else None, int(first_row), H, Hkv,
+            int(head_size), cos_sin_cache.shape[1], strides, key_cache.shape[2], _stream_ptr()))
     return None
 
 

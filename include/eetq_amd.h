@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -184,7 +184,8 @@ int eetq_w4a16_gemm_ex(const void* x, const int8_t* w_packed, const void* scales
 /* ---- side ops --------------------------------------------------------------------------------------
  * Replaces EETQ.layernorm_forward -> layernorm_forward_cuda (csrc/layernorm_kernels/layernorm.cu:98-113):
  * T5/RMS norm, out = clamp_fp16( x * rsqrt(mean(x^2) + eps) * gamma ), fp32 math, fp16 I/O.
- * Launches on `stream` (the reference uses the default stream, layernorm.cu:76). */
+ * Launches on `stream` (the reference uses the default stream, layernorm.cu:76).  Any cols > 0 and any alignment: 16-byte
+ * accesses are used only when cols % 8 == 0 and x, gamma and out are 16-byte aligned. */
 int eetq_rmsnorm_f16(const void* x, const void* gamma, void* out, float eps, int rows, int cols, void* stream);
 
 /* Replaces EETQ.rotary_embedding_neox (csrc/embedding_kernels/pos_encoding_kernels.cu:55-87) for fp16:
@@ -207,6 +208,17 @@ int eetq_rotary_neox(const int64_t* positions, void* query, void* key, const voi
 int eetq_rotary_neox_strided_f16(const int64_t* positions, void* query, void* key, const void* cos_sin_cache,
                                  int tokens, int q_heads, int k_heads, int head_size, int rot_dim, int q_stride,
                                  int k_stride, void* stream);
+
+/* eetq_rotary_neox and eetq_rotary_neox_strided_f16 with the table's row count (added within ABI revision 7): cos_sin_cache has table_rows
+ * rows (> 0, else EETQ_ERR_INVALID).  A token whose position is outside [0, table_rows) has no row in the table: nothing is
+ * read for it, its q and k are left UNROTATED, and it is counted once (eetq_decode_dropped_steps).  The three entries above
+ * carry no row count: they check no upper bound (a position beyond the table reads whatever lies behind it, like the
+ * reference); a negative position is left unrotated and counted by them as well. */
+int eetq_rotary_neox_bounded(const int64_t* positions, void* query, void* key, const void* cos_sin_cache, int table_rows,
+                             int dtype, int tokens, int heads, int head_size, int rot_dim, void* stream);
+int eetq_rotary_neox_strided_bounded_f16(const int64_t* positions, void* query, void* key, const void* cos_sin_cache,
+                                         int table_rows, int tokens, int q_heads, int k_heads, int head_size, int rot_dim,
+                                         int q_stride, int k_stride, void* stream);
 
 /* Grouped decode GEMV (extension; the reference's launcher takes one problem per call,
  * csrc/weightOnlyBatchedGemv/kernelLauncher.cu:122-232): `count` INDEPENDENT M = 1 problems -- no problem reads what
@@ -242,7 +254,8 @@ int eetq_w8a16_gemv_silu_gated(const void* gate_up, const int8_t* w_packed, cons
 
 /* Gated-MLP activation on a fused gate|up projection output (extension): out[r][i] = silu(gate_up[r][i]) *
  * gate_up[r][intermediate + i], gate_up [rows][2 * intermediate] dense, intermediate % 8 == 0.  fp32 silu rounded to fp16,
- * then an fp16 multiply. */
+ * then an fp16 multiply.  gate_up and out must be 16-byte aligned (EETQ_ERR_INVALID otherwise; the same for
+ * eetq_silu_mul_glu8_f16): the kernels move 16 bytes per access. */
 int eetq_silu_mul_f16(const void* gate_up, void* out, int rows, int intermediate, void* stream);
 
 /* Gated MLP with the activation in the projection's epilogue (extension).  "glu8" column order of a fused gate|up weight:
@@ -464,6 +477,20 @@ int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, 
                                          const int64_t* first_row_dev, int first_row, int q_heads, int k_heads, int head_size,
                                          int rot_dim, const long* strides, int max_positions, void* stream);
 
+/* The two entries above with the cos|sin table's row count (added within ABI revision 7; table_rows > 0, else EETQ_ERR_INVALID): a token
+ * whose position is >= table_rows is treated exactly like one with a negative position or a cache row outside the cache --
+ * nothing is read from the table, q is not rotated, nothing is written to the caches, and the token is counted once
+ * (eetq_decode_dropped_steps).  The entries without a row count check no upper bound on the position. */
+int eetq_rotary_neox_kvcache_bounded_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query,
+                                         const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                         void* k_cache, void* v_cache, int batch, int q_heads, int k_heads, int head_size,
+                                         int rot_dim, const long* strides, int max_positions, void* stream);
+int eetq_rotary_neox_kvcache_prefill_bounded_f16(const int64_t* positions, void* query, const void* key, const void* value,
+                                                 const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache,
+                                                 int batch, int tokens, const int64_t* first_row_dev, int first_row,
+                                                 int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                                 int max_positions, void* stream);
+
 /* Greedy decode hand-over (extension, ABI 5; the reference's recipe leaves this to transformers' generate loop,
  * examples/models/llama_transformers_example.py:68-79): for each of `batch` rows of fp16 logits [batch][vocab] (row_stride
  * elements apart) the index of the maximum -- the first one on ties, a NaN counts as the maximum: torch.argmax's answer -- is
@@ -539,6 +566,16 @@ int eetq_rope_decode_attention_f16(const int64_t* positions, const int64_t* slot
                                    int batch, int heads, int kv_heads, int max_positions, int head_dim, int splits,
                                    float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
                                    int64_t* advance, void* stream);
+/* ... with the cos|sin table's row count (added within ABI revision 7; table_rows > 0, else EETQ_ERR_INVALID).  The row count is
+ * validated but NOT yet enforced on the device: this launch checks no upper bound on positions[b], unlike
+ * eetq_rotary_neox_kvcache_bounded_f16 (the compare measured above the run-to-run spread of the decode step's attention term;
+ * INTEGRATION.md).  Callers must keep positions[b] < table_rows themselves. */
+int eetq_rope_decode_attention_bounded_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                           const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                           void* k_cache, void* v_cache, const void* mask, void* out, float* workspace,
+                                           unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                           int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                           int kv_len_bias, int64_t* advance, void* stream);
 
 /* Causal attention over a PROMPT on the matrix cores (extension, ABI revision 6): out[b][t][h] = softmax_j<=t+causal_offset(scaling
  * q[b][t][h] . k[b][h / groups][j]) v[b][h / groups][j] over the first `keys` rows of a KV cache, fp16 in / out, fp32 scores, softmax
@@ -601,7 +638,9 @@ int eetq_diag_auto_path(int bits, int M, int N, int K, int* path, int* detail);
 int eetq_diag_splitk_plan(int M, int N, int K, int* column_blocks, int* k_slices, int* ring, int* row_groups);
 
 /* Decode steps on a pre-allocated KV cache (eetq_rope_decode_attention_f16, eetq_rotary_neox_kvcache_f16) whose new token
- * was NOT written because its cache row lies outside the cache (slot >= rows: the cache is full; or a negative position).
+ * was NOT written because its cache row lies outside the cache (slot >= rows: the cache is full; or a negative position) or,
+ * through the *_bounded entries, because its position lies outside the cos|sin table; tokens that the plain rotary entries
+ * left unrotated for that reason are counted here too.
  * The kernels skip the write instead of faulting (stock transformers raises an index error there); this entry synchronises
  * the current device and reports how many such steps its kernels have dropped since the last reset (batch rows count
  * individually), optionally resetting the count.  A non-zero count means the tokens generated after that point are wrong. */

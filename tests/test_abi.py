@@ -60,6 +60,59 @@ def test_argument_validation_without_gpu(lib):
     assert lib.eetq_rotary_neox_f16(p, p, p, p, 1, 1, 64, 63, None) == -1   # odd rot_dim
 
 
+def test_side_op_refusals_without_gpu(lib):
+    """silu_mul refuses pointers that are not 16-byte aligned; the rotary entries that carry the cos|sin table's row count refuse
+    table_rows <= 0 and keep every argument check of the entries they extend.  EETQ_ERR_INVALID (-1) throughout: a launch would
+    have returned EETQ_ERR_HIP on this GPU-less host."""
+    buf = (ctypes.c_char * 4096)()
+    base = (ctypes.addressof(buf) + 15) & ~15
+    p, off8, null = ctypes.c_void_p(base), ctypes.c_void_p(base + 8), None
+    for fn in (lib.eetq_silu_mul_f16, lib.eetq_silu_mul_glu8_f16):
+        for args in ((off8, p), (p, off8), (off8, off8)):
+            assert fn(*args, 4, 64, None) == -1
+            assert b"aligned" in lib.eetq_last_error()
+        assert fn(null, p, 4, 64, None) == -1 and b"null pointer" in lib.eetq_last_error()
+        assert fn(p, p, 4, 60, None) == -1 and b"multiple of 8" in lib.eetq_last_error()
+    st = (ctypes.c_long * 12)(*([64] * 12))
+    for rows in (0, -1):
+        assert lib.eetq_rotary_neox_bounded(p, p, p, p, rows, 0, 1, 1, 64, 64, None) == -1
+        assert b"at least one row" in lib.eetq_last_error()
+        assert lib.eetq_rotary_neox_strided_bounded_f16(p, p, p, p, rows, 1, 1, 1, 64, 64, 64, 64, None) == -1
+        assert b"at least one row" in lib.eetq_last_error()
+        assert lib.eetq_rotary_neox_kvcache_bounded_f16(p, null, 0, p, p, p, p, rows, p, p, 1, 1, 1, 64, 64, st, 8, None) == -1
+        assert b"at least one row" in lib.eetq_last_error()
+        assert lib.eetq_rotary_neox_kvcache_prefill_bounded_f16(p, p, p, p, p, rows, p, p, 1, 2, null, 0, 1, 1, 64, 64, st, 8,
+                                                                None) == -1
+        assert b"at least one row" in lib.eetq_last_error()
+        assert lib.eetq_rope_decode_attention_bounded_f16(p, null, 0, p, p, p, p, rows, p, p, null, p, p, p, 1, 1, 1, 8, 64, 1,
+                                                          0.125, st, null, 0, null, None) == -1
+        assert b"at least one row" in lib.eetq_last_error()
+    # the old checks, with a valid row count
+    assert lib.eetq_rotary_neox_bounded(p, p, p, p, 16, 0, 1, 1, 64, 63, None) == -1           # odd rot_dim
+    assert b"invalid rotary shape" in lib.eetq_last_error()
+    assert lib.eetq_rotary_neox_bounded(p, p, p, p, 16, 7, 1, 1, 64, 64, None) == -1           # unknown dtype
+    assert lib.eetq_rotary_neox_bounded(p, null, p, p, 16, 0, 1, 1, 64, 64, None) == -1
+    assert b"null pointer" in lib.eetq_last_error()
+    assert lib.eetq_rotary_neox_strided_bounded_f16(p, p, p, p, 16, 1, 2, 1, 64, 64, 64, 64, None) == -1   # q_stride < q_heads * D
+    assert b"token stride" in lib.eetq_last_error()
+    assert lib.eetq_rotary_neox_kvcache_bounded_f16(p, null, 2, p, p, p, p, 16, p, p, 1, 1, 1, 64, 64, st, 8, None) == -1
+    assert b"slot_stride" in lib.eetq_last_error()
+    assert lib.eetq_rotary_neox_kvcache_bounded_f16(p, null, 0, p, p, p, p, 16, p, p, 1, 1, 1, 64, 64, null, 8, None) == -1
+    assert lib.eetq_rotary_neox_kvcache_bounded_f16(p, null, 0, p, p, p, p, 16, p, p, 1, 1, 1, 64, 66, st, 8, None) == -1   # rot > D
+    assert lib.eetq_rotary_neox_kvcache_prefill_bounded_f16(p, p, p, p, p, 16, p, p, 1, 4, null, 6, 1, 1, 64, 64, st, 8,
+                                                            None) == -1                        # rows 6 .. 9 of an 8-row cache
+    assert b"inside the cache" in lib.eetq_last_error()
+    assert lib.eetq_rope_decode_attention_bounded_f16(p, null, 0, p, p, p, p, 16, p, p, null, p, p, null, 1, 1, 1, 8, 64, 1, 0.125,
+                                                      st, null, 0, null, None) == -1           # no tickets
+    assert b"null pointer" in lib.eetq_last_error()
+    assert lib.eetq_rope_decode_attention_bounded_f16(p, null, 0, p, p, p, p, 16, p, p, null, p, p, p, 1, 3, 2, 8, 64, 1, 0.125,
+                                                      st, null, 0, null, None) == -1           # heads % kv_heads
+    assert b"invalid attention shape" in lib.eetq_last_error()
+    # the entries without a row count still refuse what they refused
+    assert lib.eetq_rotary_neox_kvcache_f16(p, null, 2, p, p, p, p, p, p, 1, 1, 1, 64, 64, st, 8, None) == -1
+    assert lib.eetq_rotary_neox_strided_f16(p, p, p, p, 1, 2, 1, 64, 64, 64, 64, None) == -1
+
+
 def test_small_batch_plan_rule_on_a_256_cu_chip(lib):
     """eetq_diag_stream_plan: host arithmetic only (cus given: no device needed).  Pins the rule of streamk.hip::pick_plan /
     pick_plan_i4 as DESIGN.md 4.2 / 4.6 state it, for an MI355X (256 CUs): form 0 registers, 1 block copy, 2 per-wave ring."""
