@@ -72,6 +72,8 @@ def _declare(L):
         "eetq_unpack_i4": [vp, sz, sz, vp, i32, vp],
         "eetq_w4a16_gemm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
         "eetq_w4a16_gemm_ex": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "eetq_w4a16_gemm_tiled": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "eetq_w4a16_gemm_tiled_supported": [i32, i32, i32],
         "eetq_rmsnorm_f16": [vp, vp, vp, f32, i32, i32, vp],
         "eetq_rotary_neox_f16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "eetq_rotary_neox": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -158,6 +160,7 @@ EXPORTED_SYMBOLS = (
     "eetq_w8a16_moe_gemm_tiled", "eetq_diag_moe_host_path",
     "eetq_w4a16_moe_gemm", "eetq_expand_i4_to_i8", "eetq_w8a16_moe_gemm_tiled_supported",
     "eetq_w4a16_moe_gemm_tiled", "eetq_w4a16_moe_gemm_tiled_supported",
+    "eetq_w4a16_gemm_tiled", "eetq_w4a16_gemm_tiled_supported",
     "eetq_moe_router_f16", "eetq_moe_topk_f16", "eetq_moe_router_sigmoid_f16", "eetq_moe_topk_sigmoid_f32",
     "eetq_rotary_neox_bounded", "eetq_rotary_neox_strided_bounded_f16", "eetq_rotary_neox_kvcache_bounded_f16",
     "eetq_rotary_neox_kvcache_prefill_bounded_f16", "eetq_rope_decode_attention_bounded_f16",

@@ -272,6 +272,10 @@ int launch_gemv_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue e
                    hipStream_t stream);
 int launch_w4a16(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                  hipStream_t stream, int path = EETQ_PATH_AUTO);
+// the tiled MFMA kernel on the int4 tiles themselves, no expansion and no scratch (gemm_int4_tiled.hip); tile_j: 0 = the launcher's
+// rule, 1 = 128 x 64, 2 = 128 x 128; EETQ_ERR_UNSUPPORTED without a message outside its shapes
+int launch_gemm_tile_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K, int tile_j,
+                        hipStream_t stream);
 int launch_gemv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                 hipStream_t stream, Prologue pro = Prologue{});
 bool gemv_stages_row(int M, int K);  // some GEMV form stages M rows of K activations in LDS (M * K <= 65536): gemv.hip

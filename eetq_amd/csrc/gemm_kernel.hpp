@@ -31,7 +31,7 @@ constexpr int kMinKSteps    = STAGES - 1;   // the statically unrolled drain nee
 // CW = waves across the tile's columns (each owns 32*J of them); 2*CW waves per workgroup.  CW = 2: the round-1 geometry,
 // one wave per SIMD.  (J, CW) = (1, 4): the 128 x 128 tile on EIGHT waves, two per SIMD -- half the accumulators and half the
 // DMA pieces per wave, and a second wave on every SIMD to issue MFMAs while the first sits in an LDS-DMA issue or a barrier.
-// BITS = 4 (grouped tile on an int4 expert stack, moe_int4_tiled.hip): a K step needs half an int4 tile per column tile, 512 bytes
+// BITS = 4 (tile on int4 weights: moe_int4_tiled.hip grouped, gemm_int4_tiled.hip dense): a K step needs half an int4 tile per column tile, 512 bytes
 template <int J, int CW = 2, int BITS = 8>
 struct TileCfg {
     static constexpr int BN            = 32 * J * CW;
@@ -152,6 +152,8 @@ __device__ __forceinline__ f16x8 make_frag(f16x2 a, f16x2 b, f16x2 c, f16x2 d)
 // separate packed ops (the int8 path's fp16(q) * s, one rounding: the same bits as expansion + the int8 tile).  The dequant fills
 // the int8 schedule's gaps: gap (jj, dword, kind) with kind = extract (three shifts, four and-or) / - 1032 / * scale.
 // K % 128 == 0 makes the K-step count even: only the tail == 6 drain exists.
+// BITS = 4 without GROUPED (gemm_int4_tiled.hip): the same weight side on ONE [K][N / 2] weight -- no row map, x_rsrc
+// spans M rows, w_rsrc the N K / 2 bytes of the launch's columns, and bias / residual take the identity epilogue's run-time branches.
 template <int ABLATE, int J, bool ACT, int CW, bool SPLIT, bool GLU = false, bool GROUPED = false, int BITS = 8>
 __device__ __forceinline__ void gemm_tile_body(
     const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales,
@@ -160,7 +162,8 @@ __device__ __forceinline__ void gemm_tile_body(
 {
     static_assert(!GROUPED || (!SPLIT && !ACT && CW == 2 && ABLATE == 0),
                   "the grouped form exists for the unsplit 4-wave identity tile (plain and GLU)");
-    static_assert(BITS == 8 || (BITS == 4 && GROUPED), "int4 tiles: the grouped, unsplit, four-wave identity tile only");
+    static_assert(BITS == 8 || (BITS == 4 && !SPLIT && !ACT && CW == 2 && ABLATE == 0 && (GROUPED || !GLU)),
+                  "int4 tiles: the unsplit, four-wave identity tile only (grouped: plain and GLU; dense: plain)");
     // N = columns of THIS launch (w, scales, y, ep.* already point at its first column); ldc = row stride of y / residual
     EETQ_GEMM_STAMP(0);
     using Cfg = TileCfg<J, CW, BITS>;

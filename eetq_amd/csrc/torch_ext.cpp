@@ -511,6 +511,60 @@ Tensor w4_a16_gemm_t(const Tensor& input, const Tensor& weight, const Tensor& sc
     return output;
 }
 
+// Extension: the prompt path of a W4A16 projection on the int4 tiles themselves (eetq_w4a16_gemm_tiled): the bits of
+// w8_a16_gemm(path="mfma")'s unsplit tile without the expansion to int8 tiles and its per-stream scratch.  The tensor checks are
+// w8_a16_gemm's for a packed int4 weight, all before any GPU work; fresh output, current stream, asynchronous.  tile: 0 = the
+// launcher's rule, 1 = 128 x 64, 2 = 128 x 128.  A shape outside w4_a16_gemm_tiled_supported raises.
+bool w4_a16_gemm_tiled_supported(int64_t M, int64_t N, int64_t K)
+{
+    if (M < 1 || N < 1 || K < 1 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return false;
+    return eetq_w4a16_gemm_tiled_supported((int)M, (int)N, (int)K) == 1;
+}
+
+Tensor w4_a16_gemm_tiled(const Tensor& input, const Tensor& weight, const Tensor& scale, const OptTensor& bias,
+                         const OptTensor& residual, int64_t tile)
+{
+    TORCH_CHECK(input.scalar_type() == at::kHalf, "w4_a16_gemm_tiled: input must be float16 (got ", input.scalar_type(), ")");
+    TORCH_CHECK(input.is_cuda(), "w4_a16_gemm_tiled: input must be a CUDA tensor");
+    TORCH_CHECK(weight.dim() == 2 && weight.scalar_type() == at::kChar && scale.scalar_type() == at::kHalf,
+                "w4_a16_gemm_tiled: weight must be an int8 [K, N/2] tensor (packed int4) and scale float16");
+    TORCH_CHECK(weight.device() == input.device() && scale.device() == input.device(),
+                "w4_a16_gemm_tiled: input, weight and scale must be on the same device");
+    TORCH_CHECK(weight.is_contiguous() && scale.is_contiguous(), "w4_a16_gemm_tiled: weight and scale must be contiguous");
+    const int64_t k = weight.size(0), n = scale.numel();
+    TORCH_CHECK(weight.size(1) * 2 == n && n > 0,
+                "w4_a16_gemm_tiled: weight must be packed int4 [K, N/2] with N scales (got [", k, ", ", weight.size(1), "] and ", n,
+                " scales)");
+    TORCH_CHECK(input.dim() >= 1 && input.size(-1) == k, "w4_a16_gemm_tiled: weight is [", k, ", ", n, " / 2] but input has K=",
+                input.dim() >= 1 ? input.size(-1) : 0);
+    TORCH_CHECK(tile >= 0 && tile <= 2, "w4_a16_gemm_tiled: tile is 0 (the launcher's rule), 1 (128 x 64) or 2 (128 x 128)");
+    const int64_t m = k ? input.numel() / k : 0;
+    if (bias) {
+        const Tensor& b = *bias;
+        TORCH_CHECK(b.scalar_type() == at::kHalf && b.device() == input.device() && b.numel() == n && b.is_contiguous(),
+                    "w4_a16_gemm_tiled: bias must be a contiguous float16 [N] tensor on the input's device");
+    }
+    if (residual) {
+        const Tensor& r = *residual;
+        TORCH_CHECK(r.scalar_type() == at::kHalf && r.device() == input.device() && r.numel() == m * n && r.is_contiguous() &&
+                        r.size(-1) == n,
+                    "w4_a16_gemm_tiled: residual must be a contiguous float16 [..., N] tensor with the output's element count, on the "
+                    "input's device");
+    }
+    Tensor output = torch::empty(out_shape(input, n), input.options());
+    if (m == 0) return output;
+    TORCH_CHECK(w4_a16_gemm_tiled_supported(m, n, k), "w4_a16_gemm_tiled: unsupported shape M=", m, ", N=", n, ", K=", k,
+                ": needs N % 16 == 0, K % 128 == 0, K >= 384, N * K / 2 < 2^31 and 128 rows of input below 2 GiB (w8_a16_gemm takes "
+                "the others)");
+    Tensor x = input.contiguous();
+    if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+    c10::DeviceGuard guard(input.device());
+    check(eetq_w4a16_gemm_tiled(x.data_ptr(), weight.data_ptr<int8_t>(), scale.data_ptr(), bias ? bias->data_ptr() : nullptr,
+                                residual ? residual->data_ptr() : nullptr, output.data_ptr(), (int)m, (int)n, (int)k, (int)tile,
+                                stream_of(input)));
+    return output;
+}
+
 // ---- side ops ---------------------------------------------------------------------------------------------------------
 // reference: layernorm_forward_cuda, layernorm.cu:98-113 (returns void; current stream here, default stream there)
 void layernorm_forward(const Tensor& input, const Tensor& gamma, Tensor& out, double eps)
@@ -1597,6 +1651,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("input"), py::arg("weight"), py::arg("scale"));
     m.def("w4_a16_gemm_t", &w4_a16_gemm_t, "the same from a packed int4 [K, N/2] weight in the gfx950 int4 layout",
           py::arg("input"), py::arg("weight"), py::arg("scale"));
+    m.def("w4_a16_gemm_tiled", &w4_a16_gemm_tiled, "W4A16 prompt gemm on the int4 tiles themselves: no expansion, no scratch",
+          py::arg("input"), py::arg("weight"), py::arg("scale"), py::arg("bias") = py::none(), py::arg("residual") = py::none(),
+          py::arg("tile") = 0);
+    m.def("w4_a16_gemm_tiled_supported", &w4_a16_gemm_tiled_supported, "1 where w4_a16_gemm_tiled takes an [M, K] x [K, N] product",
+          py::arg("M"), py::arg("N"), py::arg("K"));
     m.def("unprocess_weights", &unprocess_weights, "inverse of preprocess_weights", py::arg("processed_weight"),
           py::arg("layout") = "gfx950", py::arg("is_int4") = false);
     m.def("rotary_embedding_neox_strided", &rotary_embedding_neox_strided, "rotary embedding on strided q/k views",

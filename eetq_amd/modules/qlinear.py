@@ -17,7 +17,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from ..ops import (moe_router, moe_router_sigmoid, preprocess_weights, quant_weights, w4_a16_moe, w4_a16_moe_block,
-                   w4_a16_gemm_t, w4_a16_moe_direct_supported,
+                   w4_a16_gemm_t, w4_a16_gemm_tiled, w4_a16_gemm_tiled_supported, w4_a16_moe_direct_supported,
                    w4_a16_moe_backward, w4_a16_moe_block_sigmoid, w4_a16_moe_train, w8_a16_gemm, w8_a16_gemm_t, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_block,
                    w8_a16_moe_block_sigmoid, w8_a16_moe_train)
 from ..checkpoint import install_layout_hooks
@@ -107,9 +107,19 @@ class W4A16Linear(nn.Module):
     ``weight_scales`` [out].  Needs in_features % 128 == 0 and out_features % 16 == 0.  Inference-only unless ``trainable`` is
     set (``eet_quantize(..., bits=4, trainable=True)`` or ``utils.set_trainable``): then a call in grad mode whose input requires
     grad and that passes no ``residual`` runs through :class:`W4A16LinearMMFunction` -- the same output bits, and an input
-    gradient from ``w4_a16_gemm_t`` (the int4 weight stays frozen)."""
+    gradient from ``w4_a16_gemm_t`` (the int4 weight stays frozen).
+
+    ``prompt_path`` (a plain attribute, not a buffer: state dicts do not change; ``utils.set_prompt_path`` sets it on a model) chooses
+    what serves calls with more than 128 rows: ``"auto"``, the default, is ``w8_a16_gemm``'s rule (the nibbles are expanded to int8
+    tiles in a per-stream scratch buffer, then the W8A16 kernels run); ``"direct"`` sends such a call, where
+    ``ops.w4_a16_gemm_tiled_supported`` takes its shape, to the tiled kernel on the int4 tiles themselves (``ops.w4_a16_gemm_tiled``,
+    DESIGN.md 4.8) -- no expansion, no scratch, capturable cold -- and leaves every other call as it is."""
 
     trainable = False   # a plain attribute, not a buffer: state dicts do not change
+
+    prompt_path = "auto"
+    PROMPT_PATHS = ("auto", "direct")
+    DIRECT_MIN_ROWS = 129   # up to 128 rows AUTO already reads the int4 tiles (GEMV, stream kernel, split-K tile)
 
     def __init__(self, in_features, out_features, bias=True, dev="cuda:0"):
         super().__init__()
@@ -137,10 +147,23 @@ class W4A16Linear(nn.Module):
         mod.weight_scales = scales.half().to(dev)
         return mod
 
+    def route(self, rows):
+        """``"direct"`` when a call with ``rows`` flattened input rows runs ``ops.w4_a16_gemm_tiled``, else ``"auto"`` (shapes and
+        ``prompt_path`` only; no GPU work)."""
+        if self.prompt_path == "auto":
+            return "auto"
+        if self.prompt_path != "direct":
+            raise ValueError("W4A16Linear.prompt_path must be one of %r (got %r)" % (self.PROMPT_PATHS, self.prompt_path))
+        direct = rows >= self.DIRECT_MIN_ROWS and w4_a16_gemm_tiled_supported(rows, self.out_features, self.in_features)
+        return "direct" if direct else "auto"
+
     def forward(self, input, residual=None):
+        direct = self.route(input.numel() // self.in_features if self.in_features else 0) == "direct"
         if self.trainable and torch.is_grad_enabled() and input.requires_grad and residual is None:
-            return W4A16LinearMMFunction.apply(input, self.qweight, self.weight_scales, self.bias)
+            return W4A16LinearMMFunction.apply(input, self.qweight, self.weight_scales, self.bias, direct)
         with torch.no_grad():
+            if direct:
+                return w4_a16_gemm_tiled(input, self.qweight, self.weight_scales, bias=self.bias, residual=residual)
             return w8_a16_gemm(input, self.qweight, self.weight_scales, bias=self.bias, residual=residual)
 
     def extra_repr(self):
@@ -603,12 +626,16 @@ def input_grad_i4(grad_output, weight, scales, x_shape, x_dtype=torch.float16):
 
 class W4A16LinearMMFunction(Function):
     """:class:`EetqLinearMMFunction` over a packed int4 weight: forward = the fused int4 dequant GEMM (the bits of the module's
-    inference call); backward returns grad_input only, computed by :func:`input_grad_i4`.  ``x`` is not saved."""
+    inference call); backward returns grad_input only, computed by :func:`input_grad_i4`.  ``x`` is not saved.  ``direct``: the
+    forward runs ``w4_a16_gemm_tiled`` (the module's ``prompt_path = "direct"`` route), as its inference call does."""
 
     @staticmethod
-    def forward(ctx, x, weight, scales, bias=None):
+    def forward(ctx, x, weight, scales, bias=None, *direct):
         ctx.save_for_backward(weight, scales)
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.n_args = 4 + len(direct)   # the four-argument call of before keeps working
+        if direct and direct[0]:
+            return w4_a16_gemm_tiled(x, weight, scales, bias=bias)
         return w8_a16_gemm(x, weight, scales, bias=bias)
 
     @staticmethod
@@ -617,7 +644,7 @@ class W4A16LinearMMFunction(Function):
         grad_input = None
         if ctx.needs_input_grad[0]:
             grad_input = input_grad_i4(grad_output, weight, scales, ctx.x_shape, ctx.x_dtype)
-        return grad_input, None, None, None
+        return (grad_input,) + (None,) * (ctx.n_args - 1)
 
 
 class W8A16MoeFunction(Function):

@@ -34,6 +34,8 @@ if _C is not None:
     w8_a16_gemm_ = _C.w8_a16_gemm_
     w8_a16_gemm_t = _C.w8_a16_gemm_t
     w4_a16_gemm_t = _C.w4_a16_gemm_t
+    w4_a16_gemm_tiled = _C.w4_a16_gemm_tiled
+    w4_a16_gemm_tiled_supported = _C.w4_a16_gemm_tiled_supported
     layernorm_forward = _C.layernorm_forward
     rotary_embedding_neox = _C.rotary_embedding_neox
     rotary_embedding_neox_strided = _C.rotary_embedding_neox_strided
@@ -68,14 +70,14 @@ else:
                              rope_decode_attention, rotary_embedding_neox, rotary_embedding_neox_kvcache,
                              rotary_embedding_neox_kvcache_prefill, rotary_embedding_neox_strided, silu_mul,
                              unprocess_weights, w4_a16_moe, w4_a16_moe_path, w4_a16_moe_direct_supported, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t,
-                             w4_a16_gemm_t, w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, w4_a16_moe_backward, w4_a16_moe_train, moe_router,
+                             w4_a16_gemm_t, w4_a16_gemm_tiled, w4_a16_gemm_tiled_supported, w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, w4_a16_moe_backward, w4_a16_moe_train, moe_router,
                              w8_a16_moe_block, w4_a16_moe_block, moe_router_sigmoid, w8_a16_moe_block_sigmoid,
                              w4_a16_moe_block_sigmoid, sample_handover)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
 
-__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "layernorm_forward",
+__all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
            "greedy_handover", "sample_handover", "sampling_params", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid",

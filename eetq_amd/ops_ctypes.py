@@ -25,6 +25,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
                    LAYOUT_SM80, PATH_AUTO, PATH_GEMV, PATH_MFMA, check)
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
+           "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported",
            "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
@@ -263,6 +264,63 @@ def w4_a16_gemm_t(input, weight, scale):
         x = x.clone()
     with torch.cuda.device(input.device):
         check(_lib.lib().eetq_w4a16_gemm_t(_ptr(x), _ptr(weight), _ptr(scale), _ptr(output), m, n, k, _stream_ptr()))
+    return output
+
+
+def w4_a16_gemm_tiled_supported(M, N, K):
+    """Where :func:`w4_a16_gemm_tiled` runs: ``eetq_w4a16_gemm_tiled_supported`` (host arithmetic on the shapes alone)."""
+    if M < 1 or N < 1 or K < 1 or M >= 1 << 31 or N >= 1 << 31 or K >= 1 << 31:
+        return False
+    return _lib.lib().eetq_w4a16_gemm_tiled_supported(int(M), int(N), int(K)) == 1
+
+
+@_eager_only
+def w4_a16_gemm_tiled(input, weight, scale, bias=None, residual=None, tile=0):
+    """``y = input @ dequant(weight, scale) (+ bias) (+ residual)`` for a packed int4 ``[K, N/2]`` weight in the gfx950 int4 layout, on
+    the LDS-tiled MFMA kernel reading the int4 tiles directly (eetq_w4a16_gemm_tiled): the bits of
+    ``w8_a16_gemm(path="mfma")``'s unsplit tile without the expansion to int8 tiles and its per-stream scratch, so it captures into a
+    graph cold.  ``tile``: 0 = the launcher's rule, 1 = 128 x 64, 2 = 128 x 128.  Current stream, asynchronous.  A shape outside
+    :func:`w4_a16_gemm_tiled_supported` raises RuntimeError."""
+    if input.dtype != torch.float16:
+        raise RuntimeError("w4_a16_gemm_tiled: input must be float16 (got %s)" % input.dtype)
+    if not input.is_cuda:
+        raise RuntimeError("w4_a16_gemm_tiled: input must be a CUDA tensor")
+    if weight.dim() != 2 or weight.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise RuntimeError("w4_a16_gemm_tiled: weight must be an int8 [K, N/2] tensor (packed int4) and scale float16")
+    if weight.device != input.device or scale.device != input.device:
+        raise RuntimeError("w4_a16_gemm_tiled: input, weight and scale must be on the same device")
+    if not weight.is_contiguous() or not scale.is_contiguous():
+        raise RuntimeError("w4_a16_gemm_tiled: weight and scale must be contiguous")
+    k, n = weight.shape[0], scale.numel()
+    if weight.shape[1] * 2 != n or n == 0:
+        raise RuntimeError("w4_a16_gemm_tiled: weight must be packed int4 [K, N/2] with N scales (got [%d, %d] and %d scales)"
+                           % (k, weight.shape[1], n))
+    if input.dim() < 1 or input.shape[-1] != k:
+        raise RuntimeError("w4_a16_gemm_tiled: weight is [%d, %d / 2] but input has K=%d" % (k, n, input.shape[-1] if input.dim() else 0))
+    if tile not in (0, 1, 2):
+        raise RuntimeError("w4_a16_gemm_tiled: tile is 0 (the launcher's rule), 1 (128 x 64) or 2 (128 x 128)")
+    m = input.numel() // k if k else 0
+    if bias is not None:
+        if bias.dtype != torch.float16 or bias.device != input.device or bias.numel() != n or not bias.is_contiguous():
+            raise RuntimeError("w4_a16_gemm_tiled: bias must be a contiguous float16 [N] tensor on the input's device")
+    if residual is not None:
+        if (residual.dtype != torch.float16 or residual.device != input.device or residual.numel() != m * n
+                or not residual.is_contiguous() or residual.shape[-1] != n):
+            raise RuntimeError("w4_a16_gemm_tiled: residual must be a contiguous float16 [..., N] tensor with the output's element "
+                               "count, on the input's device")
+    output = torch.empty(tuple(input.shape[:-1]) + (n,), dtype=input.dtype, device=input.device)
+    if m == 0:
+        return output
+    if not w4_a16_gemm_tiled_supported(m, n, k):
+        raise RuntimeError("w4_a16_gemm_tiled: unsupported shape M=%d, N=%d, K=%d: needs N %% 16 == 0, K %% 128 == 0, K >= 384, "
+                           "N * K / 2 < 2^31 and 128 rows of input below 2 GiB (w8_a16_gemm takes the others)" % (m, n, k))
+    x = input.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    with torch.cuda.device(input.device):
+        check(_lib.lib().eetq_w4a16_gemm_tiled(_ptr(x), _ptr(weight), _ptr(scale), _ptr(bias) if bias is not None else None,
+                                               _ptr(residual) if residual is not None else None, _ptr(output), m, n, k, int(tile),
+                                               _stream_ptr()))
     return output
 
 

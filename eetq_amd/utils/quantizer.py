@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from ..modules.qlinear import EetqSparseMoeBlock, EetqTopKRouter, W4A16Experts, W4A16Linear, W8A16Experts, W8A16Linear
 
-__all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable"]
+__all__ = ["eet_quantize", "find_layers", "set_op_by_name", "get_named_linears", "set_trainable", "set_prompt_path"]
 
 
 def find_layers(module, include=(nn.Linear,), exclude=("lm_head",)):
@@ -95,6 +95,22 @@ def set_trainable(model, flag=True, int4_experts=False):
     for m in model.modules():
         if isinstance(m, classes):
             m.trainable = bool(flag)
+            n += 1
+    return n
+
+
+def set_prompt_path(model, path):
+    """Set ``prompt_path`` of every :class:`W4A16Linear` in ``model`` (itself included) and return how many modules it set:
+    ``"direct"`` sends calls with more than 128 rows to the tiled kernel on the int4 tiles themselves where it takes the shape (no
+    expansion to int8 tiles, no per-stream scratch, capturable into a graph cold), ``"auto"``, the default, leaves them on the
+    expansion route (:class:`W4A16Linear`).  Any other value raises ValueError before a module is touched.  Int4
+    experts have an attribute of their own (``eet_quantize(..., expert_prompt_path=...)``)."""
+    if path not in W4A16Linear.PROMPT_PATHS:
+        raise ValueError("set_prompt_path: path must be one of %r (got %r)" % (W4A16Linear.PROMPT_PATHS, path))
+    n = 0
+    for m in model.modules():
+        if isinstance(m, W4A16Linear):
+            m.prompt_path = path
             n += 1
     return n
 

@@ -177,9 +177,24 @@ int eetq_w4a16_gemm(const void* x, const int8_t* w_packed, const void* scales, c
 /* As above with an explicit kernel path: EETQ_PATH_AUTO (M = 1: dot2 GEMV on int4 tiles; 2..16: register-streaming MFMA
  * kernel; 17..128: split-K MFMA tile on int4 tiles; above: nibbles expanded to int8 tiles + the W8A16 kernels),
  * EETQ_PATH_GEMV (M <= 4), EETQ_PATH_STREAM (M <= 16), EETQ_PATH_SPLITK (M <= 128; honours EETQ_AMD_SPLITK_PLAN),
- * EETQ_PATH_MFMA (the expansion route at any M).  Other paths: EETQ_ERR_UNSUPPORTED. */
+ * EETQ_PATH_MFMA (the expansion route at any M).  Other paths: EETQ_ERR_UNSUPPORTED.  The tiled kernel on the int4 tiles
+ * themselves -- prompts without the expansion and its scratch -- is not a path of this entry: eetq_w4a16_gemm_tiled below. */
 int eetq_w4a16_gemm_ex(const void* x, const int8_t* w_packed, const void* scales, const void* bias, const void* residual,
                        void* y, int M, int N, int K, int path, void* stream);
+/* eetq_w4a16_gemm_tiled: the same product from the LDS-tiled MFMA kernel reading the int4 tiles directly: no
+ * expansion to int8 tiles, no library-owned scratch, no allocation and no synchronisation, so any shape it takes can be captured
+ * into a HIP graph cold.  A row comes out bit for bit as EETQ_PATH_MFMA's unsplit int8 tile makes it, at either tile shape.
+ *   tile_j: 0 = the launcher's rule (128 x 128 or 128 x 64 tiles by the int8 launcher's cost rule; whole rounds of wide tiles and
+ *   the ragged last round in a second launch), 1 = 128 x 64, 2 = 128 x 128 (one launch per row chunk).
+ *   Argument errors (null x / w / scales / y, M, N or K < 1, K % 128, N % 16, x / w / y not 16-byte aligned, bias not 8-byte or
+ *   residual not 16-byte aligned, tile_j outside 0..2): EETQ_ERR_INVALID, nothing launched.  A valid shape outside
+ *   eetq_w4a16_gemm_tiled_supported returns EETQ_ERR_UNSUPPORTED without a message: the caller runs eetq_w4a16_gemm. */
+int eetq_w4a16_gemm_tiled(const void* x, const int8_t* w_packed_i4, const void* scales, const void* bias, const void* residual,
+                          void* y, int M, int N, int K, int tile_j, void* stream);
+/* eetq_w4a16_gemm_tiled_supported: 1 where eetq_w4a16_gemm_tiled takes these sizes, else 0: M >= 1, N % 16 == 0, K % 128 == 0,
+ * K >= 384 (six K steps: the only drain the int4 tile has), N K / 2 < 2^31 and 128 rows of x below 2 GiB.  M is unbounded: rows
+ * go in chunks below 2 GiB.  Host arithmetic on the shapes alone: no device needed. */
+int eetq_w4a16_gemm_tiled_supported(int M, int N, int K);
 
 /* ---- side ops --------------------------------------------------------------------------------------
  * Replaces EETQ.layernorm_forward -> layernorm_forward_cuda (csrc/layernorm_kernels/layernorm.cu:98-113):
