@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gemm_tile_plan.hpp"
 #include "gemv_kernel.hpp"
 #include "moe_route_tables.hpp"
 
@@ -185,6 +186,31 @@ int eetq_diag_stream_plan(int bits, int M, int N, int K, int cus, int* form, int
     return EETQ_OK;
 }
 
+int eetq_diag_tile_plan(int bits, int M, int N, int K, int act, int tile_j, int cus, int* records, int max_records, int* count)
+{
+    EETQ_REQUIRE(records && count && max_records >= 0, "eetq_diag_tile_plan: null output pointer");
+    EETQ_REQUIRE(bits == 8 || bits == 4, "eetq_diag_tile_plan: bits must be 8 or 4");
+    // what launch_gemm_mfma (no forced shape) and launch_gemm_tile_i4 (no activation) take, by the predicates they use
+    const bool tiled = tile_plan::deep_enough(bits, K);
+    if (M < 1 || N < kTileN || N % kTileN != 0 || K < 1 || tile_j < 0 || tile_j > 2 ||
+        (bits == 8 ? tile_j != 0 : act != 0 || !tiled) || (tiled && (!tile_plan::weight_fits(bits, N, K) || tile_plan::max_rows(K) < tile_plan::kRows)))
+        return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] eetq_diag_tile_plan: a shape, activation or tile_j the tiled launcher of these bits refuses");
+    *count          = 0;
+    const auto note = [&](int row0, int rows, int col0, int cols, int tile, int k_slices) {
+        if (*count < max_records) {
+            const int r[6] = {row0, rows, col0, cols, tile, k_slices};
+            for (int i = 0; i < 6; ++i) records[6 * *count + i] = r[i];
+        }
+        ++*count;
+        return 0;
+    };
+    if (!tiled) return tile_plan::for_each_row_chunk(M, kStreamMaxM, [&](int m, int rows) { return note(m, rows, 0, N, 0, 1); });
+    const int n_cu = tile_j != 0 ? 1 : cus > 0 ? cus : device_cu_count();
+    return tile_plan::for_each_launch(M, N, K, n_cu, tile_j, bits == 8 && act == 0, [&](int m, int rows, const tile_plan::Segment& s) {
+        return note(m, rows, s.c0, s.cols, s.narrow ? 1 : 2, s.k_slices);
+    });
+}
+
 int eetq_device_supported(void)
 {
     int dev = 0;
@@ -332,10 +358,7 @@ static AutoChoice auto_path_i8(int M, int N, int K, int act)
     // LDS ring or a per-workgroup copy: streamk.hip::pick_plan) on every shape (us stream / split-K at M = 16: 4096 x 11008
     // 12.60 / 12.74, 11008 x 4096 12.48 / 13.15, 8192^2 13.9 / 18.5, 28672 x 8192 41.8 / 46.9; the other way only 5120 x 27648
     // from M = 13, 29.9 / 29.0)
-    static const bool use_splitk = [] {  // EETQ_AMD_SPLITK=0 keeps the unsplit kernels (the split forms own per-stream scratch)
-        const char* e = getenv("EETQ_AMD_SPLITK");
-        return !(e && e[0] == '0');
-    }();
+    const bool use_splitk = splitk_allowed();  // EETQ_AMD_SPLITK=0 keeps the unsplit kernels (the split forms own per-stream scratch)
     if (M <= 16) {
         // ... except a narrow, deep weight from M = 9 (a GQA k / v projection: Llama-3-70B 8192 x 1024): the stream kernel has one
         // workgroup per 16 columns -- N <= 2048 leaves at least half the CUs without one -- and walks all of K in each, while the

@@ -272,8 +272,9 @@ int launch_gemv_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue e
                    hipStream_t stream);
 int launch_w4a16(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                  hipStream_t stream, int path = EETQ_PATH_AUTO);
-// the tiled MFMA kernel on the int4 tiles themselves, no expansion and no scratch (gemm_int4_tiled.hip); tile_j: 0 = the launcher's
-// rule, 1 = 128 x 64, 2 = 128 x 128; EETQ_ERR_UNSUPPORTED without a message outside its shapes
+// the tiled MFMA kernel on the int4 tiles themselves, no expansion and no scratch (gemm_int4_tiled.hip); tile_j: 0 = the plan of
+// gemm_tile_plan.hpp (launch_gemm_mfma's, without K slices), 1 = 128 x 64, 2 = 128 x 128; EETQ_ERR_UNSUPPORTED without a message
+// outside its shapes
 int launch_gemm_tile_i4(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K, int tile_j,
                         hipStream_t stream);
 int launch_gemv(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
@@ -284,6 +285,8 @@ struct GroupedArgs;
 }
 bool gemv_grouped_supports(int K);
 int  launch_gemv_grouped(const gemv::GroupedArgs& g, int K, int rows, hipStream_t stream);
+// the LDS-tiled MFMA kernel (gemm.hip) by the plan of gemm_tile_plan.hpp (eetq_diag_tile_plan shows it); K < 320: the stream kernel
+// over 64-row chunks
 int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int M, int N, int K,
                      hipStream_t stream);
 // input gradient dx[M][K] = dy[M][N] . fp16(q s)^T of the int8 weight in its native [K][N] layout (gemm_t.hip)
@@ -300,7 +303,9 @@ int launch_moe_gemm_t_i4(const f16* dy, const uint8_t* w, const f16* scales, con
 // experts.  EETQ_ERR_UNSUPPORTED (no message) outside the tile body's limits (moe_gemm_tiled_supports): the caller runs the
 // decode kernel (moe_gemm_kernel.hpp)
 bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather);
-bool moe_tiled_narrow(int S, int E, int N);  // the launcher's tile rule: true = the 128 x 64 tile (shared with moe_int4_tiled.hip)
+// the grouped launchers' tile rule (gemm_tile_launch.hpp::launch_grouped_tiles): true = the 128 x 64 tile, by the dense cost rule
+// on the estimated row tiles (gemm_tile_plan.hpp)
+bool moe_tiled_narrow(int S, int E, int N);
 int  launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, const int* offsets, const int* sorted_slot,
                            const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream);
 int launch_rmsnorm(const f16* x, const f16* gamma, f16* out, float eps, int rows, int cols, hipStream_t stream);
@@ -365,6 +370,8 @@ void splitk_plan(int M, int N, int K, int* nb, int* s, int* stages, int* r = nul
 // true (and *r = row groups) when the row-group plan of the split-K tile applies: 97 <= M <= 1024, its workgroups fit the chip at
 // once and the tiled kernel would not K-slice the shape (gemm_splitk.hip)
 bool splitk_rows_plan(int M, int N, int K, int* r = nullptr);
+// false under EETQ_AMD_SPLITK=0 (read once per process, gemm.hip): no kernel form that needs library-owned scratch is chosen
+bool splitk_allowed();
 // the calling stream's own split-K scratch region (gemm_splitk.hip): slabs (*slab_bytes of them), one ticket array per slice
 // count (2 and 4), *max_tiles tickets each.  EETQ_ERR_UNSUPPORTED (no message) when the stream cannot have one right now.
 int splitk_region(hipStream_t stream, float** slabs, size_t* slab_bytes, unsigned** tickets2, unsigned** tickets4, size_t* max_tiles);

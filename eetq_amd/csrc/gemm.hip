@@ -21,43 +21,56 @@
 //     shadow of the current step's MFMAs (sched_barrier-pinned issue order, see gemm_kernel.hpp);
 //   * blockIdx -> tile mapping gives each XCD (own L2) a contiguous run of tiles ordered in groups of 4 row tiles: the
 //     32 workgroups resident on an XCD cover 4 row tiles x 8 column tiles, the smallest fabric footprint per K step.
+//
+// Host side: launch_gemm_mfma walks the launch plan of gemm_tile_plan.hpp -- row chunks below 2 GiB, the wide or the narrow tile by
+// the cost rule, whole rounds of wide tiles and the ragged last round -- through gemm_tile_launch.hpp, which applies every pointer
+// and epilogue offset; this file supplies the int8 limits, the kernel tables and the K-sliced launch of a ragged round.  The plan
+// is shared with gemm_int4_tiled.hip and, for the tile rule, with the grouped forms; eetq_diag_tile_plan (abi.hip) shows it.
 #include <cstdio>
 #include <cstdlib>
 
-#include "gemm_kernel.hpp"
+#include "gemm_tile_launch.hpp"
 
 namespace eetq {
 
 using namespace gemm;
 
-namespace {
-// S (2 or 4) K slices of the 128 x 64 tile over the columns [c0, c0 + cols) of an M x N problem whose row stride is ldc.
-// EETQ_ERR_UNSUPPORTED (no message): the caller runs those columns unsplit.
-int launch_tile_splitk_cols(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, f16* y, int rows, int c0, int cols,
-                            int K, int ldc, int S, hipStream_t stream)
+bool splitk_allowed()
 {
     static const bool allowed = [] {  // EETQ_AMD_SPLITK=0: no library-owned scratch anywhere (gemm_splitk.hip)
         const char* e = getenv("EETQ_AMD_SPLITK");
         return !(e && e[0] == '0');
     }();
-    constexpr int BN = TileCfg<1>::BN;
-    const int     KT = K / BK;
-    if (!allowed || (S != 2 && S != 4) || ep.act != 0 || K % BK != 0 || KT / S < kMinKSteps) return EETQ_ERR_UNSUPPORTED;
-    const int tiles = ((rows + BM - 1) / BM) * ((cols + BN - 1) / BN);
-    float*    slabs = nullptr;
+    return allowed;
+}
+
+namespace {
+// The calling stream's split-K region for `tiles` tiles of width bn in S (2 or 4) slices: its slabs and the ticket array of S.
+// EETQ_ERR_UNSUPPORTED (no message): the stream has no scratch of its own right now, or not enough of it.
+int tile_splitk_region(hipStream_t stream, int tiles, int bn, int S, float** slabs, unsigned** tickets)
+{
     unsigned *t2 = nullptr, *t4 = nullptr;
     size_t    slab_bytes = 0, max_tiles = 0;
-    int st = splitk_region(stream, &slabs, &slab_bytes, &t2, &t4, &max_tiles);
-    if (st == EETQ_ERR_UNSUPPORTED || (st == EETQ_OK && ((size_t)tiles > max_tiles || (size_t)tiles * S * BM * BN * 4 > slab_bytes)))
-        return EETQ_ERR_UNSUPPORTED;  // no scratch of its own for this stream right now
+    const int st = splitk_region(stream, slabs, &slab_bytes, &t2, &t4, &max_tiles);
     if (st != EETQ_OK) return st;
-    Epilogue e = ep;
-    if (e.bias) e.bias += c0;
-    if (e.residual) e.residual += c0;
-    const uint8_t* wc = w + (size_t)(c0 / kTileN) * (K / kTileK) * kTileBytes;
+    if ((size_t)tiles > max_tiles || (size_t)tiles * S * BM * bn * 4 > slab_bytes) return EETQ_ERR_UNSUPPORTED;
+    *tickets = S == 2 ? t2 : t4;
+    return EETQ_OK;
+}
+
+// S (2 or 4) K slices of the 128 x 64 tile over one column segment of the plan (operands already moved to it).
+// EETQ_ERR_UNSUPPORTED (no message): the caller runs those columns unsplit.
+int launch_tile_splitk_cols(const TileLaunch& t, int K, int S, hipStream_t stream)
+{
+    if (!splitk_allowed() || (S != 2 && S != 4) || t.ep.act != 0 || K % BK != 0 || (K / BK) / S < kMinKSteps) return EETQ_ERR_UNSUPPORTED;
+    const int tiles = tile_plan::row_tiles(t.rows) * tile_plan::ceil_div(t.seg.cols, TileCfg<1>::BN);  // narrow, whatever shape the fall-back has
+    float*    slabs   = nullptr;
+    unsigned* tickets = nullptr;
+    const int st      = tile_splitk_region(stream, tiles, TileCfg<1>::BN, S, &slabs, &tickets);
+    if (st != EETQ_OK) return st;
     static LargeLdsKernel<decltype(&gemm_tile_splitk_kernel<1>)> kernel{gemm_tile_splitk_kernel<1>};
-    return launch_large_lds(kernel, "gemm_tile_splitk_kernel launch", dim3(tiles * S), dim3(256), TileCfg<1>::SMEM_BYTES, stream, x, wc,
-                            scales + c0, y + c0, rows, cols, K, ldc, e, S, slabs, S == 2 ? t2 : t4);
+    return launch_large_lds(kernel, "gemm_tile_splitk_kernel launch", dim3(tiles * S), dim3(256), TileCfg<1>::SMEM_BYTES, stream, t.x, t.w,
+                            t.scales, t.y, t.rows, t.seg.cols, K, t.ldc, t.ep, S, slabs, tickets);
 }
 }  // namespace
 
@@ -66,84 +79,31 @@ int launch_gemm_mfma(const f16* x, const uint8_t* w, const f16* scales, Epilogue
 {
     // kActGlu8: the weight's columns are gate / up groups of 8 + 8 and y is [M][N / 2] (gemm_kernel.hpp, GLU); no residual
     const bool glu = ep.act == kActGlu8;
-    if (glu && (K / BK < kMinKSteps || N % 16 != 0 || ep.residual)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs two launches
-    if (K / BK < kMinKSteps) {
+    if (glu && (!tile_plan::deep_enough(8, K) || N % 16 != 0 || ep.residual)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs two launches
+    if (!tile_plan::deep_enough(8, K))
         // K < 320: a few KiB of weights per column tile; run the stream kernel over 64-row chunks instead of carrying a
         // second tiled kernel for it (the weights are re-read from L2, the activations are read once)
-        for (int m = 0; m < M; m += kStreamMaxM) {
-            const int rows = M - m < kStreamMaxM ? M - m : kStreamMaxM;
-            Epilogue  e    = ep;
+        return tile_plan::for_each_row_chunk(M, kStreamMaxM, [&](int m, int rows) {
+            Epilogue e = ep;
             if (e.residual) e.residual += (size_t)m * N;
-            int       st   = launch_streamk(x + (size_t)m * K, w, scales, e, y + (size_t)m * N, rows, N, K, stream);
-            if (st != EETQ_OK) return st;
-        }
-        return EETQ_OK;
-    }
-    // the LDS-DMA path addresses its operands with 32-bit buffer offsets
-    EETQ_REQUIRE((size_t)N * K < (1ull << 31), "weight larger than 2 GiB is not supported by the buffer-addressed DMA path");
-    // activations: split M into row chunks below 2 GiB (a multiple of the 128-row tile), one launch per chunk
-    const size_t row_bytes  = (size_t)K * 2;
-    const int    max_rows   = (int)((((1ull << 31) - 1) / row_bytes) / BM * BM);
-    EETQ_REQUIRE(max_rows >= BM, "K too large for the buffer-addressed DMA path");
-    const int n_cu = device_cu_count();
-    // one launch over columns [c0, c0 + cols) of the problem with the cheaper of the two tile shapes
-    auto launch_cols = [&](int m, int rows, int c0, int cols, int force_j) -> int {
-        const int tiles_m = (rows + BM - 1) / BM;
-        const int tiles2  = tiles_m * ((cols + TileCfg<2>::BN - 1) / TileCfg<2>::BN);
-        const int tiles1  = tiles_m * ((cols + TileCfg<1>::BN - 1) / TileCfg<1>::BN);
-        // 128 x 128 tiles are the efficient shape when they fill the chip; 128 x 64 tiles double the workgroup count:
-        // they win when the wide tiles leave CUs idle (tiles < CUs) or end in a mostly empty round.  Cost in units of one
-        // wide-tile pass; a narrow tile costs kNarrow of it (measured, profiles/r01_kbench_tile_shapes.txt).
-        constexpr double kNarrow = 0.70;
-        const double cost2 = (double)((tiles2 + n_cu - 1) / n_cu);
-        const double cost1 = kNarrow * (double)((tiles1 + n_cu - 1) / n_cu);
-        Epilogue     e     = ep;
-        if (e.bias) e.bias += c0;
-        if (e.residual) e.residual += (size_t)m * N + c0;
-        const uint8_t* wc = w + (size_t)(c0 / kTileN) * (K / kTileK) * kTileBytes;
-        const bool     narrow = force_j == 1 || (force_j == 0 && cost1 < cost2);
+            return launch_streamk(x + (size_t)m * K, w, scales, e, y + (size_t)m * N, rows, N, K, stream);
+        });
+    // the LDS-DMA path addresses its operands with 32-bit buffer offsets; the activations go in row chunks below 2 GiB
+    EETQ_REQUIRE(tile_plan::weight_fits(8, N, K), "weight larger than 2 GiB is not supported by the buffer-addressed DMA path");
+    EETQ_REQUIRE(tile_plan::max_rows(K) >= BM, "K too large for the buffer-addressed DMA path");
+    // the plan's launches (gemm_tile_plan.hpp); K slices of the ragged round under the identity epilogue only
+    return for_each_tile_launch(8, x, w, scales, ep, y, M, N, K, device_cu_count(), 0, ep.act == 0, [&](const TileLaunch& t) {
+        const int st = t.seg.k_slices > 1 ? launch_tile_splitk_cols(t, K, t.seg.k_slices, stream) : EETQ_ERR_UNSUPPORTED;
+        if (st != EETQ_ERR_UNSUPPORTED) return st;
         // [narrow][identity / activation epilogue / GLU write-out], each its own instantiation (gemm_kernel.hpp).  > 64 KiB of
         // dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
         static LargeLdsKernel<decltype(&gemm_tile_kernel<0, 2>)> kernels[2][3] = {
             {{gemm_tile_kernel<0, 2>}, {gemm_tile_kernel<0, 2, true>}, {gemm_tile_kernel<0, 2, false, 2, true>}},
             {{gemm_tile_kernel<0, 1>}, {gemm_tile_kernel<0, 1, true>}, {gemm_tile_kernel<0, 1, false, 2, true>}}};
-        const int ldc = glu ? N / 2 : N;
-        return launch_large_lds(kernels[narrow][glu ? 2 : e.act != 0], "gemm_tile_kernel launch", dim3(narrow ? tiles1 : tiles2), dim3(256),
-                                narrow ? TileCfg<1>::SMEM_BYTES : TileCfg<2>::SMEM_BYTES, stream, x + (size_t)m * K, wc, scales + c0,
-                                y + (size_t)m * ldc + (glu ? c0 / 2 : c0), rows, cols, K, ldc, e);
-    };
-    for (int m = 0; m < M; m += max_rows) {
-        const int rows    = M - m < max_rows ? M - m : max_rows;
-        const int tiles_m = (rows + BM - 1) / BM;
-        const int tn2     = (N + TileCfg<2>::BN - 1) / TileCfg<2>::BN;
-        const int T2      = tiles_m * tn2;
-        // Whole rounds of wide tiles, then the ragged last round: when that round would be less than half full its
-        // columns go to narrow tiles in a second launch (M = 1024, N = 5120: 320 wide tiles = 256 + 64 -> 256 wide +
-        // 128 narrow: 73.8 -> ~59 us).  Tile rows of the weight layout are 16 columns, so any multiple of 128 splits.
-        const int rem = T2 % n_cu;
-        if (T2 > n_cu && rem != 0 && rem * 2 < n_cu && tiles_m <= n_cu) {
-            const int cols1 = ((T2 - rem) / tiles_m) * TileCfg<2>::BN;  // columns covered by complete rounds (rounded down)
-            if (cols1 > 0 && cols1 < N) {
-                int st = launch_cols(m, rows, 0, cols1, 2);
-                if (st != EETQ_OK) return st;
-                // the ragged round: narrow tiles in TWO K slices when those fill the chip once -- half the loop for ~3.5 us of
-                // hand-over (M = 1024, N = 5120: 128 narrow tiles -> 256 workgroups of K / 2; K = 13824 164 -> ~135 us)
-                const int rem_tiles = tiles_m * ((N - cols1 + TileCfg<1>::BN - 1) / TileCfg<1>::BN);
-                st                  = EETQ_ERR_UNSUPPORTED;
-                if (rem_tiles * 2 <= n_cu && (K / BK) / 2 >= 40) {
-                    Epilogue e = ep;
-                    if (e.residual) e.residual += (size_t)m * N;
-                    st = launch_tile_splitk_cols(x + (size_t)m * K, w, scales, e, y + (size_t)m * N, rows, cols1, N - cols1, K, N, 2, stream);
-                }
-                if (st == EETQ_ERR_UNSUPPORTED) st = launch_cols(m, rows, cols1, N - cols1, 0);
-                if (st != EETQ_OK) return st;
-                continue;
-            }
-        }
-        int st = launch_cols(m, rows, 0, N, 0);
-        if (st != EETQ_OK) return st;
-    }
-    return EETQ_OK;
+        return launch_large_lds(kernels[t.seg.narrow][glu ? 2 : t.ep.act != 0], "gemm_tile_kernel launch", dim3(tile_plan::grid_of(t.rows, t.seg)),
+                                dim3(256), tile_plan::lds_bytes(t.seg.narrow, 8), stream, t.x, t.w, t.scales, t.y, t.rows, t.seg.cols, K, t.ldc,
+                                t.ep);
+    });
 }
 
 // ---- K slices of the 128 x 64 tile ------------------------------------------------------------------------------------
@@ -184,17 +144,13 @@ int launch_gemm_tile_splitk(const f16* x, const uint8_t* w, const f16* scales, E
                             hipStream_t stream, int force_s, int* used_s, bool env_plan)
 {
     if (used_s) *used_s = 1;
-    static const bool allowed = [] {  // EETQ_AMD_SPLITK=0: no library-owned scratch anywhere (gemm_splitk.hip)
-        const char* e = getenv("EETQ_AMD_SPLITK");
-        return !(e && e[0] == '0');
-    }();
+    const bool allowed = splitk_allowed();
     int S = !allowed ? 1 : (force_s ? force_s : tile_splitk_slices(M, N, K));
     bool wide = false;
     if (allowed && !force_s && S == 1 && wide_tile_splitk_slices(M, N, K) == 2) {
         S    = 2;
         wide = true;
     }
-    const int KT = K / BK;
     // EETQ_AMD_TILESPLIT_PLAN="S" overrides the slice count of the 128 x 64 tile on the explicitly FORCED path only
     // (EETQ_PATH_TILESPLIT: tuning and tests, read per call); AUTO launches never read it
     if (const char* e = (env_plan && allowed) ? getenv("EETQ_AMD_TILESPLIT_PLAN") : nullptr) {
@@ -205,21 +161,18 @@ int launch_gemm_tile_splitk(const f16* x, const uint8_t* w, const f16* scales, E
         }
     }
     const bool fits = (size_t)M * K * 2 < (1ull << 31) && (size_t)N * K < (1ull << 31);
-    if ((S != 2 && S != 4) || ep.act != 0 || !fits || K % BK != 0 || KT / S < kMinKSteps)
+    if ((S != 2 && S != 4) || ep.act != 0 || !fits || K % BK != 0 || (K / BK) / S < kMinKSteps)
         return launch_gemm_mfma(x, w, scales, ep, y, M, N, K, stream);
     const int BN    = wide ? TileCfg<2>::BN : TileCfg<1>::BN;
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    float*        slabs = nullptr;
-    unsigned *    t2 = nullptr, *t4 = nullptr;
-    size_t        slab_bytes = 0, max_tiles = 0;
-    int st = splitk_region(stream, &slabs, &slab_bytes, &t2, &t4, &max_tiles);
-    if (st == EETQ_ERR_UNSUPPORTED || (st == EETQ_OK && ((size_t)tiles > max_tiles || (size_t)tiles * S * BM * BN * 4 > slab_bytes)))
-        return launch_gemm_mfma(x, w, scales, ep, y, M, N, K, stream);  // no scratch of its own for this stream: unsplit
+    float*    slabs   = nullptr;
+    unsigned* tickets = nullptr;
+    int       st      = tile_splitk_region(stream, tiles, BN, S, &slabs, &tickets);
+    if (st == EETQ_ERR_UNSUPPORTED) return launch_gemm_mfma(x, w, scales, ep, y, M, N, K, stream);  // no scratch of its own for this stream: unsplit
     if (st != EETQ_OK) return st;
     static LargeLdsKernel<decltype(&gemm_tile_splitk_kernel<1>)> kernels[2] = {{gemm_tile_splitk_kernel<1>}, {gemm_tile_splitk_kernel<2>}};
     st = launch_large_lds(kernels[wide], "gemm_tile_splitk_kernel launch", dim3(tiles * S), dim3(256),
-                          wide ? TileCfg<2>::SMEM_BYTES : TileCfg<1>::SMEM_BYTES, stream, x, w, scales, y, M, N, K, N, ep, S, slabs,
-                          S == 2 ? t2 : t4);
+                          wide ? TileCfg<2>::SMEM_BYTES : TileCfg<1>::SMEM_BYTES, stream, x, w, scales, y, M, N, K, N, ep, S, slabs, tickets);
     if (st == EETQ_OK && used_s) *used_s = S;
     return st;
 }

@@ -14,7 +14,10 @@
 //     order must fetch there;
 //   * gather = 1: row p reads x[sorted_slot[p] / k] of x [T][K]; gather = 0: x[p] of x [S][K].  Rows past the expert's count
 //     read its last row and are never stored; rows at or past offsets[E] and rows of inactive experts are never written.
-#include "gemm_kernel.hpp"
+//   * host side: the tile rule is the dense launchers' (gemm_tile_plan.hpp) on estimated row tiles, and the launch itself -- group
+//     map, narrow / wide, ldc, grid, LDS bytes -- is launch_grouped_tiles (gemm_tile_launch.hpp), shared with moe_int4_tiled.hip;
+//     this file supplies the limits, the kernel table and the EETQ_AMD_MOE_TILE_J tuning hook as the forced J.
+#include "gemm_tile_launch.hpp"
 
 namespace eetq {
 
@@ -32,21 +35,9 @@ __global__ __launch_bounds__(256, 1) void moe_gemm_tile_kernel(const f16* __rest
 
 }  // namespace
 
-// Which tile shape: the wide tile (128 x 128) is the efficient one when it fills the chip, the narrow one (128 x 64) doubles the
-// workgroups (launch_gemm_mfma's rule and its measured 0.70 cost ratio).  The counts live on the device, so the row tiles are
-// estimated from the shapes: min(E, S) experts with the mean S / min(E, S) rows each.
-bool moe_tiled_narrow(int S, int E, int N)
-{
-    const int    A     = S < E ? S : E;
-    const int    mean  = (S + A - 1) / A;
-    const long   rows  = (long)A * ((mean + BM - 1) / BM);
-    const long   ncu   = device_cu_count();
-    const long   t2    = rows * ((N + TileCfg<2>::BN - 1) / TileCfg<2>::BN);
-    const long   t1    = rows * ((N + TileCfg<1>::BN - 1) / TileCfg<1>::BN);
-    const double cost2 = (double)((t2 + ncu - 1) / ncu);
-    const double cost1 = 0.70 * (double)((t1 + ncu - 1) / ncu);
-    return cost1 < cost2;
-}
+// Which tile shape: the dense launchers' cost rule (tile_plan::narrow_cheaper) on the row tiles estimated from the shapes, since
+// the counts live on the device (tile_plan::grouped_row_tiles).
+bool moe_tiled_narrow(int S, int E, int N) { return tile_plan::narrow_cheaper(tile_plan::grouped_row_tiles(S, E), N, device_cu_count()); }
 
 bool moe_gemm_tiled_supports(int T, int k, int E, int N, int K, bool gather)
 {
@@ -61,20 +52,15 @@ int launch_moe_gemm_tiled(const f16* x, const uint8_t* w, const f16* scales, con
                           const int* active, f16* y, int T, int k, int E, int N, int K, bool gather, bool glu8, hipStream_t stream)
 {
     if (!moe_gemm_tiled_supports(T, k, E, N, K, gather)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs moe_gemm_kernel
-    const int      S   = T * k;
-    const GroupMap map = make_group_map(offsets, sorted_slot, active, T, k, E, gather);
     static const int force_j = [] {  // EETQ_AMD_MOE_TILE_J = 1 / 2 (behind EETQ_AMD_TUNING): A/B runs of the two tile shapes
         const char* e = tuning_env("EETQ_AMD_MOE_TILE_J");
         return e ? atoi(e) : 0;
     }();
-    const bool narrow = force_j == 1 || (force_j != 2 && moe_tiled_narrow(S, E, N));
-    const int  ldc    = glu8 ? N / 2 : N;
-    const int  bn     = narrow ? TileCfg<1>::BN : TileCfg<2>::BN;
-    // [narrow][GLU]; > 64 KiB of dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
+    // [narrow][GLU]
     static LargeLdsKernel<decltype(&moe_gemm_tile_kernel<2, false>)> kernels[2][2] = {
         {{moe_gemm_tile_kernel<2, false>}, {moe_gemm_tile_kernel<2, true>}}, {{moe_gemm_tile_kernel<1, false>}, {moe_gemm_tile_kernel<1, true>}}};
-    return launch_large_lds(kernels[narrow][glu8], "moe_gemm_tile_kernel launch", dim3((unsigned)(map.R * ((N + bn - 1) / bn))), dim3(256),
-                            narrow ? TileCfg<1>::SMEM_BYTES : TileCfg<2>::SMEM_BYTES, stream, x, w, scales, y, N, K, ldc, map);
+    return launch_grouped_tiles<8>(kernels, "moe_gemm_tile_kernel launch", x, w, scales, offsets, sorted_slot, active, y, T, k, E, N, K, gather, glu8,
+                                   force_j, stream);
 }
 
 }  // namespace eetq

@@ -2,9 +2,10 @@
 // W4A16 routed experts without the expansion to int8 tiles.  The kernel is gemm_tile_body (gemm_kernel.hpp) with GROUPED and
 // BITS = 4 -- moe_gemm_tiled.hip's row map, grid rule, ring, K-half combine and write-outs; only the weight DMA, the weight
 // fragment read and the dequant differ -- so a row comes out as eetq_expand_i4_to_i8 + eetq_w8a16_moe_gemm_tiled make it, bit for
-// bit, at either tile shape.  A file of its own so that the int8 kernels' machine code in gemm.o / gemm_splitk.o /
-// moe_gemm_tiled.o does not depend on it.
-#include "gemm_kernel.hpp"
+// bit, at either tile shape.  The launch is launch_grouped_tiles (gemm_tile_launch.hpp), the int8 form's, with tile_j as the forced
+// J; this file supplies the limits and the kernel table.  A file of its own so that the int8 kernels' machine code in gemm.o /
+// gemm_splitk.o / moe_gemm_tiled.o does not depend on it.
+#include "gemm_tile_launch.hpp"
 #include "moe_gemm_kernel.hpp"
 
 namespace eetq {
@@ -44,20 +45,13 @@ int eetq_w4a16_moe_gemm_tiled(const void* x, const int8_t* w_packed_i4, const vo
     if (st != EETQ_OK) return st;
     EETQ_REQUIRE(tile_j >= 0 && tile_j <= 2, "eetq_w4a16_moe_gemm_tiled: tile_j is 0 (the launcher's rule), 1 (128 x 64) or 2 (128 x 128)");
     if (!supports(T, k, E, N, K, gather != 0)) return EETQ_ERR_UNSUPPORTED;  // quiet: the caller runs eetq_w4a16_moe_gemm
-    const GroupMap map    = make_group_map(offsets, sorted_slot, active, T, k, E, gather != 0);
-    const bool     narrow = tile_j == 1 || (tile_j == 0 && moe_tiled_narrow(T * k, E, N));
-    const int  ldc    = glu8 ? N / 2 : N;
-    using C1 = TileCfg<1, 2, 4>;
-    using C2 = TileCfg<2, 2, 4>;
-    const int bn = narrow ? C1::BN : C2::BN;
-    // [narrow][GLU]; > 64 KiB of dynamic LDS: the kernel about to be launched is opted in, once per device (common.hpp)
+    // [narrow][GLU]
     static LargeLdsKernel<decltype(&moe_gemm_tile_i4_kernel<2, false>)> kernels[2][2] = {
         {{moe_gemm_tile_i4_kernel<2, false>}, {moe_gemm_tile_i4_kernel<2, true>}},
         {{moe_gemm_tile_i4_kernel<1, false>}, {moe_gemm_tile_i4_kernel<1, true>}}};
-    return launch_large_lds(kernels[narrow][glu8 != 0], "moe_gemm_tile_i4_kernel launch", dim3((unsigned)(map.R * ((N + bn - 1) / bn))),
-                            dim3(256), narrow ? C1::SMEM_BYTES : C2::SMEM_BYTES, static_cast<hipStream_t>(stream),
-                            static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed_i4), static_cast<const f16*>(scales),
-                            static_cast<f16*>(y), N, K, ldc, map);
+    return launch_grouped_tiles<4>(kernels, "moe_gemm_tile_i4_kernel launch", static_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(w_packed_i4),
+                                   static_cast<const f16*>(scales), offsets, sorted_slot, active, static_cast<f16*>(y), T, k, E, N, K, gather != 0,
+                                   glu8 != 0, tile_j, static_cast<hipStream_t>(stream));
 }
 
 int eetq_w4a16_moe_gemm_tiled_supported(int T, int k, int E, int N, int K, int gather)

@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count, eetq_diag_tile_plan).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -651,6 +651,19 @@ int eetq_diag_auto_path(int bits, int M, int N, int K, int* path, int* detail);
  * combination, its constants fitted on the measured time of every plan -- profiles/r05_splitk_plan_regret*.jsonl), so
  * tests/test_abi.py can hold the planner against those tables without a GPU.  1 <= M <= 1024, K % 64 == 0. */
 int eetq_diag_splitk_plan(int M, int N, int K, int* column_blocks, int* k_slices, int* ring, int* row_groups);
+
+/* Diagnostic, host arithmetic only (no launch; with cus > 0 no device either; added within ABI revision 7): the launches the
+ * LDS-tiled MFMA kernel's dense launchers make for an M x K activation against a K x N weight of `bits` -- 8: eetq_w8a16_gemm_ex
+ * (EETQ_PATH_MFMA) with epilogue `act` (EETQ_ACT_*), tile_j = 0; 4: eetq_w4a16_gemm_tiled with its tile_j (0 = the rule, 1 =
+ * 128 x 64, 2 = 128 x 128), act = 0 -- on a chip with `cus` compute units (<= 0: the current device's).  One record of six ints per
+ * launch, in launch order: {row0, rows, col0, cols, tile, k_slices}; tile = 2 the 128 x 128 tile, 1 the 128 x 64 tile, 0 a 64-row
+ * chunk of the small-batch kernel (bits = 8, K < 320).  *count = the number of launches; the first min(*count, max_records)
+ * records are written.  It walks the planner the launchers walk (csrc/gemm_tile_plan.hpp) and reports what that planner ASKS for:
+ * k_slices = 2 (the ragged last round of wide tiles in two K slices of the narrow tile) needs the stream's split-K scratch region,
+ * and a launch runs that segment unsplit, with the tile shape the record names, when the stream has none or EETQ_AMD_SPLITK=0.
+ * EETQ_ERR_UNSUPPORTED for what the launcher of these bits refuses (bits = 4: K % 128 != 0, K < 384, act != 0; either: an operand
+ * beyond the 32-bit buffer offsets); EETQ_ERR_INVALID for a null pointer or other bits. */
+int eetq_diag_tile_plan(int bits, int M, int N, int K, int act, int tile_j, int cus, int* records, int max_records, int* count);
 
 /* Decode steps on a pre-allocated KV cache (eetq_rope_decode_attention_f16, eetq_rotary_neox_kvcache_f16) whose new token
  * was NOT written because its cache row lies outside the cache (slot >= rows: the cache is full; or a negative position) or,

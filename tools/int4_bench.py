@@ -22,19 +22,15 @@ SHAPES = [(4096, 4096), (4096, 11008), (11008, 4096), (5120, 5120), (5120, 13824
 
 
 def direct_plan(M, N, K, n_cu):
-    """launch_gemm_tile_i4's plan at tile_j = 0, restated (gemm_int4_tiled.hip): the tile shapes of its one or two launches"""
-    tiles_m = (M + 127) // 128
-
-    def shape(cols):
-        t2, t1 = tiles_m * ((cols + 127) // 128), tiles_m * ((cols + 63) // 64)
-        return "128x64" if 0.70 * ((t1 + n_cu - 1) // n_cu) < (t2 + n_cu - 1) // n_cu else "128x128"
-    T2 = tiles_m * ((N + 127) // 128)
-    rem = T2 % n_cu
-    if T2 > n_cu and rem and rem * 2 < n_cu and tiles_m <= n_cu:
-        cols1 = ((T2 - rem) // tiles_m) * 128
-        if 0 < cols1 < N:
-            return "128x128[:%d]+%s" % (cols1, shape(N - cols1))
-    return shape(N)
+    """launch_gemm_tile_i4's plan at tile_j = 0 (eetq_diag_tile_plan: the planner the launcher walks): the tile shapes of its one
+    or two launches"""
+    import ctypes
+    from eetq_amd import _lib
+    rec, count = (ctypes.c_int * 12)(), ctypes.c_int(0)
+    _lib.check(_lib.lib().eetq_diag_tile_plan(4, M, N, K, 0, 0, n_cu, rec, 2, ctypes.byref(count)))
+    assert count.value <= 2, "more than one row chunk"
+    shapes = ["128x64" if rec[6 * i + 4] == 1 else "128x128" for i in range(count.value)]
+    return shapes[0] if count.value == 1 else "%s[:%d]+%s" % (shapes[0], rec[3], shapes[1])
 
 
 def chain_on(stream, step, calls):
