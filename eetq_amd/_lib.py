@@ -103,6 +103,9 @@ def _declare(L):
                                            ctypes.c_float, vp, vp, i32, vp, vp],
         "eetq_prefill_attention_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp],
         "eetq_prefill_attention_supported": [i32],
+        "eetq_prefill_attention_dev_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp],
+        "eetq_prefill_attention_splits": [i32, i32, i32, i32],
+        "eetq_prefill_attention_max_splits": [],
         "eetq_decode_attention_splits": [i32, i32, i32],
         "eetq_prof_begin": [i32],
         "eetq_prof_end": [vp, i32, vp],
@@ -140,6 +143,8 @@ def _declare(L):
         fn.restype = i32
     L.eetq_quantize_workspace_floats.restype = ctypes.c_size_t
     L.eetq_quantize_workspace_floats.argtypes = [sz, sz]
+    L.eetq_prefill_attention_workspace_floats.restype = ctypes.c_size_t
+    L.eetq_prefill_attention_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.eetq_release_workspace.restype = i32
     L.eetq_release_workspace.argtypes = [ctypes.POINTER(ctypes.c_size_t)]
     L.eetq_last_error.restype = ctypes.c_char_p
@@ -165,6 +170,8 @@ EXPORTED_SYMBOLS = (
     "eetq_moe_router_f16", "eetq_moe_topk_f16", "eetq_moe_router_sigmoid_f16", "eetq_moe_topk_sigmoid_f32",
     "eetq_rotary_neox_bounded", "eetq_rotary_neox_strided_bounded_f16", "eetq_rotary_neox_kvcache_bounded_f16",
     "eetq_rotary_neox_kvcache_prefill_bounded_f16", "eetq_rope_decode_attention_bounded_f16",
+    "eetq_prefill_attention_dev_f16", "eetq_prefill_attention_splits", "eetq_prefill_attention_max_splits",
+    "eetq_prefill_attention_workspace_floats",
 )
 
 

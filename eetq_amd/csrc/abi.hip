@@ -895,6 +895,27 @@ int eetq_prefill_attention_f16(const void* q, const void* k, const void* v, void
 
 int eetq_prefill_attention_supported(int head_dim) { return prefill_attention_supports(head_dim) ? 1 : 0; }
 
+int eetq_prefill_attention_dev_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                   int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                   int splits, float scaling, const long* strides, void* stream)
+{
+    return launch_prefill_attention_dev(static_cast<const f16*>(q), static_cast<const f16*>(k), static_cast<const f16*>(v),
+                                        static_cast<f16*>(out), workspace, batch, heads, kv_heads, q_tokens, max_keys, head_dim, kv_len,
+                                        kv_len_bias, splits, scaling, strides, static_cast<hipStream_t>(stream));
+}
+
+int eetq_prefill_attention_splits(int batch, int heads, int q_tokens, int max_keys)
+{
+    return prefill_attention_splits(batch, heads, q_tokens, max_keys);
+}
+
+int eetq_prefill_attention_max_splits(void) { return prefill_attention_max_splits(); }
+
+size_t eetq_prefill_attention_workspace_floats(int batch, int heads, int q_tokens, int head_dim, int splits)
+{
+    return prefill_attention_workspace_floats(batch, heads, q_tokens, head_dim, splits);
+}
+
 int eetq_decode_dropped_steps(unsigned long long* count, int reset)
 {
     EETQ_REQUIRE(count, "null pointer");

@@ -48,9 +48,37 @@ struct PrefillArgs {
     float      c;   // scaling * log2(e)
 };
 
-template <int D>
-__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillArgs a)
+// The device-length and split-KV forms (kPfDev, kPfSplit) take the cache's length from a device counter and / or hand the key blocks
+// of a workgroup to `ns` workgroups.  Their arguments ride behind the host form's, which keeps its own kernarg block.
+struct PrefillDevArgs : PrefillArgs {
+    const int64_t* kv_len;   // DEVICE scalar or nullptr (then Tk is the host's); Tk = clamp(*kv_len + kv_len_bias, 0, Tk), koff = Tk - Tq
+    float*         ws;       // split form: per (b, h, query row, split) D unnormalised fp32 accumulators, then the (m, l) pairs
+    int            kv_len_bias, ns;
+};
+constexpr int kPfHost = 0, kPfDev = 1, kPfSplit = 2;
+constexpr int kPfMaxSplits = 16;
+
+// MODE kPfHost: keys and causal offset from the host (the fresh prompt's path, unchanged).  kPfDev: every workgroup reads the length
+// at entry -- one scalar load -- and forms Tk and koff itself; kend, nblk, the descriptors' range, `active` and `edge` follow, the
+// grid depends on Tq alone.  kPfSplit: workgroup id / ns is the (query block, head, batch row) of the other forms, id % ns its
+// share [i nblk / ns, (i + 1) nblk / ns) of that workgroup's key blocks; it leaves (o, m, l) per row in the workspace, an empty
+// share or a row with nothing to attend as (zeros, -inf, 0), and prefill_merge_kernel divides.
+template <int D, int MODE>
+__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs> a_in)
 {
+    PrefillArgs a = a_in;
+    int         wg = (int)blockIdx.x, split = 0;
+    if constexpr (MODE != kPfHost) {
+        if (a_in.kv_len) {
+            const int64_t n = *a_in.kv_len + (int64_t)a_in.kv_len_bias;   // uniform: a scalar load
+            a.Tk = (int)max((int64_t)0, min((int64_t)a.Tk, n));
+        }
+        a.koff = a.Tk - a.Tq;
+    }
+    if constexpr (MODE == kPfSplit) {
+        split = wg % a_in.ns;
+        wg /= a_in.ns;
+    }
     static_assert(D == 128 || D == 64, "head_dim 128 or 64");
     constexpr int KS = D / 16;            // k-steps of the score product
     constexpr int DT = D / 32;            // 32-channel blocks of the output
@@ -67,13 +95,19 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     // (wave in a scalar register: the per-wave tests below -- block skipped, block on the diagonal -- must be branches, not selects)
     // 1-D grid, heaviest query blocks first: id -> (query block rank, head, batch row).  With H * B a multiple of 8 all query blocks
     // of a head land on one XCD (its K / V rows are shared in that L2), and a CU's second workgroup is a light one
-    const int hb = a.H * a.B, qb = a.nqb - 1 - (int)blockIdx.x / hb, rest = (int)blockIdx.x % hb;
+    const int hb = a.H * a.B, qb = a.nqb - 1 - wg / hb, rest = wg % hb;
     const int h = rest % a.H, b = rest / a.H, hk = h / a.groups;
     const int q0 = qb * kPfBM, qrow = q0 + wave * 32 + ln;           // this lane's query row
     const int qlast_wave = q0 + wave * 32 + 31;                       // the wave's last row
     // keys this workgroup needs: rows <= its last query + koff
     const int kend  = min(a.Tk, q0 + kPfBM + a.koff);
     const int nblk  = kend > 0 ? (kend + kPfBN - 1) / kPfBN : 0;
+    // this workgroup's key blocks [j0, j1): all of them, or its share
+    int j0 = 0, j1 = nblk;
+    if constexpr (MODE == kPfSplit) {
+        j0 = (int)((long)split * nblk / a_in.ns);
+        j1 = (int)((long)(split + 1) * nblk / a_in.ns);
+    }
     // the valid rows of this (batch row, kv head) behind buffer descriptors: rows at and beyond Tk are out of range and read as zeros
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.k + b * a.k_sb + hk * a.k_sh), 0,
                                                                          (int)((unsigned)a.Tk * (unsigned)a.k_ss * 2u), 0x00020000);
@@ -135,18 +169,18 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
         }
     };
 
-    if (nblk > 0) {
-        fetch(0);
-        stage(0);
-        if (nblk > 1) fetch(1);
+    if (j1 > j0) {
+        fetch(j0);
+        stage(j0 & 1);
+        if (j1 > j0 + 1) fetch(j0 + 1);
     }
     __syncthreads();
 
-    for (int j = 0; j < nblk; ++j) {
+    for (int j = j0; j < j1; ++j) {
         const int  key0   = j * kPfBN;
         const bool active = key0 <= qlast_wave + a.koff;  // wave-uniform: some row of this wave attends this block
-        if (j + 1 < nblk) stage((j + 1) & 1);             // block j + 1: registers -> the buffer block j - 1 was read from
-        if (j + 2 < nblk) fetch(j + 2);
+        if (j + 1 < j1) stage((j + 1) & 1);               // block j + 1: registers -> the buffer block j - 1 was read from
+        if (j + 2 < j1) fetch(j + 2);
         const f16* k_lds  = k_lds2[j & 1];
         const f16* vt_lds = vt_lds2[j & 1];
         if (active) {
@@ -225,6 +259,25 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
         __syncthreads();       // block j has been read by every wave; block j + 1 is in the other buffer
     }
 
+    // ---- split form: the row's record, unnormalised (the 2^12 carry is in o and l alike and leaves in the merge's division) ----
+    if constexpr (MODE == kPfSplit) {
+        if (qrow < a.Tq) {
+            const long rec  = (((long)b * a.H + h) * a.Tq + qrow) * a_in.ns + split;
+            const long recs = (long)a.B * a.H * a.Tq * a_in.ns;
+            float*     wp   = a_in.ws + rec * D + 4 * hi;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<f32x4*>(wp + 32 * dt + 8 * g) =
+                        f32x4{o[dt][4 * g + 0], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+            if (hi == 0) {   // both halves of a lane pair hold the row's m and l
+                a_in.ws[recs * D + 2 * rec]     = m_run;
+                a_in.ws[recs * D + 2 * rec + 1] = l_run;
+            }
+        }
+        return;
+    }
     // ---- normalise and store: lane (ln, hi) holds row `qrow`, channels 32 dt + 8 g + 4 hi .. + 3 ----
     if (qrow < a.Tq) {
         const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
@@ -240,6 +293,60 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     }
 }
 
+// The `ns` records of a query row into its fp16 output: weights exp2(m_i - max m), one division.  A thread owns four channels of
+// one (b, h, row); a row whose every l is 0 (nothing to attend) gives zeros.  The records' order is the splits': deterministic.
+template <int D>
+__global__ __launch_bounds__(256) void prefill_merge_kernel(const float* __restrict__ ws, f16* __restrict__ out, long rows, int ns, int Tq,
+                                                            int H, long o_sb, long o_st, long o_sh)
+{
+    constexpr int TPR = D / 4;   // threads per row
+    const long    gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long    row = gid / TPR;
+    const int     ch  = 4 * (int)(gid % TPR);
+    if (row >= rows) return;
+    const float* ml = ws + rows * ns * D + 2 * row * ns;
+    float        m  = -INFINITY;
+    for (int i = 0; i < ns; ++i) m = fmaxf(m, ml[2 * i]);
+    const float m_use = m > -INFINITY ? m : 0.f;
+    f32x4       acc   = {0.f, 0.f, 0.f, 0.f};
+    float       l     = 0.f;
+    for (int i = 0; i < ns; ++i) {
+        const float w = __builtin_amdgcn_exp2f(ml[2 * i] - m_use);   // exp2(-inf) = 0: an empty share
+        const f32x4 o = *reinterpret_cast<const f32x4*>(ws + (row * ns + i) * D + ch);
+        l += w * ml[2 * i + 1];
+        acc += w * o;
+    }
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const int   t = (int)(row % Tq), h = (int)(row / Tq % H);
+    const long  b = row / Tq / H;
+    const f16x2 lo = {(f16)(acc[0] * inv), (f16)(acc[1] * inv)}, hh = {(f16)(acc[2] * inv), (f16)(acc[3] * inv)};
+    *reinterpret_cast<u32x2*>(out + b * o_sb + (long)t * o_st + h * o_sh + ch) = u32x2{as_u32(lo), as_u32(hh)};
+}
+
+int check_prefill_common(const f16* q, const f16* k, const f16* v, f16* out, int B, int H, int Hkv, int Tq, int Tk, int D, const long* st)
+{
+    EETQ_REQUIRE(q && k && v && out && st, "null pointer");
+    EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0 && Tk > 0, "invalid attention shape");
+    if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
+    for (int i = 0; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "strides must be multiples of 4 elements");
+    for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte loads)");
+    EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)out % 8 == 0, "q, k, v must be 16-byte aligned, out 8-byte");
+    EETQ_REQUIRE((long)Tk * st[5] * 2 < (1L << 31) && (long)Tk * st[8] * 2 < (1L << 31), "one head's cache rows must span less than 2 GiB");
+    EETQ_REQUIRE((long)((Tq + kPfBM - 1) / kPfBM) * H * B < (1L << 31), "too many workgroups");
+    return EETQ_OK;
+}
+
+void fill_prefill_args(PrefillArgs& a, const f16* q, const f16* k, const f16* v, f16* out, int B, int H, int Hkv, int Tq, int Tk,
+                       int causal_offset, float scaling, const long* st)
+{
+    a.q = q, a.k = k, a.v = v, a.out = out;
+    a.q_sb = st[0], a.q_st = st[1], a.q_sh = st[2], a.k_sb = st[3], a.k_sh = st[4], a.k_ss = st[5];
+    a.v_sb = st[6], a.v_sh = st[7], a.v_ss = st[8], a.o_sb = st[9], a.o_st = st[10], a.o_sh = st[11];
+    a.Tq = Tq, a.Tk = Tk, a.koff = causal_offset, a.groups = H / Hkv;
+    a.c = scaling * 1.4426950408889634f;
+    a.H = H, a.B = B, a.nqb = (Tq + kPfBM - 1) / kPfBM;
+}
+
 }  // namespace
 
 bool prefill_attention_supports(int D) { return D == 128 || D == 64; }
@@ -248,26 +355,80 @@ bool prefill_attention_supports(int D) { return D == 128 || D == 64; }
 int launch_prefill_attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int H, int Hkv, int Tq, int Tk, int D,
                              int causal_offset, float scaling, const long* st, hipStream_t stream)
 {
-    EETQ_REQUIRE(q && k && v && out && st, "null pointer");
-    EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0 && Tk > 0, "invalid attention shape");
-    if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
-    for (int i = 0; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "strides must be multiples of 4 elements");
-    for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte loads)");
-    EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)out % 8 == 0, "q, k, v must be 16-byte aligned, out 8-byte");
+    const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, Tk, D, st);
+    if (rc != EETQ_OK) return rc;
     PrefillArgs a;
-    a.q = q, a.k = k, a.v = v, a.out = out;
-    a.q_sb = st[0], a.q_st = st[1], a.q_sh = st[2], a.k_sb = st[3], a.k_sh = st[4], a.k_ss = st[5];
-    a.v_sb = st[6], a.v_sh = st[7], a.v_ss = st[8], a.o_sb = st[9], a.o_st = st[10], a.o_sh = st[11];
-    a.Tq = Tq, a.Tk = Tk, a.koff = causal_offset, a.groups = H / Hkv;
-    a.c = scaling * 1.4426950408889634f;
-    EETQ_REQUIRE((long)Tk * st[5] * 2 < (1L << 31) && (long)Tk * st[8] * 2 < (1L << 31), "one head's cache rows must span less than 2 GiB");
-    a.H = H, a.B = B, a.nqb = (Tq + kPfBM - 1) / kPfBM;
-    EETQ_REQUIRE((long)a.nqb * H * B < (1L << 31), "too many workgroups");
+    fill_prefill_args(a, q, k, v, out, B, H, Hkv, Tq, Tk, causal_offset, scaling, st);
     if (D == 128)
-        launch_kernel(prefill_attn_kernel<128>, dim3((unsigned)(a.nqb * H * B)), dim3(kPfThreads), 0, stream, a);
+        launch_kernel(prefill_attn_kernel<128, kPfHost>, dim3((unsigned)(a.nqb * H * B)), dim3(kPfThreads), 0, stream, a);
     else
-        launch_kernel(prefill_attn_kernel<64>, dim3((unsigned)(a.nqb * H * B)), dim3(kPfThreads), 0, stream, a);
+        launch_kernel(prefill_attn_kernel<64, kPfHost>, dim3((unsigned)(a.nqb * H * B)), dim3(kPfThreads), 0, stream, a);
     return check_hip(hipGetLastError(), "prefill_attn_kernel launch");
+}
+
+int prefill_attention_max_splits() { return kPfMaxSplits; }
+
+size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits)
+{
+    if (B <= 0 || H <= 0 || Tq <= 0 || D <= 0 || splits <= 1) return 0;
+    return (size_t)B * H * Tq * splits * (D + 2);
+}
+
+// The count the split form is worth, from the measured table (profiles/prefill_attn_append.txt): shares are doubled while
+// the grid stays within 1.25 workgroups per compute unit and every share keeps enough key blocks to pay for its record and the merge
+// launch -- 4 blocks (256 keys) while the grid covers at most half the compute units, 8 up to all of them, 16 beyond.  1 wherever the
+// query blocks alone fill the chip.  Never more shares than key blocks.
+int prefill_attention_splits(int B, int H, int Tq, int max_keys)
+{
+    if (B <= 0 || H <= 0 || Tq <= 0 || max_keys <= 0) return 1;
+    const long wgs = (long)((Tq + kPfBM - 1) / kPfBM) * H * B, cus = device_cu_count();
+    const long blocks = ((long)max_keys + kPfBN - 1) / kPfBN;
+    long       ns = 1;
+    for (long n = 2; n <= kPfMaxSplits; n *= 2) {
+        const long grid = n * wgs;
+        if (4 * grid > 5 * cus) break;
+        const long min_blocks = 2 * grid <= cus ? 4 : grid <= cus ? 8 : 16;
+        if (blocks / n < min_blocks) break;
+        ns = n;
+    }
+    return (int)ns;
+}
+
+// Device-length and split-KV launches: keys <= max_keys from *kv_len + kv_len_bias (kv_len nullptr: max_keys itself), causal offset
+// keys - Tq.  splits > 1: two plain launches, the shares into `ws` (prefill_attention_workspace_floats), then the merge.
+int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq, int max_keys,
+                                 int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st, hipStream_t stream)
+{
+    EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
+    EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
+    const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
+    if (rc != EETQ_OK) return rc;
+    EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
+    if (splits == 1 && !kv_len) return launch_prefill_attention(q, k, v, out, B, H, Hkv, Tq, max_keys, D, max_keys - Tq, scaling, st, stream);
+    PrefillDevArgs a;
+    fill_prefill_args(a, q, k, v, out, B, H, Hkv, Tq, max_keys, max_keys - Tq, scaling, st);
+    a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits;
+    const long wgs = (long)a.nqb * H * B * splits;
+    EETQ_REQUIRE(wgs < (1L << 31), "too many workgroups");
+    const dim3 grid((unsigned)wgs), block(kPfThreads);
+    if (splits == 1) {
+        if (D == 128)
+            launch_kernel(prefill_attn_kernel<128, kPfDev>, grid, block, 0, stream, a);
+        else
+            launch_kernel(prefill_attn_kernel<64, kPfDev>, grid, block, 0, stream, a);
+        return check_hip(hipGetLastError(), "prefill_attn_kernel (device length) launch");
+    }
+    const long rows = (long)B * H * Tq, threads = rows * (D / 4);
+    EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
+    const dim3 mgrid((unsigned)((threads + 255) / 256));
+    if (D == 128) {
+        launch_kernel(prefill_attn_kernel<128, kPfSplit>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    } else {
+        launch_kernel(prefill_attn_kernel<64, kPfSplit>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    }
+    return check_hip(hipGetLastError(), "prefill_attn_kernel (split) launch");
 }
 
 }  // namespace eetq

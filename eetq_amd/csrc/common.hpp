@@ -330,6 +330,12 @@ int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int 
 bool prefill_attention_supports(int D);
 int launch_prefill_attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int H, int Hkv, int Tq, int Tk, int D,
                              int causal_offset, float scaling, const long* st, hipStream_t stream);
+int    launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq, int max_keys,
+                                    int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
+                                    hipStream_t stream);
+int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
+int    prefill_attention_max_splits();
+size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
 int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
                        int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
                        int64_t* advance, hipStream_t stream);

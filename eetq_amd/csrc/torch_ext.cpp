@@ -227,8 +227,16 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
 // dense), key / value cache views [B, Hkv, rows >= keys, D]; returns [B, T, H, D] contiguous
 bool prefill_attention_supported(int64_t head_dim) { return eetq_prefill_attention_supported((int)head_dim) != 0; }
 
+int64_t prefill_attention_splits(int64_t batch, int64_t heads, int64_t q_tokens, int64_t max_keys)
+{
+    return eetq_prefill_attention_splits((int)batch, (int)heads, (int)q_tokens, (int)max_keys);
+}
+
+// kv_len (a one-element int64 tensor on the query's device): `keys` is then the upper bound and the number of keys is read on the
+// device (eetq_prefill_attention_dev_f16); splits: None = the library's rule, workspace: None = allocated here (capturable)
 Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
-                         std::optional<int64_t> causal_offset)
+                         std::optional<int64_t> causal_offset, const OptTensor& kv_len, int64_t kv_len_bias,
+                         std::optional<int64_t> splits_in, const OptTensor& workspace)
 {
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
         TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
@@ -240,11 +248,43 @@ Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& v
     TORCH_CHECK(prefill_attention_supported(D), "prefill_attention: unsupported head_dim");
     const double sc  = scaling ? *scaling : 1.0 / std::sqrt((double)D);
     const int64_t off = causal_offset ? *causal_offset : keys - T;
+    const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0;
+    int64_t      splits = 1;
+    Tensor       ws;
+    if (dev_form) {
+        TORCH_CHECK(!(kv_len && causal_offset), "prefill_attention: kv_len and causal_offset exclude each other (with kv_len the offset is "
+                                                "the device length minus the query rows)");
+        TORCH_CHECK(kv_len || kv_len_bias == 0, "prefill_attention: kv_len_bias needs kv_len");
+        if (kv_len)
+            TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(),
+                        "prefill_attention: kv_len must be a one-element int64 tensor on the query's device");
+        splits = splits_in ? *splits_in : prefill_attention_splits(B, H, T, keys);
+        TORCH_CHECK(splits >= 1 && splits <= eetq_prefill_attention_max_splits(), "prefill_attention: splits must lie in 1 .. ",
+                    eetq_prefill_attention_max_splits());
+        const int64_t need = (int64_t)eetq_prefill_attention_workspace_floats((int)B, (int)H, (int)T, (int)D, (int)splits);
+        if (workspace) {
+            TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
+                            workspace->numel() >= need,
+                        "prefill_attention: workspace must be a contiguous float32 tensor of at least ", need,
+                        " elements on the query's device");
+            ws = *workspace;
+        } else if (need > 0) {
+            ws = torch::empty({need}, query.options().dtype(at::kFloat));
+        }
+    }
     Tensor       out = torch::empty({B, T, H, D}, query.options());
     const long   st[12] = {(long)query.stride(0), (long)query.stride(1), (long)query.stride(2), (long)key.stride(0), (long)key.stride(1),
                            (long)key.stride(2),   (long)value.stride(0), (long)value.stride(1), (long)value.stride(2),
                            (long)out.stride(0),   (long)out.stride(1),   (long)out.stride(2)};
     c10::DeviceGuard guard(query.device());
+    if (kv_len || splits > 1) {
+        TORCH_CHECK(kv_len || off == keys - T, "prefill_attention: the split form takes causal_offset = keys - query rows only");
+        check(eetq_prefill_attention_dev_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(),
+                                             ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)keys,
+                                             (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, (int)splits,
+                                             (float)sc, st, stream_of(query)));
+        return out;
+    }
     check(eetq_prefill_attention_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), (int)B, (int)H, (int)Hkv, (int)T,
                                      (int)keys, (int)D, (int)off, (float)sc, st, stream_of(query)));
     return out;
@@ -1682,9 +1722,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
           py::arg("advance") = py::none());
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
-          py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(),
+          py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
           "causal attention of a prompt's query rows [B, T, H, D] over the first `keys` rows of a KV cache [B, Hkv, S, D] (MFMA)");
     m.def("prefill_attention_supported", &prefill_attention_supported, py::arg("head_dim"));
+    m.def("prefill_attention_splits", &prefill_attention_splits, py::arg("batch"), py::arg("heads"), py::arg("q_tokens"), py::arg("max_keys"),
+          "the split count prefill_attention uses with splits=None (1 = unsplit)");
     m.def("llama_decode_layer", &llama_decode_layer, "one decode step of an accelerated Llama decoder layer (six launches, one call)",
           py::arg("hidden"), py::arg("input_norm"), py::arg("qkv_weight"), py::arg("qkv_scale"), py::arg("qkv_bias"),
           py::arg("positions"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("tickets"),

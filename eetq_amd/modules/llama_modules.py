@@ -18,7 +18,8 @@ import torch.nn as nn
 
 from .. import ops
 
-__all__ = ["EETRotaryEmbedding", "EETLlamaAttention", "EETQuantLlamaAttention", "EETLlamaMLP", "fresh_static_prefill"]
+__all__ = ["EETRotaryEmbedding", "EETLlamaAttention", "EETQuantLlamaAttention", "EETLlamaMLP", "fresh_static_prefill",
+           "appended_static_prefill"]
 
 _prefill_promise = threading.local()
 
@@ -38,6 +39,23 @@ def fresh_static_prefill():
         yield
     finally:
         _prefill_promise.fresh = prev
+
+
+@contextlib.contextmanager
+def appended_static_prefill():
+    """The caller's promise for the forwards run inside (per thread): the prompt is unpadded and the static cache's rows
+    0 .. counter - 1 are this sequence's real tokens, so a prompt appended behind them attends exactly the rows below the
+    advanced counter, causally among its own.  The attention blocks write the rows as they do without the promise (behind the
+    device counter, which they advance) and then call the library's prompt kernel with the counter as its DEVICE length
+    (``ops.prefill_attention(..., kv_len=counter)``: no host read, half the key blocks of a masked pass over the whole
+    pre-allocated cache) and ignore the model-level mask.  ``GraphDecoder`` makes this promise for the later pieces of a
+    chunked prompt and for ``append=True``.  Inside it ``fresh_static_prefill`` does not hold."""
+    prev = getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False)
+    _prefill_promise.appended, _prefill_promise.fresh = True, False
+    try:
+        yield
+    finally:
+        _prefill_promise.appended, _prefill_promise.fresh = prev
 
 
 class EETRotaryEmbedding(nn.Module):
@@ -211,10 +229,19 @@ class _EETAttentionBase(nn.Module):
 
     def _attend(self, q, k, v, attention_mask, past_key_values, input_shape, kwargs, cached=None):
         """q [B, T, H, D], k/v [B, T, Hkv, D] (views into the projection output) -> [B, T, H*D].  ``cached``: the (keys, values)
-        of a static cache that already hold this call's rotated k and v (then k, v and past_key_values are unused)."""
+        of a static cache that already hold this call's rotated k and v (then k, v and past_key_values are unused), with the
+        cache's device counter, already advanced, as a third element."""
         q = q.transpose(1, 2)
         if cached is not None:
-            k, v = cached
+            k, v, counter = cached
+            if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1
+                    and not kwargs.get("output_attentions", False) and self.mfma_prefill and ops.prefill_attention is not None
+                    and q.is_cuda and q.dtype == torch.float16 and ops.prefill_attention_supported(self.head_dim)
+                    and k.stride(-1) == 1 and v.stride(-1) == 1):
+                # promised: rows 0 .. counter - 1 are this sequence's tokens, the last T of them this prompt's -> the same kernel
+                # with the counter as its device length (the causal offset follows from it in the kernel)
+                out = ops.prefill_attention(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
+                return out.reshape(*input_shape, -1), None
             if (getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1 and not kwargs.get("output_attentions", False)):
                 # promised: the cache was empty and the prompt is unpadded -> causal attention over the T rows just written
                 t_len = q.shape[2]
@@ -385,7 +412,7 @@ class EETLlamaAttention(_EETAttentionBase):
                 out, weights = self._attend(q, k, v, attention_mask, past_key_values, (bsz, q_len), kwargs)
             else:
                 out, weights = self._attend(q, None, None, attention_mask, None, (bsz, q_len), kwargs,
-                                            cached=(player.keys, player.values))
+                                            cached=(player.keys, player.values, player.cumulative_length))
         if residual is None:
             return self.o_proj(out), weights
         if hasattr(self.o_proj, "qweight"):

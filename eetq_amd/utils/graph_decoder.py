@@ -80,6 +80,10 @@ class GraphDecoder:
                         for _ in range(self.steps_per_graph):
                             self._advance()
         self.cache.reset()
+        # host-side bookkeeping of a conversation: cache rows written, and whether s_tok holds a token the caller has seen but the
+        # cache has not (the last one a generate() emitted)
+        self.rows = 0
+        self._pending = False
 
     def _fresh_prefill_ok(self):
         """True when the prompt may run under ``fresh_static_prefill``: the lean layer-by-layer model, every attention block
@@ -142,23 +146,31 @@ class GraphDecoder:
 
     @torch.no_grad()
     def generate(self, prompt, new_tokens, return_prefill_logits=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-                 seed=0, eos_token_id=None, pad_token_id=None):
-        """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens].  On a decoder built with ``sampling=True``:
+                 seed=0, eos_token_id=None, pad_token_id=None, append=False, prefill_chunk=None):
+        """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens].  ``append=True`` continues the conversation
+        the cache holds (a second turn): the token the previous ``generate`` emitted last, which the cache has not seen yet, and
+        the prompt are written behind the cached rows, so the cache holds every token the caller has seen, in order; positions
+        continue, the graphs are replayed as they were captured, and the return value is this turn's prompt and new tokens.  On
+        an empty decoder it is a plain ``generate``.  ``prefill_chunk``: see ``prefill``.  On a decoder built with ``sampling=True``:
         ``do_sample`` draws every token by temperature / top-k / top-p sampling (``seed``: the 64-bit Philox key; token i of
         row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
         finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on."""
         B, P = prompt.shape
-        if B != self.batch or P + new_tokens > self.max_len:
+        append = bool(append) and (self.rows > 0 or self._pending)
+        feed = torch.cat([self.s_tok, prompt], dim=1) if append and self._pending else prompt
+        start = self.rows if append else 0
+        fed = start + feed.shape[1]                      # cache rows once the prompt is in
+        if B != self.batch or fed + new_tokens > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))
         if not self.sampling:
             if (do_sample or temperature != 1.0 or top_k != 0 or top_p != 1.0 or seed != 0 or eos_token_id is not None
                     or pad_token_id is not None):
                 raise ValueError("GraphDecoder: sampling and EOS arguments need a decoder built with sampling=True")
-            out = self.prefill(prompt)
+            out = self.prefill(feed, chunk=prefill_chunk, append=append)
             tok = out.logits[:, -1].argmax(-1, keepdim=True)
             self.out_buf[:, :1].copy_(tok)
             self.s_tok.copy_(tok)
-            self.s_pos.fill_(P)
+            self.s_pos.fill_(fed)
             self.s_idx.fill_(1)
         else:
             from .. import ops
@@ -166,9 +178,9 @@ class GraphDecoder:
             sampling_params(temperature=float(temperature) if do_sample else 0.0, top_k=top_k, top_p=top_p, seed=seed,
                             eos_token_id=eos_token_id, pad_token_id=0 if pad_token_id is None else pad_token_id, out=self.params)
             self.done.zero_()
-            out = self.prefill(prompt)
-            # the first token: the same op on the prompt's logits at column 0 (it leaves position = P, column = 1)
-            self.s_pos.fill_(P - 1)
+            out = self.prefill(feed, chunk=prefill_chunk, append=append)
+            # the first token: the same op on the prompt's logits at column 0 (it leaves position = rows fed, column = 1)
+            self.s_pos.fill_(fed - 1)
             self.s_idx.fill_(0)
             last = out.logits[:, -1]
             ops.sample_handover(last if last.stride(-1) == 1 else last.contiguous(), self.out_buf, self.s_idx, self.s_tok, self.s_pos, self.params,
@@ -184,26 +196,48 @@ class GraphDecoder:
             else:
                 self._advance()
                 left -= 1
+        if new_tokens >= 1:   # every emitted token but the last has been fed back and cached
+            self.rows, self._pending = fed + new_tokens - 1, True
         tokens = torch.cat([prompt, self.out_buf[:, :new_tokens]], dim=1)
         return (tokens, out.logits[:, -1]) if return_prefill_logits else tokens
 
-    def prefill(self, prompt):
-        """Empty the cache and run the (unpadded) prompt [batch, P] eagerly; returns the model output, whose logits hold the LAST
-        position only where the model's forward can be told so."""
+    def prefill(self, prompt, chunk=None, append=False):
+        """Run the (unpadded) prompt [batch, P] eagerly; returns the model output of the last piece, whose logits hold the LAST
+        position only where the model's forward can be told so.  By default the cache is emptied first.  ``chunk=c``: the
+        prompt runs in pieces of at most ``c`` tokens, each behind the rows already written (activations are [batch, c, .]
+        instead of [batch, P, .]).  ``append=True``: the prompt starts behind the rows the cache holds (``self.rows``) instead
+        of emptying it.  Accelerated models attend the first piece of an emptied cache under ``fresh_static_prefill`` and every
+        other piece under ``appended_static_prefill``; other models run the same calls on their stock path."""
         P = prompt.shape[1]
+        start = self.rows if append else 0
+        if start + P > self.max_len:
+            raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError("GraphDecoder: chunk must be at least 1")
+        step = P if chunk is None else int(chunk)
         fresh = self._fresh_prefill_ok()
-        if fresh:
-            # every layer is an accelerated block on an initialised static cache: only the token counters are reset (the model
-            # derives the prompt's positions from them; the blocks never read a row at or beyond the counter, so the stock
-            # reset's zero-fill of 2 x layers cache tensors buys nothing), and the prompt is attended causally over its own
-            # rows (llama_modules.fresh_static_prefill)
-            torch._foreach_zero_([layer.cumulative_length for layer in self.cache.layers])   # one launch for all layers
-            from ..modules.llama_modules import fresh_static_prefill
-            ctx = fresh_static_prefill()
-        else:
-            self.cache.reset()
-            ctx = contextlib.nullcontext()
-        with ctx:
-            out = self.model(prompt, past_key_values=self.cache, cache_position=torch.arange(P, device=prompt.device),
-                             use_cache=True, **self._last_logits_only)
+        from ..modules.llama_modules import appended_static_prefill, fresh_static_prefill
+        if not append:
+            if fresh:
+                # every layer is an accelerated block on an initialised static cache: only the token counters are reset (the model
+                # derives the prompt's positions from them; the blocks never read a row at or beyond the counter, so the stock
+                # reset's zero-fill of 2 x layers cache tensors buys nothing), and the prompt is attended causally over its own
+                # rows (llama_modules.fresh_static_prefill)
+                torch._foreach_zero_([layer.cumulative_length for layer in self.cache.layers])   # one launch for all layers
+            else:
+                self.cache.reset()
+        out = None
+        for c0 in range(0, P, step):
+            c1 = min(P, c0 + step)
+            if not fresh:
+                ctx = contextlib.nullcontext()
+            elif c0 == 0 and not append:
+                ctx = fresh_static_prefill()
+            else:   # behind rows 0 .. start + c0 - 1, which are this sequence's tokens (llama_modules.appended_static_prefill)
+                ctx = appended_static_prefill()
+            with ctx:
+                out = self.model(prompt[:, c0:c1], past_key_values=self.cache,
+                                 cache_position=torch.arange(start + c0, start + c1, device=prompt.device), use_cache=True,
+                                 **self._last_logits_only)
+        self.rows, self._pending = start + P, False
         return out

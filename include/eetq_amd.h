@@ -604,6 +604,34 @@ int eetq_prefill_attention_f16(const void* q, const void* k, const void* v, void
                                int keys, int head_dim, int causal_offset, float scaling, const long* strides, void* stream);
 int eetq_prefill_attention_supported(int head_dim);
 
+/* ... with the number of keys read on the DEVICE, and optionally split over the keys (added within ABI revision 7).  Every workgroup
+ * reads *kv_len (DEVICE int64 scalar) at entry and attends keys = clamp(*kv_len + kv_len_bias, 0, max_keys) cache rows with
+ * causal_offset = keys - q_tokens: a prompt appended behind the rows a static cache already holds, its counter already advanced.  Per
+ * query row the arithmetic is that of eetq_prefill_attention_f16 with the same keys, bit for bit; keys <= 0 gives zeros.  Nothing is read
+ * on the host: the call can be captured.  kv_len NULL: keys = max_keys (the split form with a host length).  strides as above; the
+ * 2 GiB range rule is checked against max_keys.
+ * splits == 1: one launch, workspace may be NULL.  splits in 2 .. eetq_prefill_attention_max_splits() (16): each (query block, head,
+ * batch row) becomes `splits` workgroups, share i taking the key blocks [i n / splits, (i + 1) n / splits) of that workgroup's n
+ * blocks of 64 keys; every share leaves its unnormalised fp32 accumulators and (maximum, sum) per query row in `workspace` -- an
+ * empty share (-inf, 0, zeros), so the workspace's previous contents never matter -- and a second launch merges them (weights
+ * exp2(m_i - max m), one division).  No atomics, no tickets; deterministic.  workspace: DEVICE,
+ * eetq_prefill_attention_workspace_floats(batch, heads, q_tokens, head_dim, splits) = batch * heads * q_tokens * splits *
+ * (head_dim + 2) floats, 16-byte aligned; launches that may run concurrently need distinct workspaces.
+ * EETQ_ERR_INVALID: null q / k / v / out / strides, max_keys <= 0, splits < 1 or > 16, splits > 1 with a NULL or misaligned
+ * workspace, the stride and alignment rules above; EETQ_ERR_UNSUPPORTED: head_dim. */
+int eetq_prefill_attention_dev_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                   int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                   int splits, float scaling, const long* strides, void* stream);
+/* The split count eetq_prefill_attention_dev_f16 is tuned for (pure host function; callers size the workspace with it; 1 = unsplit).
+ * With g = ceil(q_tokens / 128) * heads * batch workgroups and n = ceil(max_keys / 64) key blocks: the largest power of two s <= 16
+ * such that, for every power of two s' <= s, s' g <= 1.25 compute units and n / s' >= 4 (s' g <= half the compute units), 8 (s' g <=
+ * all of them) or 16 (beyond).  1 wherever g alone fills the chip.  Measured at 40 x 128 and 32 / 8 x 128 heads
+ * (tools/prefill_attn_bench.py --append, profiles/prefill_attn_append.txt): more than 1 only where the split form beat the unsplit
+ * host-length call. */
+int    eetq_prefill_attention_splits(int batch, int heads, int q_tokens, int max_keys);
+int    eetq_prefill_attention_max_splits(void);
+size_t eetq_prefill_attention_workspace_floats(int batch, int heads, int q_tokens, int head_dim, int splits);
+
 /* Diagnostics: while `stamps` (DEVICE, batch * heads * splits * 8 uint64) is set, every eetq_rope_decode_attention_f16
  * launch of this process records per workgroup the 100 MHz device clock at: 0 entry, 1 scalar reads done, 2 new token
  * rotated, 3 chunk done, 4 chunk record published, 5 ticket drawn, 6 (last workgroup of a head) merge done, 7 output
