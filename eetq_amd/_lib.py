@@ -84,6 +84,12 @@ def _declare(L):
                                                          i32, vp],
         "eetq_rope_decode_attention_bounded_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
                                                    i32, ctypes.c_float, vp, vp, i32, vp, vp],
+        "eetq_decode_attention_i8kv_f16": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, vp, i32,
+                                           vp, vp],
+        "eetq_rope_decode_attention_i8kv_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
+                                                i32, i32, ctypes.c_float, vp, vp, vp, i32, vp, vp],
+        "eetq_rotary_neox_kvcache_prefill_i8_f16": [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp,
+                                                    vp, i32, vp],
         "eetq_w8a16_gemv_grouped": [vp, i32, vp],
         "eetq_decode_dropped_steps": [vp, i32],
         "eetq_rotary_neox_strided_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
@@ -172,6 +178,7 @@ EXPORTED_SYMBOLS = (
     "eetq_rotary_neox_kvcache_prefill_bounded_f16", "eetq_rope_decode_attention_bounded_f16",
     "eetq_prefill_attention_dev_f16", "eetq_prefill_attention_splits", "eetq_prefill_attention_max_splits",
     "eetq_prefill_attention_workspace_floats",
+    "eetq_decode_attention_i8kv_f16", "eetq_rope_decode_attention_i8kv_f16", "eetq_rotary_neox_kvcache_prefill_i8_f16",
 )
 
 

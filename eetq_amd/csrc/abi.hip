@@ -16,6 +16,7 @@ namespace eetq {
 // dropped-step counters of the decode kernels (attn_decode.hip, norm_rope.hip)
 int attn_dropped_steps(unsigned* count, bool reset);
 int rope_dropped_steps(unsigned* count, bool reset);
+int attn_i8_dropped_steps(unsigned* count, bool reset);
 
 namespace {
 thread_local std::string g_last_error;
@@ -925,7 +926,10 @@ int eetq_decode_dropped_steps(unsigned long long* count, int reset)
     if (st != EETQ_OK) return st;
     st = rope_dropped_steps(&r, reset != 0);
     if (st != EETQ_OK) return st;
-    *count = (unsigned long long)a + r;
+    unsigned a8 = 0;
+    st = attn_i8_dropped_steps(&a8, reset != 0);
+    if (st != EETQ_OK) return st;
+    *count = (unsigned long long)a + r + a8;
     return EETQ_OK;
 }
 
@@ -963,6 +967,48 @@ int eetq_decode_attention_f16(const void* q, const void* k_cache, const void* v_
                               static_cast<const f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
                               workspace, batch, heads, kv_heads, positions, head_dim, splits, scaling, strides, kv_len,
                               kv_len_bias, advance, static_cast<hipStream_t>(stream));
+}
+
+int eetq_decode_attention_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales,
+                                   const void* mask, void* out, float* workspace, int batch, int heads, int kv_heads, int positions,
+                                   int head_dim, int splits, float scaling, const long* strides, const long* scale_strides,
+                                   const int64_t* kv_len, int kv_len_bias, int64_t* advance, void* stream)
+{
+    return launch_attn_decode_i8(static_cast<const f16*>(q), static_cast<const int8_t*>(k_cache_i8),
+                                 static_cast<const int8_t*>(v_cache_i8), static_cast<const f16*>(kv_scales),
+                                 static_cast<const f16*>(mask), static_cast<f16*>(out), workspace, batch, heads, kv_heads, positions,
+                                 head_dim, splits, scaling, strides, scale_strides, kv_len, kv_len_bias, advance,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int eetq_rope_decode_attention_i8kv_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                        const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                        void* k_cache_i8, void* v_cache_i8, void* kv_scales, const void* mask, void* out,
+                                        float* workspace, unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                        int head_dim, int splits, float scaling, const long* strides, const long* scale_strides,
+                                        const int64_t* kv_len, int kv_len_bias, int64_t* advance, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return launch_rope_attn_decode_i8(positions, slots, slot_stride, static_cast<const f16*>(query), static_cast<const f16*>(key),
+                                      static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
+                                      static_cast<int8_t*>(k_cache_i8), static_cast<int8_t*>(v_cache_i8),
+                                      static_cast<f16*>(kv_scales), static_cast<const f16*>(mask), static_cast<f16*>(out), workspace,
+                                      tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling, strides,
+                                      scale_strides, kv_len, kv_len_bias, advance, table_rows, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rotary_neox_kvcache_prefill_i8_f16(const int64_t* positions, void* query, void* key, const void* value,
+                                            const void* cos_sin_cache, int table_rows, void* k_cache_i8, void* v_cache_i8,
+                                            void* kv_scales, int batch, int tokens, const int64_t* first_row_dev, int first_row,
+                                            int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                            const long* scale_strides, int max_positions, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return launch_rotary_kvcache_i8(positions, first_row_dev, static_cast<f16*>(query), static_cast<f16*>(key),
+                                    static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
+                                    static_cast<int8_t*>(k_cache_i8), static_cast<int8_t*>(v_cache_i8), static_cast<f16*>(kv_scales),
+                                    batch, tokens, first_row, q_heads, k_heads, head_size, rot_dim, strides, scale_strides,
+                                    max_positions, table_rows, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -345,6 +345,21 @@ int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_str
                           long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream, int tokens = 0,
                           int first_row = 0);  // tokens > 0: the prefill form (batch * tokens blocks, rows first_row + t)
 
+// the int8 KV cache (kv_i8.hpp): decode attention over int8 rows (attn_decode_i8.hip; strides as the fp16 launchers' with the cache
+// strides in bytes, scale_strides {batch, head, row} in fp16 elements) and the quantising prompt / single-token write (norm_rope.hip)
+int launch_attn_decode_i8(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, const f16* mask, f16* out, float* ws,
+                          int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* strides,
+                          const long* scale_strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance, hipStream_t stream);
+int launch_rope_attn_decode_i8(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                               const f16* v, const f16* cos_sin, int8_t* kc, int8_t* vc, f16* scales, const f16* mask, f16* out,
+                               float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                               const long* st, const long* scale_strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance,
+                               long table_rows, hipStream_t stream);
+int launch_rotary_kvcache_i8(const int64_t* pos, const int64_t* first_row_dev, f16* q, f16* k, const f16* v, const f16* cache,
+                             int8_t* kcache, int8_t* vcache, f16* scales, int batch, int tokens, int first_row, int q_heads,
+                             int k_heads, int head_size, int rot_dim, const long* st, const long* sst, int max_pos, long table_rows,
+                             hipStream_t stream);
+
 int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t stream, bool glu8 = false);
 
 // compute units of the current device (cached per device); 256 on MI355X

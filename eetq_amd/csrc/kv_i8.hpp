@@ -1,0 +1,50 @@
+// The int8 KV-cache row format: one row = the D fp16 values of one (batch row, kv head, position), quantised
+// symmetrically with a scale of its own.
+//   amax = max |x_d|                                   (exact)
+//   s    = fp16(fp32(amax) * (1.0f / 127.0f))           one fp32 multiply, round to nearest even
+//   q_d  = clamp(round_half_away(fp32(x_d) / fp32(s)), -127, 127)   IEEE fp32 divide (the Makefile asks for it); s == 0 -> 0
+// bytes are plain two's complement; -128 is never written.  Shared by the writers (norm_rope.hip, attn_decode_i8.hip) so that
+// every path to a cache row produces the same bits, and by the reader for the way back.
+#pragma once
+#include "common.hpp"
+
+namespace eetq {
+
+__device__ __forceinline__ float kv8_abs_max8(const f16x8& x)
+{
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a = fmaxf(a, fabsf((float)x[i]));
+    return a;
+}
+
+__device__ __forceinline__ f16 kv8_scale(float amax) { return (f16)(amax * (1.0f / 127.0f)); }
+
+// this lane's 8 channels -> 8 bytes (channel i in byte i)
+__device__ __forceinline__ u32x2 kv8_quant8(const f16x8& x, f16 scale)
+{
+    const float s = (float)scale;
+    u32         w[2] = {0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float r = s != 0.f ? __builtin_roundf((float)x[i] / s) : 0.f;
+        r       = fminf(fmaxf(r, -127.f), 127.f);
+        w[i >> 2] |= ((u32)(int)r & 0xffu) << (8 * (i & 3));
+    }
+    return u32x2{w[0], w[1]};
+}
+
+// 8 bytes -> the exact integers as fp16 pairs (0, 1) (2, 3) (4, 5) (6, 7): the biased-byte trick of the weight kernels
+// (dequant_dword) with one xor per dword to get from two's complement to q + 128
+__device__ __forceinline__ void kv8_unpack8(const u32x2& w, f16x2 (&h)[4])
+{
+    const u32   c64  = 0x64646464u;
+    const f16x2 bias = {(f16)1152.0f, (f16)1152.0f};
+    const u32   x0 = w.x ^ 0x80808080u, x1 = w.y ^ 0x80808080u;
+    h[0] = as_f16x2(__builtin_amdgcn_perm(x0, c64, 0x00050004u)) - bias;  // bytes [b0, 0x64, b1, 0x64]
+    h[1] = as_f16x2(__builtin_amdgcn_perm(x0, c64, 0x00070006u)) - bias;  // bytes [b2, 0x64, b3, 0x64]
+    h[2] = as_f16x2(__builtin_amdgcn_perm(x1, c64, 0x00050004u)) - bias;
+    h[3] = as_f16x2(__builtin_amdgcn_perm(x1, c64, 0x00070006u)) - bias;
+}
+
+}  // namespace eetq

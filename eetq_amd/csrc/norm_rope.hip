@@ -6,6 +6,7 @@
 //             pos_encoding_kernels.cu:12-53) for fp16: in-place NeoX rotation, fp16 arithmetic with a
 //             rounding after every multiply/add exactly like the half operators there.
 #include "common.hpp"
+#include "kv_i8.hpp"
 
 namespace eetq {
 // tokens dropped by rotary_neox_kvcache_kernel (cache row outside the cache, position outside the cos|sin table) and tokens
@@ -238,6 +239,88 @@ __global__ void rotary_neox_kvcache_kernel(const int64_t* __restrict__ positions
     }
 }
 
+// max over the G (a power of two <= 64) consecutive lanes of an aligned group
+template <int G>
+__device__ __forceinline__ float lanes_max(float v)
+{
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// The prefill form of rotary_neox_kvcache_kernel<true> for an int8 cache (kv_i8.hpp): the same 16-byte accesses, 8 channels
+// per thread and fp16 rotation, with three differences.  K is rotated IN PLACE (the prompt then attends the rotated fp16 K
+// where it lies in the projection output); the rotated K and the V of a (token, kv head) are quantised with a scale of their
+// own -- the absmax is a reduction over the head's threads, D/16 for K (a thread holds a channel and its partner), D/8 for
+// V -- and written as bytes to kcache / vcache [b][head][row][D] and as fp16 to scales [b][head][row][2] = (k scale, v scale).
+// Rows base + t, base = *slots or first_row; tokens = 1 with slots = the cache's counter is the unfused decode step.
+// Dropped tokens (row outside the cache, position outside the table) are left as they are, and counted.
+template <int D>
+__global__ __launch_bounds__(256) void rotary_neox_kvcache_i8_kernel(const int64_t* __restrict__ positions, const int64_t* __restrict__ slots,
+                                                                     f16* __restrict__ query, f16* __restrict__ key,
+                                                                     const f16* __restrict__ value, const f16* __restrict__ cache,
+                                                                     int8_t* __restrict__ kcache, int8_t* __restrict__ vcache,
+                                                                     f16* __restrict__ scales, long q_stride, long k_stride,
+                                                                     long v_stride, long c_sb, long c_sh, long c_ss, long s_sb,
+                                                                     long s_sh, long s_ss, int q_heads, int k_heads, int max_pos,
+                                                                     int tokens, int first_row, int64_t table_rows)
+{
+#pragma clang fp contract(off)
+    constexpr int embed = D / 2, e8 = embed / 8, h8 = D / 8;
+    const int     b    = blockIdx.x;
+    const int     cb   = b / tokens;
+    const int64_t rpos = positions[b];
+    const int64_t pos  = (slots ? slots[0] : (int64_t)first_row) + (b - cb * tokens);
+    if (pos < 0 || pos >= max_pos || rpos < 0 || rpos >= table_rows) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&g_rope_dropped, 1u);
+        return;
+    }
+    const f16* cp = cache + rpos * D;
+    auto rot8 = [&](const f16* src, int off, f16x8& lo, f16x8& hi) {
+        const f16x8 c = *reinterpret_cast<const f16x8*>(cp + off), sn = *reinterpret_cast<const f16x8*>(cp + embed + off);
+        const f16x8 vx = *reinterpret_cast<const f16x8*>(src + off), vy = *reinterpret_cast<const f16x8*>(src + embed + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f16 xc = vx[j] * c[j], ys = vy[j] * sn[j], yc = vy[j] * c[j], xs = vx[j] * sn[j];
+            lo[j] = xc - ys;
+            hi[j] = yc + xs;
+        }
+    };
+    if (blockIdx.y == 0) {
+        for (int i = threadIdx.x; i < q_heads * e8; i += blockDim.x) {
+            const int head = i / e8, off = (i - head * e8) * 8;
+            f16*      p = query + b * q_stride + (long)head * D;
+            f16x8     lo, hi;
+            rot8(p, off, lo, hi);
+            *reinterpret_cast<f16x8*>(p + off)         = lo;
+            *reinterpret_cast<f16x8*>(p + embed + off) = hi;
+        }
+    } else if (blockIdx.y == 1) {
+        // (a head's e8 threads are consecutive lanes of one wave and enter the loop together)
+        for (int i = threadIdx.x; i < k_heads * e8; i += blockDim.x) {
+            const int head = i / e8, off = (i - head * e8) * 8;
+            f16*      p = key + b * k_stride + (long)head * D;
+            f16x8     lo, hi;
+            rot8(p, off, lo, hi);
+            *reinterpret_cast<f16x8*>(p + off)         = lo;
+            *reinterpret_cast<f16x8*>(p + embed + off) = hi;
+            const f16 s = kv8_scale(lanes_max<e8>(fmaxf(kv8_abs_max8(lo), kv8_abs_max8(hi))));
+            int8_t*   d = kcache + cb * c_sb + head * c_sh + pos * c_ss;
+            *reinterpret_cast<u32x2*>(d + off)         = kv8_quant8(lo, s);
+            *reinterpret_cast<u32x2*>(d + embed + off) = kv8_quant8(hi, s);
+            if (off == 0) scales[cb * s_sb + head * s_sh + pos * s_ss] = s;
+        }
+    } else {
+        for (int i = threadIdx.x; i < k_heads * h8; i += blockDim.x) {
+            const int   head = i / h8, off = (i - head * h8) * 8;
+            const f16x8 x = *reinterpret_cast<const f16x8*>(value + b * v_stride + (long)head * D + off);
+            const f16   s = kv8_scale(lanes_max<h8>(kv8_abs_max8(x)));
+            *reinterpret_cast<u32x2*>(vcache + cb * c_sb + head * c_sh + pos * c_ss + off) = kv8_quant8(x, s);
+            if (off == 0) scales[cb * s_sb + head * s_sh + pos * s_ss + 1] = s;
+        }
+    }
+}
+
 // Greedy decode hand-over (extension for the HIP-graph decoder, utils/graph_decoder.py): per batch row the index of the row's
 // maximum logit -- the FIRST one on ties, a NaN counts as the maximum, like torch.argmax -- written to out_buf[b][*s_idx] and to
 // s_tok[b]; then *s_pos += 1 and *s_idx += 1.  ONE workgroup walks the rows (batch is small), so the column is read before anyone
@@ -333,6 +416,39 @@ int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_str
                                                                                 rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss,
                                                                                 q_heads, k_heads, head_size, max_pos, tokens, first_row, (int64_t)table_rows);
     return check_hip(hipGetLastError(), "rotary_neox_kvcache_kernel launch");
+}
+
+int launch_rotary_kvcache_i8(const int64_t* pos, const int64_t* first_row_dev, f16* q, f16* k, const f16* v, const f16* cache,
+                             int8_t* kcache, int8_t* vcache, f16* scales, int batch, int tokens, int first_row, int q_heads,
+                             int k_heads, int head_size, int rot_dim, const long* st, const long* sst, int max_pos, long table_rows,
+                             hipStream_t stream)
+{
+    EETQ_REQUIRE(pos && q && k && v && cache && kcache && vcache && scales && st && sst, "null pointer");
+    EETQ_REQUIRE(batch >= 0 && tokens >= 0 && q_heads > 0 && k_heads > 0 && head_size > 0 && max_pos > 0, "invalid rotary shape");
+    EETQ_REQUIRE(first_row >= 0 && (first_row_dev || (long)first_row + tokens <= max_pos), "the prefill rows must lie inside the cache");
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    EETQ_REQUIRE((long)batch * tokens < (1L << 31), "too many tokens for one launch");
+    EETQ_REQUIRE(rot_dim == head_size, "the int8 cache write needs the rotation to cover the whole head (rot_dim == head_size)");
+    if (head_size != 64 && head_size != 128)
+        return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] the int8 cache write supports head_size 64 and 128");
+    EETQ_REQUIRE(((st[0] | st[1] | st[2]) & 7) == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cache) & 15) == 0,
+                 "q / k / v token strides must be multiples of 8 elements and q, k, v, the cos|sin table 16-byte aligned");
+    EETQ_REQUIRE(((st[3] | st[4] | st[5]) & 7) == 0 && (((uintptr_t)kcache | (uintptr_t)vcache) & 7) == 0,
+                 "int8 cache strides must be multiples of 8 bytes and the caches 8-byte aligned (8-byte accesses)");
+    EETQ_REQUIRE(((sst[0] | sst[1] | sst[2]) & 1) == 0 && ((uintptr_t)scales & 3) == 0,
+                 "the scale strides must be multiples of 2 elements and the scales 4-byte aligned (one dword per row)");
+    EETQ_REQUIRE(st[5] > 0 && sst[2] > 0 && ((long)max_pos + 4096) * st[5] < (1L << 31) && ((long)max_pos + 4096) * sst[2] * 2 < (1L << 31),
+                 "one head's cache rows must span less than 2 GiB");
+    if (batch == 0 || tokens == 0) return EETQ_OK;
+    const dim3 grid(batch * tokens, 3);
+#define EETQ_ROPE8_GO(D)                                                                                                            \
+    rotary_neox_kvcache_i8_kernel<D><<<grid, 256, 0, stream>>>(pos, first_row_dev, q, k, v, cache, kcache, vcache, scales, st[0], st[1], \
+                                                               st[2], st[3], st[4], st[5], sst[0], sst[1], sst[2], q_heads, k_heads, \
+                                                               max_pos, tokens, first_row, (int64_t)table_rows)
+    if (head_size == 128) EETQ_ROPE8_GO(128);
+    else EETQ_ROPE8_GO(64);
+#undef EETQ_ROPE8_GO
+    return check_hip(hipGetLastError(), "rotary_neox_kvcache_i8_kernel launch");
 }
 
 int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t stream, bool glu8)

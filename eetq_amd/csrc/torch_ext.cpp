@@ -859,6 +859,170 @@ Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tens
     return out;
 }
 
+// ---- the int8 KV cache (include/eetq_amd.h "The int8 KV cache"): caches int8 [B, Hkv, S, D], scales fp16 [B, Hkv, S, 2] -------------
+static void check_i8_cache(const char* name, const Tensor& query, const Tensor& key_cache, const Tensor& value_cache,
+                           const Tensor& scales, int64_t B, int64_t Hkv, int64_t D)
+{
+    TORCH_CHECK(key_cache.scalar_type() == at::kChar && value_cache.scalar_type() == at::kChar && scales.scalar_type() == at::kHalf,
+                name, "the caches must be int8 and the scales float16");
+    TORCH_CHECK(key_cache.dim() == 4 && value_cache.sizes() == key_cache.sizes() && scales.dim() == 4, name,
+                "expected caches [B, Hkv, S, D] and scales [B, Hkv, S, 2]");
+    TORCH_CHECK(key_cache.size(0) == B && key_cache.size(1) == Hkv && key_cache.size(3) == D && scales.size(0) == B &&
+                    scales.size(1) == Hkv && scales.size(2) == key_cache.size(2) && scales.size(3) == 2,
+                name, "shape mismatch");
+    TORCH_CHECK(key_cache.stride(-1) == 1 && value_cache.stride(-1) == 1 && scales.stride(-1) == 1, name,
+                "cache rows and scale pairs must be dense");
+    TORCH_CHECK(key_cache.device() == query.device() && value_cache.device() == query.device() && scales.device() == query.device(),
+                name, "all tensors must be on one device");
+}
+
+Tensor decode_attention_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
+                             const OptTensor& mask, std::optional<double> scaling, std::optional<int64_t> splits_in,
+                             const OptTensor& kv_len, int64_t kv_len_bias, const OptTensor& advance)
+{
+    const char* name = "decode_attention_i8kv: ";
+    TORCH_CHECK(query.scalar_type() == at::kHalf && query.dim() == 3 && query.stride(-1) == 1 && key_cache.dim() == 4, name,
+                "expected a float16 query [B, H, D] with dense D");
+    const int64_t B = query.size(0), H = query.size(1), D = query.size(2);
+    const int64_t Hkv = key_cache.size(1), S = key_cache.size(2);
+    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, name, "shape mismatch");
+    Tensor  mrow;
+    int64_t m_sb = 0;
+    if (mask) {
+        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
+        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
+                    name, "mask must be additive float16 with a dense last dimension >= S");
+        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B, name, "the mask needs one row per batch entry (or a single shared row)");
+        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
+    }
+    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
+        if (*t)
+            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(), name,
+                        "kv_len / advance must be a one-element int64 tensor on the query's device");
+    const double sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
+    int64_t      splits = splits_in ? *splits_in : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
+    Tensor       out    = torch::empty({B, H, D}, query.options());
+    Tensor       ws     = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
+    const long   strides[11] = {(long)query.stride(0),       (long)query.stride(1),       (long)key_cache.stride(0),
+                                (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
+                                (long)value_cache.stride(1), (long)value_cache.stride(2), (long)m_sb,
+                                (long)out.stride(0),         (long)out.stride(1)};
+    const long   sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_decode_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
+                                         mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
+                                         (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides, sst,
+                                         kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
+                                         advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
+    return out;
+}
+
+Tensor rope_decode_attention_i8kv(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
+                                  const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& scales,
+                                  Tensor& tickets, const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
+                                  std::optional<int64_t> splits_in, const OptTensor& kv_len, int64_t kv_len_bias,
+                                  const OptTensor& advance)
+{
+    const char* name = "rope_decode_attention_i8kv: ";
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache})
+        TORCH_CHECK(t->scalar_type() == at::kHalf, name, "float16 query, key, value and cos|sin table expected");
+    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous(), name, "positions must be contiguous int64");
+    TORCH_CHECK(query.dim() == 3 && key.dim() == 3 && value.dim() == 3 && key_cache.dim() == 4, name,
+                "expected query [B, H, D], key / value [B, Hkv, D], caches [B, Hkv, S, D]");
+    const int64_t B = query.size(0), H = query.size(1), D = query.size(2), Hkv = key.size(1), S = key_cache.size(2);
+    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(key.size(0) == B && key.size(2) == D && value.sizes() == key.sizes() && Hkv > 0 && H % Hkv == 0 &&
+                    positions.numel() == B,
+                name, "shape mismatch");
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D, name, "[heads, head_size] must be dense");
+    TORCH_CHECK(cos_sin_cache.is_contiguous() && cos_sin_cache.size(-1) == D, name,
+                "the rotation must cover the whole head (rot_dim == D)");
+    TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.is_contiguous() && tickets.numel() >= B * H + 1 &&
+                    tickets.device() == query.device(),
+                name, "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device");
+    int slot_stride = 0;
+    if (slots) {
+        const Tensor& s = *slots;
+        TORCH_CHECK(s.scalar_type() == at::kLong && s.device() == query.device() && (s.numel() == 1 || s.numel() == B) &&
+                        s.is_contiguous(),
+                    name, "slots must be contiguous int64 on the device, 1 or B elements");
+        slot_stride = (s.numel() == B && B > 1) ? 1 : 0;
+    }
+    Tensor  mrow;
+    int64_t m_sb = 0;
+    if (mask) {
+        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
+        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
+                    name, "mask must be additive float16 with a dense last dimension >= S");
+        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B, name, "the mask needs one row per batch entry (or a single shared row)");
+        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
+    }
+    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
+        if (*t)
+            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(), name,
+                        "kv_len / advance must be a one-element int64 tensor on the query's device");
+    const double sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
+    int64_t      splits = splits_in ? *splits_in : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
+    Tensor       out    = torch::empty({B, H, D}, query.options());
+    Tensor       ws     = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
+    const long   strides[12] = {(long)query.stride(0),       (long)key.stride(0),         (long)value.stride(0),
+                                (long)key_cache.stride(0),   (long)key_cache.stride(1),   (long)key_cache.stride(2),
+                                (long)value_cache.stride(0), (long)value_cache.stride(1), (long)value_cache.stride(2),
+                                (long)m_sb,                  (long)out.stride(0),         (long)out.stride(1)};
+    const long   sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_rope_decode_attention_i8kv_f16(
+        positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(), key.data_ptr(),
+        value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(),
+        scales.data_ptr(), mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
+        reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc,
+        strides, sst, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
+        advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
+    return out;
+}
+
+// rotary_embedding_neox_kvcache_prefill writing an int8 cache; key is rotated in place as well
+// (eetq_rotary_neox_kvcache_prefill_i8_f16)
+void rotary_embedding_neox_kvcache_prefill_i8(const Tensor& positions, Tensor& query, Tensor& key, const Tensor& value,
+                                              int64_t head_size, const Tensor& cos_sin_cache, Tensor& key_cache,
+                                              Tensor& value_cache, Tensor& scales, int64_t first_row, const OptTensor& first_row_dev)
+{
+    const char* name = "rotary_embedding_neox_kvcache_prefill_i8: ";
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache}) {
+        TORCH_CHECK(t->scalar_type() == at::kHalf, name, "float16 query, key, value and cos|sin table expected");
+        TORCH_CHECK(t->is_cuda() && t->device() == query.device(), name, "all tensors must be on one CUDA device");
+    }
+    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous() && positions.device() == query.device(), name,
+                "positions must be contiguous int64 on the device");
+    TORCH_CHECK(query.dim() == 4 && key.dim() == 4 && value.dim() == 4 && key_cache.dim() == 4, name, "shape mismatch");
+    const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(2);
+    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(key.size(0) == B && key.size(1) == T && key.size(3) == D && value.sizes() == key.sizes() && D == head_size &&
+                    value_cache.strides() == key_cache.strides() && positions.numel() == B * T && first_row >= 0 &&
+                    (first_row_dev || first_row + T <= key_cache.size(2)),
+                name, "shape mismatch");
+    if (first_row_dev)
+        TORCH_CHECK(first_row_dev->scalar_type() == at::kLong && first_row_dev->numel() == 1 &&
+                        first_row_dev->device() == query.device(),
+                    name, "first_row_dev must be one int64 on the device");
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D && (B == 1 || T == 1 || t->stride(0) == T * t->stride(1)), name,
+                    "[heads, head_size] must be dense and the tokens of all rows one stride apart");
+    const int tdim = T == 1 ? 0 : 1;  // (a size-1 dimension's stride is arbitrary)
+    TORCH_CHECK(cos_sin_cache.is_contiguous(), name, "the cos|sin table must be contiguous");
+    const long strides[6] = {(long)query.stride(tdim), (long)key.stride(tdim), (long)value.stride(tdim), (long)key_cache.stride(0),
+                             (long)key_cache.stride(1), (long)key_cache.stride(2)};
+    const long sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_rotary_neox_kvcache_prefill_i8_f16(
+        positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
+        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), (int)B, (int)T,
+        first_row_dev ? first_row_dev->data_ptr<int64_t>() : nullptr, (int)first_row, (int)H, (int)Hkv, (int)head_size,
+        (int)cos_sin_cache.size(1), strides, sst, (int)key_cache.size(2), stream_of(query)));
+}
+
 Tensor silu_mul(const Tensor& gate_up, bool glu8)
 {
     TORCH_CHECK(gate_up.scalar_type() == at::kHalf && gate_up.is_cuda() && gate_up.is_contiguous(),
@@ -1721,6 +1885,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
           py::arg("advance") = py::none());
+    m.def("decode_attention_i8kv", &decode_attention_i8kv, "single-query attention over an int8 KV cache", py::arg("query"),
+          py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"), py::arg("mask") = py::none(),
+          py::arg("scaling") = py::none(), py::arg("splits") = py::none(), py::arg("kv_len") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("advance") = py::none());
+    m.def("rope_decode_attention_i8kv", &rope_decode_attention_i8kv, py::arg("positions"), py::arg("query"), py::arg("key"),
+          py::arg("value"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"),
+          py::arg("tickets"), py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
+          py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
+          py::arg("advance") = py::none());
+    m.def("rotary_embedding_neox_kvcache_prefill_i8", &rotary_embedding_neox_kvcache_prefill_i8,
+          "prompt rotary (query and key in place) + quantising int8 KV-cache write", py::arg("positions"), py::arg("query"),
+          py::arg("key"), py::arg("value"), py::arg("head_size"), py::arg("cos_sin_cache"), py::arg("key_cache"),
+          py::arg("value_cache"), py::arg("scales"), py::arg("first_row") = 0, py::arg("first_row_dev") = py::none());
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),

@@ -140,6 +140,70 @@ class _EETAttentionBase(nn.Module):
             return None
         return layer
 
+    def _int8_cache_layer(self, past_key_values):
+        """The ``Int8StaticLayer`` (utils/kv_cache.py) of this block, or None when the cache is of another kind.  (Such a layer
+        never passes ``_static_cache_layer``: no fp16 path can touch int8 bytes by accident.)"""
+        layers = getattr(past_key_values, "layers", None)
+        if layers is None or self.layer_idx >= len(layers):
+            return None
+        layer = layers[self.layer_idx]
+        if type(layer).__name__ != "Int8StaticLayer":
+            return None
+        if (not getattr(layer, "is_initialized", False) or layer.keys.dtype != torch.int8 or layer.keys.dim() != 4
+                or getattr(layer, "scales", None) is None):
+            raise RuntimeError("EETLlamaAttention: the int8 cache layer is not allocated (Int8StaticLayer.allocate)")
+        return layer
+
+    def _int8_cache_forward(self, layer, q, k, v, positions, attention_mask, kwargs):
+        """The attention of one forward on an int8 static cache: q [B, T, H, D], k / v [B, T, Hkv, D] (views into the
+        projection output, q and k not rotated yet) -> [B, T, H * D].  A single token is one launch (rotation, quantising
+        cache write, attention over the int8 rows); a promised-fresh prompt is the quantising write from row 0 followed by
+        the prompt kernel on the UNQUANTISED rotated K and the V where they lie in the projection output -- the prompt's
+        output is the fp16-cache path's bit for bit, only the cache is quantised."""
+        bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
+        if (d not in (64, 128) or not q.is_cuda or q.dtype != torch.float16 or self.decode_math_attention is not True
+                or kwargs.get("output_attentions", False) or layer.keys.shape[0] != bsz
+                or layer.keys.shape[1] != self.num_key_value_heads):
+            raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs float16 on the GPU, head size 64 or 128, the "
+                                      "library's decode attention (decode_math_attention=True), no attention weights, and "
+                                      "the batch the cache was allocated for")
+        rows = layer.keys.shape[2]
+        self._grow_table(rows)
+        table = self.rotary_emb.cos_sin_cache
+        if table.shape[-1] != d:
+            raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs the rotation to cover the whole head")
+        counter = layer.cumulative_length
+        if q_len == 1:
+            add = self._decode_mask_rows(attention_mask, bsz, rows, q.dtype, q.device)
+            if add is False:
+                raise NotImplementedError("EETLlamaAttention: this attention mask has no form the int8 decode step understands")
+            pos = positions[:, 0].contiguous()
+            if self.fused_decode_step:
+                out = ops.rope_decode_attention_i8kv(pos, q[:, 0], k[:, 0], v[:, 0], table, layer.keys, layer.values, layer.scales,
+                                                     self._step_tickets(bsz, q.device), slots=counter, mask=add,
+                                                     scaling=self.scaling, kv_len=counter, kv_len_bias=1, advance=counter)
+            else:
+                ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales,
+                                                             first_row_dev=counter)
+                out = ops.decode_attention_i8kv(q[:, 0], layer.keys, layer.values, layer.scales, mask=add, scaling=self.scaling,
+                                                kv_len=counter, kv_len_bias=1, advance=counter)
+            return out.reshape(bsz, q_len, -1)
+        if not getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False):
+            raise NotImplementedError("EETLlamaAttention: a prompt on an int8 KV cache must be promised fresh "
+                                      "(fresh_static_prefill: empty cache, unpadded prompt); a prompt appended behind int8 rows "
+                                      "needs the MFMA prompt kernel to read int8 K and V, which is not built yet")
+        if q_len > rows:
+            raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
+        ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales)
+        counter.fill_(q_len)
+        kt, vt = k.transpose(1, 2), v.transpose(1, 2)     # [B, Hkv, T, D], strides (T W, D, W, 1): the rotated fp16 K, the V
+        if self.mfma_prefill and ops.prefill_attention is not None and ops.prefill_attention_supported(d):
+            out = ops.prefill_attention(q, kt, vt, q_len, scaling=self.scaling)
+            return out.reshape(bsz, q_len, -1)
+        out = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), kt, vt, is_causal=True, scale=self.scaling,
+                                                               enable_gqa=self.num_key_value_groups > 1).transpose(1, 2)
+        return out.reshape(bsz, q_len, -1).contiguous()
+
     # (key, additive rows, the mask itself) of the most recent conversion: the model hands every layer the same mask.  ONE
     # immutable tuple, replaced whole: a reader in another thread sees the old entry or the new one, never a mixture; the
     # entry keeps the mask alive, so its id() cannot be recycled while the entry stands.
@@ -350,6 +414,14 @@ class EETLlamaAttention(_EETAttentionBase):
         v = qkv[..., (h + hkv) * d:].unflatten(-1, (hkv, d))
         positions = self._positions(position_ids, past_key_values, bsz, q_len, hidden_states.device)
         kwargs.pop("use_cache", None)
+        i8 = self._int8_cache_layer(past_key_values)
+        if i8 is not None:   # int8 rows: the library's int8 kernels or an error, never a stock path
+            out = self._int8_cache_forward(i8, q, k, v, positions, attention_mask, kwargs)
+            if residual is None:
+                return self.o_proj(out), None
+            if hasattr(self.o_proj, "qweight"):
+                return self.o_proj(out, residual=residual), None
+            return residual + self.o_proj(out), None
         layer = self._static_cache_layer(past_key_values) if q_len == 1 else None
         need = q_len
         if layer is not None:

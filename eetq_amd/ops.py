@@ -45,6 +45,9 @@ if _C is not None:
     sample_handover = _C.sample_handover
     decode_attention = _C.decode_attention
     rope_decode_attention = _C.rope_decode_attention
+    decode_attention_i8kv = _C.decode_attention_i8kv
+    rope_decode_attention_i8kv = _C.rope_decode_attention_i8kv
+    rotary_embedding_neox_kvcache_prefill_i8 = _C.rotary_embedding_neox_kvcache_prefill_i8
     silu_mul = _C.silu_mul
     prefill_attention = _C.prefill_attention                        # compiled boundary only (None -> torch's attention)
     prefill_attention_supported = _C.prefill_attention_supported
@@ -73,7 +76,8 @@ else:
                              unprocess_weights, w4_a16_moe, w4_a16_moe_path, w4_a16_moe_direct_supported, w8_a16_gemm, w8_a16_gemm_, w8_a16_gemm_t,
                              w4_a16_gemm_t, w4_a16_gemm_tiled, w4_a16_gemm_tiled_supported, w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, w4_a16_moe_backward, w4_a16_moe_train, moe_router,
                              w8_a16_moe_block, w4_a16_moe_block, moe_router_sigmoid, w8_a16_moe_block_sigmoid,
-                             w4_a16_moe_block_sigmoid, sample_handover)
+                             w4_a16_moe_block_sigmoid, sample_handover, decode_attention_i8kv, rope_decode_attention_i8kv,
+                             rotary_embedding_neox_kvcache_prefill_i8)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
@@ -81,7 +85,8 @@ else:
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
-           "greedy_handover", "sample_handover", "sampling_params", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
+           "greedy_handover", "sample_handover", "sampling_params", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv",
+           "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]
 

@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported",
-           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
+           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
@@ -909,6 +909,172 @@ def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_siz
             _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
             _ptr(value_cache), B, T, _ptr(first_row_dev) if first_row_dev is not None else None, int(first_row), H, Hkv,
             int(head_size), cos_sin_cache.shape[1], strides, key_cache.shape[2], _stream_ptr()))
+    return None
+
+
+def _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D):
+    if key_cache.dtype != torch.int8 or value_cache.dtype != torch.int8 or scales.dtype != torch.float16:
+        raise RuntimeError(name + "the caches must be int8 and the scales float16")
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape or scales.dim() != 4:
+        raise RuntimeError(name + "expected caches [B, Hkv, S, D] and scales [B, Hkv, S, 2]")
+    if (key_cache.shape[0] != B or key_cache.shape[1] != Hkv or key_cache.shape[3] != D
+            or tuple(scales.shape) != (B, Hkv, key_cache.shape[2], 2)):
+        raise RuntimeError(name + "shape mismatch")
+    if key_cache.stride(-1) != 1 or value_cache.stride(-1) != 1 or scales.stride(-1) != 1:
+        raise RuntimeError(name + "cache rows and scale pairs must be dense")
+    for t in (key_cache, value_cache, scales):
+        if t.device != query.device:
+            raise RuntimeError(name + "all tensors must be on one device")
+
+
+def _mask_row(name, mask, query, B, S):
+    if mask is None:
+        return None, 0
+    mrow = mask.reshape(mask.shape[0], -1) if mask.dim() != 2 else mask
+    if mrow.dtype != torch.float16 or mrow.shape[-1] < S or mrow.stride(-1) != 1 or mrow.device != query.device:
+        raise RuntimeError(name + "mask must be additive float16 with a dense last dimension >= S")
+    if mrow.shape[0] not in (1, B):
+        raise RuntimeError(name + "the mask needs one row per batch entry (or a single shared row)")
+    return mrow, (mrow.stride(0) if mrow.shape[0] == B and B > 1 else 0)
+
+
+@_eager_only
+def decode_attention_i8kv(query, key_cache, value_cache, scales, mask=None, scaling=None, splits=None, kv_len=None,
+                          kv_len_bias=0, advance=None):
+    """``decode_attention`` over an int8 KV cache (extension): key_cache / value_cache int8 [B, Hkv, S, D], ``scales`` float16
+    [B, Hkv, S, 2] = (k scale, v scale) of each row; attention over the dequantised rows, fp32 softmax and accumulation
+    (eetq_decode_attention_i8kv_f16).  Everything else as ``decode_attention``."""
+    name = "decode_attention_i8kv: "
+    if query.dtype != torch.float16 or query.dim() != 3 or query.stride(-1) != 1 or key_cache.dim() != 4:
+        raise RuntimeError(name + "expected a float16 query [B, H, D] with dense D")
+    B, H, D = query.shape
+    Hkv, S = key_cache.shape[1], key_cache.shape[2]
+    _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
+    if Hkv <= 0 or H % Hkv:
+        raise RuntimeError(name + "shape mismatch")
+    mrow, m_sb = _mask_row(name, mask, query, B, S)
+    for what, t in (("kv_len", kv_len), ("advance", advance)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
+            raise RuntimeError(name + "%s must be a one-element int64 tensor on the query's device" % what)
+    if scaling is None:
+        scaling = D ** -0.5
+    if splits is None:
+        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
+    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
+    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
+    strides = (ctypes.c_long * 11)(query.stride(0), query.stride(1), key_cache.stride(0), key_cache.stride(1),
+                                   key_cache.stride(2), value_cache.stride(0), value_cache.stride(1), value_cache.stride(2),
+                                   m_sb, out.stride(0), out.stride(1))
+    sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_decode_attention_i8kv_f16(_ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(scales),
+                                                        _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), B, H,
+                                                        Hkv, S, D, int(splits), float(scaling), strides, sst,
+                                                        _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
+                                                        _ptr(advance) if advance is not None else None, _stream_ptr()))
+    return out
+
+
+@_eager_only
+def rope_decode_attention_i8kv(positions, query, key, value, cos_sin_cache, key_cache, value_cache, scales, tickets,
+                               slots=None, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None):
+    """``rope_decode_attention`` on an int8 KV cache (extension), ONE launch: the rotated key and the value of the new token are
+    quantised in registers, written as bytes and scale pair to their cache row, and attended as their quantised selves.
+    Bit-identical to ``rotary_embedding_neox_kvcache_prefill_i8`` with one token followed by ``decode_attention_i8kv``
+    (eetq_rope_decode_attention_i8kv_f16)."""
+    name = "rope_decode_attention_i8kv: "
+    for t in (query, key, value, cos_sin_cache):
+        if t.dtype != torch.float16:
+            raise RuntimeError(name + "float16 query, key, value and cos|sin table expected")
+    if positions.dtype != torch.int64 or not positions.is_contiguous():
+        raise RuntimeError(name + "positions must be contiguous int64")
+    if query.dim() != 3 or key.dim() != 3 or value.dim() != 3 or key_cache.dim() != 4:
+        raise RuntimeError(name + "expected query [B, H, D], key / value [B, Hkv, D], caches [B, Hkv, S, D]")
+    B, H, D = query.shape
+    Hkv, S = key.shape[1], key_cache.shape[2]
+    _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
+    if key.shape[0] != B or key.shape[2] != D or value.shape != key.shape or Hkv <= 0 or H % Hkv or positions.numel() != B:
+        raise RuntimeError(name + "shape mismatch")
+    for t in (query, key, value):
+        if t.stride(-1) != 1 or t.stride(-2) != D:
+            raise RuntimeError(name + "[heads, head_size] must be dense")
+    if not cos_sin_cache.is_contiguous() or cos_sin_cache.shape[-1] != D:
+        raise RuntimeError(name + "the rotation must cover the whole head (rot_dim == D)")
+    if (tickets.dtype != torch.int32 or not tickets.is_contiguous() or tickets.numel() < B * H + 1
+            or tickets.device != query.device):
+        raise RuntimeError(name + "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device")
+    slot_stride = 0
+    if slots is not None:
+        if (slots.dtype != torch.int64 or slots.device != query.device or slots.numel() not in (1, B)
+                or not slots.is_contiguous()):
+            raise RuntimeError(name + "slots must be contiguous int64 on the device, 1 or B elements")
+        slot_stride = 1 if (slots.numel() == B and B > 1) else 0
+    mrow, m_sb = _mask_row(name, mask, query, B, S)
+    for what, t in (("kv_len", kv_len), ("advance", advance)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
+            raise RuntimeError(name + "%s must be a one-element int64 tensor on the query's device" % what)
+    if scaling is None:
+        scaling = D ** -0.5
+    if splits is None:
+        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
+    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
+    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
+    strides = (ctypes.c_long * 12)(query.stride(0), key.stride(0), value.stride(0), key_cache.stride(0),
+                                   key_cache.stride(1), key_cache.stride(2), value_cache.stride(0), value_cache.stride(1),
+                                   value_cache.stride(2), m_sb, out.stride(0), out.stride(1))
+    sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_rope_decode_attention_i8kv_f16(
+            _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
+            _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _ptr(scales),
+            _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits),
+            float(scaling), strides, sst, _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
+            _ptr(advance) if advance is not None else None, _stream_ptr()))
+    return out
+
+
+@_eager_only
+def rotary_embedding_neox_kvcache_prefill_i8(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
+                                             scales, first_row=0, first_row_dev=None):
+    """``rotary_embedding_neox_kvcache_prefill`` writing an int8 KV cache: ``query`` [B, T, H, D] AND ``key`` [B, T, Hkv, D] are
+    rotated in place; the rotated key and ``value`` of every (token, kv head) are quantised with a scale of their own and
+    written to rows ``base + t`` of the int8 caches [B, Hkv, S, D] and of ``scales`` (float16 [B, Hkv, S, 2]).  With T = 1 and
+    ``first_row_dev`` = the cache's counter it is the cache write of an unfused decode step
+    (eetq_rotary_neox_kvcache_prefill_i8_f16)."""
+    name = "rotary_embedding_neox_kvcache_prefill_i8: "
+    for t in (query, key, value, cos_sin_cache):
+        if t.dtype != torch.float16:
+            raise RuntimeError(name + "float16 query, key, value and cos|sin table expected")
+        if not t.is_cuda or t.device != query.device:
+            raise RuntimeError(name + "all tensors must be on one CUDA device")
+    if positions.dtype != torch.int64 or not positions.is_contiguous() or positions.device != query.device:
+        raise RuntimeError(name + "positions must be contiguous int64 on the device")
+    if query.dim() != 4 or key.dim() != 4 or value.dim() != 4 or key_cache.dim() != 4:
+        raise RuntimeError(name + "shape mismatch")
+    B, T, H, D = query.shape
+    Hkv = key.shape[2]
+    _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
+    if (key.shape != (B, T, Hkv, D) or value.shape != key.shape or D != head_size
+            or value_cache.stride() != key_cache.stride() or positions.numel() != B * T or first_row < 0
+            or (first_row_dev is None and first_row + T > key_cache.shape[2])):
+        raise RuntimeError(name + "shape mismatch")
+    if first_row_dev is not None and (first_row_dev.dtype != torch.int64 or first_row_dev.numel() != 1
+                                      or first_row_dev.device != query.device):
+        raise RuntimeError(name + "first_row_dev must be one int64 on the device")
+    for t in (query, key, value):
+        if t.stride(-1) != 1 or t.stride(-2) != D or (B != 1 and T != 1 and t.stride(0) != T * t.stride(1)):
+            raise RuntimeError(name + "[heads, head_size] must be dense and the tokens of all rows one stride apart")
+    tdim = 0 if T == 1 else 1   # (a size-1 dimension's stride is arbitrary)
+    if not cos_sin_cache.is_contiguous():
+        raise RuntimeError(name + "the cos|sin table must be contiguous")
+    strides = (ctypes.c_long * 6)(query.stride(tdim), key.stride(tdim), value.stride(tdim), key_cache.stride(0),
+                                  key_cache.stride(1), key_cache.stride(2))
+    sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_rotary_neox_kvcache_prefill_i8_f16(
+            _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
+            _ptr(value_cache), _ptr(scales), B, T, _ptr(first_row_dev) if first_row_dev is not None else None, int(first_row), H,
+            Hkv, int(head_size), cos_sin_cache.shape[1], strides, sst, key_cache.shape[2], _stream_ptr()))
     return None
 
 

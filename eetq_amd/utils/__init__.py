@@ -8,3 +8,10 @@ from .graph_decoder import GraphDecoder  # noqa: F401,E402
 from ..checkpoint import (checkpoint_layout, convert_checkpoint, convert_model_layout_, get_wire_layout,  # noqa: F401,E402
                          quantization_config, set_wire_layout, wire_layout)
 from .hf import use_with_transformers  # noqa: F401,E402
+
+
+def __getattr__(name):   # the int8 cache classes subclass transformers' static cache: imported on first use, not with the package
+    if name in ("Int8StaticCache", "Int8StaticLayer"):
+        from . import kv_cache
+        return getattr(kv_cache, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

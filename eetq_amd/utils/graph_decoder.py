@@ -16,7 +16,7 @@ __all__ = ["GraphDecoder"]
 
 
 class GraphDecoder:
-    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False):
+    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -28,20 +28,39 @@ class GraphDecoder:
         ``sampling``: the hand-over inside the graphs is ``ops.sample_handover`` on a static parameter block and static EOS
         flags instead of the argmax: ``generate`` then takes ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` /
         ``eos_token_id`` / ``pad_token_id`` per call, without recapture (needs fp16 logits on the GPU).  The default leaves
-        launches and tokens as they were."""
+        launches and tokens as they were.
+        ``kv_bits``: 16 (the default: an fp16 ``StaticCache``) or 8: an ``Int8StaticCache`` (``utils/kv_cache.py``: int8 rows with a
+        scale pair each, ``2 D + 4`` bytes per row against ``4 D``), written and read by the accelerated attention blocks' int8
+        kernels.  It needs the lean layer-by-layer model with head size 64 or 128, and runs fresh whole prompts only:
+        ``append=True`` and chunked prompts raise ``ValueError`` (prompts behind int8 rows are a follow-up)."""
+        if kv_bits not in (8, 16):
+            raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
+        self.kv_bits = int(kv_bits)
         self.lean = bool(lean)
         self.sampling = bool(sampling)
-        from transformers import StaticCache
         self.model = model
+        if self.kv_bits == 8:
+            if not self._lean():
+                raise ValueError("GraphDecoder: kv_bits=8 needs lean=True and a fully accelerated model (eet_accelerator with "
+                                 "fused_attn, fused_mlp and fused_residual): only its attention blocks write an int8 cache")
+            for layer in model.model.layers:
+                attn = getattr(layer, "self_attn", None)
+                if not hasattr(attn, "_int8_cache_layer") or getattr(attn, "head_dim", None) not in (64, 128):
+                    raise ValueError("GraphDecoder: kv_bits=8 needs attention blocks with head size 64 or 128")
+        from transformers import StaticCache
         self.batch = int(batch)
         self.max_len = int(max_len)
         dev = next(model.parameters()).device
         self.device = dev
-        try:
-            self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
-        except TypeError:  # older constructor
-            self.cache = StaticCache(config=model.config, max_batch_size=self.batch, max_cache_len=self.max_len, device=dev,
-                                     dtype=torch.float16)
+        if self.kv_bits == 8:
+            from .kv_cache import Int8StaticCache
+            self.cache = Int8StaticCache(config=model.config, max_cache_len=self.max_len).allocate(self.batch, dev)
+        else:
+            try:
+                self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
+            except TypeError:  # older constructor
+                self.cache = StaticCache(config=model.config, max_batch_size=self.batch, max_cache_len=self.max_len, device=dev,
+                                         dtype=torch.float16)
         self.s_tok = torch.zeros(self.batch, 1, dtype=torch.long, device=dev)
         self.s_pos = torch.zeros(1, dtype=torch.long, device=dev)
         # generated tokens: step i of a generate() writes column s_idx (a device counter the graphs advance themselves)
@@ -92,8 +111,10 @@ class GraphDecoder:
             return False
         for layer in self.model.model.layers:
             attn = getattr(layer, "self_attn", None)
-            if (attn is None or not getattr(attn, "static_prefill", False) or not hasattr(attn, "_static_cache_layer")
-                    or attn._static_cache_layer(self.cache) is None):
+            if attn is None or not getattr(attn, "static_prefill", False) or not hasattr(attn, "_static_cache_layer"):
+                return False
+            if attn._static_cache_layer(self.cache) is None and (not hasattr(attn, "_int8_cache_layer")
+                                                                 or attn._int8_cache_layer(self.cache) is None):
                 return False
         return True
 
@@ -156,6 +177,9 @@ class GraphDecoder:
         row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
         finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on."""
         B, P = prompt.shape
+        if self.kv_bits == 8 and (append or prefill_chunk is not None):
+            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only: append=True and "
+                             "prefill_chunk need the prompt kernel to read int8 rows (not built yet)")
         append = bool(append) and (self.rows > 0 or self._pending)
         feed = torch.cat([self.s_tok, prompt], dim=1) if append and self._pending else prompt
         start = self.rows if append else 0
@@ -209,6 +233,9 @@ class GraphDecoder:
         of emptying it.  Accelerated models attend the first piece of an emptied cache under ``fresh_static_prefill`` and every
         other piece under ``appended_static_prefill``; other models run the same calls on their stock path."""
         P = prompt.shape[1]
+        if self.kv_bits == 8 and (append or chunk is not None):
+            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only: append=True and chunk= "
+                             "need the prompt kernel to read int8 rows (not built yet)")
         start = self.rows if append else 0
         if start + P > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))

@@ -592,6 +592,60 @@ int eetq_rope_decode_attention_bounded_f16(const int64_t* positions, const int64
                                            int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
                                            int kv_len_bias, int64_t* advance, void* stream);
 
+/* The int8 KV cache (extension, added within ABI revision 7).  One cache ROW is the head_dim fp16 values of one (batch row, kv
+ * head, position); rows are quantised symmetrically, each with a scale of its own:
+ *   amax = max_d |x_d| (exact);  s = fp16(fp32(amax) * (1.0f / 127.0f)), one fp32 multiply, round to nearest even;
+ *   q_d = clamp(round_half_away(fp32(x_d) / fp32(s)), -127, 127) as int8, IEEE fp32 division (eetq_quant_weights' rounding);
+ *   -128 is never written, s == 0 gives q = 0, non-finite inputs are outside the contract.
+ * Storage: k_cache_i8 and v_cache_i8 are int8 [batch][kv_heads][positions][head_dim], plain two's complement; kv_scales is fp16
+ * [batch][kv_heads][positions][2] = (k scale, v scale) of the row, one dword per row.  Attention is over the dequantised rows
+ * ks * k8 and vs * v8 taken as exact reals, with fp32 scores, softmax state and accumulation as in the fp16 entries: the K scale is
+ * folded into the score, (ks * scaling) * (q . k8), the V scale into the probability, (p * vs) * v8.  vs * v8 is exact in fp32, so a
+ * row that holds all the weight comes out as fp16(vs * v8) bit for bit.
+ *
+ * eetq_decode_attention_i8kv_f16: eetq_decode_attention_f16 over such a cache.  strides: as there, with the k / v entries in BYTES
+ * ({q_b, q_h, k_b, k_h, k_pos, v_b, v_h, v_pos, mask_b, out_b, out_h}); scale_strides (fp16 elements): {batch, head, position}.
+ * Workspace, splits (eetq_decode_attention_splits), mask, kv_len, kv_len_bias and advance as in the fp16 entry.
+ * EETQ_ERR_INVALID (nothing launched): a null pointer; a cache stride that is not a multiple of 8 bytes or a cache that is not
+ * 8-byte aligned (8-byte loads); a scale stride that is not a multiple of 2 elements or scales that are not 4-byte aligned; a q
+ * stride that is not a multiple of 8 elements or a q that is not 16-byte aligned; (positions + 4096) * the row stride in bytes (of
+ * a cache or of the scales) >= 2 GiB.  EETQ_ERR_UNSUPPORTED: head_dim other than 64 or 128. */
+int eetq_decode_attention_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales,
+                                   const void* mask, void* out, float* workspace, int batch, int heads, int kv_heads, int positions,
+                                   int head_dim, int splits, float scaling, const long* strides, const long* scale_strides,
+                                   const int64_t* kv_len, int kv_len_bias, int64_t* advance, void* stream);
+
+/* eetq_rope_decode_attention_bounded_f16 on an int8 cache, ONE launch: K is quantised after the rotation (the rotation's bits are
+ * those of the fp16 entries), the row's bytes and scale pair are written from registers to row slots[b * slot_stride], and the new
+ * token enters the softmax as its quantised self -- the same (k8, ks, v8, vs) -- from registers: nothing in the launch reads what
+ * the launch writes, and the result equals "write the row, then eetq_decode_attention_i8kv_f16" bit for bit.  strides: as the fp16
+ * entry, cache entries in bytes; scale_strides as above; tickets, workspace, advance as the fp16 entry; table_rows is validated
+ * and not enforced on the device, as there.  A slot outside the cache (or a negative position) is neither written nor attended,
+ * and counted (eetq_decode_dropped_steps).  Errors as eetq_decode_attention_i8kv_f16, plus q / k / v strides that are not
+ * multiples of 8 elements, a q, k, v or cos|sin table that is not 16-byte aligned, table_rows <= 0, slot_stride not 0 or 1. */
+int eetq_rope_decode_attention_i8kv_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                        const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                        void* k_cache_i8, void* v_cache_i8, void* kv_scales, const void* mask, void* out,
+                                        float* workspace, unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                        int head_dim, int splits, float scaling, const long* strides, const long* scale_strides,
+                                        const int64_t* kv_len, int kv_len_bias, int64_t* advance, void* stream);
+
+/* eetq_rotary_neox_kvcache_prefill_bounded_f16 writing an int8 cache: query [batch][tokens][q_heads][head_size] AND key are rotated
+ * IN PLACE (key is writable: a prompt then attends the rotated fp16 K where it lies, unquantised), and the rotated key and the
+ * value of every (token, kv head) are quantised by the rule above and written to rows base + t of the caches and of kv_scales, base
+ * = *first_row_dev (DEVICE int64, read and not advanced) or first_row.  tokens = 1 with first_row_dev = the cache's counter is the
+ * cache write of an unfused decode step.  strides: {q_token, k_token, v_token (elements), cache_b, cache_head, cache_row (bytes,
+ * shared by both caches)}; scale_strides as above.  Tokens whose row lies outside [0, max_positions) or whose position lies outside
+ * [0, table_rows) are left untouched and counted (eetq_decode_dropped_steps).  EETQ_ERR_INVALID: null pointers, token strides that
+ * are not multiples of 8 elements, q / k / v / table not 16-byte aligned, cache strides not multiples of 8 bytes or caches not 8-byte
+ * aligned, scale strides not multiples of 2 or scales not 4-byte aligned, rot_dim != head_size, rows outside the cache (host
+ * first_row), table_rows <= 0.  EETQ_ERR_UNSUPPORTED: head_size other than 64 or 128. */
+int eetq_rotary_neox_kvcache_prefill_i8_f16(const int64_t* positions, void* query, void* key, const void* value,
+                                            const void* cos_sin_cache, int table_rows, void* k_cache_i8, void* v_cache_i8,
+                                            void* kv_scales, int batch, int tokens, const int64_t* first_row_dev, int first_row,
+                                            int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                            const long* scale_strides, int max_positions, void* stream);
+
 /* Causal attention over a PROMPT on the matrix cores (extension, ABI revision 6): out[b][t][h] = softmax_j<=t+causal_offset(scaling
  * q[b][t][h] . k[b][h / groups][j]) v[b][h / groups][j] over the first `keys` rows of a KV cache, fp16 in / out, fp32 scores, softmax
  * state and accumulation (probabilities rounded to fp16 for the second product, like flash-attn, which the reference's block calls

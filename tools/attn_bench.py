@@ -1,7 +1,10 @@
 """Decode-step attention at Llama-2-13B shapes (40 heads x 128, one new token), as the graph decoder issues it: `layers`
 independent caches (together larger than the 256 MB Infinity Cache) stepped back to back inside one HIP graph.
 Prints microseconds per layer-step for the one-launch form (eetq_rope_decode_attention_f16) over a sweep of chunk counts,
-and for the two-launch pair.  usage: python tools/attn_bench.py [--filled 1024] [--rows 1082] [--batch 1]"""
+and for the two-launch pair.  usage: python tools/attn_bench.py [--filled 1024] [--rows 1082] [--batch 1]
+--kv-bits 8: the same sweep over an int8 KV cache (eetq_rope_decode_attention_i8kv_f16).  --compare-lib PATH: one process alternates
+the fp16 one-launch form of the library at PATH (e.g. the parent commit's build), this tree's fp16 form and its int8 form, --rounds
+times each, at the default chunk count.  --write T: the prompt's cache write at T tokens, fp16 against the quantising int8 write."""
 import argparse
 import json
 import os
@@ -24,15 +27,27 @@ ap.add_argument("--stamps", action="store_true", help="per-phase device-clock de
 ap.add_argument("--stamps-fused", action="store_true", help="device-clock decomposition of the fused attention + o projection launch")
 ap.add_argument("--pair", action="store_true", help="attention + the o projection behind it (H*D x H*D int8), with and without "
                                                     "the L2 prefetch of the projection's weight inside the attention launch")
+ap.add_argument("--kv-bits", type=int, default=16, choices=(16, 8), help="8: an int8 KV cache with a scale pair per row")
+ap.add_argument("--compare-lib", default=None, help="another build of libeetq_amd.so to alternate with (its fp16 one-launch form)")
+ap.add_argument("--rounds", type=int, default=2)
+ap.add_argument("--write", type=int, default=0, help="time the prompt cache write at this many tokens instead (fp16 and int8)")
 args = ap.parse_args()
+if args.kv_bits == 8 and (args.stamps or args.stamps_fused or args.pair):
+    sys.exit("--kv-bits 8 goes with the chunk sweep, --compare-lib and --write only")
 dev = "cuda:0"
 B, H, Hkv, D, S, L = args.batch, args.heads, args.kv_heads, 128, args.rows, args.layers
 torch.manual_seed(0)
 inv = 1.0 / (10000 ** (torch.arange(0, D, 2).float() / D))
 fr = torch.einsum("i,j->ij", torch.arange(S + 64).float(), inv)
 table = torch.cat([fr.cos(), fr.sin()], -1).half().to(dev)
-kc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L)]
-vc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L)]
+want16 = args.kv_bits == 16 or args.compare_lib is not None or args.write > 0
+want8 = args.kv_bits == 8 or args.compare_lib is not None or args.write > 0
+kc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L if want16 else 0)]
+vc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L if want16 else 0)]
+# int8 rows: bytes uniform in [-127, 127], scales near 1 / 42 (an N(0, 1) row of 128 values has an absmax near 3)
+kc8 = [torch.randint(-127, 128, (B, Hkv, S, D), dtype=torch.int8, device=dev) for _ in range(L if want8 else 0)]
+vc8 = [torch.randint(-127, 128, (B, Hkv, S, D), dtype=torch.int8, device=dev) for _ in range(L if want8 else 0)]
+sc8 = [(torch.rand(B, Hkv, S, 2, device=dev) * 0.01 + 0.02).half() for _ in range(L if want8 else 0)]
 qkv = torch.randn(B, 1, (H + 2 * Hkv) * D, dtype=torch.float16, device=dev)
 q = qkv[..., : H * D].unflatten(-1, (H, D))[:, 0]
 k = qkv[..., H * D: (H + Hkv) * D].unflatten(-1, (Hkv, D))[:, 0]
@@ -40,7 +55,8 @@ v = qkv[..., (H + Hkv) * D:].unflatten(-1, (Hkv, D))[:, 0]
 pos = torch.full((B,), args.filled, dtype=torch.int64, device=dev)
 tickets = [torch.zeros(B * H + 1, dtype=torch.int32, device=dev) for _ in range(L)]
 counters = [torch.tensor(args.filled, dtype=torch.int64, device=dev) for _ in range(L)]
-kv_mb = 2 * B * Hkv * (args.filled + 1) * D * 2 / 1e6
+kv_mb = 2 * B * Hkv * (args.filled + 1) * D * 2 / 1e6            # fp16: 4 D bytes per row (K and V)
+kv8_mb = B * Hkv * (args.filled + 1) * (2 * D + 4) / 1e6         # int8: 2 D + 4
 
 
 def one_launch(i, splits):
@@ -51,6 +67,17 @@ def one_launch(i, splits):
 def two_launch(i, splits):
     ops.rotary_embedding_neox_kvcache(pos, q, k, v, D, table, kc[i], vc[i], slots=counters[i])
     return ops.decode_attention(q, kc[i], vc[i], splits=splits, kv_len=counters[i], kv_len_bias=1)
+
+
+def one_launch_i8(i, splits):
+    return ops.rope_decode_attention_i8kv(pos, q, k, v, table, kc8[i], vc8[i], sc8[i], tickets[i], slots=counters[i], splits=splits,
+                                          kv_len=counters[i], kv_len_bias=1)
+
+
+def two_launch_i8(i, splits):
+    ops.rotary_embedding_neox_kvcache_prefill_i8(pos[:, None], q[:, None], k[:, None], v[:, None], D, table, kc8[i], vc8[i], sc8[i],
+                                                 first_row_dev=counters[i])
+    return ops.decode_attention_i8kv(q, kc8[i], vc8[i], sc8[i], splits=splits, kv_len=counters[i], kv_len_bias=1)
 
 
 def timed(fn, splits, reps=30):
@@ -75,6 +102,65 @@ def timed(fn, splits, reps=30):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / (reps * L)
 
+
+def record(form, lib, bits, s, us):
+    mb = kv_mb if bits == 16 else kv8_mb
+    print(json.dumps({"form": form, "lib": lib, "kv_bits": bits, "splits": s, "batch": B, "heads": H, "kv_heads": Hkv,
+                      "filled": args.filled, "rows": S, "us_per_layer_step": round(us, 2), "kv_MB": round(mb, 1),
+                      "kv_GBps": round(mb / us * 1e3, 0)}), flush=True)
+
+
+if args.write:
+    T = args.write
+    wide = torch.randn(B, T, (H + 2 * Hkv) * D, dtype=torch.float16, device=dev)
+    wq = wide[..., : H * D].unflatten(-1, (H, D))
+    wk = wide[..., H * D: (H + Hkv) * D].unflatten(-1, (Hkv, D))
+    wv = wide[..., (H + Hkv) * D:].unflatten(-1, (Hkv, D))
+    wpos = torch.arange(T, device=dev).repeat(B, 1).contiguous()
+
+    def write16(i, _):
+        ops.rotary_embedding_neox_kvcache_prefill(wpos, wq, wk, wv, D, table, kc[i], vc[i])
+
+    def write8(i, _):
+        ops.rotary_embedding_neox_kvcache_prefill_i8(wpos, wq, wk, wv, D, table, kc8[i], vc8[i], sc8[i])
+
+    for rnd in range(args.rounds):
+        for name, fn, bits in (("prompt_write", write16, 16), ("prompt_write", write8, 8)):
+            print(json.dumps({"form": name, "kv_bits": bits, "tokens": T, "batch": B, "heads": H, "kv_heads": Hkv, "round": rnd,
+                              "us_per_layer": round(timed(fn, None), 2)}), flush=True)
+    sys.exit(0)
+
+if args.compare_lib:
+    import ctypes
+    from eetq_amd import _lib
+    mine = _lib.lib()
+    other = ctypes.CDLL(os.path.abspath(args.compare_lib))
+    for name in ("eetq_rope_decode_attention_bounded_f16", "eetq_decode_attention_splits"):
+        getattr(other, name).argtypes = getattr(mine, name).argtypes
+        getattr(other, name).restype = ctypes.c_int
+    splits = other.eetq_decode_attention_splits(B, H, S)
+    assert splits == mine.eetq_decode_attention_splits(B, H, S)
+    out_o = torch.empty(B, H, D, dtype=torch.float16, device=dev)
+    ws_o = torch.empty(B * H * splits * (D + 4), dtype=torch.float32, device=dev)
+
+    def other_one_launch(i, _):
+        st = (ctypes.c_long * 12)(q.stride(0), k.stride(0), v.stride(0), kc[i].stride(0), kc[i].stride(1), kc[i].stride(2),
+                                  vc[i].stride(0), vc[i].stride(1), vc[i].stride(2), 0, out_o.stride(0), out_o.stride(1))
+        p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        rc = other.eetq_rope_decode_attention_bounded_f16(
+            p(pos), p(counters[i]), 0, p(q), p(k), p(v), p(table), table.shape[0], p(kc[i]), p(vc[i]), None, p(out_o), p(ws_o),
+            p(tickets[i]), B, H, Hkv, S, D, splits, D ** -0.5, st, p(counters[i]), 1, None,
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, rc
+        return out_o
+
+    same = bool(torch.equal(other_one_launch(0, None).clone(), one_launch(0, splits)))
+    print(json.dumps({"compare_lib": args.compare_lib, "fp16_same_bits_as_compare_lib": same, "splits": splits}), flush=True)
+    for rnd in range(args.rounds):
+        record("one_launch", "compare", 16, "default", timed(other_one_launch, None))
+        record("one_launch", "tree", 16, "default", timed(one_launch, None))
+        record("one_launch", "tree", 8, "default", timed(one_launch_i8, None))
+    sys.exit(0)
 
 if args.pair:
     C = H * D
@@ -248,10 +334,8 @@ if args.stamps:
     print("kernel span (first entry -> last output stored), mean over launches: %.2f us" % torch.nan_to_num(last, nan=0.0).amax(1).mean())
     sys.exit(0)
 
-for name, fn in (("one_launch", one_launch), ("two_launch", two_launch)):
+forms = (("one_launch", one_launch), ("two_launch", two_launch)) if args.kv_bits == 16 else (
+    ("one_launch", one_launch_i8), ("two_launch", two_launch_i8))
+for name, fn in forms:
     for s in args.splits.split(","):
-        splits = None if s == "default" else int(s)
-        us = timed(fn, splits)
-        print(json.dumps({"form": name, "splits": s, "batch": B, "heads": H, "kv_heads": Hkv, "filled": args.filled,
-                          "rows": S, "us_per_layer_step": round(us, 2), "kv_MB": round(kv_mb, 1),
-                          "kv_GBps": round(kv_mb / us * 1e3, 0)}))
+        record(name, "tree", args.kv_bits, s, timed(fn, None if s == "default" else int(s)))
