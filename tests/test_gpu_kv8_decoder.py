@@ -4,7 +4,14 @@ tests/test_gpu_multiturn.py (hidden 256, 4 heads / 2 KV heads of 64, 2 layers, v
 The prompt attends its own unquantised keys and only the cache is quantised, so the prompt's logits are the fp16 decoder's bit
 for bit and the cache rows are the NumPy quantiser (tests/kv8_cases.py) of the fp16 decoder's rows.  Decode steps then attend
 quantised rows: their logits differ from the fp16 decoder's, by a figure that is printed and not asserted (there is no
-reference figure for it)."""
+reference figure for it).
+
+A second configuration has one KV head of 128 (hidden 256, 2 heads, 2 layers, vocab 512) and 200 cache rows: the library's
+default there is more than one chunk, so the captured one-launch form replays with tickets and a head merge, and 9 prompt
+tokens followed by 40 steps take the new row across the 16-row block edges.  In both configurations the captured, the eager
+and the unfused run must leave the same cache bytes and scale bits behind, not only the same tokens.
+
+Wall time on an MI355X: 7 s for the file, 5 s of it building the first model and its decoders."""
 import copy
 
 import numpy as np
@@ -16,6 +23,7 @@ import kv8_cases as k8c
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 MAX_LEN = 64
+MAX_LEN_128 = 200
 
 
 @pytest.fixture(scope="module")
@@ -44,6 +52,36 @@ def prompt():
 
 
 @pytest.fixture(scope="module")
+def cfg128():
+    transformers = pytest.importorskip("transformers")
+    return transformers.LlamaConfig(hidden_size=256, intermediate_size=704, num_hidden_layers=2, num_attention_heads=2,
+                                    num_key_value_heads=1, vocab_size=512, max_position_embeddings=256)
+
+
+@pytest.fixture(scope="module")
+def model128(cfg128):
+    import transformers
+    from eetq_amd.utils import eet_accelerator
+    torch.manual_seed(1)
+    stock = transformers.LlamaForCausalLM(cfg128).half().to(DEV).eval()
+    model = eet_accelerator(stock, quantize=True, fused_attn=True, fused_mlp=True, fused_norm=True, fused_residual=True)
+    assert model.model.layers[0].self_attn.head_dim == 128 and model.model.layers[0].self_attn.num_key_value_heads == 1
+    return model
+
+
+@pytest.fixture(scope="module")
+def fp16_decoder128(model128):
+    from eetq_amd.utils.graph_decoder import GraphDecoder
+    return GraphDecoder(model128, 2, MAX_LEN_128)
+
+
+@pytest.fixture(scope="module")
+def int8_decoder128(model128):
+    from eetq_amd.utils.graph_decoder import GraphDecoder
+    return GraphDecoder(model128, 2, MAX_LEN_128, kv_bits=8)
+
+
+@pytest.fixture(scope="module")
 def fp16_decoder(model):
     from eetq_amd.utils.graph_decoder import GraphDecoder
     return GraphDecoder(model, 2, MAX_LEN)
@@ -55,9 +93,7 @@ def int8_decoder(model):
     return GraphDecoder(model, 2, MAX_LEN, kv_bits=8)
 
 
-def test_prompt_logits_and_cache_rows(fp16_decoder, int8_decoder, prompt):
-    """The prompt's logits equal the fp16 decoder's bit for bit; every layer's int8 rows and scales are the NumPy quantiser of
-    the fp16 decoder's cache rows."""
+def _prompt_logits_and_cache_rows(fp16_decoder, int8_decoder, prompt):
     from eetq_amd.utils.kv_cache import Int8StaticCache
     assert isinstance(int8_decoder.cache, Int8StaticCache)
     P = prompt.shape[1]
@@ -73,23 +109,75 @@ def test_prompt_logits_and_cache_rows(fp16_decoder, int8_decoder, prompt):
         assert np.array_equal(l8.scales[:, :, :P].cpu().numpy().view(np.int16), k8c.scale_pairs(eks, evs).view(np.int16))
 
 
-def test_captured_and_eager_emit_the_same_tokens(model, int8_decoder, prompt):
+def test_prompt_logits_and_cache_rows(fp16_decoder, int8_decoder, prompt):
+    """The prompt's logits equal the fp16 decoder's bit for bit; every layer's int8 rows and scales are the NumPy quantiser of
+    the fp16 decoder's cache rows."""
+    _prompt_logits_and_cache_rows(fp16_decoder, int8_decoder, prompt)
+
+
+def test_prompt_logits_and_cache_rows_head_size_128(fp16_decoder128, int8_decoder128, prompt):
+    _prompt_logits_and_cache_rows(fp16_decoder128, int8_decoder128, prompt)
+
+
+def _filled_rows(decoder, rows):
+    """every layer's int8 bytes and scale bit patterns below the counter, which stands at `rows`"""
+    out = []
+    for layer in decoder.cache.layers:
+        assert int(layer.cumulative_length) == rows
+        out.append((layer.keys[:, :, :rows].clone(), layer.values[:, :, :rows].clone(),
+                    layer.scales[:, :, :rows].contiguous().view(torch.int16).clone()))
+    return out
+
+
+def _same_rows(a, b, what):
+    for i, (la, lb) in enumerate(zip(a, b)):
+        for name, x, y in zip(("K bytes", "V bytes", "scale bits"), la, lb):
+            bad = (x != y).flatten(3).any(-1).nonzero()
+            assert not len(bad), "%s: layer %d, %s differ in %d rows, first (b, kv head, row) %s" % (what, i, name, len(bad),
+                                                                                                  bad[:4].tolist())
+
+
+def _captured_eager_and_unfused(model, int8_decoder, prompt, max_len, steps):
+    """The captured one-launch step, the same step launched eagerly and the unfused step (write launch + two-launch attention)
+    emit the same tokens and leave the same cache rows behind."""
     from eetq_amd.utils.graph_decoder import GraphDecoder
-    eager = GraphDecoder(model, 2, MAX_LEN, capture=False, kv_bits=8)
-    a = int8_decoder.generate(prompt, 20)
-    b = eager.generate(prompt, 20)
-    assert a.shape == (2, prompt.shape[1] + 20) and torch.equal(a, b)
-    assert [int(l.cumulative_length) for l in int8_decoder.cache.layers] == [prompt.shape[1] + 19] * 2
+    eager = GraphDecoder(model, 2, max_len, capture=False, kv_bits=8)
+    rows = prompt.shape[1] + steps - 1
+    a = int8_decoder.generate(prompt, steps)
+    b = eager.generate(prompt, steps)
+    assert a.shape == (2, prompt.shape[1] + steps) and torch.equal(a, b)
+    assert [int(l.cumulative_length) for l in int8_decoder.cache.layers] == [rows] * 2
+    rows_a, rows_b = _filled_rows(int8_decoder, rows), _filled_rows(eager, rows)
     # the unfused step (write launch + two-launch attention) gives the one-launch form's tokens
     blocks = [layer.self_attn for layer in model.model.layers]
     try:
         for blk in blocks:
             blk.fused_decode_step = False
-        c = eager.generate(prompt, 20)
+        c = eager.generate(prompt, steps)
     finally:
         for blk in blocks:
             blk.fused_decode_step = True
     assert torch.equal(a, c)
+    _same_rows(rows_a, rows_b, "captured against eager")
+    _same_rows(rows_a, _filled_rows(eager, rows), "captured against unfused")
+
+
+def test_captured_and_eager_emit_the_same_tokens(model, int8_decoder, prompt):
+    _captured_eager_and_unfused(model, int8_decoder, prompt, MAX_LEN, 20)
+
+
+def test_default_chunks_at_head_size_128():
+    """Asserted, not assumed: the library's own choice for the second configuration's decode step (batch 2, 2 heads, 200 rows)
+    is more than one chunk, so its one-launch form ends in the ticket and the head merge."""
+    from eetq_amd import _lib
+    assert _lib.lib().eetq_decode_attention_splits(2, 2, MAX_LEN_128) > 1
+    assert _lib.lib().eetq_decode_attention_splits(2, 4, MAX_LEN) == 1      # the first configuration: one chunk, no merge
+
+
+def test_captured_and_eager_emit_the_same_tokens_head_size_128(model128, int8_decoder128, prompt):
+    """9 prompt tokens and 40 steps: the new row runs from 9 to 47, through blocks 0, 1 and 2 of 16 rows and over the edges
+    15 | 16 and 31 | 32."""
+    _captured_eager_and_unfused(model128, int8_decoder128, prompt, MAX_LEN_128, 40)
 
 
 def test_logit_difference_against_the_fp16_decoder(fp16_decoder, int8_decoder, prompt):
@@ -112,11 +200,19 @@ def test_logit_difference_against_the_fp16_decoder(fp16_decoder, int8_decoder, p
 
 def test_decode_step_attention_against_float32(model, cfg, prompt):
     """One decode step's attention output at module level within 2e-3 of torch float32 attention over the dequantised cache."""
+    _decode_step_attention_against_float32(model, cfg, MAX_LEN)
+
+
+def test_decode_step_attention_against_float32_head_size_128(model128, cfg128):
+    _decode_step_attention_against_float32(model128, cfg128, MAX_LEN_128)
+
+
+def _decode_step_attention_against_float32(model, cfg, max_len):
     from eetq_amd.utils.kv_cache import Int8StaticCache
     import eetq_amd.modules.llama_modules as lm
     attn = model.model.layers[0].self_attn
     h, hkv, d = attn.num_heads, attn.num_key_value_heads, attn.head_dim
-    cache = Int8StaticCache(cfg, MAX_LEN).allocate(2, DEV)
+    cache = Int8StaticCache(cfg, max_len).allocate(2, DEV)
     g = torch.Generator().manual_seed(3)
     x = (torch.randn(2, 12, 256, generator=g) * 0.5).half().to(DEV)
     x1 = (torch.randn(2, 1, 256, generator=g) * 0.5).half().to(DEV)
@@ -140,7 +236,7 @@ def test_decode_step_attention_against_float32(model, cfg, prompt):
     p = torch.softmax(torch.einsum("bhd,bhsd->bhs", q.float(), kd) * attn.scaling, dim=-1)
     ref = torch.einsum("bhs,bhsd->bhd", p, vd).reshape(2, 1, h * d)
     err = (seen["attn"].float() - ref).abs().max().item()
-    print("kv8 decoder: decode-step attention against float32 over the dequantised cache: %.3e" % err)
+    print("kv8 decoder: decode-step attention (head size %d) against float32 over the dequantised cache: %.3e" % (d, err))
     assert err < 2e-3
 
 

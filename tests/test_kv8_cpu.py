@@ -55,6 +55,73 @@ def test_quantiser_edge_rows():
     assert k8c.hot_value(np.array([[3, -5]], dtype=np.int8), np.array([0.5], dtype=np.float16)).tolist() == [[1.5, -2.5]]
 
 
+def test_edge_row_builders_deliver_what_the_gpu_tests_rely_on():
+    """tests/test_gpu_kv8_edges.py feeds `edge_rows` to the GPU writers and expects `quantize_rows` of them.  Pinned here, on the
+    NumPy quantiser alone: the tie rows are ties, the tiny rows reach the subnormal scales and the clamp, every sweep row
+    peaks at its own channel under a scale of its own."""
+    total = 0
+    for D in (64, 128):
+        fam = k8c.edge_rows(D)
+        rows, where = k8c.edge_rows_flat(D)
+        assert rows.dtype == np.float16 and rows.shape == (sum(len(r) for r in fam.values()), D)
+        assert list(fam) == ["ties", "tiny", "extreme", "sweep", "zero"] and np.isfinite(rows.astype(np.float64)).all()
+        assert not (np.signbit(rows) & (rows == 0)).any(), "no -0: the identity rotation returns the row bit for bit"
+        total += len(rows)
+        # ties: scale 2^e exactly, every other element an exact k + 0.5 quotient, every k with both signs, away from zero
+        t = fam["ties"]
+        q, s = k8c.quantize_rows(t)
+        per_e = len(t) // len(k8c.TIE_EXPONENTS)
+        assert len(t) == 2 * len(k8c.TIE_EXPONENTS) * -(-127 // (D - 1))
+        seen = set()
+        for i, e in enumerate(k8c.TIE_EXPONENTS):
+            blk = slice(i * per_e, (i + 1) * per_e)
+            assert (s[blk].astype(np.float64) == 2.0 ** e).all()
+            r = t[blk].astype(np.float32) / s[blk].astype(np.float32)[:, None]          # the quantiser's own fp32 quotient
+            assert (np.abs(r[:, 0]) == 127).all() and (np.abs(q[blk][:, 0]) == 127).all()
+            frac = np.abs(r[:, 1:]).astype(np.float64)
+            assert (frac - np.floor(frac) == 0.5).all(), "exact halves"
+            assert (np.abs(q[blk][:, 1:].astype(np.float64)) == np.floor(frac) + 1).all() and (np.sign(q[blk][:, 1:]) == np.sign(r[:, 1:])).all()
+            seen |= {(e, float(x)) for x in r[:, 1:].ravel()}
+        assert seen == {(e, sg * (k + 0.5)) for e in k8c.TIE_EXPONENTS for k in range(127) for sg in (1, -1)}
+        # round-to-nearest-even would give other bytes at every even k
+        even = np.floor(np.abs(t[:, 1:].astype(np.float64) / s.astype(np.float64)[:, None])) % 2 == 0
+        assert even.sum() >= 2 * 64 * len(k8c.TIE_EXPONENTS)
+        # tiny: the subnormal scales, a non-zero row whose scale is 0, and the clamp
+        y = fam["tiny"]
+        q, s = k8c.quantize_rows(y)
+        units = np.rint(y.astype(np.float64) / k8c.U)
+        assert np.array_equal(units * k8c.U, y.astype(np.float64)) and np.abs(units).max(-1).tolist() == list(k8c.TINY_N)
+        assert s.view(np.uint16).tolist() == [0, 0, 1, 1, 1, 2, 2, 8]
+        assert all(n // 2 in np.abs(units[i]) and 1 in np.abs(units[i]) for i, n in enumerate(k8c.TINY_N))
+        assert y[:2].any(-1).all() and not q[:2].any(), "scale 0 on a non-zero row: bytes 0"
+        i190 = k8c.TINY_N.index(190)
+        quot = y[i190].astype(np.float32) / s[i190].astype(np.float32)
+        assert np.abs(quot).max() == 190 > 127.5 and np.abs(q[i190].astype(np.int32)).max() == 127, "clamped from 190"
+        assert (np.abs(quot) > 127.5).sum() >= 1 and np.abs(q.astype(np.int32)).max() == 127
+        # extreme: scale 516, +-258 are exact halves
+        x = fam["extreme"]
+        q, s = k8c.quantize_rows(x)
+        assert x.shape == (1, D) and float(s[0]) == 516.0 and x[0, :4].tolist() == [-65504.0, 258.0, -258.0, 65504.0]
+        assert q[0, :4].tolist() == [-127, 1, -1, 127] and q[0, 4:11].tolist() == [2, -3, 4, -5, 6, -7, 8]
+        # sweep: the maximum of row c sits at channel c, signs alternate, the D scales are pairwise distinct
+        w = fam["sweep"]
+        q, s = k8c.quantize_rows(w)
+        a = np.abs(w.astype(np.float64))
+        c = np.arange(D)
+        assert w.shape == (D, D) and np.array_equal(a.argmax(-1), c)
+        assert np.array_equal(w[c, c], ((1.0 + c / D) * np.where(c % 2 == 0, 1.0, -1.0)).astype(np.float16))
+        a[c, c] = 0
+        assert a.max() <= 0.5 and len(set(s.view(np.uint16).tolist())) == D
+        assert np.array_equal(q[c, c], np.where(c % 2 == 0, 127, -127))
+        q, s = k8c.quantize_rows(fam["zero"])
+        assert fam["zero"].shape == (1, D) and s[0] == 0 and not q.any()
+        # the identity table
+        tab = k8c.identity_table(D, 5)
+        assert tab.dtype == np.float16 and tab.shape == (5, D) and (tab[:, : D // 2] == 1).all() and not tab[:, D // 2:].any()
+        assert np.array_equal(ac.rope_neox_f16(rows[:, None], tab, np.arange(len(rows)) % 5)[:, 0].view(np.uint16), rows.view(np.uint16))
+    assert total <= 300, total
+
+
 def test_quantised_hot_keys_keep_their_gap():
     """What the GPU hot-row families assert before they launch, at both head widths."""
     for D in (64, 128):
