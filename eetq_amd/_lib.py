@@ -110,6 +110,8 @@ def _declare(L):
         "eetq_prefill_attention_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp],
         "eetq_prefill_attention_supported": [i32],
         "eetq_prefill_attention_dev_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp],
+        "eetq_prefill_attention_i8kv_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp,
+                                            vp],
         "eetq_prefill_attention_splits": [i32, i32, i32, i32],
         "eetq_prefill_attention_max_splits": [],
         "eetq_decode_attention_splits": [i32, i32, i32],
@@ -179,6 +181,7 @@ EXPORTED_SYMBOLS = (
     "eetq_prefill_attention_dev_f16", "eetq_prefill_attention_splits", "eetq_prefill_attention_max_splits",
     "eetq_prefill_attention_workspace_floats",
     "eetq_decode_attention_i8kv_f16", "eetq_rope_decode_attention_i8kv_f16", "eetq_rotary_neox_kvcache_prefill_i8_f16",
+    "eetq_prefill_attention_i8kv_f16",
 )
 
 

@@ -369,20 +369,6 @@ int launch_rope_d_i8(const int64_t* kv_len, const int64_t* slots, const int64_t*
     return check_hip(hipGetLastError(), "rope_attn_decode_i8_kernel launch");
 }
 
-// the rules both int8 entries share: cache strides in bytes (8-byte loads), scale strides in fp16 elements (one dword per row)
-int check_i8_cache(const void* kc, const void* vc, const void* scales, int S, const long* cst, const long* sst)
-{
-    for (int i = 0; i < 6; ++i) EETQ_REQUIRE(cst[i] % 8 == 0, "int8 cache strides must be multiples of 8 bytes (8-byte accesses)");
-    EETQ_REQUIRE(((uintptr_t)kc | (uintptr_t)vc) % 8 == 0, "the int8 caches must be 8-byte aligned");
-    for (int i = 0; i < 3; ++i)
-        EETQ_REQUIRE(sst[i] % 2 == 0, "the scale strides must be multiples of 2 elements (one dword per row: k scale, v scale)");
-    EETQ_REQUIRE((uintptr_t)scales % 4 == 0, "the scales must be 4-byte aligned");
-    EETQ_REQUIRE(cst[2] > 0 && cst[5] > 0 && sst[2] > 0 && ((long)S + 4096) * cst[2] < (1L << 31) &&
-                     ((long)S + 4096) * cst[5] < (1L << 31) && ((long)S + 4096) * sst[2] * 2 < (1L << 31),
-                 "one head's cache rows must span less than 2 GiB");
-    return EETQ_OK;
-}
-
 }  // namespace
 
 int launch_attn_decode_i8(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, const f16* mask, f16* out, float* ws,

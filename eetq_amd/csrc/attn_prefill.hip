@@ -20,9 +20,11 @@
 // second product -- two barriers per block -- measured the same: the waves of the two resident workgroups run their phases in step.)  Two workgroups per CU (<= 256 registers: everything in the
 // architectural file, no accumulator copies).    Blocks beyond a wave's last query row are skipped by that wave; heavy query blocks are
 // dispatched first (1-D grid ordered by weight).
+// The device-length and split forms also run over an int8 KV cache (KV8, kv_i8.hpp): see the comment above the kernel.
 #include <type_traits>
 
 #include "common.hpp"
+#include "kv_i8.hpp"
 
 namespace eetq {
 
@@ -57,15 +59,36 @@ struct PrefillDevArgs : PrefillArgs {
 };
 constexpr int kPfHost = 0, kPfDev = 1, kPfSplit = 2;
 constexpr int kPfMaxSplits = 16;
+// The int8-row form (KV8; kv_i8.hpp): k and v point at int8 rows, their strides are in BYTES, and the row's scale
+// pair (k scale, v scale) lies in `scales`.  Behind the fp16 forms' arguments, which keep their kernarg blocks.
+struct PrefillDevArgs8 : PrefillDevArgs {
+    const f16* scales;
+    long       s_sb, s_sh, s_ss;   // fp16 elements between batch rows, kv heads, rows of the scale tensor
+};
+template <int MODE, bool KV8>
+using PrefillKernArgs = std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>;
 
 // MODE kPfHost: keys and causal offset from the host (the fresh prompt's path, unchanged).  kPfDev: every workgroup reads the length
 // at entry -- one scalar load -- and forms Tk and koff itself; kend, nblk, the descriptors' range, `active` and `edge` follow, the
 // grid depends on Tq alone.  kPfSplit: workgroup id / ns is the (query block, head, batch row) of the other forms, id % ns its
 // share [i nblk / ns, (i + 1) nblk / ns) of that workgroup's key blocks; it leaves (o, m, l) per row in the workspace, an empty
 // share or a row with nothing to attend as (zeros, -inf, 0), and prefill_merge_kernel divides.
-template <int D, int MODE>
-__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs> a_in)
+//
+// KV8 (kPfDev and kPfSplit only): the same tiles over an int8 cache.  What changes is fetch and stage:
+//   * a thread's share of a row is 8 bytes -- the same (rows p4 .. p4 + NLD - 1, chunk c16) ownership with 8-byte loads -- and the
+//     rows' scale dwords come through a third descriptor that ends at the valid length as well: a row at or beyond Tk reads as
+//     bytes 0, scale 0;
+//   * K bytes enter the swizzled image as exact fp16 integers (kv8_unpack8) and the K scale is folded into the score in fp32 behind
+//     the product, before the mask and the maximum: (ks * scaling) * (q . k8), the decode entries' contract.  The tile's 64 K scales
+//     sit in LDS as fp32, per buffer;
+//   * a V row enters the transposed image as fp16(vs * v8): one packed fp16 multiply of the exact integer by the row's scale, a single
+//     rounding of the exact product, denormals kept.  THE ONE DIFFERENCE from the decode entries, which fold vs into the probability
+//     in fp32: here 2^12 p * vs would leave the fp16 range (vs spans 2^-24 .. 516).  A row that holds all the weight still comes out
+//     as fp16(vs * v8) bit for bit.
+template <int D, int MODE, bool KV8 = false>
+__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8> a_in)
 {
+    static_assert(!KV8 || MODE != kPfHost, "the int8-row form takes the device-length arguments");
     PrefillArgs a = a_in;
     int         wg = (int)blockIdx.x, split = 0;
     if constexpr (MODE != kPfHost) {
@@ -90,6 +113,7 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::
     // land, one barrier per block
     __shared__ __attribute__((aligned(16))) f16 k_lds2[2][kPfBN * D];
     __shared__ __attribute__((aligned(16))) f16 vt_lds2[2][D * VT_PITCH];
+    __shared__ __attribute__((aligned(16))) float ks_lds2[2][KV8 ? kPfBN : 1];   // KV8: the tile's K scales
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, ln = lane & 31, hi = lane >> 5;
     // (wave in a scalar register: the per-wave tests below -- block skipped, block on the diagonal -- must be branches, not selects)
@@ -109,10 +133,23 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::
         j1 = (int)((long)(split + 1) * nblk / a_in.ns);
     }
     // the valid rows of this (batch row, kv head) behind buffer descriptors: rows at and beyond Tk are out of range and read as zeros
-    const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.k + b * a.k_sb + hk * a.k_sh), 0,
-                                                                         (int)((unsigned)a.Tk * (unsigned)a.k_ss * 2u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.v + b * a.v_sb + hk * a.v_sh), 0,
-                                                                         (int)((unsigned)a.Tk * (unsigned)a.v_ss * 2u), 0x00020000);
+    // (KV8: the same three lines with strides in bytes, and the rows' scale dwords behind a third descriptor)
+    constexpr unsigned EB = KV8 ? 1u : 2u;   // bytes per unit of the cache strides
+    __amdgpu_buffer_rsrc_t krs, vrs, srs;
+    if constexpr (KV8) {
+        const char* kbase = reinterpret_cast<const char*>(a.k) + b * a.k_sb + hk * a.k_sh;
+        const char* vbase = reinterpret_cast<const char*>(a.v) + b * a.v_sb + hk * a.v_sh;
+        krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kbase), 0, (int)((unsigned)a.Tk * (unsigned)a.k_ss), 0x00020000);
+        vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(vbase), 0, (int)((unsigned)a.Tk * (unsigned)a.v_ss), 0x00020000);
+        srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a_in.scales + b * a_in.s_sb + hk * a_in.s_sh), 0,
+                                                (int)((unsigned)a.Tk * (unsigned)a_in.s_ss * 2u), 0x00020000);
+    } else {
+        krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.k + b * a.k_sb + hk * a.k_sh), 0,
+                                                (int)((unsigned)a.Tk * (unsigned)a.k_ss * 2u), 0x00020000);
+        vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.v + b * a.v_sb + hk * a.v_sh), 0,
+                                                (int)((unsigned)a.Tk * (unsigned)a.v_ss * 2u), 0x00020000);
+        srs = krs;   // not used
+    }
 
     // ---- the wave's query rows as B fragments: lane (ln, hi) holds channels 16 ks + 8 hi .. + 7 of row ln ----
     f16x8 qf[KS];
@@ -133,15 +170,51 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::
     // two at D = 64) -- so that the transposed V image is written as 8- / 4-byte pieces (NLD keys of one channel: 8 LDS writes per
     // thread and tile; 2-byte writes, 64 of them, kept the LDS pipe busy for ~4 000 cycles per tile and workgroup)
     static_assert((NLD == 4 && CH == 16) || (NLD == 2 && CH == 8), "rows per thread");
-    u32x4 kreg[NLD], vreg[NLD];
+    // KV8: the chunk is the row's 8 bytes of the same 8 channels, and every thread also holds its rows' scale dwords (the CH threads
+    // of a row read the same address); the rows' V scales are needed by all of them, the K scales go to LDS from chunk 0's thread
+    using StageReg = std::conditional_t<KV8, u32x2, u32x4>;
+    StageReg  kreg[NLD], vreg[NLD];
+    u32       sreg[KV8 ? NLD : 1];
     const int c16 = tid % CH, p4 = NLD * (tid / CH);
-    const int krow_b = (int)(a.k_ss * 2), vrow_b = (int)(a.v_ss * 2);
-    const int kvo = p4 * krow_b + c16 * 16, vvo = p4 * vrow_b + c16 * 16;  // constant; tile and row offsets ride in the scalar operand
+    const int krow_b = (int)(a.k_ss * EB), vrow_b = (int)(a.v_ss * EB);
+    constexpr int CB = KV8 ? 8 : 16;       // bytes of a thread's chunk in the cache
+    const int kvo = p4 * krow_b + c16 * CB, vvo = p4 * vrow_b + c16 * CB;  // constant; tile and row offsets ride in the scalar operand
+    int srow_b = 0, svo = 0;
+    if constexpr (KV8) srow_b = (int)(a_in.s_ss * 2), svo = p4 * srow_b;
     auto fetch = [&](int j) {
 #pragma unroll
         for (int r = 0; r < NLD; ++r) {
-            kreg[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, kvo, (j * kPfBN + r) * krow_b, 0));
-            vreg[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, vvo, (j * kPfBN + r) * vrow_b, 0));
+            if constexpr (KV8) {
+                kreg[r] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(krs, kvo, (j * kPfBN + r) * krow_b, 0));
+                vreg[r] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(vrs, vvo, (j * kPfBN + r) * vrow_b, 0));
+                sreg[r] = __builtin_amdgcn_raw_buffer_load_b32(srs, svo, (j * kPfBN + r) * srow_b, 0);
+            } else {
+                kreg[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, kvo, (j * kPfBN + r) * krow_b, 0));
+                vreg[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, vvo, (j * kPfBN + r) * vrow_b, 0));
+            }
+        }
+    };
+    // KV8: 8 bytes -> the 16-byte chunk the fp16 form holds; K as the exact integers, V as fp16(vs * v8)
+    auto chunk8 = [](const u32x2& w) {
+        f16x2 h[4];
+        kv8_unpack8(w, h);
+        return f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+    };
+    auto kchunk = [&](int r) {
+        if constexpr (KV8) return __builtin_bit_cast(u32x4, chunk8(kreg[r]));
+        else return kreg[r];
+    };
+    auto vchunk = [&](int r) {
+        if constexpr (KV8) {
+            f16x2 h[4];
+            kv8_unpack8(vreg[r], h);
+            const f16   vs  = as_f16x2(sreg[r])[1];
+            const f16x2 vs2 = {vs, vs};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) h[i] = h[i] * vs2;   // one rounding of the exact product
+            return f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+        } else {
+            return __builtin_bit_cast(f16x8, vreg[r]);
         }
     };
     // K rows: 16-byte chunks XOR-swizzled by (row & (CH - 1)).  V^T image: channel row d, key column key ^ (((d >> 5) & 3) << 3): a
@@ -150,11 +223,17 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::
         f16* kl = k_lds2[buf];
         f16* vl = vt_lds2[buf];
 #pragma unroll
-        for (int r = 0; r < NLD; ++r) *reinterpret_cast<u32x4*>(kl + (p4 + r) * D + 8 * (c16 ^ ((p4 + r) & (CH - 1)))) = kreg[r];
+        for (int r = 0; r < NLD; ++r) *reinterpret_cast<u32x4*>(kl + (p4 + r) * D + 8 * (c16 ^ ((p4 + r) & (CH - 1)))) = kchunk(r);
+        if constexpr (KV8) {
+            if (c16 == 0) {
+#pragma unroll
+                for (int r = 0; r < NLD; ++r) ks_lds2[buf][p4 + r] = (float)as_f16x2(sreg[r])[0];
+            }
+        }
         f16* vp = vl + 8 * c16 * VT_PITCH + (p4 ^ (((c16 >> 2) & 3) << 3));
-        const f16x8 v0 = __builtin_bit_cast(f16x8, vreg[0]), v1 = __builtin_bit_cast(f16x8, vreg[1]);
+        const f16x8 v0 = vchunk(0), v1 = vchunk(1);
         if constexpr (NLD == 4) {
-            const f16x8 v2 = __builtin_bit_cast(f16x8, vreg[2]), v3 = __builtin_bit_cast(f16x8, vreg[3]);
+            const f16x8 v2 = vchunk(2), v3 = vchunk(3);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const f16x2 lo = {v0[e], v1[e]}, hh = {v2[e], v3[e]};
@@ -198,6 +277,19 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const std::
                     const f16x8 kf = *reinterpret_cast<const f16x8*>(k_lds + krow * D + 8 * ((2 * ks + hi) ^ (krow & (CH - 1))));
                     s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[kb], 0, 0, 0);
                 }
+            // KV8: the K scale into the score, in fp32: accumulator values 4 g .. 4 g + 3 are keys 32 kb + 8 g + 4 hi + {0..3}, one
+            // 16-byte read (the same address across ln)
+            if constexpr (KV8) {
+                const float* ksl = ks_lds2[j & 1] + 4 * hi;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 sc = *reinterpret_cast<const f32x4*>(ksl + 32 * kb + 8 * g);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) s[kb][4 * g + i] *= sc[i];
+                    }
+            }
             // ---- mask (only where the block touches the wave's diagonal or the end of the keys: a wave-uniform branch), running maximum
             // (scaled domain) ----
             const bool edge = key0 + kPfBN - 1 > q0 + wave * 32 + a.koff || key0 + kPfBN > a.Tk;
@@ -429,6 +521,51 @@ int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* 
         launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     }
     return check_hip(hipGetLastError(), "prefill_attn_kernel (split) launch");
+}
+
+// launch_prefill_attention_dev over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of
+// the scale pairs in fp16 elements.  Always the device-length kernel (kv_len nullptr: max_keys keys), or the split form and the merge.
+int launch_prefill_attention_i8kv(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, f16* out, float* ws, int B, int H,
+                                  int Hkv, int Tq, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling,
+                                  const long* st, const long* sst, hipStream_t stream)
+{
+    EETQ_REQUIRE(q && k && v && scales && out && st && sst, "null pointer");
+    EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
+    EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
+    EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0, "invalid attention shape");
+    if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
+    for (int i = 0; i < 3; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q strides must be multiples of 8 elements (16-byte loads)");
+    for (int i = 9; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "out strides must be multiples of 4 elements");
+    EETQ_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)out % 8 == 0, "q must be 16-byte aligned, out 8-byte");
+    const int rc = check_i8_cache(k, v, scales, max_keys, st + 3, sst);
+    if (rc != EETQ_OK) return rc;
+    EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
+    PrefillDevArgs8 a;
+    fill_prefill_args(a, q, reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v), out, B, H, Hkv, Tq, max_keys, max_keys - Tq,
+                      scaling, st);
+    a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits;
+    a.scales = scales, a.s_sb = sst[0], a.s_sh = sst[1], a.s_ss = sst[2];
+    const long wgs = (long)a.nqb * H * B * splits;
+    EETQ_REQUIRE(wgs < (1L << 31), "too many workgroups");
+    const dim3 grid((unsigned)wgs), block(kPfThreads);
+    if (splits == 1) {
+        if (D == 128)
+            launch_kernel(prefill_attn_kernel<128, kPfDev, true>, grid, block, 0, stream, a);
+        else
+            launch_kernel(prefill_attn_kernel<64, kPfDev, true>, grid, block, 0, stream, a);
+        return check_hip(hipGetLastError(), "prefill_attn_kernel (int8 rows) launch");
+    }
+    const long rows = (long)B * H * Tq, threads = rows * (D / 4);
+    EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
+    const dim3 mgrid((unsigned)((threads + 255) / 256));
+    if (D == 128) {
+        launch_kernel(prefill_attn_kernel<128, kPfSplit, true>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    } else {
+        launch_kernel(prefill_attn_kernel<64, kPfSplit, true>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    }
+    return check_hip(hipGetLastError(), "prefill_attn_kernel (int8 rows, split) launch");
 }
 
 }  // namespace eetq

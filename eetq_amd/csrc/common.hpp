@@ -355,6 +355,10 @@ int launch_rope_attn_decode_i8(const int64_t* positions, const int64_t* slots, i
                                float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
                                const long* st, const long* scale_strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance,
                                long table_rows, hipStream_t stream);
+// prompt attention behind int8 rows (attn_prefill.hip): launch_prefill_attention_dev with the k / v strides in bytes
+int launch_prefill_attention_i8kv(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, f16* out, float* ws, int B, int H,
+                                  int Hkv, int Tq, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling,
+                                  const long* st, const long* sst, hipStream_t stream);
 int launch_rotary_kvcache_i8(const int64_t* pos, const int64_t* first_row_dev, f16* q, f16* k, const f16* v, const f16* cache,
                              int8_t* kcache, int8_t* vcache, f16* scales, int batch, int tokens, int first_row, int q_heads,
                              int k_heads, int head_size, int rot_dim, const long* st, const long* sst, int max_pos, long table_rows,

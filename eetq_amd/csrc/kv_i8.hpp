@@ -47,4 +47,19 @@ __device__ __forceinline__ void kv8_unpack8(const u32x2& w, f16x2 (&h)[4])
     h[3] = as_f16x2(__builtin_amdgcn_perm(x1, c64, 0x00070006u)) - bias;
 }
 
+// the rules every attention entry over an int8 cache shares (attn_decode_i8.hip, attn_prefill.hip): cache strides {k_b, k_h, k_pos,
+// v_b, v_h, v_pos} in bytes (8-byte loads), scale strides in fp16 elements (one dword per row)
+inline int check_i8_cache(const void* kc, const void* vc, const void* scales, int S, const long* cst, const long* sst)
+{
+    for (int i = 0; i < 6; ++i) EETQ_REQUIRE(cst[i] % 8 == 0, "int8 cache strides must be multiples of 8 bytes (8-byte accesses)");
+    EETQ_REQUIRE(((uintptr_t)kc | (uintptr_t)vc) % 8 == 0, "the int8 caches must be 8-byte aligned");
+    for (int i = 0; i < 3; ++i)
+        EETQ_REQUIRE(sst[i] % 2 == 0, "the scale strides must be multiples of 2 elements (one dword per row: k scale, v scale)");
+    EETQ_REQUIRE((uintptr_t)scales % 4 == 0, "the scales must be 4-byte aligned");
+    EETQ_REQUIRE(cst[2] > 0 && cst[5] > 0 && sst[2] > 0 && ((long)S + 4096) * cst[2] < (1L << 31) &&
+                     ((long)S + 4096) * cst[5] < (1L << 31) && ((long)S + 4096) * sst[2] * 2 < (1L << 31),
+                 "one head's cache rows must span less than 2 GiB");
+    return EETQ_OK;
+}
+
 }  // namespace eetq

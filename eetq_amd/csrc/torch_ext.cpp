@@ -918,6 +918,51 @@ Tensor decode_attention_i8kv(const Tensor& query, const Tensor& key_cache, const
     return out;
 }
 
+// prefill_attention's device-length / split form over an int8 cache (eetq_prefill_attention_i8kv_f16): query [B, T, H, D] (any token
+// / head strides), the first `max_keys` rows of the caches, or clamp(*kv_len + kv_len_bias, 0, max_keys) of them; [B, T, H, D] contiguous
+Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
+                              int64_t max_keys, std::optional<double> scaling, const OptTensor& kv_len, int64_t kv_len_bias,
+                              std::optional<int64_t> splits_in, const OptTensor& workspace)
+{
+    const char* name = "prefill_attention_i8kv: ";
+    TORCH_CHECK(query.scalar_type() == at::kHalf && query.is_cuda() && query.dim() == 4 && query.stride(-1) == 1 && key_cache.dim() == 4,
+                name, "expected a float16 CUDA query [B, T, H, D] with dense D");
+    const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key_cache.size(1);
+    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && T > 0 && max_keys > 0 && max_keys <= key_cache.size(2), name, "shape mismatch");
+    TORCH_CHECK(prefill_attention_supported(D), name, "unsupported head_dim");
+    TORCH_CHECK(kv_len || kv_len_bias == 0, name, "kv_len_bias needs kv_len");
+    if (kv_len)
+        TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(), name,
+                    "kv_len must be a one-element int64 tensor on the query's device");
+    const double  sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
+    const int64_t splits = splits_in ? *splits_in : prefill_attention_splits(B, H, T, max_keys);
+    TORCH_CHECK(splits >= 1 && splits <= eetq_prefill_attention_max_splits(), name, "splits must lie in 1 .. ",
+                eetq_prefill_attention_max_splits());
+    const int64_t need = (int64_t)eetq_prefill_attention_workspace_floats((int)B, (int)H, (int)T, (int)D, (int)splits);
+    Tensor        ws;
+    if (workspace) {
+        TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
+                        workspace->numel() >= need,
+                    name, "workspace must be a contiguous float32 tensor of at least ", need, " elements on the query's device");
+        ws = *workspace;
+    } else if (need > 0) {
+        ws = torch::empty({need}, query.options().dtype(at::kFloat));
+    }
+    Tensor     out = torch::empty({B, T, H, D}, query.options());
+    const long st[12] = {(long)query.stride(0),       (long)query.stride(1),       (long)query.stride(2),     (long)key_cache.stride(0),
+                         (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
+                         (long)value_cache.stride(1), (long)value_cache.stride(2), (long)out.stride(0),       (long)out.stride(1),
+                         (long)out.stride(2)};
+    const long sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_prefill_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), out.data_ptr(),
+                                          ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)max_keys,
+                                          (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, (int)splits, (float)sc,
+                                          st, sst, stream_of(query)));
+    return out;
+}
+
 Tensor rope_decode_attention_i8kv(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
                                   const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& scales,
                                   Tensor& tickets, const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
@@ -1902,6 +1947,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
           "causal attention of a prompt's query rows [B, T, H, D] over the first `keys` rows of a KV cache [B, Hkv, S, D] (MFMA)");
+    m.def("prefill_attention_i8kv", &prefill_attention_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
+          py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
+          "prefill_attention behind an int8 KV cache: a prompt's query rows [B, T, H, D] over the dequantised first rows of the cache");
     m.def("prefill_attention_supported", &prefill_attention_supported, py::arg("head_dim"));
     m.def("prefill_attention_splits", &prefill_attention_splits, py::arg("batch"), py::arg("heads"), py::arg("q_tokens"), py::arg("max_keys"),
           "the split count prefill_attention uses with splits=None (1 = unsplit)");

@@ -42,20 +42,27 @@ def fresh_static_prefill():
 
 
 @contextlib.contextmanager
-def appended_static_prefill():
+def appended_static_prefill(int8_rows=False):
     """The caller's promise for the forwards run inside (per thread): the prompt is unpadded and the static cache's rows
     0 .. counter - 1 are this sequence's real tokens, so a prompt appended behind them attends exactly the rows below the
     advanced counter, causally among its own.  The attention blocks write the rows as they do without the promise (behind the
     device counter, which they advance) and then call the library's prompt kernel with the counter as its DEVICE length
     (``ops.prefill_attention(..., kv_len=counter)``: no host read, half the key blocks of a masked pass over the whole
     pre-allocated cache) and ignore the model-level mask.  ``GraphDecoder`` makes this promise for the later pieces of a
-    chunked prompt and for ``append=True``.  Inside it ``fresh_static_prefill`` does not hold."""
-    prev = getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False)
-    _prefill_promise.appended, _prefill_promise.fresh = True, False
+    chunked prompt and for ``append=True``.  Inside it ``fresh_static_prefill`` does not hold.
+
+    ``int8_rows=True`` adds a further promise (per thread, restored on exit like the other two), and it is the caller's
+    acceptance of what an appended prompt means on an INT8 cache (``Int8StaticCache``): the prompt's rows are written first
+    (rotated, quantised, behind the device counter) and the prompt then attends the DEQUANTISED rows 0 .. counter - 1 through
+    ``ops.prefill_attention_i8kv`` -- its own keys and values as their quantised selves, as a decode step sees them.  Without it
+    a prompt appended behind int8 rows raises; on an fp16 cache the flag changes nothing."""
+    prev = (getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False),
+            getattr(_prefill_promise, "int8_rows", False))
+    _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = True, False, bool(int8_rows)
     try:
         yield
     finally:
-        _prefill_promise.appended, _prefill_promise.fresh = prev
+        _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = prev
 
 
 class EETRotaryEmbedding(nn.Module):
@@ -159,7 +166,9 @@ class _EETAttentionBase(nn.Module):
         projection output, q and k not rotated yet) -> [B, T, H * D].  A single token is one launch (rotation, quantising
         cache write, attention over the int8 rows); a promised-fresh prompt is the quantising write from row 0 followed by
         the prompt kernel on the UNQUANTISED rotated K and the V where they lie in the projection output -- the prompt's
-        output is the fp16-cache path's bit for bit, only the cache is quantised."""
+        output is the fp16-cache path's bit for bit, only the cache is quantised.  A prompt promised appended WITH
+        ``int8_rows=True`` is the quantising write behind the device counter, the counter's advance, and the prompt kernel's
+        int8-row form over the dequantised rows below the counter (its own among them): no host read, capturable."""
         bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
         if (d not in (64, 128) or not q.is_cuda or q.dtype != torch.float16 or self.decode_math_attention is not True
                 or kwargs.get("output_attentions", False) or layer.keys.shape[0] != bsz
@@ -188,10 +197,24 @@ class _EETAttentionBase(nn.Module):
                 out = ops.decode_attention_i8kv(q[:, 0], layer.keys, layer.values, layer.scales, mask=add, scaling=self.scaling,
                                                 kv_len=counter, kv_len_bias=1, advance=counter)
             return out.reshape(bsz, q_len, -1)
+        if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False)
+                and getattr(_prefill_promise, "int8_rows", False)):
+            if q_len > rows:
+                raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
+            if not self.mfma_prefill or ops.prefill_attention_i8kv is None:
+                raise NotImplementedError("EETLlamaAttention: a prompt appended behind int8 rows runs on the MFMA prompt kernel "
+                                          "alone (mfma_prefill=True and the compiled operator module); no stock path reads int8 "
+                                          "K and V")
+            ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales,
+                                                         first_row_dev=counter)
+            counter.add_(q_len)
+            out = ops.prefill_attention_i8kv(q, layer.keys, layer.values, layer.scales, rows, scaling=self.scaling, kv_len=counter)
+            return out.reshape(bsz, q_len, -1)
         if not getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False):
             raise NotImplementedError("EETLlamaAttention: a prompt on an int8 KV cache must be promised fresh "
                                       "(fresh_static_prefill: empty cache, unpadded prompt); a prompt appended behind int8 rows "
-                                      "needs the MFMA prompt kernel to read int8 K and V, which is not built yet")
+                                      "attends quantised rows -- the MFMA prompt kernel reads int8 K and V only under "
+                                      "appended_static_prefill(int8_rows=True) (GraphDecoder(kv8_append=True))")
         if q_len > rows:
             raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
         ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales)

@@ -52,6 +52,7 @@ if _C is not None:
     prefill_attention = _C.prefill_attention                        # compiled boundary only (None -> torch's attention)
     prefill_attention_supported = _C.prefill_attention_supported
     prefill_attention_splits = _C.prefill_attention_splits
+    prefill_attention_i8kv = _C.prefill_attention_i8kv              # compiled boundary only, as prefill_attention
     w8_a16_gemv_grouped = _C.w8_a16_gemv_grouped
     llama_decode_layer = _C.llama_decode_layer   # compiled boundary only: its point is the interpreter time it saves
     w8_a16_moe = _C.w8_a16_moe                   # compiled boundary only (the ctypes twin refuses it)
@@ -82,6 +83,7 @@ else:
     prefill_attention = None
     prefill_attention_supported = None
     prefill_attention_splits = None
+    prefill_attention_i8kv = None
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",

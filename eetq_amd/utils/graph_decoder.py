@@ -16,7 +16,7 @@ __all__ = ["GraphDecoder"]
 
 
 class GraphDecoder:
-    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16):
+    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -31,11 +31,21 @@ class GraphDecoder:
         launches and tokens as they were.
         ``kv_bits``: 16 (the default: an fp16 ``StaticCache``) or 8: an ``Int8StaticCache`` (``utils/kv_cache.py``: int8 rows with a
         scale pair each, ``2 D + 4`` bytes per row against ``4 D``), written and read by the accelerated attention blocks' int8
-        kernels.  It needs the lean layer-by-layer model with head size 64 or 128, and runs fresh whole prompts only:
-        ``append=True`` and chunked prompts raise ``ValueError`` (prompts behind int8 rows are a follow-up)."""
+        kernels.  It needs the lean layer-by-layer model with head size 64 or 128, and by default runs fresh whole prompts only:
+        ``append=True`` and chunked prompts raise ``ValueError``.
+        ``kv8_append`` (``kv_bits=8`` only; default ``False``): the opt-in for ``append=True``, ``prefill_chunk=`` and
+        ``prefill(chunk=, append=)`` on the int8 cache, and the acceptance of what they mean there: a piece behind cached rows
+        writes its rows first and then attends the DEQUANTISED rows 0 .. counter - 1 (``ops.prefill_attention_i8kv``), its own keys
+        and values as their quantised selves, as a decode step does.  A chunked prompt is therefore NOT bit-identical to the
+        whole prompt on an int8 cache: the first piece of an emptied cache stays on the fresh path (unquantised keys, the fp16
+        decoder's bits), later pieces see quantised earlier rows.  The captured decode graphs are reused as they
+        are after an append."""
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
+        if kv8_append and kv_bits != 8:
+            raise ValueError("GraphDecoder: kv8_append=True is the opt-in of an int8 cache (kv_bits=8), got kv_bits=%r" % (kv_bits,))
         self.kv_bits = int(kv_bits)
+        self.kv8_append = bool(kv8_append)
         self.lean = bool(lean)
         self.sampling = bool(sampling)
         self.model = model
@@ -177,9 +187,9 @@ class GraphDecoder:
         row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
         finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on."""
         B, P = prompt.shape
-        if self.kv_bits == 8 and (append or prefill_chunk is not None):
-            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only: append=True and "
-                             "prefill_chunk need the prompt kernel to read int8 rows (not built yet)")
+        if self.kv_bits == 8 and not self.kv8_append and (append or prefill_chunk is not None):
+            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
+                             "built with kv8_append=True: append=True and prefill_chunk then attend quantised rows")
         append = bool(append) and (self.rows > 0 or self._pending)
         feed = torch.cat([self.s_tok, prompt], dim=1) if append and self._pending else prompt
         start = self.rows if append else 0
@@ -231,11 +241,12 @@ class GraphDecoder:
         prompt runs in pieces of at most ``c`` tokens, each behind the rows already written (activations are [batch, c, .]
         instead of [batch, P, .]).  ``append=True``: the prompt starts behind the rows the cache holds (``self.rows``) instead
         of emptying it.  Accelerated models attend the first piece of an emptied cache under ``fresh_static_prefill`` and every
-        other piece under ``appended_static_prefill``; other models run the same calls on their stock path."""
+        other piece under ``appended_static_prefill`` (``int8_rows=True`` on a decoder built with ``kv8_append=True``); other
+        models run the same calls on their stock path."""
         P = prompt.shape[1]
-        if self.kv_bits == 8 and (append or chunk is not None):
-            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only: append=True and chunk= "
-                             "need the prompt kernel to read int8 rows (not built yet)")
+        if self.kv_bits == 8 and not self.kv8_append and (append or chunk is not None):
+            raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
+                             "built with kv8_append=True: append=True and chunk= then attend quantised rows")
         start = self.rows if append else 0
         if start + P > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))
@@ -261,7 +272,7 @@ class GraphDecoder:
             elif c0 == 0 and not append:
                 ctx = fresh_static_prefill()
             else:   # behind rows 0 .. start + c0 - 1, which are this sequence's tokens (llama_modules.appended_static_prefill)
-                ctx = appended_static_prefill()
+                ctx = appended_static_prefill(int8_rows=True) if self.kv8_append else appended_static_prefill()
             with ctx:
                 out = self.model(prompt[:, c0:c1], past_key_values=self.cache,
                                  cache_position=torch.arange(start + c0, start + c1, device=prompt.device), use_cache=True,

@@ -686,6 +686,26 @@ int    eetq_prefill_attention_splits(int batch, int heads, int q_tokens, int max
 int    eetq_prefill_attention_max_splits(void);
 size_t eetq_prefill_attention_workspace_floats(int batch, int heads, int q_tokens, int head_dim, int splits);
 
+/* eetq_prefill_attention_dev_f16 over an int8 KV cache (the row format above; added within ABI revision 7): a prompt appended behind
+ * int8 rows, its own rows already written (rotated, quantised) and the counter advanced, attends the dequantised rows 0 .. keys - 1,
+ * causally among its own -- a query token sees its own key and value as their quantised selves, as the one-launch decode step does.
+ * kv_len, kv_len_bias, splits and workspace (eetq_prefill_attention_workspace_floats, eetq_prefill_attention_splits) as in
+ * eetq_prefill_attention_dev_f16; kv_len NULL: keys = max_keys.  Rows at and beyond keys are not read.  strides: as the fp16 entry,
+ * with the k / v entries in BYTES; scale_strides (fp16 elements): {batch, head, position}.
+ * Arithmetic: the tiles, the fp32 softmax state, the fp16 probabilities and the split records of the fp16 entry.  K bytes enter the
+ * first product as exact fp16 integers and the K scale is folded into the fp32 score behind it, (ks * scaling) * (q . k8), as in the
+ * decode entries.  ONE DIFFERENCE from the decode entries: a V row enters the second product as fp16(vs * v8) -- one rounding of the
+ * exact product, denormals kept -- instead of vs riding on the probability in fp32 (the probabilities here are fp16 operands carried
+ * as 2^12 p, and 2^12 p * vs would leave the fp16 range).  A row that holds all the weight still comes out as fp16(vs * v8) bit
+ * for bit.
+ * EETQ_ERR_INVALID (nothing launched): the cache, scale and 2 GiB rules of eetq_decode_attention_i8kv_f16 (against max_keys), the q
+ * and out rules of eetq_prefill_attention_f16, a null pointer, max_keys <= 0, splits < 1 or > 16, splits > 1 with a NULL or
+ * misaligned workspace.  EETQ_ERR_UNSUPPORTED: head_dim other than 64 or 128. */
+int eetq_prefill_attention_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales, void* out,
+                                    float* workspace, int batch, int heads, int kv_heads, int q_tokens, int max_keys, int head_dim,
+                                    const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* strides,
+                                    const long* scale_strides, void* stream);
+
 /* Diagnostics: while `stamps` (DEVICE, batch * heads * splits * 8 uint64) is set, every eetq_rope_decode_attention_f16
  * launch of this process records per workgroup the 100 MHz device clock at: 0 entry, 1 scalar reads done, 2 new token
  * rotated, 3 chunk done, 4 chunk record published, 5 ticket drawn, 6 (last workgroup of a head) merge done, 7 output
