@@ -110,6 +110,12 @@ def _declare(L):
         "eetq_prefill_attention_f16": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp],
         "eetq_prefill_attention_supported": [i32],
         "eetq_prefill_attention_dev_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp],
+        "eetq_prefill_attention_padded_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, ctypes.c_float, vp,
+                                              vp],
+        "eetq_decode_attention_padded_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp,
+                                             vp, vp],
+        "eetq_rope_decode_attention_padded_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                                  i32, ctypes.c_float, vp, vp, i32, vp, vp, vp],
         "eetq_prefill_attention_i8kv_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp,
                                             vp],
         "eetq_prefill_attention_splits": [i32, i32, i32, i32],
@@ -182,6 +188,7 @@ EXPORTED_SYMBOLS = (
     "eetq_prefill_attention_workspace_floats",
     "eetq_decode_attention_i8kv_f16", "eetq_rope_decode_attention_i8kv_f16", "eetq_rotary_neox_kvcache_prefill_i8_f16",
     "eetq_prefill_attention_i8kv_f16",
+    "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
 )
 
 

@@ -23,6 +23,8 @@
 // gap 1.1, scalar reads 0.35, new token + rotation 0.8, the chunk's arithmetic 1.5, workgroup merge 0.4, publish 0.5, ticket
 // 0.75, head merge 1.6, store 0.2 -- profiles/r06_attn_stamps.txt, r06_attn_bench.jsonl).  Both forms run the same chunk code
 // and the same merge arithmetic: their outputs are bit-identical.
+// Both forms also exist with a per-row first key (PAD; eetq_*_padded_f16): batch row b of a left-padded batch
+// attends rows [kv_start[b], valid length), its blocks and chunks counted from there.  The plain instantiations are unchanged.
 #include "attn_decode_shared.hpp"
 
 namespace eetq {
@@ -192,11 +194,15 @@ __device__ __forceinline__ KvSrc make_kv_src(const f16* kbase, const f16* vbase,
     return s;
 }
 
-template <int D, bool MASK, bool LONG>
+// PAD: batch row b attends rows [s, Sv), s = kv_start[b] kept inside the valid rows: the K, V and mask bases move by s rows and the
+// valid length is taken relative to s, so blocks and chunks are counted from the row's first real token (the bits of the plain form
+// on that row alone, its cache moved up by s rows) and no row below s is read.
+template <int D, bool MASK, bool LONG, bool PAD = false>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
     const f16* __restrict__ q, const f16* __restrict__ kc, const f16* __restrict__ vc, const f16* __restrict__ mask,
     float* __restrict__ ws, float scaling, int S, int groups, long q_sb, long q_sh, long k_sb, long k_sh,
-    long k_ss, long v_sb, long v_sh, long v_ss, long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias)
+    long k_ss, long v_sb, long v_sh, long v_ss, long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias,
+    const KvStartArg<PAD> kv_start)
 {
     constexpr int NW = kAttnThreads / 64;
     __shared__ float sm_m[NW], sm_l[NW];
@@ -205,11 +211,16 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
     const int split = blockIdx.x, splits = gridDim.x, h = blockIdx.y, b = blockIdx.z, hk = h / groups;
     const int tid = threadIdx.x, d0 = ((tid & 63) % (D / 8)) * 8;
     const int rib = (tid >> 6) * AttnGeo<D>::PPW + (tid & 63) / AttnGeo<D>::LPP;
-    const int Sv = valid_len(S, kv_len, kv_len_bias);
+    int  Sv = valid_len(S, kv_len, kv_len_bias);
+    long s0 = 0;  // PAD: the row's first attended cache row
+    if constexpr (PAD) {
+        s0 = clamp_kv_start(kv_start[b], Sv - 1);
+        Sv -= (int)s0;
+    }
 
     const f16x8 qv  = *reinterpret_cast<const f16x8*>(q + b * q_sb + h * q_sh + d0);
-    const KvSrc src = make_kv_src<D, MASK>(kc + b * k_sb + hk * k_sh, vc + b * v_sb + hk * v_sh, k_ss, v_ss, Sv,
-                                           MASK ? mask + b * m_sb : nullptr);
+    const KvSrc src = make_kv_src<D, MASK>(kc + b * k_sb + hk * k_sh + s0 * k_ss, vc + b * v_sb + hk * v_sh + s0 * v_ss, k_ss, v_ss, Sv,
+                                           MASK ? mask + b * m_sb + s0 : nullptr);
     KvBlocks<kUA> ta;
     KvBlocks<kUB> tb;
     load_blocks<D, kUA, MASK>(ta, src, split, splits, rib);
@@ -230,12 +241,16 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
 // grid (splits, heads, batch), 256 threads; see the file header.  The five leading pointers are preloaded into SGPRs at
 // launch (-amdgpu-kernarg-preload-count): the three scalar reads the chunk bounds depend on go out with the first
 // instructions, together with the fetch of the argument block, and nothing else stands before the first cache loads.
-template <int D, bool MASK, bool LONG>
+//
+// PAD: a fourth scalar read, kv_start[b], joins the batch (one wait, still no branch before the cache loads).  With s the start kept
+// inside [0, slot], the K, V and mask bases move by s rows, the valid length and the slot the chunk code sees are taken relative to
+// s (as in attn_decode_partial_kernel<.., PAD>: the two forms stay bit-identical); the new row is written at its absolute slot.
+template <int D, bool MASK, bool LONG, bool PAD = false>
 __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const int64_t* __restrict__ kv_len,
                                                                         const int64_t* __restrict__ slots,
                                                                         const int64_t* __restrict__ positions,
                                                                         f16* __restrict__ kc, f16* __restrict__ vc,
-                                                                        const RopeAttnArgs a)
+                                                                        const RopeAttnKernArgs<PAD> a)
 {
     constexpr int LPP = D / 8, NW = kAttnThreads / 64;
     __shared__ float    sm_m[NW], sm_l[NW];
@@ -256,11 +271,20 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     const int64_t* p_pos  = positions + b;
     const int64_t* p_slot = slots ? slots + (long)b * a.slot_stride : positions + b;
     const int64_t* p_len  = kv_len ? kv_len : positions;
-    int64_t        rpos, slot64, filled;
-    asm volatile("s_load_dwordx2 %0, %3, 0x0\n\ts_load_dwordx2 %1, %4, 0x0\n\ts_load_dwordx2 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(rpos), "=&s"(slot64), "=&s"(filled)
-                 : "s"(p_pos), "s"(p_slot), "s"(p_len)
-                 : "memory");
+    int64_t        rpos, slot64, filled, start64 = 0;
+    if constexpr (PAD) {
+        const int64_t* p_start = a.kv_start + b;
+        asm volatile("s_load_dwordx2 %0, %4, 0x0\n\ts_load_dwordx2 %1, %5, 0x0\n\ts_load_dwordx2 %2, %6, 0x0\n\t"
+                     "s_load_dwordx2 %3, %7, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(rpos), "=&s"(slot64), "=&s"(filled), "=&s"(start64)
+                     : "s"(p_pos), "s"(p_slot), "s"(p_len), "s"(p_start)
+                     : "memory");
+    } else {
+        asm volatile("s_load_dwordx2 %0, %3, 0x0\n\ts_load_dwordx2 %1, %4, 0x0\n\ts_load_dwordx2 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(rpos), "=&s"(slot64), "=&s"(filled)
+                     : "s"(p_pos), "s"(p_slot), "s"(p_len)
+                     : "memory");
+    }
     ATTN_STAMP(1);
     // a slot outside the cache is neither written nor attended, and (like the two-launch form) nothing is rotated then
     // (no upper bound on rpos here, unlike the two-launch form: launch_rope_attn_decode's table_rows)
@@ -268,7 +292,11 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     const int  slot = have_new ? (int)slot64 : -1;
     // a full cache (or a bad position) used to be silent: count the dropped steps (eetq_decode_dropped_steps)
     if (!have_new && split == 0 && h == 0 && threadIdx.x == 0) atomicAdd(&g_attn_dropped, 1u);
-    const int  Sv = kv_len ? max(0, (int)min((int64_t)a.S, filled + a.kv_len_bias)) : a.S;
+    const int  Sv_all = kv_len ? max(0, (int)min((int64_t)a.S, filled + a.kv_len_bias)) : a.S;
+    // PAD: everything the chunk code sees is relative to the row's first attended row s0 (scalar arithmetic, no branch)
+    const long s0     = PAD ? clamp_kv_start(start64, have_new ? slot : Sv_all - 1) : 0;
+    const int  Sv     = PAD ? max(0, Sv_all - (int)s0) : Sv_all;
+    const int  slot_c = PAD && have_new ? slot - (int)s0 : slot;
 
     // Memory queue order (a wave's loads return in order): the new token and its cos | sin row first, then the chunk's first
     // kUA blocks; the rotation runs on the former while the latter are on their way; attn_chunk requests the rest.
@@ -282,8 +310,8 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     const f16*  cs = a.cos_sin + (have_new ? rpos : 0) * D + (d0 < D / 2 ? d0 : d0 - D / 2);
     const f16x8 rc = *reinterpret_cast<const f16x8*>(cs), rs = *reinterpret_cast<const f16x8*>(cs + D / 2);
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler sinks these seven loads below the block loads otherwise)
-    const KvSrc src = make_kv_src<D, MASK>(kc + b * a.kc_sb + hk * a.kc_sh, vc + b * a.vc_sb + hk * a.vc_sh, a.kc_ss, a.vc_ss,
-                                           Sv, MASK ? a.mask + b * a.m_sb : nullptr);
+    const KvSrc src = make_kv_src<D, MASK>(kc + b * a.kc_sb + hk * a.kc_sh + s0 * a.kc_ss, vc + b * a.vc_sb + hk * a.vc_sh + s0 * a.vc_ss,
+                                           a.kc_ss, a.vc_ss, Sv, MASK ? a.mask + b * a.m_sb + s0 : nullptr);
     const int   rib = (tid >> 6) * AttnGeo<D>::PPW + lane / LPP;
     KvBlocks<kUA> ta;
     KvBlocks<kUB> tb;
@@ -301,34 +329,35 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     }
     ATTN_STAMP(2);
     float M, L, O;
-    attn_chunk<D, true, MASK, LONG>(qv, a.scaling, ta, tb, src, split, splits, Sv, slot, knew, vnew, sm_m, sm_l, sm_o, M, L, O);
+    attn_chunk<D, true, MASK, LONG>(qv, a.scaling, ta, tb, src, split, splits, Sv, slot_c, knew, vnew, sm_m, sm_l, sm_o, M, L, O);
 
     ATTN_STAMP(3);
     head_handoff<D>(a, split, splits, h, b, H, M, L, O, sm_o, &sm_ticket);
 }
 
 
-template <int D, bool MASK, bool LONG>
+template <int D, bool MASK, bool LONG, bool PAD>
 int launch_d2(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv, int S,
               int splits, float scaling, const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance,
-              hipStream_t stream)
+              hipStream_t stream, KvStartArg<PAD> kv_start)
 {
-    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG>, dim3(splits, H, B), dim3(kAttnThreads), 0, stream, q, k, v, mask, ws,
-                  scaling, S, H / Hkv, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], kv_len, kv_len_bias);
+    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG, PAD>, dim3(splits, H, B), dim3(kAttnThreads), 0, stream, q, k, v, mask, ws,
+                  scaling, S, H / Hkv, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], kv_len, kv_len_bias, kv_start);
     EETQ_TRY_HIP(hipGetLastError());
     launch_kernel(attn_decode_merge_kernel<D>, dim3(H, B), dim3(kAttnThreads), 0, stream, (const float*)ws, out, splits, st[9],
                   st[10], advance);
     return check_hip(hipGetLastError(), "attn_decode kernels launch");
 }
 
-template <int D>
+template <int D, bool PAD>
 int launch_d(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv, int S,
              int splits, float scaling, const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance,
-             hipStream_t stream)
+             hipStream_t stream, KvStartArg<PAD> kv_start)
 {
     const bool lng = long_chunks<D>(S, splits);
-#define EETQ_ATTN_GO(MASK, LONG) \
-    return launch_d2<D, MASK, LONG>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, st, kv_len, kv_len_bias, advance, stream)
+#define EETQ_ATTN_GO(MASK, LONG)                                                                                                  \
+    return launch_d2<D, MASK, LONG, PAD>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, st, kv_len, kv_len_bias, advance, \
+                                         stream, kv_start)
     if (mask) {
         if (lng) EETQ_ATTN_GO(true, true);
         EETQ_ATTN_GO(true, false);
@@ -338,13 +367,13 @@ int launch_d(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out
 #undef EETQ_ATTN_GO
 }
 
-template <int D>
-int launch_rope_d(const int64_t* kv_len, const int64_t* slots, const int64_t* positions, f16* kc, f16* vc, const RopeAttnArgs& a,
-                  dim3 grid, hipStream_t stream)
+template <int D, bool PAD>
+int launch_rope_d(const int64_t* kv_len, const int64_t* slots, const int64_t* positions, f16* kc, f16* vc,
+                  const RopeAttnKernArgs<PAD>& a, dim3 grid, hipStream_t stream)
 {
     const bool lng = long_chunks<D>(a.S, (int)grid.x);
 #define EETQ_ATTN_GO(MASK, LONG) \
-    launch_kernel(rope_attn_decode_kernel<D, MASK, LONG>, grid, dim3(kAttnThreads), 0, stream, kv_len, slots, positions, kc, vc, a)
+    launch_kernel(rope_attn_decode_kernel<D, MASK, LONG, PAD>, grid, dim3(kAttnThreads), 0, stream, kv_len, slots, positions, kc, vc, a)
     if (a.mask) {
         if (lng) EETQ_ATTN_GO(true, true);
         else EETQ_ATTN_GO(true, false);
@@ -358,9 +387,11 @@ int launch_rope_d(const int64_t* kv_len, const int64_t* slots, const int64_t* po
 
 }  // namespace
 
-int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
-                       int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
-                       int64_t* advance, hipStream_t stream)
+namespace {
+template <bool PAD>
+int launch_attn_decode_any(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                           int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                           int64_t* advance, hipStream_t stream, KvStartArg<PAD> kv_start)
 {
     EETQ_REQUIRE(q && k && v && out && ws && strides, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S, "invalid attention shape");
@@ -371,20 +402,43 @@ int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask
                      ((long)S + 4096) * strides[7] * 2 < (1L << 31),
                  "one head's cache rows must span less than 2 GiB");
     if (D == 128)
-        return launch_d<128>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, strides, kv_len, kv_len_bias, advance, stream);
+        return launch_d<128, PAD>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, strides, kv_len, kv_len_bias, advance, stream,
+                                  kv_start);
     if (D == 64)
-        return launch_d<64>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, strides, kv_len, kv_len_bias, advance, stream);
+        return launch_d<64, PAD>(q, k, v, mask, out, ws, B, H, Hkv, S, splits, scaling, strides, kv_len, kv_len_bias, advance, stream,
+                                 kv_start);
     return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] decode attention supports head_dim 64 and 128");
+}
+}  // namespace
+
+int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                       int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                       int64_t* advance, hipStream_t stream)
+{
+    return launch_attn_decode_any<false>(q, k, v, mask, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len, kv_len_bias,
+                                         advance, stream, NoKvStart{});
+}
+
+// launch_attn_decode with a per-row first key: batch row b attends cache rows [kv_start[b], valid length) (DEVICE [B])
+int launch_attn_decode_padded(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                              int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                              const int64_t* kv_start, int64_t* advance, hipStream_t stream)
+{
+    EETQ_REQUIRE(kv_start, "null kv_start");
+    return launch_attn_decode_any<true>(q, k, v, mask, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len, kv_len_bias,
+                                        advance, stream, kv_start);
 }
 
 static unsigned long long* g_attn_stamps = nullptr;  // process-wide diagnostic hook (not thread-safe by design)
 void set_attn_stamps(unsigned long long* buf) { g_attn_stamps = buf; }
 
-int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
-                            const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
-                            unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
-                            const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
-                            hipStream_t stream)
+namespace {
+template <bool PAD>
+int launch_rope_attn_decode_any(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                                unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                                const long* st, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int64_t* advance,
+                                long table_rows, hipStream_t stream)
 {
     EETQ_REQUIRE(positions && q && k && v && cos_sin && kc && vc && out && ws && tickets && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S && splits <= 4096,
@@ -397,7 +451,8 @@ int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int 
                  "q, k, v, the caches and the cos|sin table must be 16-byte aligned");
     EETQ_REQUIRE(st[5] > 0 && st[8] > 0 && ((long)S + 4096) * st[5] * 2 < (1L << 31) && ((long)S + 4096) * st[8] * 2 < (1L << 31),
                  "one head's cache rows must span less than 2 GiB");
-    RopeAttnArgs a;
+    RopeAttnKernArgs<PAD> a;
+    if constexpr (PAD) a.kv_start = kv_start;
     a.slot_stride = slot_stride;
     a.q = q, a.k = k, a.v = v, a.q_sb = st[0], a.k_sb = st[1], a.v_sb = st[2];
     a.cos_sin = cos_sin;
@@ -406,9 +461,34 @@ int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int 
     a.ws = ws, a.tickets = tickets, a.kv_len_bias = kv_len_bias, a.advance = advance;
     a.S = S, a.groups = H / Hkv, a.scaling = scaling;
     a.stamps = g_attn_stamps;
-    if (D == 128) return launch_rope_d<128>(kv_len, slots, positions, kc, vc, a, dim3(splits, H, B), stream);
-    if (D == 64) return launch_rope_d<64>(kv_len, slots, positions, kc, vc, a, dim3(splits, H, B), stream);
+    if (D == 128) return launch_rope_d<128, PAD>(kv_len, slots, positions, kc, vc, a, dim3(splits, H, B), stream);
+    if (D == 64) return launch_rope_d<64, PAD>(kv_len, slots, positions, kc, vc, a, dim3(splits, H, B), stream);
     return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] decode attention supports head_dim 64 and 128");
+}
+}  // namespace
+
+int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                            const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                            unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                            const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
+                            hipStream_t stream)
+{
+    return launch_rope_attn_decode_any<false>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, mask, out, ws, tickets, B, H,
+                                              Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, nullptr, advance, table_rows,
+                                              stream);
+}
+
+// launch_rope_attn_decode with a per-row first key: batch row b attends cache rows [kv_start[b], valid length) (DEVICE [B])
+int launch_rope_attn_decode_padded(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                   const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                                   unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                                   const long* st, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start,
+                                   int64_t* advance, long table_rows, hipStream_t stream)
+{
+    EETQ_REQUIRE(kv_start, "null kv_start");
+    return launch_rope_attn_decode_any<true>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, mask, out, ws, tickets, B, H,
+                                             Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, kv_start, advance, table_rows,
+                                             stream);
 }
 
 }  // namespace eetq

@@ -273,6 +273,24 @@ struct RopeAttnArgs {
     unsigned long long* stamps;  // diagnostics (eetq_diag_attn_stamps): [workgroup][8] device-clock stamps, or null
 };
 
+// The per-row first key (PAD instantiations): cache rows below kv_start[b] of batch row b are padding.  Behind the
+// plain form's arguments, which keep their kernarg block; the two-launch kernel takes the pointer (or nothing) as its last argument.
+struct RopeAttnPadArgs : RopeAttnArgs {
+    const int64_t* kv_start;  // DEVICE [batch]
+};
+template <bool PAD>
+using RopeAttnKernArgs = std::conditional_t<PAD, RopeAttnPadArgs, RopeAttnArgs>;
+struct NoKvStart {};
+template <bool PAD>
+using KvStartArg = std::conditional_t<PAD, const int64_t*, NoKvStart>;
+
+// The first attended row of a batch row: its start, kept inside [0, last] where `last` is the new token's row (one-launch form) or
+// the last valid row (two-launch form, no new token) -- a start beyond it attends that row alone, and nothing leaves the cache.
+__device__ __forceinline__ int clamp_kv_start(int64_t start, int last)
+{
+    return (int)max((int64_t)0, min(start, (int64_t)max(last, 0)));
+}
+
 // device clock (100 MHz) into slot i of this workgroup's stamp row, ordered behind everything issued so far
 #define ATTN_STAMP(i)                                                                                                  \
     do {                                                                                                               \

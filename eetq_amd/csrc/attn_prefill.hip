@@ -65,8 +65,14 @@ struct PrefillDevArgs8 : PrefillDevArgs {
     const f16* scales;
     long       s_sb, s_sh, s_ss;   // fp16 elements between batch rows, kv heads, rows of the scale tensor
 };
-template <int MODE, bool KV8>
-using PrefillKernArgs = std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>;
+// The per-row first key (PAD): batch row b's cache rows below kv_start[b] are padding.  Behind the device-length
+// arguments, which keep their kernarg block.
+struct PrefillPadArgs : PrefillDevArgs {
+    const int64_t* kv_start;   // DEVICE [batch]
+};
+template <int MODE, bool KV8, bool PAD = false>
+using PrefillKernArgs = std::conditional_t<
+    PAD, PrefillPadArgs, std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>>;
 
 // MODE kPfHost: keys and causal offset from the host (the fresh prompt's path, unchanged).  kPfDev: every workgroup reads the length
 // at entry -- one scalar load -- and forms Tk and koff itself; kend, nblk, the descriptors' range, `active` and `edge` follow, the
@@ -85,10 +91,17 @@ using PrefillKernArgs = std::conditional_t<KV8, PrefillDevArgs8, std::conditiona
 //     rounding of the exact product, denormals kept.  THE ONE DIFFERENCE from the decode entries, which fold vs into the probability
 //     in fp32: here 2^12 p * vs would leave the fp16 range (vs spans 2^-24 .. 516).  A row that holds all the weight still comes out
 //     as fp16(vs * v8) bit for bit.
-template <int D, int MODE, bool KV8 = false>
-__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8> a_in)
+//
+// PAD (kPfDev and kPfSplit, fp16 rows): batch row b starts at cache row s = clamp(kv_start[b], 0, Tk).  Its first p = clamp(s - koff, 0, Tq)
+// queries are padding and come out as zeros (zero records in the split form); then the row is MOVED: q and out by p tokens, k and v by
+// s rows, Tq -= p, Tk -= s, koff = Tk - Tq, and the unchanged code below runs in the row's own frame -- query blocks, key blocks and
+// split shares counted from its first real token, the descriptors starting there: the bits of the plain form called on that row
+// alone, and no row below s is read.  Workgroups whose query block lies beyond the row's real queries leave.
+template <int D, int MODE, bool KV8 = false, bool PAD = false>
+__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8, PAD> a_in)
 {
     static_assert(!KV8 || MODE != kPfHost, "the int8-row form takes the device-length arguments");
+    static_assert(!PAD || (MODE != kPfHost && !KV8), "the per-row first key rides on the device-length arguments, fp16 rows");
     PrefillArgs a = a_in;
     int         wg = (int)blockIdx.x, split = 0;
     if constexpr (MODE != kPfHost) {
@@ -122,6 +135,34 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     const int hb = a.H * a.B, qb = a.nqb - 1 - wg / hb, rest = wg % hb;
     const int h = rest % a.H, b = rest / a.H, hk = h / a.groups;
     const int q0 = qb * kPfBM, qrow = q0 + wave * 32 + ln;           // this lane's query row
+    int       pad_q = 0;                                              // PAD: the row's pad queries (qrow counts from the first real one)
+    const int Tq_all = a.Tq;
+    if constexpr (PAD) {
+        const int s = (int)max((int64_t)0, min((int64_t)a.Tk, a_in.kv_start[b]));   // uniform: a scalar load
+        pad_q = max(0, min(a.Tq, s - a.koff));
+        // the pad queries of this workgroup's 128 rows (counted from the row's first token): zeros, in the layout of the stores below
+        if (qrow < pad_q) {
+            if constexpr (MODE == kPfSplit) {
+                const long rec  = (((long)b * a.H + h) * Tq_all + qrow) * a_in.ns + split;
+                const long recs = (long)a.B * a.H * Tq_all * a_in.ns;
+                float*     wp   = a_in.ws + rec * D + 4 * hi;
+#pragma unroll
+                for (int i = 0; i < D / 8; ++i) *reinterpret_cast<f32x4*>(wp + 8 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (hi == 0) {
+                    a_in.ws[recs * D + 2 * rec]     = -INFINITY;
+                    a_in.ws[recs * D + 2 * rec + 1] = 0.f;
+                }
+            } else {
+                f16* op = a.out + b * a.o_sb + (long)qrow * a.o_st + h * a.o_sh + 4 * hi;
+#pragma unroll
+                for (int i = 0; i < D / 8; ++i) *reinterpret_cast<u32x2*>(op + 8 * i) = u32x2{0u, 0u};
+            }
+        }
+        a.q += (long)pad_q * a.q_st, a.out += (long)pad_q * a.o_st;
+        a.k += (long)s * a.k_ss, a.v += (long)s * a.v_ss;
+        a.Tq -= pad_q, a.Tk -= s, a.koff = a.Tk - a.Tq;
+        if (q0 >= a.Tq) return;   // workgroup-uniform, before any barrier: no real query in this block
+    }
     const int qlast_wave = q0 + wave * 32 + 31;                       // the wave's last row
     // keys this workgroup needs: rows <= its last query + koff
     const int kend  = min(a.Tk, q0 + kPfBM + a.koff);
@@ -354,8 +395,8 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     // ---- split form: the row's record, unnormalised (the 2^12 carry is in o and l alike and leaves in the merge's division) ----
     if constexpr (MODE == kPfSplit) {
         if (qrow < a.Tq) {
-            const long rec  = (((long)b * a.H + h) * a.Tq + qrow) * a_in.ns + split;
-            const long recs = (long)a.B * a.H * a.Tq * a_in.ns;
+            const long rec  = (((long)b * a.H + h) * Tq_all + qrow + pad_q) * a_in.ns + split;
+            const long recs = (long)a.B * a.H * Tq_all * a_in.ns;
             float*     wp   = a_in.ws + rec * D + 4 * hi;
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
@@ -521,6 +562,44 @@ int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* 
         launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     }
     return check_hip(hipGetLastError(), "prefill_attn_kernel (split) launch");
+}
+
+// launch_prefill_attention_dev with a per-row first key: cache rows below kv_start[b] (DEVICE [B]) of batch row b are padding (the PAD
+// form above).  Always the device-length kernel (kv_len nullptr: max_keys keys), or the split form and the unchanged merge.
+int launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                    int max_keys, int D, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int splits,
+                                    float scaling, const long* st, hipStream_t stream)
+{
+    EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
+    EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
+    const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
+    if (rc != EETQ_OK) return rc;
+    EETQ_REQUIRE(kv_start, "null kv_start");
+    EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
+    PrefillPadArgs a;
+    fill_prefill_args(a, q, k, v, out, B, H, Hkv, Tq, max_keys, max_keys - Tq, scaling, st);
+    a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits, a.kv_start = kv_start;
+    const long wgs = (long)a.nqb * H * B * splits;
+    EETQ_REQUIRE(wgs < (1L << 31), "too many workgroups");
+    const dim3 grid((unsigned)wgs), block(kPfThreads);
+    if (splits == 1) {
+        if (D == 128)
+            launch_kernel(prefill_attn_kernel<128, kPfDev, false, true>, grid, block, 0, stream, a);
+        else
+            launch_kernel(prefill_attn_kernel<64, kPfDev, false, true>, grid, block, 0, stream, a);
+        return check_hip(hipGetLastError(), "prefill_attn_kernel (per-row first key) launch");
+    }
+    const long rows = (long)B * H * Tq, threads = rows * (D / 4);
+    EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
+    const dim3 mgrid((unsigned)((threads + 255) / 256));
+    if (D == 128) {
+        launch_kernel(prefill_attn_kernel<128, kPfSplit, false, true>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    } else {
+        launch_kernel(prefill_attn_kernel<64, kPfSplit, false, true>, grid, block, 0, stream, a);
+        launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
+    }
+    return check_hip(hipGetLastError(), "prefill_attn_kernel (per-row first key, split) launch");
 }
 
 // launch_prefill_attention_dev over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of

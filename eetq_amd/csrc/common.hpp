@@ -333,12 +333,25 @@ int launch_prefill_attention(const f16* q, const f16* k, const f16* v, f16* out,
 int    launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq, int max_keys,
                                     int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
                                     hipStream_t stream);
+// ... with a per-row first key (DEVICE [B]): cache rows below kv_start[b] of batch row b are padding
+int    launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                       int max_keys, int D, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int splits,
+                                       float scaling, const long* st, hipStream_t stream);
 int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
 int    prefill_attention_max_splits();
 size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
 int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
                        int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
                        int64_t* advance, hipStream_t stream);
+// the decode entries with a per-row first key (DEVICE [B]): batch row b attends cache rows [kv_start[b], valid length)
+int launch_attn_decode_padded(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                              int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                              const int64_t* kv_start, int64_t* advance, hipStream_t stream);
+int launch_rope_attn_decode_padded(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                   const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                                   unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                                   const long* strides, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start,
+                                   int64_t* advance, long table_rows, hipStream_t stream);
 
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,
                           const f16* cache, f16* kcache, f16* vcache, int batch, int q_heads, int k_heads, int head_size, int rot_dim, long q_stride,

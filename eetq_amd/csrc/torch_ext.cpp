@@ -154,12 +154,21 @@ Tensor unprocess_weights(const Tensor& processed_weight, const std::string& layo
 
 // ---- fused dequant + GEMM ---------------------------------------------------------------------------------------------
 void layernorm_forward(const Tensor& input, const Tensor& gamma, Tensor& out, double eps);
+// kv_start of the three attention operators (the per-row first key of a left-padded batch): contiguous int64 [B] on the device
+static const int64_t* kv_start_ptr(const char* name, const OptTensor& kv_start, const Tensor& query, int64_t B)
+{
+    if (!kv_start) return nullptr;
+    TORCH_CHECK(kv_start->scalar_type() == at::kLong && kv_start->dim() == 1 && kv_start->size(0) == B && kv_start->is_contiguous() &&
+                    kv_start->device() == query.device(),
+                name, ": kv_start must be a contiguous int64 [B] tensor on the query's device");
+    return kv_start->data_ptr<int64_t>();
+}
 // eetq_rotary_neox_kvcache_f16 + eetq_decode_attention_f16 as one launch (the decode step of a static cache)
 Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
                              const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& tickets,
                              const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
                              std::optional<int64_t> splits_in, const OptTensor& kv_len, int64_t kv_len_bias,
-                             const OptTensor& advance)
+                             const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
 {
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache})
         TORCH_CHECK(t->scalar_type() == at::kHalf, "rope_decode_attention: float16 tensors expected");
@@ -211,7 +220,18 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
                                 (long)key_cache.stride(0),   (long)key_cache.stride(1),   (long)key_cache.stride(2),
                                 (long)value_cache.stride(0), (long)value_cache.stride(1), (long)value_cache.stride(2),
                                 (long)m_sb,                  (long)out.stride(0),         (long)out.stride(1)};
+    const int64_t* starts = kv_start_ptr("rope_decode_attention", kv_start, query, B);
     c10::DeviceGuard guard(query.device());
+    if (starts) {
+        check(eetq_rope_decode_attention_padded_f16(
+            positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(),
+            key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(),
+            value_cache.data_ptr(), mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
+            reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits,
+            (float)sc, strides, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
+            advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
+        return out;
+    }
     check(eetq_rope_decode_attention_bounded_f16(
         positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(),
         key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(),
@@ -236,7 +256,7 @@ int64_t prefill_attention_splits(int64_t batch, int64_t heads, int64_t q_tokens,
 // device (eetq_prefill_attention_dev_f16); splits: None = the library's rule, workspace: None = allocated here (capturable)
 Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
                          std::optional<int64_t> causal_offset, const OptTensor& kv_len, int64_t kv_len_bias,
-                         std::optional<int64_t> splits_in, const OptTensor& workspace)
+                         std::optional<int64_t> splits_in, const OptTensor& workspace, const OptTensor& kv_start = std::nullopt)
 {
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
         TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
@@ -248,7 +268,8 @@ Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& v
     TORCH_CHECK(prefill_attention_supported(D), "prefill_attention: unsupported head_dim");
     const double sc  = scaling ? *scaling : 1.0 / std::sqrt((double)D);
     const int64_t off = causal_offset ? *causal_offset : keys - T;
-    const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0;
+    const int64_t* starts = kv_start_ptr("prefill_attention", kv_start, query, B);
+    const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0 || starts;
     int64_t      splits = 1;
     Tensor       ws;
     if (dev_form) {
@@ -277,6 +298,14 @@ Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& v
                            (long)key.stride(2),   (long)value.stride(0), (long)value.stride(1), (long)value.stride(2),
                            (long)out.stride(0),   (long)out.stride(1),   (long)out.stride(2)};
     c10::DeviceGuard guard(query.device());
+    if (starts) {   // the per-row first key: always the device-length entry (kv_len None: `keys` keys, the fresh prompt)
+        TORCH_CHECK(off == keys - T, "prefill_attention: kv_start takes causal_offset = keys - query rows only");
+        check(eetq_prefill_attention_padded_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(),
+                                                ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)keys,
+                                                (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
+                                                (int)splits, (float)sc, st, stream_of(query)));
+        return out;
+    }
     if (kv_len || splits > 1) {
         TORCH_CHECK(kv_len || off == keys - T, "prefill_attention: the split form takes causal_offset = keys - query rows only");
         check(eetq_prefill_attention_dev_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(),
@@ -816,7 +845,7 @@ void sample_handover(const Tensor& logits, Tensor& out_tokens, Tensor& column, T
 
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
-                        int64_t kv_len_bias, const OptTensor& advance)
+                        int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
 {
     TORCH_CHECK(query.scalar_type() == at::kHalf && key_cache.scalar_type() == at::kHalf && value_cache.scalar_type() == at::kHalf,
                 "decode_attention: query and caches must be float16");
@@ -850,7 +879,16 @@ Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tens
                                  (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
                                  (long)value_cache.stride(1), (long)value_cache.stride(2), (long)m_sb,
                                  (long)out.stride(0),         (long)out.stride(1)};
+    const int64_t* starts = kv_start_ptr("decode_attention", kv_start, query, B);
     c10::DeviceGuard guard(query.device());
+    if (starts) {
+        check(eetq_decode_attention_padded_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
+                                               mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
+                                               (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides,
+                                               kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
+                                               advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
+        return out;
+    }
     check(eetq_decode_attention_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
                                     mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
                                     (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides,
@@ -1924,12 +1962,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none());
     m.def("rope_decode_attention", &rope_decode_attention, py::arg("positions"), py::arg("query"), py::arg("key"),
           py::arg("value"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("tickets"),
           py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none());
     m.def("decode_attention_i8kv", &decode_attention_i8kv, "single-query attention over an int8 KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"), py::arg("mask") = py::none(),
           py::arg("scaling") = py::none(), py::arg("splits") = py::none(), py::arg("kv_len") = py::none(),
@@ -1946,6 +1984,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
+          py::arg("kv_start") = py::none(),
           "causal attention of a prompt's query rows [B, T, H, D] over the first `keys` rows of a KV cache [B, Hkv, S, D] (MFMA)");
     m.def("prefill_attention_i8kv", &prefill_attention_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
           py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),

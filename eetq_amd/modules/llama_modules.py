@@ -19,7 +19,7 @@ import torch.nn as nn
 from .. import ops
 
 __all__ = ["EETRotaryEmbedding", "EETLlamaAttention", "EETQuantLlamaAttention", "EETLlamaMLP", "fresh_static_prefill",
-           "appended_static_prefill"]
+           "appended_static_prefill", "padded_static_batch"]
 
 _prefill_promise = threading.local()
 
@@ -63,6 +63,34 @@ def appended_static_prefill(int8_rows=False):
         yield
     finally:
         _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = prev
+
+
+@contextlib.contextmanager
+def padded_static_batch(starts):
+    """The caller's promise for the forwards run inside (per thread, restored on exit): the batch is LEFT-padded and cache rows
+    below ``starts[b]`` (int64 [B] on the device, read by the kernels: it may be a static tensor a captured graph refers to) of
+    batch row b are padding.  The attention blocks then hand ``kv_start=starts`` to the library's kernels, which count a row's
+    key blocks, query blocks and chunks from its first real token and never read a row below it:
+
+    * a decode step on a static cache goes through the module forward (``decode_step_state`` returns ``None``, as for an int8
+      cache) and calls ``ops.rope_decode_attention`` / ``ops.decode_attention`` with ``kv_start``;
+    * a prompt under ``fresh_static_prefill`` or ``appended_static_prefill`` calls ``ops.prefill_attention`` with ``kv_start`` (the
+      fresh prompt through the device-length entry with ``kv_len=None``); its pad queries come out as zeros.
+
+    The cache keeps its single token counter (slots, ``advance`` and the hand-over kernels are as without the promise); the
+    caller passes ``position_ids`` that count from each row's first real token.  Anything the MFMA prompt kernel or the decode
+    kernels cannot run (head size, dtype, an int8 cache, a stock attention path) raises ``ValueError`` instead of attending the
+    pads."""
+    prev = getattr(_prefill_promise, "starts", None)
+    _prefill_promise.starts = starts
+    try:
+        yield
+    finally:
+        _prefill_promise.starts = prev
+
+
+def _padded_starts():
+    return getattr(_prefill_promise, "starts", None)
 
 
 class EETRotaryEmbedding(nn.Module):
@@ -170,6 +198,9 @@ class _EETAttentionBase(nn.Module):
         ``int8_rows=True`` is the quantising write behind the device counter, the counter's advance, and the prompt kernel's
         int8-row form over the dequantised rows below the counter (its own among them): no host read, capturable."""
         bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
+        if _padded_starts() is not None:
+            raise ValueError("EETLlamaAttention: padded_static_batch (a left-padded batch) needs an fp16 static cache: the int8 "
+                             "kernels take no per-row first key")
         if (d not in (64, 128) or not q.is_cuda or q.dtype != torch.float16 or self.decode_math_attention is not True
                 or kwargs.get("output_attentions", False) or layer.keys.shape[0] != bsz
                 or layer.keys.shape[1] != self.num_key_value_heads):
@@ -290,6 +321,8 @@ class _EETAttentionBase(nn.Module):
         layer = self._static_cache_layer(past_key_values)
         if layer is None or self.decode_math_attention is not True or position_ids is None or not hidden_states.is_cuda:
             return None
+        if _padded_starts() is not None:   # the one-call layer takes no per-row first key: the module forward does
+            return None
         bsz, rows = hidden_states.shape[0], layer.keys.shape[2]
         memo = getattr(_EETAttentionBase._step_memo, "entry", None)
         if memo is None:
@@ -319,6 +352,22 @@ class _EETAttentionBase(nn.Module):
         of a static cache that already hold this call's rotated k and v (then k, v and past_key_values are unused), with the
         cache's device counter, already advanced, as a third element."""
         q = q.transpose(1, 2)
+        starts = _padded_starts()
+        if starts is not None:
+            # a left-padded batch: the MFMA prompt kernel with the per-row first key, or an error -- every other path below would
+            # attend the pads
+            if (cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False) or not self.mfma_prefill
+                    or ops.prefill_attention is None or not q.is_cuda or q.dtype != torch.float16
+                    or not ops.prefill_attention_supported(self.head_dim) or cached[0].stride(-1) != 1 or cached[1].stride(-1) != 1
+                    or not (getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False))):
+                raise ValueError("EETLlamaAttention: padded_static_batch needs the MFMA prompt kernel (float16 on the GPU, head "
+                                 "size 64 or 128, mfma_prefill=True, the compiled operator module) on an initialised fp16 static "
+                                 "cache under fresh_static_prefill or appended_static_prefill")
+            k, v, counter = cached
+            fresh = getattr(_prefill_promise, "fresh", False)
+            out = ops.prefill_attention(q.transpose(1, 2), k, v, q.shape[2] if fresh else k.shape[2], scaling=self.scaling,
+                                        kv_len=None if fresh else counter, kv_start=starts)
+            return out.reshape(*input_shape, -1), None
         if cached is not None:
             k, v, counter = cached
             if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1
@@ -457,6 +506,10 @@ class EETLlamaAttention(_EETAttentionBase):
         add = False
         if layer is not None and self.decode_math_attention is True and not kwargs.get("output_attentions", False):
             add = self._decode_mask_rows(attention_mask, bsz, layer.keys.shape[2], hidden_states.dtype, hidden_states.device)
+        starts = _padded_starts()   # a left-padded batch: the per-row first key of the decode kernels (None: the plain entries)
+        if starts is not None and q_len == 1 and add is False:
+            raise ValueError("EETLlamaAttention: padded_static_batch needs the library's decode attention on an initialised fp16 "
+                             "static cache (head size 64 or 128, decode_math_attention=True, a mask the kernel understands)")
         if add is not False:
             # decode step on an initialised static cache: ONE launch rotates q in place (by its position) and writes the
             # rotated k and v straight into the cache row the cache's own token counter names -- for a left-padded batch
@@ -472,12 +525,14 @@ class EETLlamaAttention(_EETAttentionBase):
                 # merge done by the last workgroup of each head (bit-identical to the pair of launches below)
                 out = ops.rope_decode_attention(pos, q[:, 0], k[:, 0], v[:, 0], table, layer.keys, layer.values,
                                                 self._step_tickets(bsz, q.device), slots=counter, mask=add, scaling=self.scaling,
-                                                kv_len=counter, kv_len_bias=1, advance=counter).reshape(bsz, q_len, -1)
+                                                kv_len=counter, kv_len_bias=1, advance=counter,
+                                                kv_start=starts).reshape(bsz, q_len, -1)
             else:
                 ops.rotary_embedding_neox_kvcache(pos, q[:, 0], k[:, 0], v[:, 0], self.head_dim, table, layer.keys,
                                                   layer.values, slots=counter)
                 out = ops.decode_attention(q[:, 0], layer.keys, layer.values, mask=add, scaling=self.scaling,
-                                           kv_len=counter, kv_len_bias=1, advance=counter).reshape(bsz, q_len, -1)
+                                           kv_len=counter, kv_len_bias=1, advance=counter,
+                                           kv_start=starts).reshape(bsz, q_len, -1)
             weights = None
         else:
             player = self._static_cache_layer(past_key_values) if (q_len > 1 and q.is_cuda and self.static_prefill) else None

@@ -713,15 +713,24 @@ def rotary_embedding_neox_strided(positions, query, key, head_size, cos_sin_cach
     return None
 
 
+def _check_kv_start(name, kv_start, query, B):
+    """``kv_start`` of the attention operators (the per-row first key of a left-padded batch): contiguous int64 [B] on the device."""
+    if (not torch.is_tensor(kv_start) or kv_start.dtype != torch.int64 or kv_start.dim() != 1 or kv_start.shape[0] != B
+            or not kv_start.is_contiguous() or kv_start.device != query.device):
+        raise RuntimeError("%s: kv_start must be a contiguous int64 [B] tensor on the query's device" % name)
+
+
 @_eager_only
 def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0,
-                     advance=None):
+                     advance=None, kv_start=None):
     """Single-query attention over a KV cache (extension; the decode step of the EET attention blocks).
 
     query [B, H, D] (any batch/head strides, dense D), key_cache / value_cache [B, Hkv, S, D] (dense D), mask: additive
     float16 [B, S] or [1, S] (or broadcastable [B, 1, 1, S]) with -inf at masked positions, or None.  ``kv_len`` (int64
     device scalar): only rows below ``kv_len + kv_len_bias`` are attended (the filled part of a static cache); ``advance``
-    (int64 device scalar, may be the same tensor): incremented by one when the attention has been computed.  Returns
+    (int64 device scalar, may be the same tensor): incremented by one when the attention has been computed.  ``kv_start``
+    (int64 [B] on the device): batch row b attends rows ``kv_start[b]`` and up only, its blocks and chunks counted from
+    there (a left-padded batch; eetq_decode_attention_padded_f16).  Returns
     float16 [B, H, D].  fp32 softmax and accumulation; D must be 64 or 128."""
     if query.dtype != torch.float16 or key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
         raise RuntimeError("decode_attention: query and caches must be float16")
@@ -742,6 +751,8 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
     for name, t in (("kv_len", kv_len), ("advance", advance)):
         if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
             raise RuntimeError("decode_attention: %s must be a one-element int64 tensor on the query's device" % name)
+    if kv_start is not None:
+        _check_kv_start("decode_attention", kv_start, query, B)
     if scaling is None:
         scaling = D ** -0.5
     if splits is None:  # the library's tuned default (about two workgroups per CU, at most 8 chunks)
@@ -752,6 +763,12 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
                                    key_cache.stride(2), value_cache.stride(0), value_cache.stride(1), value_cache.stride(2),
                                    m_sb, out.stride(0), out.stride(1))
     with torch.cuda.device(query.device):
+        if kv_start is not None:
+            check(_lib.lib().eetq_decode_attention_padded_f16(
+                _ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws),
+                B, H, Hkv, S, D, int(splits), float(scaling), strides, _ptr(kv_len) if kv_len is not None else None,
+                int(kv_len_bias), _ptr(kv_start), _ptr(advance) if advance is not None else None, _stream_ptr()))
+            return out
         check(_lib.lib().eetq_decode_attention_f16(_ptr(query), _ptr(key_cache), _ptr(value_cache),
                                                    _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), B, H,
                                                    Hkv, S, D, int(splits), float(scaling), strides,
@@ -762,11 +779,12 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
 
 @_eager_only
 def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache, value_cache, tickets, slots=None,
-                          mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None):
+                          mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None, kv_start=None):
     """``rotary_embedding_neox_kvcache`` followed by ``decode_attention`` as ONE launch (extension; the decode step of a
     static KV cache).  Bit-identical to that pair in the cache rows written and in the returned [B, H, D] output; the
     rotated query is not written back.  ``tickets``: an int32 device tensor of at least B * H + 1 zeros that the launch
-    leaves zeroed (launches that may overlap need their own).  The rotation must cover the whole head."""
+    leaves zeroed (launches that may overlap need their own).  The rotation must cover the whole head.  ``kv_start``: as in
+    ``decode_attention`` (eetq_rope_decode_attention_padded_f16); the new row is still written at its absolute slot."""
     for t in (query, key, value, cos_sin_cache, key_cache, value_cache):
         if t.dtype != torch.float16:
             raise RuntimeError("rope_decode_attention: float16 tensors expected")
@@ -807,6 +825,8 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
     for name, t in (("kv_len", kv_len), ("advance", advance)):
         if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
             raise RuntimeError("rope_decode_attention: %s must be a one-element int64 tensor on the query's device" % name)
+    if kv_start is not None:
+        _check_kv_start("rope_decode_attention", kv_start, query, B)
     if scaling is None:
         scaling = D ** -0.5
     if splits is None:
@@ -817,6 +837,15 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
                                    key_cache.stride(1), key_cache.stride(2), value_cache.stride(0), value_cache.stride(1),
                                    value_cache.stride(2), m_sb, out.stride(0), out.stride(1))
     with torch.cuda.device(query.device):
+        if kv_start is not None:
+            check(_lib.lib().eetq_rope_decode_attention_padded_f16(
+                _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
+                _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache),
+                _ptr(mrow) if mrow is not None else None, _ptr(out),
+                _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits), float(scaling), strides,
+                _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias), _ptr(kv_start),
+                _ptr(advance) if advance is not None else None, _stream_ptr()))
+            return out
         check(_lib.lib().eetq_rope_decode_attention_bounded_f16(
             _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
             _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache),

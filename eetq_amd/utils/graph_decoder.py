@@ -12,11 +12,35 @@ import inspect
 
 import torch
 
-__all__ = ["GraphDecoder"]
+__all__ = ["GraphDecoder", "left_pad_starts"]
+
+
+def left_pad_starts(mask):
+    """The first real column of every row of a LEFT-padded batch: ``mask`` [B, P] holds keep flags (bool or integer, non-zero =
+    a real token), as a tokenizer with ``padding_side="left"`` returns them; the result is ``P - mask.sum(1)``, int64 [B] on the
+    mask's device.  A row with a hole, right padding or no real token at all raises ``ValueError``, and so does a mask that is
+    not 2-D.  One host read."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 2 or mask.shape[1] < 1:
+        raise ValueError("GraphDecoder: attention_mask must be [batch, P] keep flags, got shape %s" % (tuple(mask.shape),))
+    if mask.is_floating_point() or mask.is_complex():
+        raise ValueError("GraphDecoder: attention_mask must hold bool or integer keep flags, got %s" % (mask.dtype,))
+    keep = mask != 0
+    P = keep.shape[1]
+    starts = P - keep.sum(1, dtype=torch.int64)
+    left_padded = keep == (torch.arange(P, device=keep.device)[None, :] >= starts[:, None])
+    ok, some = torch.stack([left_padded.all(), (starts < P).all()]).tolist()
+    if not some:
+        raise ValueError("GraphDecoder: every row of attention_mask must keep at least one token")
+    if not ok:
+        raise ValueError("GraphDecoder: attention_mask must be left-padded (zeros, then ones, in every row): a row has a hole or "
+                         "padding on the right")
+    return starts
 
 
 class GraphDecoder:
-    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False):
+    def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
+                 ragged=False):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -39,7 +63,13 @@ class GraphDecoder:
         and values as their quantised selves, as a decode step does.  A chunked prompt is therefore NOT bit-identical to the
         whole prompt on an int8 cache: the first piece of an emptied cache stays on the fresh path (unquantised keys, the fp16
         decoder's bits), later pieces see quantised earlier rows.  The captured decode graphs are reused as they
-        are after an append."""
+        are after an append.
+        ``ragged`` (default ``False``: nothing changes): the decoder takes LEFT-padded batches -- ``generate`` and ``prefill`` accept
+        ``attention_mask`` [batch, P] keep flags.  It owns a static ``s_start`` [batch] (each row's first real cache row), captures
+        its graphs under ``llama_modules.padded_static_batch(s_start)`` -- the attention kernels then count every row's blocks from
+        its first real token and never read its pad rows -- and steps with ``position_ids = s_pos - s_start`` (one small launch per
+        step, inside the graph); ``s_pos`` remains the cache row.  The decode step goes through the attention module instead of
+        the one-call layer.  It needs the lean layer-by-layer model with head size 64 or 128 and an fp16 cache (``kv_bits=16``)."""
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
         if kv8_append and kv_bits != 8:
@@ -49,6 +79,18 @@ class GraphDecoder:
         self.lean = bool(lean)
         self.sampling = bool(sampling)
         self.model = model
+        self.ragged = bool(ragged)
+        if self.ragged:
+            if self.kv_bits != 16:
+                raise ValueError("GraphDecoder: ragged=True needs an fp16 cache (kv_bits=16): the int8 kernels take no per-row first "
+                                 "key, got kv_bits=%r" % (kv_bits,))
+            if not self._lean():
+                raise ValueError("GraphDecoder: ragged=True needs lean=True and a fully accelerated model (eet_accelerator with "
+                                 "fused_attn, fused_mlp and fused_residual): only its attention blocks take a per-row first key")
+            for layer in model.model.layers:
+                attn = getattr(layer, "self_attn", None)
+                if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
+                    raise ValueError("GraphDecoder: ragged=True needs attention blocks with head size 64 or 128")
         if self.kv_bits == 8:
             if not self._lean():
                 raise ValueError("GraphDecoder: kv_bits=8 needs lean=True and a fully accelerated model (eet_accelerator with "
@@ -73,6 +115,8 @@ class GraphDecoder:
                                          dtype=torch.float16)
         self.s_tok = torch.zeros(self.batch, 1, dtype=torch.long, device=dev)
         self.s_pos = torch.zeros(1, dtype=torch.long, device=dev)
+        # ragged: every row's first real cache row (the kernels' kv_start; the captured graphs read this very tensor)
+        self.s_start = torch.zeros(self.batch, dtype=torch.long, device=dev) if self.ragged else None
         # generated tokens: step i of a generate() writes column s_idx (a device counter the graphs advance themselves)
         self.s_idx = torch.zeros(1, 1, dtype=torch.long, device=dev)
         self.out_buf = torch.zeros(self.batch, self.max_len + 1, dtype=torch.long, device=dev)
@@ -94,25 +138,36 @@ class GraphDecoder:
                 raise ValueError("GraphDecoder: sampling=True needs float16 logits on the GPU (got %s on %s)"
                                  % (first.logits.dtype, first.logits.device))
             if capture:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._advance()
-                torch.cuda.current_stream().wait_stream(side)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._advance()
-                if self.steps_per_graph > 1:
-                    self.graph_n = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph_n):
-                        for _ in range(self.steps_per_graph):
-                            self._advance()
+                with self._promise():   # (the allocating forward above ran without it: no cache layer, nothing to promise yet)
+                    self._capture()
         self.cache.reset()
         # host-side bookkeeping of a conversation: cache rows written, and whether s_tok holds a token the caller has seen but the
         # cache has not (the last one a generate() emitted)
         self.rows = 0
         self._pending = False
+
+    def _capture(self):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._advance()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._advance()
+        if self.steps_per_graph > 1:
+            self.graph_n = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph_n):
+                for _ in range(self.steps_per_graph):
+                    self._advance()
+
+    def _promise(self):
+        """``padded_static_batch(s_start)`` on a ragged decoder (every forward, captured or eager, runs inside it), else nothing."""
+        if not self.ragged:
+            return contextlib.nullcontext()
+        from ..modules.llama_modules import padded_static_batch
+        return padded_static_batch(self.s_start)
 
     def _fresh_prefill_ok(self):
         """True when the prompt may run under ``fresh_static_prefill``: the lean layer-by-layer model, every attention block
@@ -142,7 +197,10 @@ class GraphDecoder:
         if self._lean():
             base = self.model.model
             h = base.embed_tokens(self.s_tok)
-            pos = self.s_pos.view(1, 1).expand(self.batch, 1)
+            if self.ragged:   # a row's position counts from its first real token; s_pos is the cache row
+                pos = (self.s_pos - self.s_start).view(self.batch, 1)
+            else:
+                pos = self.s_pos.view(1, 1).expand(self.batch, 1)
             for layer in base.layers:
                 h = layer(h, attention_mask=None, position_ids=pos, past_key_values=self.cache, use_cache=True)
                 if isinstance(h, tuple):
@@ -177,7 +235,7 @@ class GraphDecoder:
 
     @torch.no_grad()
     def generate(self, prompt, new_tokens, return_prefill_logits=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-                 seed=0, eos_token_id=None, pad_token_id=None, append=False, prefill_chunk=None):
+                 seed=0, eos_token_id=None, pad_token_id=None, append=False, prefill_chunk=None, attention_mask=None):
         """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens].  ``append=True`` continues the conversation
         the cache holds (a second turn): the token the previous ``generate`` emitted last, which the cache has not seen yet, and
         the prompt are written behind the cached rows, so the cache holds every token the caller has seen, in order; positions
@@ -185,8 +243,13 @@ class GraphDecoder:
         an empty decoder it is a plain ``generate``.  ``prefill_chunk``: see ``prefill``.  On a decoder built with ``sampling=True``:
         ``do_sample`` draws every token by temperature / top-k / top-p sampling (``seed``: the 64-bit Philox key; token i of
         row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
-        finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on."""
+        finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on.
+        ``attention_mask`` (a decoder built with ``ragged=True`` only): the keep flags of a left-padded prompt, see ``prefill``; the
+        return value holds the pad columns as given."""
         B, P = prompt.shape
+        if attention_mask is not None and append:
+            raise ValueError("GraphDecoder: append=True takes no attention_mask: a second turn that is itself ragged would put pads "
+                             "in the middle of the cache")
         if self.kv_bits == 8 and not self.kv8_append and (append or prefill_chunk is not None):
             raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
                              "built with kv8_append=True: append=True and prefill_chunk then attend quantised rows")
@@ -200,7 +263,7 @@ class GraphDecoder:
             if (do_sample or temperature != 1.0 or top_k != 0 or top_p != 1.0 or seed != 0 or eos_token_id is not None
                     or pad_token_id is not None):
                 raise ValueError("GraphDecoder: sampling and EOS arguments need a decoder built with sampling=True")
-            out = self.prefill(feed, chunk=prefill_chunk, append=append)
+            out = self.prefill(feed, chunk=prefill_chunk, append=append, attention_mask=attention_mask)
             tok = out.logits[:, -1].argmax(-1, keepdim=True)
             self.out_buf[:, :1].copy_(tok)
             self.s_tok.copy_(tok)
@@ -212,7 +275,7 @@ class GraphDecoder:
             sampling_params(temperature=float(temperature) if do_sample else 0.0, top_k=top_k, top_p=top_p, seed=seed,
                             eos_token_id=eos_token_id, pad_token_id=0 if pad_token_id is None else pad_token_id, out=self.params)
             self.done.zero_()
-            out = self.prefill(feed, chunk=prefill_chunk, append=append)
+            out = self.prefill(feed, chunk=prefill_chunk, append=append, attention_mask=attention_mask)
             # the first token: the same op on the prompt's logits at column 0 (it leaves position = rows fed, column = 1)
             self.s_pos.fill_(fed - 1)
             self.s_idx.fill_(0)
@@ -228,22 +291,37 @@ class GraphDecoder:
                 self.graph.replay()
                 left -= 1
             else:
-                self._advance()
+                with self._promise():
+                    self._advance()
                 left -= 1
         if new_tokens >= 1:   # every emitted token but the last has been fed back and cached
             self.rows, self._pending = fed + new_tokens - 1, True
         tokens = torch.cat([prompt, self.out_buf[:, :new_tokens]], dim=1)
         return (tokens, out.logits[:, -1]) if return_prefill_logits else tokens
 
-    def prefill(self, prompt, chunk=None, append=False):
+    def prefill(self, prompt, chunk=None, append=False, attention_mask=None):
         """Run the (unpadded) prompt [batch, P] eagerly; returns the model output of the last piece, whose logits hold the LAST
         position only where the model's forward can be told so.  By default the cache is emptied first.  ``chunk=c``: the
         prompt runs in pieces of at most ``c`` tokens, each behind the rows already written (activations are [batch, c, .]
         instead of [batch, P, .]).  ``append=True``: the prompt starts behind the rows the cache holds (``self.rows``) instead
         of emptying it.  Accelerated models attend the first piece of an emptied cache under ``fresh_static_prefill`` and every
         other piece under ``appended_static_prefill`` (``int8_rows=True`` on a decoder built with ``kv8_append=True``); other
-        models run the same calls on their stock path."""
+        models run the same calls on their stock path.
+        ``attention_mask`` (a decoder built with ``ragged=True`` only; ``None`` there means all ones): [batch, P] keep flags of a
+        LEFT-padded batch (``left_pad_starts`` checks it: one host read).  Row b's first real column becomes ``s_start[b]``, the
+        pieces run with ``position_ids`` counted from it (pads: 0), and the attention blocks neither attend nor read the pad rows
+        (``llama_modules.padded_static_batch``); what the pad tokens left in the cache is never read.  The last column is real in
+        every row.  With ``append=True`` a mask raises; without one the first turn's starts persist."""
         P = prompt.shape[1]
+        if attention_mask is not None:
+            if not self.ragged:
+                raise ValueError("GraphDecoder: attention_mask needs a decoder built with ragged=True")
+            if append:
+                raise ValueError("GraphDecoder: append=True takes no attention_mask: a second turn that is itself ragged would put "
+                                 "pads in the middle of the cache")
+            if tuple(attention_mask.shape) != tuple(prompt.shape):
+                raise ValueError("GraphDecoder: attention_mask must have the prompt's shape [batch, P]")
+            starts = left_pad_starts(attention_mask)
         if self.kv_bits == 8 and not self.kv8_append and (append or chunk is not None):
             raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
                              "built with kv8_append=True: append=True and chunk= then attend quantised rows")
@@ -264,18 +342,25 @@ class GraphDecoder:
                 torch._foreach_zero_([layer.cumulative_length for layer in self.cache.layers])   # one launch for all layers
             else:
                 self.cache.reset()
+        if self.ragged and not append:
+            if attention_mask is None:
+                self.s_start.zero_()
+            else:
+                self.s_start.copy_(starts)
         out = None
         for c0 in range(0, P, step):
             c1 = min(P, c0 + step)
+            rows = torch.arange(start + c0, start + c1, device=prompt.device)
+            # ragged: a token's position counts from its row's first real token (pads: 0)
+            ragged_pos = {"position_ids": (rows[None, :] - self.s_start[:, None]).clamp_min(0)} if self.ragged else {}
             if not fresh:
                 ctx = contextlib.nullcontext()
             elif c0 == 0 and not append:
                 ctx = fresh_static_prefill()
             else:   # behind rows 0 .. start + c0 - 1, which are this sequence's tokens (llama_modules.appended_static_prefill)
                 ctx = appended_static_prefill(int8_rows=True) if self.kv8_append else appended_static_prefill()
-            with ctx:
-                out = self.model(prompt[:, c0:c1], past_key_values=self.cache,
-                                 cache_position=torch.arange(start + c0, start + c1, device=prompt.device), use_cache=True,
-                                 **self._last_logits_only)
+            with ctx, self._promise():
+                out = self.model(prompt[:, c0:c1], past_key_values=self.cache, cache_position=rows, use_cache=True,
+                                 **ragged_pos, **self._last_logits_only)
         self.rows, self._pending = start + P, False
         return out

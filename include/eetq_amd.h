@@ -592,6 +592,27 @@ int eetq_rope_decode_attention_bounded_f16(const int64_t* positions, const int64
                                            int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
                                            int kv_len_bias, int64_t* advance, void* stream);
 
+/* The decode entries with a PER-ROW FIRST KEY (extension, added within ABI revision 7): eetq_decode_attention_f16 and
+ * eetq_rope_decode_attention_bounded_f16 plus kv_start, a DEVICE int64 [batch] array: batch row b of a left-padded batch attends
+ * cache rows [s, valid length), s = kv_start[b]; rows below s are padding and are neither read nor written.  The K, V and mask bases
+ * move by s rows and the valid length and the slot are taken relative to s, so blocks and chunks are counted from the row's first
+ * real token: out[b] has the bits of the twin entry called on row b alone, on a cache of the same capacity whose rows [0, S - s)
+ * are this cache's rows [s, S), with slots - s and kv_len - s and the same splits, mask (moved by s) and scaling.  The new token
+ * is written at its absolute slot; advance, tickets, workspace and the dropped-step counter as in the twins; the two forms stay
+ * bit-identical to each other.  s is kept inside [0, slot] (one-launch form) or [0, valid length - 1] (two-launch form): a start
+ * beyond it is a caller error that attends that one row and touches nothing outside the cache.  All-zero kv_start: the twin's bits.
+ * Errors as the twins, plus a null kv_start (EETQ_ERR_INVALID, nothing launched). */
+int eetq_decode_attention_padded_f16(const void* q, const void* k_cache, const void* v_cache, const void* mask, void* out,
+                                     float* workspace, int batch, int heads, int kv_heads, int positions, int head_dim,
+                                     int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                                     const int64_t* kv_start, int64_t* advance, void* stream);
+int eetq_rope_decode_attention_padded_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                          const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                          void* k_cache, void* v_cache, const void* mask, void* out, float* workspace,
+                                          unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                          int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                          int kv_len_bias, const int64_t* kv_start, int64_t* advance, void* stream);
+
 /* The int8 KV cache (extension, added within ABI revision 7).  One cache ROW is the head_dim fp16 values of one (batch row, kv
  * head, position); rows are quantised symmetrically, each with a scale of its own:
  *   amax = max_d |x_d| (exact);  s = fp16(fp32(amax) * (1.0f / 127.0f)), one fp32 multiply, round to nearest even;
@@ -676,6 +697,16 @@ int eetq_prefill_attention_supported(int head_dim);
 int eetq_prefill_attention_dev_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
                                    int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
                                    int splits, float scaling, const long* strides, void* stream);
+/* eetq_prefill_attention_dev_f16 with a PER-ROW FIRST KEY (added within ABI revision 7): kv_start is a DEVICE int64 [batch] array,
+ * kv_start[b] the first real cache row of batch row b of a left-padded batch.  With keys as above, koff = keys - q_tokens (query t
+ * sits at cache row koff + t) and p = clamp(kv_start[b] - koff, 0, q_tokens) pad queries: out[b][:p] is ZEROS; out[b][p:] has the
+ * bits of eetq_prefill_attention_dev_f16 called on row b alone with q, k, v and out moved to the first real row -- q_tokens - p
+ * queries, keys - kv_start[b] keys, the same splits and scaling -- i.e. key blocks, query blocks and split shares are counted from
+ * the row's first real token; no cache row below kv_start[b] is read.  All-zero kv_start: the bits of the plain entry.  kv_len NULL:
+ * keys = max_keys (a fresh prompt).  Workspace and splits as there.  Errors as there, plus a null kv_start. */
+int eetq_prefill_attention_padded_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                      int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                      const int64_t* kv_start, int splits, float scaling, const long* strides, void* stream);
 /* The split count eetq_prefill_attention_dev_f16 is tuned for (pure host function; callers size the workspace with it; 1 = unsplit).
  * With g = ceil(q_tokens / 128) * heads * batch workgroups and n = ceil(max_keys / 64) key blocks: the largest power of two s <= 16
  * such that, for every power of two s' <= s, s' g <= 1.25 compute units and n / s' >= 4 (s' g <= half the compute units), 8 (s' g <=
