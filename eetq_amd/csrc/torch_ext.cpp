@@ -843,6 +843,52 @@ void sample_handover(const Tensor& logits, Tensor& out_tokens, Tensor& column, T
                                    stream_of(logits)));
 }
 
+// Prompt-lookup draft of a speculative step (extension): per row of hist [B, cols] (int64, dense rows, any row stride) the k = draft.size(1)
+// tokens that followed the longest recent n-gram (n <= max_ngram) repeating the row's tail, L = position + 1 tokens long (a DEVICE
+// int64 scalar) -> draft [B, k] (eetq_spec_ngram_draft_i64)
+void ngram_draft(const Tensor& hist, const Tensor& position, Tensor& draft, int64_t max_ngram)
+{
+    const char* name = "ngram_draft: ";
+    TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == at::kLong && hist.dim() == 2 && hist.stride(1) == 1 && hist.size(1) > 0, name,
+                "hist must be an int64 CUDA tensor [B, cols] with dense rows");
+    const int64_t B = hist.size(0);
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&position, &draft})
+        TORCH_CHECK(t->scalar_type() == at::kLong && t->device() == hist.device(), name, "int64 tensors on the history's device expected");
+    TORCH_CHECK(draft.dim() == 2 && draft.size(0) == B && draft.stride(1) == 1 && position.numel() == 1 && B > 0, name, "shape mismatch");
+    TORCH_CHECK(draft.size(1) >= 1 && draft.size(1) <= 15, name, "the draft holds 1 .. 15 tokens per row");
+    TORCH_CHECK(max_ngram >= 1 && max_ngram <= 8, name, "max_ngram must lie in 1 .. 8");
+    c10::DeviceGuard guard(hist.device());
+    check(eetq_spec_ngram_draft_i64(hist.data_ptr<int64_t>(), (long)hist.stride(0), (int)hist.size(1), (int)B, position.data_ptr<int64_t>(),
+                                    (int)max_ngram, (int)draft.size(1), draft.data_ptr<int64_t>(), (long)draft.stride(0), stream_of(hist)));
+}
+
+// Verify, accept and hand-over of a speculative step (extension): logits [B, k + 1, V] (fp16, V dense) of the rows [pending token |
+// draft]; the tokens every row confirms go to out_tokens / hist, the last one to next_token; position, column and stats advance on
+// the device (eetq_spec_accept_f16)
+void spec_accept(const Tensor& logits, const Tensor& draft, Tensor& out_tokens, Tensor& column, Tensor& next_token, Tensor& position,
+                 const Tensor& limit, Tensor& hist, Tensor& stats)
+{
+    const char* name = "spec_accept: ";
+    TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kHalf && logits.dim() == 3 && logits.stride(2) == 1, name,
+                "logits must be a float16 CUDA tensor [B, k + 1, V] with dense rows");
+    const int64_t B = logits.size(0), T = logits.size(1), V = logits.size(2);
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&draft, &out_tokens, &column, &next_token, &position, &limit, &hist, &stats})
+        TORCH_CHECK(t->scalar_type() == at::kLong && t->device() == logits.device(), name, "int64 tensors on the logits' device expected");
+    TORCH_CHECK(T >= 2 && T <= 16 && B > 0 && V > 0 && draft.dim() == 2 && draft.size(0) == B && draft.size(1) == T - 1 &&
+                    draft.stride(1) == 1 && out_tokens.dim() == 2 && out_tokens.size(0) == B && out_tokens.stride(1) == 1 &&
+                    hist.dim() == 2 && hist.size(0) == B && hist.stride(1) == 1 && next_token.numel() == B &&
+                    (next_token.dim() == 1 || (next_token.dim() == 2 && next_token.size(1) == 1)) && column.numel() == 1 &&
+                    position.numel() == 1 && limit.numel() == 1 && stats.numel() == 2 && stats.is_contiguous(),
+                name, "shape mismatch");
+    c10::DeviceGuard guard(logits.device());
+    check(eetq_spec_accept_f16(logits.data_ptr(), (long)(B == 1 ? T * V : logits.stride(0)), (long)logits.stride(1), (int)V, (int)B,
+                               (int)(T - 1), draft.data_ptr<int64_t>(), (long)draft.stride(0), out_tokens.data_ptr<int64_t>(),
+                               (long)out_tokens.stride(0), (int)out_tokens.size(1), column.data_ptr<int64_t>(),
+                               position.data_ptr<int64_t>(), limit.data_ptr<int64_t>(), next_token.data_ptr<int64_t>(),
+                               (long)(B == 1 ? 1 : next_token.stride(0)), hist.data_ptr<int64_t>(), (long)hist.stride(0),
+                               (int)hist.size(1), stats.data_ptr<int64_t>(), stream_of(logits)));
+}
+
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
                         int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
@@ -1959,6 +2005,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("sample_handover", &sample_handover, "temperature / top-k / top-p sampling + token hand-over of a decode step",
           py::arg("logits"), py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"), py::arg("params"),
           py::arg("done") = py::none(), py::arg("uniforms") = py::none());
+    m.def("ngram_draft", &ngram_draft, "prompt-lookup draft of a speculative decode step", py::arg("hist"), py::arg("position"),
+          py::arg("draft"), py::arg("max_ngram") = 3);
+    m.def("spec_accept", &spec_accept, "verify + accept + token hand-over of a speculative decode step", py::arg("logits"),
+          py::arg("draft"), py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"), py::arg("limit"),
+          py::arg("hist"), py::arg("stats"));
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,

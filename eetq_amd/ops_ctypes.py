@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported",
-           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
+           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
@@ -1159,6 +1159,61 @@ def sample_handover(logits, out_tokens, column, next_token, position, params, do
                                                   out_tokens.shape[1], _ptr(column), _ptr(next_token), _ptr(position),
                                                   _ptr(params), _ptr(done) if done is not None else None,
                                                   _ptr(uniforms) if uniforms is not None else None, _stream_ptr()))
+    return None
+
+
+@_eager_only
+def ngram_draft(hist, position, draft, max_ngram=3):
+    """Prompt-lookup draft of a speculative step in one launch: per row of ``hist`` [B, cols] (int64, dense rows, any row stride),
+    whose first ``position + 1`` columns are the row's tokens (``position``: an int64 device scalar; the last token is the pending
+    one), the ``k = draft.shape[1]`` tokens that followed the longest recent n-gram (``n <= max_ngram``, the most recent among
+    equals) repeating the row's tail go to ``draft`` [B, k]; a match that runs off the end continues into its own draft, no match
+    repeats the pending token.  (eetq_spec_ngram_draft_i64)"""
+    name = "ngram_draft: "
+    if not hist.is_cuda or hist.dtype != torch.int64 or hist.dim() != 2 or hist.stride(1) != 1 or hist.shape[1] <= 0:
+        raise RuntimeError(name + "hist must be an int64 CUDA tensor [B, cols] with dense rows")
+    B = hist.shape[0]
+    for t in (position, draft):
+        if t.dtype != torch.int64 or t.device != hist.device:
+            raise RuntimeError(name + "int64 tensors on the history's device expected")
+    if draft.dim() != 2 or draft.shape[0] != B or draft.stride(1) != 1 or position.numel() != 1 or B <= 0:
+        raise RuntimeError(name + "shape mismatch")
+    if not 1 <= draft.shape[1] <= 15:
+        raise RuntimeError(name + "the draft holds 1 .. 15 tokens per row")
+    if not 1 <= int(max_ngram) <= 8:
+        raise RuntimeError(name + "max_ngram must lie in 1 .. 8")
+    with torch.cuda.device(hist.device):
+        check(_lib.lib().eetq_spec_ngram_draft_i64(_ptr(hist), hist.stride(0), hist.shape[1], B, _ptr(position), int(max_ngram),
+                                                   draft.shape[1], _ptr(draft), draft.stride(0), _stream_ptr()))
+    return None
+
+
+@_eager_only
+def spec_accept(logits, draft, out_tokens, column, next_token, position, limit, hist, stats):
+    """Verify, accept and hand-over of a speculative step in one launch: ``logits`` [B, k + 1, V] (fp16, V dense) are the verify
+    pass over [pending token | ``draft`` [B, k]].  With g the row argmaxes (``greedy_handover``'s rule) and n the number of leading
+    draft tokens EVERY row confirms, ``adv = clamp(min(n + 1, limit - column), 0, k + 1)`` tokens are handed over: ``g[:, j]`` to
+    ``out_tokens[:, column + j]`` and ``hist[:, position + 1 + j]``, ``g[:, adv - 1]`` to ``next_token`` [B] or [B, 1]; then
+    ``position += adv``, ``column += adv``, ``stats += (1, adv)`` (int64 device tensors).  (eetq_spec_accept_f16)"""
+    name = "spec_accept: "
+    if not logits.is_cuda or logits.dtype != torch.float16 or logits.dim() != 3 or logits.stride(2) != 1:
+        raise RuntimeError(name + "logits must be a float16 CUDA tensor [B, k + 1, V] with dense rows")
+    B, T, V = logits.shape
+    for t in (draft, out_tokens, column, next_token, position, limit, hist, stats):
+        if t.dtype != torch.int64 or t.device != logits.device:
+            raise RuntimeError(name + "int64 tensors on the logits' device expected")
+    if (not 2 <= T <= 16 or B <= 0 or V <= 0 or draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] != T - 1
+            or draft.stride(1) != 1 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or out_tokens.stride(1) != 1
+            or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1 or next_token.numel() != B
+            or not (next_token.dim() == 1 or (next_token.dim() == 2 and next_token.shape[1] == 1)) or column.numel() != 1
+            or position.numel() != 1 or limit.numel() != 1 or stats.numel() != 2 or not stats.is_contiguous()):
+        raise RuntimeError(name + "shape mismatch")
+    with torch.cuda.device(logits.device):
+        check(_lib.lib().eetq_spec_accept_f16(_ptr(logits), T * V if B == 1 else logits.stride(0), logits.stride(1), V, B, T - 1,
+                                              _ptr(draft), draft.stride(0), _ptr(out_tokens), out_tokens.stride(0),
+                                              out_tokens.shape[1], _ptr(column), _ptr(position), _ptr(limit), _ptr(next_token),
+                                              1 if B == 1 else next_token.stride(0), _ptr(hist), hist.stride(0), hist.shape[1],
+                                              _ptr(stats), _stream_ptr()))
     return None
 
 

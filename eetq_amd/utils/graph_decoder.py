@@ -40,7 +40,7 @@ def left_pad_starts(mask):
 
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
-                 ragged=False):
+                 ragged=False, speculative=0, ngram=3, draft=None):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -69,7 +69,22 @@ class GraphDecoder:
         its graphs under ``llama_modules.padded_static_batch(s_start)`` -- the attention kernels then count every row's blocks from
         its first real token and never read its pad rows -- and steps with ``position_ids = s_pos - s_start`` (one small launch per
         step, inside the graph); ``s_pos`` remains the cache row.  The decode step goes through the attention module instead of
-        the one-call layer.  It needs the lean layer-by-layer model with head size 64 or 128 and an fp16 cache (``kv_bits=16``)."""
+        the one-call layer.  It needs the lean layer-by-layer model with head size 64 or 128 and an fp16 cache (``kv_bits=16``).
+        ``speculative`` (default 0: nothing changes, no state, the same graphs): ``k`` in 1 .. 15 builds a speculative greedy
+        decoder.  One verify step drafts ``k`` tokens, runs the model once over the ``k + 1`` rows
+        [pending token | draft] behind the cached rows (``appended_static_prefill``: the attention blocks write rows counter ..
+        counter + k and attend through the device counter), and ``ops.spec_accept`` hands over the 1 .. k + 1 tokens every batch
+        row confirms; the rejected rows are rolled back by setting the cache counters to the position (rows at or beyond the
+        counter are never read).  The emitted tokens are those of greedy decoding up to the kernels' rounding: a verify pass
+        computes a token's logits with the prompt kernels, a plain step with the decode kernels.  The step is its own captured
+        graph; the plain graphs are captured too and serve ``generate(speculate=False)``.  It needs what ``ragged`` needs --
+        ``lean``, a fully accelerated model, head size 64 or 128, ``kv_bits=16`` -- and the MFMA prompt kernel; ``ragged``,
+        ``sampling`` and ``kv_bits=8`` raise ``ValueError``.  ``generate`` then needs ``k`` spare cache rows.
+        ``ngram`` (1 .. 8): the longest n-gram ``ops.ngram_draft`` looks up in the sequence's own history (``s_hist``).
+        ``draft``: a callable ``draft(decoder) -> [batch, k]`` int64 tokens on the device (valid vocabulary ids) instead of the
+        lookup: the hook for a draft model and for tests.  Under capture its launches are what the graph holds: it is called
+        while capturing, never per step, so it must read and write static tensors only (``s_hist``, ``s_pos``, ``s_tok`` ...)
+        and read nothing on the host."""
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
         if kv8_append and kv_bits != 8:
@@ -80,6 +95,9 @@ class GraphDecoder:
         self.sampling = bool(sampling)
         self.model = model
         self.ragged = bool(ragged)
+        self.speculative = self._check_speculative(speculative, ngram, draft, max_len)
+        self.ngram = int(ngram)
+        self._draft_fn = draft
         if self.ragged:
             if self.kv_bits != 16:
                 raise ValueError("GraphDecoder: ragged=True needs an fp16 cache (kv_bits=16): the int8 kernels take no per-row first "
@@ -127,6 +145,16 @@ class GraphDecoder:
             self.done = torch.zeros(self.batch, dtype=torch.int32, device=dev)   # per row: EOS drawn (readable after generate)
         self.graph = None
         self.graph_n = None
+        self.graph_spec = None
+        if self.speculative:
+            k = self.speculative
+            # the rows' tokens by cache row (column position = the pending token), the step's draft, the output column generate
+            # stops at, (verify steps, tokens) of the current generate
+            self.s_hist = torch.zeros(self.batch, self.max_len, dtype=torch.long, device=dev)
+            self.s_draft = torch.zeros(self.batch, k, dtype=torch.long, device=dev)
+            self.s_limit = torch.zeros(1, dtype=torch.long, device=dev)
+            self.s_stats = torch.zeros(2, dtype=torch.long, device=dev)
+            self._spec_offsets = torch.arange(k + 1, dtype=torch.long, device=dev)
         # the prompt pass needs the LAST position's logits only (the stock forward projects all of them onto the vocabulary)
         params = inspect.signature(model.forward).parameters
         self._last_logits_only = {"logits_to_keep": 1} if "logits_to_keep" in params else {}
@@ -140,6 +168,8 @@ class GraphDecoder:
             if capture:
                 with self._promise():   # (the allocating forward above ran without it: no cache layer, nothing to promise yet)
                     self._capture()
+                if self.speculative:
+                    self._capture_spec()
         self.cache.reset()
         # host-side bookkeeping of a conversation: cache rows written, and whether s_tok holds a token the caller has seen but the
         # cache has not (the last one a generate() emitted)
@@ -161,6 +191,64 @@ class GraphDecoder:
             with torch.cuda.graph(self.graph_n):
                 for _ in range(self.steps_per_graph):
                     self._advance()
+
+    def _check_speculative(self, speculative, ngram, draft, max_len):
+        """The checked ``speculative`` (0: off).  Every refusal says which setting and why."""
+        if isinstance(speculative, bool) or not isinstance(speculative, int) or not 0 <= speculative <= 15:
+            raise ValueError("GraphDecoder: speculative must be 0 (off) or the draft length, 1 .. 15, got %r" % (speculative,))
+        if not speculative:
+            if draft is not None:
+                raise ValueError("GraphDecoder: draft= is the draft of a speculative decoder (speculative=k)")
+            return 0
+        if isinstance(ngram, bool) or not isinstance(ngram, int) or not 1 <= ngram <= 8:
+            raise ValueError("GraphDecoder: ngram must lie in 1 .. 8, got %r" % (ngram,))
+        if draft is not None and not callable(draft):
+            raise ValueError("GraphDecoder: draft must be a callable draft(decoder) -> [batch, k] int64 tokens on the device")
+        if self.sampling:
+            raise ValueError("GraphDecoder: speculative=%d does greedy verification only: a draft token is accepted when it IS the "
+                             "argmax, which says nothing about a sampled token (sampling=True)" % speculative)
+        if self.ragged:
+            raise ValueError("GraphDecoder: speculative=%d advances all rows by one shared cache counter and one position; "
+                             "ragged=True steps every row from its own first key" % speculative)
+        if self.kv_bits != 16:
+            raise ValueError("GraphDecoder: speculative=%d needs fp16 cache rows (kv_bits=16): the verify pass attends behind the "
+                             "device counter with the fp16 prompt kernel, got kv_bits=%r" % (speculative, self.kv_bits))
+        if not self._lean():
+            raise ValueError("GraphDecoder: speculative=%d needs lean=True and a fully accelerated model (eet_accelerator with "
+                             "fused_attn, fused_mlp and fused_residual): the verify pass is the lean layer loop over k + 1 rows, "
+                             "and only the accelerated attention blocks attend through the device counter" % speculative)
+        from .. import ops
+        for layer in self.model.model.layers:
+            attn = getattr(layer, "self_attn", None)
+            if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
+                raise ValueError("GraphDecoder: speculative=%d needs attention blocks with head size 64 or 128" % speculative)
+            if (not getattr(attn, "mfma_prefill", False) or not getattr(attn, "static_prefill", False) or ops.prefill_attention is None
+                    or not ops.prefill_attention_supported(attn.head_dim)):
+                raise ValueError("GraphDecoder: speculative=%d needs the MFMA prompt kernel (the compiled operator module, "
+                                 "mfma_prefill=True, static_prefill=True): no other path attends k + 1 rows behind a device "
+                                 "counter" % speculative)
+        if int(max_len) < speculative + 1:
+            raise ValueError("GraphDecoder: speculative=%d writes %d cache rows per verify step, the cache has %d"
+                             % (speculative, speculative + 1, int(max_len)))
+        return int(speculative)
+
+    def _capture_spec(self):
+        """Warm the verify step up and capture it.  With ``s_limit`` = 0 a step hands over nothing and rolls back to row 0."""
+        counters = [layer.cumulative_length for layer in self.cache.layers]
+        torch._foreach_zero_(counters)
+        self.s_pos.zero_()
+        self.s_idx.zero_()
+        self.s_limit.zero_()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._advance_spec()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph_spec = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph_spec):
+            self._advance_spec()
+        self.s_stats.zero_()
 
     def _promise(self):
         """``padded_static_batch(s_start)`` on a ragged decoder (every forward, captured or eager, runs inside it), else nothing."""
@@ -233,9 +321,51 @@ class GraphDecoder:
         self.s_pos.add_(1)
         self.s_idx.add_(1)
 
+    def _advance_spec(self):
+        """One verify step, all on the device: draft, the model over the k + 1 rows [pending token | draft] behind the cached
+        rows, accept + hand-over of 1 .. k + 1 tokens, and the rollback of the rejected rows (counter = position)."""
+        from .. import ops
+        from ..modules.llama_modules import appended_static_prefill
+        k = self.speculative
+        if self._draft_fn is not None:
+            d = self._draft_fn(self)
+            if (not torch.is_tensor(d) or tuple(d.shape) != (self.batch, k) or d.dtype != torch.long or d.device != self.s_draft.device):
+                raise ValueError("GraphDecoder: draft(decoder) must return [batch, k] = [%d, %d] int64 tokens on the device"
+                                 % (self.batch, k))
+            if d is not self.s_draft:
+                self.s_draft.copy_(d)
+        else:
+            ops.ngram_draft(self.s_hist, self.s_pos, self.s_draft, self.ngram)
+        base = self.model.model
+        ids = torch.cat([self.s_tok, self.s_draft], dim=1)                                    # [B, k + 1]
+        pos = (self.s_pos + self._spec_offsets).view(1, k + 1).expand(self.batch, k + 1)      # cache rows = positions
+        h = base.embed_tokens(ids)
+        with appended_static_prefill():
+            for layer in base.layers:
+                h = layer(h, attention_mask=None, position_ids=pos, past_key_values=self.cache, use_cache=True)
+                if isinstance(h, tuple):
+                    h = h[0]
+        lg = self.model.lm_head(base.norm(h))
+        if not (lg.is_cuda and lg.dtype == torch.float16):
+            raise ValueError("GraphDecoder: speculative decoding needs float16 logits on the GPU (got %s on %s)" % (lg.dtype, lg.device))
+        ops.spec_accept(lg if lg.stride(-1) == 1 else lg.contiguous(), self.s_draft, self.out_buf, self.s_idx, self.s_tok, self.s_pos,
+                        self.s_limit, self.s_hist, self.s_stats)
+        # the rollback: the blocks advanced their counters by k + 1; rows at or beyond the position were rejected (or hold the
+        # new pending token's predecessors' drafts) and are never read once the counter says so -- one launch for all layers
+        counters = [layer.cumulative_length for layer in self.cache.layers]
+        torch._foreach_copy_(counters, [self.s_pos.view(c.shape) for c in counters])
+
+    def spec_stats(self):
+        """(verify steps, tokens they handed over) of the last ``generate`` on a speculative decoder -- the first token, which
+        comes from the prompt's logits, is not among them.  One host read."""
+        if not self.speculative:
+            raise ValueError("GraphDecoder: spec_stats() needs a decoder built with speculative=k")
+        steps, tokens = self.s_stats.tolist()
+        return steps, tokens
+
     @torch.no_grad()
     def generate(self, prompt, new_tokens, return_prefill_logits=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-                 seed=0, eos_token_id=None, pad_token_id=None, append=False, prefill_chunk=None, attention_mask=None):
+                 seed=0, eos_token_id=None, pad_token_id=None, append=False, prefill_chunk=None, attention_mask=None, speculate=None):
         """prompt [batch, P] int64 on the model's device -> [batch, P + new_tokens].  ``append=True`` continues the conversation
         the cache holds (a second turn): the token the previous ``generate`` emitted last, which the cache has not seen yet, and
         the prompt are written behind the cached rows, so the cache holds every token the caller has seen, in order; positions
@@ -245,8 +375,19 @@ class GraphDecoder:
         row b uses counter (i, b), so one seed gives one output), otherwise the argmax; a row that emits ``eos_token_id`` is
         finished (``self.done``) and holds ``pad_token_id`` (default 0) from the next position on.
         ``attention_mask`` (a decoder built with ``ragged=True`` only): the keep flags of a left-padded prompt, see ``prefill``; the
-        return value holds the pad columns as given."""
+        return value holds the pad columns as given.
+        ``speculate``: ``None`` = on exactly when the decoder was built with ``speculative=k``; ``True`` on a plain decoder raises;
+        ``False`` on a speculative one runs the plain graphs (and keeps ``s_hist`` up to date).  A speculative call needs
+        ``k`` cache rows beyond the last token's -- a verify pass writes up to k rows past the last kept one -- replays the verify
+        graph in batches of ceil(left / (k + 1)) with ONE host read of the output column after each batch, and stops exactly at
+        ``new_tokens`` (``s_limit`` clamps the last step on the device).  ``rows``, ``s_tok`` and the cache mean what they mean
+        after a plain call, so ``append=True`` turns mix freely.  ``spec_stats()`` reports the steps it took."""
         B, P = prompt.shape
+        if speculate is None:
+            speculate = bool(self.speculative)
+        elif speculate and not self.speculative:
+            raise ValueError("GraphDecoder: speculate=True needs a decoder built with speculative=k")
+        speculate = bool(speculate)
         if attention_mask is not None and append:
             raise ValueError("GraphDecoder: append=True takes no attention_mask: a second turn that is itself ragged would put pads "
                              "in the middle of the cache")
@@ -259,6 +400,10 @@ class GraphDecoder:
         fed = start + feed.shape[1]                      # cache rows once the prompt is in
         if B != self.batch or fed + new_tokens > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))
+        if speculate and fed + new_tokens + self.speculative > self.max_len:
+            raise ValueError("GraphDecoder: a speculative generate needs %d spare cache rows (a verify pass writes up to k rows past "
+                             "the last kept one): %d rows fed + %d new tokens + %d > %d cache rows"
+                             % (self.speculative, fed, new_tokens, self.speculative, self.max_len))
         if not self.sampling:
             if (do_sample or temperature != 1.0 or top_k != 0 or top_p != 1.0 or seed != 0 or eos_token_id is not None
                     or pad_token_id is not None):
@@ -283,6 +428,20 @@ class GraphDecoder:
             ops.sample_handover(last if last.stride(-1) == 1 else last.contiguous(), self.out_buf, self.s_idx, self.s_tok, self.s_pos, self.params,
                                 self.done)
         left = new_tokens - 1
+        if self.speculative:
+            self.s_stats.zero_()
+            if new_tokens >= 1:
+                self.s_hist[:, fed:fed + 1].copy_(self.s_tok)   # the pending token's column is its cache row to be
+        if speculate and left > 0:
+            k = self.speculative
+            self.s_limit.fill_(new_tokens)
+            while left > 0:
+                for _ in range(-(-left // (k + 1))):   # the fewest steps that can finish; the device clamp forbids an overshoot
+                    if self.graph_spec is not None:
+                        self.graph_spec.replay()
+                    else:
+                        self._advance_spec()
+                left = new_tokens - int(self.s_idx)    # the one host read of a batch
         while left > 0:
             if self.graph_n is not None and left >= self.steps_per_graph:
                 self.graph_n.replay()
@@ -294,6 +453,8 @@ class GraphDecoder:
                 with self._promise():
                     self._advance()
                 left -= 1
+        if self.speculative and not speculate and new_tokens > 1:   # the plain graphs do not keep the history
+            self.s_hist[:, fed + 1:fed + new_tokens].copy_(self.out_buf[:, 1:new_tokens])
         if new_tokens >= 1:   # every emitted token but the last has been fed back and cached
             self.rows, self._pending = fed + new_tokens - 1, True
         tokens = torch.cat([prompt, self.out_buf[:, :new_tokens]], dim=1)
@@ -362,5 +523,7 @@ class GraphDecoder:
             with ctx, self._promise():
                 out = self.model(prompt[:, c0:c1], past_key_values=self.cache, cache_position=rows, use_cache=True,
                                  **ragged_pos, **self._last_logits_only)
+        if self.speculative:   # a token's column in the history is its cache row
+            self.s_hist[:, start:start + P].copy_(prompt)
         self.rows, self._pending = start + P, False
         return out

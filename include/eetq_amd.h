@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count, eetq_diag_tile_plan).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count, eetq_diag_tile_plan, eetq_spec_ngram_draft_i64, eetq_spec_accept_f16).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -544,6 +544,39 @@ int eetq_greedy_handover_f16(const void* logits, long row_stride, int vocab, int
 int eetq_sample_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
                              int out_cols, int64_t* column, int64_t* next_token, int64_t* position, const void* params,
                              int32_t* done, const float* uniforms, void* stream);
+
+/* Speculative greedy decoding by n-gram lookup (extension, added within ABI 7; what transformers' generate does with
+ * prompt_lookup_num_tokens): a draft of k tokens from the sequence's own history, and the hand-over of a verify pass over
+ * k + 1 rows.  Both are one launch each, capturable, no host sync, no allocation, no atomics: deterministic.
+ *
+ * eetq_spec_ngram_draft_i64: hist is int64 [batch][cols] (hist_stride elements apart), *position a DEVICE int64.  Per row,
+ * L = clamp(*position + 1, 1, cols); hist[b][0 .. L-1] are the row's tokens, the last one the pending token.  For
+ * n = min(max_ngram, L - 1) down to 1: the LARGEST e in [n - 1, L - 2] with hist[e-n+1 .. e] == hist[L-n .. L-1]; the first n
+ * with a hit wins (the longest match, the most recent among equals).  Then draft[b][i] = ext[e + 1 + i], i < k, where ext is
+ * hist[b][0 .. L-1] followed by the draft itself (a match that runs off the end continues into its own draft: a period-p
+ * repetition keeps cycling).  No hit: every draft[b][i] = hist[b][L-1].  draft is int64 [batch][k], draft_stride apart.
+ * EETQ_ERR_INVALID (nothing launched): a null hist / position / draft, max_ngram outside 1 .. 8, k outside 1 .. 15,
+ * batch <= 0, cols <= 0, hist_stride < cols, draft_stride < k, a pointer that is not 8-byte aligned. */
+int eetq_spec_ngram_draft_i64(const int64_t* hist, long hist_stride, int cols, int batch, const int64_t* position, int max_ngram,
+                              int k, int64_t* draft, long draft_stride, void* stream);
+
+/* eetq_spec_accept_f16: logits is fp16 [batch][k + 1][vocab] (stride_b / stride_t elements apart, vocab dense, any alignment
+ * of the rows), the verify pass over [pending token | draft].  g[b][t] = the argmax of logits[b][t] by
+ * eetq_greedy_handover_f16's rule (first index of the maximum, NaN = maximum, -0 == +0).  a_b = the number of leading t < k
+ * with draft[b][t] == g[b][t]; n = min over b of a_b (the rows share one cache counter and advance together);
+ * adv = clamp(min(n + 1, *limit - *column), 0, k + 1).  For j < adv, g[b][j] is written to out_tokens[b][*column + j]
+ * ([batch][out_cols], out_stride apart) and to hist[b][*position + 1 + j] ([batch][hist_cols], hist_stride apart), columns
+ * outside the arrays skipped; with adv > 0, next_token[b * next_stride] = g[b][adv - 1].  Then *position += adv,
+ * *column += adv, stats[0] += 1, stats[1] += adv (DEVICE int64 scalars; stats is int64[2]: verify steps, tokens).  With
+ * adv == 0 only stats[0] moves.  One workgroup walks the rows position by position and stops behind the first position a row
+ * rejects: a rejected draft reads batch rows of logits, an accepted one batch * (k + 1).
+ * EETQ_ERR_INVALID (nothing launched): a null pointer, k outside 1 .. 15, vocab <= 0, batch <= 0, stride_t or stride_b < vocab,
+ * draft_stride < k, out_cols <= 0, out_stride < out_cols, hist_cols <= 0, hist_stride < hist_cols, next_stride < 1, an int64
+ * pointer that is not 8-byte aligned, logits not 2-byte aligned. */
+int eetq_spec_accept_f16(const void* logits, long stride_b, long stride_t, int vocab, int batch, int k, const int64_t* draft,
+                         long draft_stride, int64_t* out_tokens, long out_stride, int out_cols, int64_t* column, int64_t* position,
+                         const int64_t* limit, int64_t* next_token, long next_stride, int64_t* hist, long hist_stride,
+                         int hist_cols, int64_t* stats, void* stream);
 
 /* Single-query (decode) attention over a KV cache; extension used by the EET attention blocks' decode step (the
  * reference delegates the attention product to flash-attn, python/eetq/modules/llama_modules.py:131-143).
