@@ -105,6 +105,8 @@ def _declare(L):
         "eetq_spec_ngram_draft_i64": [vp, ctypes.c_long, i32, i32, vp, i32, i32, vp, ctypes.c_long, vp],
         "eetq_spec_accept_f16": [vp, ctypes.c_long, ctypes.c_long, i32, i32, i32, vp, ctypes.c_long, vp, ctypes.c_long, i32, vp, vp, vp,
                                  vp, ctypes.c_long, vp, ctypes.c_long, i32, vp, vp],
+        "eetq_spec_sample_accept_f16": [vp, ctypes.c_long, ctypes.c_long, i32, i32, i32, vp, ctypes.c_long, vp, ctypes.c_long, i32, vp,
+                                        vp, vp, vp, ctypes.c_long, vp, ctypes.c_long, i32, vp, vp, vp, vp, ctypes.c_long, vp, vp],
         "eetq_rotary_neox_kvcache_prefill_f16": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp],
         "eetq_decode_attention_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp,
                                       vp],
@@ -192,7 +194,7 @@ EXPORTED_SYMBOLS = (
     "eetq_decode_attention_i8kv_f16", "eetq_rope_decode_attention_i8kv_f16", "eetq_rotary_neox_kvcache_prefill_i8_f16",
     "eetq_prefill_attention_i8kv_f16",
     "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
-    "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16",
+    "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16", "eetq_spec_sample_accept_f16",
 )
 
 

@@ -889,6 +889,53 @@ void spec_accept(const Tensor& logits, const Tensor& draft, Tensor& out_tokens, 
                                (int)hist.size(1), stats.data_ptr<int64_t>(), stream_of(logits)));
 }
 
+// spec_accept for sampled generation (extension): every verify row's token is the one sample_handover draws with `params` at its
+// own output column (greedy at temperature 0); a draft token is accepted iff it IS that token; rows finished by `done` (int32 [B])
+// or by an EOS token of this step hand on the pad token and never object.  `uniforms`: float32 [B, k + 1] instead of the kernel's
+// Philox stream; `workspace`: int64 [B * (k + 1)], allocated here when absent (eager use only) (eetq_spec_sample_accept_f16)
+void spec_sample_accept(const Tensor& logits, const Tensor& draft, Tensor& out_tokens, Tensor& column, Tensor& next_token,
+                        Tensor& position, const Tensor& limit, Tensor& hist, Tensor& stats, const Tensor& params, const OptTensor& done,
+                        const OptTensor& uniforms, const OptTensor& workspace)
+{
+    const char* name = "spec_sample_accept: ";
+    TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kHalf && logits.dim() == 3 && logits.stride(2) == 1, name,
+                "logits must be a float16 CUDA tensor [B, k + 1, V] with dense rows");
+    const int64_t B = logits.size(0), T = logits.size(1), V = logits.size(2);
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&draft, &out_tokens, &column, &next_token, &position, &limit, &hist, &stats})
+        TORCH_CHECK(t->scalar_type() == at::kLong && t->device() == logits.device(), name, "int64 tensors on the logits' device expected");
+    if (workspace)
+        TORCH_CHECK(workspace->scalar_type() == at::kLong && workspace->device() == logits.device(), name,
+                    "int64 tensors on the logits' device expected");
+    TORCH_CHECK(T >= 2 && T <= 16 && B > 0 && V > 0 && draft.dim() == 2 && draft.size(0) == B && draft.size(1) == T - 1 &&
+                    draft.stride(1) == 1 && out_tokens.dim() == 2 && out_tokens.size(0) == B && out_tokens.stride(1) == 1 &&
+                    hist.dim() == 2 && hist.size(0) == B && hist.stride(1) == 1 && next_token.numel() == B &&
+                    (next_token.dim() == 1 || (next_token.dim() == 2 && next_token.size(1) == 1)) && column.numel() == 1 &&
+                    position.numel() == 1 && limit.numel() == 1 && stats.numel() == 2 && stats.is_contiguous(),
+                name, "shape mismatch");
+    TORCH_CHECK(params.scalar_type() == at::kInt && params.numel() == 8 && params.is_contiguous() && params.device() == logits.device(),
+                name, "params must be a contiguous int32[8] tensor on the logits' device (sampling_params)");
+    if (done)
+        TORCH_CHECK(done->scalar_type() == at::kInt && done->numel() == B && done->is_contiguous() && done->device() == logits.device(),
+                    name, "done must be a contiguous int32 [B] tensor on the logits' device");
+    if (uniforms)
+        TORCH_CHECK(uniforms->scalar_type() == at::kFloat && uniforms->dim() == 2 && uniforms->size(0) == B && uniforms->size(1) == T &&
+                        uniforms->stride(1) == 1 && uniforms->device() == logits.device(),
+                    name, "uniforms must be a float32 [B, k + 1] tensor with dense rows on the logits' device");
+    if (workspace)
+        TORCH_CHECK(workspace->numel() >= B * T && workspace->is_contiguous(), name,
+                    "workspace must be a contiguous int64 tensor of at least B * (k + 1) elements");
+    c10::DeviceGuard guard(logits.device());
+    const Tensor ws = workspace ? *workspace : at::empty({B * T}, logits.options().dtype(at::kLong));
+    check(eetq_spec_sample_accept_f16(logits.data_ptr(), (long)(B == 1 ? T * V : logits.stride(0)), (long)logits.stride(1), (int)V, (int)B,
+                                      (int)(T - 1), draft.data_ptr<int64_t>(), (long)draft.stride(0), out_tokens.data_ptr<int64_t>(),
+                                      (long)out_tokens.stride(0), (int)out_tokens.size(1), column.data_ptr<int64_t>(),
+                                      position.data_ptr<int64_t>(), limit.data_ptr<int64_t>(), next_token.data_ptr<int64_t>(),
+                                      (long)(B == 1 ? 1 : next_token.stride(0)), hist.data_ptr<int64_t>(), (long)hist.stride(0),
+                                      (int)hist.size(1), stats.data_ptr<int64_t>(), params.data_ptr(),
+                                      done ? done->data_ptr<int32_t>() : nullptr, uniforms ? uniforms->data_ptr<float>() : nullptr,
+                                      (long)(!uniforms || B == 1 ? T : uniforms->stride(0)), ws.data_ptr<int64_t>(), stream_of(logits)));
+}
+
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
                         int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
@@ -2010,6 +2057,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("spec_accept", &spec_accept, "verify + accept + token hand-over of a speculative decode step", py::arg("logits"),
           py::arg("draft"), py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"), py::arg("limit"),
           py::arg("hist"), py::arg("stats"));
+    m.def("spec_sample_accept", &spec_sample_accept, "verify + accept + token hand-over of a speculative decode step, sampled",
+          py::arg("logits"), py::arg("draft"), py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"),
+          py::arg("limit"), py::arg("hist"), py::arg("stats"), py::arg("params"), py::arg("done") = py::none(),
+          py::arg("uniforms") = py::none(), py::arg("workspace") = py::none());
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,

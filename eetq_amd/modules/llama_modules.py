@@ -305,6 +305,11 @@ class _EETAttentionBase(nn.Module):
 
     def _step_tickets(self, batch, device):
         if self._tickets is None or self._tickets.numel() < batch * self.num_heads + 1 or self._tickets.device != device:
+            if self._tickets is not None:
+                # a captured graph (a GraphDecoder of a smaller batch on this model) may hold the buffer's address and holds no
+                # reference: freed, the block is handed to another tensor, the counters stop being zero between launches, and
+                # no workgroup of a replayed step finds itself last -- the cache counter is never advanced
+                self.__dict__.setdefault("_retired_tickets", []).append(self._tickets)
             self._tickets = torch.zeros(batch * self.num_heads + 1, dtype=torch.int32, device=device)
         return self._tickets
 

@@ -45,6 +45,7 @@ if _C is not None:
     sample_handover = _C.sample_handover
     ngram_draft = _C.ngram_draft
     spec_accept = _C.spec_accept
+    spec_sample_accept = _C.spec_sample_accept
     decode_attention = _C.decode_attention
     rope_decode_attention = _C.rope_decode_attention
     decode_attention_i8kv = _C.decode_attention_i8kv
@@ -80,7 +81,7 @@ else:
                              w4_a16_gemm_t, w4_a16_gemm_tiled, w4_a16_gemm_tiled_supported, w8_a16_gemv_grouped, w8_a16_moe, w8_a16_moe_backward, w8_a16_moe_train, w4_a16_moe_backward, w4_a16_moe_train, moe_router,
                              w8_a16_moe_block, w4_a16_moe_block, moe_router_sigmoid, w8_a16_moe_block_sigmoid,
                              w4_a16_moe_block_sigmoid, sample_handover, decode_attention_i8kv, rope_decode_attention_i8kv,
-                             rotary_embedding_neox_kvcache_prefill_i8, ngram_draft, spec_accept)
+                             rotary_embedding_neox_kvcache_prefill_i8, ngram_draft, spec_accept, spec_sample_accept)
     llama_decode_layer = None
     prefill_attention = None
     prefill_attention_supported = None
@@ -89,7 +90,7 @@ else:
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
-           "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "sampling_params", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv",
+           "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "spec_sample_accept", "sampling_params", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv",
            "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]

@@ -26,7 +26,7 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported",
-           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
+           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "spec_sample_accept", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
@@ -1214,6 +1214,53 @@ def spec_accept(logits, draft, out_tokens, column, next_token, position, limit, 
                                               out_tokens.shape[1], _ptr(column), _ptr(position), _ptr(limit), _ptr(next_token),
                                               1 if B == 1 else next_token.stride(0), _ptr(hist), hist.stride(0), hist.shape[1],
                                               _ptr(stats), _stream_ptr()))
+    return None
+
+
+@_eager_only
+def spec_sample_accept(logits, draft, out_tokens, column, next_token, position, limit, hist, stats, params, done=None, uniforms=None,
+                       workspace=None):
+    """``spec_accept`` for sampled generation, in one launch: the token of every verify row ``logits[b, t]`` is the one
+    ``sample_handover`` draws with ``params`` at column ``column + t`` for row ``b`` (greedy at temperature 0), a draft token is
+    accepted iff it IS that token, and a row that is finished (``done`` int32 [B], or an EOS token in this step) hands on the pad
+    token and never objects; ``done`` comes out as of the last position handed over.  ``uniforms``: float32 [B, k + 1] random
+    numbers instead of the kernel's Philox stream.  ``workspace``: int64 [B * (k + 1)], contents irrelevant; ``None`` allocates one
+    (eager use only: a captured graph needs a static tensor).  (eetq_spec_sample_accept_f16)"""
+    name = "spec_sample_accept: "
+    if not logits.is_cuda or logits.dtype != torch.float16 or logits.dim() != 3 or logits.stride(2) != 1:
+        raise RuntimeError(name + "logits must be a float16 CUDA tensor [B, k + 1, V] with dense rows")
+    B, T, V = logits.shape
+    for t in (draft, out_tokens, column, next_token, position, limit, hist, stats) + (() if workspace is None else (workspace,)):
+        if t.dtype != torch.int64 or t.device != logits.device:
+            raise RuntimeError(name + "int64 tensors on the logits' device expected")
+    if (not 2 <= T <= 16 or B <= 0 or V <= 0 or draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] != T - 1
+            or draft.stride(1) != 1 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or out_tokens.stride(1) != 1
+            or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1 or next_token.numel() != B
+            or not (next_token.dim() == 1 or (next_token.dim() == 2 and next_token.shape[1] == 1)) or column.numel() != 1
+            or position.numel() != 1 or limit.numel() != 1 or stats.numel() != 2 or not stats.is_contiguous()):
+        raise RuntimeError(name + "shape mismatch")
+    if params.dtype != torch.int32 or params.numel() != 8 or not params.is_contiguous() or params.device != logits.device:
+        raise RuntimeError(name + "params must be a contiguous int32[8] tensor on the logits' device (sampling_params)")
+    if done is not None and (done.dtype != torch.int32 or done.numel() != B or not done.is_contiguous()
+                             or done.device != logits.device):
+        raise RuntimeError(name + "done must be a contiguous int32 [B] tensor on the logits' device")
+    if uniforms is not None and (uniforms.dtype != torch.float32 or uniforms.dim() != 2 or tuple(uniforms.shape) != (B, T)
+                                 or uniforms.stride(1) != 1 or uniforms.device != logits.device):
+        raise RuntimeError(name + "uniforms must be a float32 [B, k + 1] tensor with dense rows on the logits' device")
+    if workspace is None:
+        workspace = torch.empty(B * T, dtype=torch.int64, device=logits.device)
+    elif workspace.numel() < B * T or not workspace.is_contiguous():
+        raise RuntimeError(name + "workspace must be a contiguous int64 tensor of at least B * (k + 1) elements")
+    with torch.cuda.device(logits.device):
+        check(_lib.lib().eetq_spec_sample_accept_f16(_ptr(logits), T * V if B == 1 else logits.stride(0), logits.stride(1), V, B, T - 1,
+                                                     _ptr(draft), draft.stride(0), _ptr(out_tokens), out_tokens.stride(0),
+                                                     out_tokens.shape[1], _ptr(column), _ptr(position), _ptr(limit),
+                                                     _ptr(next_token), 1 if B == 1 else next_token.stride(0), _ptr(hist),
+                                                     hist.stride(0), hist.shape[1], _ptr(stats), _ptr(params),
+                                                     _ptr(done) if done is not None else None,
+                                                     _ptr(uniforms) if uniforms is not None else None,
+                                                     T if uniforms is None or B == 1 else uniforms.stride(0), _ptr(workspace),
+                                                     _stream_ptr()))
     return None
 
 

@@ -40,7 +40,7 @@ def left_pad_starts(mask):
 
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
-                 ragged=False, speculative=0, ngram=3, draft=None):
+                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -79,12 +79,21 @@ class GraphDecoder:
         computes a token's logits with the prompt kernels, a plain step with the decode kernels.  The step is its own captured
         graph; the plain graphs are captured too and serve ``generate(speculate=False)``.  It needs what ``ragged`` needs --
         ``lean``, a fully accelerated model, head size 64 or 128, ``kv_bits=16`` -- and the MFMA prompt kernel; ``ragged``,
-        ``sampling`` and ``kv_bits=8`` raise ``ValueError``.  ``generate`` then needs ``k`` spare cache rows.
+        ``sampling`` (without ``spec_sampling``, below) and ``kv_bits=8`` raise ``ValueError``.  ``generate`` then needs ``k`` spare cache rows.
         ``ngram`` (1 .. 8): the longest n-gram ``ops.ngram_draft`` looks up in the sequence's own history (``s_hist``).
         ``draft``: a callable ``draft(decoder) -> [batch, k]`` int64 tokens on the device (valid vocabulary ids) instead of the
         lookup: the hook for a draft model and for tests.  Under capture its launches are what the graph holds: it is called
         while capturing, never per step, so it must read and write static tensors only (``s_hist``, ``s_pos``, ``s_tok`` ...)
-        and read nothing on the host."""
+        and read nothing on the host.  It stays a POINT-MASS draft: tokens, not distributions.
+        ``spec_sampling`` (default ``False``: nothing changes): the opt-in for ``speculative=k`` together with ``sampling=True``
+        (DESIGN.md 4.17); it needs both.  The verify step then hands over through ``ops.spec_sample_accept`` on the static
+        parameter block, the EOS flags and a static workspace: every verify row's token is drawn as ``ops.sample_handover`` draws
+        it at that token's own output column, a draft token is accepted iff it IS the drawn token -- exact speculative sampling
+        for a point-mass draft -- and a finished row hands on the pad token and never ends a step.  ``generate`` takes the
+        sampling and EOS arguments of a ``sampling=True`` decoder.  For one seed the speculative and the plain sampled decoder
+        compute the SAME function of the logits (token c of row b from its prefix's logits and Philox(seed; c, b)): their outputs
+        differ only where the prompt kernels of a verify pass and the decode kernels of a plain step round a logit differently.
+        ``generate(speculate=False)`` replays the plain sampling graphs."""
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
         if kv8_append and kv_bits != 8:
@@ -95,7 +104,12 @@ class GraphDecoder:
         self.sampling = bool(sampling)
         self.model = model
         self.ragged = bool(ragged)
-        self.speculative = self._check_speculative(speculative, ngram, draft, max_len)
+        if not isinstance(spec_sampling, bool):
+            raise ValueError("GraphDecoder: spec_sampling must be True or False, got %r" % (spec_sampling,))
+        if spec_sampling and not (self.sampling and speculative):
+            raise ValueError("GraphDecoder: spec_sampling=True is the opt-in for speculative=k together with sampling=True and "
+                             "needs both, got speculative=%r, sampling=%r" % (speculative, sampling))
+        self.speculative = self._check_speculative(speculative, ngram, draft, max_len, spec_sampling)
         self.ngram = int(ngram)
         self._draft_fn = draft
         if self.ragged:
@@ -155,6 +169,9 @@ class GraphDecoder:
             self.s_limit = torch.zeros(1, dtype=torch.long, device=dev)
             self.s_stats = torch.zeros(2, dtype=torch.long, device=dev)
             self._spec_offsets = torch.arange(k + 1, dtype=torch.long, device=dev)
+            if spec_sampling:   # the verify rows' tokens between their workgroups and the one that hands over
+                self.spec_sampling = True
+                self.s_spec_ws = torch.zeros(self.batch * (k + 1), dtype=torch.long, device=dev)
         # the prompt pass needs the LAST position's logits only (the stock forward projects all of them onto the vocabulary)
         params = inspect.signature(model.forward).parameters
         self._last_logits_only = {"logits_to_keep": 1} if "logits_to_keep" in params else {}
@@ -192,7 +209,7 @@ class GraphDecoder:
                 for _ in range(self.steps_per_graph):
                     self._advance()
 
-    def _check_speculative(self, speculative, ngram, draft, max_len):
+    def _check_speculative(self, speculative, ngram, draft, max_len, spec_sampling=False):
         """The checked ``speculative`` (0: off).  Every refusal says which setting and why."""
         if isinstance(speculative, bool) or not isinstance(speculative, int) or not 0 <= speculative <= 15:
             raise ValueError("GraphDecoder: speculative must be 0 (off) or the draft length, 1 .. 15, got %r" % (speculative,))
@@ -204,9 +221,10 @@ class GraphDecoder:
             raise ValueError("GraphDecoder: ngram must lie in 1 .. 8, got %r" % (ngram,))
         if draft is not None and not callable(draft):
             raise ValueError("GraphDecoder: draft must be a callable draft(decoder) -> [batch, k] int64 tokens on the device")
-        if self.sampling:
+        if self.sampling and not spec_sampling:
             raise ValueError("GraphDecoder: speculative=%d does greedy verification only: a draft token is accepted when it IS the "
-                             "argmax, which says nothing about a sampled token (sampling=True)" % speculative)
+                             "argmax, which says nothing about a sampled token (sampling=True); spec_sampling=True opts in to the "
+                             "sampled verify step, which accepts a draft token when it IS the drawn token" % speculative)
         if self.ragged:
             raise ValueError("GraphDecoder: speculative=%d advances all rows by one shared cache counter and one position; "
                              "ragged=True steps every row from its own first key" % speculative)
@@ -348,8 +366,12 @@ class GraphDecoder:
         lg = self.model.lm_head(base.norm(h))
         if not (lg.is_cuda and lg.dtype == torch.float16):
             raise ValueError("GraphDecoder: speculative decoding needs float16 logits on the GPU (got %s on %s)" % (lg.dtype, lg.device))
-        ops.spec_accept(lg if lg.stride(-1) == 1 else lg.contiguous(), self.s_draft, self.out_buf, self.s_idx, self.s_tok, self.s_pos,
-                        self.s_limit, self.s_hist, self.s_stats)
+        if getattr(self, "spec_sampling", False):
+            ops.spec_sample_accept(lg if lg.stride(-1) == 1 else lg.contiguous(), self.s_draft, self.out_buf, self.s_idx, self.s_tok,
+                                   self.s_pos, self.s_limit, self.s_hist, self.s_stats, self.params, self.done, None, self.s_spec_ws)
+        else:
+            ops.spec_accept(lg if lg.stride(-1) == 1 else lg.contiguous(), self.s_draft, self.out_buf, self.s_idx, self.s_tok, self.s_pos,
+                            self.s_limit, self.s_hist, self.s_stats)
         # the rollback: the blocks advanced their counters by k + 1; rows at or beyond the position were rejected (or hold the
         # new pending token's predecessors' drafts) and are never read once the counter says so -- one launch for all layers
         counters = [layer.cumulative_length for layer in self.cache.layers]

@@ -79,7 +79,7 @@ enum { EETQ_ACT_IDENTITY = 0, EETQ_ACT_RELU = 1, EETQ_ACT_GELU = 2, EETQ_ACT_SIL
 /* Revision history: 1 = round 1-2; 2 = eetq_quantize_i8_ws (sized workspace), eetq_release_stream_workspace, eetq_w4a16_gemm_ex;
  * 3 = eetq_diag_auto_path, EETQ_PATH_SPLITK accepts M <= 1024 (row groups); 4 = eetq_diag_splitk_plan; 5 =
  * eetq_rotary_neox_kvcache_prefill_f16, eetq_greedy_handover_f16, eetq_w8a16_gemm_glu8 at M > 16; 6 = eetq_prefill_attention_f16
- * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count, eetq_diag_tile_plan, eetq_spec_ngram_draft_i64, eetq_spec_accept_f16).  Revisions only ADD entry points: a caller built against an older header keeps working. */
+ * (+ _supported); 7 = eetq_w8a16_gemm_t (and, added later within 7, eetq_sample_handover_f16, eetq_w4a16_gemm_t, eetq_w4a16_moe_gemm_t, the *_bounded rotary entries that carry the cos|sin table's row count, eetq_diag_tile_plan, eetq_spec_ngram_draft_i64, eetq_spec_accept_f16, eetq_spec_sample_accept_f16).  Revisions only ADD entry points: a caller built against an older header keeps working. */
 #define EETQ_AMD_ABI_VERSION 7
 int eetq_abi_version(void);   /* EETQ_AMD_ABI_VERSION of the loaded library */
 int eetq_quantize_i8_ws(const void* w, int w_dtype, size_t K, size_t N, int8_t* q_raw, int8_t* q_packed,
@@ -577,6 +577,41 @@ int eetq_spec_accept_f16(const void* logits, long stride_b, long stride_t, int v
                          long draft_stride, int64_t* out_tokens, long out_stride, int out_cols, int64_t* column, int64_t* position,
                          const int64_t* limit, int64_t* next_token, long next_stride, int64_t* hist, long hist_stride,
                          int hist_cols, int64_t* stats, void* stream);
+
+/* Speculative decoding for SAMPLED generation (extension, added within ABI 7; what transformers' generate does
+ * with prompt_lookup_num_tokens and do_sample=True): eetq_spec_accept_f16 with every token drawn as eetq_sample_handover_f16
+ * draws it.  A draft token is a point mass, so exact speculative sampling is: draw x from the target distribution, accept iff
+ * x == draft, hand x over either way.  The first 20 arguments are those of eetq_spec_accept_f16, in its order and meaning; then
+ *   params  : the 32-byte DEVICE block of eetq_sample_handover_f16, 8-byte aligned.
+ *   done    : DEVICE int32[batch] or NULL, the rows' EOS flags.
+ *   uniforms: DEVICE float [batch][k + 1] (uniforms_stride elements apart) or NULL: the random numbers, instead of the kernel's own.
+ *   workspace: DEVICE int64[batch * (k + 1)], 8-byte aligned; contents irrelevant at entry, undefined afterwards.
+ * With col = *column, pos = *position, want = clamp(*limit - col, 0, k + 1):
+ * 1. Draw.  For every b and t < want, x[b][t] is the token eetq_sample_handover_f16 produces for the row logits[b][t] with the
+ *    same params at column col + t for row b: the greedy rule when temperature is <= 0 or NaN; otherwise u from Philox counter
+ *    (lo(col + t), hi(col + t), b, 0) keyed by the seed, or uniforms[b][t] clamped as that entry clamps it; the same NaN, +-inf,
+ *    tie, top-k and top-p rules.  Positions >= want are not read.
+ * 2. Walk t = 0 .. want - 1 with fin_b = (done[b] != 0) at entry (0 where done is NULL): y[b][t] = pad_token if fin_b, else
+ *    x[b][t]; if eos_token >= 0 and y[b][t] == eos_token, fin_b becomes 1.  Row b OBJECTS at t iff t < k, it is not fin_b after this
+ *    position, and draft[b][t] != y[b][t] (a finished row never objects).  adv = t + 1 at the first t where any row objects, else
+ *    want.
+ * 3. Hand-over.  y[b][j], j < adv, goes to out_tokens[b][col + j] and hist[b][pos + 1 + j] (columns outside the arrays skipped),
+ *    y[b][adv - 1] to next_token[b * next_stride]; *position += adv, *column += adv, stats += (1, adv); done[b] = fin_b as of
+ *    position adv - 1 (an EOS drawn at a position that was not handed over finishes nothing).  adv == 0 moves stats[0] only.
+ *    Nothing else is written, except workspace.
+ * So the token at output column c of row b is the same function of its prefix's logits and (seed, c, b) as in a decoder that calls
+ * eetq_sample_handover_f16 once per column; a position's random number decides something only once every earlier position of
+ * the step is confirmed, so using it again after a rollback biases nothing.
+ * One workgroup per (b, t), all at once; each publishes its token to workspace and takes a ticket, and the one that arrives last
+ * walks and hands over -- nobody waits.  The tickets live in bits 40.. of *position for the length of the launch:
+ * -2^39 <= *position < 2^39, nothing else may touch *position meanwhile, and no state is kept between launches.
+ * EETQ_ERR_INVALID (nothing launched): every refusal of eetq_spec_accept_f16; a null params or workspace; params or workspace not
+ * 8-byte aligned; uniforms given with uniforms_stride < k + 1; batch * (k + 1) >= 2^24. */
+int eetq_spec_sample_accept_f16(const void* logits, long stride_b, long stride_t, int vocab, int batch, int k, const int64_t* draft,
+                                long draft_stride, int64_t* out_tokens, long out_stride, int out_cols, int64_t* column,
+                                int64_t* position, const int64_t* limit, int64_t* next_token, long next_stride, int64_t* hist,
+                                long hist_stride, int hist_cols, int64_t* stats, const void* params, int32_t* done,
+                                const float* uniforms, long uniforms_stride, int64_t* workspace, void* stream);
 
 /* Single-query (decode) attention over a KV cache; extension used by the EET attention blocks' decode step (the
  * reference delegates the attention product to flash-attn, python/eetq/modules/llama_modules.py:131-143).
