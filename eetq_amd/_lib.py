@@ -126,6 +126,9 @@ def _declare(L):
         "eetq_prefill_attention_splits": [i32, i32, i32, i32],
         "eetq_prefill_attention_max_splits": [],
         "eetq_decode_attention_splits": [i32, i32, i32],
+        "eetq_decode_attention_rows_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp],
+        "eetq_decode_attention_rows_splits": [i32, i32, i32, i32, i32],
+        "eetq_decode_attention_rows_max_splits": [],
         "eetq_prof_begin": [i32],
         "eetq_prof_end": [vp, i32, vp],
         "eetq_diag_stream_read": [vp, sz, vp, vp],
@@ -164,6 +167,8 @@ def _declare(L):
     L.eetq_quantize_workspace_floats.argtypes = [sz, sz]
     L.eetq_prefill_attention_workspace_floats.restype = ctypes.c_size_t
     L.eetq_prefill_attention_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
+    L.eetq_decode_attention_rows_workspace_floats.restype = ctypes.c_size_t
+    L.eetq_decode_attention_rows_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.eetq_release_workspace.restype = i32
     L.eetq_release_workspace.argtypes = [ctypes.POINTER(ctypes.c_size_t)]
     L.eetq_last_error.restype = ctypes.c_char_p
@@ -195,6 +200,8 @@ EXPORTED_SYMBOLS = (
     "eetq_prefill_attention_i8kv_f16",
     "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
     "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16", "eetq_spec_sample_accept_f16",
+    "eetq_decode_attention_rows_f16", "eetq_decode_attention_rows_splits", "eetq_decode_attention_rows_max_splits",
+    "eetq_decode_attention_rows_workspace_floats",
 )
 
 

@@ -926,6 +926,27 @@ size_t eetq_prefill_attention_workspace_floats(int batch, int heads, int q_token
     return prefill_attention_workspace_floats(batch, heads, q_tokens, head_dim, splits);
 }
 
+int eetq_decode_attention_rows_f16(const void* q, const void* k_cache, const void* v_cache, void* out, float* workspace, int batch,
+                                   int heads, int kv_heads, int rows, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                   int splits, float scaling, const long* strides, void* stream)
+{
+    return launch_decode_attention_rows(static_cast<const f16*>(q), static_cast<const f16*>(k_cache), static_cast<const f16*>(v_cache),
+                                        static_cast<f16*>(out), workspace, batch, heads, kv_heads, rows, max_keys, head_dim, kv_len,
+                                        kv_len_bias, splits, scaling, strides, static_cast<hipStream_t>(stream));
+}
+
+int eetq_decode_attention_rows_splits(int batch, int heads, int kv_heads, int rows, int max_keys)
+{
+    return decode_attention_rows_splits(batch, heads, kv_heads, rows, max_keys);
+}
+
+int eetq_decode_attention_rows_max_splits(void) { return decode_attention_rows_max_splits(); }
+
+size_t eetq_decode_attention_rows_workspace_floats(int batch, int heads, int rows, int head_dim, int splits)
+{
+    return decode_attention_rows_workspace_floats(batch, heads, rows, head_dim, splits);
+}
+
 int eetq_decode_dropped_steps(unsigned long long* count, int reset)
 {
     EETQ_REQUIRE(count, "null pointer");

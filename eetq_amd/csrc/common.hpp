@@ -340,6 +340,13 @@ int    launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v,
 int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
 int    prefill_attention_max_splits();
 size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
+// 1 .. 16 query rows behind a long cache, split-KV on MFMA (attn_decode_rows.hip); st as launch_prefill_attention's
+int    launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R, int max_keys,
+                                    int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
+                                    hipStream_t stream);
+int    decode_attention_rows_splits(int B, int H, int Hkv, int R, int max_keys);
+int    decode_attention_rows_max_splits();
+size_t decode_attention_rows_workspace_floats(int B, int H, int R, int D, int splits);
 int launch_attn_decode(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
                        int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
                        int64_t* advance, hipStream_t stream);

@@ -319,6 +319,56 @@ Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& v
     return out;
 }
 
+// 1 .. 16 query rows behind a long cache, split-KV on the matrix cores (eetq_decode_attention_rows_f16): query [B, R, H, D] (any row /
+// head strides, D dense), cache views [B, Hkv, rows >= keys, D]; returns [B, R, H, D] contiguous.  The tensor checks and the device
+// guard are prefill_attention's; splits: None = the library's rule, workspace: None = allocated here (capturable, nothing persistent)
+int64_t decode_attention_rows_splits(int64_t batch, int64_t heads, int64_t kv_heads, int64_t rows, int64_t max_keys)
+{
+    return eetq_decode_attention_rows_splits((int)batch, (int)heads, (int)kv_heads, (int)rows, (int)max_keys);
+}
+
+Tensor decode_attention_rows(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
+                             const OptTensor& kv_len, int64_t kv_len_bias, std::optional<int64_t> splits_in, const OptTensor& workspace)
+{
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
+                    "decode_attention_rows: float16 CUDA tensors [B, R, H, D] / [B, Hkv, S, D] with a dense last dimension expected");
+    const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
+    TORCH_CHECK(key.size(0) == B && key.size(3) == D && value.sizes() == key.sizes() && Hkv > 0 && H % Hkv == 0 && keys > 0 &&
+                    keys <= key.size(2) && B > 0,
+                "decode_attention_rows: shape mismatch");
+    TORCH_CHECK(R >= 1 && R <= 16, "decode_attention_rows: 1 .. 16 query rows per batch row (got ", R, ")");
+    TORCH_CHECK(D == 64 || D == 128, "decode_attention_rows: unsupported head_dim");
+    TORCH_CHECK(kv_len || kv_len_bias == 0, "decode_attention_rows: kv_len_bias needs kv_len");
+    if (kv_len)
+        TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(),
+                    "decode_attention_rows: kv_len must be a one-element int64 tensor on the query's device");
+    const double  sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
+    const int64_t splits = splits_in ? *splits_in : decode_attention_rows_splits(B, H, Hkv, R, keys);
+    TORCH_CHECK(splits >= 1 && splits <= eetq_decode_attention_rows_max_splits(), "decode_attention_rows: splits must lie in 1 .. ",
+                eetq_decode_attention_rows_max_splits());
+    const int64_t need = (int64_t)eetq_decode_attention_rows_workspace_floats((int)B, (int)H, (int)R, (int)D, (int)splits);
+    Tensor        ws;
+    if (workspace) {
+        TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
+                        workspace->numel() >= need,
+                    "decode_attention_rows: workspace must be a contiguous float32 tensor of at least ", need,
+                    " elements on the query's device");
+        ws = *workspace;
+    } else {
+        ws = torch::empty({need}, query.options().dtype(at::kFloat));
+    }
+    Tensor     out = torch::empty({B, R, H, D}, query.options());
+    const long st[12] = {(long)query.stride(0), (long)query.stride(1), (long)query.stride(2), (long)key.stride(0), (long)key.stride(1),
+                         (long)key.stride(2),   (long)value.stride(0), (long)value.stride(1), (long)value.stride(2),
+                         (long)out.stride(0),   (long)out.stride(1),   (long)out.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_decode_attention_rows_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), ws.data_ptr<float>(), (int)B,
+                                         (int)H, (int)Hkv, (int)R, (int)keys, (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr,
+                                         (int)kv_len_bias, (int)splits, (float)sc, st, stream_of(query)));
+    return out;
+}
+
 Tensor silu_mul(const Tensor& gate_up, bool glu8 = false);
 
 void check_epilogue(const Tensor& input, const OptTensor& bias, const OptTensor& residual, int64_t m, int64_t n)
@@ -2092,6 +2142,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
           "prefill_attention behind an int8 KV cache: a prompt's query rows [B, T, H, D] over the dequantised first rows of the cache");
+    m.def("decode_attention_rows", &decode_attention_rows, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
+          py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(),
+          py::arg("workspace") = py::none(),
+          "1 .. 16 query rows [B, R, H, D], the last rows of the first `keys` rows of a KV cache [B, Hkv, S, D], attending it causally "
+          "(split-KV, MFMA)");
+    m.def("decode_attention_rows_splits", &decode_attention_rows_splits, py::arg("batch"), py::arg("heads"), py::arg("kv_heads"),
+          py::arg("rows"), py::arg("max_keys"), "the chunk count decode_attention_rows uses with splits=None");
     m.def("prefill_attention_supported", &prefill_attention_supported, py::arg("head_dim"));
     m.def("prefill_attention_splits", &prefill_attention_splits, py::arg("batch"), py::arg("heads"), py::arg("q_tokens"), py::arg("max_keys"),
           "the split count prefill_attention uses with splits=None (1 = unsplit)");

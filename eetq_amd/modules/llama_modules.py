@@ -42,7 +42,7 @@ def fresh_static_prefill():
 
 
 @contextlib.contextmanager
-def appended_static_prefill(int8_rows=False):
+def appended_static_prefill(int8_rows=False, few_rows=False):
     """The caller's promise for the forwards run inside (per thread): the prompt is unpadded and the static cache's rows
     0 .. counter - 1 are this sequence's real tokens, so a prompt appended behind them attends exactly the rows below the
     advanced counter, causally among its own.  The attention blocks write the rows as they do without the promise (behind the
@@ -55,14 +55,28 @@ def appended_static_prefill(int8_rows=False):
     acceptance of what an appended prompt means on an INT8 cache (``Int8StaticCache``): the prompt's rows are written first
     (rotated, quantised, behind the device counter) and the prompt then attends the DEQUANTISED rows 0 .. counter - 1 through
     ``ops.prefill_attention_i8kv`` -- its own keys and values as their quantised selves, as a decode step sees them.  Without it
-    a prompt appended behind int8 rows raises; on an fp16 cache the flag changes nothing."""
+    a prompt appended behind int8 rows raises; on an fp16 cache the flag changes nothing.
+
+    ``few_rows=True`` (per thread, restored on exit) promises that the appended pieces are SHORT: a piece of 2 .. 16 rows then goes
+    through ``ops.decode_attention_rows(..., kv_len=counter)`` -- the split-KV kernel for a few rows behind a long cache, the heads
+    of a kv head side by side, the cache streamed once by the whole chip -- instead of the prompt kernel's 128-row tiles
+    (``GraphDecoder(spec_attention="rows")`` makes it for its verify steps).  Longer pieces and single tokens go where they go
+    without it.  The kernel reads fp16 rows and knows one shared first key, so the flag together with ``int8_rows`` or under
+    ``padded_static_batch`` raises ``ValueError``."""
+    if few_rows and int8_rows:
+        raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) reads fp16 cache rows only; it cannot be "
+                         "combined with int8_rows")
+    if few_rows and _padded_starts() is not None:
+        raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) knows one shared first key only; it cannot "
+                         "run under padded_static_batch (a per-row first key)")
     prev = (getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False),
-            getattr(_prefill_promise, "int8_rows", False))
+            getattr(_prefill_promise, "int8_rows", False), getattr(_prefill_promise, "few_rows", False))
     _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = True, False, bool(int8_rows)
+    _prefill_promise.few_rows = bool(few_rows)
     try:
         yield
     finally:
-        _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = prev
+        (_prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows, _prefill_promise.few_rows) = prev
 
 
 @contextlib.contextmanager
@@ -81,6 +95,9 @@ def padded_static_batch(starts):
     caller passes ``position_ids`` that count from each row's first real token.  Anything the MFMA prompt kernel or the decode
     kernels cannot run (head size, dtype, an int8 cache, a stock attention path) raises ``ValueError`` instead of attending the
     pads."""
+    if starts is not None and getattr(_prefill_promise, "few_rows", False):
+        raise ValueError("padded_static_batch: appended_static_prefill(few_rows=True) is in force, and ops.decode_attention_rows "
+                         "knows one shared first key only (no per-row first key)")
     prev = getattr(_prefill_promise, "starts", None)
     _prefill_promise.starts = starts
     try:
@@ -375,6 +392,13 @@ class _EETAttentionBase(nn.Module):
             return out.reshape(*input_shape, -1), None
         if cached is not None:
             k, v, counter = cached
+            if (getattr(_prefill_promise, "few_rows", False) and getattr(_prefill_promise, "appended", False)
+                    and not getattr(_prefill_promise, "fresh", False) and 2 <= q.shape[2] <= 16
+                    and ops.decode_attention_rows is not None and not kwargs.get("output_attentions", False) and q.is_cuda
+                    and q.dtype == torch.float16 and self.head_dim in (64, 128) and k.stride(-1) == 1 and v.stride(-1) == 1):
+                # promised short: the few-row split-KV kernel, the counter as its device length (as below)
+                out = ops.decode_attention_rows(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
+                return out.reshape(*input_shape, -1), None
             if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1
                     and not kwargs.get("output_attentions", False) and self.mfma_prefill and ops.prefill_attention is not None
                     and q.is_cuda and q.dtype == torch.float16 and ops.prefill_attention_supported(self.head_dim)

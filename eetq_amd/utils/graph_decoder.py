@@ -40,7 +40,7 @@ def left_pad_starts(mask):
 
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
-                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False):
+                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt"):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -93,7 +93,25 @@ class GraphDecoder:
         sampling and EOS arguments of a ``sampling=True`` decoder.  For one seed the speculative and the plain sampled decoder
         compute the SAME function of the logits (token c of row b from its prefix's logits and Philox(seed; c, b)): their outputs
         differ only where the prompt kernels of a verify pass and the decode kernels of a plain step round a logit differently.
-        ``generate(speculate=False)`` replays the plain sampling graphs."""
+        ``generate(speculate=False)`` replays the plain sampling graphs.
+        ``spec_attention`` (default ``"prompt"``: the verify step as it has always been captured, bit for bit): ``"rows"`` runs the
+        verify step's layers under ``appended_static_prefill(few_rows=True)``, so the attention of its ``k + 1`` rows is
+        ``ops.decode_attention_rows`` -- the split-KV MFMA kernel for a few rows behind a long cache -- instead of
+        the prompt kernel, under greedy and under ``spec_sampling=True`` verification alike.  It needs ``speculative=k`` and the
+        compiled operator module; any other value raises ``ValueError``.  ``prefill`` and ``generate(append=True)`` keep the
+        prompt kernel."""
+        if spec_attention not in ("prompt", "rows"):
+            raise ValueError("GraphDecoder: spec_attention must be 'prompt' (the MFMA prompt kernel) or 'rows' (the few-row split-KV "
+                             "kernel), got %r" % (spec_attention,))
+        if spec_attention == "rows":
+            from .. import ops as _ops
+            if not speculative:
+                raise ValueError("GraphDecoder: spec_attention='rows' chooses the attention of the verify step and needs a "
+                                 "speculative decoder (speculative=k)")
+            if _ops.decode_attention_rows is None:
+                raise ValueError("GraphDecoder: spec_attention='rows' needs ops.decode_attention_rows, which lives in the compiled "
+                                 "operator module (this process runs the ctypes boundary)")
+        self.spec_attention = spec_attention
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
         if kv8_append and kv_bits != 8:
@@ -358,7 +376,7 @@ class GraphDecoder:
         ids = torch.cat([self.s_tok, self.s_draft], dim=1)                                    # [B, k + 1]
         pos = (self.s_pos + self._spec_offsets).view(1, k + 1).expand(self.batch, k + 1)      # cache rows = positions
         h = base.embed_tokens(ids)
-        with appended_static_prefill():
+        with appended_static_prefill(few_rows=self.spec_attention == "rows"):
             for layer in base.layers:
                 h = layer(h, attention_mask=None, position_ids=pos, past_key_values=self.cache, use_cache=True)
                 if isinstance(h, tuple):

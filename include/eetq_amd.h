@@ -785,6 +785,46 @@ int    eetq_prefill_attention_splits(int batch, int heads, int q_tokens, int max
 int    eetq_prefill_attention_max_splits(void);
 size_t eetq_prefill_attention_workspace_floats(int batch, int heads, int q_tokens, int head_dim, int splits);
 
+/* FEW-ROW attention behind a long cache (added within ABI revision 7): `rows` = 1 .. 16 query rows per batch row -- the last `rows`
+ * rows a static fp16 KV cache has just been given, rotated (a speculative verify step, a chunked prompt's short last piece) -- attend
+ * the cache causally among themselves, split over the keys, both products on the 16x16x32 matrix-core shape.  Semantics are exactly
+ * those of eetq_prefill_attention_dev_f16:
+ *   keys = clamp(*kv_len + kv_len_bias, 0, max_keys); kv_len NULL means keys = max_keys;
+ *   koff = keys - rows;
+ *   query t attends cache rows j with 0 <= j <= min(keys - 1, koff + t);
+ *   out[b][t][h] = softmax_j(scaling * q[b][t][h] . k[b][h / groups][j]) . v[b][h / groups][j];
+ *   a query with nothing to attend gives zeros (koff + t < 0, and keys = 0);
+ *   rows at or beyond keys are never read (they hold stale drafts or NaN).
+ * fp16 in and out; scores, softmax state and accumulators fp32; the probabilities enter the second product as fp16, carried as 2^12 p.
+ * q: the strided [batch][rows][heads][head_dim] view into the fused QKV output; caches [batch][kv_heads][rows][head_dim] with any
+ * batch / head / row strides, head_dim contiguous.  strides: the twelve of eetq_prefill_attention_f16 in the same order ({q_b, q_row,
+ * q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b, out_row, out_head}, elements), q / k / v strides multiples of 8, out strides
+ * of 4, q / k / v 16-byte aligned, out 8-byte.  head_dim 64 or 128, any heads % kv_heads == 0: the heads / kv_heads * rows (head, query
+ * row) pairs of a kv head are one tile, a K / V row is loaded once per kv head.
+ * CHUNK RULE: with n = ceil(keys / 32) blocks of 32 key rows, chunk i of `splits` owns blocks [floor(i n / splits),
+ * floor((i + 1) n / splits)), i.e. key rows [32 floor(i n / splits), min(keys, 32 floor((i + 1) n / splits))); a chunk may be empty.
+ * Always two launches: one workgroup per (chunk, kv head, batch row) leaves, per (query row, head), the record [m, l, -, -,
+ * o[head_dim]] in `workspace` -- an empty chunk or a row with nothing to attend in it (-inf, 0, zeros), so the workspace's previous
+ * contents never matter -- and a second launch merges a row's records (weights exp2(m_i - max m), one division; a fully masked row
+ * gives zeros).  No atomics, no tickets, no state between launches; deterministic.  Nothing is read on the host: capturable.
+ * workspace: DEVICE, eetq_decode_attention_rows_workspace_floats(batch, heads, rows, head_dim, splits) = batch * heads * rows *
+ * splits * (head_dim + 4) floats, 16-byte aligned, needed at every `splits` (also 1); launches that may run concurrently need
+ * distinct workspaces.
+ * EETQ_ERR_INVALID (nothing launched): null q / k_cache / v_cache / out / strides, rows outside 1 .. 16, max_keys <= 0, splits outside
+ * 1 .. eetq_decode_attention_rows_max_splits() (64), a NULL or misaligned workspace, the stride and alignment rules above, one head's
+ * cache rows spanning 2 GiB or more (checked against max_keys).  EETQ_ERR_UNSUPPORTED: head_dim other than 64 or 128. */
+int    eetq_decode_attention_rows_f16(const void* q, const void* k_cache, const void* v_cache, void* out, float* workspace, int batch,
+                                      int heads, int kv_heads, int rows, int max_keys, int head_dim, const int64_t* kv_len,
+                                      int kv_len_bias, int splits, float scaling, const long* strides, void* stream);
+/* The chunk count the entry is tuned for (pure host function; callers size the workspace with it): with g = batch * kv_heads *
+ * ceil(heads / kv_heads * rows / 64) workgroups per chunk, n = ceil(max_keys / 32) blocks and r = 2 workgroups per compute unit
+ * where heads / kv_heads * rows <= 16 (one sub-tile), else 1: min(r * compute units / g, max(n / 8, min(8, n / 4)), 32), at least 1
+ * (integer divisions) -- the grid fills the chip once, a chunk keeps 4 blocks up to 8 chunks and 8 beyond, never more than 32
+ * chunks.  Tuned from tools/attn_rows_bench.py's table (profiles/attn_rows.txt). */
+int    eetq_decode_attention_rows_splits(int batch, int heads, int kv_heads, int rows, int max_keys);
+int    eetq_decode_attention_rows_max_splits(void);
+size_t eetq_decode_attention_rows_workspace_floats(int batch, int heads, int rows, int head_dim, int splits);
+
 /* eetq_prefill_attention_dev_f16 over an int8 KV cache (the row format above; added within ABI revision 7): a prompt appended behind
  * int8 rows, its own rows already written (rotated, quantised) and the counter advanced, attends the dequantised rows 0 .. keys - 1,
  * causally among its own -- a query token sees its own key and value as their quantised selves, as the one-launch decode step does.

@@ -12,7 +12,9 @@ Per (cache rows, k): microseconds of one replay of the plain one-step graph, of 
 graph at either bound (median of --reps timings of --chain consecutive replays), tokens/s = tokens handed over / time, and the
 break-even: the tokens per verify step at which speculative decoding equals the plain 7-step graph, verify / plain-per-token.
 Writes the table to --out (default profiles/spec_decode.txt).
-usage: python tools/spec_bench.py [--caches 1024,4096] [--ks 2,4,8] [--chain 16] [--reps 7] [--layers 40]"""
+--spec-attention prompt,rows: the verify step's attention (GraphDecoder(spec_attention=...)), one table row per value, "rows" next to
+"prompt" on the same model in the same session (profiles/spec_decode_rows.txt).
+usage: python tools/spec_bench.py [--caches 1024,4096] [--ks 2,4,8] [--chain 16] [--reps 7] [--layers 40] [--spec-attention prompt]"""
 import argparse
 import os
 import statistics
@@ -29,6 +31,7 @@ ap.add_argument("--ks", default="2,4,8")
 ap.add_argument("--chain", type=int, default=16, help="consecutive replays per timing (a multiple of 7 is not needed)")
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--layers", type=int, default=40, help="decoder layers (40 = Llama-2-13B; fewer for a quick look)")
+ap.add_argument("--spec-attention", default="prompt", help="comma-separated: prompt (the MFMA prompt kernel), rows (the few-row kernel)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spec_decode.txt"))
 args = ap.parse_args()
 DEV = "cuda:0"
@@ -84,14 +87,14 @@ def main():
     lines = ["# tools/spec_bench.py: Llama-2-13B shapes (%d layers, random init, W8A16), batch 1, %s" % (args.layers, torch.cuda.get_device_name(0)),
              "# us per graph replay (median of %d timings of %d consecutive replays); tokens/s = tokens handed over / time" % (args.reps, args.chain),
              "# break-even = verify_us / plain7_us_per_token: tokens per verify step at which the speculative decoder equals the plain one",
-             "%6s %3s %10s %12s %10s %11s %10s %10s %10s %10s" % ("cache", "k", "plain1_us", "plain7_us/t", "verify_us", "verify/pl1", "tok/s_pl7",
-                                                                "tok/s_all", "tok/s_none", "break-even")]
+             "%6s %3s %6s %10s %12s %10s %11s %10s %10s %10s %10s" % ("cache", "k", "attn", "plain1_us", "plain7_us/t", "verify_us", "verify/pl1",
+                                                                    "tok/s_pl7", "tok/s_all", "tok/s_none", "break-even")]
     print("\n".join(lines), flush=True)
     mode = torch.zeros(1, dtype=torch.long, device=DEV)          # 0: the right tokens, 1: wrong ones
 
     for cache in [int(c) for c in args.caches.split(",")]:
         prompt = torch.randint(0, VOCAB, (1, cache - 1), generator=torch.Generator().manual_seed(1)).to(DEV)
-        for k in [int(x) for x in args.ks.split(",")]:
+        for k, attn in [(int(x), a) for x in args.ks.split(",") for a in args.spec_attention.split(",")]:
             def draft(dec):
                 toks, t = [], dec.s_tok
                 for _ in range(dec.speculative):
@@ -102,7 +105,7 @@ def main():
             span = args.chain * max(k + 1, 7) + k + 4              # rows one timing may write behind the prompt
             max_len = cache + span + 8
             with torch.no_grad():
-                dec = GraphDecoder(model, 1, max_len, speculative=k, draft=draft)
+                dec = GraphDecoder(model, 1, max_len, speculative=k, draft=draft, spec_attention=attn)
 
                 dec.generate(prompt, 1)                             # the prompt pass and one token: `cache` rows cached or pending
                 first = dec.s_tok.clone()
@@ -130,8 +133,8 @@ def main():
                 steps, tokens = dec.spec_stats()
                 per_none = tokens / max(steps, 1)
             verify = (v_all + v_none) / 2
-            line = "%6d %3d %10.1f %12.1f %10.1f %11.3f %10.1f %10.1f %10.1f %10.2f" % (
-                cache, k, plain1, plain7, verify, verify / plain1, 1e6 / plain7, 1e6 * per_all / v_all, 1e6 * per_none / v_none, verify / plain7)
+            line = "%6d %3d %6s %10.1f %12.1f %10.1f %11.3f %10.1f %10.1f %10.1f %10.2f" % (
+                cache, k, attn, plain1, plain7, verify, verify / plain1, 1e6 / plain7, 1e6 * per_all / v_all, 1e6 * per_none / v_none, verify / plain7)
             print(line, flush=True)
             lines.append(line)
             note = "#        verify_us / tokens per step as counted on the device: right drafts %.1f / %.2f, wrong drafts %.1f / %.2f" % (
