@@ -16,7 +16,6 @@ namespace eetq {
 // dropped-step counters of the decode kernels (attn_decode.hip, norm_rope.hip)
 int attn_dropped_steps(unsigned* count, bool reset);
 int rope_dropped_steps(unsigned* count, bool reset);
-int attn_i8_dropped_steps(unsigned* count, bool reset);
 
 namespace {
 thread_local std::string g_last_error;
@@ -956,10 +955,7 @@ int eetq_decode_dropped_steps(unsigned long long* count, int reset)
     if (st != EETQ_OK) return st;
     st = rope_dropped_steps(&r, reset != 0);
     if (st != EETQ_OK) return st;
-    unsigned a8 = 0;
-    st = attn_i8_dropped_steps(&a8, reset != 0);
-    if (st != EETQ_OK) return st;
-    *count = (unsigned long long)a + r + a8;
+    *count = (unsigned long long)a + r;
     return EETQ_OK;
 }
 

@@ -1,6 +1,6 @@
 // The pieces of the decode-attention kernels that do not depend on the cache element: geometry, the lane and workgroup
 // merges, the chunk-record merge and its kernel, the in-launch head hand-off, the NeoX rotation of the new token.
-// Included by attn_decode.hip (fp16 rows) and attn_decode_i8.hip (int8 rows); everything is internal to the including file.
+// Included by attn_decode.hip (fp16 and int8 rows) and attn_decode_rows.hip; everything is internal to the including file.
 #pragma once
 #include <type_traits>
 

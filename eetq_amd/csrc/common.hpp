@@ -365,7 +365,7 @@ int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_str
                           long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream, int tokens = 0,
                           int first_row = 0);  // tokens > 0: the prefill form (batch * tokens blocks, rows first_row + t)
 
-// the int8 KV cache (kv_i8.hpp): decode attention over int8 rows (attn_decode_i8.hip; strides as the fp16 launchers' with the cache
+// the int8 KV cache (kv_i8.hpp): decode attention over int8 rows (attn_decode.hip; strides as the fp16 launchers' with the cache
 // strides in bytes, scale_strides {batch, head, row} in fp16 elements) and the quantising prompt / single-token write (norm_rope.hip)
 int launch_attn_decode_i8(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, const f16* mask, f16* out, float* ws,
                           int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* strides,

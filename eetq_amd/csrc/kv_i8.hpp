@@ -3,7 +3,7 @@
 //   amax = max |x_d|                                   (exact)
 //   s    = fp16(fp32(amax) * (1.0f / 127.0f))           one fp32 multiply, round to nearest even
 //   q_d  = clamp(round_half_away(fp32(x_d) / fp32(s)), -127, 127)   IEEE fp32 divide (the Makefile asks for it); s == 0 -> 0
-// bytes are plain two's complement; -128 is never written.  Shared by the writers (norm_rope.hip, attn_decode_i8.hip) so that
+// bytes are plain two's complement; -128 is never written.  Shared by the writers (norm_rope.hip, attn_decode.hip) so that
 // every path to a cache row produces the same bits, and by the reader for the way back.
 #pragma once
 #include "common.hpp"
@@ -47,7 +47,7 @@ __device__ __forceinline__ void kv8_unpack8(const u32x2& w, f16x2 (&h)[4])
     h[3] = as_f16x2(__builtin_amdgcn_perm(x1, c64, 0x00070006u)) - bias;
 }
 
-// the rules every attention entry over an int8 cache shares (attn_decode_i8.hip, attn_prefill.hip): cache strides {k_b, k_h, k_pos,
+// the rules every attention entry over an int8 cache shares (attn_decode.hip, attn_prefill.hip): cache strides {k_b, k_h, k_pos,
 // v_b, v_h, v_pos} in bytes (8-byte loads), scale strides in fp16 elements (one dword per row)
 inline int check_i8_cache(const void* kc, const void* vc, const void* scales, int S, const long* cst, const long* sst)
 {

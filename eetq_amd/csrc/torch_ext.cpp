@@ -10,6 +10,7 @@
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <array>
 #include <cmath>
 #include <optional>
 #include <stdexcept>
@@ -163,6 +164,59 @@ static const int64_t* kv_start_ptr(const char* name, const OptTensor& kv_start, 
                 name, ": kv_start must be a contiguous int64 [B] tensor on the query's device");
     return kv_start->data_ptr<int64_t>();
 }
+// What the four decode-attention operators prepare alike: the slots and their stride, the mask row and its batch stride, the kv_len /
+// advance scalars, the default scaling and chunk count, the output and the workspace, the stride arrays.  name: "operator: "
+struct DecodeAttnPrep {
+    const int64_t *slots = nullptr, *kv_len;
+    int64_t*       advance;
+    int            slot_stride = 0;
+    Tensor         mrow, out, ws;
+    int64_t        m_sb = 0, splits;
+    float          sc;
+
+    DecodeAttnPrep(const char* name, const Tensor& query, int64_t S, const OptTensor* slots_in, const OptTensor& mask,
+                   std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len_in, const OptTensor& advance_in)
+    {
+        const int64_t B = query.size(0), H = query.size(1), D = query.size(2);
+        if (slots_in && *slots_in) {
+            const Tensor& s = **slots_in;
+            TORCH_CHECK(s.scalar_type() == at::kLong && s.device() == query.device() && (s.numel() == 1 || s.numel() == B) &&
+                            s.is_contiguous(),
+                        name, "slots must be contiguous int64 on the device, 1 or B elements");
+            slots       = s.data_ptr<int64_t>();
+            slot_stride = (s.numel() == B && B > 1) ? 1 : 0;
+        }
+        if (mask) {
+            mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
+            TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
+                        name, "mask must be additive float16 with a dense last dimension >= S");
+            TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B, name, "the mask needs one row per batch entry (or a single shared row)");
+            m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
+        }
+        for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len_in, &advance_in})
+            if (*t)
+                TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(), name,
+                            "kv_len / advance must be a one-element int64 tensor on the query's device");
+        kv_len  = kv_len_in ? kv_len_in->data_ptr<int64_t>() : nullptr;
+        advance = advance_in ? advance_in->data_ptr<int64_t>() : nullptr;
+        sc      = (float)(scaling ? *scaling : 1.0 / std::sqrt((double)D));
+        splits  = splits_in ? *splits_in : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
+        out     = torch::empty({B, H, D}, query.options());
+        ws      = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
+    }
+    const void* mask() const { return mrow.defined() ? mrow.data_ptr() : nullptr; }
+    // lead (q_b, q_h of the two-launch entries; q_b, k_b, v_b of the one-launch ones), the caches' six, mask_b, out_b, out_h
+    std::array<long, 12> strides(std::initializer_list<int64_t> lead, const Tensor& kc, const Tensor& vc) const
+    {
+        std::array<long, 12> st{};
+        size_t               n = 0;
+        for (int64_t v : lead) st[n++] = (long)v;
+        for (const Tensor* c : {&kc, &vc})
+            for (int i = 0; i < 3; ++i) st[n++] = (long)c->stride(i);
+        st[n++] = (long)m_sb, st[n++] = (long)out.stride(0), st[n++] = (long)out.stride(1);
+        return st;
+    }
+};
 // eetq_rotary_neox_kvcache_f16 + eetq_decode_attention_f16 as one launch (the decode step of a static cache)
 Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
                              const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& tickets,
@@ -189,58 +243,25 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
     TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.is_contiguous() && tickets.numel() >= B * H + 1 &&
                     tickets.device() == query.device(),
                 "rope_decode_attention: tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device");
-    int slot_stride = 0;
-    if (slots) {
-        const Tensor& s = *slots;
-        TORCH_CHECK(s.scalar_type() == at::kLong && s.device() == query.device() && (s.numel() == 1 || s.numel() == B) &&
-                        s.is_contiguous(),
-                    "rope_decode_attention: slots must be contiguous int64 on the device, 1 or B elements");
-        slot_stride = (s.numel() == B && B > 1) ? 1 : 0;
-    }
-    Tensor  mrow;
-    int64_t m_sb = 0;
-    if (mask) {
-        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
-        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
-                    "rope_decode_attention: mask must be additive float16 with a dense last dimension >= S");
-        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B,
-                    "rope_decode_attention: the mask needs one row per batch entry (or a single shared row)");
-        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
-    }
-    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
-        if (*t)
-            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(),
-                        "rope_decode_attention: kv_len / advance must be a one-element int64 tensor on the query's device");
-    const double sc = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    int64_t      splits = splits_in ? *splits_in
-                                    : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
-    Tensor       out = torch::empty({B, H, D}, query.options());
-    Tensor       ws  = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
-    const long   strides[12] = {(long)query.stride(0),       (long)key.stride(0),         (long)value.stride(0),
-                                (long)key_cache.stride(0),   (long)key_cache.stride(1),   (long)key_cache.stride(2),
-                                (long)value_cache.stride(0), (long)value_cache.stride(1), (long)value_cache.stride(2),
-                                (long)m_sb,                  (long)out.stride(0),         (long)out.stride(1)};
-    const int64_t* starts = kv_start_ptr("rope_decode_attention", kv_start, query, B);
-    c10::DeviceGuard guard(query.device());
+    const DecodeAttnPrep p("rope_decode_attention: ", query, S, &slots, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), key.stride(0), value.stride(0)}, key_cache, value_cache);
+    const int64_t*       starts  = kv_start_ptr("rope_decode_attention", kv_start, query, B);
+    unsigned*            tk      = reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>());
+    c10::DeviceGuard     guard(query.device());
     if (starts) {
         check(eetq_rope_decode_attention_padded_f16(
-            positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(),
-            key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(),
-            value_cache.data_ptr(), mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
-            reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits,
-            (float)sc, strides, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
-            advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-        return out;
+            positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+            cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(),
+            p.out.data_ptr(), p.ws.data_ptr<float>(), tk, (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(),
+            p.kv_len, (int)kv_len_bias, starts, p.advance, stream_of(query)));
+        return p.out;
     }
     check(eetq_rope_decode_attention_bounded_f16(
-        positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(),
-        key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(),
-        value_cache.data_ptr(),
-        mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
-        reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits,
-        (float)sc, strides, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
-        advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-    return out;
+        positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+        cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(),
+        p.out.data_ptr(), p.ws.data_ptr<float>(), tk, (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(),
+        p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
 }
 
 // causal attention over a prompt on the matrix cores (eetq_prefill_attention_f16): query [B, T, H, D] (any token / head strides, D
@@ -999,45 +1020,20 @@ Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tens
     TORCH_CHECK(key_cache.size(0) == B && key_cache.size(3) == D && H % Hkv == 0 && query.stride(-1) == 1 &&
                     key_cache.stride(-1) == 1 && value_cache.stride(-1) == 1,
                 "decode_attention: shape / stride mismatch");
-    Tensor  mrow;
-    int64_t m_sb = 0;
-    if (mask) {
-        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
-        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
-                    "decode_attention: mask must be additive float16 with a dense last dimension >= S");
-        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B,
-                    "decode_attention: the mask needs one row per batch entry (or a single shared row)");
-        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
-    }
-    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
-        if (*t)
-            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(),
-                        "decode_attention: kv_len / advance must be a one-element int64 tensor on the query's device");
-    const double  sc = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    int64_t       splits = splits_in ? *splits_in
-                                     : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
-    Tensor        out = torch::empty({B, H, D}, query.options());
-    Tensor        ws  = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
-    const long    strides[11] = {(long)query.stride(0),       (long)query.stride(1),       (long)key_cache.stride(0),
-                                 (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
-                                 (long)value_cache.stride(1), (long)value_cache.stride(2), (long)m_sb,
-                                 (long)out.stride(0),         (long)out.stride(1)};
-    const int64_t* starts = kv_start_ptr("decode_attention", kv_start, query, B);
-    c10::DeviceGuard guard(query.device());
+    const DecodeAttnPrep p("decode_attention: ", query, S, nullptr, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), query.stride(1)}, key_cache, value_cache);
+    const int64_t*       starts  = kv_start_ptr("decode_attention", kv_start, query, B);
+    c10::DeviceGuard     guard(query.device());
     if (starts) {
-        check(eetq_decode_attention_padded_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
-                                               mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
-                                               (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides,
-                                               kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
-                                               advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-        return out;
+        check(eetq_decode_attention_padded_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(), p.out.data_ptr(),
+                                               p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc,
+                                               strides.data(), p.kv_len, (int)kv_len_bias, starts, p.advance, stream_of(query)));
+        return p.out;
     }
-    check(eetq_decode_attention_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
-                                    mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
-                                    (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides,
-                                    kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
-                                    advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-    return out;
+    check(eetq_decode_attention_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(), p.out.data_ptr(),
+                                    p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(),
+                                    p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
 }
 
 // ---- the int8 KV cache (include/eetq_amd.h "The int8 KV cache"): caches int8 [B, Hkv, S, D], scales fp16 [B, Hkv, S, 2] -------------
@@ -1068,35 +1064,14 @@ Tensor decode_attention_i8kv(const Tensor& query, const Tensor& key_cache, const
     const int64_t Hkv = key_cache.size(1), S = key_cache.size(2);
     check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
     TORCH_CHECK(Hkv > 0 && H % Hkv == 0, name, "shape mismatch");
-    Tensor  mrow;
-    int64_t m_sb = 0;
-    if (mask) {
-        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
-        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
-                    name, "mask must be additive float16 with a dense last dimension >= S");
-        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B, name, "the mask needs one row per batch entry (or a single shared row)");
-        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
-    }
-    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
-        if (*t)
-            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(), name,
-                        "kv_len / advance must be a one-element int64 tensor on the query's device");
-    const double sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    int64_t      splits = splits_in ? *splits_in : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
-    Tensor       out    = torch::empty({B, H, D}, query.options());
-    Tensor       ws     = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
-    const long   strides[11] = {(long)query.stride(0),       (long)query.stride(1),       (long)key_cache.stride(0),
-                                (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
-                                (long)value_cache.stride(1), (long)value_cache.stride(2), (long)m_sb,
-                                (long)out.stride(0),         (long)out.stride(1)};
-    const long   sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
-    c10::DeviceGuard guard(query.device());
-    check(eetq_decode_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
-                                         mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(), (int)B,
-                                         (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc, strides, sst,
-                                         kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
-                                         advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-    return out;
+    const DecodeAttnPrep p(name, query, S, nullptr, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), query.stride(1)}, key_cache, value_cache);
+    const long           sst[3]  = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard     guard(query.device());
+    check(eetq_decode_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), p.mask(),
+                                         p.out.data_ptr(), p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits,
+                                         p.sc, strides.data(), sst, p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
 }
 
 // prefill_attention's device-length / split form over an int8 cache (eetq_prefill_attention_i8kv_f16): query [B, T, H, D] (any token
@@ -1168,45 +1143,16 @@ Tensor rope_decode_attention_i8kv(const Tensor& positions, const Tensor& query, 
     TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.is_contiguous() && tickets.numel() >= B * H + 1 &&
                     tickets.device() == query.device(),
                 name, "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device");
-    int slot_stride = 0;
-    if (slots) {
-        const Tensor& s = *slots;
-        TORCH_CHECK(s.scalar_type() == at::kLong && s.device() == query.device() && (s.numel() == 1 || s.numel() == B) &&
-                        s.is_contiguous(),
-                    name, "slots must be contiguous int64 on the device, 1 or B elements");
-        slot_stride = (s.numel() == B && B > 1) ? 1 : 0;
-    }
-    Tensor  mrow;
-    int64_t m_sb = 0;
-    if (mask) {
-        mrow = mask->dim() != 2 ? mask->reshape({mask->size(0), -1}) : *mask;
-        TORCH_CHECK(mrow.scalar_type() == at::kHalf && mrow.size(-1) >= S && mrow.stride(-1) == 1 && mrow.device() == query.device(),
-                    name, "mask must be additive float16 with a dense last dimension >= S");
-        TORCH_CHECK(mrow.size(0) == 1 || mrow.size(0) == B, name, "the mask needs one row per batch entry (or a single shared row)");
-        m_sb = (mrow.size(0) == B && B > 1) ? mrow.stride(0) : 0;
-    }
-    for (const OptTensor* t : std::initializer_list<const OptTensor*>{&kv_len, &advance})
-        if (*t)
-            TORCH_CHECK((*t)->scalar_type() == at::kLong && (*t)->numel() == 1 && (*t)->device() == query.device(), name,
-                        "kv_len / advance must be a one-element int64 tensor on the query's device");
-    const double sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    int64_t      splits = splits_in ? *splits_in : (int64_t)eetq_decode_attention_splits((int)B, (int)H, (int)S);
-    Tensor       out    = torch::empty({B, H, D}, query.options());
-    Tensor       ws     = torch::empty({B * H * splits * (D + 4)}, query.options().dtype(at::kFloat));
-    const long   strides[12] = {(long)query.stride(0),       (long)key.stride(0),         (long)value.stride(0),
-                                (long)key_cache.stride(0),   (long)key_cache.stride(1),   (long)key_cache.stride(2),
-                                (long)value_cache.stride(0), (long)value_cache.stride(1), (long)value_cache.stride(2),
-                                (long)m_sb,                  (long)out.stride(0),         (long)out.stride(1)};
-    const long   sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
-    c10::DeviceGuard guard(query.device());
+    const DecodeAttnPrep p(name, query, S, &slots, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), key.stride(0), value.stride(0)}, key_cache, value_cache);
+    const long           sst[3]  = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard     guard(query.device());
     check(eetq_rope_decode_attention_i8kv_f16(
-        positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride, query.data_ptr(), key.data_ptr(),
-        value.data_ptr(), cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(),
-        scales.data_ptr(), mrow.defined() ? mrow.data_ptr() : nullptr, out.data_ptr(), ws.data_ptr<float>(),
-        reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)splits, (float)sc,
-        strides, sst, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias,
-        advance ? advance->data_ptr<int64_t>() : nullptr, stream_of(query)));
-    return out;
+        positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+        cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
+        p.mask(), p.out.data_ptr(), p.ws.data_ptr<float>(), reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H,
+        (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(), sst, p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
 }
 
 // rotary_embedding_neox_kvcache_prefill writing an int8 cache; key is rotated in place as well

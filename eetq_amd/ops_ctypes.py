@@ -720,6 +720,43 @@ def _check_kv_start(name, kv_start, query, B):
         raise RuntimeError("%s: kv_start must be a contiguous int64 [B] tensor on the query's device" % name)
 
 
+def _optr(t):
+    return _ptr(t) if t is not None else None
+
+
+class _DecodeAttnPrep:
+    """What the four decode-attention operators prepare alike (``name``: "operator: "): the slots' stride, the mask row and its
+    batch stride, the ``kv_len`` / ``advance`` scalars, the default scaling and chunk count, the output, the workspace and the
+    stride array (``lead``: q_b, q_h of the two-launch entries; q_b, k_b, v_b of the one-launch ones)."""
+
+    def __init__(self, name, query, S, slots, mask, scaling, splits, kv_len, advance, lead, key_cache, value_cache):
+        B, H, D = query.shape
+        self.slot_stride = 0
+        if slots is not None:
+            if (slots.dtype != torch.int64 or slots.device != query.device or slots.numel() not in (1, B)
+                    or not slots.is_contiguous()):
+                raise RuntimeError(name + "slots must be contiguous int64 on the device, 1 or B elements")
+            self.slot_stride = 1 if (slots.numel() == B and B > 1) else 0
+        self.mrow, m_sb = None, 0
+        if mask is not None:
+            self.mrow = mrow = mask.reshape(mask.shape[0], -1) if mask.dim() != 2 else mask
+            if mrow.dtype != torch.float16 or mrow.shape[-1] < S or mrow.stride(-1) != 1 or mrow.device != query.device:
+                raise RuntimeError(name + "mask must be additive float16 with a dense last dimension >= S")
+            if mrow.shape[0] not in (1, B):
+                raise RuntimeError(name + "the mask needs one row per batch entry (or a single shared row)")
+            m_sb = mrow.stride(0) if mrow.shape[0] == B and B > 1 else 0
+        for what, t in (("kv_len", kv_len), ("advance", advance)):
+            if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
+                raise RuntimeError(name + "%s must be a one-element int64 tensor on the query's device" % what)
+        self.scaling = float(D ** -0.5 if scaling is None else scaling)
+        # the library's tuned default (about two workgroups per CU, at most 8 chunks)
+        self.splits = int(_lib.lib().eetq_decode_attention_splits(B, H, S) if splits is None else splits)
+        self.out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
+        self.ws = torch.empty((B * H * self.splits * (D + 4),), dtype=torch.float32, device=query.device)
+        st = (*lead, *key_cache.stride()[:3], *value_cache.stride()[:3], m_sb, self.out.stride(0), self.out.stride(1))
+        self.strides = (ctypes.c_long * len(st))(*st)
+
+
 @_eager_only
 def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0,
                      advance=None, kv_start=None):
@@ -740,41 +777,20 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
     Bk, Hkv, S, Dk = key_cache.shape
     if Bk != B or Dk != D or H % Hkv or query.stride(-1) != 1 or key_cache.stride(-1) != 1 or value_cache.stride(-1) != 1:
         raise RuntimeError("decode_attention: shape / stride mismatch")
-    mrow, m_sb = None, 0
-    if mask is not None:
-        mrow = mask.reshape(mask.shape[0], -1) if mask.dim() != 2 else mask
-        if mrow.dtype != torch.float16 or mrow.shape[-1] < S or mrow.stride(-1) != 1 or mrow.device != query.device:
-            raise RuntimeError("decode_attention: mask must be additive float16 with a dense last dimension >= S")
-        if mrow.shape[0] not in (1, B):
-            raise RuntimeError("decode_attention: the mask needs one row per batch entry (or a single shared row)")
-        m_sb = mrow.stride(0) if mrow.shape[0] == B and B > 1 else 0
-    for name, t in (("kv_len", kv_len), ("advance", advance)):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
-            raise RuntimeError("decode_attention: %s must be a one-element int64 tensor on the query's device" % name)
+    p = _DecodeAttnPrep("decode_attention: ", query, S, None, mask, scaling, splits, kv_len, advance,
+                        (query.stride(0), query.stride(1)), key_cache, value_cache)
     if kv_start is not None:
         _check_kv_start("decode_attention", kv_start, query, B)
-    if scaling is None:
-        scaling = D ** -0.5
-    if splits is None:  # the library's tuned default (about two workgroups per CU, at most 8 chunks)
-        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
-    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
-    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
-    strides = (ctypes.c_long * 11)(query.stride(0), query.stride(1), key_cache.stride(0), key_cache.stride(1),
-                                   key_cache.stride(2), value_cache.stride(0), value_cache.stride(1), value_cache.stride(2),
-                                   m_sb, out.stride(0), out.stride(1))
     with torch.cuda.device(query.device):
         if kv_start is not None:
             check(_lib.lib().eetq_decode_attention_padded_f16(
-                _ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws),
-                B, H, Hkv, S, D, int(splits), float(scaling), strides, _ptr(kv_len) if kv_len is not None else None,
-                int(kv_len_bias), _ptr(kv_start), _ptr(advance) if advance is not None else None, _stream_ptr()))
-            return out
-        check(_lib.lib().eetq_decode_attention_f16(_ptr(query), _ptr(key_cache), _ptr(value_cache),
-                                                   _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), B, H,
-                                                   Hkv, S, D, int(splits), float(scaling), strides,
-                                                   _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
-                                                   _ptr(advance) if advance is not None else None, _stream_ptr()))
-    return out
+                _ptr(query), _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits,
+                p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _ptr(kv_start), _optr(advance), _stream_ptr()))
+            return p.out
+        check(_lib.lib().eetq_decode_attention_f16(
+            _ptr(query), _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits,
+            p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(advance), _stream_ptr()))
+    return p.out
 
 
 @_eager_only
@@ -808,52 +824,23 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
             or tickets.device != query.device):
         raise RuntimeError("rope_decode_attention: tickets must be a zeroed int32 tensor of at least B * H + 1 elements "
                            "on the device")
-    slot_stride = 0
-    if slots is not None:
-        if (slots.dtype != torch.int64 or slots.device != query.device or slots.numel() not in (1, B)
-                or not slots.is_contiguous()):
-            raise RuntimeError("rope_decode_attention: slots must be contiguous int64 on the device, 1 or B elements")
-        slot_stride = 1 if (slots.numel() == B and B > 1) else 0
-    mrow, m_sb = None, 0
-    if mask is not None:
-        mrow = mask.reshape(mask.shape[0], -1) if mask.dim() != 2 else mask
-        if mrow.dtype != torch.float16 or mrow.shape[-1] < S or mrow.stride(-1) != 1 or mrow.device != query.device:
-            raise RuntimeError("rope_decode_attention: mask must be additive float16 with a dense last dimension >= S")
-        if mrow.shape[0] not in (1, B):
-            raise RuntimeError("rope_decode_attention: the mask needs one row per batch entry (or a single shared row)")
-        m_sb = mrow.stride(0) if mrow.shape[0] == B and B > 1 else 0
-    for name, t in (("kv_len", kv_len), ("advance", advance)):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
-            raise RuntimeError("rope_decode_attention: %s must be a one-element int64 tensor on the query's device" % name)
+    p = _DecodeAttnPrep("rope_decode_attention: ", query, S, slots, mask, scaling, splits, kv_len, advance,
+                        (query.stride(0), key.stride(0), value.stride(0)), key_cache, value_cache)
     if kv_start is not None:
         _check_kv_start("rope_decode_attention", kv_start, query, B)
-    if scaling is None:
-        scaling = D ** -0.5
-    if splits is None:
-        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
-    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
-    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
-    strides = (ctypes.c_long * 12)(query.stride(0), key.stride(0), value.stride(0), key_cache.stride(0),
-                                   key_cache.stride(1), key_cache.stride(2), value_cache.stride(0), value_cache.stride(1),
-                                   value_cache.stride(2), m_sb, out.stride(0), out.stride(1))
     with torch.cuda.device(query.device):
         if kv_start is not None:
             check(_lib.lib().eetq_rope_decode_attention_padded_f16(
-                _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
-                _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache),
-                _ptr(mrow) if mrow is not None else None, _ptr(out),
-                _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits), float(scaling), strides,
-                _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias), _ptr(kv_start),
-                _ptr(advance) if advance is not None else None, _stream_ptr()))
-            return out
+                _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+                cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), _ptr(tickets),
+                B, H, Hkv, S, D, p.splits, p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _ptr(kv_start), _optr(advance),
+                _stream_ptr()))
+            return p.out
         check(_lib.lib().eetq_rope_decode_attention_bounded_f16(
-            _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
-            _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache),
-            _ptr(mrow) if mrow is not None else None, _ptr(out),
-            _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits), float(scaling), strides,
-            _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
-            _ptr(advance) if advance is not None else None, _stream_ptr()))
-    return out
+            _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+            cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), _ptr(tickets),
+            B, H, Hkv, S, D, p.splits, p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(advance), _stream_ptr()))
+    return p.out
 
 
 @_eager_only
@@ -956,17 +943,6 @@ def _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D):
             raise RuntimeError(name + "all tensors must be on one device")
 
 
-def _mask_row(name, mask, query, B, S):
-    if mask is None:
-        return None, 0
-    mrow = mask.reshape(mask.shape[0], -1) if mask.dim() != 2 else mask
-    if mrow.dtype != torch.float16 or mrow.shape[-1] < S or mrow.stride(-1) != 1 or mrow.device != query.device:
-        raise RuntimeError(name + "mask must be additive float16 with a dense last dimension >= S")
-    if mrow.shape[0] not in (1, B):
-        raise RuntimeError(name + "the mask needs one row per batch entry (or a single shared row)")
-    return mrow, (mrow.stride(0) if mrow.shape[0] == B and B > 1 else 0)
-
-
 @_eager_only
 def decode_attention_i8kv(query, key_cache, value_cache, scales, mask=None, scaling=None, splits=None, kv_len=None,
                           kv_len_bias=0, advance=None):
@@ -981,27 +957,14 @@ def decode_attention_i8kv(query, key_cache, value_cache, scales, mask=None, scal
     _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
     if Hkv <= 0 or H % Hkv:
         raise RuntimeError(name + "shape mismatch")
-    mrow, m_sb = _mask_row(name, mask, query, B, S)
-    for what, t in (("kv_len", kv_len), ("advance", advance)):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
-            raise RuntimeError(name + "%s must be a one-element int64 tensor on the query's device" % what)
-    if scaling is None:
-        scaling = D ** -0.5
-    if splits is None:
-        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
-    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
-    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
-    strides = (ctypes.c_long * 11)(query.stride(0), query.stride(1), key_cache.stride(0), key_cache.stride(1),
-                                   key_cache.stride(2), value_cache.stride(0), value_cache.stride(1), value_cache.stride(2),
-                                   m_sb, out.stride(0), out.stride(1))
+    p = _DecodeAttnPrep(name, query, S, None, mask, scaling, splits, kv_len, advance, (query.stride(0), query.stride(1)),
+                        key_cache, value_cache)
     sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
     with torch.cuda.device(query.device):
-        check(_lib.lib().eetq_decode_attention_i8kv_f16(_ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(scales),
-                                                        _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), B, H,
-                                                        Hkv, S, D, int(splits), float(scaling), strides, sst,
-                                                        _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
-                                                        _ptr(advance) if advance is not None else None, _stream_ptr()))
-    return out
+        check(_lib.lib().eetq_decode_attention_i8kv_f16(
+            _ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(scales), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D,
+            p.splits, p.scaling, p.strides, sst, _optr(kv_len), int(kv_len_bias), _optr(advance), _stream_ptr()))
+    return p.out
 
 
 @_eager_only
@@ -1032,34 +995,16 @@ def rope_decode_attention_i8kv(positions, query, key, value, cos_sin_cache, key_
     if (tickets.dtype != torch.int32 or not tickets.is_contiguous() or tickets.numel() < B * H + 1
             or tickets.device != query.device):
         raise RuntimeError(name + "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device")
-    slot_stride = 0
-    if slots is not None:
-        if (slots.dtype != torch.int64 or slots.device != query.device or slots.numel() not in (1, B)
-                or not slots.is_contiguous()):
-            raise RuntimeError(name + "slots must be contiguous int64 on the device, 1 or B elements")
-        slot_stride = 1 if (slots.numel() == B and B > 1) else 0
-    mrow, m_sb = _mask_row(name, mask, query, B, S)
-    for what, t in (("kv_len", kv_len), ("advance", advance)):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != query.device):
-            raise RuntimeError(name + "%s must be a one-element int64 tensor on the query's device" % what)
-    if scaling is None:
-        scaling = D ** -0.5
-    if splits is None:
-        splits = _lib.lib().eetq_decode_attention_splits(B, H, S)
-    out = torch.empty((B, H, D), dtype=torch.float16, device=query.device)
-    ws = torch.empty((B * H * splits * (D + 4),), dtype=torch.float32, device=query.device)
-    strides = (ctypes.c_long * 12)(query.stride(0), key.stride(0), value.stride(0), key_cache.stride(0),
-                                   key_cache.stride(1), key_cache.stride(2), value_cache.stride(0), value_cache.stride(1),
-                                   value_cache.stride(2), m_sb, out.stride(0), out.stride(1))
+    p = _DecodeAttnPrep(name, query, S, slots, mask, scaling, splits, kv_len, advance,
+                        (query.stride(0), key.stride(0), value.stride(0)), key_cache, value_cache)
     sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
     with torch.cuda.device(query.device):
         check(_lib.lib().eetq_rope_decode_attention_i8kv_f16(
-            _ptr(positions), _ptr(slots) if slots is not None else None, slot_stride, _ptr(query), _ptr(key), _ptr(value),
-            _ptr(cos_sin_cache), cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _ptr(scales),
-            _ptr(mrow) if mrow is not None else None, _ptr(out), _ptr(ws), _ptr(tickets), B, H, Hkv, S, D, int(splits),
-            float(scaling), strides, sst, _ptr(kv_len) if kv_len is not None else None, int(kv_len_bias),
-            _ptr(advance) if advance is not None else None, _stream_ptr()))
-    return out
+            _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+            cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _ptr(scales), _optr(p.mrow), _ptr(p.out), _ptr(p.ws),
+            _ptr(tickets), B, H, Hkv, S, D, p.splits, p.scaling, p.strides, sst, _optr(kv_len), int(kv_len_bias), _optr(advance),
+            _stream_ptr()))
+    return p.out
 
 
 @_eager_only

@@ -113,7 +113,7 @@ def test_refusals_without_a_gpu(lib):
 def test_a_cache_the_decode_entry_accepts_is_accepted():
     """The shared rule (kv_i8.hpp::check_i8_cache) is one function: both entries call it with the cache's six strides."""
     src = open(os.path.join(ROOT, "eetq_amd", "csrc", "attn_prefill.hip")).read()
-    dec = open(os.path.join(ROOT, "eetq_amd", "csrc", "attn_decode_i8.hip")).read()
+    dec = open(os.path.join(ROOT, "eetq_amd", "csrc", "attn_decode.hip")).read()
     hdr = open(os.path.join(ROOT, "eetq_amd", "csrc", "kv_i8.hpp")).read()
     assert hdr.count("int check_i8_cache(") == 1 and "check_i8_cache(" in src and "check_i8_cache(" in dec
     assert "int check_i8_cache(" not in src and "int check_i8_cache(" not in dec

@@ -1,4 +1,4 @@
-"""The int8 KV cache's kernels (eetq_amd/csrc/attn_decode_i8.hip, the quantising write of norm_rope.hip) at the shapes where
+"""The int8 KV cache's kernels (eetq_amd/csrc/attn_decode.hip, the quantising write of norm_rope.hip) at the shapes where
 the chunk code's paths change (the rows of test_gpu_attn_decode_edges.py), with the input families of tests/attn_cases.py
 built as int8 bytes and fp16 scales by the NumPy quantiser of tests/kv8_cases.py:
 

@@ -1,7 +1,7 @@
 """The int8 KV cache where its own tests (test_gpu_kv8_attn.py, test_gpu_kv8_decoder.py) do not look.
 
   edge rows   tests/kv8_cases.edge_rows through BOTH quantisers on the GPU -- the prompt writer (norm_rope.hip) and the
-              in-register quantiser of the one-launch decode form (attn_decode_i8.hip): exact ties (half away from zero, never
+              in-register quantiser of the one-launch decode form (attn_decode.hip): exact ties (half away from zero, never
               to even), fp16-subnormal scales, a non-zero row whose scale rounds to 0, the clamp (it only ever bites under a
               subnormal scale), amax 65504, and a sweep that puts the row maximum on every channel in turn (the three absmax
               reductions).  Bytes and scale bit patterns equal the NumPy quantiser's.
