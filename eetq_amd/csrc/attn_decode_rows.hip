@@ -17,7 +17,7 @@
 //   S^T       = K Q^T per 16 keys: the K rows are the A operand STRAIGHT from global memory (lane = key lane & 15, channels
 //             32 ks + 8 (lane >> 4) ..: one 16-byte load per k-step), the sub-tile's Q rows the B operand, held in registers.
 //             A lane then owns ONE query column and keys 4 (lane >> 4) + i of the 16: maximum and sum are 7 local operations and
-//             two lane swaps, and the probabilities -- rounded to fp16, carried as 2^12 p (kPfPShift of attn_prefill.hip and the
+//             two lane swaps, and the probabilities -- rounded to fp16, carried as 2^12 p (kAttnPShift of common.hpp and the
 //             comment there) -- ARE the B operand of the second product: k-slots 8 g + i = key 4 g + i of the first 16-key group,
 //             8 g + 4 + i = the same of the second.
 //   O^T       += V^T P^T per 32 keys: V goes through a wave-private transposed LDS image ([channel][32 keys], 72-byte pitch; a
@@ -43,7 +43,6 @@ constexpr int   kRowsMaxR = 16;         // query rows per batch row
 constexpr int   kRowsMaxSub = 4;        // 16-row sub-tiles a workgroup holds
 constexpr int   kRowsMaxSplits = 64;
 constexpr int   kRowsVtPitch = kRowsBlk + 4;   // halfs per channel row of the transposed V image (72 bytes)
-constexpr float kRowsPShift = 12.f;     // probabilities as 2^12 p (attn_prefill.hip: kPfPShift)
 
 struct RowsArgs {
     const f16*     q;
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
                         x[4 * kb + i] = key <= lim ? sc[kb][i] * a.c : -INFINITY;
                         mloc = fmaxf(mloc, x[4 * kb + i]);
                     }
-                mloc = col_max(mloc) - kRowsPShift;                          // the maxima are kept 12 below: p as 2^12 p
+                mloc = col_max(mloc) - kAttnPShift;                          // the maxima are kept 12 below: p as 2^12 p
                 const float m_new = fmaxf(m_run[s], mloc);
                 const float m_use = m_new > -INFINITY ? m_new : 0.f;         // a row with nothing to attend yet: every p = 0
                 const float alpha = __builtin_amdgcn_exp2f(m_run[s] - m_use);   // exp2(-inf) = 0 for the first block
@@ -373,11 +372,10 @@ int launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* 
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "invalid attention shape");
     if (D != 128 && D != 64) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] few-row attention supports head_dim 64 and 128");
     EETQ_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "the workspace is always needed (two launches) and must be 16-byte aligned");
-    for (int i = 0; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "strides must be multiples of 4 elements");
-    for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte loads)");
-    EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)out % 8 == 0, "q, k, v must be 16-byte aligned, out 8-byte");
-    EETQ_REQUIRE(st[5] > 0 && st[8] > 0 && (long)max_keys * st[5] * 2 < (1L << 31) && (long)max_keys * st[8] * 2 < (1L << 31),
-                 "one head's cache rows must span less than 2 GiB");
+    const int rc = check_attn_layout(q, k, v, out, max_keys, st);
+    if (rc != EETQ_OK) return rc;
+    // (its own: the row offsets here are unsigned, and kNoRow must lie beyond every row)
+    EETQ_REQUIRE(st[5] > 0 && st[8] > 0, "one head's cache rows must span less than 2 GiB");
     RowsArgs a;
     a.q = q, a.k = k, a.v = v, a.ws = ws;
     a.q_sb = st[0], a.q_st = st[1], a.q_sh = st[2], a.k_sb = st[3], a.k_sh = st[4], a.k_ss = st[5];

@@ -32,13 +32,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kPfThreads = 256, kPfBM = 128, kPfBN = 64;
-// The probabilities are carried as 2^12 p: the running maximum is kept kPfPShift below the true one (the shift rides in the fma that
-// scales the block maximum; one constant register, no instruction in the loop), so the row maximum maps to 4 096 and the row sum to
-// 4 096 l, and the factor leaves with the division at the end.  As fp16 B operands of the second product the probabilities then keep
-// 11 significant bits down to p = 2^-26.  Unshifted, every p below 2^-14 is an fp16 subnormal with an ABSOLUTE error of up to 2^-25,
-// and a handful of such keys move an output that is itself tiny (a peaked row whose winning value is near zero) by more than its
-// own fp16 spacing (tests/test_gpu_attn_prefill_edges.py).  4 096 (1 + rounding) is far below fp16's 65 504.
-constexpr float kPfPShift = 12.f;
 
 struct PrefillArgs {
     const f16* q;
@@ -351,7 +344,7 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[kb][r]);
-            mloc = fmaf(fmaxf(mloc, __shfl_xor(mloc, 32, 64)), a.c, -kPfPShift);   // (c > 0); the maxima are kept 12 below: p as 2^12 p
+            mloc = fmaf(fmaxf(mloc, __shfl_xor(mloc, 32, 64)), a.c, -kAttnPShift);   // (c > 0); the maxima are kept 12 below: p as 2^12 p
             const float m_new = fmaxf(m_run, mloc);
             const float m_use = m_new > -INFINITY ? m_new : 0.f;             // a row with nothing to attend yet: every p = 0
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);       // exp2(-inf) = 0 for the first block
@@ -461,10 +454,8 @@ int check_prefill_common(const f16* q, const f16* k, const f16* v, f16* out, int
     EETQ_REQUIRE(q && k && v && out && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0 && Tk > 0, "invalid attention shape");
     if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
-    for (int i = 0; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "strides must be multiples of 4 elements");
-    for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte loads)");
-    EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)out % 8 == 0, "q, k, v must be 16-byte aligned, out 8-byte");
-    EETQ_REQUIRE((long)Tk * st[5] * 2 < (1L << 31) && (long)Tk * st[8] * 2 < (1L << 31), "one head's cache rows must span less than 2 GiB");
+    const int rc = check_attn_layout(q, k, v, out, Tk, st);
+    if (rc != EETQ_OK) return rc;
     EETQ_REQUIRE((long)((Tq + kPfBM - 1) / kPfBM) * H * B < (1L << 31), "too many workgroups");
     return EETQ_OK;
 }
@@ -483,6 +474,16 @@ void fill_prefill_args(PrefillArgs& a, const f16* q, const f16* k, const f16* v,
 }  // namespace
 
 bool prefill_attention_supports(int D) { return D == 128 || D == 64; }
+
+// what the 16-byte loads, the 8-byte stores and the 32-bit offsets behind the cache descriptors ask of the layout
+int check_attn_layout(const f16* q, const f16* k, const f16* v, const f16* out, int keys, const long* st)
+{
+    for (int i = 0; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "strides must be multiples of 4 elements");
+    for (int i = 0; i < 9; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte loads)");
+    EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)out % 8 == 0, "q, k, v must be 16-byte aligned, out 8-byte");
+    EETQ_REQUIRE((long)keys * st[5] * 2 < (1L << 31) && (long)keys * st[8] * 2 < (1L << 31), "one head's cache rows must span less than 2 GiB");
+    return EETQ_OK;
+}
 
 // strides (elements): {q_b, q_token, q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b, out_token, out_head}
 int launch_prefill_attention(const f16* q, const f16* k, const f16* v, f16* out, int B, int H, int Hkv, int Tq, int Tk, int D,
@@ -527,18 +528,21 @@ int prefill_attention_splits(int B, int H, int Tq, int max_keys)
     return (int)ns;
 }
 
-// Device-length and split-KV launches: keys <= max_keys from *kv_len + kv_len_bias (kv_len nullptr: max_keys itself), causal offset
-// keys - Tq.  splits > 1: two plain launches, the shares into `ws` (prefill_attention_workspace_floats), then the merge.
-int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq, int max_keys,
-                                 int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st, hipStream_t stream)
+namespace {
+
+// The one launch path of the device forms (plain, per-row first key, int8 rows).  `a` arrives with the form's own fields set
+// (kv_start; the scales), `front` runs the form's own argument checks -- every form has them between the two requirements on top
+// and the workspace's --, what1 / whatn name the form when a launch fails.  k and v: the int8 form's rows as they go into the struct.
+template <bool KV8, bool PAD, class Front>
+int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD>& a, Front front, const f16* q, const f16* k, const f16* v, f16* out, float* ws,
+                         int B, int H, int Hkv, int Tq, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits,
+                         float scaling, const long* st, hipStream_t stream, const char* what1, const char* whatn)
 {
     EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
     EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
-    const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
+    const int rc = front();
     if (rc != EETQ_OK) return rc;
     EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
-    if (splits == 1 && !kv_len) return launch_prefill_attention(q, k, v, out, B, H, Hkv, Tq, max_keys, D, max_keys - Tq, scaling, st, stream);
-    PrefillDevArgs a;
     fill_prefill_args(a, q, k, v, out, B, H, Hkv, Tq, max_keys, max_keys - Tq, scaling, st);
     a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits;
     const long wgs = (long)a.nqb * H * B * splits;
@@ -546,22 +550,38 @@ int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* 
     const dim3 grid((unsigned)wgs), block(kPfThreads);
     if (splits == 1) {
         if (D == 128)
-            launch_kernel(prefill_attn_kernel<128, kPfDev>, grid, block, 0, stream, a);
+            launch_kernel(prefill_attn_kernel<128, kPfDev, KV8, PAD>, grid, block, 0, stream, a);
         else
-            launch_kernel(prefill_attn_kernel<64, kPfDev>, grid, block, 0, stream, a);
-        return check_hip(hipGetLastError(), "prefill_attn_kernel (device length) launch");
+            launch_kernel(prefill_attn_kernel<64, kPfDev, KV8, PAD>, grid, block, 0, stream, a);
+        return check_hip(hipGetLastError(), what1);
     }
     const long rows = (long)B * H * Tq, threads = rows * (D / 4);
     EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
     const dim3 mgrid((unsigned)((threads + 255) / 256));
     if (D == 128) {
-        launch_kernel(prefill_attn_kernel<128, kPfSplit>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<128, kPfSplit, KV8, PAD>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     } else {
-        launch_kernel(prefill_attn_kernel<64, kPfSplit>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<64, kPfSplit, KV8, PAD>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     }
-    return check_hip(hipGetLastError(), "prefill_attn_kernel (split) launch");
+    return check_hip(hipGetLastError(), whatn);
+}
+
+}  // namespace
+
+// Device-length and split-KV launches: keys <= max_keys from *kv_len + kv_len_bias (kv_len nullptr: max_keys itself), causal offset
+// keys - Tq.  splits > 1: two plain launches, the shares into `ws` (prefill_attention_workspace_floats), then the merge.
+int launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq, int max_keys,
+                                 int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st, hipStream_t stream)
+{
+    // nothing for the device to decide: the host form, whose checks are the ones below (a max_keys <= 0 is reported here)
+    if (max_keys > 0 && splits == 1 && !kv_len)
+        return launch_prefill_attention(q, k, v, out, B, H, Hkv, Tq, max_keys, D, max_keys - Tq, scaling, st, stream);
+    PrefillDevArgs a;
+    return launch_prefill_forms<false, false>(
+        a, [&] { return check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st); }, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D,
+        kv_len, kv_len_bias, splits, scaling, st, stream, "prefill_attn_kernel (device length) launch", "prefill_attn_kernel (split) launch");
 }
 
 // launch_prefill_attention_dev with a per-row first key: cache rows below kv_start[b] (DEVICE [B]) of batch row b are padding (the PAD
@@ -570,36 +590,17 @@ int launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v, f1
                                     int max_keys, int D, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int splits,
                                     float scaling, const long* st, hipStream_t stream)
 {
-    EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
-    EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
-    const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
-    if (rc != EETQ_OK) return rc;
-    EETQ_REQUIRE(kv_start, "null kv_start");
-    EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
     PrefillPadArgs a;
-    fill_prefill_args(a, q, k, v, out, B, H, Hkv, Tq, max_keys, max_keys - Tq, scaling, st);
-    a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits, a.kv_start = kv_start;
-    const long wgs = (long)a.nqb * H * B * splits;
-    EETQ_REQUIRE(wgs < (1L << 31), "too many workgroups");
-    const dim3 grid((unsigned)wgs), block(kPfThreads);
-    if (splits == 1) {
-        if (D == 128)
-            launch_kernel(prefill_attn_kernel<128, kPfDev, false, true>, grid, block, 0, stream, a);
-        else
-            launch_kernel(prefill_attn_kernel<64, kPfDev, false, true>, grid, block, 0, stream, a);
-        return check_hip(hipGetLastError(), "prefill_attn_kernel (per-row first key) launch");
-    }
-    const long rows = (long)B * H * Tq, threads = rows * (D / 4);
-    EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
-    const dim3 mgrid((unsigned)((threads + 255) / 256));
-    if (D == 128) {
-        launch_kernel(prefill_attn_kernel<128, kPfSplit, false, true>, grid, block, 0, stream, a);
-        launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
-    } else {
-        launch_kernel(prefill_attn_kernel<64, kPfSplit, false, true>, grid, block, 0, stream, a);
-        launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
-    }
-    return check_hip(hipGetLastError(), "prefill_attn_kernel (per-row first key, split) launch");
+    a.kv_start = kv_start;
+    auto front = [&] {
+        const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
+        if (rc != EETQ_OK) return rc;
+        EETQ_REQUIRE(kv_start, "null kv_start");
+        return (int)EETQ_OK;
+    };
+    return launch_prefill_forms<false, true>(a, front, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D, kv_len, kv_len_bias, splits, scaling, st,
+                                             stream, "prefill_attn_kernel (per-row first key) launch",
+                                             "prefill_attn_kernel (per-row first key, split) launch");
 }
 
 // launch_prefill_attention_dev over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of
@@ -609,42 +610,19 @@ int launch_prefill_attention_i8kv(const f16* q, const int8_t* k, const int8_t* v
                                   const long* st, const long* sst, hipStream_t stream)
 {
     EETQ_REQUIRE(q && k && v && scales && out && st && sst, "null pointer");
-    EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
-    EETQ_REQUIRE(splits >= 1 && splits <= kPfMaxSplits, "splits must lie in 1 .. 16");
-    EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0, "invalid attention shape");
-    if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
-    for (int i = 0; i < 3; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q strides must be multiples of 8 elements (16-byte loads)");
-    for (int i = 9; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "out strides must be multiples of 4 elements");
-    EETQ_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)out % 8 == 0, "q must be 16-byte aligned, out 8-byte");
-    const int rc = check_i8_cache(k, v, scales, max_keys, st + 3, sst);
-    if (rc != EETQ_OK) return rc;
-    EETQ_REQUIRE(splits == 1 || (ws && (uintptr_t)ws % 16 == 0), "the split form needs a 16-byte aligned workspace");
     PrefillDevArgs8 a;
-    fill_prefill_args(a, q, reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v), out, B, H, Hkv, Tq, max_keys, max_keys - Tq,
-                      scaling, st);
-    a.kv_len = kv_len, a.ws = ws, a.kv_len_bias = kv_len_bias, a.ns = splits;
     a.scales = scales, a.s_sb = sst[0], a.s_sh = sst[1], a.s_ss = sst[2];
-    const long wgs = (long)a.nqb * H * B * splits;
-    EETQ_REQUIRE(wgs < (1L << 31), "too many workgroups");
-    const dim3 grid((unsigned)wgs), block(kPfThreads);
-    if (splits == 1) {
-        if (D == 128)
-            launch_kernel(prefill_attn_kernel<128, kPfDev, true>, grid, block, 0, stream, a);
-        else
-            launch_kernel(prefill_attn_kernel<64, kPfDev, true>, grid, block, 0, stream, a);
-        return check_hip(hipGetLastError(), "prefill_attn_kernel (int8 rows) launch");
-    }
-    const long rows = (long)B * H * Tq, threads = rows * (D / 4);
-    EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
-    const dim3 mgrid((unsigned)((threads + 255) / 256));
-    if (D == 128) {
-        launch_kernel(prefill_attn_kernel<128, kPfSplit, true>, grid, block, 0, stream, a);
-        launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
-    } else {
-        launch_kernel(prefill_attn_kernel<64, kPfSplit, true>, grid, block, 0, stream, a);
-        launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
-    }
-    return check_hip(hipGetLastError(), "prefill_attn_kernel (int8 rows, split) launch");
+    auto front = [&] {
+        EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && Tq > 0, "invalid attention shape");
+        if (!prefill_attention_supports(D)) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] prompt attention supports head_dim 64 and 128");
+        for (int i = 0; i < 3; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q strides must be multiples of 8 elements (16-byte loads)");
+        for (int i = 9; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "out strides must be multiples of 4 elements");
+        EETQ_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)out % 8 == 0, "q must be 16-byte aligned, out 8-byte");
+        return check_i8_cache(k, v, scales, max_keys, st + 3, sst);
+    };
+    return launch_prefill_forms<true, false>(a, front, q, reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v), out, ws, B, H,
+                                             Hkv, Tq, max_keys, D, kv_len, kv_len_bias, splits, scaling, st, stream,
+                                             "prefill_attn_kernel (int8 rows) launch", "prefill_attn_kernel (int8 rows, split) launch");
 }
 
 }  // namespace eetq

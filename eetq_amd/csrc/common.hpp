@@ -325,6 +325,14 @@ int launch_rope_attn_decode(const int64_t* positions, const int64_t* slots, int 
                             unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
                             const long* strides, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
                             hipStream_t stream);
+// The MFMA attention kernels (attn_prefill.hip, attn_decode_rows.hip) carry the probabilities as 2^12 p: the running maximum is kept
+// kAttnPShift below the true one (in the prompt kernel the shift rides in the fma that scales the block maximum: one constant
+// register, no instruction in the loop), so the row maximum maps to 4 096 and the row sum to 4 096 l, and the factor leaves with
+// the division at the end.  As fp16 B operands of the second product the probabilities then keep 11 significant bits down to
+// p = 2^-26.  Unshifted, every p below 2^-14 is an fp16 subnormal with an ABSOLUTE error of up to 2^-25, and a handful of such keys
+// move an output that is itself tiny (a peaked row whose winning value is near zero) by more than its own fp16 spacing
+// (tests/test_gpu_attn_prefill_edges.py).  4 096 (1 + rounding) is far below fp16's 65 504.
+constexpr float kAttnPShift = 12.f;
 // causal attention over a prompt on MFMA (attn_prefill.hip); st: {q_b, q_token, q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b,
 // out_token, out_head} in elements
 bool prefill_attention_supports(int D);
@@ -340,6 +348,9 @@ int    launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v,
 int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
 int    prefill_attention_max_splits();
 size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
+// the layout both MFMA attention launchers over fp16 rows require (attn_prefill.hip): strides % 4, q / k / v strides % 8, 16- /
+// 8-byte pointers, `keys` rows of a head within 2 GiB
+int    check_attn_layout(const f16* q, const f16* k, const f16* v, const f16* out, int keys, const long* st);
 // 1 .. 16 query rows behind a long cache, split-KV on MFMA (attn_decode_rows.hip); st as launch_prefill_attention's
 int    launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R, int max_keys,
                                     int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,

@@ -273,76 +273,105 @@ int64_t prefill_attention_splits(int64_t batch, int64_t heads, int64_t q_tokens,
     return eetq_prefill_attention_splits((int)batch, (int)heads, (int)q_tokens, (int)max_keys);
 }
 
+// The query [B, rows, H, D] and the cache views [B, Hkv, S >= keys, D] of prefill_attention and decode_attention_rows (`rows`: the
+// letter the message calls the query rows by); name: "operator: "
+static void check_prompt_qkv(const char* name, char rows, const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys)
+{
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
+                    name, "float16 CUDA tensors [B, ", rows, ", H, D] / [B, Hkv, S, D] with a dense last dimension expected");
+    const int64_t Hkv = key.size(1);
+    TORCH_CHECK(key.size(0) == query.size(0) && key.size(3) == query.size(3) && value.sizes() == key.sizes() && Hkv > 0 &&
+                    query.size(2) % Hkv == 0 && keys > 0 && keys <= key.size(2),
+                name, "shape mismatch");
+}
+// What prefill_attention, prefill_attention_i8kv and decode_attention_rows prepare alike behind their own tensor checks: the kv_len
+// scalar and its bias, the default scaling, the share count (None: the library's rule) and its range, the workspace (checked, or
+// allocated here: capturable), the output [B, rows, H, D] and the twelve strides.  name: "operator: "; always_ws: a workspace even of
+// no elements; device_form = false (prefill_attention's host form): one share, no workspace, nothing to check.
+struct PromptAttnPrep {
+    const int64_t* kv_len = nullptr;
+    int64_t        splits = 1;
+    float          sc;
+    Tensor         ws, out;
+    long           st[12];
+
+    PromptAttnPrep(const char* name, const Tensor& query, const Tensor& kc, const Tensor& vc, int64_t keys, std::optional<double> scaling,
+                   const OptTensor& kv_len_in, int64_t kv_len_bias, std::optional<int64_t> splits_in, const OptTensor& workspace,
+                   int (*default_splits)(int B, int H, int Hkv, int rows, int keys), int (*max_splits)(),
+                   size_t (*workspace_floats)(int B, int H, int rows, int D, int splits), bool always_ws, bool device_form = true)
+    {
+        const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3);
+        sc = (float)(scaling ? *scaling : 1.0 / std::sqrt((double)D));
+        if (device_form) {
+            TORCH_CHECK(kv_len_in || kv_len_bias == 0, name, "kv_len_bias needs kv_len");
+            if (kv_len_in) {
+                TORCH_CHECK(kv_len_in->scalar_type() == at::kLong && kv_len_in->numel() == 1 && kv_len_in->device() == query.device(), name,
+                            "kv_len must be a one-element int64 tensor on the query's device");
+                kv_len = kv_len_in->data_ptr<int64_t>();
+            }
+            splits = splits_in ? *splits_in : (int64_t)default_splits((int)B, (int)H, (int)kc.size(1), (int)R, (int)keys);
+            TORCH_CHECK(splits >= 1 && splits <= max_splits(), name, "splits must lie in 1 .. ", max_splits());
+            const int64_t need = (int64_t)workspace_floats((int)B, (int)H, (int)R, (int)D, (int)splits);
+            if (workspace) {
+                TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
+                                workspace->numel() >= need,
+                            name, "workspace must be a contiguous float32 tensor of at least ", need, " elements on the query's device");
+                ws = *workspace;
+            } else if (always_ws || need > 0) {
+                ws = torch::empty({need}, query.options().dtype(at::kFloat));
+            }
+        }
+        out = torch::empty({B, R, H, D}, query.options());
+        int n = 0;
+        for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &kc, &vc, &out})
+            for (int i = 0; i < 3; ++i) st[n++] = (long)t->stride(i);
+    }
+    float* workspace() const { return ws.defined() ? ws.data_ptr<float>() : nullptr; }
+};
+static int prefill_splits_rule(int B, int H, int, int T, int keys) { return eetq_prefill_attention_splits(B, H, T, keys); }
+
 // kv_len (a one-element int64 tensor on the query's device): `keys` is then the upper bound and the number of keys is read on the
 // device (eetq_prefill_attention_dev_f16); splits: None = the library's rule, workspace: None = allocated here (capturable)
 Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
                          std::optional<int64_t> causal_offset, const OptTensor& kv_len, int64_t kv_len_bias,
                          std::optional<int64_t> splits_in, const OptTensor& workspace, const OptTensor& kv_start = std::nullopt)
 {
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
-        TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
-                    "prefill_attention: float16 CUDA tensors [B, T, H, D] / [B, Hkv, S, D] with a dense last dimension expected");
+    check_prompt_qkv("prefill_attention: ", 'T', query, key, value, keys);
     const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
-    TORCH_CHECK(key.size(0) == B && key.size(3) == D && value.sizes() == key.sizes() && Hkv > 0 && H % Hkv == 0 && keys > 0 &&
-                    keys <= key.size(2) && T > 0,
-                "prefill_attention: shape mismatch");
+    TORCH_CHECK(T > 0, "prefill_attention: shape mismatch");
     TORCH_CHECK(prefill_attention_supported(D), "prefill_attention: unsupported head_dim");
-    const double sc  = scaling ? *scaling : 1.0 / std::sqrt((double)D);
     const int64_t off = causal_offset ? *causal_offset : keys - T;
     const int64_t* starts = kv_start_ptr("prefill_attention", kv_start, query, B);
     const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0 || starts;
-    int64_t      splits = 1;
-    Tensor       ws;
-    if (dev_form) {
+    if (dev_form)
         TORCH_CHECK(!(kv_len && causal_offset), "prefill_attention: kv_len and causal_offset exclude each other (with kv_len the offset is "
                                                 "the device length minus the query rows)");
-        TORCH_CHECK(kv_len || kv_len_bias == 0, "prefill_attention: kv_len_bias needs kv_len");
-        if (kv_len)
-            TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(),
-                        "prefill_attention: kv_len must be a one-element int64 tensor on the query's device");
-        splits = splits_in ? *splits_in : prefill_attention_splits(B, H, T, keys);
-        TORCH_CHECK(splits >= 1 && splits <= eetq_prefill_attention_max_splits(), "prefill_attention: splits must lie in 1 .. ",
-                    eetq_prefill_attention_max_splits());
-        const int64_t need = (int64_t)eetq_prefill_attention_workspace_floats((int)B, (int)H, (int)T, (int)D, (int)splits);
-        if (workspace) {
-            TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
-                            workspace->numel() >= need,
-                        "prefill_attention: workspace must be a contiguous float32 tensor of at least ", need,
-                        " elements on the query's device");
-            ws = *workspace;
-        } else if (need > 0) {
-            ws = torch::empty({need}, query.options().dtype(at::kFloat));
-        }
-    }
-    Tensor       out = torch::empty({B, T, H, D}, query.options());
-    const long   st[12] = {(long)query.stride(0), (long)query.stride(1), (long)query.stride(2), (long)key.stride(0), (long)key.stride(1),
-                           (long)key.stride(2),   (long)value.stride(0), (long)value.stride(1), (long)value.stride(2),
-                           (long)out.stride(0),   (long)out.stride(1),   (long)out.stride(2)};
+    const PromptAttnPrep p("prefill_attention: ", query, key, value, keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
+                           prefill_splits_rule, eetq_prefill_attention_max_splits, eetq_prefill_attention_workspace_floats, false, dev_form);
     c10::DeviceGuard guard(query.device());
     if (starts) {   // the per-row first key: always the device-length entry (kv_len None: `keys` keys, the fresh prompt)
         TORCH_CHECK(off == keys - T, "prefill_attention: kv_start takes causal_offset = keys - query rows only");
-        check(eetq_prefill_attention_padded_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(),
-                                                ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)keys,
-                                                (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, starts,
-                                                (int)splits, (float)sc, st, stream_of(query)));
-        return out;
+        check(eetq_prefill_attention_padded_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
+                                                (int)H, (int)Hkv, (int)T, (int)keys, (int)D, p.kv_len, (int)kv_len_bias, starts,
+                                                (int)p.splits, p.sc, p.st, stream_of(query)));
+        return p.out;
     }
-    if (kv_len || splits > 1) {
+    if (kv_len || p.splits > 1) {
         TORCH_CHECK(kv_len || off == keys - T, "prefill_attention: the split form takes causal_offset = keys - query rows only");
-        check(eetq_prefill_attention_dev_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(),
-                                             ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)keys,
-                                             (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, (int)splits,
-                                             (float)sc, st, stream_of(query)));
-        return out;
+        check(eetq_prefill_attention_dev_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
+                                             (int)H, (int)Hkv, (int)T, (int)keys, (int)D, p.kv_len, (int)kv_len_bias, (int)p.splits, p.sc,
+                                             p.st, stream_of(query)));
+        return p.out;
     }
-    check(eetq_prefill_attention_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), (int)B, (int)H, (int)Hkv, (int)T,
-                                     (int)keys, (int)D, (int)off, (float)sc, st, stream_of(query)));
-    return out;
+    check(eetq_prefill_attention_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), (int)B, (int)H, (int)Hkv, (int)T,
+                                     (int)keys, (int)D, (int)off, p.sc, p.st, stream_of(query)));
+    return p.out;
 }
 
 // 1 .. 16 query rows behind a long cache, split-KV on the matrix cores (eetq_decode_attention_rows_f16): query [B, R, H, D] (any row /
-// head strides, D dense), cache views [B, Hkv, rows >= keys, D]; returns [B, R, H, D] contiguous.  The tensor checks and the device
-// guard are prefill_attention's; splits: None = the library's rule, workspace: None = allocated here (capturable, nothing persistent)
+// head strides, D dense), cache views [B, Hkv, rows >= keys, D]; returns [B, R, H, D] contiguous.  The tensor checks and the
+// preparation are prefill_attention's; splits: None = the library's rule, workspace: None = allocated here (capturable, nothing persistent)
 int64_t decode_attention_rows_splits(int64_t batch, int64_t heads, int64_t kv_heads, int64_t rows, int64_t max_keys)
 {
     return eetq_decode_attention_rows_splits((int)batch, (int)heads, (int)kv_heads, (int)rows, (int)max_keys);
@@ -351,43 +380,19 @@ int64_t decode_attention_rows_splits(int64_t batch, int64_t heads, int64_t kv_he
 Tensor decode_attention_rows(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
                              const OptTensor& kv_len, int64_t kv_len_bias, std::optional<int64_t> splits_in, const OptTensor& workspace)
 {
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
-        TORCH_CHECK(t->scalar_type() == at::kHalf && t->is_cuda() && t->dim() == 4 && t->stride(-1) == 1 && t->device() == query.device(),
-                    "decode_attention_rows: float16 CUDA tensors [B, R, H, D] / [B, Hkv, S, D] with a dense last dimension expected");
+    check_prompt_qkv("decode_attention_rows: ", 'R', query, key, value, keys);
     const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
-    TORCH_CHECK(key.size(0) == B && key.size(3) == D && value.sizes() == key.sizes() && Hkv > 0 && H % Hkv == 0 && keys > 0 &&
-                    keys <= key.size(2) && B > 0,
-                "decode_attention_rows: shape mismatch");
+    TORCH_CHECK(B > 0, "decode_attention_rows: shape mismatch");
     TORCH_CHECK(R >= 1 && R <= 16, "decode_attention_rows: 1 .. 16 query rows per batch row (got ", R, ")");
     TORCH_CHECK(D == 64 || D == 128, "decode_attention_rows: unsupported head_dim");
-    TORCH_CHECK(kv_len || kv_len_bias == 0, "decode_attention_rows: kv_len_bias needs kv_len");
-    if (kv_len)
-        TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(),
-                    "decode_attention_rows: kv_len must be a one-element int64 tensor on the query's device");
-    const double  sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    const int64_t splits = splits_in ? *splits_in : decode_attention_rows_splits(B, H, Hkv, R, keys);
-    TORCH_CHECK(splits >= 1 && splits <= eetq_decode_attention_rows_max_splits(), "decode_attention_rows: splits must lie in 1 .. ",
-                eetq_decode_attention_rows_max_splits());
-    const int64_t need = (int64_t)eetq_decode_attention_rows_workspace_floats((int)B, (int)H, (int)R, (int)D, (int)splits);
-    Tensor        ws;
-    if (workspace) {
-        TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
-                        workspace->numel() >= need,
-                    "decode_attention_rows: workspace must be a contiguous float32 tensor of at least ", need,
-                    " elements on the query's device");
-        ws = *workspace;
-    } else {
-        ws = torch::empty({need}, query.options().dtype(at::kFloat));
-    }
-    Tensor     out = torch::empty({B, R, H, D}, query.options());
-    const long st[12] = {(long)query.stride(0), (long)query.stride(1), (long)query.stride(2), (long)key.stride(0), (long)key.stride(1),
-                         (long)key.stride(2),   (long)value.stride(0), (long)value.stride(1), (long)value.stride(2),
-                         (long)out.stride(0),   (long)out.stride(1),   (long)out.stride(2)};
+    const PromptAttnPrep p("decode_attention_rows: ", query, key, value, keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
+                           eetq_decode_attention_rows_splits, eetq_decode_attention_rows_max_splits,
+                           eetq_decode_attention_rows_workspace_floats, true);
     c10::DeviceGuard guard(query.device());
-    check(eetq_decode_attention_rows_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), out.data_ptr(), ws.data_ptr<float>(), (int)B,
-                                         (int)H, (int)Hkv, (int)R, (int)keys, (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr,
-                                         (int)kv_len_bias, (int)splits, (float)sc, st, stream_of(query)));
-    return out;
+    check(eetq_decode_attention_rows_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B, (int)H,
+                                         (int)Hkv, (int)R, (int)keys, (int)D, p.kv_len, (int)kv_len_bias, (int)p.splits, p.sc, p.st,
+                                         stream_of(query)));
+    return p.out;
 }
 
 Tensor silu_mul(const Tensor& gate_up, bool glu8 = false);
@@ -823,6 +828,52 @@ void rotary_embedding_neox_kvcache(const Tensor& positions, Tensor& query, const
                                                (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2), stream_of(query)));
 }
 
+// What the two cache-writing prompt rotary operators prepare alike: the float16 and device checks (f16_caches: of the caches as well),
+// positions, the 4-D shapes, first_row / first_row_dev, the one-token-stride rule and the six strides.  cache_check(B, Hkv, D) is the
+// form's own check of its caches; name: "operator: "
+struct RotaryPrefillPrep {
+    int64_t        B, T, H, Hkv;
+    const int64_t* first_row_dev = nullptr;
+    long           strides[6];
+};
+template <class CacheCheck>
+RotaryPrefillPrep rotary_prefill_prep(const char* name, bool f16_caches, const Tensor& positions, const Tensor& query, const Tensor& key,
+                                      const Tensor& value, int64_t head_size, const Tensor& cos_sin_cache, const Tensor& key_cache,
+                                      const Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev, CacheCheck cache_check)
+{
+    const Tensor* halves[6] = {&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache};
+    for (int i = 0; i < (f16_caches ? 6 : 4); ++i) {
+        TORCH_CHECK(halves[i]->scalar_type() == at::kHalf, name,
+                    f16_caches ? "float16 tensors expected" : "float16 query, key, value and cos|sin table expected");
+        TORCH_CHECK(halves[i]->is_cuda() && halves[i]->device() == query.device(), name, "all tensors must be on one CUDA device");
+    }
+    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous() && positions.device() == query.device(), name,
+                "positions must be contiguous int64 on the device");
+    TORCH_CHECK(query.dim() == 4 && key.dim() == 4 && value.dim() == 4 && key_cache.dim() == 4, name, "shape mismatch");
+    RotaryPrefillPrep p;
+    p.B = query.size(0), p.T = query.size(1), p.H = query.size(2), p.Hkv = key.size(2);
+    const int64_t B = p.B, T = p.T, D = query.size(3);
+    cache_check(B, p.Hkv, D);
+    TORCH_CHECK(key.size(0) == B && key.size(1) == T && key.size(3) == D && value.sizes() == key.sizes() && D == head_size &&
+                    value_cache.strides() == key_cache.strides() && positions.numel() == B * T && first_row >= 0 &&
+                    (first_row_dev || first_row + T <= key_cache.size(2)),
+                name, "shape mismatch");
+    if (first_row_dev) {
+        TORCH_CHECK(first_row_dev->scalar_type() == at::kLong && first_row_dev->numel() == 1 &&
+                        first_row_dev->device() == query.device(),
+                    name, "first_row_dev must be one int64 on the device");
+        p.first_row_dev = first_row_dev->data_ptr<int64_t>();
+    }
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D && (B == 1 || T == 1 || t->stride(0) == T * t->stride(1)), name,
+                    "[heads, head_size] must be dense and the tokens of all rows one stride apart");
+    const int tdim = T == 1 ? 0 : 1;  // (a size-1 dimension's stride is arbitrary)
+    TORCH_CHECK((!f16_caches || key_cache.stride(-1) == 1) && cos_sin_cache.is_contiguous(), name,
+                f16_caches ? "cache rows must be dense" : "the cos|sin table must be contiguous");
+    for (int i = 0; i < 3; ++i) p.strides[i] = (long)halves[i]->stride(tdim), p.strides[3 + i] = (long)key_cache.stride(i);
+    return p;
+}
+
 // Prefill on a pre-allocated KV cache (extension): query [B, T, H, D] rotated in place, key [B, T, Hkv, D] rotated into
 // key_cache[b, :, base + t], value copied to value_cache[b, :, base + t], base = first_row_dev (device int64) or first_row:
 // eetq_rotary_neox_kvcache_prefill_f16
@@ -831,36 +882,17 @@ void rotary_embedding_neox_kvcache_prefill(const Tensor& positions, Tensor& quer
                                            Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev)
 {
     const char* name = "rotary_embedding_neox_kvcache_prefill: ";
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache}) {
-        TORCH_CHECK(t->scalar_type() == at::kHalf, name, "float16 tensors expected");
-        TORCH_CHECK(t->is_cuda() && t->device() == query.device(), name, "all tensors must be on one CUDA device");
-    }
-    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous() && positions.device() == query.device(),
-                name, "positions must be contiguous int64 on the device");
-    TORCH_CHECK(query.dim() == 4 && key.dim() == 4 && value.dim() == 4 && key_cache.dim() == 4, name, "shape mismatch");
-    const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(2);
-    TORCH_CHECK(key.size(0) == B && key.size(1) == T && key.size(3) == D && value.sizes() == key.sizes() && D == head_size &&
-                    key_cache.size(0) == B && key_cache.size(1) == Hkv && key_cache.size(3) == D &&
-                    value_cache.sizes() == key_cache.sizes() && value_cache.strides() == key_cache.strides() &&
-                    positions.numel() == B * T && first_row >= 0 && (first_row_dev || first_row + T <= key_cache.size(2)),
-                name, "shape mismatch");
-    if (first_row_dev)
-        TORCH_CHECK(first_row_dev->scalar_type() == at::kLong && first_row_dev->numel() == 1 &&
-                        first_row_dev->device() == query.device(),
-                    name, "first_row_dev must be one int64 on the device");
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
-        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D && (B == 1 || T == 1 || t->stride(0) == T * t->stride(1)), name,
-                    "[heads, head_size] must be dense and the tokens of all rows one stride apart");
-    const int tdim = T == 1 ? 0 : 1;  // (a size-1 dimension's stride is arbitrary)
-    TORCH_CHECK(key_cache.stride(-1) == 1 && cos_sin_cache.is_contiguous(), name, "cache rows must be dense");
-    const long strides[6] = {(long)query.stride(tdim), (long)key.stride(tdim), (long)value.stride(tdim), (long)key_cache.stride(0),
-                             (long)key_cache.stride(1), (long)key_cache.stride(2)};
+    const auto  p    = rotary_prefill_prep(name, true, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row,
+                                           first_row_dev, [&](int64_t B, int64_t Hkv, int64_t D) {
+                                           TORCH_CHECK(key_cache.size(0) == B && key_cache.size(1) == Hkv && key_cache.size(3) == D &&
+                                                           value_cache.sizes() == key_cache.sizes(),
+                                                       name, "shape mismatch");
+                                       });
     c10::DeviceGuard guard(query.device());
     check(eetq_rotary_neox_kvcache_prefill_bounded_f16(
         positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
-        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)B, (int)T,
-        first_row_dev ? first_row_dev->data_ptr<int64_t>() : nullptr, (int)first_row, (int)H, (int)Hkv, (int)head_size,
-        (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2), stream_of(query)));
+        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)p.B, (int)p.T, p.first_row_dev, (int)first_row,
+        (int)p.H, (int)p.Hkv, (int)head_size, (int)cos_sin_cache.size(1), p.strides, (int)key_cache.size(2), stream_of(query)));
 }
 
 // Greedy decode hand-over (extension): argmax of logits [B, V] (fp16, dense rows) -> out_tokens[:, column] and next_token, then
@@ -1087,36 +1119,14 @@ Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, cons
     check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
     TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && T > 0 && max_keys > 0 && max_keys <= key_cache.size(2), name, "shape mismatch");
     TORCH_CHECK(prefill_attention_supported(D), name, "unsupported head_dim");
-    TORCH_CHECK(kv_len || kv_len_bias == 0, name, "kv_len_bias needs kv_len");
-    if (kv_len)
-        TORCH_CHECK(kv_len->scalar_type() == at::kLong && kv_len->numel() == 1 && kv_len->device() == query.device(), name,
-                    "kv_len must be a one-element int64 tensor on the query's device");
-    const double  sc     = scaling ? *scaling : 1.0 / std::sqrt((double)D);
-    const int64_t splits = splits_in ? *splits_in : prefill_attention_splits(B, H, T, max_keys);
-    TORCH_CHECK(splits >= 1 && splits <= eetq_prefill_attention_max_splits(), name, "splits must lie in 1 .. ",
-                eetq_prefill_attention_max_splits());
-    const int64_t need = (int64_t)eetq_prefill_attention_workspace_floats((int)B, (int)H, (int)T, (int)D, (int)splits);
-    Tensor        ws;
-    if (workspace) {
-        TORCH_CHECK(workspace->scalar_type() == at::kFloat && workspace->device() == query.device() && workspace->is_contiguous() &&
-                        workspace->numel() >= need,
-                    name, "workspace must be a contiguous float32 tensor of at least ", need, " elements on the query's device");
-        ws = *workspace;
-    } else if (need > 0) {
-        ws = torch::empty({need}, query.options().dtype(at::kFloat));
-    }
-    Tensor     out = torch::empty({B, T, H, D}, query.options());
-    const long st[12] = {(long)query.stride(0),       (long)query.stride(1),       (long)query.stride(2),     (long)key_cache.stride(0),
-                         (long)key_cache.stride(1),   (long)key_cache.stride(2),   (long)value_cache.stride(0),
-                         (long)value_cache.stride(1), (long)value_cache.stride(2), (long)out.stride(0),       (long)out.stride(1),
-                         (long)out.stride(2)};
+    const PromptAttnPrep p(name, query, key_cache, value_cache, max_keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
+                           prefill_splits_rule, eetq_prefill_attention_max_splits, eetq_prefill_attention_workspace_floats, false);
     const long sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
     c10::DeviceGuard guard(query.device());
-    check(eetq_prefill_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), out.data_ptr(),
-                                          ws.defined() ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)Hkv, (int)T, (int)max_keys,
-                                          (int)D, kv_len ? kv_len->data_ptr<int64_t>() : nullptr, (int)kv_len_bias, (int)splits, (float)sc,
-                                          st, sst, stream_of(query)));
-    return out;
+    check(eetq_prefill_attention_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
+                                          p.out.data_ptr(), p.workspace(), (int)B, (int)H, (int)Hkv, (int)T, (int)max_keys, (int)D, p.kv_len,
+                                          (int)kv_len_bias, (int)p.splits, p.sc, p.st, sst, stream_of(query)));
+    return p.out;
 }
 
 Tensor rope_decode_attention_i8kv(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
@@ -1162,37 +1172,17 @@ void rotary_embedding_neox_kvcache_prefill_i8(const Tensor& positions, Tensor& q
                                               Tensor& value_cache, Tensor& scales, int64_t first_row, const OptTensor& first_row_dev)
 {
     const char* name = "rotary_embedding_neox_kvcache_prefill_i8: ";
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache}) {
-        TORCH_CHECK(t->scalar_type() == at::kHalf, name, "float16 query, key, value and cos|sin table expected");
-        TORCH_CHECK(t->is_cuda() && t->device() == query.device(), name, "all tensors must be on one CUDA device");
-    }
-    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous() && positions.device() == query.device(), name,
-                "positions must be contiguous int64 on the device");
-    TORCH_CHECK(query.dim() == 4 && key.dim() == 4 && value.dim() == 4 && key_cache.dim() == 4, name, "shape mismatch");
-    const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(2);
-    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
-    TORCH_CHECK(key.size(0) == B && key.size(1) == T && key.size(3) == D && value.sizes() == key.sizes() && D == head_size &&
-                    value_cache.strides() == key_cache.strides() && positions.numel() == B * T && first_row >= 0 &&
-                    (first_row_dev || first_row + T <= key_cache.size(2)),
-                name, "shape mismatch");
-    if (first_row_dev)
-        TORCH_CHECK(first_row_dev->scalar_type() == at::kLong && first_row_dev->numel() == 1 &&
-                        first_row_dev->device() == query.device(),
-                    name, "first_row_dev must be one int64 on the device");
-    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
-        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D && (B == 1 || T == 1 || t->stride(0) == T * t->stride(1)), name,
-                    "[heads, head_size] must be dense and the tokens of all rows one stride apart");
-    const int tdim = T == 1 ? 0 : 1;  // (a size-1 dimension's stride is arbitrary)
-    TORCH_CHECK(cos_sin_cache.is_contiguous(), name, "the cos|sin table must be contiguous");
-    const long strides[6] = {(long)query.stride(tdim), (long)key.stride(tdim), (long)value.stride(tdim), (long)key_cache.stride(0),
-                             (long)key_cache.stride(1), (long)key_cache.stride(2)};
+    const auto  p    = rotary_prefill_prep(name, false, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row,
+                                           first_row_dev, [&](int64_t B, int64_t Hkv, int64_t D) {
+                                           check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+                                       });
     const long sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
     c10::DeviceGuard guard(query.device());
     check(eetq_rotary_neox_kvcache_prefill_i8_f16(
         positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
-        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), (int)B, (int)T,
-        first_row_dev ? first_row_dev->data_ptr<int64_t>() : nullptr, (int)first_row, (int)H, (int)Hkv, (int)head_size,
-        (int)cos_sin_cache.size(1), strides, sst, (int)key_cache.size(2), stream_of(query)));
+        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), (int)p.B, (int)p.T, p.first_row_dev,
+        (int)first_row, (int)p.H, (int)p.Hkv, (int)head_size, (int)cos_sin_cache.size(1), p.strides, sst, (int)key_cache.size(2),
+        stream_of(query)));
 }
 
 Tensor silu_mul(const Tensor& gate_up, bool glu8)

@@ -206,6 +206,10 @@ class _EETAttentionBase(nn.Module):
             raise RuntimeError("EETLlamaAttention: the int8 cache layer is not allocated (Int8StaticLayer.allocate)")
         return layer
 
+    def _mfma_prompt_ok(self, q, k, v):   # may this prompt go to the MFMA prompt kernel (ops.prefill_attention)?
+        return (self.mfma_prefill and ops.prefill_attention is not None and q.is_cuda and q.dtype == torch.float16
+                and ops.prefill_attention_supported(self.head_dim) and k.stride(-1) == 1 and v.stride(-1) == 1)
+
     def _int8_cache_forward(self, layer, q, k, v, positions, attention_mask, kwargs):
         """The attention of one forward on an int8 static cache: q [B, T, H, D], k / v [B, T, Hkv, D] (views into the
         projection output, q and k not rotated yet) -> [B, T, H * D].  A single token is one launch (rotation, quantising
@@ -268,7 +272,7 @@ class _EETAttentionBase(nn.Module):
         ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales)
         counter.fill_(q_len)
         kt, vt = k.transpose(1, 2), v.transpose(1, 2)     # [B, Hkv, T, D], strides (T W, D, W, 1): the rotated fp16 K, the V
-        if self.mfma_prefill and ops.prefill_attention is not None and ops.prefill_attention_supported(d):
+        if self._mfma_prompt_ok(q, kt, vt):
             out = ops.prefill_attention(q, kt, vt, q_len, scaling=self.scaling)
             return out.reshape(bsz, q_len, -1)
         out = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), kt, vt, is_causal=True, scale=self.scaling,
@@ -378,9 +382,7 @@ class _EETAttentionBase(nn.Module):
         if starts is not None:
             # a left-padded batch: the MFMA prompt kernel with the per-row first key, or an error -- every other path below would
             # attend the pads
-            if (cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False) or not self.mfma_prefill
-                    or ops.prefill_attention is None or not q.is_cuda or q.dtype != torch.float16
-                    or not ops.prefill_attention_supported(self.head_dim) or cached[0].stride(-1) != 1 or cached[1].stride(-1) != 1
+            if (cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False) or not self._mfma_prompt_ok(q, *cached[:2])
                     or not (getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False))):
                 raise ValueError("EETLlamaAttention: padded_static_batch needs the MFMA prompt kernel (float16 on the GPU, head "
                                  "size 64 or 128, mfma_prefill=True, the compiled operator module) on an initialised fp16 static "
@@ -400,9 +402,7 @@ class _EETAttentionBase(nn.Module):
                 out = ops.decode_attention_rows(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
                 return out.reshape(*input_shape, -1), None
             if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1
-                    and not kwargs.get("output_attentions", False) and self.mfma_prefill and ops.prefill_attention is not None
-                    and q.is_cuda and q.dtype == torch.float16 and ops.prefill_attention_supported(self.head_dim)
-                    and k.stride(-1) == 1 and v.stride(-1) == 1):
+                    and not kwargs.get("output_attentions", False) and self._mfma_prompt_ok(q, k, v)):
                 # promised: rows 0 .. counter - 1 are this sequence's tokens, the last T of them this prompt's -> the same kernel
                 # with the counter as its device length (the causal offset follows from it in the kernel)
                 out = ops.prefill_attention(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
@@ -410,8 +410,7 @@ class _EETAttentionBase(nn.Module):
             if (getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1 and not kwargs.get("output_attentions", False)):
                 # promised: the cache was empty and the prompt is unpadded -> causal attention over the T rows just written
                 t_len = q.shape[2]
-                if (self.mfma_prefill and ops.prefill_attention is not None and q.is_cuda and q.dtype == torch.float16
-                        and ops.prefill_attention_supported(self.head_dim) and k.stride(-1) == 1 and v.stride(-1) == 1):
+                if self._mfma_prompt_ok(q, k, v):
                     # the library's own flash kernel on the matrix cores: the strided query view of the QKV projection, the
                     # cache rows as they lie (ops.prefill_attention; 37 us per layer at 13B shapes against torch's 76)
                     out = ops.prefill_attention(q.transpose(1, 2), k, v, t_len, scaling=self.scaling)

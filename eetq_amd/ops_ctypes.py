@@ -885,17 +885,15 @@ def rotary_embedding_neox_kvcache(positions, query, key, value, head_size, cos_s
     return None
 
 
-@_eager_only
-def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
-                                          first_row=0, first_row_dev=None):
-    """Prefill on a pre-allocated KV cache: rotate ``query`` [B, T, H, D] in place by ``positions`` [B, T] (int64), write the
-    rotated ``key`` [B, T, Hkv, D] and ``value`` into the caches [B, Hkv, S, D] at rows ``base + t``, base = ``first_row_dev``
-    (one int64 on the device, e.g. a static cache's token counter; read, not advanced) or ``first_row``.  One launch instead
-    of rotary + two index_copy launches and their index arithmetic (eetq_rotary_neox_kvcache_prefill_f16)."""
-    name = "rotary_embedding_neox_kvcache_prefill: "
-    for t in (query, key, value, cos_sin_cache, key_cache, value_cache):
+def _rotary_prefill_prep(name, f16_caches, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
+                         first_row, first_row_dev, cache_check):
+    """What the two cache-writing prompt rotary operators prepare alike (``name``: "operator: "): the float16 and device checks
+    (``f16_caches``: of the caches as well), positions, the 4-D shapes, ``first_row`` / ``first_row_dev``, the one-token-stride
+    rule and the six strides.  ``cache_check(B, Hkv, D)`` is the form's own check of its caches.  -> (B, T, H, Hkv, strides)"""
+    for t in (query, key, value, cos_sin_cache) + ((key_cache, value_cache) if f16_caches else ()):
         if t.dtype != torch.float16:
-            raise RuntimeError(name + "float16 tensors expected")
+            raise RuntimeError(name + ("float16 tensors expected" if f16_caches
+                                       else "float16 query, key, value and cos|sin table expected"))
         if not t.is_cuda or t.device != query.device:
             raise RuntimeError(name + "all tensors must be on one CUDA device")
     if positions.dtype != torch.int64 or not positions.is_contiguous() or positions.device != query.device:
@@ -904,8 +902,8 @@ def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_siz
         raise RuntimeError(name + "shape mismatch")
     B, T, H, D = query.shape
     Hkv = key.shape[2]
-    if (key.shape != (B, T, Hkv, D) or value.shape != key.shape or D != head_size or key_cache.shape[0] != B
-            or key_cache.shape[1] != Hkv or key_cache.shape[3] != D or value_cache.shape != key_cache.shape
+    cache_check(B, Hkv, D)
+    if (key.shape != (B, T, Hkv, D) or value.shape != key.shape or D != head_size
             or value_cache.stride() != key_cache.stride() or positions.numel() != B * T or first_row < 0
             or (first_row_dev is None and first_row + T > key_cache.shape[2])):
         raise RuntimeError(name + "shape mismatch")
@@ -916,15 +914,33 @@ def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_siz
         if t.stride(-1) != 1 or t.stride(-2) != D or (B != 1 and T != 1 and t.stride(0) != T * t.stride(1)):
             raise RuntimeError(name + "[heads, head_size] must be dense and the tokens of all rows one stride apart")
     tdim = 0 if T == 1 else 1   # (a size-1 dimension's stride is arbitrary)
-    if key_cache.stride(-1) != 1 or not cos_sin_cache.is_contiguous():
-        raise RuntimeError(name + "cache rows must be dense")
+    if (f16_caches and key_cache.stride(-1) != 1) or not cos_sin_cache.is_contiguous():
+        raise RuntimeError(name + ("cache rows must be dense" if f16_caches else "the cos|sin table must be contiguous"))
     strides = (ctypes.c_long * 6)(query.stride(tdim), key.stride(tdim), value.stride(tdim), key_cache.stride(0),
                                   key_cache.stride(1), key_cache.stride(2))
+    return B, T, H, Hkv, strides
+
+
+@_eager_only
+def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
+                                          first_row=0, first_row_dev=None):
+    """Prefill on a pre-allocated KV cache: rotate ``query`` [B, T, H, D] in place by ``positions`` [B, T] (int64), write the
+    rotated ``key`` [B, T, Hkv, D] and ``value`` into the caches [B, Hkv, S, D] at rows ``base + t``, base = ``first_row_dev``
+    (one int64 on the device, e.g. a static cache's token counter; read, not advanced) or ``first_row``.  One launch instead
+    of rotary + two index_copy launches and their index arithmetic (eetq_rotary_neox_kvcache_prefill_f16)."""
+    name = "rotary_embedding_neox_kvcache_prefill: "
+
+    def cache_check(B, Hkv, D):
+        if (key_cache.shape[0] != B or key_cache.shape[1] != Hkv or key_cache.shape[3] != D
+                or value_cache.shape != key_cache.shape):
+            raise RuntimeError(name + "shape mismatch")
+    B, T, H, Hkv, strides = _rotary_prefill_prep(name, True, positions, query, key, value, head_size, cos_sin_cache, key_cache,
+                                                 value_cache, first_row, first_row_dev, cache_check)
     with torch.cuda.device(query.device):
         check(_lib.lib().eetq_rotary_neox_kvcache_prefill_bounded_f16(
             _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
-            _ptr(value_cache), B, T, _ptr(first_row_dev) if first_row_dev is not None else None, int(first_row), H, Hkv,
-            int(head_size), cos_sin_cache.shape[1], strides, key_cache.shape[2], _stream_ptr()))
+            _ptr(value_cache), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size), cos_sin_cache.shape[1], strides,
+            key_cache.shape[2], _stream_ptr()))
     return None
 
 
@@ -1016,39 +1032,15 @@ def rotary_embedding_neox_kvcache_prefill_i8(positions, query, key, value, head_
     ``first_row_dev`` = the cache's counter it is the cache write of an unfused decode step
     (eetq_rotary_neox_kvcache_prefill_i8_f16)."""
     name = "rotary_embedding_neox_kvcache_prefill_i8: "
-    for t in (query, key, value, cos_sin_cache):
-        if t.dtype != torch.float16:
-            raise RuntimeError(name + "float16 query, key, value and cos|sin table expected")
-        if not t.is_cuda or t.device != query.device:
-            raise RuntimeError(name + "all tensors must be on one CUDA device")
-    if positions.dtype != torch.int64 or not positions.is_contiguous() or positions.device != query.device:
-        raise RuntimeError(name + "positions must be contiguous int64 on the device")
-    if query.dim() != 4 or key.dim() != 4 or value.dim() != 4 or key_cache.dim() != 4:
-        raise RuntimeError(name + "shape mismatch")
-    B, T, H, D = query.shape
-    Hkv = key.shape[2]
-    _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
-    if (key.shape != (B, T, Hkv, D) or value.shape != key.shape or D != head_size
-            or value_cache.stride() != key_cache.stride() or positions.numel() != B * T or first_row < 0
-            or (first_row_dev is None and first_row + T > key_cache.shape[2])):
-        raise RuntimeError(name + "shape mismatch")
-    if first_row_dev is not None and (first_row_dev.dtype != torch.int64 or first_row_dev.numel() != 1
-                                      or first_row_dev.device != query.device):
-        raise RuntimeError(name + "first_row_dev must be one int64 on the device")
-    for t in (query, key, value):
-        if t.stride(-1) != 1 or t.stride(-2) != D or (B != 1 and T != 1 and t.stride(0) != T * t.stride(1)):
-            raise RuntimeError(name + "[heads, head_size] must be dense and the tokens of all rows one stride apart")
-    tdim = 0 if T == 1 else 1   # (a size-1 dimension's stride is arbitrary)
-    if not cos_sin_cache.is_contiguous():
-        raise RuntimeError(name + "the cos|sin table must be contiguous")
-    strides = (ctypes.c_long * 6)(query.stride(tdim), key.stride(tdim), value.stride(tdim), key_cache.stride(0),
-                                  key_cache.stride(1), key_cache.stride(2))
+    B, T, H, Hkv, strides = _rotary_prefill_prep(
+        name, False, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row, first_row_dev,
+        lambda B, Hkv, D: _i8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D))
     sst = (ctypes.c_long * 3)(scales.stride(0), scales.stride(1), scales.stride(2))
     with torch.cuda.device(query.device):
         check(_lib.lib().eetq_rotary_neox_kvcache_prefill_i8_f16(
             _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
-            _ptr(value_cache), _ptr(scales), B, T, _ptr(first_row_dev) if first_row_dev is not None else None, int(first_row), H,
-            Hkv, int(head_size), cos_sin_cache.shape[1], strides, sst, key_cache.shape[2], _stream_ptr()))
+            _ptr(value_cache), _ptr(scales), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size),
+            cos_sin_cache.shape[1], strides, sst, key_cache.shape[2], _stream_ptr()))
     return None
 
 

@@ -2,7 +2,10 @@
 
 The shape is tiny (K = 64, N = 16, M = 1: a ~2 us kernel) and the queue is drained only at the end, so the loop is bound by
 the host side of a call: argument checks, output allocation, stream lookup, the launch itself.  Also times the bare
-launch floor (an empty kernel through ctypes, no tensors) and W8A16Linear.forward.  usage: python tools/host_overhead.py"""
+launch floor (an empty kernel through ctypes, no tensors) and W8A16Linear.forward.  usage: python tools/host_overhead.py
+
+--prompt: the prompt-side operators instead (the three prompt-shaped attention operators, the two cache-writing rotary prompt
+operators in both bindings) at B = 2, H = 4 on 2 kv heads, D = 64, T = 3 behind 8 cache rows."""
 import ctypes
 import json
 import os
@@ -29,7 +32,34 @@ def per_call(fn, n=20000):
     return best * 1e6
 
 
+def prompt():
+    from eetq_amd import _ext, ops_ctypes
+    ext = _ext.load()
+    dev, (B, H, HKV, D, T, S) = "cuda:0", (2, 4, 2, 64, 3, 8)
+    half = lambda *shape: torch.zeros(shape, dtype=torch.float16, device=dev)   # noqa: E731
+    q, k, v, kc, vc, table = half(B, T, H, D), half(B, T, HKV, D), half(B, T, HKV, D), half(B, HKV, S, D), half(B, HKV, S, D), half(16, D)
+    kc8, vc8, scales = kc.to(torch.int8), vc.to(torch.int8), half(B, HKV, S, 2)
+    pos = torch.zeros(B, T, dtype=torch.int64, device=dev)
+    n = torch.tensor([S], dtype=torch.int64, device=dev)      # the device length
+    row = torch.tensor([1], dtype=torch.int64, device=dev)    # the device first row
+    out = {
+        "ext.prefill_attention (host form)": per_call(lambda: ext.prefill_attention(q, kc, vc, S)),
+        "ext.prefill_attention (kv_len)": per_call(lambda: ext.prefill_attention(q, kc, vc, S, kv_len=n)),
+        "ext.prefill_attention_i8kv (kv_len)": per_call(lambda: ext.prefill_attention_i8kv(q, kc8, vc8, scales, S, kv_len=n)),
+        "ext.decode_attention_rows (kv_len)": per_call(lambda: ext.decode_attention_rows(q, kc, vc, S, kv_len=n)),
+    }
+    for name, mod in (("ext", ext), ("ctypes", ops_ctypes)):
+        out[name + ".rotary_embedding_neox_kvcache_prefill"] = per_call(
+            lambda: mod.rotary_embedding_neox_kvcache_prefill(pos, q, k, v, D, table, kc, vc, first_row_dev=row))
+        out[name + ".rotary_embedding_neox_kvcache_prefill_i8"] = per_call(
+            lambda: mod.rotary_embedding_neox_kvcache_prefill_i8(pos, q, k, v, D, table, kc8, vc8, scales, first_row_dev=row))
+    print(json.dumps({"what": "host microseconds per call, prompt-side operators, B=2 H=4/2 D=64 T=3 S=8, queue drained at the end",
+                      **{k: round(v, 2) for k, v in out.items()}}))
+
+
 def main():
+    if "--prompt" in sys.argv[1:]:
+        return prompt()
     from eetq_amd import _ext, _lib, ops_ctypes
     from eetq_amd.modules.qlinear import W8A16Linear
     ext = _ext.load()
