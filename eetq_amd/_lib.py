@@ -127,6 +127,8 @@ def _declare(L):
         "eetq_prefill_attention_max_splits": [],
         "eetq_decode_attention_splits": [i32, i32, i32],
         "eetq_decode_attention_rows_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp],
+        "eetq_decode_attention_rows_i8kv_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp,
+                                                vp, vp],
         "eetq_decode_attention_rows_splits": [i32, i32, i32, i32, i32],
         "eetq_decode_attention_rows_max_splits": [],
         "eetq_prof_begin": [i32],
@@ -201,7 +203,7 @@ EXPORTED_SYMBOLS = (
     "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
     "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16", "eetq_spec_sample_accept_f16",
     "eetq_decode_attention_rows_f16", "eetq_decode_attention_rows_splits", "eetq_decode_attention_rows_max_splits",
-    "eetq_decode_attention_rows_workspace_floats",
+    "eetq_decode_attention_rows_workspace_floats", "eetq_decode_attention_rows_i8kv_f16",
 )
 
 

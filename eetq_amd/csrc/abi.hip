@@ -1061,6 +1061,17 @@ int eetq_prefill_attention_i8kv_f16(const void* q, const void* k_cache_i8, const
                                          kv_len_bias, splits, scaling, strides, scale_strides, static_cast<hipStream_t>(stream));
 }
 
+int eetq_decode_attention_rows_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales, void* out,
+                                        float* workspace, int batch, int heads, int kv_heads, int rows, int max_keys, int head_dim,
+                                        const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* strides,
+                                        const long* scale_strides, void* stream)
+{
+    return launch_decode_attention_rows_i8kv(static_cast<const f16*>(q), static_cast<const int8_t*>(k_cache_i8),
+                                             static_cast<const int8_t*>(v_cache_i8), static_cast<const f16*>(kv_scales),
+                                             static_cast<f16*>(out), workspace, batch, heads, kv_heads, rows, max_keys, head_dim, kv_len,
+                                             kv_len_bias, splits, scaling, strides, scale_strides, static_cast<hipStream_t>(stream));
+}
+
 int eetq_rotary_neox_kvcache_prefill_i8_f16(const int64_t* positions, void* query, void* key, const void* value,
                                             const void* cos_sin_cache, int table_rows, void* k_cache_i8, void* v_cache_i8,
                                             void* kv_scales, int batch, int tokens, const int64_t* first_row_dev, int first_row,

@@ -31,7 +31,20 @@
 //             record [m, l, -, -, o[D]] (kRecPad) -- an empty chunk or a row with nothing to attend in it (-inf, 0, zeros): the
 //             workspace's earlier contents never matter.  attn_rows_merge_kernel, a second launch, weights a row's records by
 //             exp2(m_i - max m) and divides once; a fully masked row gives zeros.  No tickets, no atomics, no state between launches.
+//
+// KV8 (the int8 row format of kv_i8.hpp; eetq_decode_attention_rows_i8kv_f16): the same work, chunks, blocks, sub-tiles, records and
+// merge over int8 rows, in the arithmetic of eetq_prefill_attention_i8kv_f16.  What changes is fetch, the A operand and stage:
+//   * a lane's share of a K row per k-step and of a V row per chunk is 8 BYTES (the same channels, strides in bytes), and lane l of a
+//     wave also loads the scale dword (k scale, v scale) of key l & 31 of the block through a third descriptor that ends at the valid
+//     length like the other two: a row at or beyond `keys` reads as bytes 0, scales 0, whatever memory holds there;
+//   * the K bytes become the A operand as exact fp16 integers (kv8_unpack8), once per block for all sub-tiles, and the K scale is
+//     folded into the fp32 score behind the product, per key, before the mask select: x = (ks * scaling log2 e) * (q . k8).  The eight
+//     scales of a lane's keys 4 (lane >> 4) + i of both 16-key groups come from the owning lanes by lane read (ds_bpermute);
+//   * a V row enters the transposed image as fp16(vs * v8): one packed fp16 multiply of the exact integer by the row's scale (read
+//     from the lane that holds the row's dword), one rounding of the exact product, denormals kept -- not vs riding on the
+//     probability.  The image, its pitch and the fragments read from it are the fp16 form's.
 #include "attn_decode_shared.hpp"
+#include "kv_i8.hpp"
 
 namespace eetq {
 
@@ -54,6 +67,14 @@ struct RowsArgs {
     int            kv_len_bias, max_keys, R, H, groups, ntg;
     float          c;        // scaling * log2(e)
 };
+// KV8: k and v point at int8 rows, their strides are in BYTES, and the rows' scale pairs lie in `scales`.  Behind the fp16 form's
+// arguments, which keep their kernarg block.
+struct RowsArgs8 : RowsArgs {
+    const f16* scales;
+    long       s_sb, s_sh, s_ss;   // fp16 elements between batch rows, kv heads, rows of the scale tensor
+};
+template <bool KV8>
+using RowsKernArgs = std::conditional_t<KV8, RowsArgs8, RowsArgs>;
 
 // the value of lane ^ 16 and lane ^ 32 folded in: every lane of a query column ends with the column's maximum / sum
 __device__ __forceinline__ float col_max(float v)
@@ -68,13 +89,13 @@ __device__ __forceinline__ float col_sum(float v)
 }
 
 // grid (splits, kv heads * ntg, batch)
-template <int D, int NSUB>
-__global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const RowsArgs a)
+template <int D, int NSUB, bool KV8 = false>
+__global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const RowsKernArgs<KV8> a)
 {
     static_assert(D == 128 || D == 64, "head_dim 128 or 64");
     constexpr int KS = D / 32;                      // k-steps of the score product
     constexpr int CT = D / 16;                      // 16-channel tiles of the output
-    constexpr int CH = D / 8;                       // 16-byte chunks per row
+    constexpr int CH = D / 8;                       // 16-byte chunks per row (KV8: 8-byte chunks, the same channels)
     constexpr int PG = 64 / CH;                     // lane groups of the V staging (4 or 8), four rows each
     constexpr int NQ = kRowsBlk / (4 * PG);         // quads of rows per lane (2 or 1)
     constexpr int REC = D + kRecPad;
@@ -112,16 +133,34 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
     }
 
     // ---- the valid rows of this (batch row, kv head) behind descriptors ----
-    const unsigned krow_b = (unsigned)(a.k_ss * 2), vrow_b = (unsigned)(a.v_ss * 2);
-    const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.k + b * a.k_sb + hk * a.k_sh), 0,
-                                                                         (int)((unsigned)keys * krow_b), 0x00020000);
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.v + b * a.v_sb + hk * a.v_sh), 0,
-                                                                         (int)((unsigned)keys * vrow_b), 0x00020000);
+    // (KV8: the same two with strides in bytes, and the rows' scale dwords behind a third one)
+    constexpr unsigned EB = KV8 ? 1u : 2u;     // bytes per unit of the cache strides and per channel
+    const unsigned krow_b = (unsigned)a.k_ss * EB, vrow_b = (unsigned)a.v_ss * EB;
+    using CacheElem = std::conditional_t<KV8, int8_t, f16>;
+    const CacheElem* kbase = reinterpret_cast<const CacheElem*>(a.k) + b * a.k_sb + hk * a.k_sh;
+    const CacheElem* vbase = reinterpret_cast<const CacheElem*>(a.v) + b * a.v_sb + hk * a.v_sh;
+    const __amdgpu_buffer_rsrc_t krs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<CacheElem*>(kbase), 0, (int)((unsigned)keys * krow_b), 0x00020000);
+    const __amdgpu_buffer_rsrc_t vrs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<CacheElem*>(vbase), 0, (int)((unsigned)keys * vrow_b), 0x00020000);
+    __amdgpu_buffer_rsrc_t srs = krs;          // fp16 rows: not used
+    unsigned               srow_b = 0;
+    if constexpr (KV8) {
+        srow_b = (unsigned)a.s_ss * 2u;
+        srs    = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.scales + b * a.s_sb + hk * a.s_sh), 0, (int)((unsigned)keys * srow_b),
+                                                   0x00020000);
+    }
     constexpr unsigned kNoRow = 0x80000000u;   // an offset beyond every descriptor (they span < 2 GiB; no 32-bit wrap): zeros, nothing read
 
-    u32x4     kc[2][KS], kn[2][KS], vreg[NQ][4];
+    using CacheReg = std::conditional_t<KV8, u32x2, u32x4>;   // a lane's 8 channels of one row
+    CacheReg  kc[2][KS], kn[2][KS], vreg[NQ][4];
+    u32       sc8 = 0u, sn8 = 0u;               // KV8: the scale dword of key (lane & 31) of the current / the next block
     const int vc = lane % CH, vp = lane / CH;   // V staging: chunk and row group of this lane
-    auto fetch = [&](u32x4 (&kd)[2][KS], int blk) {
+    auto load8 = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off) {
+        if constexpr (KV8) return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, kNt));
+        else return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, kNt));
+    };
+    auto fetch = [&](CacheReg (&kd)[2][KS], u32& sd, int blk) {
         const bool have = blk < j1;             // wave-uniform
         const unsigned key0 = (unsigned)blk * kRowsBlk;
 #pragma unroll
@@ -129,24 +168,42 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const unsigned row = key0 + 16 * kb + ln;
-                const unsigned off = have && row < (unsigned)keys ? row * krow_b + (32 * ks + 8 * g4) * 2 : kNoRow;
-                kd[kb][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, (int)off, 0, kNt));
+                const unsigned off = have && row < (unsigned)keys ? row * krow_b + (32 * ks + 8 * g4) * EB : kNoRow;
+                kd[kb][ks] = load8(krs, off);
             }
 #pragma unroll
         for (int qd = 0; qd < NQ; ++qd)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const unsigned row = key0 + qd * 4 * PG + 4 * vp + r;
-                const unsigned off = have && row < (unsigned)keys ? row * vrow_b + vc * 16 : kNoRow;
-                vreg[qd][r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, (int)off, 0, kNt));
+                const unsigned off = have && row < (unsigned)keys ? row * vrow_b + vc * 8 * EB : kNoRow;
+                vreg[qd][r] = load8(vrs, off);
             }
+        if constexpr (KV8) {
+            const unsigned row = key0 + (lane & 31);
+            sd = __builtin_amdgcn_raw_buffer_load_b32(srs, (int)(have && row < (unsigned)keys ? row * srow_b : kNoRow), 0, kNt);
+        }
     };
     f16* vt = reinterpret_cast<f16*>(lds_raw) + wave * VT_WAVE;   // this wave's image: [channel][32 keys]
-    auto stage = [&]() {
+    // a staged row's 8 channels as fp16; KV8: fp16(vs * v8), the row's scale from the lane that holds its dword (all lanes call)
+    auto vchunk = [&](int qd, int r, u32 sd) {
+        if constexpr (KV8) {
+            f16x2 h[4];
+            kv8_unpack8(vreg[qd][r], h);
+            const f16   vs  = as_f16x2((u32)__shfl((int)sd, qd * 4 * PG + 4 * vp + r, 64))[1];
+            const f16x2 vs2 = {vs, vs};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) h[i] = h[i] * vs2;   // one rounding of the exact product
+            return f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+        } else {
+            return __builtin_bit_cast(f16x8, vreg[qd][r]);
+        }
+    };
+    auto stage = [&](u32 sd) {
 #pragma unroll
         for (int qd = 0; qd < NQ; ++qd) {
-            const f16x8 v0 = __builtin_bit_cast(f16x8, vreg[qd][0]), v1 = __builtin_bit_cast(f16x8, vreg[qd][1]);
-            const f16x8 v2 = __builtin_bit_cast(f16x8, vreg[qd][2]), v3 = __builtin_bit_cast(f16x8, vreg[qd][3]);
+            const f16x8 v0 = vchunk(qd, 0, sd), v1 = vchunk(qd, 1, sd);
+            const f16x8 v2 = vchunk(qd, 2, sd), v3 = vchunk(qd, 3, sd);
             f16*        vw = vt + 8 * vc * kRowsVtPitch + qd * 4 * PG + 4 * vp;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -166,14 +223,14 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
     }
 
     if (trips > 0) {   // workgroup-uniform
-        fetch(kc, j0 + wave);
-        stage();
+        fetch(kc, sc8, j0 + wave);
+        stage(sc8);
     }
     __syncthreads();
     for (int it = 0; it < trips; ++it) {
         const int  blk  = j0 + it * kRowsWaves + wave;
         const bool next = it + 1 < trips;           // workgroup-uniform
-        if (next) fetch(kn, blk + kRowsWaves);      // V of block j goes to registers that `stage` has emptied
+        if (next) fetch(kn, sn8, blk + kRowsWaves);   // V of block j goes to registers that `stage` has emptied
         if (blk < j1) {                             // wave-uniform
             const int key0 = blk * kRowsBlk;
             // the image's fragments, shared by the sub-tiles: channels 16 ct + ln, keys 4 g4 .. + 3 and 16 + 4 g4 .. + 3
@@ -184,6 +241,27 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
                 const u32x2 lo = *reinterpret_cast<const u32x2*>(vr), hh = *reinterpret_cast<const u32x2*>(vr + 16);
                 vf[ct] = __builtin_bit_cast(f16x8, u32x4{lo.x, lo.y, hh.x, hh.y});
             }
+            // KV8: the block's A operands as exact integers, and the K scales of this lane's keys times scaling log2 e
+            f16x8 kf[KV8 ? 2 : 1][KV8 ? KS : 1];
+            float kx[8];
+            if constexpr (KV8) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        f16x2 h[4];
+                        kv8_unpack8(kc[kb][ks], h);
+                        kf[kb][ks] = f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        kx[4 * kb + i] = (float)as_f16x2((u32)__shfl((int)sc8, 16 * kb + 4 * g4 + i, 64))[0] * a.c;
+                }
+            }
+            auto kfrag = [&](int kb, int ks) {
+                if constexpr (KV8) return kf[kb][ks];
+                else return __builtin_bit_cast(f16x8, kc[kb][ks]);
+            };
 #pragma unroll
             for (int s = 0; s < NSUB; ++s) {
                 // ---- S^T = K Q^T: two 16-key groups ----
@@ -192,7 +270,7 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
                 for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
                     for (int kb = 0; kb < 2; ++kb)
-                        sc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kc[kb][ks]), qf[s][ks], sc[kb], 0, 0, 0);
+                        sc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kfrag(kb, ks), qf[s][ks], sc[kb], 0, 0, 0);
                 // ---- scaled scores, masked by select: key < keys and key <= koff + query row ----
                 const int lim = min(keys - 1, koff + qt[s]);
                 float     x[8], mloc = -INFINITY;
@@ -201,7 +279,10 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int key = key0 + 16 * kb + 4 * g4 + i;
-                        x[4 * kb + i] = key <= lim ? sc[kb][i] * a.c : -INFINITY;
+                        float xs;
+                        if constexpr (KV8) xs = kx[4 * kb + i] * sc[kb][i];
+                        else xs = sc[kb][i] * a.c;
+                        x[4 * kb + i] = key <= lim ? xs : -INFINITY;
                         mloc = fmaxf(mloc, x[4 * kb + i]);
                     }
                 mloc = col_max(mloc) - kAttnPShift;                          // the maxima are kept 12 below: p as 2^12 p
@@ -228,11 +309,12 @@ __global__ __launch_bounds__(kRowsThreads) void attn_rows_partial_kernel(const R
         }
         if (next) {
             __syncthreads();   // the image has been read
-            stage();
+            stage(sn8);
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) kc[kb][ks] = kn[kb][ks];
+            sc8 = sn8;
             __syncthreads();   // the next image is complete
         }
     }
@@ -313,16 +395,16 @@ __global__ __launch_bounds__(256) void attn_rows_merge_kernel(const float* __res
 
 int rows_tile_groups(int H, int Hkv, int R) { return (H / Hkv * R + 16 * kRowsMaxSub - 1) / (16 * kRowsMaxSub); }
 
-template <int D>
-int launch_rows_d(const RowsArgs& a, f16* out, int B, int Hkv, int splits, const long* st, hipStream_t stream)
+template <int D, bool KV8>
+int launch_rows_d(const RowsKernArgs<KV8>& a, f16* out, int B, int Hkv, int splits, const long* st, hipStream_t stream)
 {
     const dim3 grid((unsigned)splits, (unsigned)(Hkv * a.ntg), (unsigned)B), block(kRowsThreads);
     const int  nsub = a.ntg > 1 ? kRowsMaxSub : (a.groups * a.R + 15) / 16;
     switch (nsub) {
-    case 1: launch_kernel(attn_rows_partial_kernel<D, 1>, grid, block, 0, stream, a); break;
-    case 2: launch_kernel(attn_rows_partial_kernel<D, 2>, grid, block, 0, stream, a); break;
-    case 3: launch_kernel(attn_rows_partial_kernel<D, 3>, grid, block, 0, stream, a); break;
-    default: launch_kernel(attn_rows_partial_kernel<D, 4>, grid, block, 0, stream, a); break;
+    case 1: launch_kernel(attn_rows_partial_kernel<D, 1, KV8>, grid, block, 0, stream, a); break;
+    case 2: launch_kernel(attn_rows_partial_kernel<D, 2, KV8>, grid, block, 0, stream, a); break;
+    case 3: launch_kernel(attn_rows_partial_kernel<D, 3, KV8>, grid, block, 0, stream, a); break;
+    default: launch_kernel(attn_rows_partial_kernel<D, 4, KV8>, grid, block, 0, stream, a); break;
     }
     EETQ_TRY_HIP(hipGetLastError());
     const long rows = (long)B * a.H * a.R, threads = rows * (D / 4);
@@ -360,23 +442,26 @@ int decode_attention_rows_splits(int B, int H, int Hkv, int R, int max_keys)
     return (int)max(1L, min(32L, min(by_chip, by_len)));
 }
 
-// strides (elements): {q_b, q_row, q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b, out_row, out_head}
-int launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R, int max_keys,
-                                 int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
-                                 hipStream_t stream)
+namespace {
+
+// what both entries require of the call's shape, before any pointer is followed
+int check_rows_shape(int R, int max_keys, int splits, int B, int H, int Hkv, int D, const float* ws)
 {
-    EETQ_REQUIRE(q && k && v && out && st, "null pointer");
     EETQ_REQUIRE(R >= 1 && R <= kRowsMaxR, "rows must lie in 1 .. 16");
     EETQ_REQUIRE(max_keys > 0, "max_keys must be positive");
     EETQ_REQUIRE(splits >= 1 && splits <= kRowsMaxSplits, "splits must lie in 1 .. 64");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "invalid attention shape");
     if (D != 128 && D != 64) return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] few-row attention supports head_dim 64 and 128");
     EETQ_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "the workspace is always needed (two launches) and must be 16-byte aligned");
-    const int rc = check_attn_layout(q, k, v, out, max_keys, st);
-    if (rc != EETQ_OK) return rc;
-    // (its own: the row offsets here are unsigned, and kNoRow must lie beyond every row)
-    EETQ_REQUIRE(st[5] > 0 && st[8] > 0, "one head's cache rows must span less than 2 GiB");
-    RowsArgs a;
+    return EETQ_OK;
+}
+
+// the checked call's arguments into the kernels' block, and the two launches
+template <bool KV8>
+int launch_rows_checked(RowsKernArgs<KV8>& a, const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R,
+                        int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
+                        hipStream_t stream)
+{
     a.q = q, a.k = k, a.v = v, a.ws = ws;
     a.q_sb = st[0], a.q_st = st[1], a.q_sh = st[2], a.k_sb = st[3], a.k_sh = st[4], a.k_ss = st[5];
     a.v_sb = st[6], a.v_sh = st[7], a.v_ss = st[8];
@@ -385,8 +470,48 @@ int launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* 
     a.c = scaling * 1.4426950408889634f;
     EETQ_REQUIRE((long)Hkv * a.ntg <= 65535 && B <= 65535, "too many workgroups");
     EETQ_REQUIRE(((long)B * H * R * (D / 4) + 255) / 256 < (1L << 31), "too many workgroups");
-    if (D == 128) return launch_rows_d<128>(a, out, B, Hkv, splits, st, stream);
-    return launch_rows_d<64>(a, out, B, Hkv, splits, st, stream);
+    if (D == 128) return launch_rows_d<128, KV8>(a, out, B, Hkv, splits, st, stream);
+    return launch_rows_d<64, KV8>(a, out, B, Hkv, splits, st, stream);
+}
+
+}  // namespace
+
+// strides (elements): {q_b, q_row, q_head, k_b, k_head, k_row, v_b, v_head, v_row, out_b, out_row, out_head}
+int launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R, int max_keys,
+                                 int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
+                                 hipStream_t stream)
+{
+    EETQ_REQUIRE(q && k && v && out && st, "null pointer");
+    const int rcs = check_rows_shape(R, max_keys, splits, B, H, Hkv, D, ws);
+    if (rcs != EETQ_OK) return rcs;
+    const int rc = check_attn_layout(q, k, v, out, max_keys, st);
+    if (rc != EETQ_OK) return rc;
+    // (its own: the row offsets here are unsigned, and kNoRow must lie beyond every row)
+    EETQ_REQUIRE(st[5] > 0 && st[8] > 0, "one head's cache rows must span less than 2 GiB");
+    RowsArgs a;
+    return launch_rows_checked<false>(a, q, k, v, out, ws, B, H, Hkv, R, max_keys, D, kv_len, kv_len_bias, splits, scaling, st, stream);
+}
+
+// launch_decode_attention_rows over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of
+// the scale pairs in fp16 elements
+int launch_decode_attention_rows_i8kv(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, f16* out, float* ws, int B, int H,
+                                      int Hkv, int R, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits,
+                                      float scaling, const long* st, const long* sst, hipStream_t stream)
+{
+    EETQ_REQUIRE(q && k && v && scales && out && st && sst, "null pointer");
+    const int rc = check_rows_shape(R, max_keys, splits, B, H, Hkv, D, ws);
+    if (rc != EETQ_OK) return rc;
+    for (int i = 0; i < 3; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q strides must be multiples of 8 elements (16-byte loads)");
+    for (int i = 9; i < 12; ++i) EETQ_REQUIRE(st[i] % 4 == 0, "out strides must be multiples of 4 elements");
+    EETQ_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)out % 8 == 0, "q must be 16-byte aligned, out 8-byte");
+    const int rc8 = check_i8_cache(k, v, scales, max_keys, st + 3, sst);
+    if (rc8 != EETQ_OK) return rc8;
+    // (the descriptors end at keys * row stride: a row's last chunk must lie inside its own stride)
+    EETQ_REQUIRE(st[5] >= D && st[8] >= D, "an int8 cache row stride must hold head_dim bytes");
+    RowsArgs8 a;
+    a.scales = scales, a.s_sb = sst[0], a.s_sh = sst[1], a.s_ss = sst[2];
+    return launch_rows_checked<true>(a, q, reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v), out, ws, B, H, Hkv, R,
+                                     max_keys, D, kv_len, kv_len_bias, splits, scaling, st, stream);
 }
 
 }  // namespace eetq

@@ -355,6 +355,10 @@ int    check_attn_layout(const f16* q, const f16* k, const f16* v, const f16* ou
 int    launch_decode_attention_rows(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int R, int max_keys,
                                     int D, const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* st,
                                     hipStream_t stream);
+// the same over an int8 cache (kv_i8.hpp): k / v strides in bytes, sst {batch, head, row} of the scale pairs in fp16 elements
+int    launch_decode_attention_rows_i8kv(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, f16* out, float* ws, int B,
+                                         int H, int Hkv, int R, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits,
+                                         float scaling, const long* st, const long* sst, hipStream_t stream);
 int    decode_attention_rows_splits(int B, int H, int Hkv, int R, int max_keys);
 int    decode_attention_rows_max_splits();
 size_t decode_attention_rows_workspace_floats(int B, int H, int R, int D, int splits);

@@ -1129,6 +1129,31 @@ Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, cons
     return p.out;
 }
 
+// decode_attention_rows over an int8 cache (eetq_decode_attention_rows_i8kv_f16): query [B, R, H, D] (any row / head strides), R =
+// 1 .. 16, the first `max_keys` rows of the caches, or clamp(*kv_len + kv_len_bias, 0, max_keys) of them; [B, R, H, D] contiguous
+Tensor decode_attention_rows_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
+                                  int64_t max_keys, std::optional<double> scaling, const OptTensor& kv_len, int64_t kv_len_bias,
+                                  std::optional<int64_t> splits_in, const OptTensor& workspace)
+{
+    const char* name = "decode_attention_rows_i8kv: ";
+    TORCH_CHECK(query.scalar_type() == at::kHalf && query.is_cuda() && query.dim() == 4 && query.stride(-1) == 1 && key_cache.dim() == 4,
+                name, "expected a float16 CUDA query [B, R, H, D] with dense D");
+    const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3), Hkv = key_cache.size(1);
+    check_i8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(B > 0 && Hkv > 0 && H % Hkv == 0 && max_keys > 0 && max_keys <= key_cache.size(2), name, "shape mismatch");
+    TORCH_CHECK(R >= 1 && R <= 16, name, "1 .. 16 query rows per batch row (got ", R, ")");
+    TORCH_CHECK(D == 64 || D == 128, name, "unsupported head_dim");
+    const PromptAttnPrep p(name, query, key_cache, value_cache, max_keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
+                           eetq_decode_attention_rows_splits, eetq_decode_attention_rows_max_splits,
+                           eetq_decode_attention_rows_workspace_floats, true);
+    const long sst[3] = {(long)scales.stride(0), (long)scales.stride(1), (long)scales.stride(2)};
+    c10::DeviceGuard guard(query.device());
+    check(eetq_decode_attention_rows_i8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
+                                              p.out.data_ptr(), p.workspace(), (int)B, (int)H, (int)Hkv, (int)R, (int)max_keys, (int)D,
+                                              p.kv_len, (int)kv_len_bias, (int)p.splits, p.sc, p.st, sst, stream_of(query)));
+    return p.out;
+}
+
 Tensor rope_decode_attention_i8kv(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
                                   const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& scales,
                                   Tensor& tickets, const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
@@ -2083,6 +2108,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("workspace") = py::none(),
           "1 .. 16 query rows [B, R, H, D], the last rows of the first `keys` rows of a KV cache [B, Hkv, S, D], attending it causally "
           "(split-KV, MFMA)");
+    m.def("decode_attention_rows_i8kv", &decode_attention_rows_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
+          py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
+          "decode_attention_rows behind an int8 KV cache: 1 .. 16 query rows [B, R, H, D] over the dequantised first rows of the cache");
     m.def("decode_attention_rows_splits", &decode_attention_rows_splits, py::arg("batch"), py::arg("heads"), py::arg("kv_heads"),
           py::arg("rows"), py::arg("max_keys"), "the chunk count decode_attention_rows uses with splits=None");
     m.def("prefill_attention_supported", &prefill_attention_supported, py::arg("head_dim"));

@@ -42,7 +42,7 @@ def fresh_static_prefill():
 
 
 @contextlib.contextmanager
-def appended_static_prefill(int8_rows=False, few_rows=False):
+def appended_static_prefill(int8_rows=False, few_rows=False, few_rows_int8=False):
     """The caller's promise for the forwards run inside (per thread): the prompt is unpadded and the static cache's rows
     0 .. counter - 1 are this sequence's real tokens, so a prompt appended behind them attends exactly the rows below the
     advanced counter, causally among its own.  The attention blocks write the rows as they do without the promise (behind the
@@ -62,7 +62,21 @@ def appended_static_prefill(int8_rows=False, few_rows=False):
     of a kv head side by side, the cache streamed once by the whole chip -- instead of the prompt kernel's 128-row tiles
     (``GraphDecoder(spec_attention="rows")`` makes it for its verify steps).  Longer pieces and single tokens go where they go
     without it.  The kernel reads fp16 rows and knows one shared first key, so the flag together with ``int8_rows`` or under
-    ``padded_static_batch`` raises ``ValueError``."""
+    ``padded_static_batch`` raises ``ValueError``.
+
+    ``few_rows_int8=True`` (per thread, restored on exit) is the same promise on an INT8 cache and needs ``int8_rows=True``
+    (``ValueError`` without it): an appended piece of 2 .. 16 rows is written behind the device counter, quantised, the counter
+    advanced, and then attends the dequantised rows through ``ops.decode_attention_rows_i8kv(..., kv_len=counter)`` -- the few-row
+    kernel's int8-row form, in the arithmetic of ``ops.prefill_attention_i8kv`` (``GraphDecoder(speculative=k, kv_bits=8,
+    kv8_append=True, spec_attention="rows")`` makes it for its verify steps).  Longer pieces keep ``ops.prefill_attention_i8kv``,
+    single tokens the decode step; on an fp16 cache the flag changes nothing.  Under ``padded_static_batch`` it raises as
+    ``few_rows`` does."""
+    if few_rows_int8 and not int8_rows:
+        raise ValueError("appended_static_prefill: few_rows_int8 (ops.decode_attention_rows_i8kv) is a promise about an int8 cache; "
+                         "it needs int8_rows=True")
+    if few_rows_int8 and _padded_starts() is not None:
+        raise ValueError("appended_static_prefill: few_rows_int8 (ops.decode_attention_rows_i8kv) knows one shared first key only; it "
+                         "cannot run under padded_static_batch (a per-row first key)")
     if few_rows and int8_rows:
         raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) reads fp16 cache rows only; it cannot be "
                          "combined with int8_rows")
@@ -70,13 +84,15 @@ def appended_static_prefill(int8_rows=False, few_rows=False):
         raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) knows one shared first key only; it cannot "
                          "run under padded_static_batch (a per-row first key)")
     prev = (getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False),
-            getattr(_prefill_promise, "int8_rows", False), getattr(_prefill_promise, "few_rows", False))
+            getattr(_prefill_promise, "int8_rows", False), getattr(_prefill_promise, "few_rows", False),
+            getattr(_prefill_promise, "few_rows_int8", False))
     _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = True, False, bool(int8_rows)
-    _prefill_promise.few_rows = bool(few_rows)
+    _prefill_promise.few_rows, _prefill_promise.few_rows_int8 = bool(few_rows), bool(few_rows_int8)
     try:
         yield
     finally:
-        (_prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows, _prefill_promise.few_rows) = prev
+        (_prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows, _prefill_promise.few_rows,
+         _prefill_promise.few_rows_int8) = prev
 
 
 @contextlib.contextmanager
@@ -98,6 +114,9 @@ def padded_static_batch(starts):
     if starts is not None and getattr(_prefill_promise, "few_rows", False):
         raise ValueError("padded_static_batch: appended_static_prefill(few_rows=True) is in force, and ops.decode_attention_rows "
                          "knows one shared first key only (no per-row first key)")
+    if starts is not None and getattr(_prefill_promise, "few_rows_int8", False):
+        raise ValueError("padded_static_batch: appended_static_prefill(few_rows_int8=True) is in force, and "
+                         "ops.decode_attention_rows_i8kv knows one shared first key only (no per-row first key)")
     prev = getattr(_prefill_promise, "starts", None)
     _prefill_promise.starts = starts
     try:
@@ -217,7 +236,9 @@ class _EETAttentionBase(nn.Module):
         the prompt kernel on the UNQUANTISED rotated K and the V where they lie in the projection output -- the prompt's
         output is the fp16-cache path's bit for bit, only the cache is quantised.  A prompt promised appended WITH
         ``int8_rows=True`` is the quantising write behind the device counter, the counter's advance, and the prompt kernel's
-        int8-row form over the dequantised rows below the counter (its own among them): no host read, capturable."""
+        int8-row form over the dequantised rows below the counter (its own among them): no host read, capturable.  With
+        ``few_rows_int8=True`` as well, a piece of 2 .. 16 rows takes the few-row kernel's int8-row form instead
+        (``ops.decode_attention_rows_i8kv``): the same rows, the same arithmetic, other tiles."""
         bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
         if _padded_starts() is not None:
             raise ValueError("EETLlamaAttention: padded_static_batch (a left-padded batch) needs an fp16 static cache: the int8 "
@@ -259,8 +280,13 @@ class _EETAttentionBase(nn.Module):
                                           "K and V")
             ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales,
                                                          first_row_dev=counter)
+            few = getattr(_prefill_promise, "few_rows_int8", False) and 2 <= q_len <= 16
+            if few and ops.decode_attention_rows_i8kv is None:
+                raise NotImplementedError("EETLlamaAttention: appended_static_prefill(few_rows_int8=True) needs "
+                                          "ops.decode_attention_rows_i8kv, which lives in the compiled operator module")
             counter.add_(q_len)
-            out = ops.prefill_attention_i8kv(q, layer.keys, layer.values, layer.scales, rows, scaling=self.scaling, kv_len=counter)
+            attend = ops.decode_attention_rows_i8kv if few else ops.prefill_attention_i8kv
+            out = attend(q, layer.keys, layer.values, layer.scales, rows, scaling=self.scaling, kv_len=counter)
             return out.reshape(bsz, q_len, -1)
         if not getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False):
             raise NotImplementedError("EETLlamaAttention: a prompt on an int8 KV cache must be promised fresh "

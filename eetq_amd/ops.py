@@ -58,6 +58,7 @@ if _C is not None:
     prefill_attention_i8kv = _C.prefill_attention_i8kv              # compiled boundary only, as prefill_attention
     decode_attention_rows = _C.decode_attention_rows                # compiled boundary only, as prefill_attention
     decode_attention_rows_splits = _C.decode_attention_rows_splits
+    decode_attention_rows_i8kv = _C.decode_attention_rows_i8kv      # compiled boundary only, as prefill_attention
     w8_a16_gemv_grouped = _C.w8_a16_gemv_grouped
     llama_decode_layer = _C.llama_decode_layer   # compiled boundary only: its point is the interpreter time it saves
     w8_a16_moe = _C.w8_a16_moe                   # compiled boundary only (the ctypes twin refuses it)
@@ -91,13 +92,14 @@ else:
     prefill_attention_i8kv = None
     decode_attention_rows = None
     decode_attention_rows_splits = None
+    decode_attention_rows_i8kv = None
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t", "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported", "layernorm_forward",
            "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill",
            "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "spec_sample_accept", "sampling_params", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv",
            "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe", "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block", "w4_a16_moe_block", "decode_dropped_steps",
            "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid",
-           "decode_attention_rows", "decode_attention_rows_splits",
+           "decode_attention_rows", "decode_attention_rows_splits", "decode_attention_rows_i8kv",
            "release_stream_workspace", "release_workspace", "BOUNDARY"]
 
 from .sampling import sampling_params  # noqa: E402  (plain Python, shared by both bindings)

@@ -79,7 +79,14 @@ class GraphDecoder:
         computes a token's logits with the prompt kernels, a plain step with the decode kernels.  The step is its own captured
         graph; the plain graphs are captured too and serve ``generate(speculate=False)``.  It needs what ``ragged`` needs --
         ``lean``, a fully accelerated model, head size 64 or 128, ``kv_bits=16`` -- and the MFMA prompt kernel; ``ragged``,
-        ``sampling`` (without ``spec_sampling``, below) and ``kv_bits=8`` raise ``ValueError``.  ``generate`` then needs ``k`` spare cache rows.
+        ``sampling`` (without ``spec_sampling``, below) and ``kv_bits=8`` (without ``kv8_append``, next) raise ``ValueError``.
+        ``generate`` then needs ``k`` spare cache rows.
+        On an INT8 cache (``kv_bits=8``) a verify pass is rows appended behind quantised rows, so ``kv8_append=True`` -- the existing
+        acceptance of exactly that -- is what lets ``speculative=k`` build there: the verify step runs under
+        ``appended_static_prefill(int8_rows=True)``, writes its ``k + 1`` rows quantised behind the device counter and attends the
+        DEQUANTISED rows through ``ops.prefill_attention_i8kv`` (or, with ``spec_attention="rows"``, the few-row kernel's int8-row
+        form).  Draft, accept, history, stats, the spare rows and the one-copy rollback are the fp16 decoder's: stale bytes and
+        scales behind the counter are never read.  Without ``kv8_append`` the combination keeps raising.
         ``ngram`` (1 .. 8): the longest n-gram ``ops.ngram_draft`` looks up in the sequence's own history (``s_hist``).
         ``draft``: a callable ``draft(decoder) -> [batch, k]`` int64 tokens on the device (valid vocabulary ids) instead of the
         lookup: the hook for a draft model and for tests.  Under capture its launches are what the graph holds: it is called
@@ -99,7 +106,9 @@ class GraphDecoder:
         ``ops.decode_attention_rows`` -- the split-KV MFMA kernel for a few rows behind a long cache -- instead of
         the prompt kernel, under greedy and under ``spec_sampling=True`` verification alike.  It needs ``speculative=k`` and the
         compiled operator module; any other value raises ``ValueError``.  ``prefill`` and ``generate(append=True)`` keep the
-        prompt kernel."""
+        prompt kernel.  On an int8 speculative decoder (``kv_bits=8, kv8_append=True``) ``"rows"`` is
+        ``appended_static_prefill(int8_rows=True, few_rows_int8=True)`` and ``ops.decode_attention_rows_i8kv`` (the
+        chunk rule is the fp16 rows' and untuned for int8 rows); ``"prompt"`` stays the default there as well."""
         if spec_attention not in ("prompt", "rows"):
             raise ValueError("GraphDecoder: spec_attention must be 'prompt' (the MFMA prompt kernel) or 'rows' (the few-row split-KV "
                              "kernel), got %r" % (spec_attention,))
@@ -111,6 +120,9 @@ class GraphDecoder:
             if _ops.decode_attention_rows is None:
                 raise ValueError("GraphDecoder: spec_attention='rows' needs ops.decode_attention_rows, which lives in the compiled "
                                  "operator module (this process runs the ctypes boundary)")
+            if kv_bits == 8 and _ops.decode_attention_rows_i8kv is None:
+                raise ValueError("GraphDecoder: spec_attention='rows' on an int8 cache needs ops.decode_attention_rows_i8kv, which "
+                                 "lives in the compiled operator module")
         self.spec_attention = spec_attention
         if kv_bits not in (8, 16):
             raise ValueError("GraphDecoder: kv_bits must be 16 (fp16 cache) or 8 (int8 cache), got %r" % (kv_bits,))
@@ -246,9 +258,11 @@ class GraphDecoder:
         if self.ragged:
             raise ValueError("GraphDecoder: speculative=%d advances all rows by one shared cache counter and one position; "
                              "ragged=True steps every row from its own first key" % speculative)
-        if self.kv_bits != 16:
+        if self.kv_bits != 16 and not self.kv8_append:
             raise ValueError("GraphDecoder: speculative=%d needs fp16 cache rows (kv_bits=16): the verify pass attends behind the "
-                             "device counter with the fp16 prompt kernel, got kv_bits=%r" % (speculative, self.kv_bits))
+                             "device counter with the fp16 prompt kernel, got kv_bits=%r; on an int8 cache kv8_append=True opts in "
+                             "to a verify pass that attends the quantised rows (its own among them)"
+                             % (speculative, self.kv_bits))
         if not self._lean():
             raise ValueError("GraphDecoder: speculative=%d needs lean=True and a fully accelerated model (eet_accelerator with "
                              "fused_attn, fused_mlp and fused_residual): the verify pass is the lean layer loop over k + 1 rows, "
@@ -376,7 +390,12 @@ class GraphDecoder:
         ids = torch.cat([self.s_tok, self.s_draft], dim=1)                                    # [B, k + 1]
         pos = (self.s_pos + self._spec_offsets).view(1, k + 1).expand(self.batch, k + 1)      # cache rows = positions
         h = base.embed_tokens(ids)
-        with appended_static_prefill(few_rows=self.spec_attention == "rows"):
+        rows_kernel = self.spec_attention == "rows"
+        if self.kv_bits == 8:   # (kv8_append: _check_speculative) the verify rows attend quantised rows, their own among them
+            ctx = appended_static_prefill(int8_rows=True, few_rows_int8=rows_kernel)
+        else:
+            ctx = appended_static_prefill(few_rows=rows_kernel)
+        with ctx:
             for layer in base.layers:
                 h = layer(h, attention_mask=None, position_ids=pos, past_key_values=self.cache, use_cache=True)
                 if isinstance(h, tuple):

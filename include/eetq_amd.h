@@ -845,6 +845,27 @@ int eetq_prefill_attention_i8kv_f16(const void* q, const void* k_cache_i8, const
                                     const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* strides,
                                     const long* scale_strides, void* stream);
 
+/* eetq_decode_attention_rows_f16 over an int8 KV cache (the row format above; added within ABI revision 7): `rows` = 1 .. 16 query rows
+ * per batch row, their own cache rows already written (rotated, quantised) and the counter advanced, attend the DEQUANTISED rows
+ * 0 .. keys - 1 causally among themselves -- a speculative verify step on an int8 cache.  Semantics, kv_len, kv_len_bias, the CHUNK
+ * RULE, the two launches, the records and the workspace are eetq_decode_attention_rows_f16's: koff = keys - rows, query t attends rows
+ * 0 .. min(keys - 1, koff + t), rows at and beyond keys are never read (bytes and scales there may be anything, NaN scales included), a
+ * query with nothing to attend gives zeros.  eetq_decode_attention_rows_splits, _max_splits and _workspace_floats serve both entries
+ * (the chunk rule was tuned on fp16 rows and is reused as it is).  strides: as the fp16 entry, with the k / v entries in BYTES;
+ * scale_strides (fp16 elements): {batch, head, position}.
+ * Arithmetic: that of eetq_prefill_attention_i8kv_f16 on this kernel's tiles.  K bytes enter the first product as exact fp16 integers
+ * and the K scale is folded into the fp32 score behind it, per key, before the mask: (ks * scaling * log2 e) * (q . k8), the softmax in
+ * base 2.  As in the prompt entry, and UNLIKE the decode entries (which fold vs into the probability in fp32), a V row enters the second
+ * product as fp16(vs * v8) -- one rounding of the exact product, denormals kept: the probabilities are fp16 operands carried as 2^12 p,
+ * and 2^12 p * vs would leave the fp16 range.  A row that holds all the weight comes out as fp16(vs * v8) bit for bit.
+ * EETQ_ERR_INVALID (nothing launched): the cache, scale and 2 GiB rules of eetq_decode_attention_i8kv_f16 (against max_keys), a cache
+ * row stride below head_dim bytes, the q / out / rows / splits / workspace rules of eetq_decode_attention_rows_f16, a null pointer,
+ * max_keys <= 0.  EETQ_ERR_UNSUPPORTED: head_dim other than 64 or 128. */
+int eetq_decode_attention_rows_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales, void* out,
+                                        float* workspace, int batch, int heads, int kv_heads, int rows, int max_keys, int head_dim,
+                                        const int64_t* kv_len, int kv_len_bias, int splits, float scaling, const long* strides,
+                                        const long* scale_strides, void* stream);
+
 /* Diagnostics: while `stamps` (DEVICE, batch * heads * splits * 8 uint64) is set, every eetq_rope_decode_attention_f16
  * launch of this process records per workgroup the 100 MHz device clock at: 0 entry, 1 scalar reads done, 2 new token
  * rotated, 3 chunk done, 4 chunk record published, 5 ticket drawn, 6 (last workgroup of a head) merge done, 7 output

@@ -14,7 +14,10 @@ break-even: the tokens per verify step at which speculative decoding equals the 
 Writes the table to --out (default profiles/spec_decode.txt).
 --spec-attention prompt,rows: the verify step's attention (GraphDecoder(spec_attention=...)), one table row per value, "rows" next to
 "prompt" on the same model in the same session (profiles/spec_decode_rows.txt).
-usage: python tools/spec_bench.py [--caches 1024,4096] [--ks 2,4,8] [--chain 16] [--reps 7] [--layers 40] [--spec-attention prompt]"""
+--kv-bits 8: the decoder on an int8 KV cache (GraphDecoder(kv_bits=8, kv8_append=True)): plain steps and verify steps both run on
+int8 rows, so verify / plain is in plain INT8 steps (profiles/spec_decode_kv8.txt).
+usage: python tools/spec_bench.py [--caches 1024,4096] [--ks 2,4,8] [--chain 16] [--reps 7] [--layers 40] [--spec-attention prompt]
+                                  [--kv-bits 16]"""
 import argparse
 import os
 import statistics
@@ -32,6 +35,7 @@ ap.add_argument("--chain", type=int, default=16, help="consecutive replays per t
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--layers", type=int, default=40, help="decoder layers (40 = Llama-2-13B; fewer for a quick look)")
 ap.add_argument("--spec-attention", default="prompt", help="comma-separated: prompt (the MFMA prompt kernel), rows (the few-row kernel)")
+ap.add_argument("--kv-bits", type=int, default=16, choices=(16, 8), help="8: an int8 KV cache (kv8_append=True)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spec_decode.txt"))
 args = ap.parse_args()
 DEV = "cuda:0"
@@ -84,7 +88,9 @@ def timed(replay, prepare):
 def main():
     from eetq_amd.utils import GraphDecoder
     model, perm = build_model()
-    lines = ["# tools/spec_bench.py: Llama-2-13B shapes (%d layers, random init, W8A16), batch 1, %s" % (args.layers, torch.cuda.get_device_name(0)),
+    cache_kw = {"kv_bits": 8, "kv8_append": True} if args.kv_bits == 8 else {}
+    lines = ["# tools/spec_bench.py: Llama-2-13B shapes (%d layers, random init, W8A16%s), batch 1, %s"
+             % (args.layers, ", int8 KV cache" if args.kv_bits == 8 else "", torch.cuda.get_device_name(0)),
              "# us per graph replay (median of %d timings of %d consecutive replays); tokens/s = tokens handed over / time" % (args.reps, args.chain),
              "# break-even = verify_us / plain7_us_per_token: tokens per verify step at which the speculative decoder equals the plain one",
              "%6s %3s %6s %10s %12s %10s %11s %10s %10s %10s %10s" % ("cache", "k", "attn", "plain1_us", "plain7_us/t", "verify_us", "verify/pl1",
@@ -105,7 +111,7 @@ def main():
             span = args.chain * max(k + 1, 7) + k + 4              # rows one timing may write behind the prompt
             max_len = cache + span + 8
             with torch.no_grad():
-                dec = GraphDecoder(model, 1, max_len, speculative=k, draft=draft, spec_attention=attn)
+                dec = GraphDecoder(model, 1, max_len, speculative=k, draft=draft, spec_attention=attn, **cache_kw)
 
                 dec.generate(prompt, 1)                             # the prompt pass and one token: `cache` rows cached or pending
                 first = dec.s_tok.clone()
