@@ -121,6 +121,12 @@ def _declare(L):
                                              vp, vp],
         "eetq_rope_decode_attention_padded_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
                                                   i32, ctypes.c_float, vp, vp, i32, vp, vp, vp],
+        "eetq_prefill_attention_window_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, ctypes.c_float, vp,
+                                              vp],
+        "eetq_decode_attention_window_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, vp,
+                                             i32, vp, vp],
+        "eetq_rope_decode_attention_window_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                                  i32, ctypes.c_float, vp, vp, i32, vp, i32, vp, vp],
         "eetq_prefill_attention_i8kv_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp,
                                             vp],
         "eetq_prefill_attention_splits": [i32, i32, i32, i32],
@@ -201,6 +207,7 @@ EXPORTED_SYMBOLS = (
     "eetq_decode_attention_i8kv_f16", "eetq_rope_decode_attention_i8kv_f16", "eetq_rotary_neox_kvcache_prefill_i8_f16",
     "eetq_prefill_attention_i8kv_f16",
     "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
+    "eetq_prefill_attention_window_f16", "eetq_decode_attention_window_f16", "eetq_rope_decode_attention_window_f16",
     "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16", "eetq_spec_sample_accept_f16",
     "eetq_decode_attention_rows_f16", "eetq_decode_attention_rows_splits", "eetq_decode_attention_rows_max_splits",
     "eetq_decode_attention_rows_workspace_floats", "eetq_decode_attention_rows_i8kv_f16",

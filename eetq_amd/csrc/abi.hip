@@ -913,6 +913,15 @@ int eetq_prefill_attention_padded_f16(const void* q, const void* k, const void* 
                                            kv_len, kv_len_bias, kv_start, splits, scaling, strides, static_cast<hipStream_t>(stream));
 }
 
+int eetq_prefill_attention_window_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                      int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                      int window, int splits, float scaling, const long* strides, void* stream)
+{
+    return launch_prefill_attention_window(static_cast<const f16*>(q), static_cast<const f16*>(k), static_cast<const f16*>(v),
+                                           static_cast<f16*>(out), workspace, batch, heads, kv_heads, q_tokens, max_keys, head_dim,
+                                           kv_len, kv_len_bias, window, splits, scaling, strides, static_cast<hipStream_t>(stream));
+}
+
 int eetq_prefill_attention_splits(int batch, int heads, int q_tokens, int max_keys)
 {
     return prefill_attention_splits(batch, heads, q_tokens, max_keys);
@@ -1019,6 +1028,33 @@ int eetq_rope_decode_attention_padded_f16(const int64_t* positions, const int64_
                                           static_cast<f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
                                           workspace, tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling,
                                           strides, kv_len, kv_len_bias, kv_start, advance, table_rows,
+                                          static_cast<hipStream_t>(stream));
+}
+
+int eetq_decode_attention_window_f16(const void* q, const void* k_cache, const void* v_cache, const void* mask, void* out,
+                                     float* workspace, int batch, int heads, int kv_heads, int positions, int head_dim,
+                                     int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                                     const int64_t* kv_start, int window, int64_t* advance, void* stream)
+{
+    return launch_attn_decode_window(static_cast<const f16*>(q), static_cast<const f16*>(k_cache),
+                                     static_cast<const f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
+                                     workspace, batch, heads, kv_heads, positions, head_dim, splits, scaling, strides, kv_len,
+                                     kv_len_bias, kv_start, window, advance, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rope_decode_attention_window_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                          const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                          void* k_cache, void* v_cache, const void* mask, void* out, float* workspace,
+                                          unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                          int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                          int kv_len_bias, const int64_t* kv_start, int window, int64_t* advance, void* stream)
+{
+    return launch_rope_attn_decode_window(positions, slots, slot_stride, static_cast<const f16*>(query),
+                                          static_cast<const f16*>(key), static_cast<const f16*>(value),
+                                          static_cast<const f16*>(cos_sin_cache), static_cast<f16*>(k_cache),
+                                          static_cast<f16*>(v_cache), static_cast<const f16*>(mask), static_cast<f16*>(out),
+                                          workspace, tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling,
+                                          strides, kv_len, kv_len_bias, kv_start, window, advance, table_rows,
                                           static_cast<hipStream_t>(stream));
 }
 

@@ -26,7 +26,8 @@
 // r06_attn_bench.jsonl).  Both forms run the same chunk code and the same merge arithmetic: their outputs are bit-identical.
 // The fp16 forms also exist with a per-row first key (PAD; eetq_*_padded_f16): batch row b of a left-padded
 // batch attends rows [kv_start[b], valid length), its blocks and chunks counted from there.  The plain instantiations are
-// unchanged.
+// unchanged.  On top of PAD, a sliding window (WIN; eetq_*_window_f16): the first row becomes
+// max(kv_start[b], valid length - window), one scalar maximum in front of the padded form's arithmetic.
 //
 // What the cache element changes is held by the row-format policy and nothing else does:
 //   KvF16  a lane's share of a row is 16 bytes of K and 16 of V, used as loaded;
@@ -137,8 +138,8 @@ __device__ __forceinline__ void consume_range(KvBlocks<U>& t, int blk0, int dblk
 struct KvF16 {
     using Elem = f16;
     struct Scales {};  // none
-    template <bool PAD>
-    using RopeArgs = RopeAttnKernArgs<PAD>;
+    template <bool PAD, bool WIN = false>
+    using RopeArgs = std::conditional_t<WIN, RopeAttnWinArgs, RopeAttnKernArgs<PAD>>;
     template <typename A>
     static __device__ __forceinline__ Scales scales(const A&) { return {}; }
     static __device__ __forceinline__ Scales rows(const Scales&, int, int) { return {}; }
@@ -337,8 +338,8 @@ struct KvI8 {
     struct RopeArgs8 : RopeAttnArgs {  // kc_* / vc_* strides in bytes
         Scales sc;
     };
-    template <bool PAD>
-    using RopeArgs = RopeArgs8;  // (no per-row first key on int8 rows)
+    template <bool PAD, bool WIN = false>
+    using RopeArgs = RopeArgs8;  // (no per-row first key and no window on int8 rows)
     static __device__ __forceinline__ const Scales& scales(const RopeArgs8& a) { return a.sc; }
     // the scale pairs of one (batch row, kv head)
     static __device__ __forceinline__ Scales rows(const Scales& sc, int b, int hk) { return {sc.p + b * sc.st.sb + hk * sc.st.sh, sc.st}; }
@@ -489,14 +490,16 @@ __device__ __forceinline__ void attn_chunk(const f16x8& qv, float scaling, typen
 // PAD: batch row b attends rows [s, Sv), s = kv_start[b] kept inside the valid rows: the K, V and mask bases move by s rows and the
 // valid length is taken relative to s, so blocks and chunks are counted from the row's first real token (the bits of the plain form
 // on that row alone, its cache moved up by s rows) and no row below s is read.
-template <class Row, int D, bool MASK, bool LONG, bool PAD>
+// WIN (with PAD): s = max(kv_start[b] or 0, valid length - window) first, then the same: the bits of the PAD form given that start.
+template <class Row, int D, bool MASK, bool LONG, bool PAD, bool WIN = false>
 __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const typename Row::Elem* __restrict__ kc,
                                              const typename Row::Elem* __restrict__ vc, const typename Row::Scales& sc,
                                              const f16* __restrict__ mask, float* __restrict__ ws, float scaling, int S, int groups,
                                              long q_sb, long q_sh, long k_sb, long k_sh, long k_ss, long v_sb, long v_sh, long v_ss,
                                              long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias,
-                                             const KvStartArg<PAD> kv_start)
+                                             const KvFirstArg<PAD, WIN> kv_start)
 {
+    static_assert(!WIN || PAD, "the window is built on the per-row first key");
     constexpr int NW = kAttnThreads / 64;
     __shared__ float sm_m[NW], sm_l[NW];
     __shared__ __attribute__((aligned(16))) float sm_o[NW * D];
@@ -506,7 +509,13 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
     const int rib = (tid >> 6) * AttnGeo<D>::PPW + (tid & 63) / AttnGeo<D>::LPP;
     int  Sv = valid_len(S, kv_len, kv_len_bias);
     long s0 = 0;  // PAD: the row's first attended cache row
-    if constexpr (PAD) {
+    if constexpr (WIN) {
+        // a missing kv_start reads a valid address instead and counts as 0 (selects, no branch before the loads)
+        const int64_t* p_start = kv_start.kv_start ? kv_start.kv_start + b : reinterpret_cast<const int64_t*>(q);
+        const int64_t  start   = kv_start.kv_start ? *p_start : 0;
+        s0 = clamp_kv_start(window_start(start, Sv, kv_start.window), Sv - 1);
+        Sv -= (int)s0;
+    } else if constexpr (PAD) {
         s0 = clamp_kv_start(kv_start[b], Sv - 1);
         Sv -= (int)s0;
     }
@@ -532,14 +541,14 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
 }
 
 // its two argument lists (the int8 one carries the scale tensor and its strides)
-template <int D, bool MASK, bool LONG, bool PAD = false>
+template <int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
     const f16* __restrict__ q, const f16* __restrict__ kc, const f16* __restrict__ vc, const f16* __restrict__ mask,
     float* __restrict__ ws, float scaling, int S, int groups, long q_sb, long q_sh, long k_sb, long k_sh,
     long k_ss, long v_sb, long v_sh, long v_ss, long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias,
-    const KvStartArg<PAD> kv_start)
+    const KvFirstArg<PAD, WIN> kv_start)
 {
-    attn_partial<KvF16, D, MASK, LONG, PAD>(q, kc, vc, KvF16::Scales{}, mask, ws, scaling, S, groups, q_sb, q_sh, k_sb, k_sh, k_ss, v_sb,
+    attn_partial<KvF16, D, MASK, LONG, PAD, WIN>(q, kc, vc, KvF16::Scales{}, mask, ws, scaling, S, groups, q_sb, q_sh, k_sb, k_sh, k_ss, v_sb,
                                             v_sh, v_ss, m_sb, kv_len, kv_len_bias, kv_start);
 }
 template <int D, bool MASK, bool LONG>
@@ -563,14 +572,18 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_i8_kernel(
 // PAD: a fourth scalar read, kv_start[b], joins the batch (one wait, still no branch before the cache loads).  With s the start kept
 // inside [0, slot], the K, V and mask bases move by s rows, the valid length and the slot the chunk code sees are taken relative to
 // s (as in attn_partial<.., PAD>: the two forms stay bit-identical); the new row is written at its absolute slot.
-template <class Row, int D, bool MASK, bool LONG, bool PAD = false>
+//
+// WIN (with PAD): the same four reads -- a missing kv_start reads the position instead and counts as 0 --, then s = max(s, n - window)
+// with n = slot + 1 (the new token counts; without a new token the valid length), scalar arithmetic, and the PAD code as it is.
+template <class Row, int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false>
 __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const int64_t* __restrict__ kv_len,
                                                                         const int64_t* __restrict__ slots,
                                                                         const int64_t* __restrict__ positions,
                                                                         typename Row::Elem* __restrict__ kc,
                                                                         typename Row::Elem* __restrict__ vc,
-                                                                        const typename Row::template RopeArgs<PAD> a)
+                                                                        const typename Row::template RopeArgs<PAD, WIN> a)
 {
+    static_assert(!WIN || PAD, "the window is built on the per-row first key");
     constexpr int LPP = D / 8, NW = kAttnThreads / 64;
     __shared__ float    sm_m[NW], sm_l[NW];
     __shared__ __attribute__((aligned(16))) float sm_o[NW * D];
@@ -592,7 +605,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     const int64_t* p_len  = kv_len ? kv_len : positions;
     int64_t        rpos, slot64, filled, start64 = 0;
     if constexpr (PAD) {
-        const int64_t* p_start = a.kv_start + b;
+        const int64_t* p_start = WIN && !a.kv_start ? positions + b : a.kv_start + b;
         asm volatile("s_load_dwordx2 %0, %4, 0x0\n\ts_load_dwordx2 %1, %5, 0x0\n\ts_load_dwordx2 %2, %6, 0x0\n\t"
                      "s_load_dwordx2 %3, %7, 0x0\n\ts_waitcnt lgkmcnt(0)"
                      : "=&s"(rpos), "=&s"(slot64), "=&s"(filled), "=&s"(start64)
@@ -612,6 +625,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     // a full cache (or a bad position) used to be silent: count the dropped steps (eetq_decode_dropped_steps)
     if (!have_new && split == 0 && h == 0 && threadIdx.x == 0) atomicAdd(&g_attn_dropped, 1u);
     const int  Sv_all = kv_len ? max(0, (int)min((int64_t)a.S, filled + a.kv_len_bias)) : a.S;
+    if constexpr (WIN) start64 = window_start(a.kv_start ? start64 : 0, have_new ? slot + 1 : Sv_all, a.window);
     // PAD: everything the chunk code sees is relative to the row's first attended row s0 (scalar arithmetic, no branch)
     const long s0     = PAD ? clamp_kv_start(start64, have_new ? slot : Sv_all - 1) : 0;
     const int  Sv     = PAD ? max(0, Sv_all - (int)s0) : Sv_all;
@@ -668,15 +682,15 @@ int dispatch_attn(int D, bool mask, int S, int splits, const char* bad_head_dim,
     return fail(EETQ_ERR_UNSUPPORTED, bad_head_dim);
 }
 
-template <int D, bool MASK, bool LONG, bool PAD>
+template <int D, bool MASK, bool LONG, bool PAD, bool WIN>
 void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const f16* k, const f16* v, const KvF16::Scales&, const f16* mask,
                     float* ws, float scaling, int S, int groups, const long* st, const int64_t* kv_len, int kv_len_bias,
-                    KvStartArg<PAD> kv_start)
+                    KvFirstArg<PAD, WIN> kv_start)
 {
-    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG, PAD>, grid, dim3(kAttnThreads), 0, stream, q, k, v, mask, ws, scaling, S,
+    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG, PAD, WIN>, grid, dim3(kAttnThreads), 0, stream, q, k, v, mask, ws, scaling, S,
                   groups, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], kv_len, kv_len_bias, kv_start);
 }
-template <int D, bool MASK, bool LONG, bool PAD>
+template <int D, bool MASK, bool LONG, bool PAD, bool WIN>
 void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const int8_t* k, const int8_t* v, const KvI8::Scales& sc,
                     const f16* mask, float* ws, float scaling, int S, int groups, const long* st, const int64_t* kv_len,
                     int kv_len_bias, NoKvStart)
@@ -686,10 +700,10 @@ void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const int8_t* k
 }
 
 // the two-launch form over either row format; strides: q_b, q_h, the cache's six, mask_b, out_b, out_h
-template <class Row, bool PAD>
+template <class Row, bool PAD, bool WIN = false>
 int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::Elem* v, const typename Row::Scales& sc, const f16* mask,
                 f16* out, float* ws, int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* st,
-                const int64_t* kv_len, int kv_len_bias, int64_t* advance, hipStream_t stream, KvStartArg<PAD> kv_start)
+                const int64_t* kv_len, int kv_len_bias, int64_t* advance, hipStream_t stream, KvFirstArg<PAD, WIN> kv_start)
 {
     EETQ_REQUIRE(q && k && v && out && ws && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S, "invalid attention shape");
@@ -697,7 +711,7 @@ int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::E
     if (rc != EETQ_OK) return rc;
     return dispatch_attn(D, mask != nullptr, S, splits, Row::kBadHeadDim, [&](auto d, auto m, auto l) {
         constexpr int DD = decltype(d)::value;
-        launch_partial<DD, decltype(m)::value, decltype(l)::value, PAD>(dim3(splits, H, B), stream, q, k, v, sc, mask, ws, scaling, S,
+        launch_partial<DD, decltype(m)::value, decltype(l)::value, PAD, WIN>(dim3(splits, H, B), stream, q, k, v, sc, mask, ws, scaling, S,
                                                                         H / Hkv, st, kv_len, kv_len_bias, kv_start);
         EETQ_TRY_HIP(hipGetLastError());
         launch_kernel(attn_decode_merge_kernel<DD>, dim3(H, B), dim3(kAttnThreads), 0, stream, (const float*)ws, out, splits, st[9],
@@ -709,12 +723,12 @@ int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::E
 unsigned long long* g_attn_stamps = nullptr;  // process-wide diagnostic hook (not thread-safe by design)
 
 // the one-launch form over either row format; st: q_b, k_b, v_b, the cache's six, mask_b, out_b, out_h
-template <class Row, bool PAD>
+template <class Row, bool PAD, bool WIN = false>
 int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k, const f16* v,
                      const f16* cos_sin, typename Row::Elem* kc, typename Row::Elem* vc, const typename Row::Scales& sc,
                      const f16* mask, f16* out, float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits,
                      float scaling, const long* st, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start,
-                     int64_t* advance, long table_rows, hipStream_t stream)
+                     int64_t* advance, long table_rows, hipStream_t stream, int window = 0)
 {
     EETQ_REQUIRE(positions && q && k && v && cos_sin && kc && vc && out && ws && tickets && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S && splits <= 4096,
@@ -725,8 +739,9 @@ int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_st
     EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
     const int rc = Row::check_one_launch(q, k, v, cos_sin, kc, vc, sc, S, st);
     if (rc != EETQ_OK) return rc;
-    typename Row::template RopeArgs<PAD> a;
+    typename Row::template RopeArgs<PAD, WIN> a;
     if constexpr (PAD) a.kv_start = kv_start;
+    if constexpr (WIN) a.window = window;
     if constexpr (!std::is_empty_v<typename Row::Scales>) a.sc = sc;
     a.slot_stride = slot_stride;
     a.q = q, a.k = k, a.v = v, a.q_sb = st[0], a.k_sb = st[1], a.v_sb = st[2];
@@ -737,7 +752,7 @@ int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_st
     a.S = S, a.groups = H / Hkv, a.scaling = scaling;
     a.stamps = Row::kStamps ? g_attn_stamps : nullptr;
     return dispatch_attn(D, mask != nullptr, S, splits, Row::kBadHeadDim, [&](auto d, auto m, auto l) {
-        launch_kernel(rope_attn_decode_kernel<Row, decltype(d)::value, decltype(m)::value, decltype(l)::value, PAD>, dim3(splits, H, B),
+        launch_kernel(rope_attn_decode_kernel<Row, decltype(d)::value, decltype(m)::value, decltype(l)::value, PAD, WIN>, dim3(splits, H, B),
                       dim3(kAttnThreads), 0, stream, kv_len, slots, positions, kc, vc, a);
         return check_hip(hipGetLastError(), Row::kOneLaunch);
     });
@@ -763,6 +778,29 @@ int launch_attn_decode_padded(const f16* q, const f16* k, const f16* v, const f1
     EETQ_REQUIRE(kv_start, "null kv_start");
     return launch_attn<KvF16, true>(q, k, v, {}, mask, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len, kv_len_bias, advance,
                                     stream, kv_start);
+}
+
+// the decode entries with a sliding window: batch row b attends the last `window` of its valid rows, not below kv_start[b] (DEVICE
+// [B], or nullptr); the bits of the padded entries called with kv_start'[b] = max(kv_start[b], valid length - window)
+int launch_attn_decode_window(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                              int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                              const int64_t* kv_start, int window, int64_t* advance, hipStream_t stream)
+{
+    EETQ_REQUIRE(window >= 1, "the attention window must be at least 1 row");
+    return launch_attn<KvF16, true, true>(q, k, v, {}, mask, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len, kv_len_bias,
+                                          advance, stream, KvWindow{kv_start, window});
+}
+
+int launch_rope_attn_decode_window(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                   const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                                   unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                                   const long* st, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int window,
+                                   int64_t* advance, long table_rows, hipStream_t stream)
+{
+    EETQ_REQUIRE(window >= 1, "the attention window must be at least 1 row");
+    return launch_rope_attn<KvF16, true, true>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, {}, mask, out, ws, tickets, B, H,
+                                               Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, kv_start, advance, table_rows,
+                                               stream, window);
 }
 
 int launch_attn_decode_i8(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, const f16* mask, f16* out, float* ws,

@@ -284,6 +284,21 @@ struct NoKvStart {};
 template <bool PAD>
 using KvStartArg = std::conditional_t<PAD, const int64_t*, NoKvStart>;
 
+// The sliding window (WIN instantiations, built on the PAD arithmetic): batch row b attends the last `window` of its
+// n valid rows, i.e. the padded form with kv_start'[b] = max(kv_start[b], n - window); kv_start may be null (then 0).  Behind the
+// padded form's arguments; the two-launch kernel takes the pair as its last argument.
+struct RopeAttnWinArgs : RopeAttnPadArgs {
+    int window;  // >= 1, a host constant of the model
+};
+struct KvWindow {
+    const int64_t* kv_start;  // DEVICE [batch] or null
+    int            window;
+};
+template <bool PAD, bool WIN>
+using KvFirstArg = std::conditional_t<WIN, KvWindow, KvStartArg<PAD>>;
+// the first row a WIN instantiation hands to clamp_kv_start: the later of the row's own start and the window's first row
+__device__ __forceinline__ int64_t window_start(int64_t start, int n, int window) { return max(start, (int64_t)n - (int64_t)window); }
+
 // The first attended row of a batch row: its start, kept inside [0, last] where `last` is the new token's row (one-launch form) or
 // the last valid row (two-launch form, no new token) -- a start beyond it attends that row alone, and nothing leaves the cache.
 __device__ __forceinline__ int clamp_kv_start(int64_t start, int last)

@@ -20,7 +20,9 @@
 // second product -- two barriers per block -- measured the same: the waves of the two resident workgroups run their phases in step.)  Two workgroups per CU (<= 256 registers: everything in the
 // architectural file, no accumulator copies).    Blocks beyond a wave's last query row are skipped by that wave; heavy query blocks are
 // dispatched first (1-D grid ordered by weight).
-// The device-length and split forms also run over an int8 KV cache (KV8, kv_i8.hpp): see the comment above the kernel.
+// The device-length and split forms also run over an int8 KV cache (KV8, kv_i8.hpp), with a per-row first key (PAD) and with a
+// sliding window (WIN): see the comment above the kernel.
+#include <algorithm>
 #include <type_traits>
 
 #include "common.hpp"
@@ -63,9 +65,16 @@ struct PrefillDevArgs8 : PrefillDevArgs {
 struct PrefillPadArgs : PrefillDevArgs {
     const int64_t* kv_start;   // DEVICE [batch]
 };
-template <int MODE, bool KV8, bool PAD = false>
+// The sliding window (WIN): a query at cache row p attends rows max(0, p - window + 1) .. p.  Behind the device-length
+// arguments, which keep their kernarg block.
+struct PrefillWinArgs : PrefillDevArgs {
+    int window;   // >= 1, a host constant of the model
+};
+template <int MODE, bool KV8, bool PAD = false, bool WIN = false>
 using PrefillKernArgs = std::conditional_t<
-    PAD, PrefillPadArgs, std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>>;
+    WIN, PrefillWinArgs,
+    std::conditional_t<PAD, PrefillPadArgs,
+                       std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>>>;
 
 // MODE kPfHost: keys and causal offset from the host (the fresh prompt's path, unchanged).  kPfDev: every workgroup reads the length
 // at entry -- one scalar load -- and forms Tk and koff itself; kend, nblk, the descriptors' range, `active` and `edge` follow, the
@@ -90,11 +99,21 @@ using PrefillKernArgs = std::conditional_t<
 // s rows, Tq -= p, Tk -= s, koff = Tk - Tq, and the unchanged code below runs in the row's own frame -- query blocks, key blocks and
 // split shares counted from its first real token, the descriptors starting there: the bits of the plain form called on that row
 // alone, and no row below s is read.  Workgroups whose query block lies beyond the row's real queries leave.
-template <int D, int MODE, bool KV8 = false, bool PAD = false>
-__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8, PAD> a_in)
+//
+// WIN (kPfDev and kPfSplit, fp16 rows): query row t (cache row t + koff) attends keys in (t + koff - W, t + koff].  The key-block grid
+// stays absolute (blocks of 64 from row 0); a workgroup starts at its first needed block jlo = max(0, q0 + koff - W + 1) / 64 -- loop,
+// prologue and, in the split form, the shares [jlo + i n / ns, jlo + (i + 1) n / ns) of its n = nblk - jlo blocks --, a wave skips the
+// blocks that end below its first row's window, and the mask has a lower edge.  A row whose first blocks are fully masked keeps
+// m_run = -inf and every p = 0 until its window begins.  W >= keys: jlo = 0 and no lower edge is ever taken -- the bits of the
+// plain form; so are, in any launch, the rows with t + koff < W (their workgroup starts at block 0 and their wave skips nothing the
+// plain form attends).  No row below 64 (max(0, koff - W + 1) / 64) is read by the launch; rows of a lower-edge block below a row's
+// window are read and enter the value product with probability 0 (they must be finite).
+template <int D, int MODE, bool KV8 = false, bool PAD = false, bool WIN = false>
+__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8, PAD, WIN> a_in)
 {
     static_assert(!KV8 || MODE != kPfHost, "the int8-row form takes the device-length arguments");
     static_assert(!PAD || (MODE != kPfHost && !KV8), "the per-row first key rides on the device-length arguments, fp16 rows");
+    static_assert(!WIN || (MODE != kPfHost && !KV8 && !PAD), "the window rides on the device-length arguments, fp16 rows, one first key");
     PrefillArgs a = a_in;
     int         wg = (int)blockIdx.x, split = 0;
     if constexpr (MODE != kPfHost) {
@@ -162,9 +181,15 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     const int nblk  = kend > 0 ? (kend + kPfBN - 1) / kPfBN : 0;
     // this workgroup's key blocks [j0, j1): all of them, or its share
     int j0 = 0, j1 = nblk;
+    int wlo = 0;   // WIN: koff - W + 1; row t's first attended key is t + wlo
+    if constexpr (WIN) {
+        wlo = a.koff - a_in.window + 1;
+        j0  = min(nblk, max(0, q0 + wlo) / kPfBN);   // the first block a row of this workgroup attends
+    }
     if constexpr (MODE == kPfSplit) {
-        j0 = (int)((long)split * nblk / a_in.ns);
-        j1 = (int)((long)(split + 1) * nblk / a_in.ns);
+        const int jlo = j0, n = nblk - jlo;
+        j0 = jlo + (int)((long)split * n / a_in.ns);
+        j1 = jlo + (int)((long)(split + 1) * n / a_in.ns);
     }
     // the valid rows of this (batch row, kv head) behind buffer descriptors: rows at and beyond Tk are out of range and read as zeros
     // (KV8: the same three lines with strides in bytes, and the rows' scale dwords behind a third descriptor)
@@ -291,7 +316,8 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
 
     for (int j = j0; j < j1; ++j) {
         const int  key0   = j * kPfBN;
-        const bool active = key0 <= qlast_wave + a.koff;  // wave-uniform: some row of this wave attends this block
+        bool       active = key0 <= qlast_wave + a.koff;  // wave-uniform: some row of this wave attends this block
+        if constexpr (WIN) active = active && key0 + kPfBN - 1 >= q0 + wave * 32 + wlo;   // ... and it does not end below the wave's window
         if (j + 1 < j1) stage((j + 1) & 1);               // block j + 1: registers -> the buffer block j - 1 was read from
         if (j + 2 < j1) fetch(j + 2);
         const f16* k_lds  = k_lds2[j & 1];
@@ -326,7 +352,9 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
             }
             // ---- mask (only where the block touches the wave's diagonal or the end of the keys: a wave-uniform branch), running maximum
             // (scaled domain) ----
-            const bool edge = key0 + kPfBN - 1 > q0 + wave * 32 + a.koff || key0 + kPfBN > a.Tk;
+            bool edge = key0 + kPfBN - 1 > q0 + wave * 32 + a.koff || key0 + kPfBN > a.Tk;
+            // the lower edge: the block begins below the window of the wave's last real row
+            if constexpr (WIN) edge = edge || key0 < min(qlast_wave, a.Tq - 1) + wlo;
             float mloc = -INFINITY;
             if (edge) {
 #pragma unroll
@@ -334,7 +362,8 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int  key   = key0 + 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                        const bool valid = key < a.Tk && key <= qrow + a.koff;
+                        bool       valid = key < a.Tk && key <= qrow + a.koff;
+                        if constexpr (WIN) valid = valid && key >= qrow + wlo;
                         float      t     = valid ? s[kb][r] : -INFINITY;
                         asm volatile("" : "+v"(t));  // pins the select inside the branch (else: 170 select instructions on EVERY block)
                         s[kb][r] = t;
@@ -533,8 +562,8 @@ namespace {
 // The one launch path of the device forms (plain, per-row first key, int8 rows).  `a` arrives with the form's own fields set
 // (kv_start; the scales), `front` runs the form's own argument checks -- every form has them between the two requirements on top
 // and the workspace's --, what1 / whatn name the form when a launch fails.  k and v: the int8 form's rows as they go into the struct.
-template <bool KV8, bool PAD, class Front>
-int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD>& a, Front front, const f16* q, const f16* k, const f16* v, f16* out, float* ws,
+template <bool KV8, bool PAD, bool WIN = false, class Front>
+int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD, WIN>& a, Front front, const f16* q, const f16* k, const f16* v, f16* out, float* ws,
                          int B, int H, int Hkv, int Tq, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits,
                          float scaling, const long* st, hipStream_t stream, const char* what1, const char* whatn)
 {
@@ -550,19 +579,19 @@ int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD>& a, Front front, cons
     const dim3 grid((unsigned)wgs), block(kPfThreads);
     if (splits == 1) {
         if (D == 128)
-            launch_kernel(prefill_attn_kernel<128, kPfDev, KV8, PAD>, grid, block, 0, stream, a);
+            launch_kernel(prefill_attn_kernel<128, kPfDev, KV8, PAD, WIN>, grid, block, 0, stream, a);
         else
-            launch_kernel(prefill_attn_kernel<64, kPfDev, KV8, PAD>, grid, block, 0, stream, a);
+            launch_kernel(prefill_attn_kernel<64, kPfDev, KV8, PAD, WIN>, grid, block, 0, stream, a);
         return check_hip(hipGetLastError(), what1);
     }
     const long rows = (long)B * H * Tq, threads = rows * (D / 4);
     EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
     const dim3 mgrid((unsigned)((threads + 255) / 256));
     if (D == 128) {
-        launch_kernel(prefill_attn_kernel<128, kPfSplit, KV8, PAD>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<128, kPfSplit, KV8, PAD, WIN>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     } else {
-        launch_kernel(prefill_attn_kernel<64, kPfSplit, KV8, PAD>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<64, kPfSplit, KV8, PAD, WIN>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     }
     return check_hip(hipGetLastError(), whatn);
@@ -601,6 +630,25 @@ int launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v, f1
     return launch_prefill_forms<false, true>(a, front, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D, kv_len, kv_len_bias, splits, scaling, st,
                                              stream, "prefill_attn_kernel (per-row first key) launch",
                                              "prefill_attn_kernel (per-row first key, split) launch");
+}
+
+// launch_prefill_attention_dev with a sliding window (the WIN form above): query t attends the `window` cache rows up to its own.
+// Always the device-length kernel (kv_len nullptr: max_keys keys, a fresh prompt), or the split form and the unchanged merge.
+int launch_prefill_attention_window(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                    int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int window, int splits, float scaling,
+                                    const long* st, hipStream_t stream)
+{
+    PrefillWinArgs a;
+    a.window = std::min(window, std::max(max_keys, 1));   // (a longer window is the whole prefix; keeps the kernel's 32-bit arithmetic in range)
+    auto front = [&] {
+        const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, max_keys, D, st);
+        if (rc != EETQ_OK) return rc;
+        EETQ_REQUIRE(window >= 1, "the attention window must be at least 1 row");
+        return (int)EETQ_OK;
+    };
+    return launch_prefill_forms<false, false, true>(a, front, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D, kv_len, kv_len_bias, splits,
+                                                    scaling, st, stream, "prefill_attn_kernel (window) launch",
+                                                    "prefill_attn_kernel (window, split) launch");
 }
 
 // launch_prefill_attention_dev over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of

@@ -345,6 +345,10 @@ int    launch_prefill_attention_dev(const f16* q, const f16* k, const f16* v, f1
 int    launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
                                        int max_keys, int D, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int splits,
                                        float scaling, const long* st, hipStream_t stream);
+// ... with a sliding window: query t (cache row t + keys - Tq) attends the `window` rows up to its own
+int    launch_prefill_attention_window(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                       int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int window, int splits, float scaling,
+                                       const long* st, hipStream_t stream);
 int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
 int    prefill_attention_max_splits();
 size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
@@ -373,6 +377,15 @@ int launch_rope_attn_decode_padded(const int64_t* positions, const int64_t* slot
                                    const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
                                    unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
                                    const long* strides, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start,
+                                   int64_t* advance, long table_rows, hipStream_t stream);
+// the decode entries with a sliding window: the last `window` valid rows of batch row b, not below kv_start[b] (DEVICE [B] or nullptr)
+int launch_attn_decode_window(const f16* q, const f16* k, const f16* v, const f16* mask, f16* out, float* ws, int B, int H, int Hkv,
+                              int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                              const int64_t* kv_start, int window, int64_t* advance, hipStream_t stream);
+int launch_rope_attn_decode_window(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                   const f16* v, const f16* cos_sin, f16* kc, f16* vc, const f16* mask, f16* out, float* ws,
+                                   unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                                   const long* strides, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int window,
                                    int64_t* advance, long table_rows, hipStream_t stream);
 
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,

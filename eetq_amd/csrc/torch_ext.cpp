@@ -222,8 +222,10 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
                              const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, Tensor& tickets,
                              const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
                              std::optional<int64_t> splits_in, const OptTensor& kv_len, int64_t kv_len_bias,
-                             const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
+                             const OptTensor& advance, const OptTensor& kv_start = std::nullopt,
+                             std::optional<int64_t> window = std::nullopt)
 {
+    if (window) TORCH_CHECK_VALUE(*window >= 1, "rope_decode_attention: window must be at least 1 row (got ", *window, ")");
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache})
         TORCH_CHECK(t->scalar_type() == at::kHalf, "rope_decode_attention: float16 tensors expected");
     TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous(),
@@ -248,6 +250,14 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
     const int64_t*       starts  = kv_start_ptr("rope_decode_attention", kv_start, query, B);
     unsigned*            tk      = reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>());
     c10::DeviceGuard     guard(query.device());
+    if (window) {   // the last `window` valid rows, not below kv_start (which may be absent)
+        check(eetq_rope_decode_attention_window_f16(
+            positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+            cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(),
+            p.out.data_ptr(), p.ws.data_ptr<float>(), tk, (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(),
+            p.kv_len, (int)kv_len_bias, starts, (int)std::min<int64_t>(*window, INT32_MAX), p.advance, stream_of(query)));
+        return p.out;
+    }
     if (starts) {
         check(eetq_rope_decode_attention_padded_f16(
             positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
@@ -335,21 +345,37 @@ static int prefill_splits_rule(int B, int H, int, int T, int keys) { return eetq
 // device (eetq_prefill_attention_dev_f16); splits: None = the library's rule, workspace: None = allocated here (capturable)
 Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
                          std::optional<int64_t> causal_offset, const OptTensor& kv_len, int64_t kv_len_bias,
-                         std::optional<int64_t> splits_in, const OptTensor& workspace, const OptTensor& kv_start = std::nullopt)
+                         std::optional<int64_t> splits_in, const OptTensor& workspace, const OptTensor& kv_start = std::nullopt,
+                         std::optional<int64_t> window = std::nullopt)
 {
+    // the sliding window's refusals come first and are ValueErrors: they are about the combination asked for, not about the tensors
+    if (window) {
+        TORCH_CHECK_VALUE(*window >= 1, "prefill_attention: window must be at least 1 row (got ", *window, ")");
+        TORCH_CHECK_VALUE(!kv_start, "prefill_attention: window and kv_start exclude each other (the windowed prompt kernel knows one "
+                                     "shared first key; ragged prompts with a window are not built)");
+    }
     check_prompt_qkv("prefill_attention: ", 'T', query, key, value, keys);
     const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
     TORCH_CHECK(T > 0, "prefill_attention: shape mismatch");
     TORCH_CHECK(prefill_attention_supported(D), "prefill_attention: unsupported head_dim");
     const int64_t off = causal_offset ? *causal_offset : keys - T;
     const int64_t* starts = kv_start_ptr("prefill_attention", kv_start, query, B);
-    const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0 || starts;
+    const bool   dev_form = kv_len.has_value() || splits_in.has_value() || workspace.has_value() || kv_len_bias != 0 || starts || window;
     if (dev_form)
         TORCH_CHECK(!(kv_len && causal_offset), "prefill_attention: kv_len and causal_offset exclude each other (with kv_len the offset is "
                                                 "the device length minus the query rows)");
-    const PromptAttnPrep p("prefill_attention: ", query, key, value, keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
+    // window: a workgroup reads at most the window and its own 128 rows' keys -- the rule sizes the shares by that (untuned)
+    const int64_t rule_keys = window ? std::min<int64_t>(keys, std::min<int64_t>(*window, keys) + std::min<int64_t>(T, 128)) : keys;
+    const PromptAttnPrep p("prefill_attention: ", query, key, value, rule_keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
                            prefill_splits_rule, eetq_prefill_attention_max_splits, eetq_prefill_attention_workspace_floats, false, dev_form);
     c10::DeviceGuard guard(query.device());
+    if (window) {   // always the device-length entry (kv_len None: `keys` keys, the fresh prompt)
+        TORCH_CHECK(off == keys - T, "prefill_attention: window takes causal_offset = keys - query rows only");
+        check(eetq_prefill_attention_window_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
+                                                (int)H, (int)Hkv, (int)T, (int)keys, (int)D, p.kv_len, (int)kv_len_bias,
+                                                (int)std::min<int64_t>(*window, INT32_MAX), (int)p.splits, p.sc, p.st, stream_of(query)));
+        return p.out;
+    }
     if (starts) {   // the per-row first key: always the device-length entry (kv_len None: `keys` keys, the fresh prompt)
         TORCH_CHECK(off == keys - T, "prefill_attention: kv_start takes causal_offset = keys - query rows only");
         check(eetq_prefill_attention_padded_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
@@ -1041,8 +1067,10 @@ void spec_sample_accept(const Tensor& logits, const Tensor& draft, Tensor& out_t
 
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
-                        int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt)
+                        int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt,
+                        std::optional<int64_t> window = std::nullopt)
 {
+    if (window) TORCH_CHECK_VALUE(*window >= 1, "decode_attention: window must be at least 1 row (got ", *window, ")");
     TORCH_CHECK(query.scalar_type() == at::kHalf && key_cache.scalar_type() == at::kHalf && value_cache.scalar_type() == at::kHalf,
                 "decode_attention: query and caches must be float16");
     TORCH_CHECK(query.dim() == 3 && key_cache.dim() == 4 && value_cache.sizes() == key_cache.sizes(),
@@ -1056,6 +1084,13 @@ Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tens
     const auto           strides = p.strides({query.stride(0), query.stride(1)}, key_cache, value_cache);
     const int64_t*       starts  = kv_start_ptr("decode_attention", kv_start, query, B);
     c10::DeviceGuard     guard(query.device());
+    if (window) {   // the last `window` valid rows, not below kv_start (which may be absent)
+        check(eetq_decode_attention_window_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(), p.out.data_ptr(),
+                                               p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc,
+                                               strides.data(), p.kv_len, (int)kv_len_bias, starts,
+                                               (int)std::min<int64_t>(*window, INT32_MAX), p.advance, stream_of(query)));
+        return p.out;
+    }
     if (starts) {
         check(eetq_decode_attention_padded_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(), p.out.data_ptr(),
                                                p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc,
@@ -1110,9 +1145,12 @@ Tensor decode_attention_i8kv(const Tensor& query, const Tensor& key_cache, const
 // / head strides), the first `max_keys` rows of the caches, or clamp(*kv_len + kv_len_bias, 0, max_keys) of them; [B, T, H, D] contiguous
 Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
                               int64_t max_keys, std::optional<double> scaling, const OptTensor& kv_len, int64_t kv_len_bias,
-                              std::optional<int64_t> splits_in, const OptTensor& workspace)
+                              std::optional<int64_t> splits_in, const OptTensor& workspace,
+                              std::optional<int64_t> window = std::nullopt)
 {
     const char* name = "prefill_attention_i8kv: ";
+    // accepted only to be refused by name: a caller that passes the fp16 operator's argument must not get the whole prefix silently
+    TORCH_CHECK_VALUE(!window, name, "no sliding window on int8 rows (the windowed prompt kernel reads fp16 cache rows only)");
     TORCH_CHECK(query.scalar_type() == at::kHalf && query.is_cuda() && query.dim() == 4 && query.stride(-1) == 1 && key_cache.dim() == 4,
                 name, "expected a float16 CUDA query [B, T, H, D] with dense D");
     const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key_cache.size(1);
@@ -2075,12 +2113,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none(), py::arg("kv_start") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none());
     m.def("rope_decode_attention", &rope_decode_attention, py::arg("positions"), py::arg("query"), py::arg("key"),
           py::arg("value"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("tickets"),
           py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none(), py::arg("kv_start") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none());
     m.def("decode_attention_i8kv", &decode_attention_i8kv, "single-query attention over an int8 KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"), py::arg("mask") = py::none(),
           py::arg("scaling") = py::none(), py::arg("splits") = py::none(), py::arg("kv_len") = py::none(),
@@ -2097,11 +2135,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
-          py::arg("kv_start") = py::none(),
+          py::arg("kv_start") = py::none(), py::arg("window") = py::none(),
           "causal attention of a prompt's query rows [B, T, H, D] over the first `keys` rows of a KV cache [B, Hkv, S, D] (MFMA)");
     m.def("prefill_attention_i8kv", &prefill_attention_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
           py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
+          py::arg("window") = py::none(),
           "prefill_attention behind an int8 KV cache: a prompt's query rows [B, T, H, D] over the dequantised first rows of the cache");
     m.def("decode_attention_rows", &decode_attention_rows, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(),

@@ -77,6 +77,9 @@ def appended_static_prefill(int8_rows=False, few_rows=False, few_rows_int8=False
     if few_rows_int8 and _padded_starts() is not None:
         raise ValueError("appended_static_prefill: few_rows_int8 (ops.decode_attention_rows_i8kv) knows one shared first key only; it "
                          "cannot run under padded_static_batch (a per-row first key)")
+    if (few_rows or few_rows_int8) and getattr(_prefill_promise, "window", None) is not None:
+        raise ValueError("appended_static_prefill: few_rows / few_rows_int8 (the few-row kernel) has no sliding window; it cannot run "
+                         "under sliding_window_static")
     if few_rows and int8_rows:
         raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) reads fp16 cache rows only; it cannot be "
                          "combined with int8_rows")
@@ -117,6 +120,9 @@ def padded_static_batch(starts):
     if starts is not None and getattr(_prefill_promise, "few_rows_int8", False):
         raise ValueError("padded_static_batch: appended_static_prefill(few_rows_int8=True) is in force, and "
                          "ops.decode_attention_rows_i8kv knows one shared first key only (no per-row first key)")
+    if starts is not None and getattr(_prefill_promise, "window", None) is not None:
+        raise ValueError("padded_static_batch: sliding_window_static is in force, and the windowed prompt kernel knows one shared first "
+                         "key only (no ragged prompt with a window)")
     prev = getattr(_prefill_promise, "starts", None)
     _prefill_promise.starts = starts
     try:
@@ -127,6 +133,43 @@ def padded_static_batch(starts):
 
 def _padded_starts():
     return getattr(_prefill_promise, "starts", None)
+
+
+@contextlib.contextmanager
+def sliding_window_static(window):
+    """The caller's promise for the forwards run inside (per thread, restored on exit): attention looks back ``window`` rows -- a
+    query at cache row p attends rows ``max(0, p - window + 1) .. p``, itself and the ``window - 1`` rows before it (transformers'
+    ``sliding_window``).  ``window`` is a host integer >= 1, a constant of the model: it becomes a kernel argument, so a captured
+    graph serves every length.  The static cache stays as it is (rows are not recycled).  The attention blocks hand ``window=`` to
+    the library's kernels:
+
+    * a decode step on a static cache goes through the module forward (``decode_step_state`` returns ``None``) and calls
+      ``ops.rope_decode_attention`` / ``ops.decode_attention`` with ``window``;
+    * a prompt under ``fresh_static_prefill`` or ``appended_static_prefill`` calls ``ops.prefill_attention`` with ``window`` (the fresh
+      prompt through the device-length entry with ``kv_len=None``).
+
+    Anything that cannot honour the window raises ``ValueError`` instead of attending the whole prefix: an unsupported head size or
+    dtype, an int8 cache, the ``few_rows`` promises (the few-row kernel has no window), ``padded_static_batch`` (no ragged prompt
+    with a window) and every stock attention path.  ``window=None`` promises nothing."""
+    if window is not None:
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError("sliding_window_static: window must be an integer of at least 1 row, got %r" % (window,))
+        if _padded_starts() is not None:
+            raise ValueError("sliding_window_static: padded_static_batch is in force, and the windowed prompt kernel knows one shared "
+                             "first key only (no ragged prompt with a window)")
+        if getattr(_prefill_promise, "few_rows", False) or getattr(_prefill_promise, "few_rows_int8", False):
+            raise ValueError("sliding_window_static: appended_static_prefill(few_rows=True / few_rows_int8=True) is in force, and the "
+                             "few-row kernel (ops.decode_attention_rows) has no sliding window")
+    prev = getattr(_prefill_promise, "window", None)
+    _prefill_promise.window = window
+    try:
+        yield
+    finally:
+        _prefill_promise.window = prev
+
+
+def _window():
+    return getattr(_prefill_promise, "window", None)
 
 
 class EETRotaryEmbedding(nn.Module):
@@ -240,6 +283,9 @@ class _EETAttentionBase(nn.Module):
         ``few_rows_int8=True`` as well, a piece of 2 .. 16 rows takes the few-row kernel's int8-row form instead
         (``ops.decode_attention_rows_i8kv``): the same rows, the same arithmetic, other tiles."""
         bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
+        if _window() is not None:
+            raise ValueError("EETLlamaAttention: sliding_window_static needs an fp16 static cache: the int8 kernels have no sliding "
+                             "window")
         if _padded_starts() is not None:
             raise ValueError("EETLlamaAttention: padded_static_batch (a left-padded batch) needs an fp16 static cache: the int8 "
                              "kernels take no per-row first key")
@@ -375,6 +421,8 @@ class _EETAttentionBase(nn.Module):
             return None
         if _padded_starts() is not None:   # the one-call layer takes no per-row first key: the module forward does
             return None
+        if _window() is not None:          # ... and no sliding window
+            return None
         bsz, rows = hidden_states.shape[0], layer.keys.shape[2]
         memo = getattr(_EETAttentionBase._step_memo, "entry", None)
         if memo is None:
@@ -405,6 +453,23 @@ class _EETAttentionBase(nn.Module):
         cache's device counter, already advanced, as a third element."""
         q = q.transpose(1, 2)
         starts = _padded_starts()
+        window = _window()
+        if window is not None:
+            # a sliding window: the MFMA prompt kernel's windowed form, or an error -- every other path below would attend the
+            # whole prefix (a single token on a static cache never comes here: forward() hands it to the decode kernels)
+            if (starts is not None or cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False)
+                    or not self._mfma_prompt_ok(q, *cached[:2])
+                    or not (getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False))
+                    or getattr(_prefill_promise, "few_rows", False)):
+                raise ValueError("EETLlamaAttention: sliding_window_static needs the MFMA prompt kernel (float16 on the GPU, head "
+                                 "size 64 or 128, mfma_prefill=True, the compiled operator module) on an initialised fp16 static "
+                                 "cache under fresh_static_prefill or appended_static_prefill, without padded_static_batch or "
+                                 "few_rows; a single token needs the library's decode attention on such a cache")
+            k, v, counter = cached
+            fresh = getattr(_prefill_promise, "fresh", False)
+            out = ops.prefill_attention(q.transpose(1, 2), k, v, q.shape[2] if fresh else k.shape[2], scaling=self.scaling,
+                                        kv_len=None if fresh else counter, window=window)
+            return out.reshape(*input_shape, -1), None
         if starts is not None:
             # a left-padded batch: the MFMA prompt kernel with the per-row first key, or an error -- every other path below would
             # attend the pads
@@ -564,6 +629,11 @@ class EETLlamaAttention(_EETAttentionBase):
         if starts is not None and q_len == 1 and add is False:
             raise ValueError("EETLlamaAttention: padded_static_batch needs the library's decode attention on an initialised fp16 "
                              "static cache (head size 64 or 128, decode_math_attention=True, a mask the kernel understands)")
+        window = _window()          # a sliding window: the decode kernels' windowed entries (None: the entries above)
+        if window is not None and q_len == 1 and add is False:
+            raise ValueError("EETLlamaAttention: sliding_window_static needs the library's decode attention on an initialised fp16 "
+                             "static cache (head size 64 or 128, decode_math_attention=True, a mask the kernel understands)")
+        wkw = {} if window is None else {"window": window}
         if add is not False:
             # decode step on an initialised static cache: ONE launch rotates q in place (by its position) and writes the
             # rotated k and v straight into the cache row the cache's own token counter names -- for a left-padded batch
@@ -580,13 +650,13 @@ class EETLlamaAttention(_EETAttentionBase):
                 out = ops.rope_decode_attention(pos, q[:, 0], k[:, 0], v[:, 0], table, layer.keys, layer.values,
                                                 self._step_tickets(bsz, q.device), slots=counter, mask=add, scaling=self.scaling,
                                                 kv_len=counter, kv_len_bias=1, advance=counter,
-                                                kv_start=starts).reshape(bsz, q_len, -1)
+                                                kv_start=starts, **wkw).reshape(bsz, q_len, -1)
             else:
                 ops.rotary_embedding_neox_kvcache(pos, q[:, 0], k[:, 0], v[:, 0], self.head_dim, table, layer.keys,
                                                   layer.values, slots=counter)
                 out = ops.decode_attention(q[:, 0], layer.keys, layer.values, mask=add, scaling=self.scaling,
                                            kv_len=counter, kv_len_bias=1, advance=counter,
-                                           kv_start=starts).reshape(bsz, q_len, -1)
+                                           kv_start=starts, **wkw).reshape(bsz, q_len, -1)
             weights = None
         else:
             player = self._static_cache_layer(past_key_values) if (q_len > 1 and q.is_cuda and self.static_prefill) else None

@@ -724,6 +724,17 @@ def _optr(t):
     return _ptr(t) if t is not None else None
 
 
+def _check_window(name, window):
+    """``window`` of the decode-attention operators (a sliding window of that many rows): a host integer >= 1, or ``ValueError``."""
+    try:
+        rows = window.__index__()
+    except AttributeError:
+        rows = 0
+    if rows < 1:
+        raise ValueError("%s: window must be at least 1 row (got %r)" % (name, window))
+    return min(rows, 2 ** 31 - 1)
+
+
 class _DecodeAttnPrep:
     """What the four decode-attention operators prepare alike (``name``: "operator: "): the slots' stride, the mask row and its
     batch stride, the ``kv_len`` / ``advance`` scalars, the default scaling and chunk count, the output, the workspace and the
@@ -759,7 +770,7 @@ class _DecodeAttnPrep:
 
 @_eager_only
 def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0,
-                     advance=None, kv_start=None):
+                     advance=None, kv_start=None, window=None):
     """Single-query attention over a KV cache (extension; the decode step of the EET attention blocks).
 
     query [B, H, D] (any batch/head strides, dense D), key_cache / value_cache [B, Hkv, S, D] (dense D), mask: additive
@@ -767,7 +778,9 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
     device scalar): only rows below ``kv_len + kv_len_bias`` are attended (the filled part of a static cache); ``advance``
     (int64 device scalar, may be the same tensor): incremented by one when the attention has been computed.  ``kv_start``
     (int64 [B] on the device): batch row b attends rows ``kv_start[b]`` and up only, its blocks and chunks counted from
-    there (a left-padded batch; eetq_decode_attention_padded_f16).  Returns
+    there (a left-padded batch; eetq_decode_attention_padded_f16).  ``window`` (host integer >= 1): a sliding window -- batch
+    row b attends the last ``window`` of its valid rows and none below ``kv_start[b]``: the bits of the ``kv_start`` form called
+    with ``max(kv_start, valid length - window)`` (eetq_decode_attention_window_f16).  Returns
     float16 [B, H, D].  fp32 softmax and accumulation; D must be 64 or 128."""
     if query.dtype != torch.float16 or key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
         raise RuntimeError("decode_attention: query and caches must be float16")
@@ -779,9 +792,16 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
         raise RuntimeError("decode_attention: shape / stride mismatch")
     p = _DecodeAttnPrep("decode_attention: ", query, S, None, mask, scaling, splits, kv_len, advance,
                         (query.stride(0), query.stride(1)), key_cache, value_cache)
+    if window is not None:
+        window = _check_window("decode_attention", window)
     if kv_start is not None:
         _check_kv_start("decode_attention", kv_start, query, B)
     with torch.cuda.device(query.device):
+        if window is not None:
+            check(_lib.lib().eetq_decode_attention_window_f16(
+                _ptr(query), _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits,
+                p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(kv_start), window, _optr(advance), _stream_ptr()))
+            return p.out
         if kv_start is not None:
             check(_lib.lib().eetq_decode_attention_padded_f16(
                 _ptr(query), _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits,
@@ -795,12 +815,14 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
 
 @_eager_only
 def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache, value_cache, tickets, slots=None,
-                          mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None, kv_start=None):
+                          mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None, kv_start=None,
+                          window=None):
     """``rotary_embedding_neox_kvcache`` followed by ``decode_attention`` as ONE launch (extension; the decode step of a
     static KV cache).  Bit-identical to that pair in the cache rows written and in the returned [B, H, D] output; the
     rotated query is not written back.  ``tickets``: an int32 device tensor of at least B * H + 1 zeros that the launch
     leaves zeroed (launches that may overlap need their own).  The rotation must cover the whole head.  ``kv_start``: as in
-    ``decode_attention`` (eetq_rope_decode_attention_padded_f16); the new row is still written at its absolute slot."""
+    ``decode_attention`` (eetq_rope_decode_attention_padded_f16); the new row is still written at its absolute slot.
+    ``window``: as in ``decode_attention``, the valid length being the new token's slot + 1 (eetq_rope_decode_attention_window_f16)."""
     for t in (query, key, value, cos_sin_cache, key_cache, value_cache):
         if t.dtype != torch.float16:
             raise RuntimeError("rope_decode_attention: float16 tensors expected")
@@ -826,9 +848,18 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
                            "on the device")
     p = _DecodeAttnPrep("rope_decode_attention: ", query, S, slots, mask, scaling, splits, kv_len, advance,
                         (query.stride(0), key.stride(0), value.stride(0)), key_cache, value_cache)
+    if window is not None:
+        window = _check_window("rope_decode_attention", window)
     if kv_start is not None:
         _check_kv_start("rope_decode_attention", kv_start, query, B)
     with torch.cuda.device(query.device):
+        if window is not None:
+            check(_lib.lib().eetq_rope_decode_attention_window_f16(
+                _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+                cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), _ptr(tickets),
+                B, H, Hkv, S, D, p.splits, p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(kv_start), window,
+                _optr(advance), _stream_ptr()))
+            return p.out
         if kv_start is not None:
             check(_lib.lib().eetq_rope_decode_attention_padded_f16(
                 _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),

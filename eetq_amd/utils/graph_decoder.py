@@ -40,7 +40,7 @@ def left_pad_starts(mask):
 
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
-                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt"):
+                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt", window=None):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -108,7 +108,16 @@ class GraphDecoder:
         compiled operator module; any other value raises ``ValueError``.  ``prefill`` and ``generate(append=True)`` keep the
         prompt kernel.  On an int8 speculative decoder (``kv_bits=8, kv8_append=True``) ``"rows"`` is
         ``appended_static_prefill(int8_rows=True, few_rows_int8=True)`` and ``ops.decode_attention_rows_i8kv`` (the
-        chunk rule is the fp16 rows' and untuned for int8 rows); ``"prompt"`` stays the default there as well."""
+        chunk rule is the fp16 rows' and untuned for int8 rows); ``"prompt"`` stays the default there as well.
+        ``window`` (default ``None``: nothing changes): an integer ``W >= 1`` builds a SLIDING-WINDOW decoder: every
+        forward, captured or eager, runs under ``llama_modules.sliding_window_static(W)``, so a token at cache row p attends rows
+        ``max(0, p - W + 1) .. p`` -- prompts through the windowed MFMA prompt kernel, steps through the windowed decode kernels,
+        the window a kernel argument of the captured graphs.  The cache stays the static ``max_len``-row cache (rows are not
+        recycled); ``generate``, ``prefill(chunk=)``, ``append=True`` and sampling work as without it.  The decode step goes through
+        the attention module instead of the one-call layer.  It needs what ``ragged`` needs -- ``lean``, a fully accelerated model,
+        head size 64 or 128 -- and the MFMA prompt kernel; ``ragged=True`` (no ragged prompt with a window), ``kv_bits=8`` (no window
+        on int8 rows) and ``speculative=k`` (the verify step's kernels have no window) raise ``ValueError``."""
+        self.window = self._check_window(window, model, lean, ragged, kv_bits, speculative)
         if spec_attention not in ("prompt", "rows"):
             raise ValueError("GraphDecoder: spec_attention must be 'prompt' (the MFMA prompt kernel) or 'rows' (the few-row split-KV "
                              "kernel), got %r" % (spec_attention,))
@@ -239,6 +248,38 @@ class GraphDecoder:
                 for _ in range(self.steps_per_graph):
                     self._advance()
 
+    @staticmethod
+    def _check_window(window, model, lean, ragged, kv_bits, speculative):
+        """The checked ``window`` (``None``: off).  Every refusal says which setting and why."""
+        if window is None:
+            return None
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError("GraphDecoder: window must be None (off) or the sliding window's rows, an integer >= 1, got %r" % (window,))
+        if ragged:
+            raise ValueError("GraphDecoder: window=%d with ragged=True: the windowed prompt kernel knows one shared first key only "
+                             "(ragged prompts with a window are not built)" % window)
+        if kv_bits != 16:
+            raise ValueError("GraphDecoder: window=%d needs an fp16 cache (kv_bits=16): the int8 kernels have no sliding window, got "
+                             "kv_bits=%r" % (window, kv_bits))
+        if speculative:
+            raise ValueError("GraphDecoder: window=%d with speculative=%r: the verify step attends k + 1 rows behind the cache with "
+                             "kernels that have no sliding window" % (window, speculative))
+        from .. import ops
+        base = getattr(model, "model", None)
+        layers = getattr(base, "layers", None)
+        if not lean or not layers or not all(getattr(l, "fused_layer_step", False) for l in layers):
+            raise ValueError("GraphDecoder: window=%d needs lean=True and a fully accelerated model (eet_accelerator with fused_attn, "
+                             "fused_mlp and fused_residual): only its attention blocks take a sliding window" % window)
+        for layer in layers:
+            attn = getattr(layer, "self_attn", None)
+            if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
+                raise ValueError("GraphDecoder: window=%d needs attention blocks with head size 64 or 128" % window)
+            if (not getattr(attn, "mfma_prefill", False) or not getattr(attn, "static_prefill", False) or ops.prefill_attention is None
+                    or not ops.prefill_attention_supported(attn.head_dim)):
+                raise ValueError("GraphDecoder: window=%d needs the MFMA prompt kernel (the compiled operator module, "
+                                 "mfma_prefill=True, static_prefill=True): no other prompt path has a sliding window" % window)
+        return int(window)
+
     def _check_speculative(self, speculative, ngram, draft, max_len, spec_sampling=False):
         """The checked ``speculative`` (0: off).  Every refusal says which setting and why."""
         if isinstance(speculative, bool) or not isinstance(speculative, int) or not 0 <= speculative <= 15:
@@ -301,7 +342,11 @@ class GraphDecoder:
         self.s_stats.zero_()
 
     def _promise(self):
-        """``padded_static_batch(s_start)`` on a ragged decoder (every forward, captured or eager, runs inside it), else nothing."""
+        """``padded_static_batch(s_start)`` on a ragged decoder, ``sliding_window_static(window)`` on a windowed one (every forward,
+        captured or eager, runs inside it), else nothing."""
+        if self.window is not None:
+            from ..modules.llama_modules import sliding_window_static
+            return sliding_window_static(self.window)
         if not self.ragged:
             return contextlib.nullcontext()
         from ..modules.llama_modules import padded_static_batch

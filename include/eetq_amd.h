@@ -681,6 +681,26 @@ int eetq_rope_decode_attention_padded_f16(const int64_t* positions, const int64_
                                           int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
                                           int kv_len_bias, const int64_t* kv_start, int64_t* advance, void* stream);
 
+/* The decode entries with a SLIDING WINDOW (extension, added within ABI revision 7): the padded entries plus `window` >= 1, a host
+ * integer (a constant of the model: one captured graph serves a decoder).  Batch row b attends the last `window` of its n valid
+ * rows, and never a row below kv_start[b]: out[b], the cache rows written and every side effect are those of the padded entry
+ * called with kv_start'[b] = max(kv_start[b], n - window), bit for bit, and rows below kv_start' are neither read nor written.
+ * n is the valid length the kernel derives: in the one-launch form slot + 1 (the new token counts; without a new token -- a slot
+ * outside the cache -- clamp(*kv_len + kv_len_bias), or max_positions without kv_len), in the two-launch form clamp(*kv_len +
+ * kv_len_bias) or `positions`.  kv_start may be NULL (all zeros).  window >= n: the padded entry's bits with kv_start as given.  The
+ * two forms stay bit-identical to each other; no launch is added.  Errors as the padded entries (a null kv_start is none), plus
+ * window < 1 (EETQ_ERR_INVALID, nothing launched).  fp16 rows only: the int8 entries have no windowed form. */
+int eetq_decode_attention_window_f16(const void* q, const void* k_cache, const void* v_cache, const void* mask, void* out,
+                                     float* workspace, int batch, int heads, int kv_heads, int positions, int head_dim,
+                                     int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias,
+                                     const int64_t* kv_start, int window, int64_t* advance, void* stream);
+int eetq_rope_decode_attention_window_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                          const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                          void* k_cache, void* v_cache, const void* mask, void* out, float* workspace,
+                                          unsigned* tickets, int batch, int heads, int kv_heads, int max_positions,
+                                          int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                          int kv_len_bias, const int64_t* kv_start, int window, int64_t* advance, void* stream);
+
 /* The int8 KV cache (extension, added within ABI revision 7).  One cache ROW is the head_dim fp16 values of one (batch row, kv
  * head, position); rows are quantised symmetrically, each with a scale of its own:
  *   amax = max_d |x_d| (exact);  s = fp16(fp32(amax) * (1.0f / 127.0f)), one fp32 multiply, round to nearest even;
@@ -775,6 +795,20 @@ int eetq_prefill_attention_dev_f16(const void* q, const void* k, const void* v, 
 int eetq_prefill_attention_padded_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
                                       int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
                                       const int64_t* kv_start, int splits, float scaling, const long* strides, void* stream);
+/* eetq_prefill_attention_dev_f16 with a SLIDING WINDOW (added within ABI revision 7): `window` >= 1 is a host integer.  With keys and
+ * koff = keys - q_tokens as above, query t sits at cache row p = t + koff and attends rows max(0, p - window + 1) .. p: itself and the
+ * window - 1 rows before it.  The key blocks stay blocks of 64 from row 0; a workgroup with first query q0 runs blocks
+ * [jlo, n), jlo = max(0, q0 + koff - window + 1) / 64, and with splits > 1 share i takes [jlo + i m / splits, jlo + (i + 1) m / splits)
+ * of its m = n - jlo blocks.  Two consequences: (a) window >= keys gives the bits of eetq_prefill_attention_dev_f16 for every row, and
+ * in any launch every row with t + koff < window has that entry's bits; (b) no cache row below 64 * (max(0, koff - window + 1) / 64) is
+ * read by the launch -- rows of a lower-edge block below a row's window ARE read and enter the value product with probability 0, so
+ * they must be finite (they are the sequence's own tokens).  kv_len NULL: keys = max_keys (a fresh prompt).  Workspace and splits as
+ * there; callers that follow the library's rule size the shares with eetq_prefill_attention_splits(batch, heads, q_tokens,
+ * min(max_keys, window + min(q_tokens, 128))), an UNTUNED rule.  Errors as there, plus window < 1.  fp16 rows, one shared first key:
+ * there is no windowed form of the per-row first key or of the int8-row entry. */
+int eetq_prefill_attention_window_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                      int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                      int window, int splits, float scaling, const long* strides, void* stream);
 /* The split count eetq_prefill_attention_dev_f16 is tuned for (pure host function; callers size the workspace with it; 1 = unsplit).
  * With g = ceil(q_tokens / 128) * heads * batch workgroups and n = ceil(max_keys / 64) key blocks: the largest power of two s <= 16
  * such that, for every power of two s' <= s, s' g <= 1.25 compute units and n / s' >= 4 (s' g <= half the compute units), 8 (s' g <=
