@@ -10,6 +10,7 @@ projections as ONE launch over concatenated channels (bit-identical to three lau
 ``EETLlamaMLP`` (gate/up as one launch) has no counterpart in llama_modules.py; the reference fuses gate/up only in its
 offline export layer (python/eetq/models/llama.py:39-77).
 """
+import collections
 import contextlib
 import threading
 
@@ -19,12 +20,73 @@ import torch.nn as nn
 from .. import ops
 
 __all__ = ["EETRotaryEmbedding", "EETLlamaAttention", "EETQuantLlamaAttention", "EETLlamaMLP", "fresh_static_prefill",
-           "appended_static_prefill", "padded_static_batch"]
+           "appended_static_prefill", "padded_static_batch", "sliding_window_static"]
 
-_prefill_promise = threading.local()
+
+class _Promise(threading.local):
+    """What the caller has promised for the forwards of this thread (the four context managers below).  The class attributes are
+    what a thread reads before it has promised anything."""
+    fresh = False
+    appended = False
+    int8_rows = False
+    few_rows = False
+    few_rows_int8 = False
+    starts = None      # padded_static_batch: every batch row's first real cache row
+    window = None      # sliding_window_static: the rows a query looks back
+
+
+_prefill_promise = _Promise()
+_PROMISE_FIELDS = ("fresh", "appended", "int8_rows", "few_rows", "few_rows_int8", "starts", "window")
+
+_ROWS = "appended_static_prefill(few_rows=True) (ops.decode_attention_rows)"
+_ROWS8 = "appended_static_prefill(few_rows_int8=True) (ops.decode_attention_rows_i8kv)"
+_ONE_KEY = " knows one shared first key only; it cannot be combined with padded_static_batch (a per-row first key)"
+_NO_WINDOW = " has no sliding window; it cannot be combined with sliding_window_static"
+# two promises that no kernel serves together, whichever of the two is entered inside the other
+_PROMISE_CONFLICTS = (
+    ("few_rows", "starts", _ROWS + _ONE_KEY),
+    ("few_rows_int8", "starts", _ROWS8 + _ONE_KEY),
+    ("few_rows", "window", _ROWS + _NO_WINDOW),
+    ("few_rows_int8", "window", _ROWS8 + _NO_WINDOW),
+    ("starts", "window", "the windowed prompt kernel of sliding_window_static knows one shared first key only; it cannot be combined "
+                         "with padded_static_batch (no ragged prompt with a window)"),
+)
+
+
+def _check_promises(entering, state):
+    """Refuse (``ValueError``) the state that entering the manager ``entering`` would give: its own arguments first, then the
+    pairs of promises."""
+    window = state["window"]
+    if state["few_rows_int8"] and not state["int8_rows"]:
+        raise ValueError("%s: few_rows_int8 (ops.decode_attention_rows_i8kv) is a promise about an int8 cache; it needs "
+                         "int8_rows=True" % entering)
+    if state["few_rows"] and state["int8_rows"]:
+        raise ValueError("%s: few_rows (ops.decode_attention_rows) reads fp16 cache rows only; it cannot be combined with "
+                         "int8_rows" % entering)
+    if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
+        raise ValueError("%s: window must be an integer of at least 1 row, got %r" % (entering, window))
+    for a, b, why in _PROMISE_CONFLICTS:
+        if state[a] is not None and state[a] is not False and state[b] is not None:   # (starts may be a tensor: no ==)
+            raise ValueError("%s: %s" % (entering, why))
 
 
 @contextlib.contextmanager
+def _promised(entering, **fields):
+    """Set ``fields`` of this thread's promise for the body, if the state they give is allowed, and put them back after it."""
+    p = _prefill_promise
+    state = {f: getattr(p, f) for f in _PROMISE_FIELDS}
+    prev = {f: state[f] for f in fields}
+    state.update(fields)
+    _check_promises(entering, state)
+    for f, value in fields.items():
+        setattr(p, f, value)
+    try:
+        yield
+    finally:
+        for f, value in prev.items():
+            setattr(p, f, value)
+
+
 def fresh_static_prefill():
     """The caller's promise for the forwards run inside (per thread): the static KV cache holds NO tokens yet and the prompt is
     unpadded, so a prompt's attention is plain causal attention over its own T tokens.  The attention blocks then write cache
@@ -33,15 +95,9 @@ def fresh_static_prefill():
     flag of the library attention (half the work of a masked pass over the whole pre-allocated cache) and ignore the
     model-level mask.  ``GraphDecoder.generate`` makes this promise; without it a prompt
     on a static cache is attended as transformers does it: every cache row, under the model's mask."""
-    prev = getattr(_prefill_promise, "fresh", False)
-    _prefill_promise.fresh = True
-    try:
-        yield
-    finally:
-        _prefill_promise.fresh = prev
+    return _promised("fresh_static_prefill", fresh=True)
 
 
-@contextlib.contextmanager
 def appended_static_prefill(int8_rows=False, few_rows=False, few_rows_int8=False):
     """The caller's promise for the forwards run inside (per thread): the prompt is unpadded and the static cache's rows
     0 .. counter - 1 are this sequence's real tokens, so a prompt appended behind them attends exactly the rows below the
@@ -71,34 +127,10 @@ def appended_static_prefill(int8_rows=False, few_rows=False, few_rows_int8=False
     kv8_append=True, spec_attention="rows")`` makes it for its verify steps).  Longer pieces keep ``ops.prefill_attention_i8kv``,
     single tokens the decode step; on an fp16 cache the flag changes nothing.  Under ``padded_static_batch`` it raises as
     ``few_rows`` does."""
-    if few_rows_int8 and not int8_rows:
-        raise ValueError("appended_static_prefill: few_rows_int8 (ops.decode_attention_rows_i8kv) is a promise about an int8 cache; "
-                         "it needs int8_rows=True")
-    if few_rows_int8 and _padded_starts() is not None:
-        raise ValueError("appended_static_prefill: few_rows_int8 (ops.decode_attention_rows_i8kv) knows one shared first key only; it "
-                         "cannot run under padded_static_batch (a per-row first key)")
-    if (few_rows or few_rows_int8) and getattr(_prefill_promise, "window", None) is not None:
-        raise ValueError("appended_static_prefill: few_rows / few_rows_int8 (the few-row kernel) has no sliding window; it cannot run "
-                         "under sliding_window_static")
-    if few_rows and int8_rows:
-        raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) reads fp16 cache rows only; it cannot be "
-                         "combined with int8_rows")
-    if few_rows and _padded_starts() is not None:
-        raise ValueError("appended_static_prefill: few_rows (ops.decode_attention_rows) knows one shared first key only; it cannot "
-                         "run under padded_static_batch (a per-row first key)")
-    prev = (getattr(_prefill_promise, "appended", False), getattr(_prefill_promise, "fresh", False),
-            getattr(_prefill_promise, "int8_rows", False), getattr(_prefill_promise, "few_rows", False),
-            getattr(_prefill_promise, "few_rows_int8", False))
-    _prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows = True, False, bool(int8_rows)
-    _prefill_promise.few_rows, _prefill_promise.few_rows_int8 = bool(few_rows), bool(few_rows_int8)
-    try:
-        yield
-    finally:
-        (_prefill_promise.appended, _prefill_promise.fresh, _prefill_promise.int8_rows, _prefill_promise.few_rows,
-         _prefill_promise.few_rows_int8) = prev
+    return _promised("appended_static_prefill", appended=True, fresh=False, int8_rows=bool(int8_rows), few_rows=bool(few_rows),
+                     few_rows_int8=bool(few_rows_int8))
 
 
-@contextlib.contextmanager
 def padded_static_batch(starts):
     """The caller's promise for the forwards run inside (per thread, restored on exit): the batch is LEFT-padded and cache rows
     below ``starts[b]`` (int64 [B] on the device, read by the kernels: it may be a static tensor a captured graph refers to) of
@@ -114,28 +146,13 @@ def padded_static_batch(starts):
     caller passes ``position_ids`` that count from each row's first real token.  Anything the MFMA prompt kernel or the decode
     kernels cannot run (head size, dtype, an int8 cache, a stock attention path) raises ``ValueError`` instead of attending the
     pads."""
-    if starts is not None and getattr(_prefill_promise, "few_rows", False):
-        raise ValueError("padded_static_batch: appended_static_prefill(few_rows=True) is in force, and ops.decode_attention_rows "
-                         "knows one shared first key only (no per-row first key)")
-    if starts is not None and getattr(_prefill_promise, "few_rows_int8", False):
-        raise ValueError("padded_static_batch: appended_static_prefill(few_rows_int8=True) is in force, and "
-                         "ops.decode_attention_rows_i8kv knows one shared first key only (no per-row first key)")
-    if starts is not None and getattr(_prefill_promise, "window", None) is not None:
-        raise ValueError("padded_static_batch: sliding_window_static is in force, and the windowed prompt kernel knows one shared first "
-                         "key only (no ragged prompt with a window)")
-    prev = getattr(_prefill_promise, "starts", None)
-    _prefill_promise.starts = starts
-    try:
-        yield
-    finally:
-        _prefill_promise.starts = prev
+    return _promised("padded_static_batch", starts=starts)
 
 
 def _padded_starts():
-    return getattr(_prefill_promise, "starts", None)
+    return _prefill_promise.starts
 
 
-@contextlib.contextmanager
 def sliding_window_static(window):
     """The caller's promise for the forwards run inside (per thread, restored on exit): attention looks back ``window`` rows -- a
     query at cache row p attends rows ``max(0, p - window + 1) .. p``, itself and the ``window - 1`` rows before it (transformers'
@@ -151,25 +168,99 @@ def sliding_window_static(window):
     Anything that cannot honour the window raises ``ValueError`` instead of attending the whole prefix: an unsupported head size or
     dtype, an int8 cache, the ``few_rows`` promises (the few-row kernel has no window), ``padded_static_batch`` (no ragged prompt
     with a window) and every stock attention path.  ``window=None`` promises nothing."""
-    if window is not None:
-        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
-            raise ValueError("sliding_window_static: window must be an integer of at least 1 row, got %r" % (window,))
-        if _padded_starts() is not None:
-            raise ValueError("sliding_window_static: padded_static_batch is in force, and the windowed prompt kernel knows one shared "
-                             "first key only (no ragged prompt with a window)")
-        if getattr(_prefill_promise, "few_rows", False) or getattr(_prefill_promise, "few_rows_int8", False):
-            raise ValueError("sliding_window_static: appended_static_prefill(few_rows=True / few_rows_int8=True) is in force, and the "
-                             "few-row kernel (ops.decode_attention_rows) has no sliding window")
-    prev = getattr(_prefill_promise, "window", None)
-    _prefill_promise.window = window
-    try:
-        yield
-    finally:
-        _prefill_promise.window = prev
+    return _promised("sliding_window_static", window=window)
 
 
 def _window():
-    return getattr(_prefill_promise, "window", None)
+    return _prefill_promise.window
+
+
+def _decode_step_refusal(promise):   # a single token under `promise` that the decode kernels cannot take
+    return ValueError("EETLlamaAttention: %s needs the library's decode attention on an initialised fp16 static cache (head size 64 "
+                      "or 128, decode_math_attention=True, a mask the kernel understands)" % promise)
+
+
+_Route = collections.namedtuple("_Route", "op fresh extra")   # op: "prompt" | "rows" | "sdpa" | "stock"
+_STOCK = _Route("stock", False, {})
+
+
+def _route_fp16(p, cached, t_len, weights, mfma_ok, rows_ok):
+    """Where ``_attend`` sends ``t_len`` query rows under the promise ``p``.  ``cached``: the rows already lie in an initialised
+    fp16 static cache; ``weights``: the caller wants attention weights; ``mfma_ok``: ``_mfma_prompt_ok``; ``rows_ok``:
+    ``_few_rows_ok``.  Reads no tensor, calls no operator.  "prompt" is ``ops.prefill_attention`` -- ``fresh``: over the ``t_len``
+    rows just written, else over the rows below the device counter; ``extra``: the keyword it is given besides, ``window=`` or
+    ``kv_start=`` -- "rows" ``ops.decode_attention_rows``, "sdpa" causal torch attention over the ``t_len`` rows, "stock" whatever
+    runs without a promise."""
+    promised = p.fresh or p.appended
+    kernel = cached and t_len > 1 and not weights and mfma_ok and promised
+    # a sliding window or a left-padded batch: the MFMA prompt kernel's form for it, or an error -- every other path would attend
+    # the whole prefix or the pads (a single token on a static cache never comes here: forward() hands it to the decode kernels)
+    needs = ("%s needs the MFMA prompt kernel (float16 on the GPU, head size 64 or 128, mfma_prefill=True, the compiled operator "
+             "module) on an initialised fp16 static cache under fresh_static_prefill or appended_static_prefill")
+    if p.window is not None:
+        if not kernel or p.starts is not None or p.few_rows:
+            raise ValueError("EETLlamaAttention: " + needs % "sliding_window_static" + ", without padded_static_batch or few_rows; a "
+                             "single token needs the library's decode attention on such a cache")
+        return _Route("prompt", p.fresh, {"window": p.window})
+    if p.starts is not None:
+        if not kernel:
+            raise ValueError("EETLlamaAttention: " + needs % "padded_static_batch")
+        return _Route("prompt", p.fresh, {"kv_start": p.starts})
+    if not cached or t_len <= 1 or weights or not promised:
+        return _STOCK
+    if p.fresh:
+        # promised: the cache was empty and the prompt is unpadded -> causal attention over the T rows just written, by the
+        # library's own flash kernel on the matrix cores (37 us per layer at 13B shapes against torch's 76) where it can run
+        return _Route("prompt" if mfma_ok else "sdpa", True, {})
+    if p.few_rows and t_len <= 16 and rows_ok:
+        return _Route("rows", False, {})    # promised short: the few-row split-KV kernel
+    # promised: rows 0 .. counter - 1 are this sequence's tokens, the last T of them this prompt's -> the prompt kernel with the
+    # counter as its device length (the causal offset follows from it in the kernel)
+    return _Route("prompt", False, {}) if mfma_ok else _STOCK
+
+
+def _route_int8(p, t_len, rows, supported, table_ok, prompt8_ok, rows8_ok, mfma_ok):
+    """What ``_int8_cache_forward`` does with ``t_len`` query rows on an int8 cache of ``rows`` rows under the promise ``p``, or
+    the refusal: every int8 path is one of the library's kernels, never a stock one.  ``supported``: float16 on the GPU, head size
+    64 or 128, the library's decode attention, no attention weights, the cache's batch; ``table_ok``: the rotation covers the
+    whole head; ``prompt8_ok`` / ``rows8_ok``: ``ops.prefill_attention_i8kv`` (and ``mfma_prefill``) / ``ops.decode_attention_rows_i8kv``
+    are there; ``mfma_ok``: ``_mfma_prompt_ok``.  Reads no tensor, calls no operator.  "decode": the single-token step; "prompt_i8"
+    / "rows_i8": the write behind the device counter, then the int8-row prompt / few-row kernel; "prompt" / "sdpa": the write
+    from row 0, then the fp16 prompt kernel / torch attention on the unquantised rows."""
+    if p.window is not None:
+        raise ValueError("EETLlamaAttention: sliding_window_static needs an fp16 static cache: the int8 kernels have no sliding "
+                         "window")
+    if p.starts is not None:
+        raise ValueError("EETLlamaAttention: padded_static_batch (a left-padded batch) needs an fp16 static cache: the int8 "
+                         "kernels take no per-row first key")
+    if not supported:
+        raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs float16 on the GPU, head size 64 or 128, the "
+                                  "library's decode attention (decode_math_attention=True), no attention weights, and "
+                                  "the batch the cache was allocated for")
+    if not table_ok:
+        raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs the rotation to cover the whole head")
+    if t_len == 1:
+        return "decode"
+    appended8 = p.appended and not p.fresh and p.int8_rows
+    if not appended8 and (not p.fresh or p.appended):   # (fresh_static_prefill inside appended_static_prefill too: kept as it is)
+        raise NotImplementedError("EETLlamaAttention: a prompt on an int8 KV cache must be promised fresh "
+                                  "(fresh_static_prefill: empty cache, unpadded prompt); a prompt appended behind int8 rows "
+                                  "attends quantised rows -- the MFMA prompt kernel reads int8 K and V only under "
+                                  "appended_static_prefill(int8_rows=True) (GraphDecoder(kv8_append=True))")
+    if t_len > rows:
+        raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
+    if not appended8:
+        return "prompt" if mfma_ok else "sdpa"
+    if not prompt8_ok:
+        raise NotImplementedError("EETLlamaAttention: a prompt appended behind int8 rows runs on the MFMA prompt kernel "
+                                  "alone (mfma_prefill=True and the compiled operator module); no stock path reads int8 "
+                                  "K and V")
+    if not (p.few_rows_int8 and 2 <= t_len <= 16):
+        return "prompt_i8"
+    if not rows8_ok:
+        raise NotImplementedError("EETLlamaAttention: appended_static_prefill(few_rows_int8=True) needs "
+                                  "ops.decode_attention_rows_i8kv, which lives in the compiled operator module")
+    return "rows_i8"
 
 
 class EETRotaryEmbedding(nn.Module):
@@ -272,6 +363,10 @@ class _EETAttentionBase(nn.Module):
         return (self.mfma_prefill and ops.prefill_attention is not None and q.is_cuda and q.dtype == torch.float16
                 and ops.prefill_attention_supported(self.head_dim) and k.stride(-1) == 1 and v.stride(-1) == 1)
 
+    def _few_rows_ok(self, q, k, v):      # ... and these few rows to the few-row kernel (ops.decode_attention_rows)?
+        return (ops.decode_attention_rows is not None and q.is_cuda and q.dtype == torch.float16 and self.head_dim in (64, 128)
+                and k.stride(-1) == 1 and v.stride(-1) == 1)
+
     def _int8_cache_forward(self, layer, q, k, v, positions, attention_mask, kwargs):
         """The attention of one forward on an int8 static cache: q [B, T, H, D], k / v [B, T, Hkv, D] (views into the
         projection output, q and k not rotated yet) -> [B, T, H * D].  A single token is one launch (rotation, quantising
@@ -283,25 +378,17 @@ class _EETAttentionBase(nn.Module):
         ``few_rows_int8=True`` as well, a piece of 2 .. 16 rows takes the few-row kernel's int8-row form instead
         (``ops.decode_attention_rows_i8kv``): the same rows, the same arithmetic, other tiles."""
         bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
-        if _window() is not None:
-            raise ValueError("EETLlamaAttention: sliding_window_static needs an fp16 static cache: the int8 kernels have no sliding "
-                             "window")
-        if _padded_starts() is not None:
-            raise ValueError("EETLlamaAttention: padded_static_batch (a left-padded batch) needs an fp16 static cache: the int8 "
-                             "kernels take no per-row first key")
-        if (d not in (64, 128) or not q.is_cuda or q.dtype != torch.float16 or self.decode_math_attention is not True
-                or kwargs.get("output_attentions", False) or layer.keys.shape[0] != bsz
-                or layer.keys.shape[1] != self.num_key_value_heads):
-            raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs float16 on the GPU, head size 64 or 128, the "
-                                      "library's decode attention (decode_math_attention=True), no attention weights, and "
-                                      "the batch the cache was allocated for")
         rows = layer.keys.shape[2]
         self._grow_table(rows)
         table = self.rotary_emb.cos_sin_cache
-        if table.shape[-1] != d:
-            raise NotImplementedError("EETLlamaAttention: an int8 KV cache needs the rotation to cover the whole head")
+        supported = (d in (64, 128) and q.is_cuda and q.dtype == torch.float16 and self.decode_math_attention is True
+                     and not kwargs.get("output_attentions", False) and layer.keys.shape[0] == bsz
+                     and layer.keys.shape[1] == self.num_key_value_heads)
+        route = _route_int8(_prefill_promise, q_len, rows, supported, table.shape[-1] == d,
+                            self.mfma_prefill and ops.prefill_attention_i8kv is not None, ops.decode_attention_rows_i8kv is not None,
+                            q_len > 1 and self._mfma_prompt_ok(q, k, v))
         counter = layer.cumulative_length
-        if q_len == 1:
+        if route == "decode":
             add = self._decode_mask_rows(attention_mask, bsz, rows, q.dtype, q.device)
             if add is False:
                 raise NotImplementedError("EETLlamaAttention: this attention mask has no form the int8 decode step understands")
@@ -316,35 +403,17 @@ class _EETAttentionBase(nn.Module):
                 out = ops.decode_attention_i8kv(q[:, 0], layer.keys, layer.values, layer.scales, mask=add, scaling=self.scaling,
                                                 kv_len=counter, kv_len_bias=1, advance=counter)
             return out.reshape(bsz, q_len, -1)
-        if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False)
-                and getattr(_prefill_promise, "int8_rows", False)):
-            if q_len > rows:
-                raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
-            if not self.mfma_prefill or ops.prefill_attention_i8kv is None:
-                raise NotImplementedError("EETLlamaAttention: a prompt appended behind int8 rows runs on the MFMA prompt kernel "
-                                          "alone (mfma_prefill=True and the compiled operator module); no stock path reads int8 "
-                                          "K and V")
+        if route in ("prompt_i8", "rows_i8"):
             ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales,
                                                          first_row_dev=counter)
-            few = getattr(_prefill_promise, "few_rows_int8", False) and 2 <= q_len <= 16
-            if few and ops.decode_attention_rows_i8kv is None:
-                raise NotImplementedError("EETLlamaAttention: appended_static_prefill(few_rows_int8=True) needs "
-                                          "ops.decode_attention_rows_i8kv, which lives in the compiled operator module")
             counter.add_(q_len)
-            attend = ops.decode_attention_rows_i8kv if few else ops.prefill_attention_i8kv
+            attend = ops.decode_attention_rows_i8kv if route == "rows_i8" else ops.prefill_attention_i8kv
             out = attend(q, layer.keys, layer.values, layer.scales, rows, scaling=self.scaling, kv_len=counter)
             return out.reshape(bsz, q_len, -1)
-        if not getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False):
-            raise NotImplementedError("EETLlamaAttention: a prompt on an int8 KV cache must be promised fresh "
-                                      "(fresh_static_prefill: empty cache, unpadded prompt); a prompt appended behind int8 rows "
-                                      "attends quantised rows -- the MFMA prompt kernel reads int8 K and V only under "
-                                      "appended_static_prefill(int8_rows=True) (GraphDecoder(kv8_append=True))")
-        if q_len > rows:
-            raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
         ops.rotary_embedding_neox_kvcache_prefill_i8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales)
         counter.fill_(q_len)
         kt, vt = k.transpose(1, 2), v.transpose(1, 2)     # [B, Hkv, T, D], strides (T W, D, W, 1): the rotated fp16 K, the V
-        if self._mfma_prompt_ok(q, kt, vt):
+        if route == "prompt":
             out = ops.prefill_attention(q, kt, vt, q_len, scaling=self.scaling)
             return out.reshape(bsz, q_len, -1)
         out = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), kt, vt, is_causal=True, scale=self.scaling,
@@ -452,60 +521,23 @@ class _EETAttentionBase(nn.Module):
         of a static cache that already hold this call's rotated k and v (then k, v and past_key_values are unused), with the
         cache's device counter, already advanced, as a third element."""
         q = q.transpose(1, 2)
-        starts = _padded_starts()
-        window = _window()
-        if window is not None:
-            # a sliding window: the MFMA prompt kernel's windowed form, or an error -- every other path below would attend the
-            # whole prefix (a single token on a static cache never comes here: forward() hands it to the decode kernels)
-            if (starts is not None or cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False)
-                    or not self._mfma_prompt_ok(q, *cached[:2])
-                    or not (getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False))
-                    or getattr(_prefill_promise, "few_rows", False)):
-                raise ValueError("EETLlamaAttention: sliding_window_static needs the MFMA prompt kernel (float16 on the GPU, head "
-                                 "size 64 or 128, mfma_prefill=True, the compiled operator module) on an initialised fp16 static "
-                                 "cache under fresh_static_prefill or appended_static_prefill, without padded_static_batch or "
-                                 "few_rows; a single token needs the library's decode attention on such a cache")
+        t_len = q.shape[2]
+        have = cached is not None
+        route = _route_fp16(_prefill_promise, have, t_len, kwargs.get("output_attentions", False),
+                            have and self._mfma_prompt_ok(q, *cached[:2]), have and self._few_rows_ok(q, *cached[:2]))
+        if have:
             k, v, counter = cached
-            fresh = getattr(_prefill_promise, "fresh", False)
-            out = ops.prefill_attention(q.transpose(1, 2), k, v, q.shape[2] if fresh else k.shape[2], scaling=self.scaling,
-                                        kv_len=None if fresh else counter, window=window)
-            return out.reshape(*input_shape, -1), None
-        if starts is not None:
-            # a left-padded batch: the MFMA prompt kernel with the per-row first key, or an error -- every other path below would
-            # attend the pads
-            if (cached is None or q.shape[2] <= 1 or kwargs.get("output_attentions", False) or not self._mfma_prompt_ok(q, *cached[:2])
-                    or not (getattr(_prefill_promise, "fresh", False) or getattr(_prefill_promise, "appended", False))):
-                raise ValueError("EETLlamaAttention: padded_static_batch needs the MFMA prompt kernel (float16 on the GPU, head "
-                                 "size 64 or 128, mfma_prefill=True, the compiled operator module) on an initialised fp16 static "
-                                 "cache under fresh_static_prefill or appended_static_prefill")
-            k, v, counter = cached
-            fresh = getattr(_prefill_promise, "fresh", False)
-            out = ops.prefill_attention(q.transpose(1, 2), k, v, q.shape[2] if fresh else k.shape[2], scaling=self.scaling,
-                                        kv_len=None if fresh else counter, kv_start=starts)
-            return out.reshape(*input_shape, -1), None
-        if cached is not None:
-            k, v, counter = cached
-            if (getattr(_prefill_promise, "few_rows", False) and getattr(_prefill_promise, "appended", False)
-                    and not getattr(_prefill_promise, "fresh", False) and 2 <= q.shape[2] <= 16
-                    and ops.decode_attention_rows is not None and not kwargs.get("output_attentions", False) and q.is_cuda
-                    and q.dtype == torch.float16 and self.head_dim in (64, 128) and k.stride(-1) == 1 and v.stride(-1) == 1):
-                # promised short: the few-row split-KV kernel, the counter as its device length (as below)
+            if route.op == "prompt":
+                # the library's flash kernel on the matrix cores: the strided query view of the QKV projection, the cache rows as
+                # they lie.  Fresh: the T rows just written (no device length: the host form, unless a keyword follows); else the
+                # rows below the counter, which is the device length
+                out = ops.prefill_attention(q.transpose(1, 2), k, v, t_len if route.fresh else k.shape[2], scaling=self.scaling,
+                                            kv_len=None if route.fresh else counter, **route.extra)
+                return out.reshape(*input_shape, -1), None
+            if route.op == "rows":   # the counter as the few-row kernel's device length
                 out = ops.decode_attention_rows(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
                 return out.reshape(*input_shape, -1), None
-            if (getattr(_prefill_promise, "appended", False) and not getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1
-                    and not kwargs.get("output_attentions", False) and self._mfma_prompt_ok(q, k, v)):
-                # promised: rows 0 .. counter - 1 are this sequence's tokens, the last T of them this prompt's -> the same kernel
-                # with the counter as its device length (the causal offset follows from it in the kernel)
-                out = ops.prefill_attention(q.transpose(1, 2), k, v, k.shape[2], scaling=self.scaling, kv_len=counter)
-                return out.reshape(*input_shape, -1), None
-            if (getattr(_prefill_promise, "fresh", False) and q.shape[2] > 1 and not kwargs.get("output_attentions", False)):
-                # promised: the cache was empty and the prompt is unpadded -> causal attention over the T rows just written
-                t_len = q.shape[2]
-                if self._mfma_prompt_ok(q, k, v):
-                    # the library's own flash kernel on the matrix cores: the strided query view of the QKV projection, the
-                    # cache rows as they lie (ops.prefill_attention; 37 us per layer at 13B shapes against torch's 76)
-                    out = ops.prefill_attention(q.transpose(1, 2), k, v, t_len, scaling=self.scaling)
-                    return out.reshape(*input_shape, -1), None
+            if route.op == "sdpa":
                 out = torch.nn.functional.scaled_dot_product_attention(
                     q, k[:, :, :t_len], v[:, :, :t_len], is_causal=True, scale=self.scaling,
                     enable_gqa=self.num_key_value_groups > 1).transpose(1, 2)
@@ -626,13 +658,9 @@ class EETLlamaAttention(_EETAttentionBase):
         if layer is not None and self.decode_math_attention is True and not kwargs.get("output_attentions", False):
             add = self._decode_mask_rows(attention_mask, bsz, layer.keys.shape[2], hidden_states.dtype, hidden_states.device)
         starts = _padded_starts()   # a left-padded batch: the per-row first key of the decode kernels (None: the plain entries)
-        if starts is not None and q_len == 1 and add is False:
-            raise ValueError("EETLlamaAttention: padded_static_batch needs the library's decode attention on an initialised fp16 "
-                             "static cache (head size 64 or 128, decode_math_attention=True, a mask the kernel understands)")
         window = _window()          # a sliding window: the decode kernels' windowed entries (None: the entries above)
-        if window is not None and q_len == 1 and add is False:
-            raise ValueError("EETLlamaAttention: sliding_window_static needs the library's decode attention on an initialised fp16 "
-                             "static cache (head size 64 or 128, decode_math_attention=True, a mask the kernel understands)")
+        if q_len == 1 and add is False and (starts is not None or window is not None):
+            raise _decode_step_refusal("padded_static_batch" if starts is not None else "sliding_window_static")
         wkw = {} if window is None else {"window": window}
         if add is not False:
             # decode step on an initialised static cache: ONE launch rotates q in place (by its position) and writes the
@@ -670,7 +698,7 @@ class EETLlamaAttention(_EETAttentionBase):
                 table = self.rotary_emb.cos_sin_cache
                 if table.shape[-1] == d:
                     counter = player.cumulative_length
-                    if getattr(_prefill_promise, "fresh", False):   # promised empty: rows 0 .. T - 1, whatever the counter held
+                    if _prefill_promise.fresh:   # promised empty: rows 0 .. T - 1, whatever the counter held
                         ops.rotary_embedding_neox_kvcache_prefill(positions, q, k, v, d, table, player.keys, player.values)
                         counter.fill_(q_len)
                     else:

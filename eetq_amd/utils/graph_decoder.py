@@ -38,6 +38,33 @@ def left_pad_starts(mask):
     return starts
 
 
+def _lean_model(model, lean):
+    """``GraphDecoder._lean`` of a decoder that is not built yet."""
+    base = getattr(model, "model", None)
+    layers = getattr(base, "layers", None)
+    return bool(lean and layers is not None and len(layers) > 0 and hasattr(base, "embed_tokens") and hasattr(base, "norm")
+                and hasattr(model, "lm_head") and all(getattr(l, "fused_layer_step", False) for l in layers))
+
+
+def _require_accelerated(setting, model, lean, prompt_kernel):
+    """What ``ragged``, ``kv_bits=8``, ``window`` and ``speculative`` need of the model (``setting``: the one that asks, as the caller
+    wrote it): the lean layer loop over accelerated layers -- their attention blocks alone take a per-row first key, a window, a
+    device length or int8 rows -- at the head sizes their kernels have; with ``prompt_kernel`` the MFMA prompt kernel as well, the
+    only prompt path with a window or a device length."""
+    if not _lean_model(model, lean):
+        raise ValueError("GraphDecoder: %s needs lean=True and a fully accelerated model (eet_accelerator with fused_attn, "
+                         "fused_mlp and fused_residual): only its attention blocks run what the setting asks for" % setting)
+    from .. import ops
+    for layer in model.model.layers:
+        attn = getattr(layer, "self_attn", None)
+        if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
+            raise ValueError("GraphDecoder: %s needs attention blocks with head size 64 or 128" % setting)
+        if prompt_kernel and (not getattr(attn, "mfma_prefill", False) or not getattr(attn, "static_prefill", False)
+                              or ops.prefill_attention is None or not ops.prefill_attention_supported(attn.head_dim)):
+            raise ValueError("GraphDecoder: %s needs the MFMA prompt kernel (the compiled operator module, mfma_prefill=True, "
+                             "static_prefill=True): no other prompt path runs what the setting asks for" % setting)
+
+
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
                  ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt", window=None):
@@ -155,21 +182,9 @@ class GraphDecoder:
             if self.kv_bits != 16:
                 raise ValueError("GraphDecoder: ragged=True needs an fp16 cache (kv_bits=16): the int8 kernels take no per-row first "
                                  "key, got kv_bits=%r" % (kv_bits,))
-            if not self._lean():
-                raise ValueError("GraphDecoder: ragged=True needs lean=True and a fully accelerated model (eet_accelerator with "
-                                 "fused_attn, fused_mlp and fused_residual): only its attention blocks take a per-row first key")
-            for layer in model.model.layers:
-                attn = getattr(layer, "self_attn", None)
-                if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
-                    raise ValueError("GraphDecoder: ragged=True needs attention blocks with head size 64 or 128")
+            _require_accelerated("ragged=True", model, lean, prompt_kernel=False)
         if self.kv_bits == 8:
-            if not self._lean():
-                raise ValueError("GraphDecoder: kv_bits=8 needs lean=True and a fully accelerated model (eet_accelerator with "
-                                 "fused_attn, fused_mlp and fused_residual): only its attention blocks write an int8 cache")
-            for layer in model.model.layers:
-                attn = getattr(layer, "self_attn", None)
-                if not hasattr(attn, "_int8_cache_layer") or getattr(attn, "head_dim", None) not in (64, 128):
-                    raise ValueError("GraphDecoder: kv_bits=8 needs attention blocks with head size 64 or 128")
+            _require_accelerated("kv_bits=8", model, lean, prompt_kernel=False)
         from transformers import StaticCache
         self.batch = int(batch)
         self.max_len = int(max_len)
@@ -264,20 +279,7 @@ class GraphDecoder:
         if speculative:
             raise ValueError("GraphDecoder: window=%d with speculative=%r: the verify step attends k + 1 rows behind the cache with "
                              "kernels that have no sliding window" % (window, speculative))
-        from .. import ops
-        base = getattr(model, "model", None)
-        layers = getattr(base, "layers", None)
-        if not lean or not layers or not all(getattr(l, "fused_layer_step", False) for l in layers):
-            raise ValueError("GraphDecoder: window=%d needs lean=True and a fully accelerated model (eet_accelerator with fused_attn, "
-                             "fused_mlp and fused_residual): only its attention blocks take a sliding window" % window)
-        for layer in layers:
-            attn = getattr(layer, "self_attn", None)
-            if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
-                raise ValueError("GraphDecoder: window=%d needs attention blocks with head size 64 or 128" % window)
-            if (not getattr(attn, "mfma_prefill", False) or not getattr(attn, "static_prefill", False) or ops.prefill_attention is None
-                    or not ops.prefill_attention_supported(attn.head_dim)):
-                raise ValueError("GraphDecoder: window=%d needs the MFMA prompt kernel (the compiled operator module, "
-                                 "mfma_prefill=True, static_prefill=True): no other prompt path has a sliding window" % window)
+        _require_accelerated("window=%d" % window, model, lean, prompt_kernel=True)
         return int(window)
 
     def _check_speculative(self, speculative, ngram, draft, max_len, spec_sampling=False):
@@ -304,20 +306,8 @@ class GraphDecoder:
                              "device counter with the fp16 prompt kernel, got kv_bits=%r; on an int8 cache kv8_append=True opts in "
                              "to a verify pass that attends the quantised rows (its own among them)"
                              % (speculative, self.kv_bits))
-        if not self._lean():
-            raise ValueError("GraphDecoder: speculative=%d needs lean=True and a fully accelerated model (eet_accelerator with "
-                             "fused_attn, fused_mlp and fused_residual): the verify pass is the lean layer loop over k + 1 rows, "
-                             "and only the accelerated attention blocks attend through the device counter" % speculative)
-        from .. import ops
-        for layer in self.model.model.layers:
-            attn = getattr(layer, "self_attn", None)
-            if not hasattr(attn, "decode_step_state") or getattr(attn, "head_dim", None) not in (64, 128):
-                raise ValueError("GraphDecoder: speculative=%d needs attention blocks with head size 64 or 128" % speculative)
-            if (not getattr(attn, "mfma_prefill", False) or not getattr(attn, "static_prefill", False) or ops.prefill_attention is None
-                    or not ops.prefill_attention_supported(attn.head_dim)):
-                raise ValueError("GraphDecoder: speculative=%d needs the MFMA prompt kernel (the compiled operator module, "
-                                 "mfma_prefill=True, static_prefill=True): no other path attends k + 1 rows behind a device "
-                                 "counter" % speculative)
+        # (the verify pass is the lean layer loop over k + 1 rows, attended through the device counter)
+        _require_accelerated("speculative=%d" % speculative, self.model, self.lean, prompt_kernel=True)
         if int(max_len) < speculative + 1:
             raise ValueError("GraphDecoder: speculative=%d writes %d cache rows per verify step, the cache has %d"
                              % (speculative, speculative + 1, int(max_len)))
@@ -370,10 +360,7 @@ class GraphDecoder:
         """True when every decoder layer is an accelerated one (eet_accelerator with fused_attn / fused_mlp / fused_residual):
         those read positions and the cache's own token counter and need neither the causal mask nor the cos / sin tensors
         the stock ``LlamaModel.forward`` builds on every step (~20 small launches per token)."""
-        base = getattr(self.model, "model", None)
-        layers = getattr(base, "layers", None)
-        return (self.lean and layers is not None and len(layers) > 0 and hasattr(base, "embed_tokens") and hasattr(base, "norm")
-                and hasattr(self.model, "lm_head") and all(getattr(l, "fused_layer_step", False) for l in layers))
+        return _lean_model(self.model, self.lean)
 
     def _logits(self):
         """The last position's logits [batch, vocab] of one decode step on the static tensors."""
