@@ -127,6 +127,13 @@ def _declare(L):
                                              i32, vp, vp],
         "eetq_rope_decode_attention_window_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
                                                   i32, ctypes.c_float, vp, vp, i32, vp, i32, vp, vp],
+        "eetq_prefill_attention_ring_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, ctypes.c_float, vp,
+                                            vp],
+        "eetq_decode_attention_ring_f16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_float, vp, vp, i32, i32, vp, vp],
+        "eetq_rope_decode_attention_ring_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                                                ctypes.c_float, vp, vp, i32, i32, vp, vp],
+        "eetq_rotary_neox_kvcache_ring_f16": [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp],
+        "eetq_rotary_neox_kvcache_prefill_ring_f16": [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp],
         "eetq_prefill_attention_i8kv_f16": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, ctypes.c_float, vp, vp,
                                             vp],
         "eetq_prefill_attention_splits": [i32, i32, i32, i32],
@@ -208,6 +215,8 @@ EXPORTED_SYMBOLS = (
     "eetq_prefill_attention_i8kv_f16",
     "eetq_prefill_attention_padded_f16", "eetq_decode_attention_padded_f16", "eetq_rope_decode_attention_padded_f16",
     "eetq_prefill_attention_window_f16", "eetq_decode_attention_window_f16", "eetq_rope_decode_attention_window_f16",
+    "eetq_prefill_attention_ring_f16", "eetq_decode_attention_ring_f16", "eetq_rope_decode_attention_ring_f16",
+    "eetq_rotary_neox_kvcache_ring_f16", "eetq_rotary_neox_kvcache_prefill_ring_f16",
     "eetq_spec_ngram_draft_i64", "eetq_spec_accept_f16", "eetq_spec_sample_accept_f16",
     "eetq_decode_attention_rows_f16", "eetq_decode_attention_rows_splits", "eetq_decode_attention_rows_max_splits",
     "eetq_decode_attention_rows_workspace_floats", "eetq_decode_attention_rows_i8kv_f16",

@@ -771,7 +771,7 @@ int eetq_silu_mul_f16(const void* gate_up, void* out, int rows, int intermediate
 static int rotary_kvcache_entry(const int64_t* positions, const int64_t* slots, int slot_stride, void* query, const void* key,
                                 const void* value, const void* cos_sin_cache, long table_rows, void* k_cache, void* v_cache,
                                 int batch, int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
-                                int max_positions, void* stream)
+                                int max_positions, void* stream, bool ring = false)
 {
     EETQ_REQUIRE(strides, "null pointer");
     EETQ_REQUIRE(slot_stride == 0 || slot_stride == 1, "slot_stride must be 0 (one slot for the batch) or 1");
@@ -779,7 +779,7 @@ static int rotary_kvcache_entry(const int64_t* positions, const int64_t* slots, 
                                  static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
                                  static_cast<f16*>(k_cache), static_cast<f16*>(v_cache), batch, q_heads, k_heads, head_size,
                                  rot_dim, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
-                                 max_positions, table_rows, static_cast<hipStream_t>(stream));
+                                 max_positions, table_rows, static_cast<hipStream_t>(stream), 0, 0, ring);
 }
 
 int eetq_rotary_neox_kvcache_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query,
@@ -804,7 +804,8 @@ int eetq_rotary_neox_kvcache_bounded_f16(const int64_t* positions, const int64_t
 static int rotary_kvcache_prefill_entry(const int64_t* positions, void* query, const void* key, const void* value,
                                         const void* cos_sin_cache, long table_rows, void* k_cache, void* v_cache, int batch,
                                         int tokens, const int64_t* first_row_dev, int first_row, int q_heads, int k_heads,
-                                        int head_size, int rot_dim, const long* strides, int max_positions, void* stream)
+                                        int head_size, int rot_dim, const long* strides, int max_positions, void* stream,
+                                        bool ring = false)
 {
     EETQ_REQUIRE(strides, "null pointer");
     EETQ_REQUIRE(batch >= 0 && tokens >= 0, "invalid shape");
@@ -814,7 +815,7 @@ static int rotary_kvcache_prefill_entry(const int64_t* positions, void* query, c
                                  static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
                                  static_cast<f16*>(k_cache), static_cast<f16*>(v_cache), batch, q_heads, k_heads, head_size,
                                  rot_dim, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5],
-                                 max_positions, table_rows, static_cast<hipStream_t>(stream), tokens, first_row);
+                                 max_positions, table_rows, static_cast<hipStream_t>(stream), tokens, first_row, ring);
 }
 
 int eetq_rotary_neox_kvcache_prefill_f16(const int64_t* positions, void* query, const void* key, const void* value,
@@ -837,6 +838,28 @@ int eetq_rotary_neox_kvcache_prefill_bounded_f16(const int64_t* positions, void*
     return rotary_kvcache_prefill_entry(positions, query, key, value, cos_sin_cache, table_rows, k_cache, v_cache, batch, tokens,
                                         first_row_dev, first_row, q_heads, k_heads, head_size, rot_dim, strides, max_positions,
                                         stream);
+}
+
+int eetq_rotary_neox_kvcache_ring_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query, const void* key,
+                                      const void* value, const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache,
+                                      int batch, int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                      int ring_rows, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    return rotary_kvcache_entry(positions, slots, slot_stride, query, key, value, cos_sin_cache, table_rows, k_cache, v_cache,
+                                batch, q_heads, k_heads, head_size, rot_dim, strides, ring_rows, stream, true);
+}
+
+int eetq_rotary_neox_kvcache_prefill_ring_f16(const int64_t* positions, void* query, const void* key, const void* value,
+                                              const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache, int batch,
+                                              int tokens, const int64_t* first_row_dev, int first_row, int q_heads, int k_heads,
+                                              int head_size, int rot_dim, const long* strides, int ring_rows, void* stream)
+{
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    EETQ_REQUIRE(tokens <= ring_rows, "a ring cache takes at most its row count of prefill rows per call");
+    return rotary_kvcache_prefill_entry(positions, query, key, value, cos_sin_cache, table_rows, k_cache, v_cache, batch, tokens,
+                                        first_row_dev, first_row, q_heads, k_heads, head_size, rot_dim, strides, ring_rows, stream,
+                                        true);
 }
 
 int eetq_greedy_handover_f16(const void* logits, long row_stride, int vocab, int batch, int64_t* out_tokens, long out_stride,
@@ -1056,6 +1079,40 @@ int eetq_rope_decode_attention_window_f16(const int64_t* positions, const int64_
                                           workspace, tickets, batch, heads, kv_heads, max_positions, head_dim, splits, scaling,
                                           strides, kv_len, kv_len_bias, kv_start, window, advance, table_rows,
                                           static_cast<hipStream_t>(stream));
+}
+
+int eetq_prefill_attention_ring_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                    int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                    int window, int ring_rows, int splits, float scaling, const long* strides, void* stream)
+{
+    return launch_prefill_attention_ring(static_cast<const f16*>(q), static_cast<const f16*>(k), static_cast<const f16*>(v),
+                                         static_cast<f16*>(out), workspace, batch, heads, kv_heads, q_tokens, max_keys, head_dim,
+                                         kv_len, kv_len_bias, window, ring_rows, splits, scaling, strides,
+                                         static_cast<hipStream_t>(stream));
+}
+
+int eetq_decode_attention_ring_f16(const void* q, const void* k_cache, const void* v_cache, void* out, float* workspace, int batch,
+                                   int heads, int kv_heads, int ring_rows, int head_dim, int splits, float scaling,
+                                   const long* strides, const int64_t* kv_len, int kv_len_bias, int window, int64_t* advance,
+                                   void* stream)
+{
+    return launch_attn_decode_ring(static_cast<const f16*>(q), static_cast<const f16*>(k_cache), static_cast<const f16*>(v_cache),
+                                   static_cast<f16*>(out), workspace, batch, heads, kv_heads, ring_rows, head_dim, splits, scaling,
+                                   strides, kv_len, kv_len_bias, window, advance, static_cast<hipStream_t>(stream));
+}
+
+int eetq_rope_decode_attention_ring_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                        const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                        void* k_cache, void* v_cache, void* out, float* workspace, unsigned* tickets, int batch,
+                                        int heads, int kv_heads, int ring_rows, int head_dim, int splits, float scaling,
+                                        const long* strides, const int64_t* kv_len, int kv_len_bias, int window, int64_t* advance,
+                                        void* stream)
+{
+    return launch_rope_attn_decode_ring(positions, slots, slot_stride, static_cast<const f16*>(query), static_cast<const f16*>(key),
+                                        static_cast<const f16*>(value), static_cast<const f16*>(cos_sin_cache),
+                                        static_cast<f16*>(k_cache), static_cast<f16*>(v_cache), static_cast<f16*>(out), workspace,
+                                        tickets, batch, heads, kv_heads, ring_rows, head_dim, splits, scaling, strides, kv_len,
+                                        kv_len_bias, window, advance, table_rows, static_cast<hipStream_t>(stream));
 }
 
 int eetq_decode_attention_i8kv_f16(const void* q, const void* k_cache_i8, const void* v_cache_i8, const void* kv_scales,

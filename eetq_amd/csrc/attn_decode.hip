@@ -27,7 +27,8 @@
 // The fp16 forms also exist with a per-row first key (PAD; eetq_*_padded_f16): batch row b of a left-padded
 // batch attends rows [kv_start[b], valid length), its blocks and chunks counted from there.  The plain instantiations are
 // unchanged.  On top of PAD, a sliding window (WIN; eetq_*_window_f16): the first row becomes
-// max(kv_start[b], valid length - window), one scalar maximum in front of the padded form's arithmetic.
+// max(kv_start[b], valid length - window), one scalar maximum in front of the padded form's arithmetic.  On top of WIN, a ring
+// cache (RING; eetq_*_ring_f16): the same rows counted from the same first row, addressed modulo the cache's rows.
 //
 // What the cache element changes is held by the row-format policy and nothing else does:
 //   KvF16  a lane's share of a row is 16 bytes of K and 16 of V, used as loaded;
@@ -220,6 +221,59 @@ struct KvF16 {
         EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)cos_sin) % 16 == 0,
                      "q, k, v, the caches and the cos|sin table must be 16-byte aligned");
         return check_rows(S, st[5], st[8]);
+    }
+};
+
+// ---- fp16 rows of a ring cache (RING) ----
+// Logical row r of the sequence lives at physical row r mod R.  The chunk code keeps counting rows from the first attended row s0;
+// only the address changes: the descriptors cover the R rows of the ring from physical row 0, relative row i is physical row
+// p0 + i (p0 = s0 mod R), less R where that passes the end -- one compare-subtract per lane, no division --, and rows i >= Sv, which
+// the descriptors of the static forms clip, are sent out of range here (they read as zeros there and here).
+struct KvSrcRing : KvSrc {
+    unsigned p0, rows, valid;  // s0 mod R; R; Sv
+};
+constexpr unsigned kRingOob = 0x7ffffff0u;  // beyond any descriptor (check_rows: one head's rows span less than 2 GiB - 4096 rows)
+
+template <int D, int U0, int UN, int U>
+__device__ __forceinline__ void load_range_ring(KvBlocks<U>& t, const KvSrcRing& s, int blk0, int dblk, int rib)
+{
+    constexpr int BLK = AttnGeo<D>::BLK;
+    static_assert(U0 + UN <= U, "range");
+#pragma unroll
+    for (int u = U0; u < U0 + UN; ++u) {
+        const unsigned i  = (unsigned)((blk0 + u * dblk) * BLK + rib);
+        const unsigned p  = s.p0 + i;
+        const unsigned j  = p >= s.rows ? p - s.rows : p;
+        const bool     in = i < s.valid;
+        t.k[u] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(s.k, (int)(in ? j * s.k_row + s.d0b : kRingOob), 0, kNt));
+        t.v[u] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(s.v, (int)(in ? j * s.v_row + s.d0b : kRingOob), 0, kNt));
+    }
+}
+
+struct KvF16Ring : KvF16 {
+    using Src = KvSrcRing;
+    template <int D, int U0, int UN, bool MASK, int U>
+    static __device__ __forceinline__ void load(Blocks<U>& t, const Src& s, int blk0, int dblk, int rib)
+    {
+        static_assert(!MASK, "no additive mask on a ring");
+        load_range_ring<D, U0, UN>(t, s, blk0, dblk, rib);
+    }
+    // the descriptors of one (batch row, kv head): all R rows from physical row 0; s0: the first attended logical row, Sv: the rows
+    // attended from there (kept <= R: more cannot be live)
+    template <int D>
+    static __device__ __forceinline__ Src make_ring_src(const f16* kbase, const f16* vbase, long k_ss, long v_ss, int R, int s0, int Sv)
+    {
+        Src s;
+        s.k_row = (unsigned)(k_ss * 2);
+        s.v_row = (unsigned)(v_ss * 2);
+        s.d0b   = (unsigned)(((threadIdx.x & 63) % AttnGeo<D>::LPP) * 16);
+        s.k = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(kbase), 0, (int)((unsigned)R * s.k_row), 0x00020000);
+        s.v = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(vbase), 0, (int)((unsigned)R * s.v_row), 0x00020000);
+        s.m = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(kbase), 0, 0, 0x00020000);
+        s.p0    = (unsigned)s0 % (unsigned)R;
+        s.rows  = (unsigned)R;
+        s.valid = (unsigned)Sv;
+        return s;
     }
 };
 
@@ -491,7 +545,9 @@ __device__ __forceinline__ void attn_chunk(const f16x8& qv, float scaling, typen
 // valid length is taken relative to s, so blocks and chunks are counted from the row's first real token (the bits of the plain form
 // on that row alone, its cache moved up by s rows) and no row below s is read.
 // WIN (with PAD): s = max(kv_start[b] or 0, valid length - window) first, then the same: the bits of the PAD form given that start.
-template <class Row, int D, bool MASK, bool LONG, bool PAD, bool WIN = false>
+// RING (with WIN, no kv_start, no mask): S is the ring's row count R and the valid length is logical (it may exceed R); the first
+// row s0 = max(0, n - window) and the rows counted from it are those of the WIN form, their addresses wrap (KvF16Ring).
+template <class Row, int D, bool MASK, bool LONG, bool PAD, bool WIN = false, bool RING = false>
 __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const typename Row::Elem* __restrict__ kc,
                                              const typename Row::Elem* __restrict__ vc, const typename Row::Scales& sc,
                                              const f16* __restrict__ mask, float* __restrict__ ws, float scaling, int S, int groups,
@@ -500,6 +556,7 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
                                              const KvFirstArg<PAD, WIN> kv_start)
 {
     static_assert(!WIN || PAD, "the window is built on the per-row first key");
+    static_assert(!RING || (WIN && !MASK), "the ring is built on the window, without a mask");
     constexpr int NW = kAttnThreads / 64;
     __shared__ float sm_m[NW], sm_l[NW];
     __shared__ __attribute__((aligned(16))) float sm_o[NW * D];
@@ -507,9 +564,12 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
     const int split = blockIdx.x, splits = gridDim.x, h = blockIdx.y, b = blockIdx.z, hk = h / groups;
     const int tid = threadIdx.x, d0 = ((tid & 63) % (D / 8)) * 8;
     const int rib = (tid >> 6) * AttnGeo<D>::PPW + (tid & 63) / AttnGeo<D>::LPP;
-    int  Sv = valid_len(S, kv_len, kv_len_bias);
+    int  Sv = valid_len(RING ? INT32_MAX : S, kv_len, kv_len_bias);
     long s0 = 0;  // PAD: the row's first attended cache row
-    if constexpr (WIN) {
+    if constexpr (RING) {
+        s0 = clamp_kv_start(window_start(0, Sv, kv_start.window), Sv - 1);
+        Sv = min(Sv - (int)s0, S);
+    } else if constexpr (WIN) {
         // a missing kv_start reads a valid address instead and counts as 0 (selects, no branch before the loads)
         const int64_t* p_start = kv_start.kv_start ? kv_start.kv_start + b : reinterpret_cast<const int64_t*>(q);
         const int64_t  start   = kv_start.kv_start ? *p_start : 0;
@@ -521,9 +581,13 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
     }
 
     const f16x8 qv = *reinterpret_cast<const f16x8*>(q + b * q_sb + h * q_sh + d0);
-    const typename Row::Src src =
-        Row::template make_src<D, MASK>(kc + b * k_sb + hk * k_sh + s0 * k_ss, vc + b * v_sb + hk * v_sh + s0 * v_ss, Row::rows(sc, b, hk),
-                                        k_ss, v_ss, Sv, MASK ? mask + b * m_sb + s0 : nullptr);
+    const typename Row::Src src = [&] {
+        if constexpr (RING)
+            return Row::template make_ring_src<D>(kc + b * k_sb + hk * k_sh, vc + b * v_sb + hk * v_sh, k_ss, v_ss, S, (int)s0, Sv);
+        else
+            return Row::template make_src<D, MASK>(kc + b * k_sb + hk * k_sh + s0 * k_ss, vc + b * v_sb + hk * v_sh + s0 * v_ss,
+                                                   Row::rows(sc, b, hk), k_ss, v_ss, Sv, MASK ? mask + b * m_sb + s0 : nullptr);
+    }();
     typename Row::template Blocks<kUA> ta;
     typename Row::template Blocks<kUB> tb;
     Row::template load<D, 0, kUA, MASK>(ta, src, split, splits, rib);
@@ -541,15 +605,16 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
 }
 
 // its two argument lists (the int8 one carries the scale tensor and its strides)
-template <int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false>
+template <int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false, bool RING = false>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
     const f16* __restrict__ q, const f16* __restrict__ kc, const f16* __restrict__ vc, const f16* __restrict__ mask,
     float* __restrict__ ws, float scaling, int S, int groups, long q_sb, long q_sh, long k_sb, long k_sh,
     long k_ss, long v_sb, long v_sh, long v_ss, long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias,
     const KvFirstArg<PAD, WIN> kv_start)
 {
-    attn_partial<KvF16, D, MASK, LONG, PAD, WIN>(q, kc, vc, KvF16::Scales{}, mask, ws, scaling, S, groups, q_sb, q_sh, k_sb, k_sh, k_ss, v_sb,
-                                            v_sh, v_ss, m_sb, kv_len, kv_len_bias, kv_start);
+    attn_partial<std::conditional_t<RING, KvF16Ring, KvF16>, D, MASK, LONG, PAD, WIN, RING>(
+        q, kc, vc, KvF16::Scales{}, mask, ws, scaling, S, groups, q_sb, q_sh, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, m_sb, kv_len, kv_len_bias,
+        kv_start);
 }
 template <int D, bool MASK, bool LONG>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_i8_kernel(
@@ -575,7 +640,13 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_i8_kernel(
 //
 // WIN (with PAD): the same four reads -- a missing kv_start reads the position instead and counts as 0 --, then s = max(s, n - window)
 // with n = slot + 1 (the new token counts; without a new token the valid length), scalar arithmetic, and the PAD code as it is.
-template <class Row, int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false>
+//
+// RING (Row = KvF16Ring, with WIN, no kv_start, no mask; kv_len given): a.S is the ring's row count R.  The new token's logical slot
+// is its position in the sequence, so `have_new` has no upper bound -- a ring is never full; a bad position still drops the step and
+// counts --, the valid length is logical, and s, the rows counted from it and the slot the chunk code sees are the WIN form's.  The
+// bases stay at physical row 0, the loads wrap (KvF16Ring) and the new row is written at slot mod R = (s mod R) + (slot - s), less R
+// where that passes the end.  The fourth scalar read is the position again, unused: the batch and its one wait are the WIN form's.
+template <class Row, int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false, bool RING = false>
 __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const int64_t* __restrict__ kv_len,
                                                                         const int64_t* __restrict__ slots,
                                                                         const int64_t* __restrict__ positions,
@@ -584,6 +655,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
                                                                         const typename Row::template RopeArgs<PAD, WIN> a)
 {
     static_assert(!WIN || PAD, "the window is built on the per-row first key");
+    static_assert(!RING || (WIN && !MASK), "the ring is built on the window, without a mask");
     constexpr int LPP = D / 8, NW = kAttnThreads / 64;
     __shared__ float    sm_m[NW], sm_l[NW];
     __shared__ __attribute__((aligned(16))) float sm_o[NW * D];
@@ -620,15 +692,15 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     ATTN_ROW_STAMP(1);
     // a slot outside the cache is neither written nor attended, and (like the two-launch form) nothing is rotated then
     // (no upper bound on rpos here, unlike the two-launch form: launch_rope_attn's table_rows)
-    const bool have_new = slot64 >= 0 && slot64 < a.S && rpos >= 0;
+    const bool have_new = slot64 >= 0 && slot64 < (RING ? (int64_t)INT32_MAX : (int64_t)a.S) && rpos >= 0;
     const int  slot = have_new ? (int)slot64 : -1;
     // a full cache (or a bad position) used to be silent: count the dropped steps (eetq_decode_dropped_steps)
     if (!have_new && split == 0 && h == 0 && threadIdx.x == 0) atomicAdd(&g_attn_dropped, 1u);
-    const int  Sv_all = kv_len ? max(0, (int)min((int64_t)a.S, filled + a.kv_len_bias)) : a.S;
+    const int  Sv_all = kv_len ? max(0, (int)min((int64_t)(RING ? INT32_MAX : a.S), filled + a.kv_len_bias)) : a.S;
     if constexpr (WIN) start64 = window_start(a.kv_start ? start64 : 0, have_new ? slot + 1 : Sv_all, a.window);
     // PAD: everything the chunk code sees is relative to the row's first attended row s0 (scalar arithmetic, no branch)
     const long s0     = PAD ? clamp_kv_start(start64, have_new ? slot : Sv_all - 1) : 0;
-    const int  Sv     = PAD ? max(0, Sv_all - (int)s0) : Sv_all;
+    const int  Sv     = RING ? min(max(0, Sv_all - (int)s0), a.S) : PAD ? max(0, Sv_all - (int)s0) : Sv_all;
     const int  slot_c = PAD && have_new ? slot - (int)s0 : slot;
 
     // Memory queue order (a wave's loads return in order): the new token and its cos | sin row first, then the chunk's first
@@ -643,9 +715,15 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     const f16*  cs = a.cos_sin + (have_new ? rpos : 0) * D + (d0 < D / 2 ? d0 : d0 - D / 2);
     const f16x8 rc = *reinterpret_cast<const f16x8*>(cs), rs = *reinterpret_cast<const f16x8*>(cs + D / 2);
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler sinks these seven loads below the block loads otherwise)
-    const typename Row::Src src = Row::template make_src<D, MASK>(
-        kc + b * a.kc_sb + hk * a.kc_sh + s0 * a.kc_ss, vc + b * a.vc_sb + hk * a.vc_sh + s0 * a.vc_ss, Row::rows(Row::scales(a), b, hk),
-        a.kc_ss, a.vc_ss, Sv, MASK ? a.mask + b * a.m_sb + s0 : nullptr);
+    const typename Row::Src src = [&] {
+        if constexpr (RING)
+            return Row::template make_ring_src<D>(kc + b * a.kc_sb + hk * a.kc_sh, vc + b * a.vc_sb + hk * a.vc_sh, a.kc_ss, a.vc_ss, a.S,
+                                                  (int)s0, Sv);
+        else
+            return Row::template make_src<D, MASK>(kc + b * a.kc_sb + hk * a.kc_sh + s0 * a.kc_ss,
+                                                   vc + b * a.vc_sb + hk * a.vc_sh + s0 * a.vc_ss, Row::rows(Row::scales(a), b, hk),
+                                                   a.kc_ss, a.vc_ss, Sv, MASK ? a.mask + b * a.m_sb + s0 : nullptr);
+    }();
     const int   rib = (tid >> 6) * AttnGeo<D>::PPW + lane / LPP;
     typename Row::template Blocks<kUA> ta;
     typename Row::template Blocks<kUB> tb;
@@ -659,13 +737,29 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     typename Row::New nw;
     Row::template make_new<LPP>(nw, knew, vnew);
     // the cache row of the new token: once per kv head, by one position group of the head's first workgroup
-    if (have_new && split == 0 && h == hk * a.groups && tid < LPP) Row::store_new(a, kc, vc, b, hk, slot, nw, d0);
+    int wslot = slot;  // RING: the physical row of the new token
+    if constexpr (RING) {
+        const unsigned p = src.p0 + (unsigned)slot_c;
+        wslot = (int)(p >= src.rows ? p - src.rows : p);
+    }
+    if (have_new && split == 0 && h == hk * a.groups && tid < LPP) Row::store_new(a, kc, vc, b, hk, wslot, nw, d0);
     ATTN_ROW_STAMP(2);
     float M, L, O;
     attn_chunk<Row, D, true, MASK, LONG>(qv, a.scaling, ta, tb, src, split, splits, Sv, slot_c, nw, sm_m, sm_l, sm_o, M, L, O);
 
     ATTN_ROW_STAMP(3);
     head_handoff<D>(a, split, splits, h, b, H, M, L, O, sm_o, &sm_ticket);
+}
+
+// what the decode entries of a ring cache refuse (S: the ring's rows R)
+inline int check_ring(int R, int window, const int64_t* kv_start, const f16* mask, const int64_t* kv_len)
+{
+    EETQ_REQUIRE(window >= 1, "the attention window must be at least 1 row");
+    EETQ_REQUIRE(R >= window, "a ring cache must have at least `window` rows (the live rows of a decode step)");
+    EETQ_REQUIRE(!kv_start, "ring and kv_start exclude each other (no ragged ring)");
+    EETQ_REQUIRE(!mask, "ring and an additive mask exclude each other (the mask row would need the same wrap)");
+    EETQ_REQUIRE(kv_len, "a ring cache needs the device length kv_len (its valid length is logical, not the capacity)");
+    return EETQ_OK;
 }
 
 // f(D, MASK, LONG as integral constants) for the launch's head_dim, mask and capacity: the instantiation ladder
@@ -682,15 +776,15 @@ int dispatch_attn(int D, bool mask, int S, int splits, const char* bad_head_dim,
     return fail(EETQ_ERR_UNSUPPORTED, bad_head_dim);
 }
 
-template <int D, bool MASK, bool LONG, bool PAD, bool WIN>
+template <int D, bool MASK, bool LONG, bool PAD, bool WIN, bool RING>
 void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const f16* k, const f16* v, const KvF16::Scales&, const f16* mask,
                     float* ws, float scaling, int S, int groups, const long* st, const int64_t* kv_len, int kv_len_bias,
                     KvFirstArg<PAD, WIN> kv_start)
 {
-    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG, PAD, WIN>, grid, dim3(kAttnThreads), 0, stream, q, k, v, mask, ws, scaling, S,
+    launch_kernel(attn_decode_partial_kernel<D, MASK, LONG, PAD, WIN, RING && !MASK>, grid, dim3(kAttnThreads), 0, stream, q, k, v, mask, ws, scaling, S,
                   groups, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], kv_len, kv_len_bias, kv_start);
 }
-template <int D, bool MASK, bool LONG, bool PAD, bool WIN>
+template <int D, bool MASK, bool LONG, bool PAD, bool WIN, bool RING>
 void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const int8_t* k, const int8_t* v, const KvI8::Scales& sc,
                     const f16* mask, float* ws, float scaling, int S, int groups, const long* st, const int64_t* kv_len,
                     int kv_len_bias, NoKvStart)
@@ -700,18 +794,22 @@ void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const int8_t* k
 }
 
 // the two-launch form over either row format; strides: q_b, q_h, the cache's six, mask_b, out_b, out_h
-template <class Row, bool PAD, bool WIN = false>
+template <class Row, bool PAD, bool WIN = false, bool RING = false>
 int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::Elem* v, const typename Row::Scales& sc, const f16* mask,
                 f16* out, float* ws, int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* st,
                 const int64_t* kv_len, int kv_len_bias, int64_t* advance, hipStream_t stream, KvFirstArg<PAD, WIN> kv_start)
 {
     EETQ_REQUIRE(q && k && v && out && ws && st, "null pointer");
     EETQ_REQUIRE(B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && S > 0 && splits > 0 && splits <= S, "invalid attention shape");
+    if constexpr (RING) {
+        const int rc = check_ring(S, kv_start.window, kv_start.kv_start, mask, kv_len);
+        if (rc != EETQ_OK) return rc;
+    }
     const int rc = Row::check_two_launch(q, k, v, sc, S, st);
     if (rc != EETQ_OK) return rc;
     return dispatch_attn(D, mask != nullptr, S, splits, Row::kBadHeadDim, [&](auto d, auto m, auto l) {
         constexpr int DD = decltype(d)::value;
-        launch_partial<DD, decltype(m)::value, decltype(l)::value, PAD, WIN>(dim3(splits, H, B), stream, q, k, v, sc, mask, ws, scaling, S,
+        launch_partial<DD, decltype(m)::value, decltype(l)::value, PAD, WIN, RING>(dim3(splits, H, B), stream, q, k, v, sc, mask, ws, scaling, S,
                                                                         H / Hkv, st, kv_len, kv_len_bias, kv_start);
         EETQ_TRY_HIP(hipGetLastError());
         launch_kernel(attn_decode_merge_kernel<DD>, dim3(H, B), dim3(kAttnThreads), 0, stream, (const float*)ws, out, splits, st[9],
@@ -723,7 +821,7 @@ int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::E
 unsigned long long* g_attn_stamps = nullptr;  // process-wide diagnostic hook (not thread-safe by design)
 
 // the one-launch form over either row format; st: q_b, k_b, v_b, the cache's six, mask_b, out_b, out_h
-template <class Row, bool PAD, bool WIN = false>
+template <class Row, bool PAD, bool WIN = false, bool RING = false>
 int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k, const f16* v,
                      const f16* cos_sin, typename Row::Elem* kc, typename Row::Elem* vc, const typename Row::Scales& sc,
                      const f16* mask, f16* out, float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits,
@@ -737,6 +835,10 @@ int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_st
     // validated, not yet enforced on the device: with the compare in have_new the attention term of the decode budget measured
     // above the parent's run-to-run spread, so the kernel is as it was
     EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    if constexpr (RING) {
+        const int rc = check_ring(S, window, kv_start, mask, kv_len);
+        if (rc != EETQ_OK) return rc;
+    }
     const int rc = Row::check_one_launch(q, k, v, cos_sin, kc, vc, sc, S, st);
     if (rc != EETQ_OK) return rc;
     typename Row::template RopeArgs<PAD, WIN> a;
@@ -752,8 +854,10 @@ int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_st
     a.S = S, a.groups = H / Hkv, a.scaling = scaling;
     a.stamps = Row::kStamps ? g_attn_stamps : nullptr;
     return dispatch_attn(D, mask != nullptr, S, splits, Row::kBadHeadDim, [&](auto d, auto m, auto l) {
-        launch_kernel(rope_attn_decode_kernel<Row, decltype(d)::value, decltype(m)::value, decltype(l)::value, PAD, WIN>, dim3(splits, H, B),
-                      dim3(kAttnThreads), 0, stream, kv_len, slots, positions, kc, vc, a);
+        // (a ring takes no mask -- check_ring --: its MASK forms are never launched and are built as the plain row policy's)
+        constexpr bool M = decltype(m)::value, RG = RING && !M;
+        launch_kernel(rope_attn_decode_kernel<std::conditional_t<RG, KvF16Ring, Row>, decltype(d)::value, M, decltype(l)::value, PAD, WIN, RG>,
+                      dim3(splits, H, B), dim3(kAttnThreads), 0, stream, kv_len, slots, positions, kc, vc, a);
         return check_hip(hipGetLastError(), Row::kOneLaunch);
     });
 }
@@ -801,6 +905,26 @@ int launch_rope_attn_decode_window(const int64_t* positions, const int64_t* slot
     return launch_rope_attn<KvF16, true, true>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, {}, mask, out, ws, tickets, B, H,
                                                Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, kv_start, advance, table_rows,
                                                stream, window);
+}
+
+// the windowed decode entries over a RING cache of S = R rows: logical row r at physical row r mod R, kv_len the logical length; the
+// bits of the windowed entries on a static cache that holds the same logical rows.  R >= window, no kv_start, no mask.
+int launch_attn_decode_ring(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int S, int D,
+                            int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias, int window,
+                            int64_t* advance, hipStream_t stream)
+{
+    return launch_attn<KvF16, true, true, true>(q, k, v, {}, nullptr, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len,
+                                                kv_len_bias, advance, stream, KvWindow{nullptr, window});
+}
+
+int launch_rope_attn_decode_ring(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                 const f16* v, const f16* cos_sin, f16* kc, f16* vc, f16* out, float* ws, unsigned* tickets, int B,
+                                 int H, int Hkv, int S, int D, int splits, float scaling, const long* st, const int64_t* kv_len,
+                                 int kv_len_bias, int window, int64_t* advance, long table_rows, hipStream_t stream)
+{
+    return launch_rope_attn<KvF16, true, true, true>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, {}, nullptr, out, ws,
+                                                     tickets, B, H, Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, nullptr, advance,
+                                                     table_rows, stream, window);
 }
 
 int launch_attn_decode_i8(const f16* q, const int8_t* k, const int8_t* v, const f16* scales, const f16* mask, f16* out, float* ws,

@@ -21,7 +21,7 @@
 // architectural file, no accumulator copies).    Blocks beyond a wave's last query row are skipped by that wave; heavy query blocks are
 // dispatched first (1-D grid ordered by weight).
 // The device-length and split forms also run over an int8 KV cache (KV8, kv_i8.hpp), with a per-row first key (PAD) and with a
-// sliding window (WIN): see the comment above the kernel.
+// sliding window (WIN), the latter also over a ring cache (RING): see the comment above the kernel.
 #include <algorithm>
 #include <type_traits>
 
@@ -70,11 +70,18 @@ struct PrefillPadArgs : PrefillDevArgs {
 struct PrefillWinArgs : PrefillDevArgs {
     int window;   // >= 1, a host constant of the model
 };
-template <int MODE, bool KV8, bool PAD = false, bool WIN = false>
+// The ring cache (RING, on top of WIN): k and v are rings of 64 * ring_blocks rows, logical row r at physical row
+// r mod (64 * ring_blocks).  Behind the windowed arguments, which keep their kernarg block.
+struct PrefillRingArgs : PrefillWinArgs {
+    int ring_blocks;   // R / 64 >= 1
+};
+template <int MODE, bool KV8, bool PAD = false, bool WIN = false, bool RING = false>
 using PrefillKernArgs = std::conditional_t<
-    WIN, PrefillWinArgs,
-    std::conditional_t<PAD, PrefillPadArgs,
-                       std::conditional_t<KV8, PrefillDevArgs8, std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>>>;
+    RING, PrefillRingArgs,
+    std::conditional_t<WIN, PrefillWinArgs,
+                       std::conditional_t<PAD, PrefillPadArgs,
+                                          std::conditional_t<KV8, PrefillDevArgs8,
+                                                             std::conditional_t<MODE == kPfHost, PrefillArgs, PrefillDevArgs>>>>>;
 
 // MODE kPfHost: keys and causal offset from the host (the fresh prompt's path, unchanged).  kPfDev: every workgroup reads the length
 // at entry -- one scalar load -- and forms Tk and koff itself; kend, nblk, the descriptors' range, `active` and `edge` follow, the
@@ -108,9 +115,19 @@ using PrefillKernArgs = std::conditional_t<
 // plain form; so are, in any launch, the rows with t + koff < W (their workgroup starts at block 0 and their wave skips nothing the
 // plain form attends).  No row below 64 (max(0, koff - W + 1) / 64) is read by the launch; rows of a lower-edge block below a row's
 // window are read and enter the value product with probability 0 (they must be finite).
-template <int D, int MODE, bool KV8 = false, bool PAD = false, bool WIN = false>
-__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8, PAD, WIN> a_in)
+//
+// RING (with WIN): Tk, koff, the key-block grid, jlo, the shares, the wave skip and both mask edges stay in LOGICAL rows and may exceed
+// the ring; only the address of a key block changes.  The descriptors cover the R = 64 ring_blocks rows of the ring, and block j is
+// fetched from physical block j mod ring_blocks (R % 64 == 0: a block never straddles the ring's end): blocks are fetched in order,
+// so the physical block is a counter that starts at j0 mod ring_blocks -- the launch's one division -- and wraps with one scalar
+// compare, in front of the tile offset that rides in the loads' scalar operand.  What the descriptor clipped in the static forms --
+// the rows of the upper-edge block at and beyond Tk -- are rows of the ring here, stale or never written: they are masked exactly
+// as the rows below a window are and enter the value product with probability 0, so every ring row must be finite.  The host keeps
+// R >= W + Tq + 62: no key block the launch reads holds a row the call's own cache write has replaced.
+template <int D, int MODE, bool KV8 = false, bool PAD = false, bool WIN = false, bool RING = false>
+__global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const PrefillKernArgs<MODE, KV8, PAD, WIN, RING> a_in)
 {
+    static_assert(!RING || WIN, "the ring rides on the window");
     static_assert(!KV8 || MODE != kPfHost, "the int8-row form takes the device-length arguments");
     static_assert(!PAD || (MODE != kPfHost && !KV8), "the per-row first key rides on the device-length arguments, fp16 rows");
     static_assert(!WIN || (MODE != kPfHost && !KV8 && !PAD), "the window rides on the device-length arguments, fp16 rows, one first key");
@@ -203,10 +220,12 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
         srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a_in.scales + b * a_in.s_sb + hk * a_in.s_sh), 0,
                                                 (int)((unsigned)a.Tk * (unsigned)a_in.s_ss * 2u), 0x00020000);
     } else {
+        unsigned rows = (unsigned)a.Tk;
+        if constexpr (RING) rows = (unsigned)(a_in.ring_blocks * kPfBN);   // the whole ring
         krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.k + b * a.k_sb + hk * a.k_sh), 0,
-                                                (int)((unsigned)a.Tk * (unsigned)a.k_ss * 2u), 0x00020000);
+                                                (int)(rows * (unsigned)a.k_ss * 2u), 0x00020000);
         vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.v + b * a.v_sb + hk * a.v_sh), 0,
-                                                (int)((unsigned)a.Tk * (unsigned)a.v_ss * 2u), 0x00020000);
+                                                (int)(rows * (unsigned)a.v_ss * 2u), 0x00020000);
         srs = krs;   // not used
     }
 
@@ -240,7 +259,13 @@ __global__ __launch_bounds__(kPfThreads, 2) void prefill_attn_kernel(const Prefi
     const int kvo = p4 * krow_b + c16 * CB, vvo = p4 * vrow_b + c16 * CB;  // constant; tile and row offsets ride in the scalar operand
     int srow_b = 0, svo = 0;
     if constexpr (KV8) srow_b = (int)(a_in.s_ss * 2), svo = p4 * srow_b;
+    int pj = 0;   // RING: the physical block of the next fetch (fetches go block by block from j0)
+    if constexpr (RING) pj = j0 % a_in.ring_blocks;
     auto fetch = [&](int j) {
+        if constexpr (RING) {
+            j  = pj;
+            pj = pj + 1 == a_in.ring_blocks ? 0 : pj + 1;
+        }
 #pragma unroll
         for (int r = 0; r < NLD; ++r) {
             if constexpr (KV8) {
@@ -562,8 +587,8 @@ namespace {
 // The one launch path of the device forms (plain, per-row first key, int8 rows).  `a` arrives with the form's own fields set
 // (kv_start; the scales), `front` runs the form's own argument checks -- every form has them between the two requirements on top
 // and the workspace's --, what1 / whatn name the form when a launch fails.  k and v: the int8 form's rows as they go into the struct.
-template <bool KV8, bool PAD, bool WIN = false, class Front>
-int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD, WIN>& a, Front front, const f16* q, const f16* k, const f16* v, f16* out, float* ws,
+template <bool KV8, bool PAD, bool WIN = false, bool RING = false, class Front>
+int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD, WIN, RING>& a, Front front, const f16* q, const f16* k, const f16* v, f16* out, float* ws,
                          int B, int H, int Hkv, int Tq, int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int splits,
                          float scaling, const long* st, hipStream_t stream, const char* what1, const char* whatn)
 {
@@ -579,19 +604,19 @@ int launch_prefill_forms(PrefillKernArgs<kPfDev, KV8, PAD, WIN>& a, Front front,
     const dim3 grid((unsigned)wgs), block(kPfThreads);
     if (splits == 1) {
         if (D == 128)
-            launch_kernel(prefill_attn_kernel<128, kPfDev, KV8, PAD, WIN>, grid, block, 0, stream, a);
+            launch_kernel(prefill_attn_kernel<128, kPfDev, KV8, PAD, WIN, RING>, grid, block, 0, stream, a);
         else
-            launch_kernel(prefill_attn_kernel<64, kPfDev, KV8, PAD, WIN>, grid, block, 0, stream, a);
+            launch_kernel(prefill_attn_kernel<64, kPfDev, KV8, PAD, WIN, RING>, grid, block, 0, stream, a);
         return check_hip(hipGetLastError(), what1);
     }
     const long rows = (long)B * H * Tq, threads = rows * (D / 4);
     EETQ_REQUIRE((threads + 255) / 256 < (1L << 31), "too many workgroups");
     const dim3 mgrid((unsigned)((threads + 255) / 256));
     if (D == 128) {
-        launch_kernel(prefill_attn_kernel<128, kPfSplit, KV8, PAD, WIN>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<128, kPfSplit, KV8, PAD, WIN, RING>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<128>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     } else {
-        launch_kernel(prefill_attn_kernel<64, kPfSplit, KV8, PAD, WIN>, grid, block, 0, stream, a);
+        launch_kernel(prefill_attn_kernel<64, kPfSplit, KV8, PAD, WIN, RING>, grid, block, 0, stream, a);
         launch_kernel(prefill_merge_kernel<64>, mgrid, dim3(256), 0, stream, (const float*)ws, out, rows, splits, Tq, H, st[9], st[10], st[11]);
     }
     return check_hip(hipGetLastError(), whatn);
@@ -649,6 +674,31 @@ int launch_prefill_attention_window(const f16* q, const f16* k, const f16* v, f1
     return launch_prefill_forms<false, false, true>(a, front, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D, kv_len, kv_len_bias, splits,
                                                     scaling, st, stream, "prefill_attn_kernel (window) launch",
                                                     "prefill_attn_kernel (window, split) launch");
+}
+
+// launch_prefill_attention_window over a RING cache of ring_rows rows (the RING form above): logical row r at physical row
+// r mod ring_rows; max_keys and kv_len count logical rows.  ring_rows % 64 == 0 and ring_rows >= window + Tq + 62.
+int launch_prefill_attention_ring(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                  int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int window, int ring_rows, int splits,
+                                  float scaling, const long* st, hipStream_t stream)
+{
+    PrefillRingArgs a;
+    a.window      = std::min(window, std::max(max_keys, 1));
+    a.ring_blocks = ring_rows / kPfBN;
+    auto front = [&] {
+        EETQ_REQUIRE(ring_rows > 0 && ring_rows % kPfBN == 0, "a ring cache behind the prompt kernel must have a multiple of 64 rows");
+        const int rc = check_prefill_common(q, k, v, out, B, H, Hkv, Tq, ring_rows, D, st);
+        if (rc != EETQ_OK) return rc;
+        EETQ_REQUIRE(window >= 1, "the attention window must be at least 1 row");
+        EETQ_REQUIRE(max_keys <= (1 << 30), "max_keys must not exceed 2^30 logical rows");
+        EETQ_REQUIRE((long)ring_rows >= (long)window + Tq + 62,
+                     "a ring cache behind the prompt kernel must have at least window + query rows + 62 rows (a launch must not read "
+                     "key blocks its own rows have replaced)");
+        return (int)EETQ_OK;
+    };
+    return launch_prefill_forms<false, false, true, true>(a, front, q, k, v, out, ws, B, H, Hkv, Tq, max_keys, D, kv_len, kv_len_bias,
+                                                          splits, scaling, st, stream, "prefill_attn_kernel (ring) launch",
+                                                          "prefill_attn_kernel (ring, split) launch");
 }
 
 // launch_prefill_attention_dev over an int8 cache (kv_i8.hpp): st as there with the k / v entries in BYTES, sst {batch, head, row} of

@@ -349,6 +349,10 @@ int    launch_prefill_attention_padded(const f16* q, const f16* k, const f16* v,
 int    launch_prefill_attention_window(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
                                        int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int window, int splits, float scaling,
                                        const long* st, hipStream_t stream);
+// ... over a ring cache of ring_rows rows (% 64 == 0, >= window + Tq + 62): logical row r at physical row r mod ring_rows
+int    launch_prefill_attention_ring(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int Tq,
+                                     int max_keys, int D, const int64_t* kv_len, int kv_len_bias, int window, int ring_rows, int splits,
+                                     float scaling, const long* st, hipStream_t stream);
 int    prefill_attention_splits(int B, int H, int Tq, int max_keys);
 int    prefill_attention_max_splits();
 size_t prefill_attention_workspace_floats(int B, int H, int Tq, int D, int splits);
@@ -388,10 +392,20 @@ int launch_rope_attn_decode_window(const int64_t* positions, const int64_t* slot
                                    const long* strides, const int64_t* kv_len, int kv_len_bias, const int64_t* kv_start, int window,
                                    int64_t* advance, long table_rows, hipStream_t stream);
 
+// the windowed decode entries over a ring cache of S = R >= window rows: kv_len (required) counts logical rows, no kv_start, no mask
+int launch_attn_decode_ring(const f16* q, const f16* k, const f16* v, f16* out, float* ws, int B, int H, int Hkv, int S, int D,
+                            int splits, float scaling, const long* strides, const int64_t* kv_len, int kv_len_bias, int window,
+                            int64_t* advance, hipStream_t stream);
+int launch_rope_attn_decode_ring(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                                 const f16* v, const f16* cos_sin, f16* kc, f16* vc, f16* out, float* ws, unsigned* tickets, int B,
+                                 int H, int Hkv, int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                                 int kv_len_bias, int window, int64_t* advance, long table_rows, hipStream_t stream);
+
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,
                           const f16* cache, f16* kcache, f16* vcache, int batch, int q_heads, int k_heads, int head_size, int rot_dim, long q_stride,
                           long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream, int tokens = 0,
-                          int first_row = 0);  // tokens > 0: the prefill form (batch * tokens blocks, rows first_row + t)
+                          int first_row = 0,    // tokens > 0: the prefill form (batch * tokens blocks, rows first_row + t)
+                          bool ring = false);   // a ring cache of max_pos rows: row mod max_pos, no upper bound on the row
 
 // the int8 KV cache (kv_i8.hpp): decode attention over int8 rows (attn_decode.hip; strides as the fp16 launchers' with the cache
 // strides in bytes, scale_strides {batch, head, row} in fp16 elements) and the quantising prompt / single-token write (norm_rope.hip)

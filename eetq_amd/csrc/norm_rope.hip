@@ -149,7 +149,9 @@ __global__ void silu_mul_glu8_kernel(const f16* __restrict__ gu, f16* __restrict
 // VEC (round 6): rot_dim == head_size, head_size % 16 == 0 and every pointer / stride a multiple of 8 elements -> eight channels per
 // thread through 16-byte loads and stores (the scalar form moved a prompt's 62 MB per layer at 3.1 TB/s: 20 us at 1 024 tokens).
 // The same fp16 products and sums per channel, contraction off: the same bits.
-template <bool VEC>
+// RING: the cache is a ring of max_pos rows and the row counts the sequence's tokens without bound -- it is written
+// at row mod max_pos, and only a negative row (or a position outside the table) drops the token.
+template <bool VEC, bool RING = false>
 __global__ void rotary_neox_kvcache_kernel(const int64_t* __restrict__ positions, const int64_t* __restrict__ slots,
                                            int slot_stride, f16* __restrict__ query,
                                            const f16* __restrict__ key, const f16* __restrict__ value,
@@ -162,13 +164,14 @@ __global__ void rotary_neox_kvcache_kernel(const int64_t* __restrict__ positions
     const int     b    = blockIdx.x;
     const int     cb   = tokens > 0 ? b / tokens : b;                // batch row of the cache
     const int64_t rpos = positions[b];                               // index into the cos|sin table
-    const int64_t pos  = tokens > 0 ? (slots ? slots[0] : (int64_t)first_row) + (b - cb * tokens)
+    const int64_t lpos = tokens > 0 ? (slots ? slots[0] : (int64_t)first_row) + (b - cb * tokens)
                                     : slots ? slots[(long)b * slot_stride] : rpos;  // cache row the new token is written to
     // never write outside the cache, never read outside the table; counted (eetq_decode_dropped_steps)
-    if (pos < 0 || pos >= max_pos || rpos < 0 || rpos >= table_rows) {
+    if (lpos < 0 || (!RING && lpos >= max_pos) || rpos < 0 || rpos >= table_rows) {
         if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&g_rope_dropped, 1u);
         return;
     }
+    const int64_t pos = RING ? lpos % max_pos : lpos;
     const f16* cp    = cache + rpos * rot_dim;
     const int  embed = rot_dim / 2;
     if constexpr (VEC) {
@@ -394,10 +397,13 @@ int launch_greedy_handover(const f16* logits, long row_stride, int vocab, int ba
 int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_stride, f16* q, const f16* k, const f16* v,
                           const f16* cache, f16* kcache, f16* vcache, int batch, int q_heads, int k_heads, int head_size, int rot_dim, long q_stride,
                           long k_stride, long v_stride, long c_sb, long c_sh, long c_ss, int max_pos, long table_rows, hipStream_t stream,
-                          int tokens, int first_row)
+                          int tokens, int first_row, bool ring)
 {
     EETQ_REQUIRE(pos && q && k && v && cache && kcache && vcache, "null pointer");
-    EETQ_REQUIRE(tokens >= 0 && first_row >= 0 && (slots || (long)first_row + tokens <= max_pos), "the prefill rows must lie inside the cache");
+    if (ring)   // max_pos is the ring's row count: any first row, and a call's rows must not meet themselves
+        EETQ_REQUIRE(tokens >= 0 && first_row >= 0 && tokens <= max_pos, "a ring cache takes at most its row count of prefill rows per call");
+    else
+        EETQ_REQUIRE(tokens >= 0 && first_row >= 0 && (slots || (long)first_row + tokens <= max_pos), "the prefill rows must lie inside the cache");
     EETQ_REQUIRE(batch >= 0 && q_heads > 0 && k_heads > 0 && head_size > 0 && rot_dim > 0 && rot_dim % 2 == 0 &&
                      rot_dim <= head_size && max_pos > 0,
                  "invalid rotary shape");
@@ -407,6 +413,17 @@ int launch_rotary_kvcache(const int64_t* pos, const int64_t* slots, int slot_str
     const bool vec    = rot_dim == head_size && head_size % 16 == 0 &&
                      (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cache | (uintptr_t)kcache | (uintptr_t)vcache) & 15) == 0 &&
                      ((q_stride | k_stride | v_stride | c_sb | c_sh | c_ss) & 7) == 0;
+    if (ring) {
+        if (vec)
+            rotary_neox_kvcache_kernel<true, true><<<dim3(blocks, 3), 256, 0, stream>>>(
+                pos, slots, slot_stride, q, k, v, cache, kcache, vcache, rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss, q_heads,
+                k_heads, head_size, max_pos, tokens, first_row, (int64_t)table_rows);
+        else
+            rotary_neox_kvcache_kernel<false, true><<<dim3(blocks, 3), 512, 0, stream>>>(
+                pos, slots, slot_stride, q, k, v, cache, kcache, vcache, rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss, q_heads,
+                k_heads, head_size, max_pos, tokens, first_row, (int64_t)table_rows);
+        return check_hip(hipGetLastError(), "rotary_neox_kvcache_kernel (ring) launch");
+    }
     if (vec)
         rotary_neox_kvcache_kernel<true><<<dim3(blocks, 3), 256, 0, stream>>>(pos, slots, slot_stride, q, k, v, cache, kcache, vcache,
                                                                                rot_dim, q_stride, k_stride, v_stride, c_sb, c_sh, c_ss,

@@ -164,6 +164,18 @@ static const int64_t* kv_start_ptr(const char* name, const OptTensor& kv_start, 
                 name, ": kv_start must be a contiguous int64 [B] tensor on the query's device");
     return kv_start->data_ptr<int64_t>();
 }
+// `ring` of the decode-attention operators (the cache tensors are rings of R = S rows): what it needs and excludes,
+// as ValueErrors -- they are about the combination asked for, not about the tensors
+static void check_decode_ring(const char* name, bool ring, const std::optional<int64_t>& window, const OptTensor& kv_start,
+                              const OptTensor& mask, const OptTensor& kv_len, int64_t R)
+{
+    if (!ring) return;
+    TORCH_CHECK_VALUE(window.has_value(), name, ": ring needs window (a ring cache holds the last rows of a sliding window only)");
+    TORCH_CHECK_VALUE(R >= *window, name, ": a ring cache of ", R, " rows is too small for window ", *window, " (R >= window)");
+    TORCH_CHECK_VALUE(!kv_start, name, ": ring and kv_start exclude each other (no ragged ring)");
+    TORCH_CHECK_VALUE(!mask, name, ": ring and an additive mask exclude each other (the mask row would need the same wrap)");
+    TORCH_CHECK_VALUE(kv_len.has_value(), name, ": ring needs kv_len (the valid length of a ring is logical, not its capacity)");
+}
 // What the four decode-attention operators prepare alike: the slots and their stride, the mask row and its batch stride, the kv_len /
 // advance scalars, the default scaling and chunk count, the output and the workspace, the stride arrays.  name: "operator: "
 struct DecodeAttnPrep {
@@ -223,9 +235,10 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
                              const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
                              std::optional<int64_t> splits_in, const OptTensor& kv_len, int64_t kv_len_bias,
                              const OptTensor& advance, const OptTensor& kv_start = std::nullopt,
-                             std::optional<int64_t> window = std::nullopt)
+                             std::optional<int64_t> window = std::nullopt, bool ring = false)
 {
     if (window) TORCH_CHECK_VALUE(*window >= 1, "rope_decode_attention: window must be at least 1 row (got ", *window, ")");
+    check_decode_ring("rope_decode_attention", ring, window, kv_start, mask, kv_len, key_cache.dim() == 4 ? key_cache.size(2) : 0);
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache})
         TORCH_CHECK(t->scalar_type() == at::kHalf, "rope_decode_attention: float16 tensors expected");
     TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous(),
@@ -250,6 +263,14 @@ Tensor rope_decode_attention(const Tensor& positions, const Tensor& query, const
     const int64_t*       starts  = kv_start_ptr("rope_decode_attention", kv_start, query, B);
     unsigned*            tk      = reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>());
     c10::DeviceGuard     guard(query.device());
+    if (ring) {   // the windowed entry's bits, the cache rows addressed modulo S
+        check(eetq_rope_decode_attention_ring_f16(
+            positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+            cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), p.out.data_ptr(),
+            p.ws.data_ptr<float>(), tk, (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(), p.kv_len,
+            (int)kv_len_bias, (int)std::min<int64_t>(*window, INT32_MAX), p.advance, stream_of(query)));
+        return p.out;
+    }
     if (window) {   // the last `window` valid rows, not below kv_start (which may be absent)
         check(eetq_rope_decode_attention_window_f16(
             positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
@@ -346,15 +367,29 @@ static int prefill_splits_rule(int B, int H, int, int T, int keys) { return eetq
 Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
                          std::optional<int64_t> causal_offset, const OptTensor& kv_len, int64_t kv_len_bias,
                          std::optional<int64_t> splits_in, const OptTensor& workspace, const OptTensor& kv_start = std::nullopt,
-                         std::optional<int64_t> window = std::nullopt)
+                         std::optional<int64_t> window = std::nullopt, bool ring = false)
 {
+    // ring: key / value are rings of R = key.size(2) rows; `keys` and kv_len count logical rows and may exceed R
+    if (ring) {
+        TORCH_CHECK_VALUE(window.has_value(), "prefill_attention: ring needs window (a ring cache holds the last rows of a sliding window only)");
+        TORCH_CHECK_VALUE(!causal_offset, "prefill_attention: ring takes causal_offset = keys - query rows only");
+        if (key.dim() == 4 && query.dim() == 4) {
+            const int64_t R = key.size(2), T = query.size(1);
+            TORCH_CHECK_VALUE(R % 64 == 0, "prefill_attention: a ring cache behind the prompt kernel must have a multiple of 64 rows (got ", R,
+                              ": a key block must not straddle the ring's end)");
+            TORCH_CHECK_VALUE(*window >= 1 && R >= *window + T + 62, "prefill_attention: a ring cache of ", R, " rows is too small for window ",
+                              *window, " and ", T, " query rows (R >= window + query rows + 62: a launch must not read key blocks its own "
+                              "rows have replaced)");
+        }
+    }
     // the sliding window's refusals come first and are ValueErrors: they are about the combination asked for, not about the tensors
     if (window) {
         TORCH_CHECK_VALUE(*window >= 1, "prefill_attention: window must be at least 1 row (got ", *window, ")");
         TORCH_CHECK_VALUE(!kv_start, "prefill_attention: window and kv_start exclude each other (the windowed prompt kernel knows one "
                                      "shared first key; ragged prompts with a window are not built)");
     }
-    check_prompt_qkv("prefill_attention: ", 'T', query, key, value, keys);
+    check_prompt_qkv("prefill_attention: ", 'T', query, key, value, ring && key.dim() == 4 ? std::min<int64_t>(keys, key.size(2)) : keys);
+    TORCH_CHECK(keys > 0 && keys <= (int64_t(1) << 30), "prefill_attention: keys out of range");
     const int64_t B = query.size(0), T = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
     TORCH_CHECK(T > 0, "prefill_attention: shape mismatch");
     TORCH_CHECK(prefill_attention_supported(D), "prefill_attention: unsupported head_dim");
@@ -369,6 +404,13 @@ Tensor prefill_attention(const Tensor& query, const Tensor& key, const Tensor& v
     const PromptAttnPrep p("prefill_attention: ", query, key, value, rule_keys, scaling, kv_len, kv_len_bias, splits_in, workspace,
                            prefill_splits_rule, eetq_prefill_attention_max_splits, eetq_prefill_attention_workspace_floats, false, dev_form);
     c10::DeviceGuard guard(query.device());
+    if (ring) {   // the windowed entry's bits, the cache rows addressed modulo key.size(2)
+        check(eetq_prefill_attention_ring_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
+                                              (int)H, (int)Hkv, (int)T, (int)keys, (int)D, p.kv_len, (int)kv_len_bias,
+                                              (int)std::min<int64_t>(*window, INT32_MAX), (int)key.size(2), (int)p.splits, p.sc, p.st,
+                                              stream_of(query)));
+        return p.out;
+    }
     if (window) {   // always the device-length entry (kv_len None: `keys` keys, the fresh prompt)
         TORCH_CHECK(off == keys - T, "prefill_attention: window takes causal_offset = keys - query rows only");
         check(eetq_prefill_attention_window_f16(query.data_ptr(), key.data_ptr(), value.data_ptr(), p.out.data_ptr(), p.workspace(), (int)B,
@@ -404,8 +446,11 @@ int64_t decode_attention_rows_splits(int64_t batch, int64_t heads, int64_t kv_he
 }
 
 Tensor decode_attention_rows(const Tensor& query, const Tensor& key, const Tensor& value, int64_t keys, std::optional<double> scaling,
-                             const OptTensor& kv_len, int64_t kv_len_bias, std::optional<int64_t> splits_in, const OptTensor& workspace)
+                             const OptTensor& kv_len, int64_t kv_len_bias, std::optional<int64_t> splits_in, const OptTensor& workspace,
+                             bool ring = false)
 {
+    // accepted only to be refused by name
+    TORCH_CHECK_VALUE(!ring, "decode_attention_rows: no ring cache behind the few-row kernel (it reads rows by their logical index)");
     check_prompt_qkv("decode_attention_rows: ", 'R', query, key, value, keys);
     const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3), Hkv = key.size(1);
     TORCH_CHECK(B > 0, "decode_attention_rows: shape mismatch");
@@ -819,7 +864,7 @@ void rotary_embedding_neox_strided(const Tensor& positions, Tensor& query, Tenso
 
 void rotary_embedding_neox_kvcache(const Tensor& positions, Tensor& query, const Tensor& key, const Tensor& value,
                                    int64_t head_size, const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache,
-                                   const OptTensor& slots)
+                                   const OptTensor& slots, bool ring = false)
 {
     for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache})
         TORCH_CHECK(t->scalar_type() == at::kHalf, "rotary_embedding_neox_kvcache: float16 tensors expected");
@@ -847,6 +892,14 @@ void rotary_embedding_neox_kvcache(const Tensor& positions, Tensor& query, const
     const long strides[6] = {(long)query.stride(0), (long)key.stride(0), (long)value.stride(0), (long)key_cache.stride(0),
                              (long)key_cache.stride(1), (long)key_cache.stride(2)};
     c10::DeviceGuard guard(query.device());
+    if (ring) {   // the caches are rings of key_cache.size(2) rows: the slot counts the sequence's tokens, the row is slot mod rows
+        check(eetq_rotary_neox_kvcache_ring_f16(positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr, slot_stride,
+                                                query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
+                                                (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)B, (int)H,
+                                                (int)Hkv, (int)head_size, (int)cos_sin_cache.size(1), strides, (int)key_cache.size(2),
+                                                stream_of(query)));
+        return;
+    }
     check(eetq_rotary_neox_kvcache_bounded_f16(positions.data_ptr<int64_t>(), slots ? slots->data_ptr<int64_t>() : nullptr,
                                                slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
                                                cos_sin_cache.data_ptr(), (int)cos_sin_cache.size(0), key_cache.data_ptr(),
@@ -865,7 +918,8 @@ struct RotaryPrefillPrep {
 template <class CacheCheck>
 RotaryPrefillPrep rotary_prefill_prep(const char* name, bool f16_caches, const Tensor& positions, const Tensor& query, const Tensor& key,
                                       const Tensor& value, int64_t head_size, const Tensor& cos_sin_cache, const Tensor& key_cache,
-                                      const Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev, CacheCheck cache_check)
+                                      const Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev, CacheCheck cache_check,
+                                      bool ring = false)
 {
     const Tensor* halves[6] = {&query, &key, &value, &cos_sin_cache, &key_cache, &value_cache};
     for (int i = 0; i < (f16_caches ? 6 : 4); ++i) {
@@ -882,7 +936,7 @@ RotaryPrefillPrep rotary_prefill_prep(const char* name, bool f16_caches, const T
     cache_check(B, p.Hkv, D);
     TORCH_CHECK(key.size(0) == B && key.size(1) == T && key.size(3) == D && value.sizes() == key.sizes() && D == head_size &&
                     value_cache.strides() == key_cache.strides() && positions.numel() == B * T && first_row >= 0 &&
-                    (first_row_dev || first_row + T <= key_cache.size(2)),
+                    (ring ? T <= key_cache.size(2) : (first_row_dev || first_row + T <= key_cache.size(2))),
                 name, "shape mismatch");
     if (first_row_dev) {
         TORCH_CHECK(first_row_dev->scalar_type() == at::kLong && first_row_dev->numel() == 1 &&
@@ -905,7 +959,7 @@ RotaryPrefillPrep rotary_prefill_prep(const char* name, bool f16_caches, const T
 // eetq_rotary_neox_kvcache_prefill_f16
 void rotary_embedding_neox_kvcache_prefill(const Tensor& positions, Tensor& query, const Tensor& key, const Tensor& value,
                                            int64_t head_size, const Tensor& cos_sin_cache, Tensor& key_cache,
-                                           Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev)
+                                           Tensor& value_cache, int64_t first_row, const OptTensor& first_row_dev, bool ring = false)
 {
     const char* name = "rotary_embedding_neox_kvcache_prefill: ";
     const auto  p    = rotary_prefill_prep(name, true, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row,
@@ -913,8 +967,15 @@ void rotary_embedding_neox_kvcache_prefill(const Tensor& positions, Tensor& quer
                                            TORCH_CHECK(key_cache.size(0) == B && key_cache.size(1) == Hkv && key_cache.size(3) == D &&
                                                            value_cache.sizes() == key_cache.sizes(),
                                                        name, "shape mismatch");
-                                       });
+                                       }, ring);
     c10::DeviceGuard guard(query.device());
+    if (ring) {   // rows (base + t) mod key_cache.size(2)
+        check(eetq_rotary_neox_kvcache_prefill_ring_f16(
+            positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
+            (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)p.B, (int)p.T, p.first_row_dev, (int)first_row,
+            (int)p.H, (int)p.Hkv, (int)head_size, (int)cos_sin_cache.size(1), p.strides, (int)key_cache.size(2), stream_of(query)));
+        return;
+    }
     check(eetq_rotary_neox_kvcache_prefill_bounded_f16(
         positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
         (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), (int)p.B, (int)p.T, p.first_row_dev, (int)first_row,
@@ -1068,9 +1129,10 @@ void spec_sample_accept(const Tensor& logits, const Tensor& draft, Tensor& out_t
 Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const OptTensor& mask,
                         std::optional<double> scaling, std::optional<int64_t> splits_in, const OptTensor& kv_len,
                         int64_t kv_len_bias, const OptTensor& advance, const OptTensor& kv_start = std::nullopt,
-                        std::optional<int64_t> window = std::nullopt)
+                        std::optional<int64_t> window = std::nullopt, bool ring = false)
 {
     if (window) TORCH_CHECK_VALUE(*window >= 1, "decode_attention: window must be at least 1 row (got ", *window, ")");
+    check_decode_ring("decode_attention", ring, window, kv_start, mask, kv_len, key_cache.dim() == 4 ? key_cache.size(2) : 0);
     TORCH_CHECK(query.scalar_type() == at::kHalf && key_cache.scalar_type() == at::kHalf && value_cache.scalar_type() == at::kHalf,
                 "decode_attention: query and caches must be float16");
     TORCH_CHECK(query.dim() == 3 && key_cache.dim() == 4 && value_cache.sizes() == key_cache.sizes(),
@@ -1084,6 +1146,13 @@ Tensor decode_attention(const Tensor& query, const Tensor& key_cache, const Tens
     const auto           strides = p.strides({query.stride(0), query.stride(1)}, key_cache, value_cache);
     const int64_t*       starts  = kv_start_ptr("decode_attention", kv_start, query, B);
     c10::DeviceGuard     guard(query.device());
+    if (ring) {   // the windowed entry's bits, the cache rows addressed modulo S
+        check(eetq_decode_attention_ring_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.out.data_ptr(),
+                                             p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc,
+                                             strides.data(), p.kv_len, (int)kv_len_bias, (int)std::min<int64_t>(*window, INT32_MAX),
+                                             p.advance, stream_of(query)));
+        return p.out;
+    }
     if (window) {   // the last `window` valid rows, not below kv_start (which may be absent)
         check(eetq_decode_attention_window_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), p.mask(), p.out.data_ptr(),
                                                p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc,
@@ -1146,9 +1215,10 @@ Tensor decode_attention_i8kv(const Tensor& query, const Tensor& key_cache, const
 Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
                               int64_t max_keys, std::optional<double> scaling, const OptTensor& kv_len, int64_t kv_len_bias,
                               std::optional<int64_t> splits_in, const OptTensor& workspace,
-                              std::optional<int64_t> window = std::nullopt)
+                              std::optional<int64_t> window = std::nullopt, bool ring = false)
 {
     const char* name = "prefill_attention_i8kv: ";
+    TORCH_CHECK_VALUE(!ring, name, "no ring cache of int8 rows (the ring prompt kernel reads fp16 cache rows only)");
     // accepted only to be refused by name: a caller that passes the fp16 operator's argument must not get the whole prefix silently
     TORCH_CHECK_VALUE(!window, name, "no sliding window on int8 rows (the windowed prompt kernel reads fp16 cache rows only)");
     TORCH_CHECK(query.scalar_type() == at::kHalf && query.is_cuda() && query.dim() == 4 && query.stride(-1) == 1 && key_cache.dim() == 4,
@@ -1171,9 +1241,10 @@ Tensor prefill_attention_i8kv(const Tensor& query, const Tensor& key_cache, cons
 // 1 .. 16, the first `max_keys` rows of the caches, or clamp(*kv_len + kv_len_bias, 0, max_keys) of them; [B, R, H, D] contiguous
 Tensor decode_attention_rows_i8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
                                   int64_t max_keys, std::optional<double> scaling, const OptTensor& kv_len, int64_t kv_len_bias,
-                                  std::optional<int64_t> splits_in, const OptTensor& workspace)
+                                  std::optional<int64_t> splits_in, const OptTensor& workspace, bool ring = false)
 {
     const char* name = "decode_attention_rows_i8kv: ";
+    TORCH_CHECK_VALUE(!ring, name, "no ring cache behind the few-row kernel (it reads rows by their logical index)");
     TORCH_CHECK(query.scalar_type() == at::kHalf && query.is_cuda() && query.dim() == 4 && query.stride(-1) == 1 && key_cache.dim() == 4,
                 name, "expected a float16 CUDA query [B, R, H, D] with dense D");
     const int64_t B = query.size(0), R = query.size(1), H = query.size(2), D = query.size(3), Hkv = key_cache.size(1);
@@ -2091,11 +2162,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("positions"), py::arg("query"), py::arg("key"), py::arg("head_size"), py::arg("cos_sin_cache"));
     m.def("rotary_embedding_neox_kvcache", &rotary_embedding_neox_kvcache, "decode-step rotary + KV-cache write",
           py::arg("positions"), py::arg("query"), py::arg("key"), py::arg("value"), py::arg("head_size"),
-          py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("slots") = py::none());
+          py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("slots") = py::none(),
+          py::arg("ring") = false);
     m.def("rotary_embedding_neox_kvcache_prefill", &rotary_embedding_neox_kvcache_prefill, "prompt rotary + KV-cache write",
           py::arg("positions"), py::arg("query"), py::arg("key"), py::arg("value"), py::arg("head_size"),
           py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("first_row") = 0,
-          py::arg("first_row_dev") = py::none());
+          py::arg("first_row_dev") = py::none(), py::arg("ring") = false);
     m.def("greedy_handover", &greedy_handover, "argmax + token hand-over of a greedy decode step", py::arg("logits"),
           py::arg("out_tokens"), py::arg("column"), py::arg("next_token"), py::arg("position"));
     m.def("sample_handover", &sample_handover, "temperature / top-k / top-p sampling + token hand-over of a decode step",
@@ -2113,12 +2185,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("decode_attention", &decode_attention, "single-query attention over a KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none(),
+          py::arg("ring") = false);
     m.def("rope_decode_attention", &rope_decode_attention, py::arg("positions"), py::arg("query"), py::arg("key"),
           py::arg("value"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("tickets"),
           py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
           py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
-          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none());
+          py::arg("advance") = py::none(), py::arg("kv_start") = py::none(), py::arg("window") = py::none(),
+          py::arg("ring") = false);
     m.def("decode_attention_i8kv", &decode_attention_i8kv, "single-query attention over an int8 KV cache", py::arg("query"),
           py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"), py::arg("mask") = py::none(),
           py::arg("scaling") = py::none(), py::arg("splits") = py::none(), py::arg("kv_len") = py::none(),
@@ -2135,21 +2209,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("causal_offset") = py::none(), py::kw_only(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
-          py::arg("kv_start") = py::none(), py::arg("window") = py::none(),
+          py::arg("kv_start") = py::none(), py::arg("window") = py::none(), py::arg("ring") = false,
           "causal attention of a prompt's query rows [B, T, H, D] over the first `keys` rows of a KV cache [B, Hkv, S, D] (MFMA)");
     m.def("prefill_attention_i8kv", &prefill_attention_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
           py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
           py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
-          py::arg("window") = py::none(),
+          py::arg("window") = py::none(), py::arg("ring") = false,
           "prefill_attention behind an int8 KV cache: a prompt's query rows [B, T, H, D] over the dequantised first rows of the cache");
     m.def("decode_attention_rows", &decode_attention_rows, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),
           py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(),
-          py::arg("workspace") = py::none(),
+          py::arg("workspace") = py::none(), py::arg("ring") = false,
           "1 .. 16 query rows [B, R, H, D], the last rows of the first `keys` rows of a KV cache [B, Hkv, S, D], attending it causally "
           "(split-KV, MFMA)");
     m.def("decode_attention_rows_i8kv", &decode_attention_rows_i8kv, py::arg("query"), py::arg("key_cache"), py::arg("value_cache"),
           py::arg("scales"), py::arg("max_keys"), py::arg("scaling") = py::none(), py::arg("kv_len") = py::none(),
-          py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("splits") = py::none(), py::arg("workspace") = py::none(), py::arg("ring") = false,
           "decode_attention_rows behind an int8 KV cache: 1 .. 16 query rows [B, R, H, D] over the dequantised first rows of the cache");
     m.def("decode_attention_rows_splits", &decode_attention_rows_splits, py::arg("batch"), py::arg("heads"), py::arg("kv_heads"),
           py::arg("rows"), py::arg("max_keys"), "the chunk count decode_attention_rows uses with splits=None");

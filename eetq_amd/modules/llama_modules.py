@@ -33,10 +33,11 @@ class _Promise(threading.local):
     few_rows_int8 = False
     starts = None      # padded_static_batch: every batch row's first real cache row
     window = None      # sliding_window_static: the rows a query looks back
+    ring = False       # sliding_window_static(ring=True): the static cache is a ring, logical row r at row r mod its rows
 
 
 _prefill_promise = _Promise()
-_PROMISE_FIELDS = ("fresh", "appended", "int8_rows", "few_rows", "few_rows_int8", "starts", "window")
+_PROMISE_FIELDS = ("fresh", "appended", "int8_rows", "few_rows", "few_rows_int8", "starts", "window", "ring")
 
 _ROWS = "appended_static_prefill(few_rows=True) (ops.decode_attention_rows)"
 _ROWS8 = "appended_static_prefill(few_rows_int8=True) (ops.decode_attention_rows_i8kv)"
@@ -65,6 +66,8 @@ def _check_promises(entering, state):
                          "int8_rows" % entering)
     if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
         raise ValueError("%s: window must be an integer of at least 1 row, got %r" % (entering, window))
+    if state["ring"] and window is None:
+        raise ValueError("%s: ring=True needs a window (a ring cache holds the last rows of a sliding window only)" % entering)
     for a, b, why in _PROMISE_CONFLICTS:
         if state[a] is not None and state[a] is not False and state[b] is not None:   # (starts may be a tensor: no ==)
             raise ValueError("%s: %s" % (entering, why))
@@ -153,7 +156,7 @@ def _padded_starts():
     return _prefill_promise.starts
 
 
-def sliding_window_static(window):
+def sliding_window_static(window, ring=False):
     """The caller's promise for the forwards run inside (per thread, restored on exit): attention looks back ``window`` rows -- a
     query at cache row p attends rows ``max(0, p - window + 1) .. p``, itself and the ``window - 1`` rows before it (transformers'
     ``sliding_window``).  ``window`` is a host integer >= 1, a constant of the model: it becomes a kernel argument, so a captured
@@ -167,18 +170,39 @@ def sliding_window_static(window):
 
     Anything that cannot honour the window raises ``ValueError`` instead of attending the whole prefix: an unsupported head size or
     dtype, an int8 cache, the ``few_rows`` promises (the few-row kernel has no window), ``padded_static_batch`` (no ragged prompt
-    with a window) and every stock attention path.  ``window=None`` promises nothing."""
-    return _promised("sliding_window_static", window=window)
+    with a window) and every stock attention path.  ``window=None`` promises nothing.
+
+    ``ring=True`` (needs a window; ``ValueError`` without one) adds the promise that the static cache is a RING (DESIGN.md 4.7d,
+    ``utils.kv_cache.RollingStaticCache``): its layers hold R rows, the token counter keeps counting the sequence's tokens, and
+    logical row r lives at row ``r mod R``.  The attention blocks then pass ``ring=True`` to the cache-write and attention operators
+    besides ``window``, and ignore the model-level mask (its columns would be physical rows; the prompt is unpadded, as under
+    ``fresh_static_prefill`` / ``appended_static_prefill``).  Nothing new conflicts: ``ring`` lives only with ``window``, whose refusals already cover int8 rows,
+    ``few_rows`` and ``padded_static_batch``.  A prompt call of T rows needs ``R % 64 == 0`` and ``R >= window + T + 62`` -- T at most
+    the chunk the ring was sized for (``kv_cache.ring_rows``) -- and is refused (``ValueError``) before anything is written
+    otherwise; a decode step needs ``R >= window``."""
+    return _promised("sliding_window_static", window=window, ring=bool(ring))
 
 
 def _window():
     return _prefill_promise.window
 
 
+def _ring_prompt_check(rows, window, t_len):
+    """Refuse (``ValueError``) a prompt call of ``t_len`` rows on a ring cache of ``rows`` rows under ``window``: the ring prompt
+    kernel's capacity rule, checked before the rows are written."""
+    chunk = rows - window - 62
+    if rows % 64 or t_len > chunk:
+        raise ValueError("EETLlamaAttention: sliding_window_static(%d, ring=True): a prompt call of %d rows exceeds the chunk of this "
+                         "ring cache (%d rows: a multiple of 64 and at least window + T + 62 are needed, so T <= %d); cut the prompt "
+                         "into pieces (GraphDecoder(rolling_chunk=))" % (window, t_len, rows, max(chunk, 0)))
+
+
 def _decode_step_refusal(promise):   # a single token under `promise` that the decode kernels cannot take
     return ValueError("EETLlamaAttention: %s needs the library's decode attention on an initialised fp16 static cache (head size 64 "
                       "or 128, decode_math_attention=True, a mask the kernel understands)" % promise)
 
+
+_RING_MAX_KEYS = 1 << 30   # the logical key bound ops.prefill_attention takes on a ring cache
 
 _Route = collections.namedtuple("_Route", "op fresh extra")   # op: "prompt" | "rows" | "sdpa" | "stock"
 _STOCK = _Route("stock", False, {})
@@ -201,7 +225,8 @@ def _route_fp16(p, cached, t_len, weights, mfma_ok, rows_ok):
         if not kernel or p.starts is not None or p.few_rows:
             raise ValueError("EETLlamaAttention: " + needs % "sliding_window_static" + ", without padded_static_batch or few_rows; a "
                              "single token needs the library's decode attention on such a cache")
-        return _Route("prompt", p.fresh, {"window": p.window})
+        # (ring: read tolerantly -- a promise record without the field promises no ring)
+        return _Route("prompt", p.fresh, {"window": p.window, "ring": True} if getattr(p, "ring", False) else {"window": p.window})
     if p.starts is not None:
         if not kernel:
             raise ValueError("EETLlamaAttention: " + needs % "padded_static_batch")
@@ -531,7 +556,9 @@ class _EETAttentionBase(nn.Module):
                 # the library's flash kernel on the matrix cores: the strided query view of the QKV projection, the cache rows as
                 # they lie.  Fresh: the T rows just written (no device length: the host form, unless a keyword follows); else the
                 # rows below the counter, which is the device length
-                out = ops.prefill_attention(q.transpose(1, 2), k, v, t_len if route.fresh else k.shape[2], scaling=self.scaling,
+                # (a ring: the rows below the counter are logical and unbounded by the tensor's rows)
+                bound = _RING_MAX_KEYS if route.extra.get("ring") else k.shape[2]
+                out = ops.prefill_attention(q.transpose(1, 2), k, v, t_len if route.fresh else bound, scaling=self.scaling,
                                             kv_len=None if route.fresh else counter, **route.extra)
                 return out.reshape(*input_shape, -1), None
             if route.op == "rows":   # the counter as the few-row kernel's device length
@@ -655,13 +682,18 @@ class EETLlamaAttention(_EETAttentionBase):
                 need = seen + q_len
         self._grow_table(need)
         add = False
-        if layer is not None and self.decode_math_attention is True and not kwargs.get("output_attentions", False):
-            add = self._decode_mask_rows(attention_mask, bsz, layer.keys.shape[2], hidden_states.dtype, hidden_states.device)
         starts = _padded_starts()   # a left-padded batch: the per-row first key of the decode kernels (None: the plain entries)
         window = _window()          # a sliding window: the decode kernels' windowed entries (None: the entries above)
+        if layer is not None and self.decode_math_attention is True and not kwargs.get("output_attentions", False):
+            if window is not None and _prefill_promise.ring:
+                add = None   # a ring: the model-level mask's columns are physical rows and say nothing; the promise replaces it
+            else:
+                add = self._decode_mask_rows(attention_mask, bsz, layer.keys.shape[2], hidden_states.dtype, hidden_states.device)
         if q_len == 1 and add is False and (starts is not None or window is not None):
             raise _decode_step_refusal("padded_static_batch" if starts is not None else "sliding_window_static")
         wkw = {} if window is None else {"window": window}
+        ring = window is not None and _prefill_promise.ring
+        rkw = {"ring": True} if ring else {}   # a ring cache: the write and attention operators address rows modulo the cache's
         if add is not False:
             # decode step on an initialised static cache: ONE launch rotates q in place (by its position) and writes the
             # rotated k and v straight into the cache row the cache's own token counter names -- for a left-padded batch
@@ -678,13 +710,13 @@ class EETLlamaAttention(_EETAttentionBase):
                 out = ops.rope_decode_attention(pos, q[:, 0], k[:, 0], v[:, 0], table, layer.keys, layer.values,
                                                 self._step_tickets(bsz, q.device), slots=counter, mask=add, scaling=self.scaling,
                                                 kv_len=counter, kv_len_bias=1, advance=counter,
-                                                kv_start=starts, **wkw).reshape(bsz, q_len, -1)
+                                                kv_start=starts, **wkw, **rkw).reshape(bsz, q_len, -1)
             else:
                 ops.rotary_embedding_neox_kvcache(pos, q[:, 0], k[:, 0], v[:, 0], self.head_dim, table, layer.keys,
-                                                  layer.values, slots=counter)
+                                                  layer.values, slots=counter, **rkw)
                 out = ops.decode_attention(q[:, 0], layer.keys, layer.values, mask=add, scaling=self.scaling,
                                            kv_len=counter, kv_len_bias=1, advance=counter,
-                                           kv_start=starts, **wkw).reshape(bsz, q_len, -1)
+                                           kv_start=starts, **wkw, **rkw).reshape(bsz, q_len, -1)
             weights = None
         else:
             player = self._static_cache_layer(past_key_values) if (q_len > 1 and q.is_cuda and self.static_prefill) else None
@@ -696,14 +728,16 @@ class EETLlamaAttention(_EETAttentionBase):
                 # add + counter add + two index_copy launches, behind the separate rotary launch.  Same bits in the cache.
                 self._grow_table(player.keys.shape[2])
                 table = self.rotary_emb.cos_sin_cache
+                if ring:   # (the caller keeps the table as long as the sequence: a ring's rows say nothing about it)
+                    _ring_prompt_check(player.keys.shape[2], window, q_len)
                 if table.shape[-1] == d:
                     counter = player.cumulative_length
                     if _prefill_promise.fresh:   # promised empty: rows 0 .. T - 1, whatever the counter held
-                        ops.rotary_embedding_neox_kvcache_prefill(positions, q, k, v, d, table, player.keys, player.values)
+                        ops.rotary_embedding_neox_kvcache_prefill(positions, q, k, v, d, table, player.keys, player.values, **rkw)
                         counter.fill_(q_len)
                     else:
                         ops.rotary_embedding_neox_kvcache_prefill(positions, q, k, v, d, table, player.keys, player.values,
-                                                                  first_row_dev=counter)
+                                                                  first_row_dev=counter, **rkw)
                         counter.add_(q_len)
                 else:
                     player = None

@@ -735,6 +735,21 @@ def _check_window(name, window):
     return min(rows, 2 ** 31 - 1)
 
 
+def _check_ring(name, window, kv_start, mask, kv_len, rows):
+    """``ring=True`` of the decode-attention operators (the cache tensors are rings of ``rows`` rows): what it needs and excludes,
+    as ``ValueError``."""
+    if window is None:
+        raise ValueError("%s: ring needs window (a ring cache holds the last rows of a sliding window only)" % name)
+    if rows < _check_window(name, window):
+        raise ValueError("%s: a ring cache of %d rows is too small for window %d (R >= window)" % (name, rows, window))
+    if kv_start is not None:
+        raise ValueError("%s: ring and kv_start exclude each other (no ragged ring)" % name)
+    if mask is not None:
+        raise ValueError("%s: ring and an additive mask exclude each other (the mask row would need the same wrap)" % name)
+    if kv_len is None:
+        raise ValueError("%s: ring needs kv_len (the valid length of a ring is logical, not its capacity)" % name)
+
+
 class _DecodeAttnPrep:
     """What the four decode-attention operators prepare alike (``name``: "operator: "): the slots' stride, the mask row and its
     batch stride, the ``kv_len`` / ``advance`` scalars, the default scaling and chunk count, the output, the workspace and the
@@ -770,7 +785,7 @@ class _DecodeAttnPrep:
 
 @_eager_only
 def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0,
-                     advance=None, kv_start=None, window=None):
+                     advance=None, kv_start=None, window=None, ring=False):
     """Single-query attention over a KV cache (extension; the decode step of the EET attention blocks).
 
     query [B, H, D] (any batch/head strides, dense D), key_cache / value_cache [B, Hkv, S, D] (dense D), mask: additive
@@ -780,12 +795,16 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
     (int64 [B] on the device): batch row b attends rows ``kv_start[b]`` and up only, its blocks and chunks counted from
     there (a left-padded batch; eetq_decode_attention_padded_f16).  ``window`` (host integer >= 1): a sliding window -- batch
     row b attends the last ``window`` of its valid rows and none below ``kv_start[b]``: the bits of the ``kv_start`` form called
-    with ``max(kv_start, valid length - window)`` (eetq_decode_attention_window_f16).  Returns
+    with ``max(kv_start, valid length - window)`` (eetq_decode_attention_window_f16).  ``ring=True`` (needs ``window`` and
+    ``kv_len``; no ``kv_start``, no mask): the caches are rings of S >= window rows, logical row r at row r mod S, ``kv_len`` the
+    logical length -- the bits of the windowed form on a static cache of the same logical rows (eetq_decode_attention_ring_f16).  Returns
     float16 [B, H, D].  fp32 softmax and accumulation; D must be 64 or 128."""
     if query.dtype != torch.float16 or key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
         raise RuntimeError("decode_attention: query and caches must be float16")
     if query.dim() != 3 or key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
         raise RuntimeError("decode_attention: expected query [B, H, D] and caches [B, Hkv, S, D]")
+    if ring:
+        _check_ring("decode_attention", window, kv_start, mask, kv_len, key_cache.shape[2])
     B, H, D = query.shape
     Bk, Hkv, S, Dk = key_cache.shape
     if Bk != B or Dk != D or H % Hkv or query.stride(-1) != 1 or key_cache.stride(-1) != 1 or value_cache.stride(-1) != 1:
@@ -797,6 +816,11 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
     if kv_start is not None:
         _check_kv_start("decode_attention", kv_start, query, B)
     with torch.cuda.device(query.device):
+        if ring:
+            check(_lib.lib().eetq_decode_attention_ring_f16(
+                _ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits, p.scaling,
+                p.strides, _ptr(kv_len), int(kv_len_bias), window, _optr(advance), _stream_ptr()))
+            return p.out
         if window is not None:
             check(_lib.lib().eetq_decode_attention_window_f16(
                 _ptr(query), _ptr(key_cache), _ptr(value_cache), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D, p.splits,
@@ -816,13 +840,15 @@ def decode_attention(query, key_cache, value_cache, mask=None, scaling=None, spl
 @_eager_only
 def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache, value_cache, tickets, slots=None,
                           mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None, kv_start=None,
-                          window=None):
+                          window=None, ring=False):
     """``rotary_embedding_neox_kvcache`` followed by ``decode_attention`` as ONE launch (extension; the decode step of a
     static KV cache).  Bit-identical to that pair in the cache rows written and in the returned [B, H, D] output; the
     rotated query is not written back.  ``tickets``: an int32 device tensor of at least B * H + 1 zeros that the launch
     leaves zeroed (launches that may overlap need their own).  The rotation must cover the whole head.  ``kv_start``: as in
     ``decode_attention`` (eetq_rope_decode_attention_padded_f16); the new row is still written at its absolute slot.
-    ``window``: as in ``decode_attention``, the valid length being the new token's slot + 1 (eetq_rope_decode_attention_window_f16)."""
+    ``window``: as in ``decode_attention``, the valid length being the new token's slot + 1 (eetq_rope_decode_attention_window_f16).
+    ``ring``: as in ``decode_attention``; the slot is the token's logical row -- a ring is never full -- and the new row is written
+    at slot mod S (eetq_rope_decode_attention_ring_f16)."""
     for t in (query, key, value, cos_sin_cache, key_cache, value_cache):
         if t.dtype != torch.float16:
             raise RuntimeError("rope_decode_attention: float16 tensors expected")
@@ -830,6 +856,8 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
         raise RuntimeError("rope_decode_attention: positions must be contiguous int64")
     if query.dim() != 3 or key.dim() != 3 or value.dim() != 3 or key_cache.dim() != 4 or value_cache.shape != key_cache.shape:
         raise RuntimeError("rope_decode_attention: expected query [B, H, D], key / value [B, Hkv, D], caches [B, Hkv, S, D]")
+    if ring:
+        _check_ring("rope_decode_attention", window, kv_start, mask, kv_len, key_cache.shape[2])
     B, H, D = query.shape
     Hkv, S = key.shape[1], key_cache.shape[2]
     if (key.shape[0] != B or key.shape[2] != D or value.shape != key.shape or key_cache.shape[0] != B
@@ -853,6 +881,12 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
     if kv_start is not None:
         _check_kv_start("rope_decode_attention", kv_start, query, B)
     with torch.cuda.device(query.device):
+        if ring:
+            check(_lib.lib().eetq_rope_decode_attention_ring_f16(
+                _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+                cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _ptr(p.out), _ptr(p.ws), _ptr(tickets), B, H, Hkv, S, D,
+                p.splits, p.scaling, p.strides, _ptr(kv_len), int(kv_len_bias), window, _optr(advance), _stream_ptr()))
+            return p.out
         if window is not None:
             check(_lib.lib().eetq_rope_decode_attention_window_f16(
                 _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
@@ -876,11 +910,12 @@ def rope_decode_attention(positions, query, key, value, cos_sin_cache, key_cache
 
 @_eager_only
 def rotary_embedding_neox_kvcache(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
-                                  slots=None):
+                                  slots=None, ring=False):
     """Decode step: rotate ``query`` [B, H, D] in place by ``positions`` [B] (int64), write the rotated ``key`` [B, Hkv, D]
     and ``value`` [B, Hkv, D] into the caches [B, Hkv, S, D] at row ``slots`` (int64 on the device: one element = the same
     row for the whole batch, e.g. a static cache's token counter, or [B]); ``slots=None`` writes at ``positions`` (they
-    differ for left-padded batches).  One launch instead of rotary + two cache copies."""
+    differ for left-padded batches).  One launch instead of rotary + two cache copies.  ``ring=True``: the caches are rings of
+    S rows, the row counts the sequence's tokens without bound and is written at row mod S (eetq_rotary_neox_kvcache_ring_f16)."""
     for t in (query, key, value, cos_sin_cache, key_cache, value_cache):
         if t.dtype != torch.float16:
             raise RuntimeError("rotary_embedding_neox_kvcache: float16 tensors expected")
@@ -907,6 +942,12 @@ def rotary_embedding_neox_kvcache(positions, query, key, value, head_size, cos_s
     strides = (ctypes.c_long * 6)(query.stride(0), key.stride(0), value.stride(0), key_cache.stride(0),
                                   key_cache.stride(1), key_cache.stride(2))
     with torch.cuda.device(query.device):
+        if ring:
+            check(_lib.lib().eetq_rotary_neox_kvcache_ring_f16(
+                _ptr(positions), _optr(slots), slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+                cos_sin_cache.shape[0], _ptr(key_cache), _ptr(value_cache), B, H, Hkv, int(head_size), cos_sin_cache.shape[1], strides,
+                key_cache.shape[2], _stream_ptr()))
+            return None
         check(_lib.lib().eetq_rotary_neox_kvcache_bounded_f16(_ptr(positions), _ptr(slots) if slots is not None else None,
                                                               slot_stride, _ptr(query), _ptr(key), _ptr(value),
                                                               _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
@@ -917,7 +958,7 @@ def rotary_embedding_neox_kvcache(positions, query, key, value, head_size, cos_s
 
 
 def _rotary_prefill_prep(name, f16_caches, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
-                         first_row, first_row_dev, cache_check):
+                         first_row, first_row_dev, cache_check, ring=False):
     """What the two cache-writing prompt rotary operators prepare alike (``name``: "operator: "): the float16 and device checks
     (``f16_caches``: of the caches as well), positions, the 4-D shapes, ``first_row`` / ``first_row_dev``, the one-token-stride
     rule and the six strides.  ``cache_check(B, Hkv, D)`` is the form's own check of its caches.  -> (B, T, H, Hkv, strides)"""
@@ -936,7 +977,7 @@ def _rotary_prefill_prep(name, f16_caches, positions, query, key, value, head_si
     cache_check(B, Hkv, D)
     if (key.shape != (B, T, Hkv, D) or value.shape != key.shape or D != head_size
             or value_cache.stride() != key_cache.stride() or positions.numel() != B * T or first_row < 0
-            or (first_row_dev is None and first_row + T > key_cache.shape[2])):
+            or (T > key_cache.shape[2] if ring else (first_row_dev is None and first_row + T > key_cache.shape[2]))):
         raise RuntimeError(name + "shape mismatch")
     if first_row_dev is not None and (first_row_dev.dtype != torch.int64 or first_row_dev.numel() != 1
                                       or first_row_dev.device != query.device):
@@ -954,11 +995,12 @@ def _rotary_prefill_prep(name, f16_caches, positions, query, key, value, head_si
 
 @_eager_only
 def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
-                                          first_row=0, first_row_dev=None):
+                                          first_row=0, first_row_dev=None, ring=False):
     """Prefill on a pre-allocated KV cache: rotate ``query`` [B, T, H, D] in place by ``positions`` [B, T] (int64), write the
     rotated ``key`` [B, T, Hkv, D] and ``value`` into the caches [B, Hkv, S, D] at rows ``base + t``, base = ``first_row_dev``
     (one int64 on the device, e.g. a static cache's token counter; read, not advanced) or ``first_row``.  One launch instead
-    of rotary + two index_copy launches and their index arithmetic (eetq_rotary_neox_kvcache_prefill_f16)."""
+    of rotary + two index_copy launches and their index arithmetic (eetq_rotary_neox_kvcache_prefill_f16).  ``ring=True``: the
+    caches are rings of S >= T rows and the rows are ``(base + t) mod S`` (eetq_rotary_neox_kvcache_prefill_ring_f16)."""
     name = "rotary_embedding_neox_kvcache_prefill: "
 
     def cache_check(B, Hkv, D):
@@ -966,8 +1008,14 @@ def rotary_embedding_neox_kvcache_prefill(positions, query, key, value, head_siz
                 or value_cache.shape != key_cache.shape):
             raise RuntimeError(name + "shape mismatch")
     B, T, H, Hkv, strides = _rotary_prefill_prep(name, True, positions, query, key, value, head_size, cos_sin_cache, key_cache,
-                                                 value_cache, first_row, first_row_dev, cache_check)
+                                                 value_cache, first_row, first_row_dev, cache_check, ring)
     with torch.cuda.device(query.device):
+        if ring:
+            check(_lib.lib().eetq_rotary_neox_kvcache_prefill_ring_f16(
+                _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
+                _ptr(value_cache), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size), cos_sin_cache.shape[1],
+                strides, key_cache.shape[2], _stream_ptr()))
+            return None
         check(_lib.lib().eetq_rotary_neox_kvcache_prefill_bounded_f16(
             _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
             _ptr(value_cache), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size), cos_sin_cache.shape[1], strides,

@@ -67,7 +67,8 @@ def _require_accelerated(setting, model, lean, prompt_kernel):
 
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
-                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt", window=None):
+                 ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt", window=None,
+                 rolling=False, rolling_chunk=512):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -143,8 +144,16 @@ class GraphDecoder:
         recycled); ``generate``, ``prefill(chunk=)``, ``append=True`` and sampling work as without it.  The decode step goes through
         the attention module instead of the one-call layer.  It needs what ``ragged`` needs -- ``lean``, a fully accelerated model,
         head size 64 or 128 -- and the MFMA prompt kernel; ``ragged=True`` (no ragged prompt with a window), ``kv_bits=8`` (no window
-        on int8 rows) and ``speculative=k`` (the verify step's kernels have no window) raise ``ValueError``."""
+        on int8 rows) and ``speculative=k`` (the verify step's kernels have no window) raise ``ValueError``.
+        ``rolling`` (default ``False``; needs ``window``): the cache becomes a ``kv_cache.RollingStaticCache`` -- a RING of
+        ``kv_cache.ring_rows(W, rolling_chunk)`` rows per layer instead of ``max_len`` -- and every forward runs under
+        ``sliding_window_static(W, ring=True)``.  ``max_len`` stays the bound on the SEQUENCE: the token buffers and the rotary table
+        cover it, the cache does not.  ``generate`` / ``prefill`` cut any prompt into pieces of at most ``rolling_chunk`` tokens (a
+        smaller ``prefill_chunk`` / ``chunk`` is kept), the first fresh, the later ones appended; ``append=True``, sampling, captured and
+        eager stepping work as without it, and one captured graph serves every length: wrapping is kernel arithmetic on the device
+        counter.  ``rolling=True`` without ``window``, or with ``ragged``, ``kv_bits=8`` or ``speculative``, raises ``ValueError``."""
         self.window = self._check_window(window, model, lean, ragged, kv_bits, speculative)
+        self.rolling, self.rolling_chunk = self._check_rolling(rolling, rolling_chunk, window, ragged, kv_bits, speculative)
         if spec_attention not in ("prompt", "rows"):
             raise ValueError("GraphDecoder: spec_attention must be 'prompt' (the MFMA prompt kernel) or 'rows' (the few-row split-KV "
                              "kernel), got %r" % (spec_attention,))
@@ -193,6 +202,12 @@ class GraphDecoder:
         if self.kv_bits == 8:
             from .kv_cache import Int8StaticCache
             self.cache = Int8StaticCache(config=model.config, max_cache_len=self.max_len).allocate(self.batch, dev)
+        elif self.rolling:
+            from .kv_cache import RollingStaticCache
+            self.cache = RollingStaticCache(config=model.config, window=self.window, chunk=self.rolling_chunk)
+            # the rotary tables cover the sequence, not the ring (grown here: never during capture)
+            for layer in model.model.layers:
+                layer.self_attn._grow_table(self.max_len)
         else:
             try:
                 self.cache = StaticCache(config=model.config, max_cache_len=self.max_len)
@@ -282,6 +297,26 @@ class GraphDecoder:
         _require_accelerated("window=%d" % window, model, lean, prompt_kernel=True)
         return int(window)
 
+    @staticmethod
+    def _check_rolling(rolling, rolling_chunk, window, ragged, kv_bits, speculative):
+        """The checked (``rolling``, ``rolling_chunk``).  Every refusal says which setting and why."""
+        if not rolling:
+            return False, None
+        if window is None:
+            raise ValueError("GraphDecoder: rolling=True needs window=W: a rolling cache holds the last rows of a sliding window only")
+        if ragged:
+            raise ValueError("GraphDecoder: rolling=True with ragged=True: there is no ragged ring (the ring kernels know one shared "
+                             "first key)")
+        if kv_bits != 16:
+            raise ValueError("GraphDecoder: rolling=True needs an fp16 cache (kv_bits=16): there is no ring of int8 rows, got "
+                             "kv_bits=%r" % (kv_bits,))
+        if speculative:
+            raise ValueError("GraphDecoder: rolling=True with speculative=%r: the verify step's kernels read cache rows by their "
+                             "logical index (no ring)" % (speculative,))
+        if isinstance(rolling_chunk, bool) or not isinstance(rolling_chunk, int) or rolling_chunk < 1:
+            raise ValueError("GraphDecoder: rolling_chunk must be the longest prompt piece, an integer >= 1, got %r" % (rolling_chunk,))
+        return True, int(rolling_chunk)
+
     def _check_speculative(self, speculative, ngram, draft, max_len, spec_sampling=False):
         """The checked ``speculative`` (0: off).  Every refusal says which setting and why."""
         if isinstance(speculative, bool) or not isinstance(speculative, int) or not 0 <= speculative <= 15:
@@ -336,7 +371,7 @@ class GraphDecoder:
         captured or eager, runs inside it), else nothing."""
         if self.window is not None:
             from ..modules.llama_modules import sliding_window_static
-            return sliding_window_static(self.window)
+            return sliding_window_static(self.window, ring=self.rolling)
         if not self.ragged:
             return contextlib.nullcontext()
         from ..modules.llama_modules import padded_static_batch
@@ -583,6 +618,8 @@ class GraphDecoder:
         if chunk is not None and int(chunk) < 1:
             raise ValueError("GraphDecoder: chunk must be at least 1")
         step = P if chunk is None else int(chunk)
+        if self.rolling:   # a ring admits pieces of at most rolling_chunk rows
+            step = min(step, self.rolling_chunk)
         fresh = self._fresh_prefill_ok()
         from ..modules.llama_modules import appended_static_prefill, fresh_static_prefill
         if not append:

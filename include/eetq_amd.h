@@ -505,6 +505,19 @@ int eetq_rotary_neox_kvcache_prefill_bounded_f16(const int64_t* positions, void*
                                                  int batch, int tokens, const int64_t* first_row_dev, int first_row,
                                                  int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
                                                  int max_positions, void* stream);
+/* The two bounded cache-write entries on a RING cache (extension, added within ABI revision 7; "The ring cache" below): the caches
+ * hold `ring_rows` rows and the row an entry derives -- slots[..] or the position; *first_row_dev or first_row, plus t -- counts the
+ * sequence's tokens without an upper bound and is written at row mod ring_rows.  Only a negative row or a position outside the table
+ * drops a token (and counts).  The prefill entry takes at most ring_rows tokens per call (EETQ_ERR_INVALID beyond: a call's rows must
+ * not meet themselves).  Everything else as the bounded entries; the bits written are theirs. */
+int eetq_rotary_neox_kvcache_ring_f16(const int64_t* positions, const int64_t* slots, int slot_stride, void* query, const void* key,
+                                      const void* value, const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache,
+                                      int batch, int q_heads, int k_heads, int head_size, int rot_dim, const long* strides,
+                                      int ring_rows, void* stream);
+int eetq_rotary_neox_kvcache_prefill_ring_f16(const int64_t* positions, void* query, const void* key, const void* value,
+                                              const void* cos_sin_cache, int table_rows, void* k_cache, void* v_cache, int batch,
+                                              int tokens, const int64_t* first_row_dev, int first_row, int q_heads, int k_heads,
+                                              int head_size, int rot_dim, const long* strides, int ring_rows, void* stream);
 
 /* Greedy decode hand-over (extension, ABI 5; the reference's recipe leaves this to transformers' generate loop,
  * examples/models/llama_transformers_example.py:68-79): for each of `batch` rows of fp16 logits [batch][vocab] (row_stride
@@ -701,6 +714,28 @@ int eetq_rope_decode_attention_window_f16(const int64_t* positions, const int64_
                                           int head_dim, int splits, float scaling, const long* strides, const int64_t* kv_len,
                                           int kv_len_bias, const int64_t* kv_start, int window, int64_t* advance, void* stream);
 
+/* THE RING CACHE (extension, added within ABI revision 7): the capacity half of the sliding window.  k_cache / v_cache hold R =
+ * `ring_rows` rows and logical cache row r -- the token's position in the sequence, from 0, unbounded -- lives at physical row
+ * r mod R.  Keys are stored rotated, so a row carries its position and nothing is re-rotated.  Everything the windowed entries
+ * compute stays in logical rows (the valid length n, the first attended row max(0, n - window), blocks, chunks, shares, masks);
+ * only the address of a row changes.  The contract: each ring entry returns THE BITS of its windowed entry (same window, same
+ * splits, same LONG form -- decided by the capacity passed: R here) called on a static cache that holds the same logical rows, and
+ * the one-launch entry writes the new row at physical row slot mod R and no other.  kv_len is REQUIRED and counts logical rows (it
+ * may exceed R); `slots` / positions are logical as well: a ring is never full, so only a negative slot or position drops a step.
+ * Decode entries: R >= window (EETQ_ERR_INVALID below; the live rows of a step are n - window .. n - 1).  No kv_start and no mask
+ * (their arguments are gone).  Default splits as the static entries, taken from R -- untuned for rings.
+ * Every row of the ring must hold finite values (allocate zeros; stale rows are old real rows): see the prompt entry. */
+int eetq_decode_attention_ring_f16(const void* q, const void* k_cache, const void* v_cache, void* out, float* workspace, int batch,
+                                   int heads, int kv_heads, int ring_rows, int head_dim, int splits, float scaling,
+                                   const long* strides, const int64_t* kv_len, int kv_len_bias, int window, int64_t* advance,
+                                   void* stream);
+int eetq_rope_decode_attention_ring_f16(const int64_t* positions, const int64_t* slots, int slot_stride, const void* query,
+                                        const void* key, const void* value, const void* cos_sin_cache, int table_rows,
+                                        void* k_cache, void* v_cache, void* out, float* workspace, unsigned* tickets, int batch,
+                                        int heads, int kv_heads, int ring_rows, int head_dim, int splits, float scaling,
+                                        const long* strides, const int64_t* kv_len, int kv_len_bias, int window, int64_t* advance,
+                                        void* stream);
+
 /* The int8 KV cache (extension, added within ABI revision 7).  One cache ROW is the head_dim fp16 values of one (batch row, kv
  * head, position); rows are quantised symmetrically, each with a scale of its own:
  *   amax = max_d |x_d| (exact);  s = fp16(fp32(amax) * (1.0f / 127.0f)), one fp32 multiply, round to nearest even;
@@ -809,6 +844,18 @@ int eetq_prefill_attention_padded_f16(const void* q, const void* k, const void* 
 int eetq_prefill_attention_window_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
                                       int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
                                       int window, int splits, float scaling, const long* strides, void* stream);
+/* eetq_prefill_attention_window_f16 on a RING cache ("The ring cache" above): k / v hold `ring_rows` rows, max_keys and kv_len count
+ * logical rows (max_keys <= 2^30, it may exceed ring_rows), and key block j is read from physical block j mod (ring_rows / 64).
+ * The bits of the windowed entry on a static cache of the same logical rows.  ring_rows % 64 == 0 (a key block never straddles the
+ * ring's end) and ring_rows >= window + q_tokens + 62 (EETQ_ERR_INVALID otherwise): the lowest row a launch reads is
+ * 64 floor((koff - window + 1) / 64) >= koff - window - 62, the highest row the call's cache write has just replaced, koff +
+ * q_tokens - 1, aliases logical row koff + q_tokens - 1 - ring_rows, and the rule keeps the second below the first.  Rows of the
+ * upper-edge block at and beyond the keys -- clipped by the descriptor on a static cache -- are rows of the ring here, stale or
+ * never written; like the rows of a lower-edge block below a window they are read and enter the value product with probability
+ * 0, so EVERY row of the ring must be finite.  Splits and workspace as the windowed entry (same untuned rule). */
+int eetq_prefill_attention_ring_f16(const void* q, const void* k, const void* v, void* out, float* workspace, int batch, int heads,
+                                    int kv_heads, int q_tokens, int max_keys, int head_dim, const int64_t* kv_len, int kv_len_bias,
+                                    int window, int ring_rows, int splits, float scaling, const long* strides, void* stream);
 /* The split count eetq_prefill_attention_dev_f16 is tuned for (pure host function; callers size the workspace with it; 1 = unsplit).
  * With g = ceil(q_tokens / 128) * heads * batch workgroups and n = ceil(max_keys / 64) key blocks: the largest power of two s <= 16
  * such that, for every power of two s' <= s, s' g <= 1.25 compute units and n / s' >= 4 (s' g <= half the compute units), 8 (s' g <=
