@@ -38,8 +38,16 @@ int launch_inst(const f16* x, const uint8_t* w, const f16* scales, Epilogue ep, 
         // the plain projection (no bias, residual or activation) has its own instantiation of every M = 1 kernel form: same
         // arithmetic, same bits, no run-time epilogue (gemv_kernel.hpp: PLAIN)
         if (!ep.bias && !ep.residual && ep.act == 0) {
-            static std::atomic<unsigned long long> opted_plain{0};
-            return go(gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, NORM, 8, true>, opted_plain);
+            if constexpr (XREG && EXACT && D == 4) {
+                // ... and the register-resident exact-fit form (K = 4096) its minimal-argument entry (gemv_kernel.hpp: gemv_plain_kernel);
+                // it needs 1 KiB of LDS, so no opt-in
+                launch_kernel(gemv::gemv_plain_kernel<WAVES, D, OCC>, dim3(N / kTileN), dim3(WAVES * 64), smem, stream, x, w,
+                              scales, y);
+                return check_hip(hipGetLastError(), "gemv_plain_kernel launch");
+            } else {
+                static std::atomic<unsigned long long> opted_plain{0};
+                return go(gemv_kernel<M, WAVES, D, EXACT, XREG, XV, OCC, NORM, 8, true>, opted_plain);
+            }
         }
     }
     static std::atomic<unsigned long long> opted{0};

@@ -482,6 +482,19 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void gemv_kernel(
     gemv_body<M, WAVES, D, EXACT, XREG, XV, NORM, BITS, PLAIN>(x, w, scales, y, N, K, ep, pro, blockIdx.x);
 }
 
+// The minimal-argument entry of the plain exact-fit projection (M = 1, int8, K = 64 WAVES D -- 4096 at 16 x 4 -- no bias, residual or
+// activation): the PLAIN body reads nine of gemv_kernel's eighteen argument dwords, yet every wave of the launch (4096 at N = K = 4096)
+// is started with all sixteen preloaded ones in its SGPRs.  Here the four pointers are the whole list: K is WAVES * D * 64 by the
+// exact-fit contract (a constant to the address arithmetic), N only ever addressed rows m > 0.  Same body, same bits.  An empty
+// kernel's launch ramp (first to last workgroup in) is 0.88 us with 2, 8 or 9 preloaded dwords and 1.00 with 16, its chain step 1.67
+// against 1.71; the GEMV's chain step 4.41 against 4.48 us (profiles/r07_gemv_plain_entry.txt).
+template <int WAVES, int D, int MIN_WAVES_PER_SIMD>
+__global__ __launch_bounds__(WAVES * 64, MIN_WAVES_PER_SIMD) void gemv_plain_kernel(
+    const f16* __restrict__ x, const uint8_t* __restrict__ w, const f16* __restrict__ scales, f16* __restrict__ y)
+{
+    gemv_body<1, WAVES, D, true, true, 1, 0, 8, true>(x, w, scales, y, 0, WAVES * D * Codec<8>::kTileK, Epilogue{}, Prologue{}, blockIdx.x);
+}
+
 // ---- grouped launch: ONE dispatch over the tile rows of up to kMaxGroup independent M = 1 problems of equal K ----------
 // A single 16 MiB GEMV dispatch spends ~1.8 us of its ~4.8 on launch ramp, first-byte latency and tail; problems that do not
 // depend on each other (the q / k / v or gate / up projections of an unfused layer, the experts of one token, ...) pay that

@@ -16,7 +16,7 @@ def main():
     path = sys.argv[1]
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
     warm = int(sys.argv[3]) if len(sys.argv) > 3 else 200
-    rows = [r for r in csv.DictReader(open(path)) if "gemv_kernel" in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(path)) if "gemv_kernel" in r["Kernel_Name"] or "gemv_plain_kernel" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows])
     segs = [("parity", 1), ("warm-up (eager)", warm), ("graph pre-capture warm (eager, side stream)", 3),
