@@ -1,5 +1,6 @@
-// Single-query ("decode") attention over a KV cache of fp16 rows or of int8 rows (kv_i8.hpp): fp16 in / fp16 out,
-// fp32 softmax and accumulation.  One set of kernels over a row-format policy (KvF16, KvI8).
+// Single-query ("decode") attention over a KV cache of fp16 rows, of int8 rows (kv_i8.hpp) or of fp8 e4m3 rows
+// (kv_f8.hpp): fp16 in / fp16 out, fp32 softmax and accumulation.  One set of kernels over a row-format policy
+// (KvF16, KvI8, KvF8).
 //
 // No counterpart in the reference's csrc: its EETLlamaAttention delegates the attention product to flash-attn
 // (python/eetq/modules/llama_modules.py:131-143).  The stock library kernel this box offers for a single query token runs
@@ -39,9 +40,16 @@
 //          row that holds all the weight comes out as fp16(vs * v8) bit for bit.  The one-launch form quantises the new
 //          token's rotated K and its V in registers, writes bytes and scale pair from one position group per kv head, and
 //          every workgroup attends the new row as its quantised self from registers.
+//   KvF8   8 bytes of each and nothing else: the scale pair belongs to the kv head, not to the row.  Bytes become fp16 pairs (K, for
+//          v_dot2_f32_f16) and floats (V) by the hardware converts, exactly; ks * scaling is formed once per workgroup and is the
+//          score's scalar, vs multiplies the chunk's output once (the head-scale hook, empty in the other two formats), so a row
+//          that holds all the weight comes out as fp16(fp32(v8) * vs) bit for bit.  The one-launch form quantises the new token's
+//          rotated K and its V in registers -- a divide, a clamp and a convert per channel, no lane reduction --, writes the bytes
+//          from one position group per kv head, and every workgroup attends the new row as its quantised self from registers.
 // The loaders and the two online-softmax bodies (load_range, consume_range) stay whole, one overload per format: sharing their skeleton over small per-format
 // helpers reorders the fp16 kernels' instructions (docs/HISTORY.md, "Decode attention: one kernel template").
 #include "attn_decode_shared.hpp"
+#include "kv_f8.hpp"
 #include "kv_i8.hpp"
 
 namespace eetq {
@@ -53,6 +61,16 @@ __device__ unsigned g_attn_dropped = 0;
 namespace eetq {
 
 namespace {
+
+// The head-scale hook: what a format with one scale pair per kv head (KvF8) loads once per workgroup, folds into the score's
+// scalar and applies to the chunk's output.  The formats without such a pair leave it empty.
+struct NoHeadScale {
+    struct Head {};
+    template <typename S>
+    static __device__ __forceinline__ Head head(const S&, int) { return {}; }
+    static __device__ __forceinline__ float score_scale(const Head&, float scaling) { return scaling; }
+    static __device__ __forceinline__ void scale_out(const Head&, float&) {}
+};
 
 // ---- fp16 rows ----
 struct KvSrc {
@@ -136,7 +154,7 @@ __device__ __forceinline__ void consume_range(KvBlocks<U>& t, int blk0, int dblk
     }
 }
 
-struct KvF16 {
+struct KvF16 : NoHeadScale {
     using Elem = f16;
     struct Scales {};  // none
     template <bool PAD, bool WIN = false>
@@ -182,7 +200,7 @@ struct KvF16 {
     }
 
     template <int LPP>
-    static __device__ __forceinline__ void make_new(New& nw, const f16x8& knew, const f16x8& vnew)
+    static __device__ __forceinline__ void make_new(New& nw, const f16x8& knew, const f16x8& vnew, const Head&)
     {
         nw.k = knew;
         nw.v = vnew;
@@ -383,7 +401,7 @@ __device__ __forceinline__ void consume_range(KvBlocks8<U>& t, int blk0, int dbl
     }
 }
 
-struct KvI8 {
+struct KvI8 : NoHeadScale {
     using Elem = int8_t;
     struct Scales {
         f16*         p;  // [.., 2]: (k scale, v scale) of every row
@@ -438,7 +456,7 @@ struct KvI8 {
 
     // the row as the cache holds it: every position group of every workgroup has the whole row across its LPP lanes
     template <int LPP>
-    static __device__ __forceinline__ void make_new(New& nw, const f16x8& knew, const f16x8& vnew)
+    static __device__ __forceinline__ void make_new(New& nw, const f16x8& knew, const f16x8& vnew, const Head&)
     {
         const f16 ks = kv8_scale(group_max<LPP>(kv8_abs_max8(knew))), vs = kv8_scale(group_max<LPP>(kv8_abs_max8(vnew)));
         nw.k = kv8_quant8(knew, ks);
@@ -477,6 +495,179 @@ struct KvI8 {
         EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cos_sin) % 16 == 0,
                      "q, k, v and the cos|sin table must be 16-byte aligned");
         return check_cache(kc, vc, sc, S, st + 3);
+    }
+};
+
+// ---- fp8 e4m3 rows, one scale pair per kv head (kv_f8.hpp) ----
+struct KvSrcF8 {
+    __amdgpu_buffer_rsrc_t k, v, m;       // the valid rows of one (batch row, kv head); m: the mask row (MASK only)
+    unsigned               k_row, v_row;  // bytes between cache rows
+    unsigned               d0b;           // this lane's channel offset in bytes
+};
+template <int U>
+struct KvBlocksF8 {
+    u32x2          k[U], v[U];
+    unsigned short m[U];
+};
+// the new token's row as the cache will hold it: this lane's 8 bytes of each
+struct NewRowF8 {
+    u32x2 k, v;
+};
+
+template <int D, int U0, int UN, bool MASK, int U>
+__device__ __forceinline__ void load_range(KvBlocksF8<U>& t, const KvSrcF8& s, int blk0, int dblk, int rib)
+{
+    constexpr int BLK = AttnGeo<D>::BLK;
+    static_assert(U0 + UN <= U, "range");
+#pragma unroll
+    for (int u = U0; u < U0 + UN; ++u) {
+        const unsigned j = (unsigned)((blk0 + u * dblk) * BLK + rib);
+        t.k[u] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(s.k, (int)(j * s.k_row + s.d0b), 0, kNt));
+        t.v[u] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(s.v, (int)(j * s.v_row + s.d0b), 0, kNt));
+        if constexpr (MASK) t.m[u] = __builtin_amdgcn_raw_buffer_load_b16(s.m, (int)(j * 2u), 0, 0);
+    }
+}
+
+// consume_range on fp8 rows.  `scaling` arrives with the head's K scale folded in (KvF8::score_scale); the V scale is not seen
+// here at all (KvF8::scale_out, once per chunk): o accumulates p * v8 with v8 exact in fp32.
+template <int D, int U0, int UN, bool SUBST, bool MASK, int U>
+__device__ __forceinline__ void consume_range(KvBlocksF8<U>& t, int blk0, int dblk, int rib, int Sv, int slot, const NewRowF8& nw,
+                                              const f16x2 (&q2)[4], float scaling, float& m, float& l, float (&o)[8])
+{
+#pragma clang fp contract(off)
+    static_assert(U0 + UN <= U, "range");
+    constexpr int LPP = AttnGeo<D>::LPP, BLK = AttnGeo<D>::BLK;
+    if ((blk0 + U0 * dblk) * BLK >= Sv) return;  // workgroup-uniform
+    const int slot_blk = SUBST && slot >= 0 ? slot / BLK : -1;
+    float     sc[U];
+#pragma unroll
+    for (int u = U0; u < U0 + UN; ++u) {
+        const int blk = blk0 + u * dblk, j = blk * BLK + rib;
+        if (SUBST && blk == slot_blk) {  // workgroup-uniform
+            const bool mine = j == slot;
+            t.k[u] = mine ? nw.k : t.k[u];
+            t.v[u] = mine ? nw.v : t.v[u];
+        }
+        f16x2 kh[4];
+        kvf8_unpack8_f16(t.k[u], kh);
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a = __builtin_amdgcn_fdot2(kh[i], q2[i], a, false);
+        a = group_sum<LPP>(a) * scaling;
+        if constexpr (MASK) a += (float)__builtin_bit_cast(f16, t.m[u]);
+        sc[u] = j < Sv ? a : -INFINITY;
+    }
+    float mn = m;
+#pragma unroll
+    for (int u = U0; u < U0 + UN; ++u) mn = fmaxf(mn, sc[u]);
+    if (mn > -INFINITY) {  // group-uniform
+        const float keep = __expf(m - mn);
+        l *= keep;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] *= keep;
+#pragma unroll
+        for (int u = U0; u < U0 + UN; ++u) {
+            const float p = __expf(sc[u] - mn);
+            l += p;
+            float vf[8];
+            kvf8_unpack8_f32(t.v[u], vf);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o[i] = fmaf(p, vf[i], o[i]);
+        }
+        m = mn;
+    }
+}
+
+struct KvF8 {
+    using Elem = uint8_t;
+    struct Scales {
+        const float* p;  // [kv_heads][2]: (k scale, v scale) of every kv head
+    };
+    struct RopeArgsF8 : RopeAttnArgs {  // kc_* / vc_* strides in bytes
+        Scales sc;
+    };
+    template <bool PAD, bool WIN = false>
+    using RopeArgs = RopeArgsF8;  // (no per-row first key, no window and no ring on fp8 rows)
+    static __device__ __forceinline__ const Scales& scales(const RopeArgsF8& a) { return a.sc; }
+    // the scale pair of one kv head (every batch row shares it)
+    static __device__ __forceinline__ Scales rows(const Scales& sc, int, int hk) { return {sc.p + 2 * hk}; }
+    static constexpr bool kStamps = false;
+
+    // the head-scale hook: one scalar load of the pair per workgroup
+    struct Head {
+        float ks, vs;
+    };
+    static __device__ __forceinline__ Head head(const Scales& sc, int hk) { return {sc.p[2 * hk], sc.p[2 * hk + 1]}; }
+    static __device__ __forceinline__ float score_scale(const Head& hd, float scaling) { return hd.ks * scaling; }
+    static __device__ __forceinline__ void scale_out(const Head& hd, float& O) { O *= hd.vs; }
+
+    using Src = KvSrcF8;
+    template <int U>
+    using Blocks = KvBlocksF8<U>;
+    using New = NewRowF8;
+
+    // (one forwarding level, as in KvF16)
+    template <int D, int U0, int UN, bool MASK, int U>
+    static __device__ __forceinline__ void load(Blocks<U>& t, const Src& s, int blk0, int dblk, int rib)
+    {
+        load_range<D, U0, UN, MASK>(t, s, blk0, dblk, rib);
+    }
+    template <int D, int U0, int UN, bool SUBST, bool MASK, int U>
+    static __device__ __forceinline__ void consume(Blocks<U>& t, int blk0, int dblk, int rib, int Sv, int slot, const New& nw,
+                                                   const f16x2 (&q2)[4], float scaling, float& m, float& l, float (&o)[8])
+    {
+        consume_range<D, U0, UN, SUBST, MASK>(t, blk0, dblk, rib, Sv, slot, nw, q2, scaling, m, l, o);
+    }
+
+    // the buffer descriptors of one (batch row, kv head), ending at the valid length Sv; strides in bytes; no scale descriptor
+    template <int D, bool MASK>
+    static __device__ __forceinline__ Src make_src(const uint8_t* kbase, const uint8_t* vbase, const Scales&, long k_ss, long v_ss,
+                                                   int Sv, const f16* mrow)
+    {
+        Src s;
+        s.k_row = (unsigned)k_ss;
+        s.v_row = (unsigned)v_ss;
+        s.d0b   = (unsigned)(((threadIdx.x & 63) % AttnGeo<D>::LPP) * 8);
+        s.k = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(kbase), 0, (int)((unsigned)Sv * s.k_row), 0x00020000);
+        s.v = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vbase), 0, (int)((unsigned)Sv * s.v_row), 0x00020000);
+        s.m = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(MASK ? mrow : reinterpret_cast<const f16*>(kbase)), 0,
+                                                MASK ? Sv * 2 : 0, 0x00020000);
+        return s;
+    }
+
+    // the row as the cache holds it: every lane quantises its own 8 channels, nothing crosses lanes
+    template <int LPP>
+    static __device__ __forceinline__ void make_new(New& nw, const f16x8& knew, const f16x8& vnew, const Head& hd)
+    {
+        nw.k = kvf8_quant8(knew, hd.ks);
+        nw.v = kvf8_quant8(vnew, hd.vs);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    static __device__ __forceinline__ void store_new(const RopeArgsF8& a, uint8_t* kc, uint8_t* vc, int b, int hk, int slot,
+                                                     const New& nw, int d0)
+    {
+        *reinterpret_cast<u32x2*>(kc + b * a.kc_sb + hk * a.kc_sh + (long)slot * a.kc_ss + d0) = nw.k;
+        *reinterpret_cast<u32x2*>(vc + b * a.vc_sb + hk * a.vc_sh + (long)slot * a.vc_ss + d0) = nw.v;
+    }
+
+    // ---- host ----
+    static constexpr const char* kBadHeadDim   = "[eetq_amd] decode attention on an fp8 cache supports head_dim 64 and 128";
+    static constexpr const char* kTwoLaunch    = "attn_decode_f8 kernels launch";
+    static constexpr const char* kOneLaunch    = "rope_attn_decode_f8_kernel launch";
+    static constexpr bool        kSlotStride01 = true;
+    static int check_two_launch(const f16* q, const uint8_t* k, const uint8_t* v, const Scales& sc, int S, const long* st)
+    {
+        EETQ_REQUIRE(st[0] % 8 == 0 && st[1] % 8 == 0, "q strides must be multiples of 8 elements (16-byte loads)");
+        EETQ_REQUIRE((uintptr_t)q % 16 == 0, "q must be 16-byte aligned");
+        return check_f8_cache(k, v, sc.p, S, st + 2);
+    }
+    static int check_one_launch(const f16* q, const f16* k, const f16* v, const f16* cos_sin, const uint8_t* kc, const uint8_t* vc,
+                                const Scales& sc, int S, const long* st)
+    {
+        for (int i = 0; i < 3; ++i) EETQ_REQUIRE(st[i] % 8 == 0, "q / k / v strides must be multiples of 8 elements (16-byte accesses)");
+        EETQ_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cos_sin) % 16 == 0,
+                     "q, k, v and the cos|sin table must be 16-byte aligned");
+        return check_f8_cache(kc, vc, sc.p, S, st + 3);
     }
 };
 
@@ -580,6 +771,7 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
         Sv -= (int)s0;
     }
 
+    const typename Row::Head hd = Row::head(sc, hk);
     const f16x8 qv = *reinterpret_cast<const f16x8*>(q + b * q_sb + h * q_sh + d0);
     const typename Row::Src src = [&] {
         if constexpr (RING)
@@ -593,7 +785,9 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
     Row::template load<D, 0, kUA, MASK>(ta, src, split, splits, rib);
     float                    M, L, O;
     const typename Row::New none = {};
-    attn_chunk<Row, D, false, MASK, LONG>(qv, scaling, ta, tb, src, split, splits, Sv, -1, none, sm_m, sm_l, sm_o, M, L, O);
+    attn_chunk<Row, D, false, MASK, LONG>(qv, Row::score_scale(hd, scaling), ta, tb, src, split, splits, Sv, -1, none, sm_m, sm_l, sm_o,
+                                          M, L, O);
+    Row::scale_out(hd, O);
     if (tid < D) {
         float* out = ws + (((size_t)b * gridDim.x + split) * gridDim.y + h) * (D + kRecPad);  // [batch][split][head][record]
         out[kRecPad + tid] = O;
@@ -604,7 +798,7 @@ __device__ __forceinline__ void attn_partial(const f16* __restrict__ q, const ty
     }
 }
 
-// its two argument lists (the int8 one carries the scale tensor and its strides)
+// its three argument lists (the int8 one carries the scale tensor and its strides, the fp8 one the per-head scale pairs)
 template <int D, bool MASK, bool LONG, bool PAD = false, bool WIN = false, bool RING = false>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_kernel(
     const f16* __restrict__ q, const f16* __restrict__ kc, const f16* __restrict__ vc, const f16* __restrict__ mask,
@@ -625,6 +819,16 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_i8_kernel(
 {
     attn_partial<KvI8, D, MASK, LONG, false>(q, kc, vc, KvI8::Scales{const_cast<f16*>(scales), sst}, mask, ws, scaling, S, groups, q_sb,
                                              q_sh, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, m_sb, kv_len, kv_len_bias, NoKvStart{});
+}
+
+template <int D, bool MASK, bool LONG>
+__global__ __launch_bounds__(kAttnThreads) void attn_decode_partial_f8_kernel(
+    const f16* __restrict__ q, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc, const float* __restrict__ scales,
+    const f16* __restrict__ mask, float* __restrict__ ws, float scaling, int S, int groups, long q_sb, long q_sh, long k_sb,
+    long k_sh, long k_ss, long v_sb, long v_sh, long v_ss, long m_sb, const int64_t* __restrict__ kv_len, int kv_len_bias)
+{
+    attn_partial<KvF8, D, MASK, LONG, false>(q, kc, vc, KvF8::Scales{scales}, mask, ws, scaling, S, groups, q_sb, q_sh, k_sb, k_sh, k_ss,
+                                             v_sb, v_sh, v_ss, m_sb, kv_len, kv_len_bias, NoKvStart{});
 }
 
 #define ATTN_ROW_STAMP(i) \
@@ -690,6 +894,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
                      : "memory");
     }
     ATTN_ROW_STAMP(1);
+    const typename Row::Head hd = Row::head(Row::scales(a), hk);
     // a slot outside the cache is neither written nor attended, and (like the two-launch form) nothing is rotated then
     // (no upper bound on rpos here, unlike the two-launch form: launch_rope_attn's table_rows)
     const bool have_new = slot64 >= 0 && slot64 < (RING ? (int64_t)INT32_MAX : (int64_t)a.S) && rpos >= 0;
@@ -735,7 +940,7 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     }
     __builtin_amdgcn_sched_barrier(0);
     typename Row::New nw;
-    Row::template make_new<LPP>(nw, knew, vnew);
+    Row::template make_new<LPP>(nw, knew, vnew, hd);
     // the cache row of the new token: once per kv head, by one position group of the head's first workgroup
     int wslot = slot;  // RING: the physical row of the new token
     if constexpr (RING) {
@@ -745,7 +950,9 @@ __global__ __launch_bounds__(kAttnThreads) void rope_attn_decode_kernel(const in
     if (have_new && split == 0 && h == hk * a.groups && tid < LPP) Row::store_new(a, kc, vc, b, hk, wslot, nw, d0);
     ATTN_ROW_STAMP(2);
     float M, L, O;
-    attn_chunk<Row, D, true, MASK, LONG>(qv, a.scaling, ta, tb, src, split, splits, Sv, slot_c, nw, sm_m, sm_l, sm_o, M, L, O);
+    attn_chunk<Row, D, true, MASK, LONG>(qv, Row::score_scale(hd, a.scaling), ta, tb, src, split, splits, Sv, slot_c, nw, sm_m, sm_l, sm_o,
+                                         M, L, O);
+    Row::scale_out(hd, O);
 
     ATTN_ROW_STAMP(3);
     head_handoff<D>(a, split, splits, h, b, H, M, L, O, sm_o, &sm_ticket);
@@ -793,7 +1000,16 @@ void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const int8_t* k
                   scaling, S, groups, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], sc.st, kv_len, kv_len_bias);
 }
 
-// the two-launch form over either row format; strides: q_b, q_h, the cache's six, mask_b, out_b, out_h
+template <int D, bool MASK, bool LONG, bool PAD, bool WIN, bool RING>
+void launch_partial(dim3 grid, hipStream_t stream, const f16* q, const uint8_t* k, const uint8_t* v, const KvF8::Scales& sc,
+                    const f16* mask, float* ws, float scaling, int S, int groups, const long* st, const int64_t* kv_len,
+                    int kv_len_bias, NoKvStart)
+{
+    launch_kernel(attn_decode_partial_f8_kernel<D, MASK, LONG>, grid, dim3(kAttnThreads), 0, stream, q, k, v, sc.p, mask, ws, scaling, S,
+                  groups, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], kv_len, kv_len_bias);
+}
+
+// the two-launch form over any row format; strides: q_b, q_h, the cache's six, mask_b, out_b, out_h
 template <class Row, bool PAD, bool WIN = false, bool RING = false>
 int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::Elem* v, const typename Row::Scales& sc, const f16* mask,
                 f16* out, float* ws, int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* st,
@@ -820,7 +1036,7 @@ int launch_attn(const f16* q, const typename Row::Elem* k, const typename Row::E
 
 unsigned long long* g_attn_stamps = nullptr;  // process-wide diagnostic hook (not thread-safe by design)
 
-// the one-launch form over either row format; st: q_b, k_b, v_b, the cache's six, mask_b, out_b, out_h
+// the one-launch form over any row format; st: q_b, k_b, v_b, the cache's six, mask_b, out_b, out_h
 template <class Row, bool PAD, bool WIN = false, bool RING = false>
 int launch_rope_attn(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k, const f16* v,
                      const f16* cos_sin, typename Row::Elem* kc, typename Row::Elem* vc, const typename Row::Scales& sc,
@@ -971,7 +1187,29 @@ int launch_rope_attn_decode_i8(const int64_t* positions, const int64_t* slots, i
                                          S, D, splits, scaling, st, kv_len, kv_len_bias, nullptr, advance, table_rows, stream);
 }
 
-// the dropped-step count of both row formats since the last reset
+// the fp8 e4m3 cache (kv_f8.hpp): scales fp32 [kv_heads][2], cache strides in bytes
+int launch_attn_decode_f8(const f16* q, const uint8_t* k, const uint8_t* v, const float* scales, const f16* mask, f16* out, float* ws,
+                          int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                          int kv_len_bias, int64_t* advance, hipStream_t stream)
+{
+    EETQ_REQUIRE(scales, "null pointer");
+    return launch_attn<KvF8, false>(q, k, v, KvF8::Scales{scales}, mask, out, ws, B, H, Hkv, S, D, splits, scaling, strides, kv_len,
+                                    kv_len_bias, advance, stream, NoKvStart{});
+}
+
+int launch_rope_attn_decode_f8(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                               const f16* v, const f16* cos_sin, uint8_t* kc, uint8_t* vc, const float* scales, const f16* mask,
+                               f16* out, float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                               const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
+                               hipStream_t stream)
+{
+    EETQ_REQUIRE(scales, "null pointer");
+    return launch_rope_attn<KvF8, false>(positions, slots, slot_stride, q, k, v, cos_sin, kc, vc, KvF8::Scales{scales}, mask, out, ws,
+                                         tickets, B, H, Hkv, S, D, splits, scaling, st, kv_len, kv_len_bias, nullptr, advance,
+                                         table_rows, stream);
+}
+
+// the dropped-step count of every row format since the last reset
 int attn_dropped_steps(unsigned* count, bool reset)
 {
     EETQ_TRY_HIP(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_attn_dropped), sizeof(unsigned)));

@@ -426,6 +426,19 @@ int launch_rotary_kvcache_i8(const int64_t* pos, const int64_t* first_row_dev, f
                              int k_heads, int head_size, int rot_dim, const long* st, const long* sst, int max_pos, long table_rows,
                              hipStream_t stream);
 
+// the fp8 e4m3 KV cache (kv_f8.hpp): the int8 launchers' shapes with scales fp32 [kv_heads][2] and no scale strides
+int launch_attn_decode_f8(const f16* q, const uint8_t* k, const uint8_t* v, const float* scales, const f16* mask, f16* out, float* ws,
+                          int B, int H, int Hkv, int S, int D, int splits, float scaling, const long* strides, const int64_t* kv_len,
+                          int kv_len_bias, int64_t* advance, hipStream_t stream);
+int launch_rope_attn_decode_f8(const int64_t* positions, const int64_t* slots, int slot_stride, const f16* q, const f16* k,
+                               const f16* v, const f16* cos_sin, uint8_t* kc, uint8_t* vc, const float* scales, const f16* mask,
+                               f16* out, float* ws, unsigned* tickets, int B, int H, int Hkv, int S, int D, int splits, float scaling,
+                               const long* st, const int64_t* kv_len, int kv_len_bias, int64_t* advance, long table_rows,
+                               hipStream_t stream);
+int launch_rotary_kvcache_f8(const int64_t* pos, const int64_t* first_row_dev, f16* q, f16* k, const f16* v, const f16* cache,
+                             uint8_t* kcache, uint8_t* vcache, const float* scales, int batch, int tokens, int first_row, int q_heads,
+                             int k_heads, int head_size, int rot_dim, const long* st, int max_pos, long table_rows, hipStream_t stream);
+
 int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t stream, bool glu8 = false);
 
 // compute units of the current device (cached per device); 256 on MI355X

@@ -6,6 +6,7 @@
 //             pos_encoding_kernels.cu:12-53) for fp16: in-place NeoX rotation, fp16 arithmetic with a
 //             rounding after every multiply/add exactly like the half operators there.
 #include "common.hpp"
+#include "kv_f8.hpp"
 #include "kv_i8.hpp"
 
 namespace eetq {
@@ -324,6 +325,67 @@ __global__ __launch_bounds__(256) void rotary_neox_kvcache_i8_kernel(const int64
     }
 }
 
+// rotary_neox_kvcache_i8_kernel for an fp8 e4m3 cache (kv_f8.hpp): the same in-place rotation of q and k, the same rows and the
+// same drops.  The scale pair belongs to the kv head -- scales fp32 [k_heads][2], read, never written --, so a thread quantises
+// the 8 (K: 16) channels it holds with a divide, a clamp and a convert each: no reduction across the head's threads.
+template <int D>
+__global__ __launch_bounds__(256) void rotary_neox_kvcache_f8_kernel(const int64_t* __restrict__ positions, const int64_t* __restrict__ slots,
+                                                                     f16* __restrict__ query, f16* __restrict__ key,
+                                                                     const f16* __restrict__ value, const f16* __restrict__ cache,
+                                                                     uint8_t* __restrict__ kcache, uint8_t* __restrict__ vcache,
+                                                                     const float* __restrict__ scales, long q_stride, long k_stride,
+                                                                     long v_stride, long c_sb, long c_sh, long c_ss, int q_heads,
+                                                                     int k_heads, int max_pos, int tokens, int first_row,
+                                                                     int64_t table_rows)
+{
+#pragma clang fp contract(off)
+    constexpr int embed = D / 2, e8 = embed / 8, h8 = D / 8;
+    const int     b    = blockIdx.x;
+    const int     cb   = b / tokens;
+    const int64_t rpos = positions[b];
+    const int64_t pos  = (slots ? slots[0] : (int64_t)first_row) + (b - cb * tokens);
+    if (pos < 0 || pos >= max_pos || rpos < 0 || rpos >= table_rows) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&g_rope_dropped, 1u);
+        return;
+    }
+    const f16* cp = cache + rpos * D;
+    auto rot8 = [&](f16* p, int off, f16x8& lo, f16x8& hi) {
+        const f16x8 c = *reinterpret_cast<const f16x8*>(cp + off), sn = *reinterpret_cast<const f16x8*>(cp + embed + off);
+        const f16x8 vx = *reinterpret_cast<const f16x8*>(p + off), vy = *reinterpret_cast<const f16x8*>(p + embed + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f16 xc = vx[j] * c[j], ys = vy[j] * sn[j], yc = vy[j] * c[j], xs = vx[j] * sn[j];
+            lo[j] = xc - ys;
+            hi[j] = yc + xs;
+        }
+        *reinterpret_cast<f16x8*>(p + off)         = lo;
+        *reinterpret_cast<f16x8*>(p + embed + off) = hi;
+    };
+    if (blockIdx.y == 0) {
+        for (int i = threadIdx.x; i < q_heads * e8; i += blockDim.x) {
+            const int head = i / e8, off = (i - head * e8) * 8;
+            f16x8     lo, hi;
+            rot8(query + b * q_stride + (long)head * D, off, lo, hi);
+        }
+    } else if (blockIdx.y == 1) {
+        for (int i = threadIdx.x; i < k_heads * e8; i += blockDim.x) {
+            const int head = i / e8, off = (i - head * e8) * 8;
+            f16x8     lo, hi;
+            rot8(key + b * k_stride + (long)head * D, off, lo, hi);
+            const float s = scales[2 * head];
+            uint8_t*    d = kcache + cb * c_sb + head * c_sh + pos * c_ss;
+            *reinterpret_cast<u32x2*>(d + off)         = kvf8_quant8(lo, s);
+            *reinterpret_cast<u32x2*>(d + embed + off) = kvf8_quant8(hi, s);
+        }
+    } else {
+        for (int i = threadIdx.x; i < k_heads * h8; i += blockDim.x) {
+            const int   head = i / h8, off = (i - head * h8) * 8;
+            const f16x8 x = *reinterpret_cast<const f16x8*>(value + b * v_stride + (long)head * D + off);
+            *reinterpret_cast<u32x2*>(vcache + cb * c_sb + head * c_sh + pos * c_ss + off) = kvf8_quant8(x, scales[2 * head + 1]);
+        }
+    }
+}
+
 // Greedy decode hand-over (extension for the HIP-graph decoder, utils/graph_decoder.py): per batch row the index of the row's
 // maximum logit -- the FIRST one on ties, a NaN counts as the maximum, like torch.argmax -- written to out_buf[b][*s_idx] and to
 // s_tok[b]; then *s_pos += 1 and *s_idx += 1.  ONE workgroup walks the rows (batch is small), so the column is read before anyone
@@ -466,6 +528,35 @@ int launch_rotary_kvcache_i8(const int64_t* pos, const int64_t* first_row_dev, f
     else EETQ_ROPE8_GO(64);
 #undef EETQ_ROPE8_GO
     return check_hip(hipGetLastError(), "rotary_neox_kvcache_i8_kernel launch");
+}
+
+int launch_rotary_kvcache_f8(const int64_t* pos, const int64_t* first_row_dev, f16* q, f16* k, const f16* v, const f16* cache,
+                             uint8_t* kcache, uint8_t* vcache, const float* scales, int batch, int tokens, int first_row, int q_heads,
+                             int k_heads, int head_size, int rot_dim, const long* st, int max_pos, long table_rows, hipStream_t stream)
+{
+    EETQ_REQUIRE(pos && q && k && v && cache && kcache && vcache && scales && st, "null pointer");
+    EETQ_REQUIRE(batch >= 0 && tokens >= 0 && q_heads > 0 && k_heads > 0 && head_size > 0 && max_pos > 0, "invalid rotary shape");
+    EETQ_REQUIRE(first_row >= 0 && (first_row_dev || (long)first_row + tokens <= max_pos), "the prefill rows must lie inside the cache");
+    EETQ_REQUIRE(table_rows > 0, "the cos|sin table must have at least one row");
+    EETQ_REQUIRE((long)batch * tokens < (1L << 31), "too many tokens for one launch");
+    EETQ_REQUIRE(rot_dim == head_size, "the fp8 cache write needs the rotation to cover the whole head (rot_dim == head_size)");
+    if (head_size != 64 && head_size != 128)
+        return fail(EETQ_ERR_UNSUPPORTED, "[eetq_amd] the fp8 cache write supports head_size 64 and 128");
+    EETQ_REQUIRE(((st[0] | st[1] | st[2]) & 7) == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cache) & 15) == 0,
+                 "q / k / v token strides must be multiples of 8 elements and q, k, v, the cos|sin table 16-byte aligned");
+    const long cst[6] = {st[3], st[4], st[5], st[3], st[4], st[5]};
+    const int  rc     = check_f8_cache(kcache, vcache, scales, max_pos, cst);
+    if (rc != EETQ_OK) return rc;
+    if (batch == 0 || tokens == 0) return EETQ_OK;
+    const dim3 grid(batch * tokens, 3);
+#define EETQ_ROPE_F8_GO(D)                                                                                                          \
+    rotary_neox_kvcache_f8_kernel<D><<<grid, 256, 0, stream>>>(pos, first_row_dev, q, k, v, cache, kcache, vcache, scales, st[0], st[1], \
+                                                               st[2], st[3], st[4], st[5], q_heads, k_heads, max_pos, tokens, first_row, \
+                                                               (int64_t)table_rows)
+    if (head_size == 128) EETQ_ROPE_F8_GO(128);
+    else EETQ_ROPE_F8_GO(64);
+#undef EETQ_ROPE_F8_GO
+    return check_hip(hipGetLastError(), "rotary_neox_kvcache_f8_kernel launch");
 }
 
 int launch_silu_mul(const f16* gu, f16* out, int rows, int inter, hipStream_t stream, bool glu8)

@@ -1319,6 +1319,99 @@ void rotary_embedding_neox_kvcache_prefill_i8(const Tensor& positions, Tensor& q
         stream_of(query)));
 }
 
+// ---- the fp8 KV cache (include/eetq_amd.h "The fp8 KV cache"): caches float8_e4m3fn [B, Hkv, S, D], scales float32 [Hkv, 2] --------
+static void check_f8_cache(const char* name, const Tensor& query, const Tensor& key_cache, const Tensor& value_cache,
+                           const Tensor& scales, int64_t B, int64_t Hkv, int64_t D)
+{
+    TORCH_CHECK(key_cache.scalar_type() == at::kFloat8_e4m3fn && value_cache.scalar_type() == at::kFloat8_e4m3fn &&
+                    scales.scalar_type() == at::kFloat,
+                name, "the caches must be float8_e4m3fn and the scales float32");
+    TORCH_CHECK(key_cache.dim() == 4 && value_cache.sizes() == key_cache.sizes() && scales.dim() == 2, name,
+                "expected caches [B, Hkv, S, D] and scales [Hkv, 2]");
+    TORCH_CHECK(key_cache.size(0) == B && key_cache.size(1) == Hkv && key_cache.size(3) == D && scales.size(0) == Hkv &&
+                    scales.size(1) == 2,
+                name, "shape mismatch");
+    TORCH_CHECK(key_cache.stride(-1) == 1 && value_cache.stride(-1) == 1 && scales.is_contiguous(), name,
+                "cache rows must be dense and the scales contiguous");
+    TORCH_CHECK(key_cache.device() == query.device() && value_cache.device() == query.device() && scales.device() == query.device(),
+                name, "all tensors must be on one device");
+}
+
+Tensor decode_attention_f8kv(const Tensor& query, const Tensor& key_cache, const Tensor& value_cache, const Tensor& scales,
+                             const OptTensor& mask, std::optional<double> scaling, std::optional<int64_t> splits_in,
+                             const OptTensor& kv_len, int64_t kv_len_bias, const OptTensor& advance)
+{
+    const char* name = "decode_attention_f8kv: ";
+    TORCH_CHECK(query.scalar_type() == at::kHalf && query.dim() == 3 && query.stride(-1) == 1 && key_cache.dim() == 4, name,
+                "expected a float16 query [B, H, D] with dense D");
+    const int64_t B = query.size(0), H = query.size(1), D = query.size(2);
+    const int64_t Hkv = key_cache.size(1), S = key_cache.size(2);
+    check_f8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, name, "shape mismatch");
+    const DecodeAttnPrep p(name, query, S, nullptr, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), query.stride(1)}, key_cache, value_cache);
+    c10::DeviceGuard     guard(query.device());
+    check(eetq_decode_attention_f8kv_f16(query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), p.mask(),
+                                         p.out.data_ptr(), p.ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)S, (int)D, (int)p.splits,
+                                         p.sc, strides.data(), p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
+}
+
+Tensor rope_decode_attention_f8kv(const Tensor& positions, const Tensor& query, const Tensor& key, const Tensor& value,
+                                  const Tensor& cos_sin_cache, Tensor& key_cache, Tensor& value_cache, const Tensor& scales,
+                                  Tensor& tickets, const OptTensor& slots, const OptTensor& mask, std::optional<double> scaling,
+                                  std::optional<int64_t> splits_in, const OptTensor& kv_len, int64_t kv_len_bias,
+                                  const OptTensor& advance)
+{
+    const char* name = "rope_decode_attention_f8kv: ";
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value, &cos_sin_cache})
+        TORCH_CHECK(t->scalar_type() == at::kHalf, name, "float16 query, key, value and cos|sin table expected");
+    TORCH_CHECK(positions.scalar_type() == at::kLong && positions.is_contiguous(), name, "positions must be contiguous int64");
+    TORCH_CHECK(query.dim() == 3 && key.dim() == 3 && value.dim() == 3 && key_cache.dim() == 4, name,
+                "expected query [B, H, D], key / value [B, Hkv, D], caches [B, Hkv, S, D]");
+    const int64_t B = query.size(0), H = query.size(1), D = query.size(2), Hkv = key.size(1), S = key_cache.size(2);
+    check_f8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+    TORCH_CHECK(key.size(0) == B && key.size(2) == D && value.sizes() == key.sizes() && Hkv > 0 && H % Hkv == 0 &&
+                    positions.numel() == B,
+                name, "shape mismatch");
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&query, &key, &value})
+        TORCH_CHECK(t->stride(-1) == 1 && t->stride(-2) == D, name, "[heads, head_size] must be dense");
+    TORCH_CHECK(cos_sin_cache.is_contiguous() && cos_sin_cache.size(-1) == D, name,
+                "the rotation must cover the whole head (rot_dim == D)");
+    TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.is_contiguous() && tickets.numel() >= B * H + 1 &&
+                    tickets.device() == query.device(),
+                name, "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device");
+    const DecodeAttnPrep p(name, query, S, &slots, mask, scaling, splits_in, kv_len, advance);
+    const auto           strides = p.strides({query.stride(0), key.stride(0), value.stride(0)}, key_cache, value_cache);
+    c10::DeviceGuard     guard(query.device());
+    check(eetq_rope_decode_attention_f8kv_f16(
+        positions.data_ptr<int64_t>(), p.slots, p.slot_stride, query.data_ptr(), key.data_ptr(), value.data_ptr(),
+        cos_sin_cache.data_ptr(), (int)(cos_sin_cache.numel() / D), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(),
+        p.mask(), p.out.data_ptr(), p.ws.data_ptr<float>(), reinterpret_cast<unsigned*>(tickets.data_ptr<int32_t>()), (int)B, (int)H,
+        (int)Hkv, (int)S, (int)D, (int)p.splits, p.sc, strides.data(), p.kv_len, (int)kv_len_bias, p.advance, stream_of(query)));
+    return p.out;
+}
+
+// rotary_embedding_neox_kvcache_prefill writing an fp8 cache; key is rotated in place as well
+// (eetq_rotary_neox_kvcache_prefill_f8_f16)
+void rotary_embedding_neox_kvcache_prefill_f8(const Tensor& positions, Tensor& query, Tensor& key, const Tensor& value,
+                                              int64_t head_size, const Tensor& cos_sin_cache, Tensor& key_cache,
+                                              Tensor& value_cache, const Tensor& scales, int64_t first_row,
+                                              const OptTensor& first_row_dev)
+{
+    const char* name = "rotary_embedding_neox_kvcache_prefill_f8: ";
+    const auto  p    = rotary_prefill_prep(name, false, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row,
+                                           first_row_dev, [&](int64_t B, int64_t Hkv, int64_t D) {
+                                           check_f8_cache(name, query, key_cache, value_cache, scales, B, Hkv, D);
+                                       });
+    c10::DeviceGuard guard(query.device());
+    check(eetq_rotary_neox_kvcache_prefill_f8_f16(
+        positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), value.data_ptr(), cos_sin_cache.data_ptr(),
+        (int)cos_sin_cache.size(0), key_cache.data_ptr(), value_cache.data_ptr(), scales.data_ptr(), (int)p.B, (int)p.T, p.first_row_dev,
+        (int)first_row, (int)p.H, (int)p.Hkv, (int)head_size, (int)cos_sin_cache.size(1), p.strides, (int)key_cache.size(2),
+        stream_of(query)));
+}
+
 Tensor silu_mul(const Tensor& gate_up, bool glu8)
 {
     TORCH_CHECK(gate_up.scalar_type() == at::kHalf && gate_up.is_cuda() && gate_up.is_contiguous(),
@@ -2204,6 +2297,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("advance") = py::none());
     m.def("rotary_embedding_neox_kvcache_prefill_i8", &rotary_embedding_neox_kvcache_prefill_i8,
           "prompt rotary (query and key in place) + quantising int8 KV-cache write", py::arg("positions"), py::arg("query"),
+          py::arg("key"), py::arg("value"), py::arg("head_size"), py::arg("cos_sin_cache"), py::arg("key_cache"),
+          py::arg("value_cache"), py::arg("scales"), py::arg("first_row") = 0, py::arg("first_row_dev") = py::none());
+    m.def("decode_attention_f8kv", &decode_attention_f8kv, "single-query attention over an fp8 (e4m3) KV cache", py::arg("query"),
+          py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"), py::arg("mask") = py::none(),
+          py::arg("scaling") = py::none(), py::arg("splits") = py::none(), py::arg("kv_len") = py::none(),
+          py::arg("kv_len_bias") = 0, py::arg("advance") = py::none());
+    m.def("rope_decode_attention_f8kv", &rope_decode_attention_f8kv, py::arg("positions"), py::arg("query"), py::arg("key"),
+          py::arg("value"), py::arg("cos_sin_cache"), py::arg("key_cache"), py::arg("value_cache"), py::arg("scales"),
+          py::arg("tickets"), py::arg("slots") = py::none(), py::arg("mask") = py::none(), py::arg("scaling") = py::none(),
+          py::arg("splits") = py::none(), py::arg("kv_len") = py::none(), py::arg("kv_len_bias") = 0,
+          py::arg("advance") = py::none());
+    m.def("rotary_embedding_neox_kvcache_prefill_f8", &rotary_embedding_neox_kvcache_prefill_f8,
+          "prompt rotary (query and key in place) + quantising fp8 (e4m3) KV-cache write", py::arg("positions"), py::arg("query"),
           py::arg("key"), py::arg("value"), py::arg("head_size"), py::arg("cos_sin_cache"), py::arg("key_cache"),
           py::arg("value_cache"), py::arg("scales"), py::arg("first_row") = 0, py::arg("first_row_dev") = py::none());
     m.def("prefill_attention", &prefill_attention, py::arg("query"), py::arg("key"), py::arg("value"), py::arg("keys"),

@@ -288,6 +288,33 @@ def _route_int8(p, t_len, rows, supported, table_ok, prompt8_ok, rows8_ok, mfma_
     return "rows_i8"
 
 
+def _route_fp8(p, t_len, rows, supported, table_ok, mfma_ok):
+    """``_route_int8`` for an fp8 cache (``Fp8StaticLayer``), which is built for fresh whole prompts and single-token steps only:
+    "decode", or "prompt" / "sdpa" (the quantising write from row 0, then the fp16 prompt kernel / torch attention on the
+    unquantised rows).  Every other promise is refused.  Reads no tensor, calls no operator."""
+    for held, what in ((p.window is not None or p.ring, "sliding_window_static (the fp8 kernels have no sliding window and no ring)"),
+                       (p.starts is not None, "padded_static_batch (the fp8 kernels take no per-row first key)"),
+                       (p.few_rows or p.few_rows_int8, "appended_static_prefill(few_rows*=True) (the few-row kernel reads no fp8 rows)"),
+                       (p.appended, "appended_static_prefill (no prompt kernel reads fp8 rows: a prompt on an fp8 KV cache must "
+                                    "be promised fresh -- fresh_static_prefill: empty cache, unpadded prompt)")):
+        if held:
+            raise ValueError("EETLlamaAttention: an fp8 KV cache cannot be combined with " + what)
+    if not supported:
+        raise NotImplementedError("EETLlamaAttention: an fp8 KV cache needs float16 on the GPU, head size 64 or 128, the "
+                                  "library's decode attention (decode_math_attention=True), no attention weights, and "
+                                  "the batch the cache was allocated for")
+    if not table_ok:
+        raise NotImplementedError("EETLlamaAttention: an fp8 KV cache needs the rotation to cover the whole head")
+    if t_len == 1:
+        return "decode"
+    if not p.fresh:
+        raise NotImplementedError("EETLlamaAttention: a prompt on an fp8 KV cache must be promised fresh "
+                                  "(fresh_static_prefill: empty cache, unpadded prompt)")
+    if t_len > rows:
+        raise ValueError("EETLlamaAttention: the prompt is longer than the cache")
+    return "prompt" if mfma_ok else "sdpa"
+
+
 class EETRotaryEmbedding(nn.Module):
     """cos|sin cache [max_position, dim] in fp16 and the in-place NeoX rotation (reference :19-65)."""
 
@@ -384,6 +411,19 @@ class _EETAttentionBase(nn.Module):
             raise RuntimeError("EETLlamaAttention: the int8 cache layer is not allocated (Int8StaticLayer.allocate)")
         return layer
 
+    def _fp8_cache_layer(self, past_key_values):
+        """The ``Fp8StaticLayer`` (utils/kv_cache.py) of this block, or None when the cache is of another kind."""
+        layers = getattr(past_key_values, "layers", None)
+        if layers is None or self.layer_idx >= len(layers):
+            return None
+        layer = layers[self.layer_idx]
+        if type(layer).__name__ != "Fp8StaticLayer":
+            return None
+        if (not getattr(layer, "is_initialized", False) or layer.keys.dtype != torch.float8_e4m3fn or layer.keys.dim() != 4
+                or getattr(layer, "scales", None) is None):
+            raise RuntimeError("EETLlamaAttention: the fp8 cache layer is not allocated (Fp8StaticLayer.allocate)")
+        return layer
+
     def _mfma_prompt_ok(self, q, k, v):   # may this prompt go to the MFMA prompt kernel (ops.prefill_attention)?
         return (self.mfma_prefill and ops.prefill_attention is not None and q.is_cuda and q.dtype == torch.float16
                 and ops.prefill_attention_supported(self.head_dim) and k.stride(-1) == 1 and v.stride(-1) == 1)
@@ -441,6 +481,44 @@ class _EETAttentionBase(nn.Module):
         if route == "prompt":
             out = ops.prefill_attention(q, kt, vt, q_len, scaling=self.scaling)
             return out.reshape(bsz, q_len, -1)
+        out = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), kt, vt, is_causal=True, scale=self.scaling,
+                                                               enable_gqa=self.num_key_value_groups > 1).transpose(1, 2)
+        return out.reshape(bsz, q_len, -1).contiguous()
+
+    def _fp8_cache_forward(self, layer, q, k, v, positions, attention_mask, kwargs):
+        """``_int8_cache_forward`` on an fp8 static cache, for what is built there: a single token is one launch (rotation,
+        quantising cache write, attention over the e4m3 rows; two launches when ``fused_decode_step`` is off); a promised-fresh
+        prompt is the quantising write from row 0 followed by the prompt kernel on the UNQUANTISED rotated K and the V -- the
+        prompt's output is the fp16-cache path's bit for bit, only the cache is quantised."""
+        bsz, q_len, d = q.shape[0], q.shape[1], self.head_dim
+        rows = layer.keys.shape[2]
+        self._grow_table(rows)
+        table = self.rotary_emb.cos_sin_cache
+        supported = (d in (64, 128) and q.is_cuda and q.dtype == torch.float16 and self.decode_math_attention is True
+                     and not kwargs.get("output_attentions", False) and layer.keys.shape[0] == bsz
+                     and layer.keys.shape[1] == self.num_key_value_heads)
+        route = _route_fp8(_prefill_promise, q_len, rows, supported, table.shape[-1] == d,
+                           q_len > 1 and self._mfma_prompt_ok(q, k, v))
+        counter = layer.cumulative_length
+        if route == "decode":
+            add = self._decode_mask_rows(attention_mask, bsz, rows, q.dtype, q.device)
+            if add is False:
+                raise NotImplementedError("EETLlamaAttention: this attention mask has no form the fp8 decode step understands")
+            if self.fused_decode_step:
+                out = ops.rope_decode_attention_f8kv(positions[:, 0].contiguous(), q[:, 0], k[:, 0], v[:, 0], table, layer.keys,
+                                                     layer.values, layer.scales, self._step_tickets(bsz, q.device), slots=counter,
+                                                     mask=add, scaling=self.scaling, kv_len=counter, kv_len_bias=1, advance=counter)
+            else:
+                ops.rotary_embedding_neox_kvcache_prefill_f8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales,
+                                                             first_row_dev=counter)
+                out = ops.decode_attention_f8kv(q[:, 0], layer.keys, layer.values, layer.scales, mask=add, scaling=self.scaling,
+                                                kv_len=counter, kv_len_bias=1, advance=counter)
+            return out.reshape(bsz, q_len, -1)
+        ops.rotary_embedding_neox_kvcache_prefill_f8(positions, q, k, v, d, table, layer.keys, layer.values, layer.scales)
+        counter.fill_(q_len)
+        kt, vt = k.transpose(1, 2), v.transpose(1, 2)     # [B, Hkv, T, D]: the rotated fp16 K, the V
+        if route == "prompt":
+            return ops.prefill_attention(q, kt, vt, q_len, scaling=self.scaling).reshape(bsz, q_len, -1)
         out = torch.nn.functional.scaled_dot_product_attention(q.transpose(1, 2), kt, vt, is_causal=True, scale=self.scaling,
                                                                enable_gqa=self.num_key_value_groups > 1).transpose(1, 2)
         return out.reshape(bsz, q_len, -1).contiguous()
@@ -664,9 +742,12 @@ class EETLlamaAttention(_EETAttentionBase):
         v = qkv[..., (h + hkv) * d:].unflatten(-1, (hkv, d))
         positions = self._positions(position_ids, past_key_values, bsz, q_len, hidden_states.device)
         kwargs.pop("use_cache", None)
-        i8 = self._int8_cache_layer(past_key_values)
-        if i8 is not None:   # int8 rows: the library's int8 kernels or an error, never a stock path
-            out = self._int8_cache_forward(i8, q, k, v, positions, attention_mask, kwargs)
+        i8, f8 = self._int8_cache_layer(past_key_values), self._fp8_cache_layer(past_key_values)
+        if i8 is not None or f8 is not None:   # quantised rows: the library's own kernels or an error, never a stock path
+            if i8 is not None:
+                out = self._int8_cache_forward(i8, q, k, v, positions, attention_mask, kwargs)
+            else:
+                out = self._fp8_cache_forward(f8, q, k, v, positions, attention_mask, kwargs)
             if residual is None:
                 return self.o_proj(out), None
             if hasattr(self.o_proj, "qweight"):

@@ -26,7 +26,8 @@ from ._lib import (ACT_GELU, ACT_IDENTITY, ACT_RELU, ACT_SILU, DTYPE_F16, DTYPE_
 
 __all__ = ["quant_weights", "preprocess_weights", "unprocess_weights", "w8_a16_gemm", "w8_a16_gemm_", "w8_a16_gemm_t", "w4_a16_gemm_t",
            "w4_a16_gemm_tiled", "w4_a16_gemm_tiled_supported",
-           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "spec_sample_accept", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
+           "layernorm_forward", "rotary_embedding_neox", "rotary_embedding_neox_strided", "rotary_embedding_neox_kvcache", "rotary_embedding_neox_kvcache_prefill", "greedy_handover", "sample_handover", "ngram_draft", "spec_accept", "spec_sample_accept", "decode_attention", "rope_decode_attention", "decode_attention_i8kv", "rope_decode_attention_i8kv", "rotary_embedding_neox_kvcache_prefill_i8", "decode_attention_f8kv", "rope_decode_attention_f8kv",
+           "rotary_embedding_neox_kvcache_prefill_f8", "silu_mul", "convert_layout", "w8_a16_gemv_grouped", "w8_a16_moe",
            "w8_a16_moe_train", "w8_a16_moe_backward", "w4_a16_moe", "w4_a16_moe_train", "w4_a16_moe_backward", "w4_a16_moe_path", "w4_a16_moe_direct_supported", "moe_router", "w8_a16_moe_block",
            "w4_a16_moe_block", "moe_router_sigmoid", "w8_a16_moe_block_sigmoid", "w4_a16_moe_block_sigmoid"]
 
@@ -1120,6 +1121,104 @@ def rotary_embedding_neox_kvcache_prefill_i8(positions, query, key, value, head_
             _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
             _ptr(value_cache), _ptr(scales), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size),
             cos_sin_cache.shape[1], strides, sst, key_cache.shape[2], _stream_ptr()))
+    return None
+
+
+def _f8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D):
+    if (key_cache.dtype != torch.float8_e4m3fn or value_cache.dtype != torch.float8_e4m3fn
+            or scales.dtype != torch.float32):
+        raise RuntimeError(name + "the caches must be float8_e4m3fn and the scales float32")
+    if key_cache.dim() != 4 or value_cache.shape != key_cache.shape or scales.dim() != 2:
+        raise RuntimeError(name + "expected caches [B, Hkv, S, D] and scales [Hkv, 2]")
+    if (key_cache.shape[0] != B or key_cache.shape[1] != Hkv or key_cache.shape[3] != D
+            or tuple(scales.shape) != (Hkv, 2)):
+        raise RuntimeError(name + "shape mismatch")
+    if key_cache.stride(-1) != 1 or value_cache.stride(-1) != 1 or not scales.is_contiguous():
+        raise RuntimeError(name + "cache rows must be dense and the scales contiguous")
+    for t in (key_cache, value_cache, scales):
+        if t.device != query.device:
+            raise RuntimeError(name + "all tensors must be on one device")
+
+
+@_eager_only
+def decode_attention_f8kv(query, key_cache, value_cache, scales, mask=None, scaling=None, splits=None, kv_len=None,
+                          kv_len_bias=0, advance=None):
+    """``decode_attention`` over an fp8 KV cache (extension): key_cache / value_cache float8_e4m3fn [B, Hkv, S, D], ``scales``
+    float32 [Hkv, 2] = (k scale, v scale) of each kv head; attention over ``ks * k8`` and ``vs * v8``, fp32 softmax and
+    accumulation (eetq_decode_attention_f8kv_f16).  Everything else as ``decode_attention``."""
+    name = "decode_attention_f8kv: "
+    if query.dtype != torch.float16 or query.dim() != 3 or query.stride(-1) != 1 or key_cache.dim() != 4:
+        raise RuntimeError(name + "expected a float16 query [B, H, D] with dense D")
+    B, H, D = query.shape
+    Hkv, S = key_cache.shape[1], key_cache.shape[2]
+    _f8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
+    if Hkv <= 0 or H % Hkv:
+        raise RuntimeError(name + "shape mismatch")
+    p = _DecodeAttnPrep(name, query, S, None, mask, scaling, splits, kv_len, advance, (query.stride(0), query.stride(1)),
+                        key_cache, value_cache)
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_decode_attention_f8kv_f16(
+            _ptr(query), _ptr(key_cache), _ptr(value_cache), _ptr(scales), _optr(p.mrow), _ptr(p.out), _ptr(p.ws), B, H, Hkv, S, D,
+            p.splits, p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(advance), _stream_ptr()))
+    return p.out
+
+
+@_eager_only
+def rope_decode_attention_f8kv(positions, query, key, value, cos_sin_cache, key_cache, value_cache, scales, tickets,
+                               slots=None, mask=None, scaling=None, splits=None, kv_len=None, kv_len_bias=0, advance=None):
+    """``rope_decode_attention`` on an fp8 KV cache (extension), ONE launch: the rotated key and the value of the new token are
+    quantised in registers, written as bytes to their cache row, and attended as their quantised selves.  Bit-identical to
+    ``rotary_embedding_neox_kvcache_prefill_f8`` with one token followed by ``decode_attention_f8kv``
+    (eetq_rope_decode_attention_f8kv_f16)."""
+    name = "rope_decode_attention_f8kv: "
+    for t in (query, key, value, cos_sin_cache):
+        if t.dtype != torch.float16:
+            raise RuntimeError(name + "float16 query, key, value and cos|sin table expected")
+    if positions.dtype != torch.int64 or not positions.is_contiguous():
+        raise RuntimeError(name + "positions must be contiguous int64")
+    if query.dim() != 3 or key.dim() != 3 or value.dim() != 3 or key_cache.dim() != 4:
+        raise RuntimeError(name + "expected query [B, H, D], key / value [B, Hkv, D], caches [B, Hkv, S, D]")
+    B, H, D = query.shape
+    Hkv, S = key.shape[1], key_cache.shape[2]
+    _f8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D)
+    if key.shape[0] != B or key.shape[2] != D or value.shape != key.shape or Hkv <= 0 or H % Hkv or positions.numel() != B:
+        raise RuntimeError(name + "shape mismatch")
+    for t in (query, key, value):
+        if t.stride(-1) != 1 or t.stride(-2) != D:
+            raise RuntimeError(name + "[heads, head_size] must be dense")
+    if not cos_sin_cache.is_contiguous() or cos_sin_cache.shape[-1] != D:
+        raise RuntimeError(name + "the rotation must cover the whole head (rot_dim == D)")
+    if (tickets.dtype != torch.int32 or not tickets.is_contiguous() or tickets.numel() < B * H + 1
+            or tickets.device != query.device):
+        raise RuntimeError(name + "tickets must be a zeroed int32 tensor of at least B * H + 1 elements on the device")
+    p = _DecodeAttnPrep(name, query, S, slots, mask, scaling, splits, kv_len, advance,
+                        (query.stride(0), key.stride(0), value.stride(0)), key_cache, value_cache)
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_rope_decode_attention_f8kv_f16(
+            _ptr(positions), _optr(slots), p.slot_stride, _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache),
+            cos_sin_cache.numel() // D, _ptr(key_cache), _ptr(value_cache), _ptr(scales), _optr(p.mrow), _ptr(p.out), _ptr(p.ws),
+            _ptr(tickets), B, H, Hkv, S, D, p.splits, p.scaling, p.strides, _optr(kv_len), int(kv_len_bias), _optr(advance),
+            _stream_ptr()))
+    return p.out
+
+
+@_eager_only
+def rotary_embedding_neox_kvcache_prefill_f8(positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache,
+                                             scales, first_row=0, first_row_dev=None):
+    """``rotary_embedding_neox_kvcache_prefill`` writing an fp8 KV cache: ``query`` [B, T, H, D] AND ``key`` [B, T, Hkv, D] are
+    rotated in place; the rotated key and ``value`` are written as e4m3 bytes, ``e4m3_rne(clamp(x / s, -448, 448))`` with the kv
+    head's scale from ``scales`` (float32 [Hkv, 2]), to rows ``base + t`` of the caches [B, Hkv, S, D].  With T = 1 and
+    ``first_row_dev`` = the cache's counter it is the cache write of an unfused decode step
+    (eetq_rotary_neox_kvcache_prefill_f8_f16)."""
+    name = "rotary_embedding_neox_kvcache_prefill_f8: "
+    B, T, H, Hkv, strides = _rotary_prefill_prep(
+        name, False, positions, query, key, value, head_size, cos_sin_cache, key_cache, value_cache, first_row, first_row_dev,
+        lambda B, Hkv, D: _f8_cache_check(name, query, key_cache, value_cache, scales, B, Hkv, D))
+    with torch.cuda.device(query.device):
+        check(_lib.lib().eetq_rotary_neox_kvcache_prefill_f8_f16(
+            _ptr(positions), _ptr(query), _ptr(key), _ptr(value), _ptr(cos_sin_cache), cos_sin_cache.shape[0], _ptr(key_cache),
+            _ptr(value_cache), _ptr(scales), B, T, _optr(first_row_dev), int(first_row), H, Hkv, int(head_size),
+            cos_sin_cache.shape[1], strides, key_cache.shape[2], _stream_ptr()))
     return None
 
 

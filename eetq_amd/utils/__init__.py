@@ -10,8 +10,8 @@ from ..checkpoint import (checkpoint_layout, convert_checkpoint, convert_model_l
 from .hf import use_with_transformers  # noqa: F401,E402
 
 
-def __getattr__(name):   # the int8 cache classes subclass transformers' static cache: imported on first use, not with the package
-    if name in ("Int8StaticCache", "Int8StaticLayer"):
+def __getattr__(name):   # the quantised cache classes subclass transformers' static cache: imported on first use, not with the package
+    if name in ("Int8StaticCache", "Int8StaticLayer", "Fp8StaticCache", "Fp8StaticLayer"):
         from . import kv_cache
         return getattr(kv_cache, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

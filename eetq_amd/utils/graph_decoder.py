@@ -68,7 +68,7 @@ def _require_accelerated(setting, model, lean, prompt_kernel):
 class GraphDecoder:
     def __init__(self, model, batch, max_len, capture=True, lean=True, steps_per_graph=7, sampling=False, kv_bits=16, kv8_append=False,
                  ragged=False, speculative=0, ngram=3, draft=None, spec_sampling=False, spec_attention="prompt", window=None,
-                 rolling=False, rolling_chunk=512):
+                 rolling=False, rolling_chunk=512, kv_dtype=None, kv_scales=None):
         """``max_len``: cache rows (prompt + new tokens).  ``capture=False`` keeps the same static-cache stepping but runs
         every step eagerly (used to check the graph against the launches it was captured from).  ``lean``: step fully
         accelerated models layer by layer instead of through the stock model forward (see ``_lean``).
@@ -151,7 +151,14 @@ class GraphDecoder:
         cover it, the cache does not.  ``generate`` / ``prefill`` cut any prompt into pieces of at most ``rolling_chunk`` tokens (a
         smaller ``prefill_chunk`` / ``chunk`` is kept), the first fresh, the later ones appended; ``append=True``, sampling, captured and
         eager stepping work as without it, and one captured graph serves every length: wrapping is kernel arithmetic on the device
-        counter.  ``rolling=True`` without ``window``, or with ``ragged``, ``kv_bits=8`` or ``speculative``, raises ``ValueError``."""
+        counter.  ``rolling=True`` without ``window``, or with ``ragged``, ``kv_bits=8`` or ``speculative``, raises ``ValueError``.
+        ``kv_dtype`` (default ``None``: nothing changes) = ``"fp8_e4m3"``: an ``Fp8StaticCache`` (``utils/kv_cache.py``: one e4m3
+        byte per element, ``2 D`` bytes per row, one (k scale, v scale) pair per kv head), written and read by the
+        attention blocks' fp8 kernels.  ``kv_scales`` = ``(k_scale, v_scale)``, each a number or one value per kv head (default 1.0),
+        goes to ``Fp8StaticCache.set_scales``.  It needs the lean layer-by-layer model with head size 64 or 128 and runs fresh whole
+        prompts only: together with ``kv_bits=8``, ``ragged``, ``window``, ``rolling``, ``speculative``, ``append=`` or
+        ``prefill_chunk=`` / ``chunk=`` it raises ``ValueError``."""
+        self.kv_dtype = self._check_kv_dtype(kv_dtype, kv_scales, kv_bits, ragged, window, rolling, speculative)
         self.window = self._check_window(window, model, lean, ragged, kv_bits, speculative)
         self.rolling, self.rolling_chunk = self._check_rolling(rolling, rolling_chunk, window, ragged, kv_bits, speculative)
         if spec_attention not in ("prompt", "rows"):
@@ -194,6 +201,8 @@ class GraphDecoder:
             _require_accelerated("ragged=True", model, lean, prompt_kernel=False)
         if self.kv_bits == 8:
             _require_accelerated("kv_bits=8", model, lean, prompt_kernel=False)
+        if self.kv_dtype:
+            _require_accelerated("kv_dtype=%r" % self.kv_dtype, model, lean, prompt_kernel=False)
         from transformers import StaticCache
         self.batch = int(batch)
         self.max_len = int(max_len)
@@ -202,6 +211,11 @@ class GraphDecoder:
         if self.kv_bits == 8:
             from .kv_cache import Int8StaticCache
             self.cache = Int8StaticCache(config=model.config, max_cache_len=self.max_len).allocate(self.batch, dev)
+        elif self.kv_dtype:
+            from .kv_cache import Fp8StaticCache
+            self.cache = Fp8StaticCache(config=model.config, max_cache_len=self.max_len).allocate(self.batch, dev)
+            if kv_scales is not None:
+                self.cache.set_scales(*kv_scales)
         elif self.rolling:
             from .kv_cache import RollingStaticCache
             self.cache = RollingStaticCache(config=model.config, window=self.window, chunk=self.rolling_chunk)
@@ -277,6 +291,31 @@ class GraphDecoder:
             with torch.cuda.graph(self.graph_n):
                 for _ in range(self.steps_per_graph):
                     self._advance()
+
+    @staticmethod
+    def _check_kv_dtype(kv_dtype, kv_scales, kv_bits, ragged, window, rolling, speculative):
+        """``kv_dtype`` as given, or the refusal of what an fp8 cache is not built for."""
+        if kv_dtype is None:
+            if kv_scales is not None:
+                raise ValueError("GraphDecoder: kv_scales are the scales of an fp8 cache and need kv_dtype='fp8_e4m3'")
+            return None
+        if kv_dtype != "fp8_e4m3":
+            raise ValueError("GraphDecoder: kv_dtype must be None or 'fp8_e4m3', got %r" % (kv_dtype,))
+        for held, other in ((kv_bits == 8, "kv_bits=8"), (ragged, "ragged=True"), (window is not None, "window=%r" % (window,)),
+                            (rolling, "rolling=True"), (speculative, "speculative=%r" % (speculative,))):
+            if held:
+                raise ValueError("GraphDecoder: kv_dtype='fp8_e4m3' cannot be combined with %s: the fp8 cache serves fresh whole "
+                                 "prompts and single-token decode steps only" % other)
+        if kv_scales is not None and (not isinstance(kv_scales, (tuple, list)) or len(kv_scales) != 2):
+            raise ValueError("GraphDecoder: kv_scales must be a pair (k_scale, v_scale), got %r" % (kv_scales,))
+        return kv_dtype
+
+    def _refuse_fp8_pieces(self, append, chunk, chunk_name):
+        """An fp8 cache takes fresh whole prompts only."""
+        if self.kv_dtype and (append or chunk is not None):
+            raise ValueError("GraphDecoder: kv_dtype='fp8_e4m3' cannot be combined with %s: no prompt kernel reads fp8 rows, so a "
+                             "prompt behind cached rows has nothing to attend them with"
+                             % ("append=True" if append else "%s=%r" % (chunk_name, chunk)))
 
     @staticmethod
     def _check_window(window, model, lean, ragged, kv_bits, speculative):
@@ -386,8 +425,9 @@ class GraphDecoder:
             attn = getattr(layer, "self_attn", None)
             if attn is None or not getattr(attn, "static_prefill", False) or not hasattr(attn, "_static_cache_layer"):
                 return False
-            if attn._static_cache_layer(self.cache) is None and (not hasattr(attn, "_int8_cache_layer")
-                                                                 or attn._int8_cache_layer(self.cache) is None):
+            if attn._static_cache_layer(self.cache) is None and not any(
+                    hasattr(attn, look) and getattr(attn, look)(self.cache) is not None
+                    for look in ("_int8_cache_layer", "_fp8_cache_layer")):
                 return False
         return True
 
@@ -520,6 +560,7 @@ class GraphDecoder:
         if self.kv_bits == 8 and not self.kv8_append and (append or prefill_chunk is not None):
             raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
                              "built with kv8_append=True: append=True and prefill_chunk then attend quantised rows")
+        self._refuse_fp8_pieces(append, prefill_chunk, "prefill_chunk")
         append = bool(append) and (self.rows > 0 or self._pending)
         feed = torch.cat([self.s_tok, prompt], dim=1) if append and self._pending else prompt
         start = self.rows if append else 0
@@ -612,6 +653,7 @@ class GraphDecoder:
         if self.kv_bits == 8 and not self.kv8_append and (append or chunk is not None):
             raise ValueError("GraphDecoder: an int8 cache (kv_bits=8) takes fresh whole prompts only unless the decoder was "
                              "built with kv8_append=True: append=True and chunk= then attend quantised rows")
+        self._refuse_fp8_pieces(append, chunk, "chunk")
         start = self.rows if append else 0
         if start + P > self.max_len:
             raise ValueError("GraphDecoder: built for batch %d and %d cache rows" % (self.batch, self.max_len))

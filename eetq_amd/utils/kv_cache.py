@@ -1,10 +1,16 @@
-"""The library's own static KV caches for the accelerated Llama blocks (extension): int8 rows, and a ring.
+"""The library's own static KV caches for the accelerated Llama blocks (extension): int8 rows, fp8
+rows, and a ring.
 
 ``Int8StaticCache`` is a transformers ``StaticCache`` whose layers hold ``keys`` / ``values`` as int8 [B, Hkv, S, D] and one
 ``scales`` tensor, float16 [B, Hkv, S, 2] = (k scale, v scale) of each row: ``2 D + 4`` bytes per row against ``4 D``.  Rows are
 written and read by the library's own kernels only (``ops.rotary_embedding_neox_kvcache_prefill_i8``,
 ``ops.rope_decode_attention_i8kv``, ``ops.decode_attention_i8kv``), which the ``eet_accelerator`` attention blocks call when they
 meet such a layer; the stock ``update()`` path refuses it.  ``GraphDecoder(..., kv_bits=8)`` builds one.
+
+``Fp8StaticCache`` holds ``keys`` / ``values`` as ``torch.float8_e4m3fn`` [B, Hkv, S, D] and one ``scales`` tensor per layer,
+float32 [Hkv, 2] = (k scale, v scale) of each kv head, 1.0 unless ``set_scales`` says otherwise: ``2 D`` bytes per row.  Written
+and read by ``ops.rotary_embedding_neox_kvcache_prefill_f8``, ``ops.rope_decode_attention_f8kv`` and
+``ops.decode_attention_f8kv`` only.  ``GraphDecoder(..., kv_dtype="fp8_e4m3")`` builds one.
 
 ``RollingStaticCache`` is a ``StaticCache`` of fp16 rows whose layers hold ``ring_rows(window, chunk)`` rows instead of the
 sequence's length: under ``llama_modules.sliding_window_static(window, ring=True)`` the attention blocks write logical row r at
@@ -14,7 +20,7 @@ of any length.  ``GraphDecoder(..., window=W, rolling=True)`` builds one.
 import torch
 from transformers.cache_utils import Cache, StaticCache, StaticLayer
 
-__all__ = ["Int8StaticLayer", "Int8StaticCache", "RollingStaticCache", "ring_rows"]
+__all__ = ["Int8StaticLayer", "Int8StaticCache", "Fp8StaticLayer", "Fp8StaticCache", "RollingStaticCache", "ring_rows"]
 
 
 def ring_rows(window, chunk):
@@ -81,6 +87,71 @@ class Int8StaticCache(StaticCache):
         head_dim = getattr(text, "head_dim", None) or text.hidden_size // text.num_attention_heads
         for layer in self.layers:
             layer.allocate(batch, heads, head_dim, device)
+        return self
+
+
+class Fp8StaticLayer(StaticLayer):
+    """One layer of an ``Fp8StaticCache``: e4m3 rows and one (k scale, v scale) pair per kv head.  Allocated eagerly, like the
+    int8 layer.  ``reset`` is the static layer's: the scales belong to the model, not to the sequence, and stay."""
+
+    supports_early_init = False
+
+    def __init__(self, max_cache_len, **kwargs):
+        super().__init__(max_cache_len=max_cache_len)
+        self.scales = None
+
+    def allocate(self, batch, heads, head_dim, device):
+        self.dtype, self.device = torch.float8_e4m3fn, torch.device(device)
+        self.batch_size, self.num_heads = int(batch), int(heads)
+        self.k_head_dim = self.v_head_dim = int(head_dim)
+        shape = (self.batch_size, self.num_heads, self.max_cache_len, self.k_head_dim)
+        self.keys = torch.zeros(shape, dtype=torch.uint8, device=self.device).view(torch.float8_e4m3fn)
+        self.values = torch.zeros(shape, dtype=torch.uint8, device=self.device).view(torch.float8_e4m3fn)
+        self.scales = torch.ones((self.num_heads, 2), dtype=torch.float32, device=self.device)
+        self.cumulative_length = self.cumulative_length.to(self.device)
+        self.is_initialized = True
+        return self
+
+    def set_scales(self, k_scale, v_scale):
+        """(k scale, v scale): each a number or a tensor of one value per kv head; positive and finite.  Rows already written keep
+        the bytes of the scales they were written with."""
+        if self.scales is None:
+            raise RuntimeError("Fp8StaticLayer.set_scales: allocate the layer first")
+        for col, (name, v) in enumerate((("k_scale", k_scale), ("v_scale", v_scale))):
+            t = torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1)
+            if t.numel() not in (1, self.num_heads):
+                raise ValueError("Fp8StaticLayer.set_scales: %s must be a scalar or one value per kv head (%d), got %d values"
+                                 % (name, self.num_heads, t.numel()))
+            if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+                raise ValueError("Fp8StaticLayer.set_scales: %s must be positive and finite" % name)
+            self.scales[:, col] = t.to(self.device).expand(self.num_heads)
+        return self
+
+    def lazy_initialization(self, key_states, value_states):
+        raise RuntimeError("Fp8StaticLayer is allocated eagerly: call allocate(batch, heads, head_dim, device)")
+
+    def update(self, key_states, value_states, *args, **kwargs):
+        raise RuntimeError("Fp8StaticLayer.update: only eet_accelerator attention blocks write an fp8 KV cache (its rows are "
+                           "quantised by the library's kernels); this attention block called the stock cache update")
+
+
+class Fp8StaticCache(StaticCache):
+    """``StaticCache`` with e4m3 rows and per-head scales: one ``Fp8StaticLayer`` per decoder layer (full attention only)."""
+
+    def __init__(self, config, max_cache_len, **kwargs):
+        text = config.get_text_config(decoder=True) if hasattr(config, "get_text_config") else config
+        kinds = getattr(text, "layer_types", None)
+        if kinds is not None and any(k != "full_attention" for k in kinds):
+            raise ValueError("Fp8StaticCache: full-attention layers only (got layer_types=%r)" % (kinds,))
+        self._text_config = text
+        Cache.__init__(self, layers=[Fp8StaticLayer(max_cache_len) for _ in range(text.num_hidden_layers)])
+
+    allocate = Int8StaticCache.allocate
+
+    def set_scales(self, k_scale, v_scale):
+        """``Fp8StaticLayer.set_scales`` on every layer."""
+        for layer in self.layers:
+            layer.set_scales(k_scale, v_scale)
         return self
 
 

@@ -4,7 +4,8 @@ Prints microseconds per layer-step for the one-launch form (eetq_rope_decode_att
 and for the two-launch pair.  usage: python tools/attn_bench.py [--filled 1024] [--rows 1082] [--batch 1]
 --kv-bits 8: the same sweep over an int8 KV cache (eetq_rope_decode_attention_i8kv_f16).  --compare-lib PATH: one process alternates
 the fp16 one-launch form of the library at PATH (e.g. the parent commit's build), this tree's fp16 form and its int8 form, --rounds
-times each, at the default chunk count.  --write T: the prompt's cache write at T tokens, fp16 against the quantising int8 write."""
+times each, at the default chunk count, and its fp8 form (eetq_rope_decode_attention_f8kv_f16: e4m3 rows, one scale pair per kv head).
+--kv-dtype fp8_e4m3: the chunk sweep over an fp8 KV cache.  --write T: the prompt's cache write at T tokens, fp16 against the quantising int8 write."""
 import argparse
 import json
 import os
@@ -28,6 +29,7 @@ ap.add_argument("--stamps-fused", action="store_true", help="device-clock decomp
 ap.add_argument("--pair", action="store_true", help="attention + the o projection behind it (H*D x H*D int8), with and without "
                                                     "the L2 prefetch of the projection's weight inside the attention launch")
 ap.add_argument("--kv-bits", type=int, default=16, choices=(16, 8), help="8: an int8 KV cache with a scale pair per row")
+ap.add_argument("--kv-dtype", default=None, choices=("fp8_e4m3",), help="an fp8 KV cache with a scale pair per kv head")
 ap.add_argument("--compare-lib", default=None, help="another build of libeetq_amd.so to alternate with (its fp16 one-launch form)")
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--write", type=int, default=0, help="time the prompt cache write at this many tokens instead (fp16 and int8)")
@@ -40,7 +42,8 @@ torch.manual_seed(0)
 inv = 1.0 / (10000 ** (torch.arange(0, D, 2).float() / D))
 fr = torch.einsum("i,j->ij", torch.arange(S + 64).float(), inv)
 table = torch.cat([fr.cos(), fr.sin()], -1).half().to(dev)
-want16 = args.kv_bits == 16 or args.compare_lib is not None or args.write > 0
+wantf8 = args.kv_dtype is not None or args.compare_lib is not None
+want16 = (args.kv_bits == 16 and args.kv_dtype is None) or args.compare_lib is not None or args.write > 0
 want8 = args.kv_bits == 8 or args.compare_lib is not None or args.write > 0
 kc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L if want16 else 0)]
 vc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(L if want16 else 0)]
@@ -48,6 +51,10 @@ vc = [torch.randn(B, Hkv, S, D, dtype=torch.float16, device=dev) for _ in range(
 kc8 = [torch.randint(-127, 128, (B, Hkv, S, D), dtype=torch.int8, device=dev) for _ in range(L if want8 else 0)]
 vc8 = [torch.randint(-127, 128, (B, Hkv, S, D), dtype=torch.int8, device=dev) for _ in range(L if want8 else 0)]
 sc8 = [(torch.rand(B, Hkv, S, 2, device=dev) * 0.01 + 0.02).half() for _ in range(L if want8 else 0)]
+# fp8 rows: the e4m3 bytes of N(0, 1) values, scales 1
+kcf8 = [torch.randn(B, Hkv, S, D, device=dev).to(torch.float8_e4m3fn) for _ in range(L if wantf8 else 0)]
+vcf8 = [torch.randn(B, Hkv, S, D, device=dev).to(torch.float8_e4m3fn) for _ in range(L if wantf8 else 0)]
+scf8 = torch.ones(Hkv, 2, dtype=torch.float32, device=dev)
 qkv = torch.randn(B, 1, (H + 2 * Hkv) * D, dtype=torch.float16, device=dev)
 q = qkv[..., : H * D].unflatten(-1, (H, D))[:, 0]
 k = qkv[..., H * D: (H + Hkv) * D].unflatten(-1, (Hkv, D))[:, 0]
@@ -57,6 +64,7 @@ tickets = [torch.zeros(B * H + 1, dtype=torch.int32, device=dev) for _ in range(
 counters = [torch.tensor(args.filled, dtype=torch.int64, device=dev) for _ in range(L)]
 kv_mb = 2 * B * Hkv * (args.filled + 1) * D * 2 / 1e6            # fp16: 4 D bytes per row (K and V)
 kv8_mb = B * Hkv * (args.filled + 1) * (2 * D + 4) / 1e6         # int8: 2 D + 4
+kvf8_mb = B * Hkv * (args.filled + 1) * 2 * D / 1e6              # fp8: 2 D
 
 
 def one_launch(i, splits):
@@ -78,6 +86,17 @@ def two_launch_i8(i, splits):
     ops.rotary_embedding_neox_kvcache_prefill_i8(pos[:, None], q[:, None], k[:, None], v[:, None], D, table, kc8[i], vc8[i], sc8[i],
                                                  first_row_dev=counters[i])
     return ops.decode_attention_i8kv(q, kc8[i], vc8[i], sc8[i], splits=splits, kv_len=counters[i], kv_len_bias=1)
+
+
+def one_launch_f8(i, splits):
+    return ops.rope_decode_attention_f8kv(pos, q, k, v, table, kcf8[i], vcf8[i], scf8, tickets[i], slots=counters[i], splits=splits,
+                                          kv_len=counters[i], kv_len_bias=1)
+
+
+def two_launch_f8(i, splits):
+    ops.rotary_embedding_neox_kvcache_prefill_f8(pos[:, None], q[:, None], k[:, None], v[:, None], D, table, kcf8[i], vcf8[i], scf8,
+                                                 first_row_dev=counters[i])
+    return ops.decode_attention_f8kv(q, kcf8[i], vcf8[i], scf8, splits=splits, kv_len=counters[i], kv_len_bias=1)
 
 
 def timed(fn, splits, reps=30):
@@ -104,7 +123,7 @@ def timed(fn, splits, reps=30):
 
 
 def record(form, lib, bits, s, us):
-    mb = kv_mb if bits == 16 else kv8_mb
+    mb = kv_mb if bits == 16 else kv8_mb if bits == 8 else kvf8_mb
     print(json.dumps({"form": form, "lib": lib, "kv_bits": bits, "splits": s, "batch": B, "heads": H, "kv_heads": Hkv,
                       "filled": args.filled, "rows": S, "us_per_layer_step": round(us, 2), "kv_MB": round(mb, 1),
                       "kv_GBps": round(mb / us * 1e3, 0)}), flush=True)
@@ -160,6 +179,7 @@ if args.compare_lib:
         record("one_launch", "compare", 16, "default", timed(other_one_launch, None))
         record("one_launch", "tree", 16, "default", timed(one_launch, None))
         record("one_launch", "tree", 8, "default", timed(one_launch_i8, None))
+        record("one_launch", "tree", "fp8_e4m3", "default", timed(one_launch_f8, None))
     sys.exit(0)
 
 if args.pair:
@@ -334,8 +354,8 @@ if args.stamps:
     print("kernel span (first entry -> last output stored), mean over launches: %.2f us" % torch.nan_to_num(last, nan=0.0).amax(1).mean())
     sys.exit(0)
 
-forms = (("one_launch", one_launch), ("two_launch", two_launch)) if args.kv_bits == 16 else (
-    ("one_launch", one_launch_i8), ("two_launch", two_launch_i8))
+forms = (("one_launch", one_launch_f8), ("two_launch", two_launch_f8)) if args.kv_dtype else (
+    ("one_launch", one_launch), ("two_launch", two_launch)) if args.kv_bits == 16 else (("one_launch", one_launch_i8), ("two_launch", two_launch_i8))
 for name, fn in forms:
     for s in args.splits.split(","):
-        record(name, "tree", args.kv_bits, s, timed(fn, None if s == "default" else int(s)))
+        record(name, "tree", args.kv_dtype or args.kv_bits, s, timed(fn, None if s == "default" else int(s)))
